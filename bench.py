@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — IQL gradient-steps/sec at batch=256 on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch: draw 256 row indices
@@ -22,9 +22,11 @@ The timed region never contains a graph capture or instantiation for ANY --steps
 run from its first 2 or 4 steps launched directly plus replays of fixed chunk graphs (64 / 16 / 4 / 2 / 1 steps; captured,
 instantiated and rehearsed by prepare_train_steps before the warm-up).
 
-Prints ONE JSON line on rank 0 (contract in the round prompt) with `roofline` (the backward kernel, the step's
-dominant launch, against the fp32-MFMA peak) and, at N = 1, `cpu_baseline` (oracle/iql_torch_port.py — a PyTorch-CPU
-port of the reference step — timed on the host cores for a bounded sample).
+A plain run sets up, warms up, times EXACTLY --steps steps once, writes the parameters the timed steps left
+(--dump-outputs) and prints ONE JSON line on rank 0.  --full adds what the headline does not need: the median of
+several timed regions (--repeats), a trained-and-finite sanity step (and the replica check at N > 1), `roofline`
+(the backward kernel, the step's dominant launch, against the fp32-MFMA peak) and, at N = 1, `cpu_baseline`
+(oracle/iql_torch_port.py — a PyTorch-CPU port of the reference step — timed on the host cores for a bounded sample).
 """
 from __future__ import annotations
 
@@ -77,7 +79,11 @@ def parse_args(argv=None):
     ap.add_argument("--exchange", choices=("auto", "rccl", "p2p"), default="auto",
                     help="N > 1: gradient exchange (auto = time both in the warm-up, keep the faster valid one)")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed repeats of --steps, the MEDIAN is reported (default: 5 when --steps >= 1000, else 1)")
+                    help="timed repeats of --steps, the MEDIAN is reported (default: 1; with --full 5 when --steps >= 1000)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sanity step, roofline, kernel times and (N = 1) the CPU baseline; off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the parameters left by the last timed step as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=14.0,
                     help="budget per thread setting of the cpu_baseline leg (after 200 warm-up steps; it stops at 2 000 steps)")
@@ -164,6 +170,18 @@ def main(argv=None):
                          f"(python bench.py --gpus N starts them itself)\n")
         return 2
     return run_rank(args, world)
+
+
+def dump_outputs(tr, out_dir: str) -> None:
+    """What a caller of the timed path holds after its last step: the trained networks' parameters and the Polyak
+    target, one float32 array per tensor (DIR/<net>.<parameter>.npy, about 1.7 MB at the default dims)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for net in ("qf", "vf", "actor", "q_target"):
+        for name, t in getattr(tr, net).state_dict().items():
+            np.save(os.path.join(out_dir, f"{net}.{name}.npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def run_rank(args, world: int) -> int:
@@ -332,15 +350,19 @@ def run_rank(args, world: int) -> int:
 
     if warm > 0:
         run(warm)
-    repeats = args.repeats if args.repeats > 0 else (5 if args.steps >= 1000 else 1)
+    repeats = args.repeats if args.repeats > 0 else (5 if args.full and args.steps >= 1000 else 1)
     dts = [timed(args.steps) for _ in range(repeats)]      # EXACTLY --steps per timed region; the median region is reported
     dt = sorted(dts)[len(dts) // 2]
 
-    # sanity: the run trained (losses finite), replicas still identical
-    log = tr.train(buf.sample(B)) if world == 1 else tr.train_on_buffer(buf, B, seed=1, sync=True)
-    assert all(np.isfinite(v) for v in log.values()), log
-    if world > 1:
-        assert replicas_equal(), "replicas diverged or a peer wait timed out"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
+
+    if args.full:
+        # sanity: the run trained (losses finite), replicas still identical
+        log = tr.train(buf.sample(B)) if world == 1 else tr.train_on_buffer(buf, B, seed=1, sync=True)
+        assert all(np.isfinite(v) for v in log.values()), log
+        if world > 1:
+            assert replicas_equal(), "replicas diverged or a peer wait timed out"
 
     # ---- roofline of the dominant kernel (backward): its average launch duration is measured live with
     # HIP events on the launch stream around back-to-back launches of that kernel on the bench batch
@@ -348,7 +370,7 @@ def run_rank(args, world: int) -> int:
     f_fwd, f_bwd = flops(S, A, B)
     roof = None
     lb = args.precision == "bf16" and B > LB_MIN_ROWS and S + A + 1 <= 80 and os.environ.get("IQLHIP_LB", "1") != "0"
-    if rank == 0:
+    if rank == 0 and args.full:
         batch = buf.sample(B)
         t_fwd = tr.time_kernel(batch, 0, 500)
         t_bwd = tr.time_kernel(batch, 1, 500)
@@ -462,7 +484,7 @@ def run_rank(args, world: int) -> int:
     }
     if roof:
         out["roofline"] = roof
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import iql_torch_port as port
         try:
             ncpu = len(os.sched_getaffinity(0))

@@ -1,182 +1,136 @@
-"""Drop-in check: the reference's OWN jsrl_utils.py, imported unmodified from
-/root/reference, runs against this repo's `iql` module (sys.path order decides which `iql` the flat
-sibling import `from iql import ...` resolves to).  Host-only third-party modules that are not
-installed are stubbed exactly as tools/make_goldens.py does.  Skipped where the reference is absent
-(the GPU box): nothing of the reference travels."""
+"""Drop-in check: what the reference's OWN jsrl_utils.py does with the `iql` module runs against
+this repo's `iql`.  The reference's calls are recorded as data in fixture g16 (tools/make_goldens.py ran jsrl_utils.py
+against this repo's classes and logged, from its side of the boundary, the names it imports from `iql`, every
+constructor call with its arguments, every method call and attribute write make_actor / get_learning_agent make, and
+the layout of the reference's own checkpoint after one training step).  The tests replay those calls; nothing of the
+reference is needed at test time."""
+import json
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference/algorithms/finetune"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "g16_dropin_surface.npz")
 
 
 @pytest.fixture(scope="module")
-def ref_jsrl():
+def surface():
     import iql as ours  # this repo's drop-in (conftest put jsrl-corl_amd first on sys.path)
-
-    def stub(name, **attrs):
-        if name in sys.modules:
-            return sys.modules[name]
-        m = types.ModuleType(name)
-        for k, v in attrs.items():
-            setattr(m, k, v)
-        sys.modules[name] = m
-        return m
-
-    class _Any:
-        def __init__(self, *a, **k):
-            pass
-
-    for pkg in ("gym", "gymnasium"):
-        wr = stub(pkg + ".wrappers")
-        sp = stub(pkg + ".spaces", Discrete=_Any)
-        stub(pkg, Env=_Any, wrappers=wr, spaces=sp, register_envs=lambda *a, **k: None)
-    pol = stub("stable_baselines3.sac.policies", Actor=_Any)
-    sac = stub("stable_baselines3.sac", policies=pol)
-    stub("stable_baselines3", SAC=_Any, sac=sac)
-    sys.path.append(REF)          # AFTER ours: `iql` stays ours, the sibling modules come from the reference
-    import jsrl_utils
-    assert jsrl_utils.ImplicitQLearning is ours.ImplicitQLearning
-    yield jsrl_utils, ours
-    sys.path.remove(REF)
+    return json.loads(str(np.load(GOLDEN, allow_pickle=False)["meta"])), ours
 
 
-class Cfg:
-    device = "cpu"
-    actor_dropout = 0.0
-    iql_deterministic = False
-    vf_lr = qf_lr = actor_lr = 3e-4
-    discount, tau, beta, iql_tau = 0.99, 0.005, 3.0, 0.7
-    n_curriculum_stages, horizon_fn, no_agent_types, rolling_mean_n, tolerance = 5, "time_step", True, 5, 0.05
-    guide_heuristic_fn = None
-    offline_iterations = 123
+def _replay(ours, events, objs):
+    """Make the recorded calls on this repo's classes; objs maps the recording's object ids to the live objects."""
+    def dec(v):
+        if isinstance(v, dict) and "obj" in v:
+            return objs[v["obj"]]
+        if isinstance(v, dict) and "optimizer" in v:
+            return getattr(torch.optim, v["optimizer"])(objs[v["params_of"]].parameters(), lr=v["lr"])
+        if isinstance(v, dict) and "state_dict_of" in v:
+            return objs[v["state_dict_of"]].state_dict()
+        return v
+
+    for ev in events:
+        if "new" in ev:
+            objs[ev["id"]] = getattr(ours, ev["new"])(*[dec(a) for a in ev["args"]],
+                                                      **{k: dec(a) for k, a in ev["kwargs"].items()})
+        elif "setattr" in ev:
+            setattr(objs[ev["on"]], ev["setattr"], ev["value"])
+        else:
+            out = getattr(objs[ev["on"]], ev["call"])(*[dec(a) for a in ev.get("args", [])])
+            if ev["call"] == "to":
+                objs[ev["on"]] = out
+    return objs
 
 
-def test_reference_make_actor_builds_our_trainer(ref_jsrl):
-    jsrl, ours = ref_jsrl
-    tr = jsrl.make_actor(Cfg(), 17, 6, 1.0, max_steps=1000)
+def test_reference_make_actor_builds_our_trainer(surface):
+    rec, ours = surface
+    for name in rec["imported_from_iql"]:             # jsrl_utils.py: from iql import (...)
+        assert isinstance(getattr(ours, name), type), name
+    sc = rec["scenarios"]["make_actor_max_steps"]
+    tr = _replay(ours, sc["events"], {})[sc["returns"]]
     assert isinstance(tr, ours.ImplicitQLearning) and isinstance(tr.actor, ours.GaussianPolicy)
     assert tr.actor_lr_schedule is not None and tr.total_it == 0
-    tr2 = jsrl.make_actor(Cfg(), 17, 6, 1.0)           # online learner: no LR schedule (jsrl_utils.py:351)
+    sc = rec["scenarios"]["make_actor_online"]        # online learner: no LR schedule (jsrl_utils.py:351)
+    tr2 = _replay(ours, sc["events"], {})[sc["returns"]]
     assert tr2.actor_lr_schedule is None
     a = tr.actor.act(np.zeros(17, dtype=np.float32), "cpu")
     assert a.shape == (6,) and np.all(np.abs(a) <= 1.0)
 
 
-def test_reference_learning_agent_handoff(ref_jsrl):
-    jsrl, ours = ref_jsrl
-    cfg = Cfg()
-    cfg.n_curriculum_stages = 1
-    guide = jsrl.make_actor(cfg, 17, 6, 1.0, max_steps=1000)
-    trainer, cfg2 = jsrl.get_learning_agent(cfg, guide, 300, 17, 6, 1.0)
-    assert trainer.total_it == cfg.offline_iterations                     # jsrl_utils.py:355
+def test_reference_learning_agent_handoff(surface):
+    rec, ours = surface
+    objs = _replay(ours, rec["scenarios"]["guide"]["events"], {})
+    sc = rec["scenarios"]["get_learning_agent"]
+    guide = objs[sc["guide"]]
+    trainer = _replay(ours, sc["events"], objs)[sc["returns"]]
+    assert trainer.total_it == 123                                         # jsrl_utils.py:355 (offline_iterations)
     assert all(torch.equal(a, b) for a, b in zip(trainer.actor.parameters(), guide.actor.parameters()))
     assert all(torch.equal(a, b) for a, b in zip(trainer.q_target.parameters(), guide.qf.parameters()))
-    assert cfg2.curriculum_stage_idx == 0 and cfg2.best_eval_score == -np.inf
 
 
-def test_reference_curriculum_logic_runs(ref_jsrl):
-    jsrl, _ = ref_jsrl
-    cfg = jsrl.prepare_finetuning(300, Cfg())
-    assert list(cfg.all_curriculum_stages) == [300, 225, 150, 75, 0]
+def _describe(x):
+    """Layout of a (nested) state_dict as tools/make_goldens.py records it."""
+    if isinstance(x, torch.Tensor):
+        return {"tensor": list(x.shape), "dtype": str(x.dtype).replace("torch.", "")}
+    if isinstance(x, dict):
+        return {"dict": [[k, _describe(v)] for k, v in x.items()]}
+    if isinstance(x, (list, tuple)):
+        return {"list": [_describe(v) for v in x]}
+    return {"value": x}
 
 
-def test_checkpoints_are_interchangeable_with_the_reference(ref_jsrl, tmp_path):
+def _fill(desc, gen):
+    """A checkpoint of the recorded layout: seeded values in every tensor, the recorded values everywhere else."""
+    if "tensor" in desc:
+        return torch.randn(desc["tensor"], generator=gen).to(getattr(torch, desc["dtype"]))
+    if "dict" in desc:
+        return {k: _fill(v, gen) for k, v in desc["dict"]}
+    if "list" in desc:
+        return [_fill(v, gen) for v in desc["list"]]
+    return desc["value"]
+
+
+def _tensors(x, path=""):
+    if isinstance(x, torch.Tensor):
+        yield path, x
+    elif isinstance(x, dict):
+        for k, v in x.items():
+            yield from _tensors(v, f"{path}/{k}")
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            yield from _tensors(v, f"{path}/{i}")
+
+
+def test_checkpoints_are_interchangeable_with_the_reference(surface, tmp_path):
     """a state_dict saved by either implementation loads into the other (same keys, shapes,
-    optimizer-state layout), via torch.save / torch.load(weights_only=True)."""
-    import importlib.util
-    jsrl, ours = ref_jsrl
-    # the reference's own iql.py under another module name (ours owns the name `iql`)
-    for name in ("d4rl", "wandb", "pyrallis"):
-        if name not in sys.modules:
-            m = types.ModuleType(name)
-            if name == "pyrallis":
-                m.wrap = lambda *a, **k: (lambda fn: fn)
-            sys.modules[name] = m
-    spec = importlib.util.spec_from_file_location("ref_iql_module", os.path.join(REF, "iql.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-
-    def make(mod):
-        torch.manual_seed(3)
-        q, v, a = mod.TwinQ(17, 6), mod.ValueFunction(17), mod.GaussianPolicy(17, 6, 1.0)
-        return mod.ImplicitQLearning(1.0, a, torch.optim.Adam(a.parameters(), lr=3e-4), q,
-                                     torch.optim.Adam(q.parameters(), lr=3e-4), v,
-                                     torch.optim.Adam(v.parameters(), lr=3e-4), max_steps=1000, device="cpu")
-
-    r = make(ref)
-    batch = [torch.randn(64, 17), torch.rand(64, 6) * 2 - 1, torch.randn(64, 1), torch.randn(64, 17), torch.zeros(64, 1)]
-    r.train(batch)                                     # reference takes a real step: optimizer state exists
+    optimizer-state layout), via torch.save / torch.load(weights_only=True).  Reference -> ours: a checkpoint of the
+    reference's recorded layout loads and lands value for value.  Ours -> reference: what ours saves has exactly the
+    reference's layout (so the reference's load_state_dict accepts it) and carries the loaded values back bit for bit
+    (so the reference restarted from ours continues exactly as from its own checkpoint)."""
+    rec, ours = surface
+    ref_sd = _fill(rec["checkpoint"], torch.Generator().manual_seed(5))
     f1 = tmp_path / "ref.pt"
-    torch.save(r.state_dict(), f1)
-    o = make(ours)
+    torch.save(ref_sd, f1)
+    torch.manual_seed(3)
+    q, v, a = ours.TwinQ(17, 6), ours.ValueFunction(17), ours.GaussianPolicy(17, 6, 1.0)
+    o = ours.ImplicitQLearning(1.0, a, torch.optim.Adam(a.parameters(), lr=3e-4), q, torch.optim.Adam(q.parameters(), lr=3e-4),
+                               v, torch.optim.Adam(v.parameters(), lr=3e-4), max_steps=1000, device="cpu")
     o.load_state_dict(torch.load(f1, weights_only=True))
-    assert o.total_it == 1 and o._adam_t == {"v": 0, "q": 0, "pi": 0}   # (arenas attach on a GPU device only)
-    for a, b in zip(o.qf.parameters(), r.qf.parameters()):
-        assert torch.equal(a, b)
-    st_o, st_r = o.q_optimizer.state_dict(), r.q_optimizer.state_dict()
-    assert st_o["state"].keys() == st_r["state"].keys()
-    assert torch.equal(st_o["state"][0]["exp_avg"], st_r["state"][0]["exp_avg"])
-    assert o.actor_lr_schedule.state_dict() == r.actor_lr_schedule.state_dict()
+    assert o.total_it == ref_sd["total_it"] == 1 and o._adam_t == {"v": 0, "q": 0, "pi": 0}   # (arenas attach on a GPU device only)
+    for (_, x), y in zip(o.qf.named_parameters(), ref_sd["qf"].values()):
+        assert torch.equal(x, y)
+    st_o = o.q_optimizer.state_dict()
+    assert st_o["state"].keys() == ref_sd["q_optimizer"]["state"].keys()
+    assert torch.equal(st_o["state"][0]["exp_avg"], ref_sd["q_optimizer"]["state"][0]["exp_avg"])
+    assert o.actor_lr_schedule.state_dict() == ref_sd["actor_lr_schedule"]
     # and back: ours -> reference
     f2 = tmp_path / "ours.pt"
     torch.save(o.state_dict(), f2)
-    r2 = make(ref)
-    r2.load_state_dict(torch.load(f2, weights_only=True))
-    for a, b in zip(r2.actor.parameters(), r.actor.parameters()):
-        assert torch.equal(a, b)
-    # identical continuation: the reference restarted from ITS checkpoint vs from OURS (after a load the target
-    # net is a copy of qf in both — the reference's quirk)
-    r3 = make(ref)
-    r3.load_state_dict(torch.load(f1, weights_only=True))
-    log_a, log_b = r3.train(batch), r2.train(batch)
-    assert log_a == log_b
-
-
-def test_jsrl_host_logic_is_unchanged_by_the_drop_in(ref_jsrl):
-    """SURVEY §8c "G9 JSRL host logic" (fixture g13, generated with the reference's OWN iql): prepare_finetuning's
-    curricula, the horizon_update_callback trace over a fixed evaluation sequence and timestep_horizon's truth table
-    come out the same when jsrl_utils.py runs against this repo's `iql`."""
-    import contextlib
-    import io
-    import json
-    jsrl, _ = ref_jsrl
-    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "g13_jsrl_hostlogic.npz"), allow_pickle=False)
-    meta = json.loads(str(z["meta"]))
-
-    class C(Cfg):
-        n_curriculum_stages = meta["n_curriculum_stages"]
-        rolling_mean_n, tolerance = meta["rolling_mean_n"], meta["tolerance"]
-        batch_size = 256
-
-    cfg = jsrl.prepare_finetuning(meta["init_horizon"], C())
-    assert np.array_equal(np.asarray(cfg.all_curriculum_stages, dtype=np.float64), z["stages_time_step"])
-    assert np.array_equal(np.asarray(cfg.all_agent_types, dtype=np.float64), z["agent_types_disabled"])
-    c2 = C()
-    c2.no_agent_types, c2.horizon_fn = False, "goal_dist"
-    c2 = jsrl.prepare_finetuning(12.5, c2)
-    assert np.array_equal(np.asarray(c2.all_curriculum_stages, dtype=np.float64), z["stages_goal_dist"])
-    assert np.array_equal(np.asarray(c2.all_agent_types, dtype=np.float64), z["agent_types_enabled"])
-    trace = []
-    with contextlib.redirect_stdout(io.StringIO()):
-        for r in z["evals"]:
-            cfg = jsrl.horizon_update_callback(cfg, float(r))
-            trace.append([cfg.curriculum_stage_idx, cfg.curriculum_stage, cfg.agent_type_stage, cfg.best_eval_score,
-                          float(np.mean(cfg.rolling_mean_rews))])
-    assert np.array_equal(np.asarray(trace, dtype=np.float64), z["callback_trace"])
-    t = jsrl.prepare_finetuning(meta["init_horizon"], C())
-    for row in z["timestep_horizon_table"]:
-        stage_idx, ep_type, step, use, val = row
-        if stage_idx < 0:
-            t.curriculum_stage = np.nan
-        else:
-            t.curriculum_stage_idx = int(stage_idx)
-            t.curriculum_stage = t.all_curriculum_stages[int(stage_idx)]
-        t.ep_agent_type = ep_type
-        got_use, got_val = jsrl.timestep_horizon(int(step), None, None, t)
-        assert (float(got_use), float(got_val)) == (use, val), row
+    back = torch.load(f2, weights_only=True)
+    assert json.loads(json.dumps(_describe(back))) == rec["checkpoint"]
+    got, want = dict(_tensors(back)), dict(_tensors(ref_sd))
+    assert got.keys() == want.keys()
+    for k in want:
+        assert torch.equal(got[k], want[k]), k

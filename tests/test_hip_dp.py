@@ -172,7 +172,7 @@ def _bench_two_ranks_one_gpu(extra_env, args=("--rows", "200000", "--steps", "40
     env.update({"HSA_ENABLE_IPC_MODE_LEGACY": "0", "IQLHIP_DIST_BACKEND": "gloo", "IQLHIP_PREPARE_WARM_CHUNKS": "0"})
     env.update(extra_env)
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--no-cpu-baseline",
            "--master-port", str(29300 + os.getpid() % 500)] + list(args)
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert out.returncode == 0, out.stderr.decode("utf-8", "replace")[-3000:]

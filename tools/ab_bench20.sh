@@ -7,7 +7,7 @@ mkdir -p "$(dirname "$out")"; : > "$out"
 for i in $(seq 1 "$n"); do
   for tag in A B; do
     if [ $tag = A ]; then e=$a; else e=$b; fi
-    v=$(env $e python bench.py --gpus 1 $args --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'], d['ms_per_step'], d['roofline'].get('kernel_us'))") || exit 1
+    v=$(env $e python bench.py --full --gpus 1 $args --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'], d['ms_per_step'], d['roofline'].get('kernel_us'))") || exit 1
     echo "$tag [$e] run $i: $v" >> "$out"
   done
 done

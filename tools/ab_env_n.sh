@@ -6,7 +6,7 @@ args=${BENCH_ARGS:---steps 20 --warmup 5}
 mkdir -p "$(dirname "$out")"; : > "$out"
 for i in $(seq 1 "$n"); do
   for e in "$@"; do
-    v=$(env $e python bench.py --gpus 1 $args --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'])") || exit 1
+    v=$(env $e python bench.py --full --gpus 1 $args --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['value'])") || exit 1
     echo "[$e] $v" >> "$out"
   done
   echo "round $i done"

@@ -631,6 +631,154 @@ def offline_surface_case(ref_root, outdir):
     print("g15_offline_surface ok:", desc["mlp_keys"]["zero"])
 
 
+def _describe(x):
+    """JSON-able layout of a (nested) state_dict: tensors as shape / dtype, everything else as its value."""
+    if isinstance(x, torch.Tensor):
+        return {"tensor": list(x.shape), "dtype": str(x.dtype).replace("torch.", "")}
+    if isinstance(x, dict):
+        return {"dict": [[k, _describe(v)] for k, v in x.items()]}
+    if isinstance(x, (list, tuple)):
+        return {"list": [_describe(v) for v in x]}
+    return {"value": x}
+
+
+def dropin_surface_case(ref, ref_root, outdir):
+    """G16: the reference's jsrl_utils.py run against THIS repo's `iql`, recorded as data: which names it imports from
+    `iql`, every constructor / method call / attribute write make_actor and get_learning_agent make on those classes
+    (optimizers as {type, lr, params_of}), and the layout of the reference's own checkpoint after one training step
+    (tests/test_dropin_reference.py replays the calls and checks checkpoints in both directions against the layout)."""
+    sys.path.insert(0, os.path.join(ROOT, "jsrl-corl_amd"))
+    spec = importlib.util.spec_from_file_location("iqlhip_iql", os.path.join(ROOT, "jsrl-corl_amd", "iql.py"))
+    ours = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ours)
+    events, objs = [], []
+
+    def oid(o):
+        for i, p in enumerate(objs):
+            if p is o:
+                return i
+        return None
+
+    def enc(v):
+        if isinstance(v, torch.optim.Optimizer):
+            ps = [p for g in v.param_groups for p in g["params"]]
+            owner = [i for i, o in enumerate(objs) if isinstance(o, torch.nn.Module)
+                     and [id(p) for p in o.parameters()] == [id(p) for p in ps]]
+            return {"optimizer": type(v).__name__, "lr": v.param_groups[0]["lr"], "params_of": owner[0]}
+        if oid(v) is not None:
+            return {"obj": oid(v)}
+        if isinstance(v, dict) and all(isinstance(k, str) for k in v) and getattr(v, "_state_dict_of", None) is not None:
+            return {"state_dict_of": v._state_dict_of}
+        if isinstance(v, torch.device):
+            return str(v)
+        assert v is None or isinstance(v, (bool, int, float, str)), type(v)
+        return v
+
+    class _SD(dict):
+        _state_dict_of = None
+
+    def recording(cls):
+        class R(cls):
+            def __init__(self, *a, **k):
+                ev = {"new": cls.__name__, "args": [enc(x) for x in a], "kwargs": {n: enc(x) for n, x in k.items()}}
+                super().__init__(*a, **k)
+                objs.append(self)
+                ev["id"] = len(objs) - 1
+                events.append(ev)
+                object.__setattr__(self, "_rec_ready", True)
+
+            def __setattr__(self, name, value):
+                if getattr(self, "_rec_ready", False) and isinstance(value, (int, float)) and not name.startswith("_") \
+                        and not getattr(self, "_in_call", False):
+                    events.append({"setattr": name, "on": oid(self), "value": value})
+                super().__setattr__(name, value)
+
+            def to(self, *a, **k):
+                if oid(self) is not None:          # (not the trainer's own deep copies)
+                    events.append({"call": "to", "on": oid(self), "args": [enc(x) for x in a]})
+                return super().to(*a, **k)
+
+            def state_dict(self, *a, **k):
+                sd = _SD(super().state_dict(*a, **k))
+                sd._state_dict_of = oid(self)
+                if isinstance(self, ours.ImplicitQLearning):
+                    events.append({"call": "state_dict", "on": oid(self)})
+                return sd
+
+            def partial_load_state_dict(self, sd):
+                events.append({"call": "partial_load_state_dict", "on": oid(self), "args": [enc(sd)]})
+                object.__setattr__(self, "_in_call", True)
+                try:
+                    return super().partial_load_state_dict(dict(sd))
+                finally:
+                    object.__setattr__(self, "_in_call", False)
+        R.__name__ = R.__qualname__ = cls.__name__
+        return R
+
+    rec = types.ModuleType("iql")
+    names = [n for n in dir(ours) if isinstance(getattr(ours, n), type)]
+    for n in names:
+        c = getattr(ours, n)
+        setattr(rec, n, recording(c) if issubclass(c, torch.nn.Module) or c is ours.ImplicitQLearning else c)
+    for name, attrs in (("stable_baselines3.sac.policies", {"Actor": type("Actor", (), {})}),):
+        if name not in sys.modules:
+            sys.modules[name] = types.ModuleType(name)
+            for k, v in attrs.items():
+                setattr(sys.modules[name], k, v)
+    for name, sub_ in (("stable_baselines3.sac", "policies"), ("stable_baselines3", "sac")):
+        if name not in sys.modules:
+            sys.modules[name] = types.ModuleType(name)
+            setattr(sys.modules[name], sub_, sys.modules[name + "." + sub_])
+    sys.modules["stable_baselines3"].SAC = getattr(sys.modules["stable_baselines3"], "SAC", type("SAC", (), {}))
+    saved = sys.modules.get("iql")
+    sys.modules["iql"] = rec
+    try:
+        jspec = importlib.util.spec_from_file_location("ref_jsrl_utils_dropin", os.path.join(ref_root, "algorithms", "finetune", "jsrl_utils.py"))
+        jsrl = importlib.util.module_from_spec(jspec)
+        jspec.loader.exec_module(jsrl)
+    finally:
+        if saved is not None:
+            sys.modules["iql"] = saved
+    imported = sorted(n for n, v in vars(jsrl).items() if any(v is getattr(rec, m) for m in names))
+
+    class Cfg:
+        device = "cpu"
+        actor_dropout = 0.0
+        iql_deterministic = False
+        vf_lr = qf_lr = actor_lr = 3e-4
+        discount, tau, beta, iql_tau = 0.99, 0.005, 3.0, 0.7
+        n_curriculum_stages, horizon_fn, no_agent_types, rolling_mean_n, tolerance = 5, "time_step", True, 5, 0.05
+        guide_heuristic_fn = None
+        offline_iterations = 123
+
+    scen = {}
+    torch.manual_seed(0)
+    for tag, call in (("make_actor_max_steps", lambda: jsrl.make_actor(Cfg(), 17, 6, 1.0, max_steps=1000)),
+                      ("make_actor_online", lambda: jsrl.make_actor(Cfg(), 17, 6, 1.0))):
+        del events[:]
+        out = call()
+        scen[tag] = {"events": list(events), "returns": oid(out)}
+    cfg = Cfg()
+    cfg.n_curriculum_stages = 1
+    del events[:]
+    guide = jsrl.make_actor(cfg, 17, 6, 1.0, max_steps=1000)
+    scen["guide"] = {"events": list(events), "returns": oid(guide)}
+    del events[:]
+    trainer, _ = jsrl.get_learning_agent(cfg, guide, 300, 17, 6, 1.0)
+    scen["get_learning_agent"] = {"events": list(events), "returns": oid(trainer), "guide": oid(guide)}
+
+    # the reference's own checkpoint after one training step (seed 3, the batch drawn right after the nets)
+    torch.manual_seed(3)
+    q, v, a = ref.TwinQ(17, 6), ref.ValueFunction(17), ref.GaussianPolicy(17, 6, 1.0)
+    r = ref.ImplicitQLearning(1.0, a, torch.optim.Adam(a.parameters(), lr=3e-4), q, torch.optim.Adam(q.parameters(), lr=3e-4),
+                              v, torch.optim.Adam(v.parameters(), lr=3e-4), max_steps=1000, device="cpu")
+    batch = [torch.randn(64, 17), torch.rand(64, 6) * 2 - 1, torch.randn(64, 1), torch.randn(64, 17), torch.zeros(64, 1)]
+    r.train(batch)
+    desc = {"imported_from_iql": imported, "scenarios": scen, "checkpoint": _describe(r.state_dict())}
+    np.savez(os.path.join(outdir, "g16_dropin_surface.npz"), meta=np.array(json.dumps(desc)))
+    print("g16_dropin_surface ok:", imported, {k: len(v["events"]) for k, v in scen.items()})
+
+
 def round2_cases(ref, args):
     jsrl = import_reference_jsrl(args.ref)
     resume_case(ref, "g11_resume_S17A6_gauss", 17, 6, True, 110, 13, args.out)
@@ -639,6 +787,7 @@ def round2_cases(ref, args):
     jsrl_hostlogic_case(jsrl, args.out)
     bf16_largebatch_case(ref, "g14_c5_B1024_dropout", args.out)
     offline_surface_case(args.ref, args.out)
+    dropin_surface_case(ref, args.ref, args.out)
 
 
 def main():
@@ -651,6 +800,9 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     torch.set_num_threads(1)
     ref = import_reference(args.ref)
+    if args.only == "dropin":
+        dropin_surface_case(ref, args.ref, args.out)
+        return
     if args.only == "r2":
         round2_cases(ref, args)
         return
