@@ -297,6 +297,35 @@ int iqlhip_rows_normalize(float* rows_dev, int64_t ld, int32_t state_dim, int32_
 /* Device-side index draw used by iqlhip_train_steps, exposed for tests. */
 int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- trainer groups -------------------------------------------------------------------------------------------
+ * K independent agents (contexts) of the same shape stepped together: every kernel launch of a group step covers all
+ * K agents (seed sweeps and hyper-parameter sweeps of one configuration on one GPU).  Each agent keeps its own arenas,
+ * Adam state, target nets, scratch, scalars and batches; after a group call every member is exactly where the same
+ * steps run alone (iqlhip_step / iqlhip_train_steps) would have left it, bit for bit.
+ * Members: 1..IQLHIP_MAX_GROUP distinct contexts on one device with equal state / action dims, policy kind and
+ * precision; no data-parallel exchange, no actor dropout (IQLHIP_EUNSUPPORTED).  Batches: one size for all members,
+ * small-batch kernels only (bf16: at most 512 rows).  A group call invalidates each member's train_steps continuation
+ * (the staging buffer is overwritten).  The members must outlive the group; a context that is destroyed or re-created
+ * means a new group. */
+#define IQLHIP_MAX_GROUP 16
+#define IQLHIP_GROUP_MAX_STEPS 1024   /* steps per iqlhip_group_train_steps call */
+typedef struct iqlhip_group iqlhip_group;
+int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out);
+int iqlhip_group_destroy(iqlhip_group* group);
+/* One step per member on caller-given batches (batches[k], sc[k]); out[3k] (value, q, actor per member) or NULL.
+ * With out != NULL the call synchronises `stream`. */
+int iqlhip_group_step(iqlhip_group* group, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
+                      void* stream);
+/* n steps per member with row indices drawn on the device: member k draws from rows[k] (packed rows, stride ld,
+ * size[k] rows) under (seeds[k], offsets[k]) exactly as iqlhip_train_steps(..., seed, stream_offset) does, and takes
+ * its per-step scalars from tables[k] (n x iqlhip_step_scalars, host memory, free again on return).  The losses of
+ * every step go to a per-member ring read by iqlhip_group_read_losses.  flags: reserved (0). */
+int iqlhip_group_train_steps(iqlhip_group* group, const float* const* rows, int64_t ld, const int64_t* size, int32_t B,
+                             const void* const* tables, int32_t n, const uint64_t* seeds, const uint64_t* offsets,
+                             int32_t flags, void* stream);
+/* out[k][n][3]: the losses of the first n steps of the last group call; synchronises `stream`. */
+int iqlhip_group_read_losses(iqlhip_group* group, float* out, int32_t n, void* stream);
+
 /* ---- policy inference ---------------------------------------------------- */
 /* GaussianPolicy.act (algorithms/finetune/iql.py:371-379), DeterministicPolicy.act (:404-413) and the batched policy
  * forward of evaluation loops (eval_actor, jsrl_w_iql.py:62-179):

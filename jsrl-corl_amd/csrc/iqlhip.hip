@@ -2214,3 +2214,301 @@ extern "C" int iqlhip_debug_read(iqlhip_ctx* c, const char* name, float* host_ou
   if (n_out) *n_out = n;
   return IQLHIP_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Trainer groups (include/iqlhip.h): K contexts of identical dims stepped together.  Every launch of a group step covers
+// all K agents (grid.y = agent); each agent's launch arguments are a device-resident GroupRec (iqlhip_kernels.h) the
+// host writes once per call, together with the agents' scalar tables, in ONE host-to-device copy from pinned memory.
+struct iqlhip_group {
+  int k = 0;
+  int device = 0;
+  iqlhip_ctx* m[IQLHIP_MAX_GROUP] = {};
+  char* blob_dev = nullptr;           // [GroupRec x k | pad][scalars: k x IQLHIP_GROUP_MAX_STEPS]
+  char* blob_pin = nullptr;           // pinned staging of the same bytes
+  size_t tab_off = 0, blob_bytes = 0;
+  float* ring_dev = nullptr;          // [k][IQLHIP_GROUP_MAX_STEPS][4] losses of the last call
+  float* ring_pin = nullptr;
+  int last_n = 0;                     // steps of the last call (rows of the ring that are valid)
+  hipEvent_t up_done = nullptr;       // the last upload has read blob_pin
+  bool up_pending = false;
+};
+
+static int group_check_members(iqlhip_ctx* const* members, int k) {
+  if (!members) return fail(IQLHIP_EINVAL, "members is NULL");
+  if (k < 1 || k > IQLHIP_MAX_GROUP) return fail(IQLHIP_EINVAL, "group size %d outside [1,%d]", k, IQLHIP_MAX_GROUP);
+  for (int i = 0; i < k; ++i) {
+    if (!members[i]) return fail(IQLHIP_EINVAL, "member %d is NULL", i);
+    for (int j = 0; j < i; ++j)
+      if (members[j] == members[i]) return fail(IQLHIP_EINVAL, "member %d is member %d again", i, j);
+  }
+  const iqlhip_ctx* a = members[0];
+  for (int i = 0; i < k; ++i) {
+    const iqlhip_ctx* c = members[i];
+    if (c->device != a->device) return fail(IQLHIP_EINVAL, "member %d is on device %d, member 0 on %d", i, c->device, a->device);
+    if (c->dims.state_dim != a->dims.state_dim || c->dims.action_dim != a->dims.action_dim || c->dims.policy != a->dims.policy)
+      return fail(IQLHIP_EINVAL, "member %d has other dims or policy kind than member 0", i);
+    if (c->precision != a->precision) return fail(IQLHIP_EINVAL, "member %d has another precision than member 0", i);
+    if (c->xch_mode != IQLHIP_XCH_NONE || c->world > 1)
+      return fail(IQLHIP_EUNSUPPORTED, "member %d has data parallelism enabled (not supported in a group)", i);
+    if (c->drop_p > 0.f) return fail(IQLHIP_EUNSUPPORTED, "member %d uses actor dropout (not supported in a group)", i);
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
+  if (!g) return fail(IQLHIP_EINVAL, "NULL group");
+  DevGuard guard(g->device);
+  (void)hipDeviceSynchronize();       // a group call may still be running on some stream
+  if (g->blob_dev) (void)hipFree(g->blob_dev);
+  if (g->blob_pin) (void)hipHostFree(g->blob_pin);
+  if (g->ring_dev) (void)hipFree(g->ring_dev);
+  if (g->ring_pin) (void)hipHostFree(g->ring_pin);
+  if (g->up_done) (void)hipEventDestroy(g->up_done);
+  delete g;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out) {
+  if (!out) return fail(IQLHIP_EINVAL, "out is NULL");
+  int rc = group_check_members(members, k);
+  if (rc) return rc;
+  iqlhip_group* g = new iqlhip_group();
+  g->k = k;
+  g->device = members[0]->device;
+  for (int i = 0; i < k; ++i) g->m[i] = members[i];
+  DevGuard guard(g->device);
+  auto setup = [&]() -> int {
+    g->tab_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
+    g->blob_bytes = g->tab_off + (size_t)k * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars);
+    HIPCHK(hipMalloc((void**)&g->blob_dev, g->blob_bytes));
+    HIPCHK(hipHostMalloc((void**)&g->blob_pin, g->blob_bytes, hipHostMallocDefault));
+    memset(g->blob_pin, 0, g->blob_bytes);
+    const size_t ring = (size_t)k * IQLHIP_GROUP_MAX_STEPS * 4 * sizeof(float);
+    HIPCHK(hipMalloc((void**)&g->ring_dev, ring));
+    HIPCHK(hipMemset(g->ring_dev, 0, ring));
+    HIPCHK(hipHostMalloc((void**)&g->ring_pin, ring, hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&g->up_done, hipEventDisableTiming));
+    const iqlhip_ctx* c = members[0];
+    const void* fwd[8] = {(const void*)iql_fwd_group_kernel<false, false, false>, (const void*)iql_fwd_group_kernel<false, true, false>,
+                          (const void*)iql_fwd_group_kernel<true, false, false>,  (const void*)iql_fwd_group_kernel<true, true, false>,
+                          (const void*)iql_fwd_group_kernel<false, false, true>,  (const void*)iql_fwd_group_kernel<false, true, true>,
+                          (const void*)iql_fwd_group_kernel<true, false, true>,   (const void*)iql_fwd_group_kernel<true, true, true>};
+    for (const void* f : fwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_fwd_solo));
+    const void* bwd[4] = {(const void*)iql_bwd_group_kernel<false, false>, (const void*)iql_bwd_group_kernel<false, true>,
+                          (const void*)iql_bwd_group_kernel<true, false>,  (const void*)iql_bwd_group_kernel<true, true>};
+    for (const void* f : bwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd));
+    return IQLHIP_OK;
+  };
+  rc = setup();
+  if (rc) {
+    const std::string msg = g_err;
+    iqlhip_group_destroy(g);
+    g_err = msg;
+    return rc;
+  }
+  *out = g;
+  return IQLHIP_OK;
+}
+
+// Geometry of a group step: the forward's slices per block chosen for the whole group grid (the single-agent rule applied
+// to K x the row tiles); the backward's (b) blocks take one slice each (iql_bwd_group_kernel).  Results do not depend on
+// either (bit-identical for every slice count).
+struct GroupGeom { int n_rt, n_chunk, fwd_l2, fwd_nb, bwd_nb, upd_nb; bool full; };
+static GroupGeom group_geom(const iqlhip_ctx* c, int rows, int k) {
+  GroupGeom q;
+  q.n_rt = (rows + RT_ROWS - 1) / RT_ROWS;
+  q.n_chunk = (rows + CHUNK_ROWS - 1) / CHUNK_ROWS;
+  q.fwd_l2 = fwd_spb_l2(c, k * q.n_rt);
+  q.fwd_nb = (q.fwd_l2 == 2) ? 8 * 2 * ((q.n_rt + 1) / 2) : 8 * q.n_rt * (NSPLIT >> q.fwd_l2);
+  const int per_net = 32 * q.n_chunk + 4 * q.n_rt;
+  q.bwd_nb = 8 * ((per_net + 1) / 2);
+  long long seg_max = 0;
+  for (int n = 0; n < 4; ++n) {
+    const long long end = (n < 3) ? c->L.net[n + 1].seg_begin : c->L.n_params;
+    seg_max = std::max(seg_max, end - c->L.net[n].seg_begin);
+  }
+  q.upd_nb = 8 * (int)((seg_max + 2047) / 2048);
+  q.full = (rows % CHUNK_ROWS) == 0;
+  return q;
+}
+
+// Checks shared by both step entry points (before any device work).
+static int group_check_call(iqlhip_group* g, int rows) {
+  if (!g) return fail(IQLHIP_EINVAL, "NULL group");
+  int rc = group_check_members(g->m, g->k);
+  if (rc) return rc;
+  for (int i = 0; i < g->k; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    if (!c->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called", i);
+    if (rows < 1 || rows > c->dims.max_batch)
+      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, max_batch=%d]", i, rows, c->dims.max_batch);
+  }
+  if (g->m[0]->precision == 1 && rows > LB_MIN_ROWS)
+    return fail(IQLHIP_EUNSUPPORTED, "bf16 groups take batches of at most %d rows (the large-batch kernels have no group form)", LB_MIN_ROWS);
+  return IQLHIP_OK;
+}
+
+// Write agent i's record (host side) for a call of n steps on batches of `rows` rows staged at xb.
+static void group_record(iqlhip_group* g, int i, const GroupGeom& q, int rows, int n, const float* xb,
+                         const iqlhip_step_scalars* sc0) {
+  iqlhip_ctx* c = g->m[i];
+  GroupRec& r = ((GroupRec*)g->blob_pin)[i];
+  memset(&r, 0, sizeof r);
+  r.p = make_step(c, rows, sc0->inv_batch);
+  r.p.xb = xb;
+  r.p.spb_l2 = q.fwd_l2;
+  r.q_heads = r.p.sc.heads; r.q_xb = xb; r.q_h1 = r.p.sc.h1; r.q_h0 = r.p.sc.h0; r.q_params = c->params;
+  r.q_dims = (unsigned)r.p.S | ((unsigned)r.p.A << 8) | ((unsigned)r.p.policy << 14);
+  r.q_ldB = (unsigned)r.p.ld | ((unsigned)rows << 10);
+  r.q_mbc = (unsigned)r.p.sc.max_batch | ((unsigned)q.n_chunk << 16);
+  r.q_rts = (unsigned)q.n_rt;         // (one-slice backward: no slice or donation word)
+  r.u = make_upd(c, sc0, rows, nullptr);
+  r.u.sched = (const iqlhip_step_scalars*)(g->blob_dev + g->tab_off) + (size_t)i * IQLHIP_GROUP_MAX_STEPS;
+  r.u.sched_idx = 0;
+  r.u.loss_ring = g->ring_dev + (size_t)i * IQLHIP_GROUP_MAX_STEPS * 4;
+  r.u.ring_slot = 0;
+  r.u_p = r.u.params; r.u_m = r.u.m; r.u_v = r.u.v; r.u_slab_a = r.u.slab_a;
+  r.u_s0 = (unsigned)c->L.net[0].seg_begin; r.u_s1 = (unsigned)c->L.net[1].seg_begin;
+  r.u_s2 = (unsigned)c->L.net[2].seg_begin; r.u_s3 = (unsigned)c->L.net[3].seg_begin; r.u_end = (unsigned)c->L.net[3].seg_end;
+  r.u_flags = (r.u.n_chunk == 1) ? UPD_EARLY_G : 0u;
+  r.n_steps = n;
+  r.xb = (float*)xb;
+  r.B = rows;
+}
+
+// Wait until the previous upload has read the pinned staging (normally long done: the host builds the next call's
+// records while the GPU runs this one's steps).
+static int group_staging_free(iqlhip_group* g) {
+  if (g->up_pending) HIPCHK(hipEventSynchronize(g->up_done));
+  g->up_pending = false;
+  return IQLHIP_OK;
+}
+
+static int group_upload(iqlhip_group* g, int n, hipStream_t st) {
+  // records + the used rows of every agent's table (the tables are strided by IQLHIP_GROUP_MAX_STEPS)
+  const size_t bytes = g->tab_off + ((size_t)(g->k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars);
+  HIPCHK(hipMemcpyAsync(g->blob_dev, g->blob_pin, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(g->up_done, st));
+  g->up_pending = true;
+  return IQLHIP_OK;
+}
+
+static void group_launch_step(iqlhip_group* g, const GroupGeom& q, int s, hipStream_t st) {
+  const iqlhip_ctx* c = g->m[0];
+  const GroupRec* recs = (const GroupRec*)g->blob_dev;
+  const int K = g->k;
+  const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K, fmulti = q.fwd_l2 > 0;
+  const size_t lds = fwd_lds(c, q.fwd_nb * K);
+  const dim3 fg(q.fwd_nb, K), bg(q.bwd_nb, K), ug(q.upd_nb, K);
+#define FWD_G(BF, DMA, MU) hipLaunchKernelGGL((iql_fwd_group_kernel<BF, DMA, MU>), fg, dim3(256), lds, st, recs)
+  if (fmulti) {
+    if (bf) { if (dma) FWD_G(true, true, true); else FWD_G(true, false, true); }
+    else    { if (dma) FWD_G(false, true, true); else FWD_G(false, false, true); }
+  } else {
+    if (bf) { if (dma) FWD_G(true, true, false); else FWD_G(true, false, false); }
+    else    { if (dma) FWD_G(false, true, false); else FWD_G(false, false, false); }
+  }
+#undef FWD_G
+#define BWD_G(BF, FU) hipLaunchKernelGGL((iql_bwd_group_kernel<BF, FU>), bg, dim3(256), c->lds_bwd, st, recs)
+  if (bf) { if (q.full) BWD_G(true, true); else BWD_G(true, false); }
+  else    { if (q.full) BWD_G(false, true); else BWD_G(false, false); }
+#undef BWD_G
+  hipLaunchKernelGGL(iql_update_group_kernel, ug, dim3(256), 0, st, recs, s);
+}
+
+static int group_losses_out(iqlhip_group* g, float* out, int n, hipStream_t st) {
+  if (!out) return IQLHIP_OK;
+  const size_t row = (size_t)IQLHIP_GROUP_MAX_STEPS * 4;
+  for (int i = 0; i < g->k; ++i)
+    HIPCHK(hipMemcpyAsync(g->ring_pin + i * row, g->ring_dev + i * row, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < g->k; ++i)
+    for (int s = 0; s < n; ++s)
+      for (int j = 0; j < 3; ++j) out[((size_t)i * n + s) * 3 + j] = g->ring_pin[i * row + (size_t)s * 4 + j];
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
+                                 void* stream) {
+  if (!g || !batches || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  const int rows = batches[0].rows;
+  int rc = group_check_call(g, rows);
+  if (rc) return rc;
+  for (int i = 0; i < g->k; ++i) {
+    rc = check_batch(g->m[i], &batches[i]);
+    if (rc) return rc;
+    if (batches[i].rows != rows) return fail(IQLHIP_EINVAL, "member %d: batch of %d rows, member 0: %d (one batch size per group)", i, batches[i].rows, rows);
+    if (batches[i].idx_dev && (rc = check_indexed(g->m[i], &batches[i]))) return rc;
+  }
+  DevGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  rc = group_staging_free(g);
+  if (rc) return rc;
+  const GroupGeom q = group_geom(g->m[0], rows, g->k);
+  for (int i = 0; i < g->k; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    c->cont.valid = false;
+    const float* xb = nullptr;
+    rc = stage_batch(c, &batches[i], st, &xb);
+    if (rc) return rc;
+    refresh_shadows(c, st);
+    group_record(g, i, q, rows, 1, xb, &sc[i]);
+    ((iqlhip_step_scalars*)(g->blob_pin + g->tab_off))[(size_t)i * IQLHIP_GROUP_MAX_STEPS] = sc[i];
+  }
+  rc = group_upload(g, 1, st);
+  if (rc) return rc;
+  group_launch_step(g, q, 0, st);
+  HIPCHK(hipGetLastError());
+  g->last_n = 1;
+  return group_losses_out(g, out, 1, st);
+}
+
+extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
+                                        int32_t B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                        const uint64_t* offsets, int32_t flags, void* stream) {
+  (void)flags;
+  if (!g || !rows || !size || !tables || !seeds || !offsets) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = group_check_call(g, B);
+  if (rc) return rc;
+  if (n < 1 || n > IQLHIP_GROUP_MAX_STEPS) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", IQLHIP_GROUP_MAX_STEPS);
+  for (int i = 0; i < g->k; ++i) {
+    rc = check_train_args(g->m[i], rows[i], ld, B);
+    if (rc) return rc;
+    if (size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty buffer", i);
+    if (!tables[i]) return fail(IQLHIP_EINVAL, "member %d: NULL scalar table", i);
+  }
+  DevGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  rc = group_staging_free(g);
+  if (rc) return rc;
+  const GroupGeom q = group_geom(g->m[0], B, g->k);
+  for (int i = 0; i < g->k; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
+    refresh_shadows(c, st);
+    const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
+    group_record(g, i, q, B, n, c->xb, &tab[0]);
+    GroupRec& r = ((GroupRec*)g->blob_pin)[i];
+    r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
+    memcpy(g->blob_pin + g->tab_off + (size_t)i * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars), tab,
+           (size_t)n * sizeof(iqlhip_step_scalars));
+  }
+  rc = group_upload(g, n, st);
+  if (rc) return rc;
+  const iqlhip_ctx* c0 = g->m[0];
+  const int gather_nb = (int)std::min<int64_t>(((int64_t)B * (c0->row_ld / 4) + 255) / 256, 1024);
+  for (int s = 0; s < n; ++s) {
+    hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev, s);
+    group_launch_step(g, q, s, st);
+  }
+  HIPCHK(hipGetLastError());
+  g->last_n = n;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, void* stream) {
+  if (!g || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n < 1 || n > g->last_n) return fail(IQLHIP_EINVAL, "n_steps %d outside [1,%d] (steps of the last group call)", n, g->last_n);
+  DevGuard guard(g->device);
+  return group_losses_out(g, out, n, (hipStream_t)stream);
+}

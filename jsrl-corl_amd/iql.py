@@ -15,3 +15,4 @@ from iqlhip_networks import (LOG_STD_MAX, LOG_STD_MIN, MLP, DeterministicPolicy,
                              TwinQ, ValueFunction)
 from iqlhip_replay import OfflineReplayBuffer, ReplayBuffer, TensorBatch  # noqa: F401
 from iqlhip_trainer import EXP_ADV_MAX, ImplicitQLearning  # noqa: F401
+from iqlhip_group import ImplicitQLearningGroup  # noqa: F401  (K trainers of one shape stepped together)

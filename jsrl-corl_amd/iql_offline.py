@@ -12,3 +12,4 @@ from iqlhip_networks import LOG_STD_MAX, LOG_STD_MIN, Squeeze, TwinQ, ValueFunct
 from iqlhip_offline import MLP, DeterministicPolicy, GaussianPolicy, ImplicitQLearning, eval_actor  # noqa: F401
 from iqlhip_replay import OfflineReplayBuffer as ReplayBuffer, TensorBatch  # noqa: F401
 from iqlhip_trainer import EXP_ADV_MAX  # noqa: F401
+from iqlhip_group import ImplicitQLearningGroup  # noqa: F401  (K trainers of one shape stepped together)

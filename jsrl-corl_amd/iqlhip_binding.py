@@ -17,6 +17,8 @@ IQLHIP_HIDDEN = 256
 IQLHIP_ACT_ROWS = 4096      # rows per iqlhip_actor_forward call (include/iqlhip.h)
 IQLHIP_MAX_WORLD = 8
 IQLHIP_GRAPH_STEPS = 64
+IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
+IQLHIP_GROUP_MAX_STEPS = 1024  # steps per iqlhip_group_train_steps call
 IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
 XCH_NONE, XCH_RCCL, XCH_P2P = 0, 1, 2
@@ -127,6 +129,13 @@ SYMBOLS = [
     ("iqlhip_debug_time_kernel", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.POINTER(C.c_float),
                                            C.c_void_p]),
     ("iqlhip_debug_drain_spin", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    ("iqlhip_group_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    ("iqlhip_group_destroy", C.c_int, [C.c_void_p]),
+    ("iqlhip_group_step", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p]),
+    ("iqlhip_group_train_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64), C.c_int32,
+                                           C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.c_int32, C.c_void_p]),
+    ("iqlhip_group_read_losses", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

@@ -1,0 +1,190 @@
+"""Trainer groups: K independent ImplicitQLearning trainers of identical shape stepped together.
+
+The reference runs seeds and hyper-parameter settings of one configuration side by side as separate processes
+(algorithms/finetune/ray_trainer_4seed.py: four seeds per GPU; ray_hyperparam.py).  A group runs them in ONE process:
+every HIP launch of a group step covers all K agents (iqlhip_group_* in include/iqlhip.h).  Each member keeps its own
+parameters, Adam state, target nets, hyper-parameters, learning-rate schedule, index stream and replay buffer; after a
+group call every member is exactly — bit for bit — where the same steps run alone (`train` / `train_steps`) would have
+left it, so its state_dict, checkpoints, act() and later solo calls carry on unchanged.
+
+    group = ImplicitQLearningGroup([trainer_seed0, trainer_seed1, trainer_seed2, trainer_seed3])
+    losses = group.train_steps(buffer, n_steps=1000, batch_size=256, seeds=[0, 1, 2, 3])   # [4, 1000, 3]
+
+Not supported (NotImplementedError): data parallelism, actor dropout > 0, bf16 batches of more than 512 rows.
+A group of one runs the solo entry points themselves (the same results; the solo driver is faster for one agent).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+import iqlhip_binding as hb
+from iqlhip_trainer import K_MAX, ImplicitQLearning
+
+BF16_MAX_ROWS = 512      # bf16 batches beyond this run the large-batch kernels, which have no group form
+
+
+class ImplicitQLearningGroup:
+    def __init__(self, trainers: Sequence[ImplicitQLearning]):
+        trainers = list(trainers)
+        if not 1 <= len(trainers) <= hb.IQLHIP_MAX_GROUP:
+            raise ValueError(f"iqlhip: a group has 1..{hb.IQLHIP_MAX_GROUP} trainers, got {len(trainers)}")
+        self.trainers = trainers
+        self._check_members()
+        self._g = None
+        self._ctxs = None
+
+    # ------------------------------------------------------------------ validation (no library call)
+    def _check_members(self) -> None:
+        trs = self.trainers
+        for i, t in enumerate(trs):
+            if not isinstance(t, ImplicitQLearning):
+                raise ValueError(f"iqlhip: group member {i} is not an ImplicitQLearning trainer")
+            if any(t is u for u in trs[:i]):
+                raise ValueError(f"iqlhip: group member {i} is the same trainer as an earlier member")
+        for i, t in enumerate(trs):
+            if t._ctx is None:
+                raise RuntimeError(f"iqlhip: group member {i} is not on a GPU device (device='cuda'); there is no CPU "
+                                   "implementation of the step in this package")
+        t0 = trs[0]
+        for i, t in enumerate(trs):
+            if t._dev != t0._dev:
+                raise ValueError(f"iqlhip: group member {i} is on {t._dev}, member 0 on {t0._dev}")
+            if (t._S, t._A, t._gaussian) != (t0._S, t0._A, t0._gaussian):
+                raise ValueError(f"iqlhip: group member {i} has dims (S={t._S}, A={t._A}, gaussian={t._gaussian}), "
+                                 f"member 0 (S={t0._S}, A={t0._A}, gaussian={t0._gaussian})")
+            if getattr(t, "_precision", "f32") != getattr(t0, "_precision", "f32"):
+                raise ValueError(f"iqlhip: group member {i} has another precision than member 0")
+            if t._dp_world > 1 or t._dp_exchange is not None:
+                raise NotImplementedError(f"iqlhip: group member {i} has data parallelism enabled (not supported in a group)")
+            if t.actor.training and t._actor_dropout_p() > 0.0:
+                raise NotImplementedError(f"iqlhip: group member {i} uses actor dropout (not supported in a group)")
+
+    def _check_batch_size(self, B: int) -> None:
+        if getattr(self.trainers[0], "_precision", "f32") == "bf16" and B > BF16_MAX_ROWS:
+            raise NotImplementedError(f"iqlhip: bf16 groups take batches of at most {BF16_MAX_ROWS} rows (got {B})")
+
+    # ------------------------------------------------------------------ the library group
+    def _group(self):
+        """The library group over the members' current contexts (re-created when a member re-attached)."""
+        ctxs = tuple(int(t._ctx.value) for t in self.trainers)
+        if self._g is not None and ctxs == self._ctxs:
+            return self._g
+        self._release()
+        arr = (C.c_void_p * len(ctxs))(*ctxs)
+        g = C.c_void_p()
+        hb.check(hb.lib().iqlhip_group_create(arr, len(ctxs), C.byref(g)))
+        self._g, self._ctxs = g, ctxs
+        return g
+
+    def _release(self) -> None:
+        if self._g is not None:
+            hb.check(hb.lib().iqlhip_group_destroy(self._g))
+            self._g = None
+            self._ctxs = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return len(self.trainers)
+
+    # ------------------------------------------------------------------ eager steps
+    def train(self, batches: Sequence) -> List[Dict[str, float]]:
+        """One step per member on its own batch (ImplicitQLearning.train for each, in one set of launches).  All batches
+        have the same number of rows.  Returns one losses dict per member."""
+        batches = list(batches)
+        K = len(self.trainers)
+        if len(batches) != K:
+            raise ValueError(f"iqlhip: {len(batches)} batches for a group of {K}")
+        self._check_members()
+        B = int(batches[0][0].shape[0])
+        for i, b in enumerate(batches):
+            if int(b[0].shape[0]) != B:
+                raise ValueError(f"iqlhip: batch {i} has {int(b[0].shape[0])} rows, batch 0 has {B} (one batch size per group)")
+        self._check_batch_size(B)
+        if K == 1:      # a group of one IS the solo step (whose eager path returns through host-mapped words: faster)
+            return [self.trainers[0].train(batches[0])]
+        for t in self.trainers:
+            t._prepare(B)
+        structs, keep, scs, t_after = (hb.Batch * K)(), [], (hb.StepScalars * K)(), []
+        for i, (t, batch) in enumerate(zip(self.trainers, batches)):
+            b, kp, _ = t._batch_struct(batch)
+            structs[i] = b
+            keep.append(kp)
+            t1 = {g: n + 1 for g, n in t._adam_t.items()}
+            t._fill_scalars(scs[i], t1, t._current_lrs(), 1.0 / B)
+            t_after.append(t1)
+        out = (C.c_float * (3 * K))()
+        g = self._group()
+        hb.check(hb.lib().iqlhip_group_step(g, structs, scs, out, self.trainers[0]._stream()))
+        del keep
+        logs = []
+        for i, t in enumerate(self.trainers):
+            t.total_it += 1
+            t._adam_t = t_after[i]
+            t._advance_schedule(1)
+            t._ts_token = None
+            t._eager_next = None
+            logs.append({"value_loss": float(out[3 * i]), "q_loss": float(out[3 * i + 1]),
+                         "actor_loss": float(out[3 * i + 2])})
+        return logs
+
+    # ------------------------------------------------------------------ device-drawn steps
+    def train_steps(self, buffers, n_steps: int, batch_size: int, seeds: Sequence[int],
+                    return_losses: bool = True, chunk: int = K_MAX) -> Optional[np.ndarray]:
+        """n_steps `sample -> train` iterations per member (ImplicitQLearning.train_steps for each): member k draws its
+        rows from buffers[k] (or the one shared buffer) under seeds[k] — exactly the rows its own train_steps(buffer,
+        n_steps, batch_size, seed=seeds[k]) would draw.  Returns losses [K, n_steps, 3] when return_losses, else None."""
+        K = len(self.trainers)
+        bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
+        seeds = [int(s) for s in seeds]
+        if len(bufs) != K or len(seeds) != K:
+            raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer) and {K} seeds")
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        self._check_members()
+        self._check_batch_size(batch_size)
+        if K == 1:      # a group of one IS the solo call (chunk graphs, rows staged by idle forward blocks: faster)
+            out = self.trainers[0].train_steps(bufs[0], n_steps, batch_size, seed=seeds[0], return_losses=return_losses,
+                                               chunk=chunk)
+            return None if out is None else out[None]
+        sizes, inv = [], []
+        for t, buf in zip(self.trainers, bufs):
+            size, ib = t._train_steps_args(buf, batch_size)
+            sizes.append(size)
+            inv.append(ib)
+        if len({b._ld for b in bufs}) != 1:
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
+        lib, stream = hb.lib(), self.trainers[0]._stream()
+        g = self._group()
+        rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
+        size_arr = (C.c_int64 * K)(*sizes)
+        seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
+        half = (batch_size + 1) // 2
+        losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
+        done = 0
+        while done < n_steps:
+            k = min(chunk, n_steps - done)
+            offs = (C.c_uint64 * K)(*[t.total_it * half for t in self.trainers])
+            tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
+            tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
+            rc = lib.iqlhip_group_train_steps(g, rows, bufs[0]._ld, size_arr, batch_size, tab_ptrs, k, seed_arr, offs, 0,
+                                              stream)
+            for t in self.trainers:
+                t._ts_token = None
+            hb.check(rc)
+            for t in self.trainers:
+                t.total_it += k
+            if return_losses:
+                out = (C.c_float * (K * k * 3))()
+                hb.check(lib.iqlhip_group_read_losses(g, out, k, stream))
+                losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
+            done += k
+        return losses
