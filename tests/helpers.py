@@ -212,3 +212,115 @@ def step_batch(S, A, B, seed, **kw):
     d = synth.synth_transitions(B, S, A, seed=seed, **kw)
     return {"s": d["observations"], "a": d["actions"], "r": d["rewards"], "ns": d["next_observations"],
             "d": d["terminals"]}
+
+
+# ---------------------------------------------------------------------------
+# Which kernels a shape takes: Python restatements of the host's dispatch rules in csrc/iqlhip.hip, so that a test case's
+# comment about its path is checked rather than asserted.
+
+def w0_lds_k(S, A):
+    """iqlhip_create's layer-0 staging rule: the widest layer-0 input whose weights the forward stages in LDS (through
+    registers up to 64, by LDS-DMA above that: the forward's DMA=true instantiations); 0 = every W0 read from global."""
+    row_ld = (2 * S + A + 2 + 3) // 4 * 4
+    fixed = 4 * (32 * 260 + 32 * 68 + 32 * row_ld + ((A + 15) // 16 * 16) * 68 + 32 + 512 + 16)
+
+    def fits(k):
+        return fixed + 256 * k * 4 + 4096 <= 160 * 1024 - 1024
+    if S + A <= 96 and fits(S + A):
+        return S + A
+    if S <= 96 and fits(S):
+        return S
+    return 0
+
+
+def fwd_spb_l2(n_row_tiles, n_cus=256):
+    """fwd_spb_l2: the forward's column slices per block (log2); > 0 selects the MULTI instantiations."""
+    if 8 * n_row_tiles * 4 <= n_cus:
+        return 0
+    return 1 if 8 * n_row_tiles * 2 <= n_cus else 2
+
+
+def uses_large_batch_kernels(S, A, B):
+    """use_lb for a bf16 step: more than 512 rows and S + A + 1 <= 80."""
+    return B > 512 and S + A + 1 <= 80
+
+
+# ---------------------------------------------------------------------------
+# Row-permutation checks.  Every IQL loss is a mean of per-row terms (adv is detached, there is no batch statistic), so a
+# batch's gradient is the sum of its rows' terms and must not change, beyond fp32 summation order, when the rows are
+# permuted — whatever precision the kernels use for a row's own values.  An fp32 sum of terms x_r taken in an order of
+# depth d lies within d * u * sum_r |x_r| of the exact sum (u = 2^-24); two orders differ by at most twice that.
+
+FP32_U = 2.0 ** -24
+PERM_DEPTH = 16       # summation depth granted per gradient element
+
+
+def rows_of(batch, idx):
+    return {k: np.ascontiguousarray(v[idx]) for k, v in batch.items()}
+
+
+def row_abs_grad_sums(params, batch, hyper):
+    """{net: {tensor: sum over rows of |that row's term of the gradient|}} in float64 — the scale of each gradient
+    element's fp32 summation error (the oracle's per-row deltas, combined with absolute values)."""
+    from oracle import iql_oracle as O
+    f = np.float64
+    n = f(batch["s"].shape[0])
+    ref = O.iql_losses_and_grads(params, batch, hyper, dtype=f)
+    P = {k: {t: v.astype(f) for t, v in p.items()} for k, p in params.items()}
+    s, a = batch["s"].astype(f), batch["a"].astype(f)
+    r, d = batch["r"].astype(f), batch["d"].astype(f)
+    adv, w, mu = ref["adv"], ref["exp_adv"], ref["mu"]
+    wgt = np.abs(f(hyper["iql_tau"]) - (adv < 0).astype(f))
+    y = r + (1.0 - d) * f(hyper["discount"]) * ref["next_v"]
+    diff = a - mu
+    if hyper.get("deterministic", False):
+        dmu = -2.0 * w[:, None] * diff / n
+    else:
+        var = np.exp(np.clip(P["pi"]["log_std"], O.LOG_STD_MIN, O.LOG_STD_MAX)) ** 2
+        dmu = -w[:, None] * diff / var / n
+    douts = {"vf": (-2.0 * wgt * adv / n)[:, None], "q1": ((ref["q1"] - y) / n)[:, None],
+             "q2": ((ref["q2"] - y) / n)[:, None], "pi": dmu * (1.0 - mu * mu)}
+    sa = np.concatenate([s, a], 1)
+    xs = {"vf": s, "q1": sa, "q2": sa, "pi": s}
+    out = {}
+    for net, dout in douts.items():
+        h0, h1 = ref["acts"][net]
+        p = P[net]
+        dh1 = (dout @ p["w2"]) * (h1 > 0)
+        dh0 = (dh1 @ p["w1"]) * (h0 > 0)
+        out[net] = {"w2": np.abs(dout).T @ np.abs(h1), "b2": np.abs(dout).sum(0),
+                    "w1": np.abs(dh1).T @ np.abs(h0), "b1": np.abs(dh1).sum(0),
+                    "w0": np.abs(dh0).T @ np.abs(xs[net]), "b0": np.abs(dh0).sum(0)}
+    if not hyper.get("deterministic", False):
+        inside = (P["pi"]["log_std"] >= O.LOG_STD_MIN) & (P["pi"]["log_std"] <= O.LOG_STD_MAX)
+        out["pi"]["log_std"] = (np.abs(w[:, None] * (1.0 - diff * diff / var)) / n).sum(0) * inside
+    return out
+
+
+def smallest_row_groups(B):
+    """The smallest row groups the kernels handle separately: the ragged remainder of the 32-row tiles (one row when B
+    is a multiple of 32), at the end of the batch and — where a reversal moves them there — at its start."""
+    tail = B % 32 or 1
+    out = [np.arange(B - tail, B)]
+    if B > tail:
+        out.append(np.arange(0, tail))
+    return out
+
+
+def permutation_bounds(params, batch, hyper):
+    """{(net, tensor): (tolerance, contribution)}, both max-abs over the tensor's elements.
+    tolerance = 2 * PERM_DEPTH * u * max_ij sum_r |g_rij|: two fp32 orders of the same per-row terms.
+    contribution = the smaller, over smallest_row_groups, of that group's own gradient (float64 oracle with the batch's
+    divisor: the oracle is row-additive, tests/test_oracle_rows.py) — what the gradient moves by if the kernels drop or
+    double the group."""
+    from oracle import iql_oracle as O
+    B = batch["s"].shape[0]
+    sums = row_abs_grad_sums(params, batch, hyper)
+    contrib = {}
+    for grp in smallest_row_groups(B):
+        g = O.iql_losses_and_grads(params, rows_of(batch, grp), hyper, dtype=np.float64, grad_scale_rows=B)["grads"]
+        for net, ts in g.items():
+            for t, v in ts.items():
+                contrib[(net, t)] = min(contrib.get((net, t), np.inf), float(np.max(np.abs(v))))
+    return {(net, t): (2.0 * PERM_DEPTH * FP32_U * float(np.max(v)), contrib[(net, t)])
+            for net, ts in sums.items() for t, v in ts.items()}
