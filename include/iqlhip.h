@@ -325,6 +325,20 @@ int iqlhip_group_train_steps(iqlhip_group* group, const float* const* rows, int6
                              int32_t flags, void* stream);
 /* out[k][n][3]: the losses of the first n steps of the last group call; synchronises `stream`. */
 int iqlhip_group_read_losses(iqlhip_group* group, float* out, int32_t n, void* stream);
+/* One online-loop iteration per member (iqlhip_online_step for each member k, in one set of launches and one
+ * synchronisation): row_host[k][ld] is stored at ring row pointer[k] of rows_dev[k] (capacity[k] rows, stride ld; no
+ * two members' rings may overlap), the rows rows_dev[k][idx_host[k][0..n)] are gathered and one step runs on them with
+ * scalars sc[k]; out[k][3] receives the losses.  act_state_host != NULL ([k][state_dim]) additionally evaluates
+ * actor.act(state) with member k's updated policy for every k with act_mask[k] != 0 (act_mask == NULL: every
+ * member) into act_out_host[k][action_dim], with max_action[k] and the device noise of act_seed[k] (0: the mean
+ * action) as in iqlhip_online_step.  Host arrays are ordinary memory.  Everything is checked before any device work:
+ * the iqlhip_online_step checks per member, the group checks, indices within capacity[k] (IQLHIP_EINDEX).
+ * Synchronous. */
+int iqlhip_group_online_step(iqlhip_group* group, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                             const int64_t* pointer, const float* row_host, const int64_t* idx_host, int32_t n,
+                             const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
+                             const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
+                             float* act_out_host, void* stream);
 
 /* ---- policy inference ---------------------------------------------------- */
 /* GaussianPolicy.act (algorithms/finetune/iql.py:371-379), DeterministicPolicy.act (:404-413) and the batched policy

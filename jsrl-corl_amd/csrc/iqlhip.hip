@@ -1208,10 +1208,9 @@ extern "C" int iqlhip_get_timing(iqlhip_ctx* c, float out_us[4]) {
 // Wait for the completion word of a synchronous entry point: spin on host-mapped memory (no HIP call: a stream
 // synchronise was measured at 12-17 us of host time AFTER the GPU had finished, profiles/r03_sync_cost.txt); bounded —
 // after 2 s the stream is synchronised the ordinary way, so a lost store cannot hang the caller.
-static int wait_done(iqlhip_ctx* c, unsigned long long val, hipStream_t st) {
+static int wait_word(const unsigned long long* f, unsigned long long val, hipStream_t st) {
   // (acquire loads: the callers read the pinned loss words right behind this — those loads must not move in front of
   //  the flag's)
-  const unsigned long long* f = c->done_pin;
   if (__atomic_load_n(f, __ATOMIC_ACQUIRE) == val) return IQLHIP_OK;
   const double t0 = now_us();
   for (;;) {
@@ -1222,6 +1221,7 @@ static int wait_done(iqlhip_ctx* c, unsigned long long val, hipStream_t st) {
   if (__atomic_load_n(f, __ATOMIC_ACQUIRE) != val) return fail(IQLHIP_EHIP, "the step's completion word was not written");
   return IQLHIP_OK;
 }
+static int wait_done(iqlhip_ctx* c, unsigned long long val, hipStream_t st) { return wait_word(c->done_pin, val, st); }
 
 static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* out_sync, void* stream,
                      bool defer_wait = false);
@@ -2231,6 +2231,13 @@ struct iqlhip_group {
   int last_n = 0;                     // steps of the last call (rows of the ring that are valid)
   hipEvent_t up_done = nullptr;       // the last upload has read blob_pin
   bool up_pending = false;
+  // iqlhip_group_online_step: its own records (a synchronous call — the staging is free again when it returns)
+  //   [GroupRec x k][StepParams x k: act forward][GroupOnlineRec x k][GroupActRec x k][iqlhip_step_scalars x k]
+  char* on_dev = nullptr;
+  char* on_pin = nullptr;
+  size_t on_act_off = 0, on_gather_off = 0, on_fin_off = 0, on_tab_off = 0, on_bytes = 0;
+  unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
+  unsigned long long done_seq = 0;
 };
 
 static int group_check_members(iqlhip_ctx* const* members, int k) {
@@ -2264,6 +2271,9 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   if (g->ring_dev) (void)hipFree(g->ring_dev);
   if (g->ring_pin) (void)hipHostFree(g->ring_pin);
   if (g->up_done) (void)hipEventDestroy(g->up_done);
+  if (g->on_dev) (void)hipFree(g->on_dev);
+  if (g->on_pin) (void)hipHostFree(g->on_pin);
+  if (g->done_pin) (void)hipHostFree(g->done_pin);
   delete g;
   return IQLHIP_OK;
 }
@@ -2288,6 +2298,16 @@ extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_gro
     HIPCHK(hipMemset(g->ring_dev, 0, ring));
     HIPCHK(hipHostMalloc((void**)&g->ring_pin, ring, hipHostMallocDefault));
     HIPCHK(hipEventCreateWithFlags(&g->up_done, hipEventDisableTiming));
+    g->on_act_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
+    g->on_gather_off = g->on_act_off + (size_t)up((int64_t)k * sizeof(StepParams), 256);
+    g->on_fin_off = g->on_gather_off + (size_t)up((int64_t)k * sizeof(GroupOnlineRec), 256);
+    g->on_tab_off = g->on_fin_off + (size_t)up((int64_t)k * sizeof(GroupActRec), 256);
+    g->on_bytes = g->on_tab_off + (size_t)k * sizeof(iqlhip_step_scalars);
+    HIPCHK(hipMalloc((void**)&g->on_dev, g->on_bytes));
+    HIPCHK(hipHostMalloc((void**)&g->on_pin, g->on_bytes, hipHostMallocDefault));
+    memset(g->on_pin, 0, g->on_bytes);
+    HIPCHK(hipHostMalloc((void**)&g->done_pin, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+    memset(g->done_pin, 0, 8 * sizeof(unsigned long long));
     const iqlhip_ctx* c = members[0];
     const void* fwd[8] = {(const void*)iql_fwd_group_kernel<false, false, false>, (const void*)iql_fwd_group_kernel<false, true, false>,
                           (const void*)iql_fwd_group_kernel<true, false, false>,  (const void*)iql_fwd_group_kernel<true, true, false>,
@@ -2297,6 +2317,9 @@ extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_gro
     const void* bwd[4] = {(const void*)iql_bwd_group_kernel<false, false>, (const void*)iql_bwd_group_kernel<false, true>,
                           (const void*)iql_bwd_group_kernel<true, false>,  (const void*)iql_bwd_group_kernel<true, true>};
     for (const void* f : bwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd));
+    const void* act[4] = {(const void*)iql_act_fwd_group_kernel<false, false>, (const void*)iql_act_fwd_group_kernel<false, true>,
+                          (const void*)iql_act_fwd_group_kernel<true, false>,  (const void*)iql_act_fwd_group_kernel<true, true>};
+    for (const void* f : act) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_fwd_solo));
     return IQLHIP_OK;
   };
   rc = setup();
@@ -2348,11 +2371,11 @@ static int group_check_call(iqlhip_group* g, int rows) {
   return IQLHIP_OK;
 }
 
-// Write agent i's record (host side) for a call of n steps on batches of `rows` rows staged at xb.
-static void group_record(iqlhip_group* g, int i, const GroupGeom& q, int rows, int n, const float* xb,
-                         const iqlhip_step_scalars* sc0) {
+// Write agent i's record r (host side) for a call of n steps on batches of `rows` rows staged at xb; sched: the
+// device address of the agent's scalar table.
+static void group_record(iqlhip_group* g, GroupRec& r, int i, const GroupGeom& q, int rows, int n, const float* xb,
+                         const iqlhip_step_scalars* sc0, const iqlhip_step_scalars* sched) {
   iqlhip_ctx* c = g->m[i];
-  GroupRec& r = ((GroupRec*)g->blob_pin)[i];
   memset(&r, 0, sizeof r);
   r.p = make_step(c, rows, sc0->inv_batch);
   r.p.xb = xb;
@@ -2363,7 +2386,7 @@ static void group_record(iqlhip_group* g, int i, const GroupGeom& q, int rows, i
   r.q_mbc = (unsigned)r.p.sc.max_batch | ((unsigned)q.n_chunk << 16);
   r.q_rts = (unsigned)q.n_rt;         // (one-slice backward: no slice or donation word)
   r.u = make_upd(c, sc0, rows, nullptr);
-  r.u.sched = (const iqlhip_step_scalars*)(g->blob_dev + g->tab_off) + (size_t)i * IQLHIP_GROUP_MAX_STEPS;
+  r.u.sched = sched;
   r.u.sched_idx = 0;
   r.u.loss_ring = g->ring_dev + (size_t)i * IQLHIP_GROUP_MAX_STEPS * 4;
   r.u.ring_slot = 0;
@@ -2393,9 +2416,12 @@ static int group_upload(iqlhip_group* g, int n, hipStream_t st) {
   return IQLHIP_OK;
 }
 
-static void group_launch_step(iqlhip_group* g, const GroupGeom& q, int s, hipStream_t st) {
+static const iqlhip_step_scalars* group_sched(const iqlhip_group* g, int i) {
+  return (const iqlhip_step_scalars*)(g->blob_dev + g->tab_off) + (size_t)i * IQLHIP_GROUP_MAX_STEPS;
+}
+
+static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st) {
   const iqlhip_ctx* c = g->m[0];
-  const GroupRec* recs = (const GroupRec*)g->blob_dev;
   const int K = g->k;
   const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K, fmulti = q.fwd_l2 > 0;
   const size_t lds = fwd_lds(c, q.fwd_nb * K);
@@ -2452,12 +2478,12 @@ extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, c
     rc = stage_batch(c, &batches[i], st, &xb);
     if (rc) return rc;
     refresh_shadows(c, st);
-    group_record(g, i, q, rows, 1, xb, &sc[i]);
+    group_record(g, ((GroupRec*)g->blob_pin)[i], i, q, rows, 1, xb, &sc[i], group_sched(g, i));
     ((iqlhip_step_scalars*)(g->blob_pin + g->tab_off))[(size_t)i * IQLHIP_GROUP_MAX_STEPS] = sc[i];
   }
   rc = group_upload(g, 1, st);
   if (rc) return rc;
-  group_launch_step(g, q, 0, st);
+  group_launch_step(g, (const GroupRec*)g->blob_dev, q, 0, st);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
@@ -2487,7 +2513,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
     c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
     refresh_shadows(c, st);
     const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
-    group_record(g, i, q, B, n, c->xb, &tab[0]);
+    group_record(g, ((GroupRec*)g->blob_pin)[i], i, q, B, n, c->xb, &tab[0], group_sched(g, i));
     GroupRec& r = ((GroupRec*)g->blob_pin)[i];
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
     memcpy(g->blob_pin + g->tab_off + (size_t)i * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars), tab,
@@ -2499,7 +2525,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
   const int gather_nb = (int)std::min<int64_t>(((int64_t)B * (c0->row_ld / 4) + 255) / 256, 1024);
   for (int s = 0; s < n; ++s) {
     hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev, s);
-    group_launch_step(g, q, s, st);
+    group_launch_step(g, (const GroupRec*)g->blob_dev, q, s, st);
   }
   HIPCHK(hipGetLastError());
   g->last_n = n;
@@ -2511,4 +2537,115 @@ extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, 
   if (n < 1 || n > g->last_n) return fail(IQLHIP_EINVAL, "n_steps %d outside [1,%d] (steps of the last group call)", n, g->last_n);
   DevGuard guard(g->device);
   return group_losses_out(g, out, n, (hipStream_t)stream);
+}
+
+// One online iteration of every member (iqlhip_online_step for each, include/iqlhip.h) in one set of launches: ring
+// writes + gathers (+ the act states' packing), forward, backward, update with each member's losses landing in its own
+// pinned words, then — members that asked for one — the next action with the updated policy, and one completion word
+// the host spins on.  Everything is checked before any device work and before any counter moves.
+extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                        const int64_t* pointer, const float* row_host, const int64_t* idx_host, int32_t n,
+                                        const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
+                                        const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
+                                        float* act_out_host, void* stream) {
+  if (!g || !rows_dev || !capacity || !pointer || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (act_state_host && (!max_action || !act_seed || !act_out_host))
+    return fail(IQLHIP_EINVAL, "act_state_host without max_action, act_seed or act_out_host");
+  int rc = group_check_call(g, n);
+  if (rc) return rc;
+  const int K = g->k;
+  for (int i = 0; i < K; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
+    if (!rows_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL ring", i);
+    if (((uintptr_t)rows_dev[i]) & 15) return fail(IQLHIP_EINVAL, "member %d: packed rows must be 16-byte aligned", i);
+    if (capacity[i] < 1 || pointer[i] < 0 || pointer[i] >= capacity[i])
+      return fail(IQLHIP_EINVAL, "member %d: ring pointer outside the buffer", i);
+    for (int j = 0; j < i; ++j) {      // (two members writing one ring would race on its rows)
+      const uintptr_t a0 = (uintptr_t)rows_dev[i], a1 = a0 + (uintptr_t)(capacity[i] * ld) * sizeof(float);
+      const uintptr_t b0 = (uintptr_t)rows_dev[j], b1 = b0 + (uintptr_t)(capacity[j] * ld) * sizeof(float);
+      if (a0 < b1 && b0 < a1) return fail(IQLHIP_EINVAL, "members %d and %d share ring rows (one buffer per member)", j, i);
+    }
+    rc = check_host_indices(idx_host + (size_t)i * n, n, capacity[i]);
+    if (rc) return rc;
+  }
+  DevGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  const iqlhip_ctx* c0 = g->m[0];
+  const int S = c0->dims.state_dim, A = c0->dims.action_dim;
+  const bool gauss = c0->dims.policy == IQLHIP_POLICY_GAUSSIAN;
+  const GroupGeom q = group_geom(c0, n, K);
+  GroupRec* recs = (GroupRec*)g->on_pin;
+  StepParams* aps = (StepParams*)(g->on_pin + g->on_act_off);
+  GroupOnlineRec* ons = (GroupOnlineRec*)(g->on_pin + g->on_gather_off);
+  GroupActRec* fins = (GroupActRec*)(g->on_pin + g->on_fin_off);
+  iqlhip_step_scalars* tab = (iqlhip_step_scalars*)(g->on_pin + g->on_tab_off);
+  const iqlhip_step_scalars* tab_dev = (const iqlhip_step_scalars*)(g->on_dev + g->on_tab_off);
+  int n_req = 0;
+  for (int i = 0; i < K; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
+    memcpy(c->on_row_pin, row_host + (size_t)i * ld, (size_t)ld * sizeof(float));
+    memcpy(c->on_idx_pin, idx_host + (size_t)i * n, (size_t)n * sizeof(long long));
+    tab[i] = sc[i];
+    group_record(g, recs[i], i, q, n, 1, c->xb, &sc[i], tab_dev + i);
+    recs[i].u.losses_mirror = c->on_loss_pin;
+    const bool req = act_state_host && (!act_mask || act_mask[i]);
+    GroupOnlineRec& o = ons[i];
+    o.rows = rows_dev[i]; o.row_pin = c->on_row_pin; o.idx_pin = c->on_idx_pin; o.xb = c->xb;
+    o.act_pin = req ? c->on_act_pin : nullptr; o.xb_act = c->xb_act;
+    o.ld = ld; o.pointer = pointer[i]; o.n = n; o.S = S;
+    if (!req) continue;
+    memcpy(c->on_act_pin, act_state_host + (size_t)i * S, (size_t)S * sizeof(float));
+    // the record actor_forward_impl passes for one row
+    StepParams p = make_step(c, 1, 1.f);
+    p.xb = c->xb_act;
+    p.only_inst = 6;
+    p.slot[6] = -1;
+    p.drop_bits = nullptr;
+    p.sc.heads = c->heads_act;
+    p.sc.max_batch = 0;
+    aps[n_req] = p;
+    GroupActRec& f = fins[n_req];
+    const bool noise = act_seed[i] != 0 && gauss;      // (the call counter moves only when noise is drawn, as solo)
+    f.heads = c->heads_act; f.log_std = p.log_std; f.out = c->on_act_pin + IQLHIP_MAX_INPUT;
+    f.max_action = max_action[i]; f.ls_min = c->hyper.log_std_min; f.ls_max = c->hyper.log_std_max;
+    f.seed = noise ? act_seed[i] : 0ull;
+    f.call = noise ? c->act_calls++ : 0ull;
+    ++n_req;
+  }
+  // (a synchronous call: the previous one's upload has been read long ago)
+  HIPCHK(hipMemcpyAsync(g->on_dev, g->on_pin, g->on_bytes, hipMemcpyHostToDevice, st));
+  const int gather_nb = (int)((n * (ld / 4) + 255) / 256);
+  hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st,
+                     (const GroupOnlineRec*)(g->on_dev + g->on_gather_off));
+  for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
+  group_launch_step(g, (const GroupRec*)g->on_dev, q, 0, st);
+  const unsigned long long done_val = ++g->done_seq;
+  if (n_req > 0) {
+    // (bf16: the update has just rewritten the shadows from the new masters — the conversion refresh_shadows makes)
+    const StepParams* ap = (const StepParams*)(g->on_dev + g->on_act_off);
+    const bool bf = c0->precision == 1, dma = c0->w0_lds_k > W0_LDS_MAX_K;
+    const dim3 ag(NSPLIT, n_req);
+    const size_t lds = fwd_lds(c0, NSPLIT);
+    if (bf) { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, true>), ag, dim3(256), lds, st, ap);
+              else hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, false>), ag, dim3(256), lds, st, ap); }
+    else    { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, true>), ag, dim3(256), lds, st, ap);
+              else hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, false>), ag, dim3(256), lds, st, ap); }
+    hipLaunchKernelGGL(iql_actor_finish_group_kernel, dim3(1), dim3(256), 0, st,
+                       (const GroupActRec*)(g->on_dev + g->on_fin_off), n_req, A, g->done_pin, done_val);
+  } else {
+    hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, g->done_pin, done_val);
+  }
+  HIPCHK(hipGetLastError());
+  g->last_n = 1;
+  rc = wait_word(g->done_pin, done_val, st);
+  if (rc) return rc;
+  for (int i = 0; i < K; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    for (int j = 0; j < 3; ++j) out[3 * i + j] = c->on_loss_pin[j];
+    if (act_state_host && (!act_mask || act_mask[i]))
+      memcpy(act_out_host + (size_t)i * A, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
+  }
+  return IQLHIP_OK;
 }

@@ -1323,3 +1323,86 @@ __global__ __launch_bounds__(256) void iql_online_gather_kernel(float* rows, lon
     *(f32x4*)(xb + (long long)r * ld + 4 * c4) = *(const f32x4*)(src + 4 * c4);
   }
 }
+
+// ---------------------------------------------------------------------------
+// Trainer-group online iteration (iqlhip_group_online_step): the kernels above that a solo iqlhip_online_step
+// launches, in group form (grid.y = member), with their arguments in device records the host uploads once per call.
+struct GroupOnlineRec {
+  float* rows;                        // the member's ring (packed rows, stride ld)
+  const float* row_pin;               // its new transition (pinned, host-mapped: the context's on_row_pin)
+  const long long* idx_pin;           // its sampled indices (pinned, host-mapped: on_idx_pin)
+  float* xb;                          // its staging batch
+  const float* act_pin;               // its next-act state (pinned: on_act_pin) or NULL: no action requested
+  float* xb_act;                      // its inference staging
+  long long ld, pointer;
+  int n, S;
+};
+// Per requesting member: the arguments iql_actor_finish_kernel takes (one row).
+struct GroupActRec {
+  const float* heads;                 // the member's heads_act (policy partials of its one row)
+  const float* log_std;               // NULL: deterministic policy
+  float* out;                         // pinned action words (on_act_pin + IQLHIP_MAX_INPUT)
+  float max_action, ls_min, ls_max;
+  unsigned long long seed, call;      // seed 0: the mean action
+};
+
+// iql_online_gather_kernel per member: the ring write, the gather from pinned indices (an index equal to `pointer`
+// reads the new row from the pinned copy), and — members that asked for an action — the packing of the act state into
+// xb_act that iql_pack_states_kernel does for one row (block 0).  Every member has the same n and ld (one grid).
+__global__ __launch_bounds__(256) void iql_online_gather_group_kernel(const GroupOnlineRec* __restrict__ recs) {
+  __shared__ long long s_idx[260];
+  const GroupOnlineRec& g = recs[blockIdx.y];
+  float* rows = g.rows;
+  const float* row_host = g.row_pin;
+  const long long ld = g.ld, pointer = g.pointer;
+  const int n = g.n;
+  const int q = (int)(ld >> 2);
+  const int e0 = (int)blockIdx.x * 256;
+  const int r_first = e0 / q;
+  const int r_last = min((e0 + 255) / q, n - 1);
+  if ((int)threadIdx.x <= r_last - r_first) s_idx[threadIdx.x] = g.idx_pin[r_first + threadIdx.x];
+  if (blockIdx.x == 0) {
+    for (int c4 = (int)threadIdx.x; c4 < q; c4 += 256)
+      *(f32x4*)(rows + pointer * ld + 4 * c4) = *(const f32x4*)(row_host + 4 * c4);
+    if (g.act_pin)
+      for (int c = (int)threadIdx.x; c < (int)ld; c += 256) g.xb_act[c] = (c < g.S) ? g.act_pin[c] : 0.f;
+  }
+  __syncthreads();
+  const int e = e0 + (int)threadIdx.x;
+  if (e < n * q) {
+    const int r = e / q, c4 = e - r * q;
+    const long long i = s_idx[r - r_first];
+    const float* src = (i == pointer) ? row_host : rows + i * ld;
+    *(f32x4*)(g.xb + (long long)r * ld + 4 * c4) = *(const f32x4*)(src + 4 * c4);
+  }
+}
+
+// The policy-inference forward (iql_fwd_kernel<BF16, W0DMA, false, true>: only_inst = 6, blockIdx.x = row tile *
+// NSPLIT + column slice) for the members that asked for an action: grid.y = requesting member, ps[j] its StepParams.
+template <bool BF16, bool W0DMA>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_act_fwd_group_kernel(const StepParams* __restrict__ ps) {
+  constexpr bool MULTI = false, ONE = true;
+  const StepParams& p = ps[blockIdx.y];
+#include "iqlhip_fwd_body.inc"
+}
+
+// iql_actor_finish_kernel for one row of each of n_req members in one block (n_req * A <= 16 * 32), then the call's
+// completion word: every member's losses (written by the update before this launch) and actions are in pinned memory.
+__global__ __launch_bounds__(256) void iql_actor_finish_group_kernel(const GroupActRec* __restrict__ recs, int n_req, int A,
+                                                                     unsigned long long* done_flag,
+                                                                     unsigned long long done_val) {
+  for (int e = (int)threadIdx.x; e < n_req * A; e += 256) {
+    const int j = e / A, d = e - j * A;
+    const GroupActRec& r = recs[j];
+    actor_finish_elem(r.heads, d, A, r.max_action, r.log_std, r.ls_min, r.ls_max, nullptr, 0, r.seed, r.call, r.out, A);
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(done_flag, done_val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The completion word of a group online call without actions: launched behind the update, whose blocks have stored
+// every member's losses in pinned memory by then (stream order).
+__global__ void iql_group_done_kernel(unsigned long long* done_flag, unsigned long long done_val) {
+  if (threadIdx.x == 0) __hip_atomic_store(done_flag, done_val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}

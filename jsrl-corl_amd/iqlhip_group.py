@@ -10,8 +10,15 @@ left it, so its state_dict, checkpoints, act() and later solo calls carry on unc
     group = ImplicitQLearningGroup([trainer_seed0, trainer_seed1, trainer_seed2, trainer_seed3])
     losses = group.train_steps(buffer, n_steps=1000, batch_size=256, seeds=[0, 1, 2, 3])   # [4, 1000, 3]
 
-Not supported (NotImplementedError): data parallelism, actor dropout > 0, bf16 batches of more than 512 rows.
-A group of one runs the solo entry points themselves (the same results; the solo driver is faster for one agent).
+The online fine-tuning loop (algorithms/finetune/iql.py:741-773, jsrl_w_iql.py:512-548) of all members is one call per
+iteration (ImplicitQLearning.online_step for each member, in member order; one ring per member):
+
+    logs, actions = group.online_step(buffers, states, actions, rewards, next_states, dones, 256, act_next=next_states)
+
+Not supported (NotImplementedError): data parallelism, actor dropout > 0, bf16 batches of more than 512 rows.  Groups
+capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
+runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
+driver is faster for one agent).
 """
 from __future__ import annotations
 
@@ -188,3 +195,113 @@ class ImplicitQLearningGroup:
                 losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
             done += k
         return losses
+
+    # ------------------------------------------------------------------ the online loop
+    def online_step(self, buffers, states, actions, rewards, next_states, dones, batch_size: int,
+                    act_next: Optional[Sequence] = None, rngs: Optional[Sequence[np.random.RandomState]] = None):
+        """One iteration of the online loop for every member in ONE library call (ImplicitQLearning.online_step for
+        each, in member order): member k stores its transition (states[k], actions[k], rewards[k], next_states[k],
+        dones[k]) in buffers[k], draws `randint(0, size_k, batch_size)` over its size after the insert — from
+        rngs[k] (a np.random.RandomState), or from the global np.random in member order when rngs is None — and takes
+        one step on those rows.  buffers are K distinct finetune ReplayBuffers on the members' GPU with one row stride.
+        act_next: None, or K entries (a state or None): member k's entry gives actor.act(state) with its UPDATED
+        policy, as the solo act_next does.  Returns one train()-style dict per member; with act_next, (logs, actions)
+        where actions[k] is None for members that asked for none.  Buffers, step counts and schedules move only once
+        the call has succeeded."""
+        K = len(self.trainers)
+        per = {"buffers": buffers, "states": states, "actions": actions, "rewards": rewards,
+               "next_states": next_states, "dones": dones}
+        if act_next is not None:
+            per["act_next"] = act_next
+        if rngs is not None:
+            per["rngs"] = rngs
+        for name, v in per.items():
+            if not isinstance(v, (list, tuple)) or len(v) != K:
+                raise ValueError(f"iqlhip: online_step of a group of {K} needs {name} as a list of {K} entries")
+        bufs = list(buffers)
+        self._check_members()
+        self._check_batch_size(batch_size)
+        if K == 1 and rngs is None:      # a group of one IS the solo call
+            tr = self.trainers[0]
+            an = None if act_next is None else act_next[0]
+            res = tr.online_step(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], batch_size,
+                                 act_next=an)
+            if act_next is None:
+                return [res]
+            if an is None:
+                return [res], [None]
+            return [res[0]], [res[1]]
+        from iqlhip_replay import ReplayBuffer
+        for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
+            t._prepare(batch_size)
+            if not getattr(buf, "_gpu", False) or buf._rows.device != t._dev:
+                raise ValueError(f"iqlhip: online_step needs a ReplayBuffer on the trainer's GPU (member {i})")
+            if type(buf)._index_bound is not ReplayBuffer._index_bound or \
+                    type(buf).add_transition is not ReplayBuffer.add_transition:
+                raise NotImplementedError("online_step needs the finetune ReplayBuffer (the offline flavour has no "
+                                          f"add_transition; member {i})")
+            if any(buf is b or buf._rows.data_ptr() == b._rows.data_ptr() for b in bufs[:i]):
+                raise ValueError(f"iqlhip: member {i} shares a replay buffer with an earlier member (one buffer each)")
+        ld = bufs[0]._ld
+        if any(b._ld != ld for b in bufs):
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        t0 = self.trainers[0]
+        S, A = t0._S, t0._A
+        rows = np.zeros((K, ld), dtype=np.float32)
+        for k in range(K):
+            rows[k, :S] = np.asarray(states[k], dtype=np.float32).reshape(-1)
+            rows[k, S: S + A] = np.asarray(actions[k], dtype=np.float32).reshape(-1)
+            rows[k, S + A: 2 * S + A] = np.asarray(next_states[k], dtype=np.float32).reshape(-1)
+            rows[k, 2 * S + A] = np.float32(rewards[k])
+            rows[k, 2 * S + A + 1] = np.float32(dones[k])
+        want = [k for k in range(K) if act_next is not None and act_next[k] is not None]
+        a_in = a_out = mask = max_a = seeds = None
+        if want:
+            a_in = np.zeros((K, S), dtype=np.float32)
+            for k in want:
+                a_in[k] = np.asarray(act_next[k], dtype=np.float32).reshape(-1)
+            a_out = np.zeros((K, A), dtype=np.float32)
+            mask = np.array([k in want for k in range(K)], dtype=np.int32)
+            max_a = np.array([float(t.actor.max_action) for t in self.trainers], dtype=np.float32)
+            seeds = np.array([t._act_seed() if (t.actor.training and t._gaussian) else 0 for t in self.trainers],
+                             dtype=np.uint64)
+        # (the buffers' and the trainers' counters move only once the library call has succeeded)
+        pointers = [b._pointer for b in bufs]
+        new_sizes = [min(b._size + 1, b._buffer_size) for b in bufs]
+        idx = np.empty((K, batch_size), dtype=np.int64)
+        for k in range(K):               # sample()'s draw over the size AFTER the insert
+            rng = np.random if rngs is None else rngs[k]
+            idx[k] = rng.randint(0, new_sizes[k], size=batch_size)
+        scs, adam_next = (hb.StepScalars * K)(), []
+        for k, t in enumerate(self.trainers):
+            t1 = {g: n + 1 for g, n in t._adam_t.items()}
+            t._fill_scalars(scs[k], t1, t._current_lrs(), 1.0 / batch_size)
+            adam_next.append(t1)
+        out = (C.c_float * (3 * K))()
+        ring_ptrs = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
+        caps = (C.c_int64 * K)(*[b._buffer_size for b in bufs])
+        ptrs = (C.c_int64 * K)(*pointers)
+
+        def addr(a):
+            return None if a is None else a.ctypes.data
+
+        g = self._group()
+        rc = hb.lib().iqlhip_group_online_step(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
+                                               batch_size, scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds),
+                                               addr(a_out), t0._stream())
+        hb.check(rc)
+        logs = []
+        for k, (t, buf) in enumerate(zip(self.trainers, bufs)):
+            buf._writes += 1
+            buf._pointer = (pointers[k] + 1) % buf._buffer_size
+            buf._size = new_sizes[k]
+            t.total_it += 1
+            t._adam_t = adam_next[k]
+            t._advance_schedule(1)
+            t._ts_token = None
+            t._eager_next = None
+            logs.append({"value_loss": float(out[3 * k]), "q_loss": float(out[3 * k + 1]),
+                         "actor_loss": float(out[3 * k + 2])})
+        if act_next is None:
+            return logs
+        return logs, [a_out[k].copy() if k in want else None for k in range(K)]
