@@ -339,6 +339,19 @@ int iqlhip_group_online_step(iqlhip_group* group, float* const* rows_dev, int64_
                              const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
                              const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
                              float* act_out_host, void* stream);
+/* Policy inference for every member of a group in one set of launches.  Member k maps its rows[k] states
+ * (row stride ld_s) to rows[k] actions (row stride ld_a), exactly as iqlhip_actor_forward (seeds[k] == 0: the mean)
+ * or iqlhip_actor_sample (seeds[k] != 0: device N(0,1) noise, member k's act() call counter advances by one) on that
+ * member would, with max_action[k].  rows[k] == 0 skips member k and leaves its counter alone.  rows[k] <=
+ * max(max_batch_k, IQLHIP_ACT_ROWS).  states / actions may be device memory or host-mapped pinned memory.  Eval-mode
+ * forward (no dropout).  Checked before any device work or counter change: NULL arguments, unbound members, row
+ * counts, strides, NULL pointers of members with rows, the group rules, unknown flags.  Asynchronous on `stream`
+ * (successive calls of one group on one stream); flags & IQLHIP_GROUP_ACT_WAIT: returns once every action is written
+ * (the host spins on a completion word instead of synchronising the stream: the form for host-mapped actions). */
+#define IQLHIP_GROUP_ACT_WAIT 1
+int iqlhip_group_actor_forward(iqlhip_group* group, const float* const* states, int64_t ld_s, const int32_t* rows,
+                               const uint64_t* seeds, const float* max_action, float* const* actions, int64_t ld_a,
+                               int32_t flags, void* stream);
 
 /* ---- policy inference ---------------------------------------------------- */
 /* GaussianPolicy.act (algorithms/finetune/iql.py:371-379), DeterministicPolicy.act (:404-413) and the batched policy

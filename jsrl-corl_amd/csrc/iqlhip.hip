@@ -2238,6 +2238,15 @@ struct iqlhip_group {
   size_t on_act_off = 0, on_gather_off = 0, on_fin_off = 0, on_tab_off = 0, on_bytes = 0;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
+  // iqlhip_group_actor_forward: its own records [GroupPackRec x k][StepParams x k][GroupActRowsRec x k], built in
+  // act_host; uploaded from act_pin only when they differ from the last upload (act_last) — an evaluation loop's calls
+  // repeat theirs.  (An asynchronous call: the next upload waits for act_up, this one's, before it rewrites act_pin.)
+  char* act_dev = nullptr;
+  char* act_pin = nullptr;
+  std::vector<char> act_host, act_last;
+  size_t act_fwd_off = 0, act_fin_off = 0, act_bytes = 0;
+  hipEvent_t act_up = nullptr;
+  bool act_pending = false;
 };
 
 static int group_check_members(iqlhip_ctx* const* members, int k) {
@@ -2274,6 +2283,9 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   if (g->on_dev) (void)hipFree(g->on_dev);
   if (g->on_pin) (void)hipHostFree(g->on_pin);
   if (g->done_pin) (void)hipHostFree(g->done_pin);
+  if (g->act_dev) (void)hipFree(g->act_dev);
+  if (g->act_pin) (void)hipHostFree(g->act_pin);
+  if (g->act_up) (void)hipEventDestroy(g->act_up);
   delete g;
   return IQLHIP_OK;
 }
@@ -2308,6 +2320,15 @@ extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_gro
     memset(g->on_pin, 0, g->on_bytes);
     HIPCHK(hipHostMalloc((void**)&g->done_pin, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     memset(g->done_pin, 0, 8 * sizeof(unsigned long long));
+    g->act_fwd_off = (size_t)up((int64_t)k * sizeof(GroupPackRec), 256);
+    g->act_fin_off = g->act_fwd_off + (size_t)up((int64_t)k * sizeof(StepParams), 256);
+    g->act_bytes = g->act_fin_off + (size_t)k * sizeof(GroupActRowsRec);
+    HIPCHK(hipMalloc((void**)&g->act_dev, g->act_bytes));
+    HIPCHK(hipHostMalloc((void**)&g->act_pin, g->act_bytes, hipHostMallocDefault));
+    memset(g->act_pin, 0, g->act_bytes);
+    g->act_host.assign(g->act_bytes, 0);
+    g->act_last.assign(g->act_bytes, 1);     // (differs from any first call's records: the first call uploads)
+    HIPCHK(hipEventCreateWithFlags(&g->act_up, hipEventDisableTiming));
     const iqlhip_ctx* c = members[0];
     const void* fwd[8] = {(const void*)iql_fwd_group_kernel<false, false, false>, (const void*)iql_fwd_group_kernel<false, true, false>,
                           (const void*)iql_fwd_group_kernel<true, false, false>,  (const void*)iql_fwd_group_kernel<true, true, false>,
@@ -2648,4 +2669,97 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
       memcpy(act_out_host + (size_t)i * A, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
   }
   return IQLHIP_OK;
+}
+
+// Policy inference of every member (iqlhip_actor_forward / iqlhip_actor_sample for each, include/iqlhip.h) in one set
+// of launches: the members' states packed into their xb_act, the policy forward (iql_act_fwd_group_kernel, grid.y =
+// requesting member, grid.x = the longest member's row tiles x NSPLIT — a block past a shorter member's rows loads its
+// last row again, clamped, and stores nothing: every store of the body is guarded by row < p.rows), and the finish over
+// each member's rows.  Everything is checked before any device work and before any counter moves.
+extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* states, int64_t ld_s, const int32_t* rows,
+                                          const uint64_t* seeds, const float* max_action, float* const* actions,
+                                          int64_t ld_a, int32_t flags, void* stream) {
+  if (!g || !states || !rows || !seeds || !max_action || !actions) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = group_check_members(g->m, g->k);
+  if (rc) return rc;
+  const int K = g->k;
+  const iqlhip_ctx* c0 = g->m[0];
+  const int S = c0->dims.state_dim, A = c0->dims.action_dim;
+  for (int i = 0; i < K; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    if (!c->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called", i);
+    if (rows[i] < 0 || rows[i] > c->act_cap)
+      return fail(IQLHIP_EINVAL, "member %d: rows %d outside [0, %d]", i, rows[i], c->act_cap);
+    if (rows[i] > 0 && (!states[i] || !actions[i])) return fail(IQLHIP_EINVAL, "member %d: NULL states or actions", i);
+  }
+  if (ld_s < S || ld_a < A) return fail(IQLHIP_EINVAL, "row stride smaller than the row");
+  if (flags & ~IQLHIP_GROUP_ACT_WAIT) return fail(IQLHIP_EINVAL, "unknown flags 0x%x", (unsigned)flags);
+  int n_req = 0, max_rows = 0;
+  for (int i = 0; i < K; ++i) {
+    if (rows[i] > 0) ++n_req;
+    max_rows = std::max(max_rows, (int)rows[i]);
+  }
+  if (n_req == 0) return IQLHIP_OK;
+  DevGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  GroupPackRec* packs = (GroupPackRec*)g->act_host.data();
+  StepParams* ps = (StepParams*)(g->act_host.data() + g->act_fwd_off);
+  GroupActRowsRec* fins = (GroupActRowsRec*)(g->act_host.data() + g->act_fin_off);
+  int j = 0;
+  for (int i = 0; i < K; ++i) {
+    if (rows[i] == 0) continue;        // (no launch, no counter: the solo caller makes no call for no rows)
+    iqlhip_ctx* c = g->m[i];
+    const int n = rows[i];
+    GroupPackRec& pk = packs[j];
+    pk.xb = c->xb_act; pk.s = states[i]; pk.ld_s = (long long)ld_s; pk.ld = (int)c->row_ld; pk.S = S; pk.n = n;
+    // the record actor_forward_impl passes
+    StepParams p = make_step(c, n, 1.f / (float)n);
+    p.xb = c->xb_act;
+    p.only_inst = 6;
+    p.slot[6] = -1;
+    p.drop_bits = nullptr;
+    p.sc.heads = c->heads_act;
+    p.sc.max_batch = 0;
+    ps[j] = p;
+    GroupActRowsRec& f = fins[j];
+    f.heads = c->heads_act; f.log_std = p.log_std; f.out = actions[i]; f.ld_out = (long long)ld_a; f.n = n; f.A = A;
+    f.max_action = max_action[i]; f.ls_min = c->hyper.log_std_min; f.ls_max = c->hyper.log_std_max;
+    f.seed = seeds[i];
+    f.call = seeds[i] != 0 ? c->act_calls++ : 0ull;      // (iqlhip_actor_sample: one call number per call)
+    ++j;
+  }
+  if (memcmp(g->act_host.data(), g->act_last.data(), g->act_bytes) != 0) {
+    if (g->act_pending) HIPCHK(hipEventSynchronize(g->act_up));    // the previous upload has read act_pin
+    g->act_pending = false;
+    memcpy(g->act_pin, g->act_host.data(), g->act_bytes);
+    HIPCHK(hipMemcpyAsync(g->act_dev, g->act_pin, g->act_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(g->act_up, st));
+    g->act_pending = true;
+    g->act_last = g->act_host;
+  }
+  const int pack_nb = (int)std::min<int64_t>(((int64_t)max_rows * c0->row_ld + 255) / 256, 1024);
+  hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_req), dim3(256), 0, st, (const GroupPackRec*)g->act_dev);
+  for (int i = 0; i < K; ++i)
+    if (rows[i] > 0) refresh_shadows(g->m[i], st);
+  const StepParams* ap = (const StepParams*)(g->act_dev + g->act_fwd_off);
+  const bool bf = c0->precision == 1, dma = c0->w0_lds_k > W0_LDS_MAX_K;
+  const int nbx = (max_rows + RT_ROWS - 1) / RT_ROWS * NSPLIT;
+  const dim3 ag(nbx, n_req);
+  const size_t lds = fwd_lds(c0, nbx * n_req);
+  if (bf) { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, true>), ag, dim3(256), lds, st, ap);
+            else hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, false>), ag, dim3(256), lds, st, ap); }
+  else    { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, true>), ag, dim3(256), lds, st, ap);
+            else hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, false>), ag, dim3(256), lds, st, ap); }
+  hipLaunchKernelGGL(iql_actor_finish_rows_group_kernel, dim3((max_rows * A + 255) / 256, n_req), dim3(256), 0, st,
+                     (const GroupActRowsRec*)(g->act_dev + g->act_fin_off));
+  if (!(flags & IQLHIP_GROUP_ACT_WAIT)) {
+    HIPCHK(hipGetLastError());
+    return IQLHIP_OK;
+  }
+  // synchronous: a completion word behind the finish (stream order: every action is stored by then), the host spins
+  // on it instead of synchronising the stream
+  const unsigned long long done_val = ++g->done_seq;
+  hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, g->done_pin, done_val);
+  HIPCHK(hipGetLastError());
+  return wait_word(g->done_pin, done_val, st);
 }

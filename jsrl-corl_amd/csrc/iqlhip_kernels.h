@@ -1406,3 +1406,43 @@ __global__ __launch_bounds__(256) void iql_actor_finish_group_kernel(const Group
 __global__ void iql_group_done_kernel(unsigned long long* done_flag, unsigned long long done_val) {
   if (threadIdx.x == 0) __hip_atomic_store(done_flag, done_val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// ---------------------------------------------------------------------------
+// Trainer-group policy inference (iqlhip_group_actor_forward): iqlhip_actor_forward / iqlhip_actor_sample of every
+// requesting member in one set of launches — pack, iql_act_fwd_group_kernel, finish — with grid.y = requesting member
+// and each member's arguments in a device record the host uploads once per call.
+struct GroupPackRec {                 // iql_pack_states_kernel's arguments
+  float* xb;                          // the member's xb_act
+  const float* s;                     // its states (device or host-mapped memory)
+  long long ld_s;
+  int ld, S, n;
+};
+struct GroupActRowsRec {              // iql_actor_finish_kernel's arguments (no caller noise: seed or the mean)
+  const float* heads;                 // the member's heads_act
+  const float* log_std;               // NULL: deterministic policy
+  float* out;                         // its actions (device or host-mapped memory), row stride ld_out
+  long long ld_out;
+  int n, A;
+  float max_action, ls_min, ls_max;
+  unsigned long long seed, call;      // seed 0: the mean action
+};
+
+// iql_pack_states_kernel per member (grid.y): grid.x strides over the longest member's n * ld elements.
+__global__ __launch_bounds__(256) void iql_pack_states_group_kernel(const GroupPackRec* __restrict__ recs) {
+  const GroupPackRec& r = recs[blockIdx.y];
+  const int ld = r.ld, S = r.S, total = r.n * ld;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    const int i = e / ld;
+    const int c = e - i * ld;
+    r.xb[e] = (c < S) ? r.s[i * r.ld_s + c] : 0.f;
+  }
+}
+
+// iql_actor_finish_kernel per member (grid.y) over its n rows: element e = row * A + d, numbered as there, so the
+// device noise of (seed, call) is the solo call's draw element for element.
+__global__ __launch_bounds__(256) void iql_actor_finish_rows_group_kernel(const GroupActRowsRec* __restrict__ recs) {
+  const GroupActRowsRec& r = recs[blockIdx.y];
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < r.n * r.A)
+    actor_finish_elem(r.heads, e, r.A, r.max_action, r.log_std, r.ls_min, r.ls_max, nullptr, 0, r.seed, r.call, r.out, r.ld_out);
+}

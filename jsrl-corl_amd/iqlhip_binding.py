@@ -18,6 +18,7 @@ IQLHIP_ACT_ROWS = 4096      # rows per iqlhip_actor_forward call (include/iqlhip
 IQLHIP_MAX_WORLD = 8
 IQLHIP_GRAPH_STEPS = 64
 IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
+IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the actions are written
 IQLHIP_GROUP_MAX_STEPS = 1024  # steps per iqlhip_group_train_steps call
 IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
@@ -140,6 +141,9 @@ SYMBOLS = [
                                            C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int32,
                                            C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("iqlhip_group_actor_forward", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_void_p),
+                                             C.c_int64, C.c_int32, C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

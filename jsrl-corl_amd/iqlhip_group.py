@@ -15,6 +15,10 @@ iteration (ImplicitQLearning.online_step for each member, in member order; one r
 
     logs, actions = group.online_step(buffers, states, actions, rewards, next_states, dones, 256, act_next=next_states)
 
+Policy inference of all members is one call too (actor.act / ImplicitQLearning.actor_forward for each, in member
+order): `group.act(states)` for one state per member (lockstep evaluation: iqlhip_hostutil.eval_actors),
+`group.actor_forward(states)` for batches.
+
 Not supported (NotImplementedError): data parallelism, actor dropout > 0, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
@@ -26,6 +30,7 @@ import ctypes as C
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
+import torch
 
 import iqlhip_binding as hb
 from iqlhip_trainer import K_MAX, ImplicitQLearning
@@ -42,6 +47,7 @@ class ImplicitQLearningGroup:
         self._check_members()
         self._g = None
         self._ctxs = None
+        self._act_bufs = None
 
     # ------------------------------------------------------------------ validation (no library call)
     def _check_members(self) -> None:
@@ -305,3 +311,76 @@ class ImplicitQLearningGroup:
         if act_next is None:
             return logs
         return logs, [a_out[k].copy() if k in want else None for k in range(K)]
+
+    # ------------------------------------------------------------------ policy inference
+    def _actor_call(self, rows: Sequence[int], in_ptrs, ld_s: int, out_ptrs, ld_a: int, seeds, max_action,
+                    flags: int = 0) -> None:
+        K = len(self.trainers)
+        hb.check(hb.lib().iqlhip_group_actor_forward(self._group(), (C.c_void_p * K)(*in_ptrs), ld_s,
+                                                     (C.c_int32 * K)(*rows), (C.c_uint64 * K)(*seeds),
+                                                     (C.c_float * K)(*max_action), (C.c_void_p * K)(*out_ptrs), ld_a,
+                                                     flags, self.trainers[0]._stream()))
+
+    def act(self, states: Sequence) -> List[Optional[np.ndarray]]:
+        """actor.act(states[k], "cuda") of every member with a state (None: no action), in ONE library call and one
+        wait (a completion word the host spins on): member k samples iff its actor is in training mode and its
+        policy is Gaussian, as actor.act decides.  Returns K actions (np.float32[A], or None) — bit for bit,
+        random-stream counters included, what the K solo calls in member order return."""
+        K = len(self.trainers)
+        if not isinstance(states, (list, tuple)) or len(states) != K:
+            raise ValueError(f"iqlhip: act of a group of {K} needs states as a list of {K} entries")
+        self._check_members()
+        if K == 1:      # a group of one IS the solo call
+            t = self.trainers[0]
+            if states[0] is None:
+                return [None]
+            return [t.act_one(states[0], float(t.actor.max_action), sample=t.actor.training)]
+        t0 = self.trainers[0]
+        S, A = t0._S, t0._A
+        if self._act_bufs is None:
+            h_in = torch.empty((K, S), dtype=torch.float32).pin_memory()
+            h_out = torch.empty((K, A), dtype=torch.float32).pin_memory()
+            self._act_bufs = (h_in, h_out, h_in.numpy(), h_out.numpy())
+        h_in, h_out, in_np, out_np = self._act_bufs
+        want = [s is not None for s in states]
+        for k in range(K):
+            if want[k]:
+                in_np[k, :] = np.asarray(states[k], dtype=np.float32).reshape(-1)
+        seeds = [t._act_seed() if (w and t.actor.training and t._gaussian) else 0 for t, w in zip(self.trainers, want)]
+        base_in, base_out = h_in.data_ptr(), h_out.data_ptr()
+        self._actor_call([int(w) for w in want], [base_in + 4 * S * k for k in range(K)], S,
+                         [base_out + 4 * A * k for k in range(K)], A, seeds,
+                         [float(t.actor.max_action) for t in self.trainers], flags=hb.IQLHIP_GROUP_ACT_WAIT)
+        return [out_np[k].copy() if want[k] else None for k in range(K)]
+
+    def actor_forward(self, states: Sequence[torch.Tensor], sample: bool = False,
+                      max_action: Optional[float] = None) -> List[torch.Tensor]:
+        """ImplicitQLearning.actor_forward(states[k], sample, max_action) of every member, one library call per
+        chunk: states[k] is a [n_k, S] tensor (n_k may differ, and may be 0); returns K device tensors [n_k, A], bit
+        for bit the solo results.  Inputs above a member's row cap are split as the solo method splits them, so each
+        member's random-stream counter moves as it would alone."""
+        K = len(self.trainers)
+        if not isinstance(states, (list, tuple)) or len(states) != K:
+            raise ValueError(f"iqlhip: actor_forward of a group of {K} needs states as a list of {K} tensors")
+        self._check_members()
+        if K == 1:
+            return [self.trainers[0].actor_forward(states[0], sample=sample, max_action=max_action)]
+        t0 = self.trainers[0]
+        S, A = t0._S, t0._A
+        xs = [t._as_dev(x).reshape(-1, S) for t, x in zip(self.trainers, states)]
+        outs = [torch.empty((x.shape[0], A), dtype=torch.float32, device=t._dev) for t, x in zip(self.trainers, xs)]
+        caps = [max(t._max_batch, hb.IQLHIP_ACT_ROWS) for t in self.trainers]
+        mas = [float(t.max_action if max_action is None else max_action) for t in self.trainers]
+        n_calls = max([-(-x.shape[0] // c) for x, c in zip(xs, caps)] + [0])
+        for j in range(n_calls):
+            rows, ins, ptrs, seeds = [], [], [], []
+            for t, x, out, cap in zip(self.trainers, xs, outs, caps):
+                r0 = j * cap
+                r1 = min(x.shape[0], r0 + cap)
+                n = max(0, r1 - r0)
+                rows.append(n)
+                ins.append(x[r0:r1].data_ptr() if n else None)
+                ptrs.append(out[r0:r1].data_ptr() if n else None)
+                seeds.append(t._act_seed() if (n and sample and t._gaussian) else 0)
+            self._actor_call(rows, ins, S, ptrs, A, seeds, mas)
+        return outs

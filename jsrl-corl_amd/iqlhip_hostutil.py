@@ -9,7 +9,7 @@ from __future__ import annotations
 import os
 import random
 import uuid
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -109,6 +109,74 @@ def eval_actor(env, actor: nn.Module, device: str, n_episodes: int, seed: int) -
         returns.append(total)
     actor.train()
     return np.asarray(returns), np.mean(successes)
+
+
+def _group_for(actors, device):
+    """The trainer group that can act for `actors` on `device` (their owning trainers, two or more, distinct, a valid
+    GPU group), else None.  Valid means the library accepts the group too: its rules are checked on the contexts, e.g.
+    a member whose last training step ran with actor dropout keeps that dropout rate in its context and is refused
+    even while its actor is in eval mode."""
+    if len(actors) < 2:
+        return None
+    from iqlhip_group import ImplicitQLearningGroup
+    from iqlhip_networks import _hip_owner
+    owners = [_hip_owner(a, device) for a in actors]
+    if any(o is None or o.actor is not a for o, a in zip(owners, actors)):
+        return None
+    try:
+        group = ImplicitQLearningGroup(owners)
+        group._group()          # the library group now, so that its refusal selects the per-actor path
+    except (ValueError, RuntimeError, NotImplementedError):
+        return None
+    return group
+
+
+@torch.no_grad()
+def eval_actors(envs, actors, device: str, n_episodes: int, seeds) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """eval_actor(envs[k], actors[k], device, n_episodes, seeds[k]) for every k, in lockstep: each round steps every
+    member still inside its episodes, with one group act() for all of them when the actors' trainers form a GPU
+    group (else — and for a round with one member left — per-actor act() calls in member order: the same results).  Each env sees exactly eval_actor's call
+    sequence (seed, reset, step, ...); a member whose episodes are done drops out of later rounds."""
+    envs, actors, seeds = list(envs), list(actors), list(seeds)
+    K = len(actors)
+    if len(envs) != K or len(seeds) != K:
+        raise ValueError(f"eval_actors: {len(envs)} envs, {K} actors and {len(seeds)} seeds (one each)")
+    for env, seed in zip(envs, seeds):
+        env.seed(seed)
+    for a in actors:
+        a.eval()
+    group = _group_for(actors, device)
+    returns = [[] for _ in range(K)]
+    successes = [[] for _ in range(K)]
+    state, total, reached = [None] * K, [0.0] * K, [False] * K
+    live = [k for k in range(K) if n_episodes > 0]
+    for k in live:
+        state[k] = envs[k].reset()
+    try:
+        while live:
+            if group is not None and len(live) > 1:
+                acts = group.act([state[k] if k in live else None for k in range(K)])
+            else:
+                acts = [actors[k].act(state[k], device) if k in live else None for k in range(K)]
+            still = []
+            for k in live:
+                state[k], reward, done, infos = envs[k].step(acts[k])
+                total[k] += reward
+                reached[k] = reached[k] or is_goal_reached(reward, infos)
+                if done:
+                    successes[k].append(float(reached[k]))
+                    returns[k].append(total[k])
+                    if len(returns[k]) == n_episodes:
+                        continue
+                    state[k], total[k], reached[k] = envs[k].reset(), 0.0, False
+                still.append(k)
+            live = still
+    finally:
+        if group is not None:
+            group._release()
+    for a in actors:
+        a.train()
+    return [(np.asarray(returns[k]), np.mean(successes[k])) for k in range(K)]
 
 
 def return_reward_range(dataset: Dict, max_episode_steps: int) -> Tuple[float, float]:

@@ -72,3 +72,8 @@ class ImplicitQLearning(_tr.ImplicitQLearning):
 def eval_actor(env, actor: nn.Module, device: str, n_episodes: int, seed: int) -> np.ndarray:
     returns, _ = _host.eval_actor(env, actor, device, n_episodes, seed)
     return returns
+
+
+def eval_actors(envs, actors, device: str, n_episodes: int, seeds):
+    """eval_actor for every member in lockstep (iqlhip_hostutil.eval_actors): the episode returns of each."""
+    return [returns for returns, _ in _host.eval_actors(envs, actors, device, n_episodes, seeds)]
