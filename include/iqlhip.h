@@ -303,14 +303,25 @@ int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed
  * Adam state, target nets, scratch, scalars and batches; after a group call every member is exactly where the same
  * steps run alone (iqlhip_step / iqlhip_train_steps) would have left it, bit for bit.
  * Members: 1..IQLHIP_MAX_GROUP distinct contexts on one device with equal state / action dims, policy kind and
- * precision; no data-parallel exchange, no actor dropout (IQLHIP_EUNSUPPORTED).  Batches: one size for all members,
+ * precision; no data-parallel exchange; actor dropout (iqlhip_set_dropout with p > 0) only in a group created with
+ * IQLHIP_GROUP_DROPOUT (IQLHIP_EUNSUPPORTED otherwise).  Batches: one size for all members,
  * small-batch kernels only (bf16: at most 512 rows).  A group call invalidates each member's train_steps continuation
  * (the staging buffer is overwritten).  The members must outlive the group; a context that is destroyed or re-created
  * means a new group. */
 #define IQLHIP_MAX_GROUP 16
 #define IQLHIP_GROUP_MAX_STEPS 1024   /* steps per iqlhip_group_train_steps call */
 typedef struct iqlhip_group iqlhip_group;
+/* iqlhip_group_create_flags with flags = 0. */
 int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out);
+/* flags & IQLHIP_GROUP_DROPOUT: members may train with actor dropout, each with its own rate (0 included), seed and
+ * stream position.  Every training call draws member k's keep-bits exactly as its solo call would — key drop_seed,
+ * the member's threshold, position drop_step — in the group's own launches, and moves the position as the solo call
+ * does: iqlhip_group_step / iqlhip_group_online_step by one for a member that draws, iqlhip_group_train_steps by n
+ * for every member.  Masks written by iqlhip_debug_write_masks are kept (no draw for that member).  The inference
+ * forwards stay eval-mode.  Unknown flag bits: IQLHIP_EINVAL, checked before any member is looked at; *out is
+ * written on success only. */
+#define IQLHIP_GROUP_DROPOUT 1
+int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int32_t flags, iqlhip_group** out);
 int iqlhip_group_destroy(iqlhip_group* group);
 /* One step per member on caller-given batches (batches[k], sc[k]); out[3k] (value, q, actor per member) or NULL.
  * With out != NULL the call synchronises `stream`. */

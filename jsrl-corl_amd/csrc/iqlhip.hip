@@ -2219,23 +2219,28 @@ extern "C" int iqlhip_debug_read(iqlhip_ctx* c, const char* name, float* host_ou
 // Trainer groups (include/iqlhip.h): K contexts of identical dims stepped together.  Every launch of a group step covers
 // all K agents (grid.y = agent); each agent's launch arguments are a device-resident GroupRec (iqlhip_kernels.h) the
 // host writes once per call, together with the agents' scalar tables, in ONE host-to-device copy from pinned memory.
+// A group created with IQLHIP_GROUP_DROPOUT also uploads one GroupDropRec per member in that copy: the members' actor
+// dropout keep-bits are drawn by the group's own launches, each from the member's own stream (seed, rate, position).
 struct iqlhip_group {
   int k = 0;
   int device = 0;
+  int flags = 0;                      // IQLHIP_GROUP_*
   iqlhip_ctx* m[IQLHIP_MAX_GROUP] = {};
-  char* blob_dev = nullptr;           // [GroupRec x k | pad][scalars: k x IQLHIP_GROUP_MAX_STEPS]
+  // [GroupRec x k | pad][IQLHIP_GROUP_DROPOUT: GroupDropRec x k | pad][scalars: k x IQLHIP_GROUP_MAX_STEPS]
+  char* blob_dev = nullptr;
   char* blob_pin = nullptr;           // pinned staging of the same bytes
-  size_t tab_off = 0, blob_bytes = 0;
+  size_t drop_off = 0, tab_off = 0, blob_bytes = 0;
   float* ring_dev = nullptr;          // [k][IQLHIP_GROUP_MAX_STEPS][4] losses of the last call
   float* ring_pin = nullptr;
   int last_n = 0;                     // steps of the last call (rows of the ring that are valid)
   hipEvent_t up_done = nullptr;       // the last upload has read blob_pin
   bool up_pending = false;
   // iqlhip_group_online_step: its own records (a synchronous call — the staging is free again when it returns)
-  //   [GroupRec x k][StepParams x k: act forward][GroupOnlineRec x k][GroupActRec x k][iqlhip_step_scalars x k]
+  //   [GroupRec x k][StepParams x k: act forward][GroupOnlineRec x k][GroupActRec x k]
+  //   [IQLHIP_GROUP_DROPOUT: GroupDropRec x k][iqlhip_step_scalars x k]
   char* on_dev = nullptr;
   char* on_pin = nullptr;
-  size_t on_act_off = 0, on_gather_off = 0, on_fin_off = 0, on_tab_off = 0, on_bytes = 0;
+  size_t on_act_off = 0, on_gather_off = 0, on_fin_off = 0, on_drop_off = 0, on_tab_off = 0, on_bytes = 0;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
   // iqlhip_group_actor_forward: its own records [GroupPackRec x k][StepParams x k][GroupActRowsRec x k], built in
@@ -2249,7 +2254,7 @@ struct iqlhip_group {
   bool act_pending = false;
 };
 
-static int group_check_members(iqlhip_ctx* const* members, int k) {
+static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
   if (!members) return fail(IQLHIP_EINVAL, "members is NULL");
   if (k < 1 || k > IQLHIP_MAX_GROUP) return fail(IQLHIP_EINVAL, "group size %d outside [1,%d]", k, IQLHIP_MAX_GROUP);
   for (int i = 0; i < k; ++i) {
@@ -2266,7 +2271,8 @@ static int group_check_members(iqlhip_ctx* const* members, int k) {
     if (c->precision != a->precision) return fail(IQLHIP_EINVAL, "member %d has another precision than member 0", i);
     if (c->xch_mode != IQLHIP_XCH_NONE || c->world > 1)
       return fail(IQLHIP_EUNSUPPORTED, "member %d has data parallelism enabled (not supported in a group)", i);
-    if (c->drop_p > 0.f) return fail(IQLHIP_EUNSUPPORTED, "member %d uses actor dropout (not supported in a group)", i);
+    if (c->drop_p > 0.f && !(flags & IQLHIP_GROUP_DROPOUT))
+      return fail(IQLHIP_EUNSUPPORTED, "member %d uses actor dropout (not supported in a group)", i);
   }
   return IQLHIP_OK;
 }
@@ -2290,17 +2296,21 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   return IQLHIP_OK;
 }
 
-extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out) {
+extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int32_t flags, iqlhip_group** out) {
   if (!out) return fail(IQLHIP_EINVAL, "out is NULL");
-  int rc = group_check_members(members, k);
+  if (flags & ~IQLHIP_GROUP_DROPOUT) return fail(IQLHIP_EINVAL, "unknown flags 0x%x", (unsigned)flags);
+  int rc = group_check_members(members, k, flags);
   if (rc) return rc;
   iqlhip_group* g = new iqlhip_group();
   g->k = k;
+  g->flags = flags;
   g->device = members[0]->device;
   for (int i = 0; i < k; ++i) g->m[i] = members[i];
   DevGuard guard(g->device);
   auto setup = [&]() -> int {
-    g->tab_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
+    const bool dropout = (flags & IQLHIP_GROUP_DROPOUT) != 0;       // (without it: the layouts of a plain group)
+    g->drop_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
+    g->tab_off = g->drop_off + (dropout ? (size_t)up((int64_t)k * sizeof(GroupDropRec), 256) : 0);
     g->blob_bytes = g->tab_off + (size_t)k * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars);
     HIPCHK(hipMalloc((void**)&g->blob_dev, g->blob_bytes));
     HIPCHK(hipHostMalloc((void**)&g->blob_pin, g->blob_bytes, hipHostMallocDefault));
@@ -2313,7 +2323,8 @@ extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_gro
     g->on_act_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
     g->on_gather_off = g->on_act_off + (size_t)up((int64_t)k * sizeof(StepParams), 256);
     g->on_fin_off = g->on_gather_off + (size_t)up((int64_t)k * sizeof(GroupOnlineRec), 256);
-    g->on_tab_off = g->on_fin_off + (size_t)up((int64_t)k * sizeof(GroupActRec), 256);
+    g->on_drop_off = g->on_fin_off + (size_t)up((int64_t)k * sizeof(GroupActRec), 256);
+    g->on_tab_off = g->on_drop_off + (dropout ? (size_t)up((int64_t)k * sizeof(GroupDropRec), 256) : 0);
     g->on_bytes = g->on_tab_off + (size_t)k * sizeof(iqlhip_step_scalars);
     HIPCHK(hipMalloc((void**)&g->on_dev, g->on_bytes));
     HIPCHK(hipHostMalloc((void**)&g->on_pin, g->on_bytes, hipHostMallocDefault));
@@ -2354,6 +2365,10 @@ extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_gro
   return IQLHIP_OK;
 }
 
+extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out) {
+  return iqlhip_group_create_flags(members, k, 0, out);
+}
+
 // Geometry of a group step: the forward's slices per block chosen for the whole group grid (the single-agent rule applied
 // to K x the row tiles); the backward's (b) blocks take one slice each (iql_bwd_group_kernel).  Results do not depend on
 // either (bit-identical for every slice count).
@@ -2379,7 +2394,7 @@ static GroupGeom group_geom(const iqlhip_ctx* c, int rows, int k) {
 // Checks shared by both step entry points (before any device work).
 static int group_check_call(iqlhip_group* g, int rows) {
   if (!g) return fail(IQLHIP_EINVAL, "NULL group");
-  int rc = group_check_members(g->m, g->k);
+  int rc = group_check_members(g->m, g->k, g->flags);
   if (rc) return rc;
   for (int i = 0; i < g->k; ++i) {
     const iqlhip_ctx* c = g->m[i];
@@ -2418,6 +2433,45 @@ static void group_record(iqlhip_group* g, GroupRec& r, int i, const GroupGeom& q
   r.n_steps = n;
   r.xb = (float*)xb;
   r.B = rows;
+}
+
+// Actor dropout (IQLHIP_GROUP_DROPOUT): does member c draw keep-bits in a group call?  (a rate of 0 reads none;
+// injected masks stay as they were written)
+static bool group_draws(const iqlhip_ctx* c) { return c->drop_p > 0.f && !c->drop_inject; }
+
+// A drawing member's record (host side) for a call on batches of `rows` rows (<= max_batch: group_check_call) that
+// starts at the member's current stream position.  (GroupRec::p already carries drop_bits — parity 0 — and drop_scale
+// of a member with a rate: make_step.)
+static GroupDropRec group_drop_record(const iqlhip_ctx* c, int rows) {
+  GroupDropRec d;
+  memset(&d, 0, sizeof d);
+  d.bits = c->drop_bits;
+  d.n_rows = rows;
+  d.max_batch = c->dims.max_batch;
+  d.thresh = drop_thresh(c->drop_p);
+  d.active = 1;
+  d.seed = c->drop_seed;
+  d.step0 = c->drop_step;
+  return d;
+}
+
+// One-step calls (iqlhip_group_step, iqlhip_group_online_step): the drawing members' records packed at the front of
+// `d` (iql_dropmask_group_kernel's grid.y).  Returns their number.
+static int group_drop_records_packed(const iqlhip_group* g, GroupDropRec* d, int rows) {
+  int n = 0;
+  if (!(g->flags & IQLHIP_GROUP_DROPOUT)) return 0;
+  for (int i = 0; i < g->k; ++i)
+    if (group_draws(g->m[i])) d[n++] = group_drop_record(g->m[i], rows);
+  return n;
+}
+
+// ... their draw at drop_step (one launch for all of them, where the solo steps launch iql_dropmask_kernel each), and
+// drop_step += 1 as the solo step's.  `drops`: the device copy of the packed records.
+static void group_launch_dropmask(iqlhip_group* g, const GroupDropRec* drops, int n_draw, int rows, hipStream_t st) {
+  if (n_draw == 0) return;
+  hipLaunchKernelGGL(iql_dropmask_group_kernel, dim3((2 * rows * 8 + 255) / 256, n_draw), dim3(256), 0, st, drops);
+  for (int i = 0; i < g->k; ++i)
+    if (group_draws(g->m[i])) g->m[i]->drop_step += 1;
 }
 
 // Wait until the previous upload has read the pinned staging (normally long done: the host builds the next call's
@@ -2502,8 +2556,10 @@ extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, c
     group_record(g, ((GroupRec*)g->blob_pin)[i], i, q, rows, 1, xb, &sc[i], group_sched(g, i));
     ((iqlhip_step_scalars*)(g->blob_pin + g->tab_off))[(size_t)i * IQLHIP_GROUP_MAX_STEPS] = sc[i];
   }
+  const int n_draw = group_drop_records_packed(g, (GroupDropRec*)(g->blob_pin + g->drop_off), rows);
   rc = group_upload(g, 1, st);
   if (rc) return rc;
+  group_launch_dropmask(g, (const GroupDropRec*)(g->blob_dev + g->drop_off), n_draw, rows, st);
   group_launch_step(g, (const GroupRec*)g->blob_dev, q, 0, st);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
@@ -2540,14 +2596,32 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
     memcpy(g->blob_pin + g->tab_off + (size_t)i * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars), tab,
            (size_t)n * sizeof(iqlhip_step_scalars));
   }
+  // actor dropout: one record per member (indexed like the GroupRecs; active = the member draws), step s at drop_step + s
+  bool draws = false;
+  if (g->flags & IQLHIP_GROUP_DROPOUT) {
+    GroupDropRec* d = (GroupDropRec*)(g->blob_pin + g->drop_off);
+    for (int i = 0; i < g->k; ++i) {
+      d[i] = group_drop_record(g->m[i], B);
+      d[i].active = group_draws(g->m[i]) ? 1 : 0;
+      draws = draws || d[i].active;
+    }
+  }
   rc = group_upload(g, n, st);
   if (rc) return rc;
   const iqlhip_ctx* c0 = g->m[0];
   const int gather_nb = (int)std::min<int64_t>(((int64_t)B * (c0->row_ld / 4) + 255) / 256, 1024);
+  // (a grid with a thread per gathered float4 and per keep-bit word: the words come from its far end)
+  const int drop_nb = gather_nb + (2 * B * 8 + 255) / 256;
   for (int s = 0; s < n; ++s) {
-    hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev, s);
+    if (draws)
+      hipLaunchKernelGGL(iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev,
+                         (const GroupDropRec*)(g->blob_dev + g->drop_off), s);
+    else
+      hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev, s);
     group_launch_step(g, (const GroupRec*)g->blob_dev, q, s, st);
   }
+  if (g->flags & IQLHIP_GROUP_DROPOUT)      // (iqlhip_train_steps moves every context's position, whatever its rate)
+    for (int i = 0; i < g->k; ++i) g->m[i]->drop_step += (unsigned long long)n;
   HIPCHK(hipGetLastError());
   g->last_n = n;
   return IQLHIP_OK;
@@ -2635,12 +2709,14 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
     f.call = noise ? c->act_calls++ : 0ull;
     ++n_req;
   }
+  const int n_draw = group_drop_records_packed(g, (GroupDropRec*)(g->on_pin + g->on_drop_off), n);
   // (a synchronous call: the previous one's upload has been read long ago)
   HIPCHK(hipMemcpyAsync(g->on_dev, g->on_pin, g->on_bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((n * (ld / 4) + 255) / 256);
   hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st,
                      (const GroupOnlineRec*)(g->on_dev + g->on_gather_off));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
+  group_launch_dropmask(g, (const GroupDropRec*)(g->on_dev + g->on_drop_off), n_draw, n, st);
   group_launch_step(g, (const GroupRec*)g->on_dev, q, 0, st);
   const unsigned long long done_val = ++g->done_seq;
   if (n_req > 0) {
@@ -2680,7 +2756,7 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
                                           const uint64_t* seeds, const float* max_action, float* const* actions,
                                           int64_t ld_a, int32_t flags, void* stream) {
   if (!g || !states || !rows || !seeds || !max_action || !actions) return fail(IQLHIP_EINVAL, "NULL argument");
-  int rc = group_check_members(g->m, g->k);
+  int rc = group_check_members(g->m, g->k, g->flags);
   if (rc) return rc;
   const int K = g->k;
   const iqlhip_ctx* c0 = g->m[0];

@@ -1074,6 +1074,48 @@ __global__ __launch_bounds__(256) void iql_gather_group_kernel(const GroupRec* _
                     (unsigned long long)r.size, (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
 }
 
+// Actor dropout in a group (IQLHIP_GROUP_DROPOUT): one record per member, an array of its own next to the GroupRecs.
+// A member's keep-bits are the ones its solo calls draw — dropmask_words under (seed, step) with the member's
+// threshold — into parity 0 of its own buffer: a group's launches are stream-ordered, so step s + 1's draw cannot
+// overtake step s's backward.  Only the words a step reads are drawn: rows < n_rows of each of the two layers.
+struct GroupDropRec {
+  unsigned* bits;                     // the member's keep-bits [2 layers][max_batch][8]
+  int n_rows;                         // rows of the call's batches
+  int max_batch;                      // rows per layer of `bits`
+  unsigned thresh;                    // drop_thresh(p)
+  int active;                         // 0: nothing to draw (rate 0, or masks written by iqlhip_debug_write_masks)
+  unsigned long long seed, step0;     // the member's stream: key, and its position at the call's step 0
+};
+__device__ __forceinline__ void group_drop_words(const GroupDropRec& d, unsigned long long step, int first, int stride) {
+  const int per = d.n_rows * 8;
+  for (int v = first; v < 2 * per; v += stride) {
+    const int w = (v < per) ? v : d.max_batch * 8 + (v - per);
+    dropmask_words(d.bits, w + 1, d.thresh, d.seed, step, w, w + 1);      // (word w alone)
+  }
+}
+
+// iql_dropmask_kernel for every drawing member of an eager or online group call (grid.y = record; the host packs the
+// drawing members' records to the front): one launch where K solo steps pay K.
+__global__ __launch_bounds__(256) void iql_dropmask_group_kernel(const GroupDropRec* __restrict__ drops) {
+  const GroupDropRec& d = drops[blockIdx.y];
+  group_drop_words(d, d.step0, (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+}
+
+// iql_gather_group_kernel plus the step's keep-bits of the members that draw some (drops[member]), in the same launch:
+// the gather occupies the first blocks, the keep-bit words are taken from the far end of the grid (idle_block_work's
+// split).  Launched instead of iql_gather_group_kernel only when some member of the call draws.
+__global__ __launch_bounds__(256) void iql_gather_drop_group_kernel(const GroupRec* __restrict__ recs,
+                                                                    const GroupDropRec* __restrict__ drops, int step) {
+  const GroupRec& r = recs[blockIdx.y];
+  const int s = min(max(step, 0), r.n_steps - 1);
+  gather_rows_drawn(r.rows, r.ld, r.xb, r.B, r.seed, r.offset, (unsigned long long)s * (unsigned long long)r.B,
+                    (unsigned long long)r.size, (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+  const GroupDropRec& d = drops[blockIdx.y];
+  if (d.active)
+    group_drop_words(d, d.step0 + (unsigned long long)s, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x,
+                     (int)gridDim.x * 256);
+}
+
 // Policy inference (GaussianPolicy.act / DeterministicPolicy.act, algorithms/finetune/iql.py:371-379, 404-413):
 // states -> packed rows whose first S columns are the state (the rest zero), then iql_fwd_kernel with
 // only_inst = 6, then this finish kernel over the policy head partials:

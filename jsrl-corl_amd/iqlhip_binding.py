@@ -19,6 +19,7 @@ IQLHIP_MAX_WORLD = 8
 IQLHIP_GRAPH_STEPS = 64
 IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
 IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the actions are written
+IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train with actor dropout
 IQLHIP_GROUP_MAX_STEPS = 1024  # steps per iqlhip_group_train_steps call
 IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
@@ -131,6 +132,7 @@ SYMBOLS = [
                                            C.c_void_p]),
     ("iqlhip_debug_drain_spin", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("iqlhip_group_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    ("iqlhip_group_create_flags", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.POINTER(C.c_void_p)]),
     ("iqlhip_group_destroy", C.c_int, [C.c_void_p]),
     ("iqlhip_group_step", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_group_train_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64), C.c_int32,

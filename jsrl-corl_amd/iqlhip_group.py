@@ -19,7 +19,22 @@ Policy inference of all members is one call too (actor.act / ImplicitQLearning.a
 order): `group.act(states)` for one state per member (lockstep evaluation: iqlhip_hostutil.eval_actors),
 `group.actor_forward(states)` for batches.
 
-Not supported (NotImplementedError): data parallelism, actor dropout > 0, bf16 batches of more than 512 rows.  Groups
+Actor dropout (the reference's adroit configurations: actor_dropout 0.1) is opt-in:
+
+    for seed, t in zip(seeds, trainers):
+        t.set_dropout_seed(seed)
+    group = ImplicitQLearningGroup(trainers, actor_dropout=True)
+
+Members may then train with dropout, each with its own rate (0 included) and its own train() / eval() mode; every
+member's keep-bits are the ones its solo steps would draw, from its own stream position, so the bit-for-bit promise
+above holds with dropout too.  A trainer keys its keep-bit stream with the process's torch.initial_seed() unless
+ImplicitQLearning.set_dropout_seed(seed) was called: the members of a sweep share a process, so they should call it
+with distinct seeds (as above), or they all draw the same masks.  Without actor_dropout=True a group behaves exactly
+as before the option existed: a member in training mode with dropout > 0 is refused (NotImplementedError).  The
+inference forwards are eval-mode: online_step(act_next=...) and act() for a member that is in training mode with
+dropout > 0 raise NotImplementedError, as the solo online_step does.
+
+Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
 driver is faster for one agent).
@@ -39,11 +54,12 @@ BF16_MAX_ROWS = 512      # bf16 batches beyond this run the large-batch kernels,
 
 
 class ImplicitQLearningGroup:
-    def __init__(self, trainers: Sequence[ImplicitQLearning]):
+    def __init__(self, trainers: Sequence[ImplicitQLearning], actor_dropout: bool = False):
         trainers = list(trainers)
         if not 1 <= len(trainers) <= hb.IQLHIP_MAX_GROUP:
             raise ValueError(f"iqlhip: a group has 1..{hb.IQLHIP_MAX_GROUP} trainers, got {len(trainers)}")
         self.trainers = trainers
+        self._actor_dropout = bool(actor_dropout)
         self._check_members()
         self._g = None
         self._ctxs = None
@@ -72,8 +88,17 @@ class ImplicitQLearningGroup:
                 raise ValueError(f"iqlhip: group member {i} has another precision than member 0")
             if t._dp_world > 1 or t._dp_exchange is not None:
                 raise NotImplementedError(f"iqlhip: group member {i} has data parallelism enabled (not supported in a group)")
+            if not self._actor_dropout and t.actor.training and t._actor_dropout_p() > 0.0:
+                raise NotImplementedError(f"iqlhip: group member {i} uses actor dropout (not supported in a group "
+                                          "without actor_dropout=True)")
+
+    def _check_eval_forward(self, members, what: str) -> None:
+        """The library's inference forward is eval-mode: refuse it for a member that would act with dropout."""
+        for i in members:
+            t = self.trainers[i]
             if t.actor.training and t._actor_dropout_p() > 0.0:
-                raise NotImplementedError(f"iqlhip: group member {i} uses actor dropout (not supported in a group)")
+                raise NotImplementedError(f"iqlhip: {what}: the library's inference forward is eval-mode (no actor "
+                                          f"dropout; member {i} is in training mode)")
 
     def _check_batch_size(self, B: int) -> None:
         if getattr(self.trainers[0], "_precision", "f32") == "bf16" and B > BF16_MAX_ROWS:
@@ -88,7 +113,10 @@ class ImplicitQLearningGroup:
         self._release()
         arr = (C.c_void_p * len(ctxs))(*ctxs)
         g = C.c_void_p()
-        hb.check(hb.lib().iqlhip_group_create(arr, len(ctxs), C.byref(g)))
+        if self._actor_dropout:
+            hb.check(hb.lib().iqlhip_group_create_flags(arr, len(ctxs), hb.IQLHIP_GROUP_DROPOUT, C.byref(g)))
+        else:
+            hb.check(hb.lib().iqlhip_group_create(arr, len(ctxs), C.byref(g)))
         self._g, self._ctxs = g, ctxs
         return g
 
@@ -227,6 +255,8 @@ class ImplicitQLearningGroup:
         bufs = list(buffers)
         self._check_members()
         self._check_batch_size(batch_size)
+        if act_next is not None:         # (before any ring, counter or parameter moves)
+            self._check_eval_forward([k for k in range(K) if act_next[k] is not None], "online_step(act_next=...)")
         if K == 1 and rngs is None:      # a group of one IS the solo call
             tr = self.trainers[0]
             an = None if act_next is None else act_next[0]
@@ -330,6 +360,7 @@ class ImplicitQLearningGroup:
         if not isinstance(states, (list, tuple)) or len(states) != K:
             raise ValueError(f"iqlhip: act of a group of {K} needs states as a list of {K} entries")
         self._check_members()
+        self._check_eval_forward([k for k in range(K) if states[k] is not None], "act")
         if K == 1:      # a group of one IS the solo call
             t = self.trainers[0]
             if states[0] is None:

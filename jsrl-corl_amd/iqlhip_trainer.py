@@ -327,8 +327,19 @@ class ImplicitQLearning:
         p_eff = self._actor_dropout_p() if self.actor.training else 0.0
         if p_eff != self._dropout_sent:
             rank = self._dp_rank if self._dp_world > 1 else 0
-            hb.check(hb.lib().iqlhip_set_dropout(self._ctx, p_eff, dp.rank_seed(torch.initial_seed(), rank)))
+            seed = getattr(self, "_dropout_seed", None)
+            if seed is None:
+                seed = torch.initial_seed()
+            hb.check(hb.lib().iqlhip_set_dropout(self._ctx, p_eff, dp.rank_seed(seed, rank)))
             self._dropout_sent = p_eff
+
+    def set_dropout_seed(self, seed: int) -> None:
+        """Key this trainer's actor-dropout keep-bit stream with `seed` instead of the process's torch.initial_seed().
+        Solo sweeps run one process per seed, so their streams differ by themselves; the members of one
+        ImplicitQLearningGroup share a process and would all draw the same masks without it.  Takes effect with the
+        next step (the stream position is kept).  Not part of the reference's surface."""
+        self._dropout_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._dropout_sent = None        # (the next _prepare sends the rate and the new key)
 
     def _actor_dropout_p(self) -> float:
         """max p over the actor's nn.Dropout layers; the layer list is cached (walking named_modules costs ~13 us a
