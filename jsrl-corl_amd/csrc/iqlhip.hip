@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #define GRAPH_STEPS IQLHIP_GRAPH_STEPS
@@ -39,6 +40,37 @@ static int fail(int code, const char* fmt, ...) {
   } while (0)
 
 static inline int64_t up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// Runtime flags -> template arguments: with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...).
+// Every kernel family with bool template parameters has ONE selector built on it (flags -> instantiation), next to its
+// launcher; the solo launch, the group launch and the hipFuncSetAttribute loop (set_max_lds) all go through that selector,
+// so a family's instantiation list is written once.  The selectors also fix the ORDER in which the instantiations are
+// emitted (first flag outermost, false before true, selector by selector down this file), and with it where each kernel
+// lies in the code object; the step time is sensitive to that (profiles/r09_host_fold_host_ab.txt), so they keep the
+// order the code object has always had — which is why the flags of a selector are not always in template order.
+template <class F> static auto with_bools(F&& f) { return f(); }
+template <class F, class... Bs> static auto with_bools(F&& f, bool b, Bs... rest) {
+  if (!b) return with_bools([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+  return with_bools([&](auto... t) { return f(std::true_type{}, t...); }, rest...);
+}
+static auto fwd_one_kernel(bool bf, bool dma) {      // policy inference (StepParams::only_inst): its own instantiations
+  return with_bools([](auto BF, auto DMA) { return &iql_fwd_kernel<BF.value, DMA.value, false, true>; }, bf, dma);
+}
+static auto fwd_kernel(bool bf, bool dma, bool multi) {
+  return with_bools([](auto MU, auto BF, auto DMA) { return &iql_fwd_kernel<BF.value, DMA.value, MU.value>; }, multi, bf, dma);
+}
+static auto bwd_kernel(bool bf, bool full, bool multi) {
+  return with_bools([](auto MU, auto BF, auto FU) { return &iql_bwd_kernel<BF.value, FU.value, MU.value>; }, multi, bf, full);
+}
+static auto bwd_rows_kernel(bool csplit) {
+  return with_bools([](auto CS) { return &iql_bwd_rows_kernel<CS.value>; }, csplit);
+}
+// Allow `lds` bytes of dynamic LDS in every instantiation of a family: sel(m) = its selector called with bit i of m as flag i.
+template <class Sel> static int set_max_lds(int n_flags, size_t lds, Sel sel) {
+  for (unsigned m = 0; m < (1u << n_flags); ++m)
+    HIPCHK(hipFuncSetAttribute((const void*)sel(m), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return IQLHIP_OK;
+}
 
 // Diagnostic (IQLHIP_TRACE=1): host timestamps inside iqlhip_train_steps, printed to stderr at the end of the call.
 static inline double now_us() {
@@ -366,30 +398,13 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   const size_t lds_b = (size_t)(RT_ROWS * H0_LD + 4 * 32 * T64_LD + RT_ROWS * T64_LD + RT_ROWS * 36 + 4 +
                                 RT_ROWS * XR_LD_MAX) * sizeof(float);
   c->lds_bwd = std::max(lds_a, lds_b);
-  {
-    const void* fwd1[4] = {(const void*)iql_fwd_kernel<false, false, false, true>, (const void*)iql_fwd_kernel<false, true, false, true>,
-                           (const void*)iql_fwd_kernel<true, false, false, true>,  (const void*)iql_fwd_kernel<true, true, false, true>};
-    for (const void* f : fwd1) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_fwd_solo));
-    const void* fwd[8] = {(const void*)iql_fwd_kernel<false, false, false>, (const void*)iql_fwd_kernel<false, true, false>,
-                          (const void*)iql_fwd_kernel<true, false, false>,  (const void*)iql_fwd_kernel<true, true, false>,
-                          (const void*)iql_fwd_kernel<false, false, true>,  (const void*)iql_fwd_kernel<false, true, true>,
-                          (const void*)iql_fwd_kernel<true, false, true>,   (const void*)iql_fwd_kernel<true, true, true>};
-    for (const void* f : fwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_fwd_solo));
-  }
-  {
-    const void* bwd[8] = {(const void*)iql_bwd_kernel<false, false, false>, (const void*)iql_bwd_kernel<false, true, false>,
-                          (const void*)iql_bwd_kernel<true, false, false>,  (const void*)iql_bwd_kernel<true, true, false>,
-                          (const void*)iql_bwd_kernel<false, false, true>,  (const void*)iql_bwd_kernel<false, true, true>,
-                          (const void*)iql_bwd_kernel<true, false, true>,   (const void*)iql_bwd_kernel<true, true, true>};
-    for (const void* f : bwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd));
-  }
-  {
-    // large-batch backward, row blocks: [dH1 tile | H1 tile | dH0 tile | dY | dy] (iql_bwd_rows_kernel)
-    c->lds_bwd_lb = (size_t)(3 * 32 * H0B_LD + 32 * LB_DYLD) * 2 + 32 * 4 + (size_t)(2 * 4 * 32 + 16) * 4;      // (+ the block sums' partials)
-    HIPCHK(hipFuncSetAttribute((const void*)iql_bwd_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd_lb));
-    HIPCHK(hipFuncSetAttribute((const void*)iql_bwd_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd_lb));
-  }
-  return IQLHIP_OK;
+  // large-batch backward, row blocks: [dH1 tile | H1 tile | dH0 tile | dY | dy] (iql_bwd_rows_kernel)
+  c->lds_bwd_lb = (size_t)(3 * 32 * H0B_LD + 32 * LB_DYLD) * 2 + 32 * 4 + (size_t)(2 * 4 * 32 + 16) * 4;      // (+ the block sums' partials)
+  int rc = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_kernel(m & 1, m & 2, m & 4); });
+  if (!rc) rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_one_kernel(m & 1, m & 2); });
+  if (!rc) rc = set_max_lds(3, c->lds_bwd, [](unsigned m) { return bwd_kernel(m & 1, m & 2, m & 4); });
+  if (!rc) rc = set_max_lds(1, c->lds_bwd_lb, [](unsigned m) { return bwd_rows_kernel(m & 1); });
+  return rc;
 }
 
 extern "C" int iqlhip_create(const iqlhip_dims* dims, const iqlhip_hyper* hyper, int device, iqlhip_ctx** out) {
@@ -690,6 +705,19 @@ static StepParams make_step(const iqlhip_ctx* c, int rows, float inv_batch) {
   return p;
 }
 
+// The forward record of policy inference over `rows` rows packed in xb_act (iqlhip_actor_forward, and the trainer
+// groups' act launches, which pass the same record per member).
+static StepParams act_step_params(const iqlhip_ctx* c, int rows) {
+  StepParams p = make_step(c, rows, 1.f / (float)rows);
+  p.xb = c->xb_act;
+  p.only_inst = 6;
+  p.slot[6] = -1;            // inference keeps no activations
+  p.drop_bits = nullptr;     // eval-mode forward; a training-mode policy with dropout stays on the caller's side
+  p.sc.heads = c->heads_act; // the policy partials of row r land at heads[max_batch * HEAD_LD + r * A * NSPLIT ...]:
+  p.sc.max_batch = 0;        // with max_batch = 0 that is heads_act[r * A * NSPLIT ...]
+  return p;
+}
+
 static UpdParams make_upd(const iqlhip_ctx* c, const iqlhip_step_scalars* sc, int rows, const float* flat) {
   UpdParams u;
   u.L = c->L;
@@ -738,22 +766,10 @@ static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c
 
 static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
-  const size_t lds = fwd_lds(c, nb);
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
-#define FWD_LAUNCH(BF, DMA, MU) hipLaunchKernelGGL((iql_fwd_kernel<BF, DMA, MU>), dim3(nb), dim3(256), lds, st, p)
-#define FWD_LAUNCH_ONE(BF, DMA) hipLaunchKernelGGL((iql_fwd_kernel<BF, DMA, false, true>), dim3(nb), dim3(256), lds, st, p)
-  if (p.only_inst >= 0) {        // policy inference (iqlhip_actor_forward): its own instantiation
-    if (bf) { if (dma) FWD_LAUNCH_ONE(true, true); else FWD_LAUNCH_ONE(true, false); }
-    else    { if (dma) FWD_LAUNCH_ONE(false, true); else FWD_LAUNCH_ONE(false, false); }
-  } else if (multi) {
-    if (bf) { if (dma) FWD_LAUNCH(true, true, true); else FWD_LAUNCH(true, false, true); }
-    else    { if (dma) FWD_LAUNCH(false, true, true); else FWD_LAUNCH(false, false, true); }
-  } else {
-    if (bf) { if (dma) FWD_LAUNCH(true, true, false); else FWD_LAUNCH(true, false, false); }
-    else    { if (dma) FWD_LAUNCH(false, true, false); else FWD_LAUNCH(false, false, false); }
-  }
-#undef FWD_LAUNCH
-#undef FWD_LAUNCH_ONE
+  // (policy inference — iqlhip_actor_forward — has its own instantiations)
+  const auto kernel = (p.only_inst >= 0) ? fwd_one_kernel(bf, dma) : fwd_kernel(bf, dma, multi);
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
 }
 
 // Column slices per forward block (log2).  One block per (instance, row tile, slice) while that grid fits the chip in
@@ -766,6 +782,9 @@ static int fwd_spb_l2(const iqlhip_ctx* c, int n_rt) {
   if (8 * n_rt * 2 <= c->n_cus) return 1;
   return 2;
 }
+// Blocks of a forward grid (per agent) over n_rt row tiles at 2^l2 slices per block.  (Full-width blocks: each XCD of
+// a net's pair takes the row tiles of one parity — iql_fwd_kernel's block map.)
+static int fwd_blocks(int n_rt, int l2) { return (l2 == 2) ? 8 * 2 * ((n_rt + 1) / 2) : 8 * n_rt * (NSPLIT >> l2); }
 static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st) {
   StepParams p = p_in;
   if (p.only_inst < 0 && use_lb(c, p.rows)) {
@@ -786,11 +805,8 @@ static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
     return;
   }
   const int n_rt = (p.rows + RT_ROWS - 1) / RT_ROWS;
-  const int l2 = fwd_spb_l2(c, n_rt);
-  p.spb_l2 = l2;
-  // (full-width blocks: each XCD of a net's pair takes the row tiles of one parity — iql_fwd_kernel's block map)
-  const int nb = (l2 == 2) ? 8 * 2 * ((n_rt + 1) / 2) : 8 * n_rt * (NSPLIT >> l2);
-  launch_fwd_grid(c, p, nb, st);
+  p.spb_l2 = fwd_spb_l2(c, n_rt);
+  launch_fwd_grid(c, p, fwd_blocks(n_rt, p.spb_l2), st);
 }
 // Column slices per (b) block of the backward (log2): one while the whole grid — 4 nets x (32 dW1 tiles per 256-row
 // chunk + 4 slices per row tile) — is at most two rounds of the chip (up to 512 rows: measured equal or better), else 4:
@@ -800,6 +816,24 @@ static int bwd_spb_l2(const iqlhip_ctx* c, int n_chunk, int n_rt) {
   if (c->bwd_spb_force >= 0) return c->bwd_spb_force;
   return (4 * (32 * n_chunk + 4 * n_rt) <= 2 * c->n_cus) ? 0 : 2;
 }
+// Blocks of a backward grid (per agent): per net 32 dW1 tiles per chunk + the (b) blocks of 2^l2 slices per row tile,
+// two nets per XCD pair, + the policy's n_don donated dW1 tiles at the ends of the scalar nets' queues.
+static int bwd_blocks(int n_chunk, int n_rt, int l2, int n_don) {
+  const int per_net = 32 * n_chunk + (4 >> l2) * n_rt;
+  return 8 * ((per_net + 1) / 2 + (n_don + 5) / 6);
+}
+// The backward's leading arguments: preloaded into SGPRs with each wave (build: -mllvm -amdgpu-kernarg-preload-count=14),
+// what a block needs to issue its first loads, see iql_bwd_kernel.  (GroupRec carries the same words per agent.)
+struct BwdWords { const float *heads, *xb, *h1, *h0, *params; unsigned dims, ldB, mbc, rts; };
+static BwdWords bwd_words(const iqlhip_ctx* c, const StepParams& p, int n_chunk, int n_rt, unsigned spb_l2) {
+  BwdWords w;
+  w.heads = p.sc.heads; w.xb = p.xb; w.h1 = p.sc.h1; w.h0 = p.sc.h0; w.params = c->params;
+  w.dims = (unsigned)p.S | ((unsigned)p.A << 8) | ((unsigned)p.policy << 14);
+  w.ldB = (unsigned)p.ld | ((unsigned)p.rows << 10);
+  w.mbc = (unsigned)p.sc.max_batch | ((unsigned)n_chunk << 16);
+  w.rts = (unsigned)n_rt | (spb_l2 << 10);
+  return w;
+}
 static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st) {
   StepParams p = p_in;
   if (use_lb(c, p.rows)) {
@@ -807,8 +841,8 @@ static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
     const int kq = c->dims.state_dim + c->dims.action_dim;
     (void)kq;
     if (c->lb_bwd_part != 2) {
-      if (lb_geom(c, p.rows).csplit) hipLaunchKernelGGL(iql_bwd_rows_kernel<true>, dim3(8 * a.nbb), dim3(256), c->lds_bwd_lb, st, p, a);
-      else hipLaunchKernelGGL(iql_bwd_rows_kernel<false>, dim3(8 * (a.nbb / 2)), dim3(256), c->lds_bwd_lb, st, p, a);
+      const bool csplit = lb_geom(c, p.rows).csplit;
+      hipLaunchKernelGGL(bwd_rows_kernel(csplit), dim3(8 * (csplit ? a.nbb : a.nbb / 2)), dim3(256), c->lds_bwd_lb, st, p, a);
     }
     if (c->lb_bwd_part != 1)
       hipLaunchKernelGGL(iql_bwd_gemm_kernel, dim3(8 * ((LB_NJOB * a.n_cg + 1 + 1) / 2)), dim3(256), 0, st, p, a);      // (+ 1: the reduction job)
@@ -818,7 +852,6 @@ static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
   const int n_chunk = (p.rows + CHUNK_ROWS - 1) / CHUNK_ROWS;
   int l2 = bwd_spb_l2(c, n_chunk, n_rt);
   if (c->precision == 1 && l2 > 0) l2 = 2;      // bf16, large batches: a (b) block takes the whole row tile in one pass
-  const int per_net = 32 * n_chunk + (4 >> l2) * n_rt;
   // multi-round launches: this many of the policy's dW1-tile blocks run at the ends of the scalar nets' XCD queues
   // (iql_bwd_kernel); share of its 32 n_chunk tiles tuned on obs 17 / act 6 and obs 39 / act 28 (profiles/r02_slices_per_block.txt)
   // Measured optimum of the share: 50 % at 28 action dims (1 024 rows 37.6 -> 30.8 us, bf16 32.7 -> 24.3; 2 048 rows
@@ -829,26 +862,10 @@ static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
     n_don = std::min(32 * n_chunk, (32 * n_chunk * pct + 50) / 100);
   }
   p.spb_l2 = (l2 << 2) | (n_don << 8);
-  const dim3 grid(8 * ((per_net + 1) / 2 + (n_don + 5) / 6));
   const bool full = (p.rows % CHUNK_ROWS) == 0;      // every tile of every block lies inside the batch: no clamps
-  const bool bf = c->precision == 1, multi = l2 > 0;
-  // the leading arguments are preloaded into SGPRs with each wave (build: -mllvm -amdgpu-kernarg-preload-count=14): what a
-  // block needs to issue its first loads, see iql_bwd_kernel
-  const float* q_heads = p.sc.heads; const float* q_xb = p.xb; const float* q_h1 = p.sc.h1; const float* q_h0 = p.sc.h0;
-  const float* q_params = c->params;
-  const unsigned q_dims = (unsigned)p.S | ((unsigned)p.A << 8) | ((unsigned)p.policy << 14);
-  const unsigned q_ldB = (unsigned)p.ld | ((unsigned)p.rows << 10);
-  const unsigned q_mbc = (unsigned)p.sc.max_batch | ((unsigned)n_chunk << 16);
-  const unsigned q_rts = (unsigned)n_rt | ((unsigned)p.spb_l2 << 10);
-#define BWD_LAUNCH(BF, FU, MU) hipLaunchKernelGGL((iql_bwd_kernel<BF, FU, MU>), grid, dim3(256), c->lds_bwd, st, q_heads, q_xb, q_h1, q_h0, q_params, q_dims, q_ldB, q_mbc, q_rts, p)
-  if (multi) {
-    if (bf) { if (full) BWD_LAUNCH(true, true, true); else BWD_LAUNCH(true, false, true); }
-    else    { if (full) BWD_LAUNCH(false, true, true); else BWD_LAUNCH(false, false, true); }
-  } else {
-    if (bf) { if (full) BWD_LAUNCH(true, true, false); else BWD_LAUNCH(true, false, false); }
-    else    { if (full) BWD_LAUNCH(false, true, false); else BWD_LAUNCH(false, false, false); }
-  }
-#undef BWD_LAUNCH
+  const BwdWords w = bwd_words(c, p, n_chunk, n_rt, (unsigned)p.spb_l2);
+  hipLaunchKernelGGL(bwd_kernel(c->precision == 1, full, /*multi=*/l2 > 0), dim3(bwd_blocks(n_chunk, n_rt, l2, n_don)), dim3(256),
+                     c->lds_bwd, st, w.heads, w.xb, w.h1, w.h0, w.params, w.dims, w.ldB, w.mbc, w.rts, p);
 }
 static unsigned drop_thresh(float p) {
   const double t = (double)p * 4294967296.0;
@@ -862,29 +879,36 @@ static void launch_dropmask(const iqlhip_ctx* c, unsigned long long seed, unsign
                      drop_thresh(c->drop_p), seed, step, hdr, k);
 }
 
-static void launch_upd(const iqlhip_ctx* c, UpdParams u, hipStream_t st) {
-  // grid: 8 x the 2 048-float windows of the longest net segment (iql_update_kernel's XCD-affine element map)
+// Blocks of an update grid (per agent): 8 x the 2 048-float windows of the longest net segment (iql_update_kernel's
+// XCD-affine element map).
+static int upd_blocks(const iqlhip_ctx* c) {
   long long seg_max = 0;
   for (int n = 0; n < 4; ++n) {
     const long long end = (n < 3) ? c->L.net[n + 1].seg_begin : c->L.n_params;
     seg_max = std::max(seg_max, end - c->L.net[n].seg_begin);
   }
-  const int nb = 8 * (int)((seg_max + 2047) / 2048);
-  const bool peer = u.n_peer > 0;
-  // the leading arguments are preloaded into SGPRs with each wave (iql_update_kernel)
-  const unsigned q_s0 = (unsigned)c->L.net[0].seg_begin, q_s1 = (unsigned)c->L.net[1].seg_begin, q_s2 = (unsigned)c->L.net[2].seg_begin,
-                 q_s3 = (unsigned)c->L.net[3].seg_begin, q_end = (unsigned)c->L.net[3].seg_end;
-  const unsigned q_flags = (!peer && !u.flat_grads && !u.slab_x && u.n_chunk == 1) ? UPD_EARLY_G : 0u;
-#define UPD_LAUNCH(T, P) hipLaunchKernelGGL((iql_update_kernel<T, P>), dim3(nb), dim3(256), 0, st, u.params, u.m, u.v, u.slab_a, q_s0, q_s1, q_s2, q_s3, q_end, q_flags, u)
-#define UPD_LAUNCH_LB(T, P) hipLaunchKernelGGL((iql_update_kernel<T, P, true>), dim3(nb), dim3(256), 0, st, u.params, u.m, u.v, u.slab_a, q_s0, q_s1, q_s2, q_s3, q_end, q_flags, u)
-  if (u.slab_x) {      // large-batch bf16 step: the LB instantiations (gradient from the chunk-group slabs unless an exchange
-                       // delivered it flat; the operand images of W0 / W1 written next to the bf16 shadows)
-    if (u.sched) { if (peer) UPD_LAUNCH_LB(true, true); else UPD_LAUNCH_LB(true, false); }
-    else         { if (peer) UPD_LAUNCH_LB(false, true); else UPD_LAUNCH_LB(false, false); }
-  } else if (u.sched) { if (peer) UPD_LAUNCH(true, true); else UPD_LAUNCH(true, false); }
-  else              { if (peer) UPD_LAUNCH(false, true); else UPD_LAUNCH(false, false); }
-#undef UPD_LAUNCH
-#undef UPD_LAUNCH_LB
+  return 8 * (int)((seg_max + 2047) / 2048);
+}
+// The update's leading arguments behind its four arena pointers: preloaded into SGPRs with each wave (iql_update_kernel).
+// (GroupRec carries the same words per agent.)
+struct UpdWords { unsigned s0, s1, s2, s3, end, flags; };
+static UpdWords upd_words(const iqlhip_ctx* c, const UpdParams& u) {
+  UpdWords w;
+  w.s0 = (unsigned)c->L.net[0].seg_begin; w.s1 = (unsigned)c->L.net[1].seg_begin; w.s2 = (unsigned)c->L.net[2].seg_begin;
+  w.s3 = (unsigned)c->L.net[3].seg_begin; w.end = (unsigned)c->L.net[3].seg_end;
+  w.flags = (u.n_peer == 0 && !u.flat_grads && !u.slab_x && u.n_chunk == 1) ? UPD_EARLY_G : 0u;
+  return w;
+}
+// (true before false in this family and the next, LB outermost: hence the negated flags, see with_bools)
+static auto upd_kernel(bool from_table, bool peer, bool lb) {
+  return with_bools([](auto NLB, auto NT, auto NP) { return &iql_update_kernel<!NT.value, !NP.value, !NLB.value>; }, !lb, !from_table, !peer);
+}
+static void launch_upd(const iqlhip_ctx* c, UpdParams u, hipStream_t st) {
+  const UpdWords w = upd_words(c, u);
+  // (u.slab_x: a large-batch bf16 step — the LB instantiations: gradient from the chunk-group slabs unless an exchange
+  //  delivered it flat; the operand images of W0 / W1 written next to the bf16 shadows)
+  hipLaunchKernelGGL(upd_kernel(/*from_table=*/u.sched != nullptr, /*peer=*/u.n_peer > 0, /*lb=*/u.slab_x != nullptr), dim3(upd_blocks(c)),
+                     dim3(256), 0, st, u.params, u.m, u.v, u.slab_a, w.s0, w.s1, w.s2, w.s3, w.end, w.flags, u);
 }
 
 // bf16 path: rebuild the bf16 shadows from the fp32 masters (the caller owns the masters and may have written them
@@ -896,13 +920,12 @@ static void refresh_shadows(const iqlhip_ctx* c, hipStream_t st) {
                      c->wsh, c->tsh, (long long)c->L.n_params, (long long)c->L.n_target, c->L, c->wimg);
 }
 
+static auto flatten_kernel(bool sys, bool lb) {
+  return with_bools([](auto NLB, auto NSYS) { return &iql_grad_flatten_kernel<!NSYS.value, !NLB.value>; }, !lb, !sys);
+}
 static void launch_flatten(const iqlhip_ctx* c, const UpdParams& u, float* out, bool sys, hipStream_t st) {
   const int nb = (int)((c->L.n_params / 4 + 255) / 256);
-  if (u.slab_x) {
-    if (sys) hipLaunchKernelGGL((iql_grad_flatten_kernel<true, true>), dim3(nb), dim3(256), 0, st, u, out);
-    else hipLaunchKernelGGL((iql_grad_flatten_kernel<false, true>), dim3(nb), dim3(256), 0, st, u, out);
-  } else if (sys) hipLaunchKernelGGL(iql_grad_flatten_kernel<true>, dim3(nb), dim3(256), 0, st, u, out);
-  else hipLaunchKernelGGL(iql_grad_flatten_kernel<false>, dim3(nb), dim3(256), 0, st, u, out);
+  hipLaunchKernelGGL(flatten_kernel(sys, /*lb=*/u.slab_x != nullptr), dim3(nb), dim3(256), 0, st, u, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -2110,13 +2133,7 @@ static int actor_forward_impl(iqlhip_ctx* c, const float* states_dev, int64_t ld
   hipLaunchKernelGGL(iql_pack_states_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c->xb_act, (int)c->row_ld, S,
                      rows, states_dev, (long long)ld_s);
   refresh_shadows(c, st);
-  StepParams p = make_step(c, rows, 1.f / (float)rows);
-  p.xb = c->xb_act;
-  p.only_inst = 6;
-  p.slot[6] = -1;            // inference keeps no activations
-  p.drop_bits = nullptr;     // eval-mode forward; a training-mode policy with dropout stays on the caller's side
-  p.sc.heads = c->heads_act; // the policy partials of row r land at heads[max_batch * HEAD_LD + r * A * NSPLIT ...]:
-  p.sc.max_batch = 0;        // with max_batch = 0 that is heads_act[r * A * NSPLIT ...]
+  const StepParams p = act_step_params(c, rows);
   const int n_rt = (rows + RT_ROWS - 1) / RT_ROWS;
   launch_fwd_grid(c, p, n_rt * NSPLIT, st);
   hipLaunchKernelGGL(iql_actor_finish_kernel, dim3((rows * A + 255) / 256), dim3(256), 0, st, c->heads_act, rows, A,
@@ -2221,35 +2238,61 @@ extern "C" int iqlhip_debug_read(iqlhip_ctx* c, const char* name, float* host_ou
 // host writes once per call, together with the agents' scalar tables, in ONE host-to-device copy from pinned memory.
 // A group created with IQLHIP_GROUP_DROPOUT also uploads one GroupDropRec per member in that copy: the members' actor
 // dropout keep-bits are drawn by the group's own launches, each from the member's own stream (seed, rate, position).
+
+// A block of launch records that exists twice: `pin`, pinned host memory the host writes, and `dev`, the device memory
+// one hipMemcpyAsync brings it to.  Sections are appended in order (add), each at the next 256-byte boundary; a
+// Section<T> is the typed handle of one, host() / device() its view in either copy, at() in any buffer of the same layout.
+template <class T> struct Section { size_t off = 0; };
+struct Staging {
+  char* dev = nullptr;
+  char* pin = nullptr;
+  size_t bytes = 0;
+  template <class T> Section<T> add(size_t count) {
+    Section<T> s;
+    s.off = (size_t)up((int64_t)bytes, 256);
+    bytes = s.off + count * sizeof(T);
+    return s;
+  }
+  template <class T> static T* at(char* base, Section<T> s) { return (T*)(base + s.off); }
+  template <class T> T* host(Section<T> s) const { return at(pin, s); }
+  template <class T> const T* device(Section<T> s) const { return at(dev, s); }
+  int alloc() {      // (the pinned copy starts zeroed: records are uploaded — and compared — whole, padding included)
+    HIPCHK(hipMalloc((void**)&dev, bytes));
+    HIPCHK(hipHostMalloc((void**)&pin, bytes, hipHostMallocDefault));
+    memset(pin, 0, bytes);
+    return IQLHIP_OK;
+  }
+  void free() { if (dev) (void)hipFree(dev); if (pin) (void)hipHostFree(pin); }
+};
+
 struct iqlhip_group {
   int k = 0;
   int device = 0;
   int flags = 0;                      // IQLHIP_GROUP_*
   iqlhip_ctx* m[IQLHIP_MAX_GROUP] = {};
-  // [GroupRec x k | pad][IQLHIP_GROUP_DROPOUT: GroupDropRec x k | pad][scalars: k x IQLHIP_GROUP_MAX_STEPS]
-  char* blob_dev = nullptr;
-  char* blob_pin = nullptr;           // pinned staging of the same bytes
-  size_t drop_off = 0, tab_off = 0, blob_bytes = 0;
+  // iqlhip_group_step / iqlhip_group_train_steps: the agents' records, the IQLHIP_GROUP_DROPOUT records (no rows
+  // without the flag) and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS]
+  Staging train;
+  Section<GroupRec> recs; Section<GroupDropRec> drops; Section<iqlhip_step_scalars> tabs;
   float* ring_dev = nullptr;          // [k][IQLHIP_GROUP_MAX_STEPS][4] losses of the last call
   float* ring_pin = nullptr;
   int last_n = 0;                     // steps of the last call (rows of the ring that are valid)
-  hipEvent_t up_done = nullptr;       // the last upload has read blob_pin
+  hipEvent_t up_done = nullptr;       // the last upload has read train.pin
   bool up_pending = false;
-  // iqlhip_group_online_step: its own records (a synchronous call — the staging is free again when it returns)
-  //   [GroupRec x k][StepParams x k: act forward][GroupOnlineRec x k][GroupActRec x k]
-  //   [IQLHIP_GROUP_DROPOUT: GroupDropRec x k][iqlhip_step_scalars x k]
-  char* on_dev = nullptr;
-  char* on_pin = nullptr;
-  size_t on_act_off = 0, on_gather_off = 0, on_fin_off = 0, on_drop_off = 0, on_tab_off = 0, on_bytes = 0;
+  // iqlhip_group_online_step: its own records (a synchronous call — the staging is free again when it returns): the
+  // agents' records, the act forwards' and the ring writes + gathers', the act finishes', the dropout records (as above)
+  // and one row of scalars per agent
+  Staging on;
+  Section<GroupRec> on_recs; Section<StepParams> on_aps; Section<GroupOnlineRec> on_gathers; Section<GroupActRec> on_fins;
+  Section<GroupDropRec> on_drops; Section<iqlhip_step_scalars> on_tabs;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
-  // iqlhip_group_actor_forward: its own records [GroupPackRec x k][StepParams x k][GroupActRowsRec x k], built in
-  // act_host; uploaded from act_pin only when they differ from the last upload (act_last) — an evaluation loop's calls
-  // repeat theirs.  (An asynchronous call: the next upload waits for act_up, this one's, before it rewrites act_pin.)
-  char* act_dev = nullptr;
-  char* act_pin = nullptr;
+  // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in act_host (the
+  // same layout); uploaded through act.pin only when they differ from the last upload (act_last) — an evaluation loop's
+  // calls repeat theirs.  (An asynchronous call: the next upload waits for act_up, this one's, before it rewrites act.pin.)
+  Staging act;
+  Section<GroupPackRec> act_packs; Section<StepParams> act_ps; Section<GroupActRowsRec> act_fins;
   std::vector<char> act_host, act_last;
-  size_t act_fwd_off = 0, act_fin_off = 0, act_bytes = 0;
   hipEvent_t act_up = nullptr;
   bool act_pending = false;
 };
@@ -2277,20 +2320,28 @@ static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
   return IQLHIP_OK;
 }
 
+// The group kernels' selectors (with_bools).
+static auto fwd_group_kernel(bool bf, bool dma, bool multi) {
+  return with_bools([](auto MU, auto BF, auto DMA) { return &iql_fwd_group_kernel<BF.value, DMA.value, MU.value>; }, multi, bf, dma);
+}
+static auto bwd_group_kernel(bool bf, bool full) {
+  return with_bools([](auto BF, auto FU) { return &iql_bwd_group_kernel<BF.value, FU.value>; }, bf, full);
+}
+static auto act_fwd_group_kernel(bool bf, bool dma) {
+  return with_bools([](auto BF, auto DMA) { return &iql_act_fwd_group_kernel<BF.value, DMA.value>; }, bf, dma);
+}
+
 extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   if (!g) return fail(IQLHIP_EINVAL, "NULL group");
   DevGuard guard(g->device);
   (void)hipDeviceSynchronize();       // a group call may still be running on some stream
-  if (g->blob_dev) (void)hipFree(g->blob_dev);
-  if (g->blob_pin) (void)hipHostFree(g->blob_pin);
+  g->train.free();
+  g->on.free();
+  g->act.free();
   if (g->ring_dev) (void)hipFree(g->ring_dev);
   if (g->ring_pin) (void)hipHostFree(g->ring_pin);
   if (g->up_done) (void)hipEventDestroy(g->up_done);
-  if (g->on_dev) (void)hipFree(g->on_dev);
-  if (g->on_pin) (void)hipHostFree(g->on_pin);
   if (g->done_pin) (void)hipHostFree(g->done_pin);
-  if (g->act_dev) (void)hipFree(g->act_dev);
-  if (g->act_pin) (void)hipHostFree(g->act_pin);
   if (g->act_up) (void)hipEventDestroy(g->act_up);
   delete g;
   return IQLHIP_OK;
@@ -2308,51 +2359,36 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
   for (int i = 0; i < k; ++i) g->m[i] = members[i];
   DevGuard guard(g->device);
   auto setup = [&]() -> int {
-    const bool dropout = (flags & IQLHIP_GROUP_DROPOUT) != 0;       // (without it: the layouts of a plain group)
-    g->drop_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
-    g->tab_off = g->drop_off + (dropout ? (size_t)up((int64_t)k * sizeof(GroupDropRec), 256) : 0);
-    g->blob_bytes = g->tab_off + (size_t)k * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars);
-    HIPCHK(hipMalloc((void**)&g->blob_dev, g->blob_bytes));
-    HIPCHK(hipHostMalloc((void**)&g->blob_pin, g->blob_bytes, hipHostMallocDefault));
-    memset(g->blob_pin, 0, g->blob_bytes);
+    const size_t n_drop = (flags & IQLHIP_GROUP_DROPOUT) ? k : 0;      // (without the flag: the layouts of a plain group)
+    g->recs = g->train.add<GroupRec>(k);
+    g->drops = g->train.add<GroupDropRec>(n_drop);
+    g->tabs = g->train.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
+    g->on_recs = g->on.add<GroupRec>(k);
+    g->on_aps = g->on.add<StepParams>(k);
+    g->on_gathers = g->on.add<GroupOnlineRec>(k);
+    g->on_fins = g->on.add<GroupActRec>(k);
+    g->on_drops = g->on.add<GroupDropRec>(n_drop);
+    g->on_tabs = g->on.add<iqlhip_step_scalars>(k);
+    g->act_packs = g->act.add<GroupPackRec>(k);
+    g->act_ps = g->act.add<StepParams>(k);
+    g->act_fins = g->act.add<GroupActRowsRec>(k);
+    for (Staging* s : {&g->train, &g->on, &g->act})
+      if (int rc_s = s->alloc()) return rc_s;
+    g->act_host.assign(g->act.bytes, 0);
+    g->act_last.assign(g->act.bytes, 1);     // (differs from any first call's records: the first call uploads)
     const size_t ring = (size_t)k * IQLHIP_GROUP_MAX_STEPS * 4 * sizeof(float);
     HIPCHK(hipMalloc((void**)&g->ring_dev, ring));
     HIPCHK(hipMemset(g->ring_dev, 0, ring));
     HIPCHK(hipHostMalloc((void**)&g->ring_pin, ring, hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&g->up_done, hipEventDisableTiming));
-    g->on_act_off = (size_t)up((int64_t)k * sizeof(GroupRec), 256);
-    g->on_gather_off = g->on_act_off + (size_t)up((int64_t)k * sizeof(StepParams), 256);
-    g->on_fin_off = g->on_gather_off + (size_t)up((int64_t)k * sizeof(GroupOnlineRec), 256);
-    g->on_drop_off = g->on_fin_off + (size_t)up((int64_t)k * sizeof(GroupActRec), 256);
-    g->on_tab_off = g->on_drop_off + (dropout ? (size_t)up((int64_t)k * sizeof(GroupDropRec), 256) : 0);
-    g->on_bytes = g->on_tab_off + (size_t)k * sizeof(iqlhip_step_scalars);
-    HIPCHK(hipMalloc((void**)&g->on_dev, g->on_bytes));
-    HIPCHK(hipHostMalloc((void**)&g->on_pin, g->on_bytes, hipHostMallocDefault));
-    memset(g->on_pin, 0, g->on_bytes);
     HIPCHK(hipHostMalloc((void**)&g->done_pin, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     memset(g->done_pin, 0, 8 * sizeof(unsigned long long));
-    g->act_fwd_off = (size_t)up((int64_t)k * sizeof(GroupPackRec), 256);
-    g->act_fin_off = g->act_fwd_off + (size_t)up((int64_t)k * sizeof(StepParams), 256);
-    g->act_bytes = g->act_fin_off + (size_t)k * sizeof(GroupActRowsRec);
-    HIPCHK(hipMalloc((void**)&g->act_dev, g->act_bytes));
-    HIPCHK(hipHostMalloc((void**)&g->act_pin, g->act_bytes, hipHostMallocDefault));
-    memset(g->act_pin, 0, g->act_bytes);
-    g->act_host.assign(g->act_bytes, 0);
-    g->act_last.assign(g->act_bytes, 1);     // (differs from any first call's records: the first call uploads)
+    HIPCHK(hipEventCreateWithFlags(&g->up_done, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&g->act_up, hipEventDisableTiming));
     const iqlhip_ctx* c = members[0];
-    const void* fwd[8] = {(const void*)iql_fwd_group_kernel<false, false, false>, (const void*)iql_fwd_group_kernel<false, true, false>,
-                          (const void*)iql_fwd_group_kernel<true, false, false>,  (const void*)iql_fwd_group_kernel<true, true, false>,
-                          (const void*)iql_fwd_group_kernel<false, false, true>,  (const void*)iql_fwd_group_kernel<false, true, true>,
-                          (const void*)iql_fwd_group_kernel<true, false, true>,   (const void*)iql_fwd_group_kernel<true, true, true>};
-    for (const void* f : fwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_fwd_solo));
-    const void* bwd[4] = {(const void*)iql_bwd_group_kernel<false, false>, (const void*)iql_bwd_group_kernel<false, true>,
-                          (const void*)iql_bwd_group_kernel<true, false>,  (const void*)iql_bwd_group_kernel<true, true>};
-    for (const void* f : bwd) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bwd));
-    const void* act[4] = {(const void*)iql_act_fwd_group_kernel<false, false>, (const void*)iql_act_fwd_group_kernel<false, true>,
-                          (const void*)iql_act_fwd_group_kernel<true, false>,  (const void*)iql_act_fwd_group_kernel<true, true>};
-    for (const void* f : act) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_fwd_solo));
-    return IQLHIP_OK;
+    int rc_a = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_group_kernel(m & 1, m & 2, m & 4); });
+    if (!rc_a) rc_a = set_max_lds(2, c->lds_bwd, [](unsigned m) { return bwd_group_kernel(m & 1, m & 2); });
+    if (!rc_a) rc_a = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return act_fwd_group_kernel(m & 1, m & 2); });
+    return rc_a;
   };
   rc = setup();
   if (rc) {
@@ -2378,29 +2414,26 @@ static GroupGeom group_geom(const iqlhip_ctx* c, int rows, int k) {
   q.n_rt = (rows + RT_ROWS - 1) / RT_ROWS;
   q.n_chunk = (rows + CHUNK_ROWS - 1) / CHUNK_ROWS;
   q.fwd_l2 = fwd_spb_l2(c, k * q.n_rt);
-  q.fwd_nb = (q.fwd_l2 == 2) ? 8 * 2 * ((q.n_rt + 1) / 2) : 8 * q.n_rt * (NSPLIT >> q.fwd_l2);
-  const int per_net = 32 * q.n_chunk + 4 * q.n_rt;
-  q.bwd_nb = 8 * ((per_net + 1) / 2);
-  long long seg_max = 0;
-  for (int n = 0; n < 4; ++n) {
-    const long long end = (n < 3) ? c->L.net[n + 1].seg_begin : c->L.n_params;
-    seg_max = std::max(seg_max, end - c->L.net[n].seg_begin);
-  }
-  q.upd_nb = 8 * (int)((seg_max + 2047) / 2048);
+  q.fwd_nb = fwd_blocks(q.n_rt, q.fwd_l2);
+  q.bwd_nb = bwd_blocks(q.n_chunk, q.n_rt, 0, 0);
+  q.upd_nb = upd_blocks(c);
   q.full = (rows % CHUNK_ROWS) == 0;
   return q;
 }
 
-// Checks shared by both step entry points (before any device work).
+// Per-member checks the entry points share (before any device work): bound arenas ...
+static int group_check_bound(const iqlhip_group* g, int i) {
+  return g->m[i]->params ? IQLHIP_OK : fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called", i);
+}
+// ... and, for the step entry points, batches of `rows` rows.
 static int group_check_call(iqlhip_group* g, int rows) {
   if (!g) return fail(IQLHIP_EINVAL, "NULL group");
   int rc = group_check_members(g->m, g->k, g->flags);
   if (rc) return rc;
   for (int i = 0; i < g->k; ++i) {
-    const iqlhip_ctx* c = g->m[i];
-    if (!c->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called", i);
-    if (rows < 1 || rows > c->dims.max_batch)
-      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, max_batch=%d]", i, rows, c->dims.max_batch);
+    if ((rc = group_check_bound(g, i))) return rc;
+    if (rows < 1 || rows > g->m[i]->dims.max_batch)
+      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, max_batch=%d]", i, rows, g->m[i]->dims.max_batch);
   }
   if (g->m[0]->precision == 1 && rows > LB_MIN_ROWS)
     return fail(IQLHIP_EUNSUPPORTED, "bf16 groups take batches of at most %d rows (the large-batch kernels have no group form)", LB_MIN_ROWS);
@@ -2408,7 +2441,7 @@ static int group_check_call(iqlhip_group* g, int rows) {
 }
 
 // Write agent i's record r (host side) for a call of n steps on batches of `rows` rows staged at xb; sched: the
-// device address of the agent's scalar table.
+// device address of the agent's scalar table.  The leading-argument words are the solo launchers' (bwd_words, upd_words).
 static void group_record(iqlhip_group* g, GroupRec& r, int i, const GroupGeom& q, int rows, int n, const float* xb,
                          const iqlhip_step_scalars* sc0, const iqlhip_step_scalars* sched) {
   iqlhip_ctx* c = g->m[i];
@@ -2416,20 +2449,17 @@ static void group_record(iqlhip_group* g, GroupRec& r, int i, const GroupGeom& q
   r.p = make_step(c, rows, sc0->inv_batch);
   r.p.xb = xb;
   r.p.spb_l2 = q.fwd_l2;
-  r.q_heads = r.p.sc.heads; r.q_xb = xb; r.q_h1 = r.p.sc.h1; r.q_h0 = r.p.sc.h0; r.q_params = c->params;
-  r.q_dims = (unsigned)r.p.S | ((unsigned)r.p.A << 8) | ((unsigned)r.p.policy << 14);
-  r.q_ldB = (unsigned)r.p.ld | ((unsigned)rows << 10);
-  r.q_mbc = (unsigned)r.p.sc.max_batch | ((unsigned)q.n_chunk << 16);
-  r.q_rts = (unsigned)q.n_rt;         // (one-slice backward: no slice or donation word)
+  const BwdWords b = bwd_words(c, r.p, q.n_chunk, q.n_rt, 0u);      // (one-slice backward: no slice or donation word)
+  r.q_heads = b.heads; r.q_xb = b.xb; r.q_h1 = b.h1; r.q_h0 = b.h0; r.q_params = b.params;
+  r.q_dims = b.dims; r.q_ldB = b.ldB; r.q_mbc = b.mbc; r.q_rts = b.rts;
   r.u = make_upd(c, sc0, rows, nullptr);
   r.u.sched = sched;
   r.u.sched_idx = 0;
   r.u.loss_ring = g->ring_dev + (size_t)i * IQLHIP_GROUP_MAX_STEPS * 4;
   r.u.ring_slot = 0;
+  const UpdWords w = upd_words(c, r.u);
   r.u_p = r.u.params; r.u_m = r.u.m; r.u_v = r.u.v; r.u_slab_a = r.u.slab_a;
-  r.u_s0 = (unsigned)c->L.net[0].seg_begin; r.u_s1 = (unsigned)c->L.net[1].seg_begin;
-  r.u_s2 = (unsigned)c->L.net[2].seg_begin; r.u_s3 = (unsigned)c->L.net[3].seg_begin; r.u_end = (unsigned)c->L.net[3].seg_end;
-  r.u_flags = (r.u.n_chunk == 1) ? UPD_EARLY_G : 0u;
+  r.u_s0 = w.s0; r.u_s1 = w.s1; r.u_s2 = w.s2; r.u_s3 = w.s3; r.u_end = w.end; r.u_flags = w.flags;
   r.n_steps = n;
   r.xb = (float*)xb;
   r.B = rows;
@@ -2484,37 +2514,29 @@ static int group_staging_free(iqlhip_group* g) {
 
 static int group_upload(iqlhip_group* g, int n, hipStream_t st) {
   // records + the used rows of every agent's table (the tables are strided by IQLHIP_GROUP_MAX_STEPS)
-  const size_t bytes = g->tab_off + ((size_t)(g->k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars);
-  HIPCHK(hipMemcpyAsync(g->blob_dev, g->blob_pin, bytes, hipMemcpyHostToDevice, st));
+  const size_t bytes = g->tabs.off + ((size_t)(g->k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars);
+  HIPCHK(hipMemcpyAsync(g->train.dev, g->train.pin, bytes, hipMemcpyHostToDevice, st));
   HIPCHK(hipEventRecord(g->up_done, st));
   g->up_pending = true;
   return IQLHIP_OK;
 }
 
-static const iqlhip_step_scalars* group_sched(const iqlhip_group* g, int i) {
-  return (const iqlhip_step_scalars*)(g->blob_dev + g->tab_off) + (size_t)i * IQLHIP_GROUP_MAX_STEPS;
-}
+// Agent i's scalar table of a train-staging call: the host copy the caller's rows go to, and its device address.
+static iqlhip_step_scalars* group_tab(const iqlhip_group* g, int i) { return g->train.host(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
+static const iqlhip_step_scalars* group_sched(const iqlhip_group* g, int i) { return g->train.device(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
 
 static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st) {
   const iqlhip_ctx* c = g->m[0];
   const int K = g->k;
-  const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K, fmulti = q.fwd_l2 > 0;
-  const size_t lds = fwd_lds(c, q.fwd_nb * K);
-  const dim3 fg(q.fwd_nb, K), bg(q.bwd_nb, K), ug(q.upd_nb, K);
-#define FWD_G(BF, DMA, MU) hipLaunchKernelGGL((iql_fwd_group_kernel<BF, DMA, MU>), fg, dim3(256), lds, st, recs)
-  if (fmulti) {
-    if (bf) { if (dma) FWD_G(true, true, true); else FWD_G(true, false, true); }
-    else    { if (dma) FWD_G(false, true, true); else FWD_G(false, false, true); }
-  } else {
-    if (bf) { if (dma) FWD_G(true, true, false); else FWD_G(true, false, false); }
-    else    { if (dma) FWD_G(false, true, false); else FWD_G(false, false, false); }
-  }
-#undef FWD_G
-#define BWD_G(BF, FU) hipLaunchKernelGGL((iql_bwd_group_kernel<BF, FU>), bg, dim3(256), c->lds_bwd, st, recs)
-  if (bf) { if (q.full) BWD_G(true, true); else BWD_G(true, false); }
-  else    { if (q.full) BWD_G(false, true); else BWD_G(false, false); }
-#undef BWD_G
-  hipLaunchKernelGGL(iql_update_group_kernel, ug, dim3(256), 0, st, recs, s);
+  const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K;
+  hipLaunchKernelGGL(fwd_group_kernel(bf, dma, /*multi=*/q.fwd_l2 > 0), dim3(q.fwd_nb, K), dim3(256), fwd_lds(c, q.fwd_nb * K), st, recs);
+  hipLaunchKernelGGL(bwd_group_kernel(bf, q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs);
+  hipLaunchKernelGGL(iql_update_group_kernel, dim3(q.upd_nb, K), dim3(256), 0, st, recs, s);
+}
+
+// The policy forward of n_req requesting members (both act paths): record j of `ps` on grid.y = j, `lds` from fwd_lds.
+static void group_launch_act_fwd(const iqlhip_ctx* c0, const StepParams* ps, int nbx, int n_req, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL(act_fwd_group_kernel(c0->precision == 1, c0->w0_lds_k > W0_LDS_MAX_K), dim3(nbx, n_req), dim3(256), lds, st, ps);
 }
 
 static int group_losses_out(iqlhip_group* g, float* out, int n, hipStream_t st) {
@@ -2553,14 +2575,14 @@ extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, c
     rc = stage_batch(c, &batches[i], st, &xb);
     if (rc) return rc;
     refresh_shadows(c, st);
-    group_record(g, ((GroupRec*)g->blob_pin)[i], i, q, rows, 1, xb, &sc[i], group_sched(g, i));
-    ((iqlhip_step_scalars*)(g->blob_pin + g->tab_off))[(size_t)i * IQLHIP_GROUP_MAX_STEPS] = sc[i];
+    group_record(g, g->train.host(g->recs)[i], i, q, rows, 1, xb, &sc[i], group_sched(g, i));
+    group_tab(g, i)[0] = sc[i];
   }
-  const int n_draw = group_drop_records_packed(g, (GroupDropRec*)(g->blob_pin + g->drop_off), rows);
+  const int n_draw = group_drop_records_packed(g, g->train.host(g->drops), rows);
   rc = group_upload(g, 1, st);
   if (rc) return rc;
-  group_launch_dropmask(g, (const GroupDropRec*)(g->blob_dev + g->drop_off), n_draw, rows, st);
-  group_launch_step(g, (const GroupRec*)g->blob_dev, q, 0, st);
+  group_launch_dropmask(g, g->train.device(g->drops), n_draw, rows, st);
+  group_launch_step(g, g->train.device(g->recs), q, 0, st);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
@@ -2590,16 +2612,15 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
     c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
     refresh_shadows(c, st);
     const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
-    group_record(g, ((GroupRec*)g->blob_pin)[i], i, q, B, n, c->xb, &tab[0], group_sched(g, i));
-    GroupRec& r = ((GroupRec*)g->blob_pin)[i];
+    GroupRec& r = g->train.host(g->recs)[i];
+    group_record(g, r, i, q, B, n, c->xb, &tab[0], group_sched(g, i));
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
-    memcpy(g->blob_pin + g->tab_off + (size_t)i * IQLHIP_GROUP_MAX_STEPS * sizeof(iqlhip_step_scalars), tab,
-           (size_t)n * sizeof(iqlhip_step_scalars));
+    memcpy(group_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
   }
   // actor dropout: one record per member (indexed like the GroupRecs; active = the member draws), step s at drop_step + s
   bool draws = false;
   if (g->flags & IQLHIP_GROUP_DROPOUT) {
-    GroupDropRec* d = (GroupDropRec*)(g->blob_pin + g->drop_off);
+    GroupDropRec* d = g->train.host(g->drops);
     for (int i = 0; i < g->k; ++i) {
       d[i] = group_drop_record(g->m[i], B);
       d[i].active = group_draws(g->m[i]) ? 1 : 0;
@@ -2612,13 +2633,13 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
   const int gather_nb = (int)std::min<int64_t>(((int64_t)B * (c0->row_ld / 4) + 255) / 256, 1024);
   // (a grid with a thread per gathered float4 and per keep-bit word: the words come from its far end)
   const int drop_nb = gather_nb + (2 * B * 8 + 255) / 256;
+  const GroupRec* recs = g->train.device(g->recs);
   for (int s = 0; s < n; ++s) {
     if (draws)
-      hipLaunchKernelGGL(iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev,
-                         (const GroupDropRec*)(g->blob_dev + g->drop_off), s);
+      hipLaunchKernelGGL(iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0, st, recs, g->train.device(g->drops), s);
     else
-      hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, (const GroupRec*)g->blob_dev, s);
-    group_launch_step(g, (const GroupRec*)g->blob_dev, q, s, st);
+      hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, recs, s);
+    group_launch_step(g, recs, q, s, st);
   }
   if (g->flags & IQLHIP_GROUP_DROPOUT)      // (iqlhip_train_steps moves every context's position, whatever its rate)
     for (int i = 0; i < g->k; ++i) g->m[i]->drop_step += (unsigned long long)n;
@@ -2670,12 +2691,13 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
   const int S = c0->dims.state_dim, A = c0->dims.action_dim;
   const bool gauss = c0->dims.policy == IQLHIP_POLICY_GAUSSIAN;
   const GroupGeom q = group_geom(c0, n, K);
-  GroupRec* recs = (GroupRec*)g->on_pin;
-  StepParams* aps = (StepParams*)(g->on_pin + g->on_act_off);
-  GroupOnlineRec* ons = (GroupOnlineRec*)(g->on_pin + g->on_gather_off);
-  GroupActRec* fins = (GroupActRec*)(g->on_pin + g->on_fin_off);
-  iqlhip_step_scalars* tab = (iqlhip_step_scalars*)(g->on_pin + g->on_tab_off);
-  const iqlhip_step_scalars* tab_dev = (const iqlhip_step_scalars*)(g->on_dev + g->on_tab_off);
+  const Staging& on = g->on;
+  GroupRec* recs = on.host(g->on_recs);
+  StepParams* aps = on.host(g->on_aps);
+  GroupOnlineRec* ons = on.host(g->on_gathers);
+  GroupActRec* fins = on.host(g->on_fins);
+  iqlhip_step_scalars* tab = on.host(g->on_tabs);
+  auto act_requested = [&](int i) { return act_state_host && (!act_mask || act_mask[i]); };
   int n_req = 0;
   for (int i = 0; i < K; ++i) {
     iqlhip_ctx* c = g->m[i];
@@ -2683,54 +2705,38 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
     memcpy(c->on_row_pin, row_host + (size_t)i * ld, (size_t)ld * sizeof(float));
     memcpy(c->on_idx_pin, idx_host + (size_t)i * n, (size_t)n * sizeof(long long));
     tab[i] = sc[i];
-    group_record(g, recs[i], i, q, n, 1, c->xb, &sc[i], tab_dev + i);
+    group_record(g, recs[i], i, q, n, 1, c->xb, &sc[i], on.device(g->on_tabs) + i);
     recs[i].u.losses_mirror = c->on_loss_pin;
-    const bool req = act_state_host && (!act_mask || act_mask[i]);
+    const bool req = act_requested(i);
     GroupOnlineRec& o = ons[i];
     o.rows = rows_dev[i]; o.row_pin = c->on_row_pin; o.idx_pin = c->on_idx_pin; o.xb = c->xb;
     o.act_pin = req ? c->on_act_pin : nullptr; o.xb_act = c->xb_act;
     o.ld = ld; o.pointer = pointer[i]; o.n = n; o.S = S;
     if (!req) continue;
     memcpy(c->on_act_pin, act_state_host + (size_t)i * S, (size_t)S * sizeof(float));
-    // the record actor_forward_impl passes for one row
-    StepParams p = make_step(c, 1, 1.f);
-    p.xb = c->xb_act;
-    p.only_inst = 6;
-    p.slot[6] = -1;
-    p.drop_bits = nullptr;
-    p.sc.heads = c->heads_act;
-    p.sc.max_batch = 0;
-    aps[n_req] = p;
+    aps[n_req] = act_step_params(c, 1);
     GroupActRec& f = fins[n_req];
     const bool noise = act_seed[i] != 0 && gauss;      // (the call counter moves only when noise is drawn, as solo)
-    f.heads = c->heads_act; f.log_std = p.log_std; f.out = c->on_act_pin + IQLHIP_MAX_INPUT;
+    f.heads = c->heads_act; f.log_std = aps[n_req].log_std; f.out = c->on_act_pin + IQLHIP_MAX_INPUT;
     f.max_action = max_action[i]; f.ls_min = c->hyper.log_std_min; f.ls_max = c->hyper.log_std_max;
     f.seed = noise ? act_seed[i] : 0ull;
     f.call = noise ? c->act_calls++ : 0ull;
     ++n_req;
   }
-  const int n_draw = group_drop_records_packed(g, (GroupDropRec*)(g->on_pin + g->on_drop_off), n);
+  const int n_draw = group_drop_records_packed(g, on.host(g->on_drops), n);
   // (a synchronous call: the previous one's upload has been read long ago)
-  HIPCHK(hipMemcpyAsync(g->on_dev, g->on_pin, g->on_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((n * (ld / 4) + 255) / 256);
-  hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st,
-                     (const GroupOnlineRec*)(g->on_dev + g->on_gather_off));
+  hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
-  group_launch_dropmask(g, (const GroupDropRec*)(g->on_dev + g->on_drop_off), n_draw, n, st);
-  group_launch_step(g, (const GroupRec*)g->on_dev, q, 0, st);
+  group_launch_dropmask(g, on.device(g->on_drops), n_draw, n, st);
+  group_launch_step(g, on.device(g->on_recs), q, 0, st);
   const unsigned long long done_val = ++g->done_seq;
   if (n_req > 0) {
     // (bf16: the update has just rewritten the shadows from the new masters — the conversion refresh_shadows makes)
-    const StepParams* ap = (const StepParams*)(g->on_dev + g->on_act_off);
-    const bool bf = c0->precision == 1, dma = c0->w0_lds_k > W0_LDS_MAX_K;
-    const dim3 ag(NSPLIT, n_req);
-    const size_t lds = fwd_lds(c0, NSPLIT);
-    if (bf) { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, true>), ag, dim3(256), lds, st, ap);
-              else hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, false>), ag, dim3(256), lds, st, ap); }
-    else    { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, true>), ag, dim3(256), lds, st, ap);
-              else hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, false>), ag, dim3(256), lds, st, ap); }
-    hipLaunchKernelGGL(iql_actor_finish_group_kernel, dim3(1), dim3(256), 0, st,
-                       (const GroupActRec*)(g->on_dev + g->on_fin_off), n_req, A, g->done_pin, done_val);
+    group_launch_act_fwd(c0, on.device(g->on_aps), NSPLIT, n_req, fwd_lds(c0, NSPLIT), st);
+    hipLaunchKernelGGL(iql_actor_finish_group_kernel, dim3(1), dim3(256), 0, st, on.device(g->on_fins), n_req, A, g->done_pin,
+                       done_val);
   } else {
     hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, g->done_pin, done_val);
   }
@@ -2741,8 +2747,7 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
   for (int i = 0; i < K; ++i) {
     const iqlhip_ctx* c = g->m[i];
     for (int j = 0; j < 3; ++j) out[3 * i + j] = c->on_loss_pin[j];
-    if (act_state_host && (!act_mask || act_mask[i]))
-      memcpy(act_out_host + (size_t)i * A, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
+    if (act_requested(i)) memcpy(act_out_host + (size_t)i * A, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
   }
   return IQLHIP_OK;
 }
@@ -2762,10 +2767,9 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
   const iqlhip_ctx* c0 = g->m[0];
   const int S = c0->dims.state_dim, A = c0->dims.action_dim;
   for (int i = 0; i < K; ++i) {
-    const iqlhip_ctx* c = g->m[i];
-    if (!c->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called", i);
-    if (rows[i] < 0 || rows[i] > c->act_cap)
-      return fail(IQLHIP_EINVAL, "member %d: rows %d outside [0, %d]", i, rows[i], c->act_cap);
+    if ((rc = group_check_bound(g, i))) return rc;
+    if (rows[i] < 0 || rows[i] > g->m[i]->act_cap)
+      return fail(IQLHIP_EINVAL, "member %d: rows %d outside [0, %d]", i, rows[i], g->m[i]->act_cap);
     if (rows[i] > 0 && (!states[i] || !actions[i])) return fail(IQLHIP_EINVAL, "member %d: NULL states or actions", i);
   }
   if (ld_s < S || ld_a < A) return fail(IQLHIP_EINVAL, "row stride smaller than the row");
@@ -2778,9 +2782,12 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
   if (n_req == 0) return IQLHIP_OK;
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
-  GroupPackRec* packs = (GroupPackRec*)g->act_host.data();
-  StepParams* ps = (StepParams*)(g->act_host.data() + g->act_fwd_off);
-  GroupActRowsRec* fins = (GroupActRowsRec*)(g->act_host.data() + g->act_fin_off);
+  Staging& act = g->act;
+  // (records are written field by field into act_host, whose padding bytes stay zero, or copied whole from a record
+  //  make_step has zeroed: the comparison below sees equal bytes for equal records)
+  GroupPackRec* packs = Staging::at(g->act_host.data(), g->act_packs);
+  StepParams* ps = Staging::at(g->act_host.data(), g->act_ps);
+  GroupActRowsRec* fins = Staging::at(g->act_host.data(), g->act_fins);
   int j = 0;
   for (int i = 0; i < K; ++i) {
     if (rows[i] == 0) continue;        // (no launch, no counter: the solo caller makes no call for no rows)
@@ -2788,46 +2795,31 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
     const int n = rows[i];
     GroupPackRec& pk = packs[j];
     pk.xb = c->xb_act; pk.s = states[i]; pk.ld_s = (long long)ld_s; pk.ld = (int)c->row_ld; pk.S = S; pk.n = n;
-    // the record actor_forward_impl passes
-    StepParams p = make_step(c, n, 1.f / (float)n);
-    p.xb = c->xb_act;
-    p.only_inst = 6;
-    p.slot[6] = -1;
-    p.drop_bits = nullptr;
-    p.sc.heads = c->heads_act;
-    p.sc.max_batch = 0;
-    ps[j] = p;
+    ps[j] = act_step_params(c, n);
     GroupActRowsRec& f = fins[j];
-    f.heads = c->heads_act; f.log_std = p.log_std; f.out = actions[i]; f.ld_out = (long long)ld_a; f.n = n; f.A = A;
+    f.heads = c->heads_act; f.log_std = ps[j].log_std; f.out = actions[i]; f.ld_out = (long long)ld_a; f.n = n; f.A = A;
     f.max_action = max_action[i]; f.ls_min = c->hyper.log_std_min; f.ls_max = c->hyper.log_std_max;
     f.seed = seeds[i];
     f.call = seeds[i] != 0 ? c->act_calls++ : 0ull;      // (iqlhip_actor_sample: one call number per call)
     ++j;
   }
-  if (memcmp(g->act_host.data(), g->act_last.data(), g->act_bytes) != 0) {
-    if (g->act_pending) HIPCHK(hipEventSynchronize(g->act_up));    // the previous upload has read act_pin
+  if (memcmp(g->act_host.data(), g->act_last.data(), act.bytes) != 0) {
+    if (g->act_pending) HIPCHK(hipEventSynchronize(g->act_up));    // the previous upload has read act.pin
     g->act_pending = false;
-    memcpy(g->act_pin, g->act_host.data(), g->act_bytes);
-    HIPCHK(hipMemcpyAsync(g->act_dev, g->act_pin, g->act_bytes, hipMemcpyHostToDevice, st));
+    memcpy(act.pin, g->act_host.data(), act.bytes);
+    HIPCHK(hipMemcpyAsync(act.dev, act.pin, act.bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(g->act_up, st));
     g->act_pending = true;
     g->act_last = g->act_host;
   }
   const int pack_nb = (int)std::min<int64_t>(((int64_t)max_rows * c0->row_ld + 255) / 256, 1024);
-  hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_req), dim3(256), 0, st, (const GroupPackRec*)g->act_dev);
+  hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_req), dim3(256), 0, st, act.device(g->act_packs));
   for (int i = 0; i < K; ++i)
     if (rows[i] > 0) refresh_shadows(g->m[i], st);
-  const StepParams* ap = (const StepParams*)(g->act_dev + g->act_fwd_off);
-  const bool bf = c0->precision == 1, dma = c0->w0_lds_k > W0_LDS_MAX_K;
   const int nbx = (max_rows + RT_ROWS - 1) / RT_ROWS * NSPLIT;
-  const dim3 ag(nbx, n_req);
-  const size_t lds = fwd_lds(c0, nbx * n_req);
-  if (bf) { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, true>), ag, dim3(256), lds, st, ap);
-            else hipLaunchKernelGGL((iql_act_fwd_group_kernel<true, false>), ag, dim3(256), lds, st, ap); }
-  else    { if (dma) hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, true>), ag, dim3(256), lds, st, ap);
-            else hipLaunchKernelGGL((iql_act_fwd_group_kernel<false, false>), ag, dim3(256), lds, st, ap); }
+  group_launch_act_fwd(c0, act.device(g->act_ps), nbx, n_req, fwd_lds(c0, nbx * n_req), st);
   hipLaunchKernelGGL(iql_actor_finish_rows_group_kernel, dim3((max_rows * A + 255) / 256, n_req), dim3(256), 0, st,
-                     (const GroupActRowsRec*)(g->act_dev + g->act_fin_off));
+                     act.device(g->act_fins));
   if (!(flags & IQLHIP_GROUP_ACT_WAIT)) {
     HIPCHK(hipGetLastError());
     return IQLHIP_OK;

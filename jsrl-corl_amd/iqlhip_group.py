@@ -136,6 +136,28 @@ class ImplicitQLearningGroup:
         return len(self.trainers)
 
     # ------------------------------------------------------------------ eager steps
+    def _next_scalars(self, inv_batch: float):
+        """Every member's scalars for its next step, and the Adam step counts they belong to (for _commit_step)."""
+        scs, adam_next = (hb.StepScalars * len(self.trainers))(), []
+        for k, t in enumerate(self.trainers):
+            t1 = {g: n + 1 for g, n in t._adam_t.items()}
+            t._fill_scalars(scs[k], t1, t._current_lrs(), inv_batch)
+            adam_next.append(t1)
+        return scs, adam_next
+
+    def _commit_step(self, adam_next, out) -> List[Dict[str, float]]:
+        """Move every member's counters and schedule past the step the library has taken; out: its losses [K][3]."""
+        logs = []
+        for k, t in enumerate(self.trainers):
+            t.total_it += 1
+            t._adam_t = adam_next[k]
+            t._advance_schedule(1)
+            t._ts_token = None
+            t._eager_next = None
+            logs.append({"value_loss": float(out[3 * k]), "q_loss": float(out[3 * k + 1]),
+                         "actor_loss": float(out[3 * k + 2])})
+        return logs
+
     def train(self, batches: Sequence) -> List[Dict[str, float]]:
         """One step per member on its own batch (ImplicitQLearning.train for each, in one set of launches).  All batches
         have the same number of rows.  Returns one losses dict per member."""
@@ -153,28 +175,17 @@ class ImplicitQLearningGroup:
             return [self.trainers[0].train(batches[0])]
         for t in self.trainers:
             t._prepare(B)
-        structs, keep, scs, t_after = (hb.Batch * K)(), [], (hb.StepScalars * K)(), []
+        structs, keep = (hb.Batch * K)(), []
         for i, (t, batch) in enumerate(zip(self.trainers, batches)):
             b, kp, _ = t._batch_struct(batch)
             structs[i] = b
             keep.append(kp)
-            t1 = {g: n + 1 for g, n in t._adam_t.items()}
-            t._fill_scalars(scs[i], t1, t._current_lrs(), 1.0 / B)
-            t_after.append(t1)
+        scs, adam_next = self._next_scalars(1.0 / B)
         out = (C.c_float * (3 * K))()
         g = self._group()
         hb.check(hb.lib().iqlhip_group_step(g, structs, scs, out, self.trainers[0]._stream()))
         del keep
-        logs = []
-        for i, t in enumerate(self.trainers):
-            t.total_it += 1
-            t._adam_t = t_after[i]
-            t._advance_schedule(1)
-            t._ts_token = None
-            t._eager_next = None
-            logs.append({"value_loss": float(out[3 * i]), "q_loss": float(out[3 * i + 1]),
-                         "actor_loss": float(out[3 * i + 2])})
-        return logs
+        return self._commit_step(adam_next, out)
 
     # ------------------------------------------------------------------ device-drawn steps
     def train_steps(self, buffers, n_steps: int, batch_size: int, seeds: Sequence[int],
@@ -308,11 +319,7 @@ class ImplicitQLearningGroup:
         for k in range(K):               # sample()'s draw over the size AFTER the insert
             rng = np.random if rngs is None else rngs[k]
             idx[k] = rng.randint(0, new_sizes[k], size=batch_size)
-        scs, adam_next = (hb.StepScalars * K)(), []
-        for k, t in enumerate(self.trainers):
-            t1 = {g: n + 1 for g, n in t._adam_t.items()}
-            t._fill_scalars(scs[k], t1, t._current_lrs(), 1.0 / batch_size)
-            adam_next.append(t1)
+        scs, adam_next = self._next_scalars(1.0 / batch_size)
         out = (C.c_float * (3 * K))()
         ring_ptrs = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
         caps = (C.c_int64 * K)(*[b._buffer_size for b in bufs])
@@ -326,18 +333,11 @@ class ImplicitQLearningGroup:
                                                batch_size, scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds),
                                                addr(a_out), t0._stream())
         hb.check(rc)
-        logs = []
-        for k, (t, buf) in enumerate(zip(self.trainers, bufs)):
+        for k, buf in enumerate(bufs):
             buf._writes += 1
             buf._pointer = (pointers[k] + 1) % buf._buffer_size
             buf._size = new_sizes[k]
-            t.total_it += 1
-            t._adam_t = adam_next[k]
-            t._advance_schedule(1)
-            t._ts_token = None
-            t._eager_next = None
-            logs.append({"value_loss": float(out[3 * k]), "q_loss": float(out[3 * k + 1]),
-                         "actor_loss": float(out[3 * k + 2])})
+        logs = self._commit_step(adam_next, out)
         if act_next is None:
             return logs
         return logs, [a_out[k].copy() if k in want else None for k in range(K)]
