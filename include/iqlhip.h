@@ -188,16 +188,24 @@ int64_t iqlhip_grad_words(const iqlhip_ctx* ctx);   /* n_params + 4 */
 
 /* n_steps consecutive `sample -> train` iterations without host round trips: row indices are drawn on the device
  * (Philox4x32-10, uniform with replacement over [0,size) like np.random.randint at iql.py:172; index j of the call comes
- * from counter stream_offset + j / 2), per-step scalars come from `sc` (host array of n_steps, free again on return).
+ * from counter stream_offset + j / 2, modulo 2^64: counter words (lo32, hi32, 0x49514C48, 0), key (lo32 seed, hi32 seed);
+ * an even j takes output words o1:o0, an odd j o3:o2 as 64 random bits r, index = floor(r * size / 2^64); step k of the
+ * call trains on indices k * batch_rows .. (k + 1) * batch_rows - 1.  A call consumes ceil(n_steps * batch_rows / 2)
+ * counters.  With an odd batch_rows a step's first index alternates between a counter's two word pairs, and a caller
+ * that starts every call on a fresh counter — the Python shim passes stream_offset = total_it * ceil(batch_rows / 2) —
+ * does not continue the previous call's stream: the rows drawn then depend on how the steps are split into calls (with
+ * an even batch_rows they do not).  DESIGN.md "Random streams" has all four device streams),
+ * per-step scalars come from `sc` (host array of n_steps, free again on return).
  * The loss of every step is kept in a device ring read by iqlhip_read_loss_ring.
  * Replaces the offline loop body sample()->train() (algorithms/offline/iql.py:631-635).
  * A call = one set-up launch + replays of fixed chunk graphs (IQLHIP_GRAPH_STEPS = 64 steps, 16, 4, 2, 1) that chain on
  * the device; nothing is captured per value of n_steps.
  * flags: IQLHIP_TS_CONTINUE — the caller states that the replay rows have not been written since the previous
  * iqlhip_train_steps call; if that call ended where this one starts (same rows / size / batch_rows / seed,
- * stream_offset = its offset + n_steps * batch_rows / 2, an even n_steps, no other step entry point in between — the
- * library checks all of that) the rows its last forward staged for "the next step" ARE this call's step 0 and nothing
- * is gathered up front.  Results are identical with and without the flag. */
+ * stream_offset = its offset + n_steps * batch_rows / 2 exactly, an even n_steps (so that n_steps * batch_rows is even
+ * and the previous call ended on a whole counter), no other step entry point in between — the library checks all of
+ * that) the rows its last forward staged for "the next step" ARE this call's step 0 and nothing is gathered up front.
+ * Results are identical with and without the flag: it never changes which rows a (seed, stream_offset) pair draws. */
 #define IQLHIP_TS_CONTINUE 1
 int iqlhip_train_steps(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int64_t size, int32_t batch_rows,
                        const iqlhip_step_scalars* sc, int32_t n_steps, uint64_t seed, uint64_t stream_offset,
