@@ -140,6 +140,21 @@ int iqlhip_set_dropout(iqlhip_ctx* ctx, float p, uint64_t seed);
  * replaced and set them on its successor, so that neither random stream restarts mid-run. */
 int iqlhip_get_counters(const iqlhip_ctx* ctx, uint64_t out[2]);
 int iqlhip_set_counters(iqlhip_ctx* ctx, const uint64_t in[2]);
+/* Actor dropout INSIDE policy inference (the online loop asks a training-mode actor for its next action, algorithms/
+ * finetune/iql.py:725-738: the nn.Dropout layers are live): p in [0,1), 0 = off (the default: every inference entry
+ * point then behaves and launches exactly as without this call).  Independent of iqlhip_set_dropout — the training
+ * rate stays what it is.  With p > 0, iqlhip_actor_forward, iqlhip_actor_sample, the act forward of iqlhip_online_step,
+ * and — member by member, each with its own rate, key and position — iqlhip_group_actor_forward and the act forward of
+ * iqlhip_group_online_step draw the call's keep-bits on the device and run the policy forward with them (keep scale
+ * 1.f / (1.f - p)).  A stream of its own: Philox4x32-10, key `seed`, counter words (w, j | 0x41445250 "ADRP", lo32 n,
+ * hi32 n), j = 0..7, w = row * 16 + layer * 8 + q (rows restart at 0 with every library call), bit 4 j + t of the word
+ * = (output t >= p * 2^32), bit b = hidden unit 32 q + b; n = the context's position, which moves by one with every
+ * library inference call that draws (rate > 0, rows > 0, arguments accepted).  The bits live in a buffer of their own
+ * (never the training steps'); allocated by the first call with p > 0. */
+int iqlhip_set_act_dropout(iqlhip_ctx* ctx, float p, uint64_t seed);
+/* That stream's position n (iqlhip_get_counters / iqlhip_set_counters keep their two words). */
+int iqlhip_get_act_dropout_counter(const iqlhip_ctx* ctx, uint64_t* out);
+int iqlhip_set_act_dropout_counter(iqlhip_ctx* ctx, uint64_t n);
 /* Tests: inject keep-bits for the next steps instead of drawing them ([rows][8] uint32 per layer, bit j of
  * word w = hidden unit 32w + j); cleared by the next iqlhip_set_dropout. */
 int iqlhip_debug_write_masks(iqlhip_ctx* ctx, const uint32_t* keep0_host, const uint32_t* keep1_host, int32_t rows,
@@ -326,7 +341,8 @@ int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out);
  * the member's threshold, position drop_step — in the group's own launches, and moves the position as the solo call
  * does: iqlhip_group_step / iqlhip_group_online_step by one for a member that draws, iqlhip_group_train_steps by n
  * for every member.  Masks written by iqlhip_debug_write_masks are kept (no draw for that member).  The inference
- * forwards stay eval-mode.  Unknown flag bits: IQLHIP_EINVAL, checked before any member is looked at; *out is
+ * forwards are eval-mode for every member without an inference rate (iqlhip_set_act_dropout; a member with one needs
+ * this flag too).  Unknown flag bits: IQLHIP_EINVAL, checked before any member is looked at; *out is
  * written on success only. */
 #define IQLHIP_GROUP_DROPOUT 1
 int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int32_t flags, iqlhip_group** out);
@@ -363,7 +379,8 @@ int iqlhip_group_online_step(iqlhip_group* group, float* const* rows_dev, int64_
  * or iqlhip_actor_sample (seeds[k] != 0: device N(0,1) noise, member k's act() call counter advances by one) on that
  * member would, with max_action[k].  rows[k] == 0 skips member k and leaves its counter alone.  rows[k] <=
  * max(max_batch_k, IQLHIP_ACT_ROWS).  states / actions may be device memory or host-mapped pinned memory.  Eval-mode
- * forward (no dropout).  Checked before any device work or counter change: NULL arguments, unbound members, row
+ * forward, except for members with an inference rate (iqlhip_set_act_dropout): those draw their keep-bits as their solo
+ * call would, in the same launches.  Checked before any device work or counter change: NULL arguments, unbound members, row
  * counts, strides, NULL pointers of members with rows, the group rules, unknown flags.  Asynchronous on `stream`
  * (successive calls of one group on one stream); flags & IQLHIP_GROUP_ACT_WAIT: returns once every action is written
  * (the host spins on a completion word instead of synchronising the stream: the form for host-mapped actions). */
@@ -377,8 +394,8 @@ int iqlhip_group_actor_forward(iqlhip_group* group, const float* const* states, 
  * forward of evaluation loops (eval_actor, jsrl_w_iql.py:62-179):
  *   actions[r] = clamp(max_action * (tanh(MLP_pi(states[r])) + exp(clamp(log_std)) * noise[r]), -max_action, max_action)
  * noise_dev == NULL gives the mean (eval mode, or the deterministic policy); with a Gaussian policy in training mode
- * the caller passes standard-normal noise [rows][action_dim] (dist.sample() of iql.py:376).  Dropout is NOT applied
- * (eval-mode forward).  rows <= max(max_batch, IQLHIP_ACT_ROWS) per call.  Uses the bound parameter arena;
+ * the caller passes standard-normal noise [rows][action_dim] (dist.sample() of iql.py:376).  Dropout is applied only at
+ * the rate iqlhip_set_act_dropout has set (default 0: eval-mode forward).  rows <= max(max_batch, IQLHIP_ACT_ROWS) per call.  Uses the bound parameter arena;
  * asynchronous on `stream`.  states / noise / actions may be device memory or host-mapped (pinned) memory. */
 #define IQLHIP_ACT_ROWS 4096
 int iqlhip_actor_forward(iqlhip_ctx* ctx, const float* states_dev, int64_t ld_s, int32_t rows, const float* noise_dev,
@@ -396,7 +413,9 @@ int iqlhip_stream_synchronize(void* stream);
 /* ---- introspection (tests, profiling) ----------------------------------- */
 /* Copy a named library-owned scratch array to host (synchronous).  Names:
  * "h0","h1" (activations [4][max_batch][256]), "heads" (partial head sums),
- * "grads" (flat summed gradient, n_params), "loss_parts". */
+ * "grads" (flat summed gradient, n_params), "loss_parts", "drop_bits" (the training steps' keep-bit words,
+ * [2 layers][max_batch][8]), "act_drop_bits" (the last inference call's, [2 layers][max(max_batch, IQLHIP_ACT_ROWS)][8];
+ * only after iqlhip_set_act_dropout with p > 0). */
 int iqlhip_debug_read(iqlhip_ctx* ctx, const char* name, float* host_out, int64_t max_floats, int64_t* n_out,
                       void* stream);
 /* Micro-benchmark hook: `repeat` back-to-back launches of one kernel of the step (0 fwd, 1 bwd,

@@ -163,6 +163,11 @@ struct iqlhip_ctx {
   float drop_p = 0.f;
   unsigned long long drop_seed = 0, drop_step = 0;
   bool drop_inject = false;           // tests: masks were written by iqlhip_debug_write_masks, do not regenerate
+  // actor dropout inside policy inference (iqlhip_set_act_dropout): a rate, key, position and buffer of its own
+  unsigned* act_drop_bits = nullptr;  // [2 layers][act_cap][8] keep-bits of the last inference call that drew (allocated
+                                      // by the first iqlhip_set_act_dropout with p > 0)
+  float act_drop_p = 0.f;
+  unsigned long long act_drop_seed = 0, act_drop_calls = 0;
   int precision = 0;                  // 0: fp32 MFMA everywhere; 1: bf16 operands for the layer-0/1, dW1, dH0, dW0 products
   __bf16* wsh = nullptr;              // bf16 path: shadow of the parameter arena [n_params] (W1 is read from it) ...
   __bf16* tsh = nullptr;              // ... and of the target arena [n_target]; written by the update kernel, refreshed
@@ -448,7 +453,7 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
   void* bufs[] = {c->sc.h0, c->sc.h1, c->sc.heads, c->sc.slab_a, c->sc.slab_b, c->sc.loss_parts, c->sc.losses,
                   c->flat_tmp, c->sched_call, c->sched_cur, c->hdr, c->stamps, c->xb, c->xb2, c->xb_act,
-                  c->heads_act, c->drop_bits, c->xstatus, c->xflat, c->wsh, c->tsh, c->pi_t, c->dh1g, c->slab_x, c->wimg};
+                  c->heads_act, c->drop_bits, c->act_drop_bits, c->xstatus, c->xflat, c->wsh, c->tsh, c->pi_t, c->dh1g, c->slab_x, c->wimg};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < 4; ++i) {
     if (c->sched_pin[i]) (void)hipHostFree(c->sched_pin[i]);
@@ -517,6 +522,32 @@ extern "C" int iqlhip_set_dropout(iqlhip_ctx* c, float p, uint64_t seed) {
   c->drop_p = p;
   c->drop_seed = seed;
   c->drop_inject = false;
+  return IQLHIP_OK;
+}
+
+// The inference side of actor dropout: its own rate and key (the training rate above is untouched), position
+// act_drop_calls.  The keep-bit buffer is allocated with the first rate > 0.
+extern "C" int iqlhip_set_act_dropout(iqlhip_ctx* c, float p, uint64_t seed) {
+  if (!c) return fail(IQLHIP_EINVAL, "NULL ctx");
+  if (!(p >= 0.f && p < 1.f)) return fail(IQLHIP_EINVAL, "dropout probability must be in [0,1)");
+  if (p > 0.f && !c->act_drop_bits) {
+    DevGuard guard(c->device);
+    const size_t bytes = (size_t)2 * c->act_cap * 8 * sizeof(unsigned);
+    HIPCHK(hipMalloc((void**)&c->act_drop_bits, bytes));
+    HIPCHK(hipMemset(c->act_drop_bits, 0xFF, bytes));
+  }
+  c->act_drop_p = p;
+  c->act_drop_seed = seed;
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_get_act_dropout_counter(const iqlhip_ctx* c, uint64_t* out) {
+  if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  *out = c->act_drop_calls;
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_set_act_dropout_counter(iqlhip_ctx* c, uint64_t n) {
+  if (!c) return fail(IQLHIP_EINVAL, "NULL ctx");
+  c->act_drop_calls = n;
   return IQLHIP_OK;
 }
 
@@ -712,9 +743,18 @@ static StepParams act_step_params(const iqlhip_ctx* c, int rows) {
   p.xb = c->xb_act;
   p.only_inst = 6;
   p.slot[6] = -1;            // inference keeps no activations
-  p.drop_bits = nullptr;     // eval-mode forward; a training-mode policy with dropout stays on the caller's side
+  p.drop_bits = nullptr;     // the training steps' keep-bits are not the inference forward's
+  p.drop_scale = 1.f;
   p.sc.heads = c->heads_act; // the policy partials of row r land at heads[max_batch * HEAD_LD + r * A * NSPLIT ...]:
   p.sc.max_batch = 0;        // with max_batch = 0 that is heads_act[r * A * NSPLIT ...]
+  if (c->act_drop_p > 0.f) {
+    // inference with dropout: the forward reads layer 1's keep-bits at row max_batch + r of drop_bits, so max_batch
+    // is the layer stride of act_drop_bits (act_cap) and the heads pointer is moved back by what that adds
+    p.drop_bits = c->act_drop_bits;
+    p.drop_scale = 1.f / (1.f - c->act_drop_p);
+    p.sc.max_batch = c->act_cap;
+    p.sc.heads = c->heads_act - (size_t)c->act_cap * HEAD_LD;
+  }
   return p;
 }
 
@@ -870,6 +910,22 @@ static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
 static unsigned drop_thresh(float p) {
   const double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
+}
+
+// The keep-bit draw of one inference call on `rows` rows at the context's current position (active = 0: rate 0,
+// nothing is drawn and the position stays).
+static ActDropRec act_drop_record(const iqlhip_ctx* c, int rows) {
+  ActDropRec d;
+  memset(&d, 0, sizeof d);
+  d.active = (c->act_drop_p > 0.f && rows > 0) ? 1 : 0;
+  if (!d.active) return d;
+  d.bits = c->act_drop_bits;
+  d.n_rows = rows;
+  d.cap = c->act_cap;
+  d.thresh = drop_thresh(c->act_drop_p);
+  d.seed = c->act_drop_seed;
+  d.call = c->act_drop_calls;
+  return d;
 }
 
 static void launch_dropmask(const iqlhip_ctx* c, unsigned long long seed, unsigned long long step,
@@ -2130,8 +2186,15 @@ static int actor_forward_impl(iqlhip_ctx* c, const float* states_dev, int64_t ld
   if (rows == 0) return IQLHIP_OK;
   hipStream_t st = (hipStream_t)stream;
   const int total = rows * (int)c->row_ld;
-  hipLaunchKernelGGL(iql_pack_states_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c->xb_act, (int)c->row_ld, S,
-                     rows, states_dev, (long long)ld_s);
+  const ActDropRec drop = act_drop_record(c, rows);
+  if (drop.active) {       // the call's keep-bits come from the packing launch; the stream moves on by one call
+    hipLaunchKernelGGL(iql_pack_states_drop_kernel, dim3((total + 255) / 256 + (2 * rows * 8 + 255) / 256), dim3(256), 0, st,
+                       c->xb_act, (int)c->row_ld, S, rows, states_dev, (long long)ld_s, drop);
+    c->act_drop_calls += 1;
+  } else {
+    hipLaunchKernelGGL(iql_pack_states_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c->xb_act, (int)c->row_ld, S,
+                       rows, states_dev, (long long)ld_s);
+  }
   refresh_shadows(c, st);
   const StepParams p = act_step_params(c, rows);
   const int n_rt = (rows + RT_ROWS - 1) / RT_ROWS;
@@ -2217,6 +2280,10 @@ extern "C" int iqlhip_debug_read(iqlhip_ctx* c, const char* name, float* host_ou
   else if (!strcmp(name, "heads")) { src = c->sc.heads; n = (int64_t)MB * HEAD_LD + (int64_t)NSPLIT * MB * c->dims.action_dim; }
   else if (!strcmp(name, "loss_parts")) { src = c->sc.loss_parts; n = 4 * 64; }
   else if (!strcmp(name, "drop_bits")) { src = (const float*)c->drop_bits; n = (int64_t)2 * MB * 8; }
+  else if (!strcmp(name, "act_drop_bits")) {
+    if (!c->act_drop_bits) return fail(IQLHIP_EINVAL, "no inference keep-bits: iqlhip_set_act_dropout has set no rate > 0");
+    src = (const float*)c->act_drop_bits; n = (int64_t)2 * c->act_cap * 8;
+  }
   else if (!strcmp(name, "stamps")) {   // 64-bit stamps returned as pairs of 32-bit words
     if (!c->stamps) return fail(IQLHIP_EINVAL, "library built without -DIQL_STAMPS");
     src = (const float*)c->stamps; n = 4096 * 16 * 2;
@@ -2284,7 +2351,7 @@ struct iqlhip_group {
   // and one row of scalars per agent
   Staging on;
   Section<GroupRec> on_recs; Section<StepParams> on_aps; Section<GroupOnlineRec> on_gathers; Section<GroupActRec> on_fins;
-  Section<GroupDropRec> on_drops; Section<iqlhip_step_scalars> on_tabs;
+  Section<GroupDropRec> on_drops; Section<ActDropRec> on_adrops; Section<iqlhip_step_scalars> on_tabs;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
   // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in act_host (the
@@ -2292,6 +2359,7 @@ struct iqlhip_group {
   // calls repeat theirs.  (An asynchronous call: the next upload waits for act_up, this one's, before it rewrites act.pin.)
   Staging act;
   Section<GroupPackRec> act_packs; Section<StepParams> act_ps; Section<GroupActRowsRec> act_fins;
+  Section<ActDropRec> act_drops;      // (IQLHIP_GROUP_DROPOUT groups: the inference keep-bit draws, indexed like act_packs)
   std::vector<char> act_host, act_last;
   hipEvent_t act_up = nullptr;
   bool act_pending = false;
@@ -2314,7 +2382,7 @@ static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
     if (c->precision != a->precision) return fail(IQLHIP_EINVAL, "member %d has another precision than member 0", i);
     if (c->xch_mode != IQLHIP_XCH_NONE || c->world > 1)
       return fail(IQLHIP_EUNSUPPORTED, "member %d has data parallelism enabled (not supported in a group)", i);
-    if (c->drop_p > 0.f && !(flags & IQLHIP_GROUP_DROPOUT))
+    if ((c->drop_p > 0.f || c->act_drop_p > 0.f) && !(flags & IQLHIP_GROUP_DROPOUT))
       return fail(IQLHIP_EUNSUPPORTED, "member %d uses actor dropout (not supported in a group)", i);
   }
   return IQLHIP_OK;
@@ -2368,10 +2436,12 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->on_gathers = g->on.add<GroupOnlineRec>(k);
     g->on_fins = g->on.add<GroupActRec>(k);
     g->on_drops = g->on.add<GroupDropRec>(n_drop);
+    g->on_adrops = g->on.add<ActDropRec>(n_drop);
     g->on_tabs = g->on.add<iqlhip_step_scalars>(k);
     g->act_packs = g->act.add<GroupPackRec>(k);
     g->act_ps = g->act.add<StepParams>(k);
     g->act_fins = g->act.add<GroupActRowsRec>(k);
+    g->act_drops = g->act.add<ActDropRec>(n_drop);
     for (Staging* s : {&g->train, &g->on, &g->act})
       if (int rc_s = s->alloc()) return rc_s;
     g->act_host.assign(g->act.bytes, 0);
@@ -2698,6 +2768,10 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
   GroupActRec* fins = on.host(g->on_fins);
   iqlhip_step_scalars* tab = on.host(g->on_tabs);
   auto act_requested = [&](int i) { return act_state_host && (!act_mask || act_mask[i]); };
+  // inference keep-bits of the requesting members whose act forward runs with dropout (one record per member)
+  const bool with_adrops = (g->flags & IQLHIP_GROUP_DROPOUT) != 0;
+  ActDropRec* adrops = with_adrops ? on.host(g->on_adrops) : nullptr;
+  bool act_draws = false;
   int n_req = 0;
   for (int i = 0; i < K; ++i) {
     iqlhip_ctx* c = g->m[i];
@@ -2712,9 +2786,11 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
     o.rows = rows_dev[i]; o.row_pin = c->on_row_pin; o.idx_pin = c->on_idx_pin; o.xb = c->xb;
     o.act_pin = req ? c->on_act_pin : nullptr; o.xb_act = c->xb_act;
     o.ld = ld; o.pointer = pointer[i]; o.n = n; o.S = S;
+    if (with_adrops) adrops[i] = act_drop_record(c, req ? 1 : 0);
     if (!req) continue;
     memcpy(c->on_act_pin, act_state_host + (size_t)i * S, (size_t)S * sizeof(float));
     aps[n_req] = act_step_params(c, 1);
+    if (with_adrops && adrops[i].active) { act_draws = true; c->act_drop_calls += 1; }
     GroupActRec& f = fins[n_req];
     const bool noise = act_seed[i] != 0 && gauss;      // (the call counter moves only when noise is drawn, as solo)
     f.heads = c->heads_act; f.log_std = aps[n_req].log_std; f.out = c->on_act_pin + IQLHIP_MAX_INPUT;
@@ -2727,7 +2803,11 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
   // (a synchronous call: the previous one's upload has been read long ago)
   HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((n * (ld / 4) + 255) / 256);
-  hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
+  if (act_draws)
+    hipLaunchKernelGGL(iql_online_gather_drop_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers),
+                       on.device(g->on_adrops));
+  else
+    hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
   group_launch_dropmask(g, on.device(g->on_drops), n_draw, n, st);
   group_launch_step(g, on.device(g->on_recs), q, 0, st);
@@ -2788,6 +2868,9 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
   GroupPackRec* packs = Staging::at(g->act_host.data(), g->act_packs);
   StepParams* ps = Staging::at(g->act_host.data(), g->act_ps);
   GroupActRowsRec* fins = Staging::at(g->act_host.data(), g->act_fins);
+  const bool with_drops = (g->flags & IQLHIP_GROUP_DROPOUT) != 0;
+  ActDropRec* drops = with_drops ? Staging::at(g->act_host.data(), g->act_drops) : nullptr;
+  bool act_draws = false;
   int j = 0;
   for (int i = 0; i < K; ++i) {
     if (rows[i] == 0) continue;        // (no launch, no counter: the solo caller makes no call for no rows)
@@ -2796,6 +2879,10 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
     GroupPackRec& pk = packs[j];
     pk.xb = c->xb_act; pk.s = states[i]; pk.ld_s = (long long)ld_s; pk.ld = (int)c->row_ld; pk.S = S; pk.n = n;
     ps[j] = act_step_params(c, n);
+    if (with_drops) {
+      drops[j] = act_drop_record(c, n);
+      if (drops[j].active) { act_draws = true; c->act_drop_calls += 1; }
+    }
     GroupActRowsRec& f = fins[j];
     f.heads = c->heads_act; f.log_std = ps[j].log_std; f.out = actions[i]; f.ld_out = (long long)ld_a; f.n = n; f.A = A;
     f.max_action = max_action[i]; f.ls_min = c->hyper.log_std_min; f.ls_max = c->hyper.log_std_max;
@@ -2813,7 +2900,11 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
     g->act_last = g->act_host;
   }
   const int pack_nb = (int)std::min<int64_t>(((int64_t)max_rows * c0->row_ld + 255) / 256, 1024);
-  hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_req), dim3(256), 0, st, act.device(g->act_packs));
+  if (act_draws)           // (a grid with blocks for the longest member's keep-bit words at its far end)
+    hipLaunchKernelGGL(iql_pack_states_drop_group_kernel, dim3(pack_nb + (2 * max_rows * 8 + 255) / 256, n_req), dim3(256), 0,
+                       st, act.device(g->act_packs), act.device(g->act_drops));
+  else
+    hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_req), dim3(256), 0, st, act.device(g->act_packs));
   for (int i = 0; i < K; ++i)
     if (rows[i] > 0) refresh_shadows(g->m[i], st);
   const int nbx = (max_rows + RT_ROWS - 1) / RT_ROWS * NSPLIT;

@@ -294,19 +294,24 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 
 // Dropout keep-bits for one step: word w (of n_words = 2 * max_batch * 8) gets 32 independent Bernoulli(1-p)
 // bits: keep iff u32 >= thresh (thresh = p * 2^32).  Stream: key = seed, counter = (word, call, step).
+// (keep_word: the 32 bits of stream word w at position pos — eight counters (w, j | tag, lo32 pos, hi32 pos), bit
+//  4 j + t = (output t >= thresh); the training stream's tag is "DROP", the inference stream's "ADRP")
+__device__ __forceinline__ unsigned keep_word(uint32_t w, uint32_t tag, unsigned thresh, unsigned long long seed,
+                                              unsigned long long pos) {
+  unsigned word = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    uint32_t c[4] = {w, (uint32_t)j | tag, (uint32_t)pos, (uint32_t)(pos >> 32)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) word |= (c[q] >= thresh ? 1u : 0u) << (4 * j + q);
+  }
+  return word;
+}
 __device__ __forceinline__ void dropmask_words(unsigned* bits, int n_words, unsigned thresh, unsigned long long seed,
                                                unsigned long long step, int first, int stride) {
-  for (int w = first; w < n_words; w += stride) {
-    unsigned word = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      uint32_t c[4] = {(uint32_t)w, (uint32_t)j | 0x44524F50u /* "DROP" */, (uint32_t)step, (uint32_t)(step >> 32)};
-      philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) word |= (c[q] >= thresh ? 1u : 0u) << (4 * j + q);
-    }
-    bits[w] = word;
-  }
+  for (int w = first; w < n_words; w += stride)
+    bits[w] = keep_word((uint32_t)w, 0x44524F50u /* "DROP" */, thresh, seed, step);
 }
 
 // Index j of a call's draw: Philox4x32-10, counter = ctr0 + j / 2, key = seed; the counter's four words give two
@@ -1120,13 +1125,46 @@ __global__ __launch_bounds__(256) void iql_gather_drop_group_kernel(const GroupR
 // states -> packed rows whose first S columns are the state (the rest zero), then iql_fwd_kernel with
 // only_inst = 6, then this finish kernel over the policy head partials:
 //   action = clamp(max_action * (tanh(pre) [+ exp(clamp(log_std)) * noise]), -max_action, +max_action)
-__global__ void iql_pack_states_kernel(float* xb, int ld, int S, int n, const float* s, long long ld_s) {
+__device__ __forceinline__ void pack_states(float* xb, int ld, int S, int n, const float* s, long long ld_s) {
   const int total = n * ld;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     const int i = e / ld;
     const int c = e - i * ld;
     xb[e] = (c < S) ? s[i * ld_s + c] : 0.f;
   }
+}
+__global__ void iql_pack_states_kernel(float* xb, int ld, int S, int n, const float* s, long long ld_s) {
+  pack_states(xb, ld, S, n, s, ld_s);
+}
+
+// Actor dropout inside policy inference (iqlhip_set_act_dropout): the keep-bits of ONE inference call, a stream of
+// its own — tag "ADRP", position = the context's act_drop_calls, stream word = row * 16 + layer * 8 + q (no buffer
+// size in it) — drawn into the context's act_drop_bits [2 layers][cap][8], which only the inference forward reads
+// (the training steps' drop_bits are never written here: a chunk graph has pre-drawn the next step's parity there).
+// Only rows < n_rows are drawn, by the launch that packs the call's states: the packing takes the first blocks, the
+// words come from the far end of the grid (idle_block_work's split).
+struct ActDropRec {
+  unsigned* bits;                     // the context's act_drop_bits
+  int n_rows;                         // rows of the call
+  int cap;                            // rows per layer of `bits` (the context's act capacity)
+  unsigned thresh;                    // drop_thresh(p)
+  int active;                         // 0: nothing to draw (rate 0)
+  unsigned long long seed, call;      // key, and the call's position in the stream
+};
+__device__ __forceinline__ void act_drop_words(const ActDropRec& d, int first, int stride) {
+  const int per = d.n_rows * 8;
+  for (int v = first; v < 2 * per; v += stride) {
+    const int layer = (v >= per) ? 1 : 0, rq = v - layer * per;       // rq = row * 8 + q
+    const uint32_t w = (uint32_t)((rq >> 3) * 16 + layer * 8 + (rq & 7));
+    d.bits[layer * d.cap * 8 + rq] = keep_word(w, 0x41445250u /* "ADRP" */, d.thresh, d.seed, d.call);
+  }
+}
+// iql_pack_states_kernel plus the call's keep-bits (launched instead of it only when the context's inference rate
+// is > 0; the grid has a thread per packed element and per keep-bit word)
+__global__ __launch_bounds__(256) void iql_pack_states_drop_kernel(float* xb, int ld, int S, int n, const float* s,
+                                                                   long long ld_s, ActDropRec d) {
+  pack_states(xb, ld, S, n, s, ld_s);
+  act_drop_words(d, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
 }
 
 // noise: caller-supplied N(0,1) values, or — rng_seed != 0 — drawn here: Philox4x32-10 keyed by the seed, counter
@@ -1391,9 +1429,8 @@ struct GroupActRec {
 // iql_online_gather_kernel per member: the ring write, the gather from pinned indices (an index equal to `pointer`
 // reads the new row from the pinned copy), and — members that asked for an action — the packing of the act state into
 // xb_act that iql_pack_states_kernel does for one row (block 0).  Every member has the same n and ld (one grid).
-__global__ __launch_bounds__(256) void iql_online_gather_group_kernel(const GroupOnlineRec* __restrict__ recs) {
+__device__ __forceinline__ void online_gather_member(const GroupOnlineRec& g) {
   __shared__ long long s_idx[260];
-  const GroupOnlineRec& g = recs[blockIdx.y];
   float* rows = g.rows;
   const float* row_host = g.row_pin;
   const long long ld = g.ld, pointer = g.pointer;
@@ -1417,6 +1454,18 @@ __global__ __launch_bounds__(256) void iql_online_gather_group_kernel(const Grou
     const float* src = (i == pointer) ? row_host : rows + i * ld;
     *(f32x4*)(g.xb + (long long)r * ld + 4 * c4) = *(const f32x4*)(src + 4 * c4);
   }
+}
+__global__ __launch_bounds__(256) void iql_online_gather_group_kernel(const GroupOnlineRec* __restrict__ recs) {
+  online_gather_member(recs[blockIdx.y]);
+}
+// ... plus the keep-bits of the act forwards that run with dropout (drops[member]; launched instead of the kernel
+// above only when some requesting member's inference rate is > 0): one row's 16 words, from the far end of the grid.
+__global__ __launch_bounds__(256) void iql_online_gather_drop_group_kernel(const GroupOnlineRec* __restrict__ recs,
+                                                                           const ActDropRec* __restrict__ drops) {
+  online_gather_member(recs[blockIdx.y]);
+  const ActDropRec& d = drops[blockIdx.y];
+  if (d.active)
+    act_drop_words(d, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
 }
 
 // The policy-inference forward (iql_fwd_kernel<BF16, W0DMA, false, true>: only_inst = 6, blockIdx.x = row tile *
@@ -1472,12 +1521,17 @@ struct GroupActRowsRec {              // iql_actor_finish_kernel's arguments (no
 // iql_pack_states_kernel per member (grid.y): grid.x strides over the longest member's n * ld elements.
 __global__ __launch_bounds__(256) void iql_pack_states_group_kernel(const GroupPackRec* __restrict__ recs) {
   const GroupPackRec& r = recs[blockIdx.y];
-  const int ld = r.ld, S = r.S, total = r.n * ld;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const int i = e / ld;
-    const int c = e - i * ld;
-    r.xb[e] = (c < S) ? r.s[i * r.ld_s + c] : 0.f;
-  }
+  pack_states(r.xb, r.ld, r.S, r.n, r.s, r.ld_s);
+}
+// ... plus the call's keep-bits of the requesting members whose inference rate is > 0 (drops[j] belongs to packs[j];
+// launched instead of the kernel above only when there is such a member).
+__global__ __launch_bounds__(256) void iql_pack_states_drop_group_kernel(const GroupPackRec* __restrict__ recs,
+                                                                         const ActDropRec* __restrict__ drops) {
+  const GroupPackRec& r = recs[blockIdx.y];
+  pack_states(r.xb, r.ld, r.S, r.n, r.s, r.ld_s);
+  const ActDropRec& d = drops[blockIdx.y];
+  if (d.active)
+    act_drop_words(d, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
 }
 
 // iql_actor_finish_kernel per member (grid.y) over its n rows: element e = row * A + d, numbered as there, so the

@@ -32,7 +32,9 @@ ImplicitQLearning.set_dropout_seed(seed) was called: the members of a sweep shar
 with distinct seeds (as above), or they all draw the same masks.  Without actor_dropout=True a group behaves exactly
 as before the option existed: a member in training mode with dropout > 0 is refused (NotImplementedError).  The
 inference forwards are eval-mode: online_step(act_next=...) and act() for a member that is in training mode with
-dropout > 0 raise NotImplementedError, as the solo online_step does.
+dropout > 0 raise NotImplementedError, as the solo online_step does — unless that member has opted in with
+ImplicitQLearning.set_act_dropout(True): it then acts with keep-bits drawn on the device, exactly as its solo
+act() / actor_forward() / online_step(act_next=...) would (its own rate, key and stream position).
 
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
@@ -93,12 +95,16 @@ class ImplicitQLearningGroup:
                                           "without actor_dropout=True)")
 
     def _check_eval_forward(self, members, what: str) -> None:
-        """The library's inference forward is eval-mode: refuse it for a member that would act with dropout."""
+        """The library's inference forward is eval-mode for a member that has not opted in (set_act_dropout): refuse it
+        for such a member that would act with dropout.  Then send every acting member's inference rate and key."""
         for i in members:
             t = self.trainers[i]
-            if t.actor.training and t._actor_dropout_p() > 0.0:
+            if t.acts_with_dropout() and not t._act_dropout:
                 raise NotImplementedError(f"iqlhip: {what}: the library's inference forward is eval-mode (no actor "
-                                          f"dropout; member {i} is in training mode)")
+                                          f"dropout; member {i} is in training mode and has not called "
+                                          "set_act_dropout(True))")
+        for i in members:
+            self.trainers[i]._prepare_act()
 
     def _check_batch_size(self, B: int) -> None:
         if getattr(self.trainers[0], "_precision", "f32") == "bf16" and B > BF16_MAX_ROWS:
@@ -394,6 +400,8 @@ class ImplicitQLearningGroup:
         if not isinstance(states, (list, tuple)) or len(states) != K:
             raise ValueError(f"iqlhip: actor_forward of a group of {K} needs states as a list of {K} tensors")
         self._check_members()
+        for t in self.trainers:          # (members that have not opted in to act dropout keep the eval-mode forward)
+            t._prepare_act()
         if K == 1:
             return [self.trainers[0].actor_forward(states[0], sample=sample, max_action=max_action)]
         t0 = self.trainers[0]

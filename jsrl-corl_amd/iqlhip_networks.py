@@ -86,8 +86,8 @@ def _hip_owner(actor: nn.Module, device) -> Optional[object]:
     owner = ref() if ref is not None else None
     if owner is None or not owner.can_act_on(device):
         return None
-    if actor.training and dropout_p(actor) > 0.0:
-        return None          # training-mode dropout inside act(): the library's inference forward is eval-mode
+    if actor.training and dropout_p(actor) > 0.0 and not getattr(owner, "_act_dropout", False):
+        return None          # training-mode dropout inside act() without the owner's set_act_dropout(True): PyTorch path
     return owner
 
 

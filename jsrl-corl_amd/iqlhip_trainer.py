@@ -97,6 +97,9 @@ class ImplicitQLearning:
         self._adam_t = {"v": 0, "q": 0, "pi": 0}
         self._hyper_sent = None
         self._act_bufs = None
+        self._act_dropout = False     # set_act_dropout: actor dropout inside the device inference forward (opt-in)
+        self._act_dropout_sent = None  # (rate, key) the context's inference side holds; None: never sent (rate 0)
+        self._act_key_stale = False   # set_dropout_seed since: the next inference call sends the new key
         if _is_gpu(device):
             self._attach(max_batch=256)
             register_actor_owner(self.actor, self)
@@ -176,6 +179,11 @@ class ImplicitQLearning:
             ctr = (C.c_uint64 * 2)()
             hb.check(hb.lib().iqlhip_get_counters(self._ctx, ctr))
             hb.check(hb.lib().iqlhip_set_counters(ctx, ctr))
+            n_act = C.c_uint64(0)       # ... and the inference keep-bit stream's position, rate and key
+            hb.check(hb.lib().iqlhip_get_act_dropout_counter(self._ctx, C.byref(n_act)))
+            hb.check(hb.lib().iqlhip_set_act_dropout_counter(ctx, n_act))
+            if self._act_dropout_sent is not None:
+                hb.check(hb.lib().iqlhip_set_act_dropout(ctx, *self._act_dropout_sent))
         self._release()                 # the previous (smaller) context, only now that the new one exists
         self._ctx = ctx
         self._table_cache = None
@@ -326,12 +334,49 @@ class ImplicitQLearning:
         # actor dropout follows the module's mode, like nn.Dropout (active in train(), off in eval())
         p_eff = self._actor_dropout_p() if self.actor.training else 0.0
         if p_eff != self._dropout_sent:
-            rank = self._dp_rank if self._dp_world > 1 else 0
-            seed = getattr(self, "_dropout_seed", None)
-            if seed is None:
-                seed = torch.initial_seed()
-            hb.check(hb.lib().iqlhip_set_dropout(self._ctx, p_eff, dp.rank_seed(seed, rank)))
+            hb.check(hb.lib().iqlhip_set_dropout(self._ctx, p_eff, self._dropout_key()))
             self._dropout_sent = p_eff
+
+    def _dropout_key(self) -> int:
+        """The key of this trainer's keep-bit streams: set_dropout_seed(seed), else torch.initial_seed(), per rank."""
+        rank = self._dp_rank if self._dp_world > 1 else 0
+        seed = getattr(self, "_dropout_seed", None)
+        if seed is None:
+            seed = torch.initial_seed()
+        return dp.rank_seed(seed, rank)
+
+    def set_act_dropout(self, enabled: bool) -> None:
+        """Opt in to (or out of) actor dropout inside the device inference forward.  The reference's online loop asks
+        a training-mode actor for its next action (algorithms/finetune/iql.py:725-738), so an actor built with dropout
+        acts through live nn.Dropout layers.  With the opt-in, `actor.act(state, "cuda")`, `actor_forward` and
+        `online_step(act_next=...)` of such an actor run on the device with keep-bits drawn there (a stream of its own
+        under the dropout key, one position per library call; DESIGN.md "Random streams"); in eval() mode, or with rate
+        0, they run exactly as without it.  Default off: a training-mode dropout actor then acts through its PyTorch
+        modules and act_next is refused.  Not part of the reference's surface."""
+        self._act_dropout = bool(enabled)
+
+    def acts_with_dropout(self) -> bool:
+        """True if the actor's next act() applies dropout (training mode, rate > 0)."""
+        return bool(self.actor.training and self._actor_dropout_p() > 0.0)
+
+    def _prepare_act(self) -> None:
+        """Before an inference call: the rate the forward applies (the module's, in training mode, once opted in) and
+        the key, sent when they change.  A trainer that never opted in sends nothing: the context's rate is 0."""
+        sent = self._act_dropout_sent
+        if not self._act_dropout and sent is None:
+            return
+        p_eff = self._actor_dropout_p() if (self._act_dropout and self.actor.training) else 0.0
+        if sent is None or sent[0] != p_eff or self._act_key_stale:      # (cached like _dropout_sent)
+            pair = (p_eff, self._dropout_key())
+            hb.check(hb.lib().iqlhip_set_act_dropout(self._ctx, *pair))
+            self._act_dropout_sent, self._act_key_stale = pair, False
+
+    def act_dropout_calls(self) -> int:
+        """Position of the inference keep-bit stream: library inference calls that have drawn so far."""
+        self._require_gpu()
+        n = C.c_uint64(0)
+        hb.check(hb.lib().iqlhip_get_act_dropout_counter(self._ctx, C.byref(n)))
+        return int(n.value)
 
     def set_dropout_seed(self, seed: int) -> None:
         """Key this trainer's actor-dropout keep-bit stream with `seed` instead of the process's torch.initial_seed().
@@ -340,6 +385,7 @@ class ImplicitQLearning:
         next step (the stream position is kept).  Not part of the reference's surface."""
         self._dropout_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self._dropout_sent = None        # (the next _prepare sends the rate and the new key)
+        self._act_key_stale = True       # (... and the next inference call of an opted-in trainer)
 
     def _actor_dropout_p(self) -> float:
         """max p over the actor's nn.Dropout layers; the layer list is cached (walking named_modules costs ~13 us a
@@ -534,9 +580,10 @@ class ImplicitQLearning:
         a_in = a_out = None
         seed = 0
         if act_next is not None:
-            from iqlhip_networks import dropout_p
-            if self.actor.training and dropout_p(self.actor) > 0.0:
-                raise NotImplementedError("act_next: the library's inference forward is eval-mode (no actor dropout)")
+            if self.acts_with_dropout() and not self._act_dropout:
+                raise NotImplementedError("act_next: the library's inference forward is eval-mode (no actor dropout) "
+                                          "unless set_act_dropout(True) was called")
+            self._prepare_act()
             a_in = np.ascontiguousarray(np.asarray(act_next, dtype=np.float32).reshape(-1))
             a_out = np.empty(A, dtype=np.float32)
             seed = self._act_seed() if (self.actor.training and self._gaussian) else 0
@@ -977,8 +1024,10 @@ class ImplicitQLearning:
         """Batched policy forward on the device: [n, S] float32 -> actions [n, A]
         = clamp(max_action * (tanh(MLP(s)) [+ sigma * N(0,1) if `sample` and the policy is Gaussian]), +-max_action).
         The batched form of GaussianPolicy.act / DeterministicPolicy.act (iql.py:371-379, 404-413) for evaluation
-        loops; eval-mode forward (no dropout)."""
+        loops.  Eval-mode forward (no dropout) unless set_act_dropout(True) was called and the actor is in training
+        mode: then every library call (a chunk of at most the row cap) draws its rows' keep-bits."""
         self._require_gpu()
+        self._prepare_act()
         x = self._as_dev(states).reshape(-1, self._S)
         n = x.shape[0]
         ma = float(self.max_action if max_action is None else max_action)
@@ -1011,6 +1060,7 @@ class ImplicitQLearning:
         (host-mapped memory over PCIe: ~120 B each way), so the call is three launches and one stream
         synchronisation — no staging copies, no per-call allocation."""
         self._require_gpu()
+        self._prepare_act()
         if self._act_bufs is None:
             h_in = torch.empty((1, self._S), dtype=torch.float32).pin_memory()
             h_out = torch.empty((1, self._A), dtype=torch.float32).pin_memory()
@@ -1064,7 +1114,7 @@ class ImplicitQLearning:
 
     def debug_read(self, name: str) -> np.ndarray:
         self._require_gpu()
-        cap = 4 * self._max_batch * 256 + 64
+        cap = max(4 * self._max_batch * 256, 16 * max(self._max_batch, hb.IQLHIP_ACT_ROWS)) + 64
         buf = (C.c_float * cap)()
         n = C.c_int64(0)
         hb.check(hb.lib().iqlhip_debug_read(self._ctx, name.encode(), buf, cap, C.byref(n), self._stream()))
