@@ -327,8 +327,10 @@ int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed
  * steps run alone (iqlhip_step / iqlhip_train_steps) would have left it, bit for bit.
  * Members: 1..IQLHIP_MAX_GROUP distinct contexts on one device with equal state / action dims, policy kind and
  * precision; no data-parallel exchange; actor dropout (iqlhip_set_dropout with p > 0) only in a group created with
- * IQLHIP_GROUP_DROPOUT (IQLHIP_EUNSUPPORTED otherwise).  Batches: one size for all members,
- * small-batch kernels only (bf16: at most 512 rows).  A group call invalidates each member's train_steps continuation
+ * IQLHIP_GROUP_DROPOUT (IQLHIP_EUNSUPPORTED otherwise).  Batches: one size for all members through iqlhip_group_step /
+ * _train_steps / _online_step, a size per member through their _mixed forms (the same launches: each launch's grid is
+ * the largest member's, a member's record bounds its own work); small-batch kernels only (bf16: at most 512 rows per
+ * member).  A group call invalidates each member's train_steps continuation
  * (the staging buffer is overwritten).  The members must outlive the group; a context that is destroyed or re-created
  * means a new group. */
 #define IQLHIP_MAX_GROUP 16
@@ -351,6 +353,11 @@ int iqlhip_group_destroy(iqlhip_group* group);
  * With out != NULL the call synchronises `stream`. */
 int iqlhip_group_step(iqlhip_group* group, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
                       void* stream);
+/* iqlhip_group_step where batches[k].rows may differ from member to member (1 <= rows <= member k's max_batch; bf16:
+ * <= 512): member k ends exactly where iqlhip_step on batches[k] leaves it.  Any group takes it; with equal rows it
+ * is iqlhip_group_step.  Everything is checked, per member, before any device work or counter change. */
+int iqlhip_group_step_mixed(iqlhip_group* group, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
+                            void* stream);
 /* n steps per member with row indices drawn on the device: member k draws from rows[k] (packed rows, stride ld,
  * size[k] rows) under (seeds[k], offsets[k]) exactly as iqlhip_train_steps(..., seed, stream_offset) does, and takes
  * its per-step scalars from tables[k] (n x iqlhip_step_scalars, host memory, free again on return).  The losses of
@@ -358,6 +365,12 @@ int iqlhip_group_step(iqlhip_group* group, const iqlhip_batch* batches, const iq
 int iqlhip_group_train_steps(iqlhip_group* group, const float* const* rows, int64_t ld, const int64_t* size, int32_t B,
                              const void* const* tables, int32_t n, const uint64_t* seeds, const uint64_t* offsets,
                              int32_t flags, void* stream);
+/* iqlhip_group_train_steps with a batch size per member, B[k] (NULL: IQLHIP_EINVAL): step s of member k draws the
+ * indices j = s * B[k] + r, r < B[k], of its own stream — exactly what iqlhip_train_steps with batch B[k] draws; n is
+ * common to the call.  The checks of iqlhip_group_train_steps apply per member, before any device work. */
+int iqlhip_group_train_steps_mixed(iqlhip_group* group, const float* const* rows, int64_t ld, const int64_t* size,
+                                   const int32_t* B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                   const uint64_t* offsets, int32_t flags, void* stream);
 /* out[k][n][3]: the losses of the first n steps of the last group call; synchronises `stream`. */
 int iqlhip_group_read_losses(iqlhip_group* group, float* out, int32_t n, void* stream);
 /* One online-loop iteration per member (iqlhip_online_step for each member k, in one set of launches and one
@@ -374,6 +387,13 @@ int iqlhip_group_online_step(iqlhip_group* group, float* const* rows_dev, int64_
                              const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
                              const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
                              float* act_out_host, void* stream);
+/* iqlhip_group_online_step with a batch size per member, n[k] (NULL: IQLHIP_EINVAL): idx_host holds the members' index
+ * lists one after another, member k's n[k] indices starting at n[0] + ... + n[k-1].  The same checks, per member. */
+int iqlhip_group_online_step_mixed(iqlhip_group* group, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                   const int64_t* pointer, const float* row_host, const int64_t* idx_host,
+                                   const int32_t* n, const iqlhip_step_scalars* sc, float* out,
+                                   const float* act_state_host, const int32_t* act_mask, const float* max_action,
+                                   const uint64_t* act_seed, float* act_out_host, void* stream);
 /* Policy inference for every member of a group in one set of launches.  Member k maps its rows[k] states
  * (row stride ld_s) to rows[k] actions (row stride ld_a), exactly as iqlhip_actor_forward (seeds[k] == 0: the mean)
  * or iqlhip_actor_sample (seeds[k] != 0: device N(0,1) noise, member k's act() call counter advances by one) on that

@@ -2475,19 +2475,45 @@ extern "C" int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_gro
   return iqlhip_group_create_flags(members, k, 0, out);
 }
 
-// Geometry of a group step: the forward's slices per block chosen for the whole group grid (the single-agent rule applied
-// to K x the row tiles); the backward's (b) blocks take one slice each (iql_bwd_group_kernel).  Results do not depend on
-// either (bit-identical for every slice count).
-struct GroupGeom { int n_rt, n_chunk, fwd_l2, fwd_nb, bwd_nb, upd_nb; bool full; };
-static GroupGeom group_geom(const iqlhip_ctx* c, int rows, int k) {
+// One row count per member: what the step entry points work on.  The uniform entry points pass one count k times.
+struct GroupRows { int32_t v[IQLHIP_MAX_GROUP]; };
+static GroupRows group_rows_all(int32_t rows) {
+  GroupRows r;
+  for (int i = 0; i < IQLHIP_MAX_GROUP; ++i) r.v[i] = rows;
+  return r;
+}
+
+// Geometry of a group step.  Per member: its row tiles and chunks (its record carries them: a block beyond a member's
+// own count exits).  Per launch: grid.x is the largest member's block count, grid.y the member.  The forward's slices
+// per block are chosen for the whole group grid (the single-agent rule applied to the sum of the members' row tiles);
+// the backward's (b) blocks take one slice each (iql_bwd_group_kernel).  Results do not depend on either (bit-identical
+// for every slice count).  full: every member's rows fill whole chunks (the backward's FULL instantiation).
+struct GroupGeom {
+  int n_rt[IQLHIP_MAX_GROUP], n_chunk[IQLHIP_MAX_GROUP];
+  int max_rows, fwd_l2, fwd_nb, fwd_work, bwd_nb, upd_nb;      // fwd_work: the forward blocks that have a row tile
+  bool full;
+};
+static GroupGeom group_geom(const iqlhip_group* g, const int32_t* rows) {
+  const iqlhip_ctx* c = g->m[0];
   GroupGeom q;
-  q.n_rt = (rows + RT_ROWS - 1) / RT_ROWS;
-  q.n_chunk = (rows + CHUNK_ROWS - 1) / CHUNK_ROWS;
-  q.fwd_l2 = fwd_spb_l2(c, k * q.n_rt);
-  q.fwd_nb = fwd_blocks(q.n_rt, q.fwd_l2);
-  q.bwd_nb = bwd_blocks(q.n_chunk, q.n_rt, 0, 0);
+  memset(&q, 0, sizeof q);
+  int rt_sum = 0;
+  q.full = true;
+  for (int i = 0; i < g->k; ++i) {
+    q.n_rt[i] = (rows[i] + RT_ROWS - 1) / RT_ROWS;
+    q.n_chunk[i] = (rows[i] + CHUNK_ROWS - 1) / CHUNK_ROWS;
+    q.max_rows = std::max(q.max_rows, (int)rows[i]);
+    q.full = q.full && (rows[i] % CHUNK_ROWS) == 0;
+    rt_sum += q.n_rt[i];
+  }
+  q.fwd_l2 = fwd_spb_l2(c, rt_sum);
+  for (int i = 0; i < g->k; ++i) {
+    const int nb = fwd_blocks(q.n_rt[i], q.fwd_l2);
+    q.fwd_nb = std::max(q.fwd_nb, nb);
+    q.fwd_work += nb;
+    q.bwd_nb = std::max(q.bwd_nb, bwd_blocks(q.n_chunk[i], q.n_rt[i], 0, 0));
+  }
   q.upd_nb = upd_blocks(c);
-  q.full = (rows % CHUNK_ROWS) == 0;
   return q;
 }
 
@@ -2495,18 +2521,19 @@ static GroupGeom group_geom(const iqlhip_ctx* c, int rows, int k) {
 static int group_check_bound(const iqlhip_group* g, int i) {
   return g->m[i]->params ? IQLHIP_OK : fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called", i);
 }
-// ... and, for the step entry points, batches of `rows` rows.
-static int group_check_call(iqlhip_group* g, int rows) {
+// ... and, for the step entry points, a batch of rows[i] rows for member i.
+static int group_check_call(iqlhip_group* g, const int32_t* rows) {
   if (!g) return fail(IQLHIP_EINVAL, "NULL group");
   int rc = group_check_members(g->m, g->k, g->flags);
   if (rc) return rc;
   for (int i = 0; i < g->k; ++i) {
     if ((rc = group_check_bound(g, i))) return rc;
-    if (rows < 1 || rows > g->m[i]->dims.max_batch)
-      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, max_batch=%d]", i, rows, g->m[i]->dims.max_batch);
+    if (rows[i] < 1 || rows[i] > g->m[i]->dims.max_batch)
+      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, max_batch=%d]", i, rows[i], g->m[i]->dims.max_batch);
   }
-  if (g->m[0]->precision == 1 && rows > LB_MIN_ROWS)
-    return fail(IQLHIP_EUNSUPPORTED, "bf16 groups take batches of at most %d rows (the large-batch kernels have no group form)", LB_MIN_ROWS);
+  for (int i = 0; i < g->k; ++i)
+    if (g->m[0]->precision == 1 && rows[i] > LB_MIN_ROWS)
+      return fail(IQLHIP_EUNSUPPORTED, "bf16 groups take batches of at most %d rows (the large-batch kernels have no group form)", LB_MIN_ROWS);
   return IQLHIP_OK;
 }
 
@@ -2519,7 +2546,7 @@ static void group_record(iqlhip_group* g, GroupRec& r, int i, const GroupGeom& q
   r.p = make_step(c, rows, sc0->inv_batch);
   r.p.xb = xb;
   r.p.spb_l2 = q.fwd_l2;
-  const BwdWords b = bwd_words(c, r.p, q.n_chunk, q.n_rt, 0u);      // (one-slice backward: no slice or donation word)
+  const BwdWords b = bwd_words(c, r.p, q.n_chunk[i], q.n_rt[i], 0u);      // (one-slice backward: no slice or donation word)
   r.q_heads = b.heads; r.q_xb = b.xb; r.q_h1 = b.h1; r.q_h0 = b.h0; r.q_params = b.params;
   r.q_dims = b.dims; r.q_ldB = b.ldB; r.q_mbc = b.mbc; r.q_rts = b.rts;
   r.u = make_upd(c, sc0, rows, nullptr);
@@ -2557,19 +2584,20 @@ static GroupDropRec group_drop_record(const iqlhip_ctx* c, int rows) {
 
 // One-step calls (iqlhip_group_step, iqlhip_group_online_step): the drawing members' records packed at the front of
 // `d` (iql_dropmask_group_kernel's grid.y).  Returns their number.
-static int group_drop_records_packed(const iqlhip_group* g, GroupDropRec* d, int rows) {
+static int group_drop_records_packed(const iqlhip_group* g, GroupDropRec* d, const int32_t* rows) {
   int n = 0;
   if (!(g->flags & IQLHIP_GROUP_DROPOUT)) return 0;
   for (int i = 0; i < g->k; ++i)
-    if (group_draws(g->m[i])) d[n++] = group_drop_record(g->m[i], rows);
+    if (group_draws(g->m[i])) d[n++] = group_drop_record(g->m[i], rows[i]);
   return n;
 }
 
 // ... their draw at drop_step (one launch for all of them, where the solo steps launch iql_dropmask_kernel each), and
-// drop_step += 1 as the solo step's.  `drops`: the device copy of the packed records.
-static void group_launch_dropmask(iqlhip_group* g, const GroupDropRec* drops, int n_draw, int rows, hipStream_t st) {
+// drop_step += 1 as the solo step's.  `drops`: the device copy of the packed records; max_rows: the largest member's
+// rows (each record bounds its own member's words).
+static void group_launch_dropmask(iqlhip_group* g, const GroupDropRec* drops, int n_draw, int max_rows, hipStream_t st) {
   if (n_draw == 0) return;
-  hipLaunchKernelGGL(iql_dropmask_group_kernel, dim3((2 * rows * 8 + 255) / 256, n_draw), dim3(256), 0, st, drops);
+  hipLaunchKernelGGL(iql_dropmask_group_kernel, dim3((2 * max_rows * 8 + 255) / 256, n_draw), dim3(256), 0, st, drops);
   for (int i = 0; i < g->k; ++i)
     if (group_draws(g->m[i])) g->m[i]->drop_step += 1;
 }
@@ -2599,7 +2627,7 @@ static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const Group
   const iqlhip_ctx* c = g->m[0];
   const int K = g->k;
   const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K;
-  hipLaunchKernelGGL(fwd_group_kernel(bf, dma, /*multi=*/q.fwd_l2 > 0), dim3(q.fwd_nb, K), dim3(256), fwd_lds(c, q.fwd_nb * K), st, recs);
+  hipLaunchKernelGGL(fwd_group_kernel(bf, dma, /*multi=*/q.fwd_l2 > 0), dim3(q.fwd_nb, K), dim3(256), fwd_lds(c, q.fwd_work), st, recs);
   hipLaunchKernelGGL(bwd_group_kernel(bf, q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs);
   hipLaunchKernelGGL(iql_update_group_kernel, dim3(q.upd_nb, K), dim3(256), 0, st, recs, s);
 }
@@ -2621,23 +2649,26 @@ static int group_losses_out(iqlhip_group* g, float* out, int n, hipStream_t st) 
   return IQLHIP_OK;
 }
 
-extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
-                                 void* stream) {
+// iqlhip_group_step (mixed = false: every batch has batches[0]'s rows) and iqlhip_group_step_mixed.
+static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out, void* stream,
+                      bool mixed) {
   if (!g || !batches || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
-  const int rows = batches[0].rows;
-  int rc = group_check_call(g, rows);
+  GroupRows rows = group_rows_all(batches[0].rows);
+  if (mixed)
+    for (int i = 0; i < g->k && i < IQLHIP_MAX_GROUP; ++i) rows.v[i] = batches[i].rows;
+  int rc = group_check_call(g, rows.v);
   if (rc) return rc;
   for (int i = 0; i < g->k; ++i) {
     rc = check_batch(g->m[i], &batches[i]);
     if (rc) return rc;
-    if (batches[i].rows != rows) return fail(IQLHIP_EINVAL, "member %d: batch of %d rows, member 0: %d (one batch size per group)", i, batches[i].rows, rows);
+    if (!mixed && batches[i].rows != rows.v[0]) return fail(IQLHIP_EINVAL, "member %d: batch of %d rows, member 0: %d (one batch size per group)", i, batches[i].rows, rows.v[0]);
     if (batches[i].idx_dev && (rc = check_indexed(g->m[i], &batches[i]))) return rc;
   }
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
   rc = group_staging_free(g);
   if (rc) return rc;
-  const GroupGeom q = group_geom(g->m[0], rows, g->k);
+  const GroupGeom q = group_geom(g, rows.v);
   for (int i = 0; i < g->k; ++i) {
     iqlhip_ctx* c = g->m[i];
     c->cont.valid = false;
@@ -2645,29 +2676,37 @@ extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, c
     rc = stage_batch(c, &batches[i], st, &xb);
     if (rc) return rc;
     refresh_shadows(c, st);
-    group_record(g, g->train.host(g->recs)[i], i, q, rows, 1, xb, &sc[i], group_sched(g, i));
+    group_record(g, g->train.host(g->recs)[i], i, q, rows.v[i], 1, xb, &sc[i], group_sched(g, i));
     group_tab(g, i)[0] = sc[i];
   }
-  const int n_draw = group_drop_records_packed(g, g->train.host(g->drops), rows);
+  const int n_draw = group_drop_records_packed(g, g->train.host(g->drops), rows.v);
   rc = group_upload(g, 1, st);
   if (rc) return rc;
-  group_launch_dropmask(g, g->train.device(g->drops), n_draw, rows, st);
+  group_launch_dropmask(g, g->train.device(g->drops), n_draw, q.max_rows, st);
   group_launch_step(g, g->train.device(g->recs), q, 0, st);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
 }
+extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
+                                 void* stream) {
+  return group_step(g, batches, sc, out, stream, /*mixed=*/false);
+}
+extern "C" int iqlhip_group_step_mixed(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc,
+                                       float* out, void* stream) {
+  return group_step(g, batches, sc, out, stream, /*mixed=*/true);
+}
 
-extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
-                                        int32_t B, const void* const* tables, int32_t n, const uint64_t* seeds,
-                                        const uint64_t* offsets, int32_t flags, void* stream) {
-  (void)flags;
-  if (!g || !rows || !size || !tables || !seeds || !offsets) return fail(IQLHIP_EINVAL, "NULL argument");
+// iqlhip_group_train_steps (B: one count k times) and iqlhip_group_train_steps_mixed: member i draws B[i] rows a step.
+static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size, const int32_t* B,
+                             const void* const* tables, int32_t n, const uint64_t* seeds, const uint64_t* offsets,
+                             void* stream) {
+  if (!g || !rows || !size || !B || !tables || !seeds || !offsets) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = group_check_call(g, B);
   if (rc) return rc;
   if (n < 1 || n > IQLHIP_GROUP_MAX_STEPS) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", IQLHIP_GROUP_MAX_STEPS);
   for (int i = 0; i < g->k; ++i) {
-    rc = check_train_args(g->m[i], rows[i], ld, B);
+    rc = check_train_args(g->m[i], rows[i], ld, B[i]);
     if (rc) return rc;
     if (size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty buffer", i);
     if (!tables[i]) return fail(IQLHIP_EINVAL, "member %d: NULL scalar table", i);
@@ -2676,14 +2715,14 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
   hipStream_t st = (hipStream_t)stream;
   rc = group_staging_free(g);
   if (rc) return rc;
-  const GroupGeom q = group_geom(g->m[0], B, g->k);
+  const GroupGeom q = group_geom(g, B);
   for (int i = 0; i < g->k; ++i) {
     iqlhip_ctx* c = g->m[i];
     c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
     refresh_shadows(c, st);
     const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
     GroupRec& r = g->train.host(g->recs)[i];
-    group_record(g, r, i, q, B, n, c->xb, &tab[0], group_sched(g, i));
+    group_record(g, r, i, q, B[i], n, c->xb, &tab[0], group_sched(g, i));
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
     memcpy(group_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
   }
@@ -2692,7 +2731,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
   if (g->flags & IQLHIP_GROUP_DROPOUT) {
     GroupDropRec* d = g->train.host(g->drops);
     for (int i = 0; i < g->k; ++i) {
-      d[i] = group_drop_record(g->m[i], B);
+      d[i] = group_drop_record(g->m[i], B[i]);
       d[i].active = group_draws(g->m[i]) ? 1 : 0;
       draws = draws || d[i].active;
     }
@@ -2700,9 +2739,10 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
   rc = group_upload(g, n, st);
   if (rc) return rc;
   const iqlhip_ctx* c0 = g->m[0];
-  const int gather_nb = (int)std::min<int64_t>(((int64_t)B * (c0->row_ld / 4) + 255) / 256, 1024);
+  // (grids sized by the largest member: every record bounds its own member's rows and words)
+  const int gather_nb = (int)std::min<int64_t>(((int64_t)q.max_rows * (c0->row_ld / 4) + 255) / 256, 1024);
   // (a grid with a thread per gathered float4 and per keep-bit word: the words come from its far end)
-  const int drop_nb = gather_nb + (2 * B * 8 + 255) / 256;
+  const int drop_nb = gather_nb + (2 * q.max_rows * 8 + 255) / 256;
   const GroupRec* recs = g->train.device(g->recs);
   for (int s = 0; s < n; ++s) {
     if (draws)
@@ -2717,6 +2757,19 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* row
   g->last_n = n;
   return IQLHIP_OK;
 }
+extern "C" int iqlhip_group_train_steps(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
+                                        int32_t B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                        const uint64_t* offsets, int32_t flags, void* stream) {
+  (void)flags;
+  const GroupRows b = group_rows_all(B);
+  return group_train_steps(g, rows, ld, size, b.v, tables, n, seeds, offsets, stream);
+}
+extern "C" int iqlhip_group_train_steps_mixed(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
+                                              const int32_t* B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                              const uint64_t* offsets, int32_t flags, void* stream) {
+  (void)flags;
+  return group_train_steps(g, rows, ld, size, B, tables, n, seeds, offsets, stream);
+}
 
 extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, void* stream) {
   if (!g || !out) return fail(IQLHIP_EINVAL, "NULL argument");
@@ -2729,17 +2782,21 @@ extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, 
 // writes + gathers (+ the act states' packing), forward, backward, update with each member's losses landing in its own
 // pinned words, then — members that asked for one — the next action with the updated policy, and one completion word
 // the host spins on.  Everything is checked before any device work and before any counter moves.
-extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
-                                        const int64_t* pointer, const float* row_host, const int64_t* idx_host, int32_t n,
-                                        const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
-                                        const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
-                                        float* act_out_host, void* stream) {
-  if (!g || !rows_dev || !capacity || !pointer || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+// iqlhip_group_online_step (n: one count k times) and iqlhip_group_online_step_mixed: member i steps on n[i] rows, its
+// indices at idx_host[n[0] + ... + n[i - 1]].
+static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                             const int64_t* pointer, const float* row_host, const int64_t* idx_host, const int32_t* n,
+                             const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
+                             const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
+                             float* act_out_host, void* stream) {
+  if (!g || !rows_dev || !capacity || !pointer || !row_host || !idx_host || !n || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (act_state_host && (!max_action || !act_seed || !act_out_host))
     return fail(IQLHIP_EINVAL, "act_state_host without max_action, act_seed or act_out_host");
   int rc = group_check_call(g, n);
   if (rc) return rc;
   const int K = g->k;
+  size_t idx0[IQLHIP_MAX_GROUP];      // where member i's indices start in idx_host
+  for (int i = 0; i < K; ++i) idx0[i] = i ? idx0[i - 1] + (size_t)n[i - 1] : 0;
   for (int i = 0; i < K; ++i) {
     const iqlhip_ctx* c = g->m[i];
     if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
@@ -2752,7 +2809,7 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
       const uintptr_t b0 = (uintptr_t)rows_dev[j], b1 = b0 + (uintptr_t)(capacity[j] * ld) * sizeof(float);
       if (a0 < b1 && b0 < a1) return fail(IQLHIP_EINVAL, "members %d and %d share ring rows (one buffer per member)", j, i);
     }
-    rc = check_host_indices(idx_host + (size_t)i * n, n, capacity[i]);
+    rc = check_host_indices(idx_host + idx0[i], n[i], capacity[i]);
     if (rc) return rc;
   }
   DevGuard guard(g->device);
@@ -2760,7 +2817,7 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
   const iqlhip_ctx* c0 = g->m[0];
   const int S = c0->dims.state_dim, A = c0->dims.action_dim;
   const bool gauss = c0->dims.policy == IQLHIP_POLICY_GAUSSIAN;
-  const GroupGeom q = group_geom(c0, n, K);
+  const GroupGeom q = group_geom(g, n);
   const Staging& on = g->on;
   GroupRec* recs = on.host(g->on_recs);
   StepParams* aps = on.host(g->on_aps);
@@ -2777,15 +2834,15 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
     iqlhip_ctx* c = g->m[i];
     c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
     memcpy(c->on_row_pin, row_host + (size_t)i * ld, (size_t)ld * sizeof(float));
-    memcpy(c->on_idx_pin, idx_host + (size_t)i * n, (size_t)n * sizeof(long long));
+    memcpy(c->on_idx_pin, idx_host + idx0[i], (size_t)n[i] * sizeof(long long));
     tab[i] = sc[i];
-    group_record(g, recs[i], i, q, n, 1, c->xb, &sc[i], on.device(g->on_tabs) + i);
+    group_record(g, recs[i], i, q, n[i], 1, c->xb, &sc[i], on.device(g->on_tabs) + i);
     recs[i].u.losses_mirror = c->on_loss_pin;
     const bool req = act_requested(i);
     GroupOnlineRec& o = ons[i];
     o.rows = rows_dev[i]; o.row_pin = c->on_row_pin; o.idx_pin = c->on_idx_pin; o.xb = c->xb;
     o.act_pin = req ? c->on_act_pin : nullptr; o.xb_act = c->xb_act;
-    o.ld = ld; o.pointer = pointer[i]; o.n = n; o.S = S;
+    o.ld = ld; o.pointer = pointer[i]; o.n = n[i]; o.S = S;
     if (with_adrops) adrops[i] = act_drop_record(c, req ? 1 : 0);
     if (!req) continue;
     memcpy(c->on_act_pin, act_state_host + (size_t)i * S, (size_t)S * sizeof(float));
@@ -2802,14 +2859,14 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
   const int n_draw = group_drop_records_packed(g, on.host(g->on_drops), n);
   // (a synchronous call: the previous one's upload has been read long ago)
   HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
-  const int gather_nb = (int)((n * (ld / 4) + 255) / 256);
+  const int gather_nb = (int)((q.max_rows * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
   if (act_draws)
     hipLaunchKernelGGL(iql_online_gather_drop_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers),
                        on.device(g->on_adrops));
   else
     hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
-  group_launch_dropmask(g, on.device(g->on_drops), n_draw, n, st);
+  group_launch_dropmask(g, on.device(g->on_drops), n_draw, q.max_rows, st);
   group_launch_step(g, on.device(g->on_recs), q, 0, st);
   const unsigned long long done_val = ++g->done_seq;
   if (n_req > 0) {
@@ -2830,6 +2887,24 @@ extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev,
     if (act_requested(i)) memcpy(act_out_host + (size_t)i * A, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
   }
   return IQLHIP_OK;
+}
+extern "C" int iqlhip_group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                        const int64_t* pointer, const float* row_host, const int64_t* idx_host, int32_t n,
+                                        const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
+                                        const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
+                                        float* act_out_host, void* stream) {
+  const GroupRows r = group_rows_all(n);
+  return group_online_step(g, rows_dev, ld, capacity, pointer, row_host, idx_host, r.v, sc, out, act_state_host, act_mask,
+                           max_action, act_seed, act_out_host, stream);
+}
+extern "C" int iqlhip_group_online_step_mixed(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                              const int64_t* pointer, const float* row_host, const int64_t* idx_host,
+                                              const int32_t* n, const iqlhip_step_scalars* sc, float* out,
+                                              const float* act_state_host, const int32_t* act_mask,
+                                              const float* max_action, const uint64_t* act_seed, float* act_out_host,
+                                              void* stream) {
+  return group_online_step(g, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, act_mask,
+                           max_action, act_seed, act_out_host, stream);
 }
 
 // Policy inference of every member (iqlhip_actor_forward / iqlhip_actor_sample for each, include/iqlhip.h) in one set

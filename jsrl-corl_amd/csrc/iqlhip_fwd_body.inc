@@ -1,7 +1,9 @@
 // Body of the forward — included by iql_fwd_kernel and iql_fwd_group_kernel (iqlhip_kernels.h):
 // ONE body for the single-agent kernel and its trainer-group form, so the arithmetic exists once.  blockIdx.x / gridDim.x
 // are the block's index and grid size of ONE agent's launch in both (a group kernel's agent is blockIdx.y).
-// In scope: template flags BF16, W0DMA, MULTI, ONE and the agent's `p` (StepParams).
+// In scope: template flags BF16, W0DMA, MULTI, ONE, the agent's `p` (StepParams) and ROW_EXIT: a block whose row tile
+// lies outside the agent's batch exits under every block map (iql_fwd_group_kernel only: its grid.x is the largest
+// member's; a single agent's one- and two-slice grids are sized exactly and compile without the test).
   RT_ENTRY();
   const int bid = blockIdx.x;
   // XCD-affine block map (consecutive workgroups go round the 8 XCDs: XCD x = blockIdx & 7).  Across a kernel boundary an
@@ -35,9 +37,11 @@
   } else if (spb_l2 == 0) {
     ns = 2 * ((fr >> 1) & 1) + fh;
     rt = fr >> 2;
+    if (ROW_EXIT && rt * RT_ROWS >= p.rows) return;
   } else if (spb_l2 == 1) {
     ns = 2 * fh;
     rt = fr >> 1;
+    if (ROW_EXIT && rt * RT_ROWS >= p.rows) return;
   } else {
     ns = 0;
     rt = 2 * (fr >> 1) + fh;

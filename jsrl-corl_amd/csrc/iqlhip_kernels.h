@@ -406,6 +406,7 @@ __device__ __forceinline__ void l0_chunk_bf16(f32x4 (&acc)[2][4], const float (&
 // scalar-cache misses at the start of every training forward instead of one.
 template <bool BF16, bool W0DMA, bool MULTI, bool ONE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_kernel(StepParams p) {
+  constexpr bool ROW_EXIT = false;      // (a grid of exactly this agent's row tiles)
 #include "iqlhip_fwd_body.inc"
 }
 
@@ -1021,7 +1022,9 @@ __global__ __launch_bounds__(256) void iql_update_kernel(float* q_p, float* q_m,
 // The host writes one record per agent into device memory — exactly what the single-agent launches pass as kernel
 // arguments — and the group kernels run the bodies the single-agent kernels include (iqlhip_*_body.inc) on record
 // blockIdx.y.  Nothing of an agent is shared with another: each record points at that agent's own arenas, scratch and
-// staging buffer.
+// staging buffer.  The members' batches may differ in rows (the _mixed entry points): grid.x of every launch is the
+// largest member's block count, and a record bounds its own member's work — the forward by p.rows (ROW_EXIT), the
+// backward by q_ldB / q_mbc / q_rts, the gathers and keep-bit draws by B / n_rows, the update by u's chunk count.
 struct GroupRec {
   StepParams p;                       // forward + backward (spb_l2: the forward's slices per block for the group grid)
   const float* q_heads; const float* q_xb; const float* q_h1; const float* q_h0; const float* q_params;
@@ -1042,6 +1045,7 @@ struct GroupRec {
 template <bool BF16, bool W0DMA, bool MULTI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_group_kernel(const GroupRec* __restrict__ recs) {
   constexpr bool ONE = false;
+  constexpr bool ROW_EXIT = true;       // (grid.x: the member with the most row tiles — the others' extra blocks exit)
   const StepParams& p = recs[blockIdx.y].p;
 #include "iqlhip_fwd_body.inc"
 }
@@ -1428,7 +1432,8 @@ struct GroupActRec {
 
 // iql_online_gather_kernel per member: the ring write, the gather from pinned indices (an index equal to `pointer`
 // reads the new row from the pinned copy), and — members that asked for an action — the packing of the act state into
-// xb_act that iql_pack_states_kernel does for one row (block 0).  Every member has the same n and ld (one grid).
+// xb_act that iql_pack_states_kernel does for one row (block 0).  Every member has the same ld; the grid is sized for
+// the largest n (a block past a member's own n reads no index and writes no row).
 __device__ __forceinline__ void online_gather_member(const GroupOnlineRec& g) {
   __shared__ long long s_idx[260];
   float* rows = g.rows;
@@ -1472,7 +1477,7 @@ __global__ __launch_bounds__(256) void iql_online_gather_drop_group_kernel(const
 // NSPLIT + column slice) for the members that asked for an action: grid.y = requesting member, ps[j] its StepParams.
 template <bool BF16, bool W0DMA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_act_fwd_group_kernel(const StepParams* __restrict__ ps) {
-  constexpr bool MULTI = false, ONE = true;
+  constexpr bool MULTI = false, ONE = true, ROW_EXIT = false;      // (blocks past a member's rows store nothing)
   const StepParams& p = ps[blockIdx.y];
 #include "iqlhip_fwd_body.inc"
 }

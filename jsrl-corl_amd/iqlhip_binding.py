@@ -141,6 +141,15 @@ SYMBOLS = [
     ("iqlhip_group_train_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64), C.c_int32,
                                            C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                            C.c_int32, C.c_void_p]),
+    ("iqlhip_group_step_mixed", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.POINTER(C.c_float),
+                                          C.c_void_p]),
+    ("iqlhip_group_train_steps_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int32,
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),
+    ("iqlhip_group_online_step_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                                 C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("iqlhip_group_read_losses", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
     ("iqlhip_group_online_step", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int32,

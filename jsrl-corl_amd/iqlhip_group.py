@@ -36,6 +36,16 @@ dropout > 0 raise NotImplementedError, as the solo online_step does — unless t
 ImplicitQLearning.set_act_dropout(True): it then acts with keep-bits drawn on the device, exactly as its solo
 act() / actor_forward() / online_step(act_next=...) would (its own rate, key and stream position).
 
+Members may train at different batch sizes (the reference's hyper-parameter sweep samples batch_size per trial) in a
+group that opted in:
+
+    group = ImplicitQLearningGroup(trainers, mixed_batch=True)
+    losses = group.train_steps(buffer, 1000, batch_size=[64, 128, 256, 512], seeds=[0, 1, 2, 3])
+
+train() then takes batches of different row counts, and train_steps() / online_step() take batch_size as an int or as
+one int per member; the launches are the same in number, and member k still ends where its solo steps at its own
+size end.  Without mixed_batch=True unequal sizes are refused (ValueError), as before the option existed.
+
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
@@ -56,12 +66,15 @@ BF16_MAX_ROWS = 512      # bf16 batches beyond this run the large-batch kernels,
 
 
 class ImplicitQLearningGroup:
-    def __init__(self, trainers: Sequence[ImplicitQLearning], actor_dropout: bool = False):
+    _mixed_batch = False      # (the option's default: online_step / train_steps read it before they look at a member)
+
+    def __init__(self, trainers: Sequence[ImplicitQLearning], actor_dropout: bool = False, mixed_batch: bool = False):
         trainers = list(trainers)
         if not 1 <= len(trainers) <= hb.IQLHIP_MAX_GROUP:
             raise ValueError(f"iqlhip: a group has 1..{hb.IQLHIP_MAX_GROUP} trainers, got {len(trainers)}")
         self.trainers = trainers
         self._actor_dropout = bool(actor_dropout)
+        self._mixed_batch = bool(mixed_batch)
         self._check_members()
         self._g = None
         self._ctxs = None
@@ -110,6 +123,21 @@ class ImplicitQLearningGroup:
         if getattr(self.trainers[0], "_precision", "f32") == "bf16" and B > BF16_MAX_ROWS:
             raise NotImplementedError(f"iqlhip: bf16 groups take batches of at most {BF16_MAX_ROWS} rows (got {B})")
 
+    @staticmethod
+    def _batch_sizes(K: int, batch_size, mixed_batch: bool) -> List[int]:
+        """batch_size (an int, or one int per member) as K sizes.  Unequal sizes need a mixed_batch group."""
+        if isinstance(batch_size, (int, np.integer)):
+            sizes = [int(batch_size)] * K
+        else:
+            sizes = [int(b) for b in batch_size]
+            if len(sizes) != K:
+                raise ValueError(f"iqlhip: {len(sizes)} batch sizes for a group of {K}")
+        if any(b < 1 for b in sizes):
+            raise ValueError(f"iqlhip: batch sizes must be >= 1, got {sizes}")
+        if not mixed_batch and any(b != sizes[0] for b in sizes):
+            raise ValueError(f"iqlhip: batch sizes {sizes} differ (one batch size per group without mixed_batch=True)")
+        return sizes
+
     # ------------------------------------------------------------------ the library group
     def _group(self):
         """The library group over the members' current contexts (re-created when a member re-attached)."""
@@ -142,12 +170,13 @@ class ImplicitQLearningGroup:
         return len(self.trainers)
 
     # ------------------------------------------------------------------ eager steps
-    def _next_scalars(self, inv_batch: float):
-        """Every member's scalars for its next step, and the Adam step counts they belong to (for _commit_step)."""
+    def _next_scalars(self, inv_batch: Sequence[float]):
+        """Every member's scalars for its next step (inv_batch[k]: one over its batch's rows), and the Adam step counts
+        they belong to (for _commit_step)."""
         scs, adam_next = (hb.StepScalars * len(self.trainers))(), []
         for k, t in enumerate(self.trainers):
             t1 = {g: n + 1 for g, n in t._adam_t.items()}
-            t._fill_scalars(scs[k], t1, t._current_lrs(), inv_batch)
+            t._fill_scalars(scs[k], t1, t._current_lrs(), inv_batch[k])
             adam_next.append(t1)
         return scs, adam_next
 
@@ -166,39 +195,44 @@ class ImplicitQLearningGroup:
 
     def train(self, batches: Sequence) -> List[Dict[str, float]]:
         """One step per member on its own batch (ImplicitQLearning.train for each, in one set of launches).  All batches
-        have the same number of rows.  Returns one losses dict per member."""
+        have the same number of rows, unless the group was built with mixed_batch=True.  Returns one losses dict per
+        member."""
         batches = list(batches)
         K = len(self.trainers)
         if len(batches) != K:
             raise ValueError(f"iqlhip: {len(batches)} batches for a group of {K}")
         self._check_members()
-        B = int(batches[0][0].shape[0])
-        for i, b in enumerate(batches):
-            if int(b[0].shape[0]) != B:
-                raise ValueError(f"iqlhip: batch {i} has {int(b[0].shape[0])} rows, batch 0 has {B} (one batch size per group)")
-        self._check_batch_size(B)
+        Bs = [int(b[0].shape[0]) for b in batches]
+        for i, B in enumerate(Bs):
+            if B != Bs[0] and not self._mixed_batch:
+                raise ValueError(f"iqlhip: batch {i} has {B} rows, batch 0 has {Bs[0]} (one batch size per group)")
+        for B in Bs:
+            self._check_batch_size(B)
         if K == 1:      # a group of one IS the solo step (whose eager path returns through host-mapped words: faster)
             return [self.trainers[0].train(batches[0])]
-        for t in self.trainers:
+        for t, B in zip(self.trainers, Bs):
             t._prepare(B)
         structs, keep = (hb.Batch * K)(), []
         for i, (t, batch) in enumerate(zip(self.trainers, batches)):
             b, kp, _ = t._batch_struct(batch)
             structs[i] = b
             keep.append(kp)
-        scs, adam_next = self._next_scalars(1.0 / B)
+        scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
         out = (C.c_float * (3 * K))()
         g = self._group()
-        hb.check(hb.lib().iqlhip_group_step(g, structs, scs, out, self.trainers[0]._stream()))
+        step = hb.lib().iqlhip_group_step_mixed if self._mixed_batch else hb.lib().iqlhip_group_step
+        hb.check(step(g, structs, scs, out, self.trainers[0]._stream()))
         del keep
         return self._commit_step(adam_next, out)
 
     # ------------------------------------------------------------------ device-drawn steps
-    def train_steps(self, buffers, n_steps: int, batch_size: int, seeds: Sequence[int],
+    def train_steps(self, buffers, n_steps: int, batch_size, seeds: Sequence[int],
                     return_losses: bool = True, chunk: int = K_MAX) -> Optional[np.ndarray]:
         """n_steps `sample -> train` iterations per member (ImplicitQLearning.train_steps for each): member k draws its
         rows from buffers[k] (or the one shared buffer) under seeds[k] — exactly the rows its own train_steps(buffer,
-        n_steps, batch_size, seed=seeds[k]) would draw.  Returns losses [K, n_steps, 3] when return_losses, else None."""
+        n_steps, batch_size, seed=seeds[k]) would draw.  batch_size: an int, or one int per member (unequal sizes:
+        mixed_batch groups only; member k then draws what its train_steps at batch_size[k] would).  Returns losses
+        [K, n_steps, 3] when return_losses, else None."""
         K = len(self.trainers)
         bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
         seeds = [int(s) for s in seeds]
@@ -206,15 +240,17 @@ class ImplicitQLearningGroup:
             raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer) and {K} seeds")
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
         self._check_members()
-        self._check_batch_size(batch_size)
+        for B in Bs:
+            self._check_batch_size(B)
         if K == 1:      # a group of one IS the solo call (chunk graphs, rows staged by idle forward blocks: faster)
-            out = self.trainers[0].train_steps(bufs[0], n_steps, batch_size, seed=seeds[0], return_losses=return_losses,
+            out = self.trainers[0].train_steps(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
                                                chunk=chunk)
             return None if out is None else out[None]
         sizes, inv = [], []
-        for t, buf in zip(self.trainers, bufs):
-            size, ib = t._train_steps_args(buf, batch_size)
+        for t, buf, B in zip(self.trainers, bufs, Bs):
+            size, ib = t._train_steps_args(buf, B)
             sizes.append(size)
             inv.append(ib)
         if len({b._ld for b in bufs}) != 1:
@@ -225,16 +261,21 @@ class ImplicitQLearningGroup:
         rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
         size_arr = (C.c_int64 * K)(*sizes)
         seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
-        half = (batch_size + 1) // 2
+        B_arr = (C.c_int32 * K)(*Bs)
+        halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
         losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
         done = 0
         while done < n_steps:
             k = min(chunk, n_steps - done)
-            offs = (C.c_uint64 * K)(*[t.total_it * half for t in self.trainers])
+            offs = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
             tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
             tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
-            rc = lib.iqlhip_group_train_steps(g, rows, bufs[0]._ld, size_arr, batch_size, tab_ptrs, k, seed_arr, offs, 0,
-                                              stream)
+            if self._mixed_batch:
+                rc = lib.iqlhip_group_train_steps_mixed(g, rows, bufs[0]._ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs,
+                                                        0, stream)
+            else:
+                rc = lib.iqlhip_group_train_steps(g, rows, bufs[0]._ld, size_arr, Bs[0], tab_ptrs, k, seed_arr, offs, 0,
+                                                  stream)
             for t in self.trainers:
                 t._ts_token = None
             hb.check(rc)
@@ -248,13 +289,14 @@ class ImplicitQLearningGroup:
         return losses
 
     # ------------------------------------------------------------------ the online loop
-    def online_step(self, buffers, states, actions, rewards, next_states, dones, batch_size: int,
+    def online_step(self, buffers, states, actions, rewards, next_states, dones, batch_size,
                     act_next: Optional[Sequence] = None, rngs: Optional[Sequence[np.random.RandomState]] = None):
         """One iteration of the online loop for every member in ONE library call (ImplicitQLearning.online_step for
         each, in member order): member k stores its transition (states[k], actions[k], rewards[k], next_states[k],
         dones[k]) in buffers[k], draws `randint(0, size_k, batch_size)` over its size after the insert — from
         rngs[k] (a np.random.RandomState), or from the global np.random in member order when rngs is None — and takes
-        one step on those rows.  buffers are K distinct finetune ReplayBuffers on the members' GPU with one row stride.
+        one step on those rows.  batch_size: an int, or one int per member (unequal sizes: mixed_batch groups only).
+        buffers are K distinct finetune ReplayBuffers on the members' GPU with one row stride.
         act_next: None, or K entries (a state or None): member k's entry gives actor.act(state) with its UPDATED
         policy, as the solo act_next does.  Returns one train()-style dict per member; with act_next, (logs, actions)
         where actions[k] is None for members that asked for none.  Buffers, step counts and schedules move only once
@@ -270,14 +312,16 @@ class ImplicitQLearningGroup:
             if not isinstance(v, (list, tuple)) or len(v) != K:
                 raise ValueError(f"iqlhip: online_step of a group of {K} needs {name} as a list of {K} entries")
         bufs = list(buffers)
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
         self._check_members()
-        self._check_batch_size(batch_size)
+        for B in Bs:
+            self._check_batch_size(B)
         if act_next is not None:         # (before any ring, counter or parameter moves)
             self._check_eval_forward([k for k in range(K) if act_next[k] is not None], "online_step(act_next=...)")
         if K == 1 and rngs is None:      # a group of one IS the solo call
             tr = self.trainers[0]
             an = None if act_next is None else act_next[0]
-            res = tr.online_step(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], batch_size,
+            res = tr.online_step(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], Bs[0],
                                  act_next=an)
             if act_next is None:
                 return [res]
@@ -286,7 +330,7 @@ class ImplicitQLearningGroup:
             return [res[0]], [res[1]]
         from iqlhip_replay import ReplayBuffer
         for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
-            t._prepare(batch_size)
+            t._prepare(Bs[i])
             if not getattr(buf, "_gpu", False) or buf._rows.device != t._dev:
                 raise ValueError(f"iqlhip: online_step needs a ReplayBuffer on the trainer's GPU (member {i})")
             if type(buf)._index_bound is not ReplayBuffer._index_bound or \
@@ -321,11 +365,12 @@ class ImplicitQLearningGroup:
         # (the buffers' and the trainers' counters move only once the library call has succeeded)
         pointers = [b._pointer for b in bufs]
         new_sizes = [min(b._size + 1, b._buffer_size) for b in bufs]
-        idx = np.empty((K, batch_size), dtype=np.int64)
+        idx = []                         # (the members' index lists one after another)
         for k in range(K):               # sample()'s draw over the size AFTER the insert
             rng = np.random if rngs is None else rngs[k]
-            idx[k] = rng.randint(0, new_sizes[k], size=batch_size)
-        scs, adam_next = self._next_scalars(1.0 / batch_size)
+            idx.append(np.asarray(rng.randint(0, new_sizes[k], size=Bs[k]), dtype=np.int64))
+        idx = np.ascontiguousarray(np.concatenate(idx))
+        scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
         out = (C.c_float * (3 * K))()
         ring_ptrs = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
         caps = (C.c_int64 * K)(*[b._buffer_size for b in bufs])
@@ -335,9 +380,14 @@ class ImplicitQLearningGroup:
             return None if a is None else a.ctypes.data
 
         g = self._group()
-        rc = hb.lib().iqlhip_group_online_step(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
-                                               batch_size, scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds),
-                                               addr(a_out), t0._stream())
+        if self._mixed_batch:
+            rc = hb.lib().iqlhip_group_online_step_mixed(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
+                                                         (C.c_int32 * K)(*Bs), scs, out, addr(a_in), addr(mask),
+                                                         addr(max_a), addr(seeds), addr(a_out), t0._stream())
+        else:
+            rc = hb.lib().iqlhip_group_online_step(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
+                                                   Bs[0], scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds),
+                                                   addr(a_out), t0._stream())
         hb.check(rc)
         for k, buf in enumerate(bufs):
             buf._writes += 1
