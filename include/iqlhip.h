@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 300          /* 0.3.0 */
+#define IQLHIP_VERSION 310          /* 0.3.1 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -317,6 +317,29 @@ int iqlhip_cols_mean_std(const float* x_dev, int64_t ld, int32_t ncols, int64_t 
  * x = (x - mean[c]) / std[c] in fp32 — bit-identical to numpy given the same mean / std. */
 int iqlhip_rows_normalize(float* rows_dev, int64_t ld, int32_t state_dim, int32_t action_dim, int64_t row0, int64_t n,
                           const float* mean_dev, const float* std_dev, void* stream);
+/* return_reward_range (:262-274) over n packed rows from row0, in storage order: min and max of the episode returns,
+ * and the number of complete episodes.  Row i ends an episode iff its done column is non-zero or its episode has
+ * reached max_episode_steps rows; a trailing run that ends neither way is no episode (the reference keeps only its
+ * length).  A return is the float64 sum of the episode's float32 rewards, added in ascending row order one after the
+ * other (one thread walks one episode), so out_min_max is bit-identical to the reference's Python floats.  No complete
+ * episode (the reference's min([]) raises ValueError): IQLHIP_EINVAL, *out_episodes = 0, out_min_max untouched.  NaN
+ * rewards are outside the contract (Python's min / max depend on the order of their arguments there).  Device scratch
+ * (8 B per row) is allocated and freed on `stream`.  Synchronises `stream`. */
+int iqlhip_rows_return_range(const float* rows_dev, int64_t ld, int32_t state_dim, int32_t action_dim, int64_t row0,
+                             int64_t n, int32_t max_episode_steps, double out_min_max[2], int64_t* out_episodes,
+                             void* stream);
+/* modify_reward's rescaling (:280-281) applied in place to the reward column of n packed rows from row0, in fp32 as two
+ * separately rounded operations: r = r / divide_by (IEEE division), then r = r * multiply_by — what numpy's
+ * `rewards /= max_ret - min_ret; rewards *= max_episode_steps` does to a float32 array, with
+ * divide_by = (float)(max_ret - min_ret) (subtracted in double) and multiply_by = (float)max_episode_steps.
+ * divide_by == 0: IQLHIP_EINVAL.  No other column is written. */
+int iqlhip_rows_reward_scale(float* rows_dev, int64_t ld, int32_t state_dim, int32_t action_dim, int64_t row0, int64_t n,
+                             float divide_by, float multiply_by, void* stream);
+/* modify_reward's antmaze branch (:287-288): r = r - subtract in fp32 on the same column. */
+int iqlhip_rows_reward_shift(float* rows_dev, int64_t ld, int32_t state_dim, int32_t action_dim, int64_t row0, int64_t n,
+                             float subtract, void* stream);
+/* The three calls above refuse, before any device work, with IQLHIP_EINVAL: a NULL pointer, n < 1, row0 < 0,
+ * max_episode_steps < 1, ld < iqlhip_row_stride(state_dim, action_dim). */
 /* Device-side index draw used by iqlhip_train_steps, exposed for tests. */
 int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed, uint64_t offset, void* stream);
 

@@ -2005,6 +2005,92 @@ extern "C" int iqlhip_rows_normalize(float* rows_dev, int64_t ld, int32_t S, int
 }
 
 // ---------------------------------------------------------------------------
+// Reward ingest (return_reward_range / modify_reward, algorithms/finetune/iql.py:262-289): kernels in iqlhip_kernels.h.
+static int reward_args_ok(const void* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n, const char* who) {
+  if (!rows_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n < 1 || row0 < 0 || S < 1 || A < 1 || ld < iqlhip_row_stride(S, A)) return fail(IQLHIP_EINVAL, "bad %s geometry", who);
+  return IQLHIP_OK;
+}
+
+static int launch_return_range(const float* rows_dev, long long ld, int S, int A, long long row0, long long n, long long T,
+                               char* scratch, RRResult* res_host, hipStream_t st) {
+  const long long ntiles = (n + RR_TILE - 1) / RR_TILE;
+  const int nb = (int)std::min<long long>(ntiles, RR_MAX_BLOCKS);
+  // scratch: prev[n] | tile partials[ntiles] | block results[nb] | result
+  long long* prev = (long long*)scratch;
+  long long* tiles = prev + n;
+  RRResult* blocks = (RRResult*)(tiles + ntiles);
+  RRResult* res = blocks + nb;
+  const int rcol = 2 * S + A, dcol = rcol + 1;
+  hipLaunchKernelGGL(iql_rr_scan_reduce_kernel, dim3(nb), dim3(RR_TILE), 0, st, rows_dev, ld, dcol, row0, n, ntiles, tiles);
+  hipLaunchKernelGGL(iql_rr_scan_partials_kernel, dim3(1), dim3(RR_TILE), 0, st, tiles, ntiles);
+  hipLaunchKernelGGL(iql_rr_scan_apply_kernel, dim3(nb), dim3(RR_TILE), 0, st, rows_dev, ld, dcol, row0, n, ntiles,
+                     (const long long*)tiles, prev);
+  hipLaunchKernelGGL(iql_rr_episode_kernel, dim3(nb), dim3(RR_TILE), 0, st, rows_dev, ld, rcol, row0, n, ntiles, T,
+                     (const long long*)prev, blocks);
+  hipLaunchKernelGGL(iql_rr_finish_kernel, dim3(1), dim3(RR_TILE), 0, st, (const RRResult*)blocks, nb, res);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(res_host, res, sizeof(RRResult), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_rows_return_range(const float* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n,
+                                        int32_t max_episode_steps, double out_min_max[2], int64_t* out_episodes,
+                                        void* stream) {
+  if (!out_min_max || !out_episodes) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = reward_args_ok(rows_dev, ld, S, A, row0, n, "rows_return_range");
+  if (rc) return rc;
+  if (max_episode_steps < 1) return fail(IQLHIP_EINVAL, "max_episode_steps must be at least 1");
+  hipStream_t st = (hipStream_t)stream;
+  const long long ntiles = ((long long)n + RR_TILE - 1) / RR_TILE;
+  const size_t bytes = ((size_t)n + (size_t)ntiles) * sizeof(long long) + ((size_t)std::min<long long>(ntiles, RR_MAX_BLOCKS) + 1) * sizeof(RRResult);
+  char* scratch = nullptr;
+  HIPCHK(hipMallocAsync((void**)&scratch, bytes, st));
+  RRResult res;
+  rc = launch_return_range(rows_dev, (long long)ld, S, A, (long long)row0, (long long)n, (long long)max_episode_steps,
+                           scratch, &res, st);
+  const hipError_t e = hipFreeAsync(scratch, st);
+  if (rc) return rc;
+  HIPCHK(e);
+  *out_episodes = (int64_t)res.episodes;
+  if (res.episodes < 1)       // the reference's min([]) raises ValueError
+    return fail(IQLHIP_EINVAL, "no complete episode in %lld rows (no terminal, and fewer than max_episode_steps = %d rows)",
+                (long long)n, (int)max_episode_steps);
+  out_min_max[0] = res.min_ret;
+  out_min_max[1] = res.max_ret;
+  return IQLHIP_OK;
+}
+
+static int launch_reward_map(bool shift, float* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n, float a,
+                             float b, void* stream) {
+  const int nb = (int)std::min<int64_t>((n + 255) / 256, 8192);
+  if (shift)
+    hipLaunchKernelGGL(iql_rows_reward_map_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, rows_dev, (long long)ld,
+                       2 * S + A, (long long)row0, (long long)n, a, b);
+  else
+    hipLaunchKernelGGL(iql_rows_reward_map_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, rows_dev, (long long)ld,
+                       2 * S + A, (long long)row0, (long long)n, a, b);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_rows_reward_scale(float* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n,
+                                        float divide_by, float multiply_by, void* stream) {
+  const int rc = reward_args_ok(rows_dev, ld, S, A, row0, n, "rows_reward_scale");
+  if (rc) return rc;
+  if (divide_by == 0.f) return fail(IQLHIP_EINVAL, "divide_by is zero (max_ret == min_ret)");
+  return launch_reward_map(false, rows_dev, ld, S, A, row0, n, divide_by, multiply_by, stream);
+}
+
+extern "C" int iqlhip_rows_reward_shift(float* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n,
+                                        float subtract, void* stream) {
+  const int rc = reward_args_ok(rows_dev, ld, S, A, row0, n, "rows_reward_shift");
+  if (rc) return rc;
+  return launch_reward_map(true, rows_dev, ld, S, A, row0, n, subtract, 0.f, stream);
+}
+
+// ---------------------------------------------------------------------------
 extern "C" int iqlhip_rows_fill_synth(float* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n,
                                       uint64_t seed, float p_done, int32_t antmaze_rewards, void* stream) {
   if (!rows_dev) return fail(IQLHIP_EINVAL, "NULL argument");

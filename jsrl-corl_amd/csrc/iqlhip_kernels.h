@@ -1383,6 +1383,165 @@ __global__ void iql_rows_normalize_kernel(float* rows, long long ld, int S, int 
 }
 
 // ---------------------------------------------------------------------------
+// Reward ingest: return_reward_range / modify_reward (algorithms/finetune/iql.py:262-289) on n packed rows from row0,
+// in storage order.  Row i (0-based in the range) ends an episode iff d[i] != 0 or its episode has reached T rows.
+// With p(i) = the largest j < i with d[j] != 0 (-1 if none) and o = i - p(i) - 1:  row i ends an episode iff
+// d[i] != 0 || (o + 1) % T == 0, and that episode's first row is p(i) + 1 + (o / T) * T — no sequential pass.
+//   1. iql_rr_scan_{reduce,partials,apply}_kernel: prev[i] = max over j <= i of (d[j] != 0 ? j : -1), an inclusive
+//      prefix max in three plain launches (a partial per 256-row tile, one block scans the partials, every tile
+//      rescans itself on top of its predecessor's partial).  No block ever waits for another one: a grid may exceed
+//      what the device holds at once, and a block that spins on one that is not scheduled yet never ends.
+//      p(i) = prev[i - 1], and d[i] != 0 iff prev[i] == i.
+//   2. iql_rr_episode_kernel: one thread per row; the thread of a row that ends an episode adds that episode's
+//      float32 rewards in float64, first row to last, one after the other — the reference's `ep_ret += float(r)`, so
+//      the sums (and with them min / max) are the reference's Python floats bit for bit.  The loads are one float per
+//      row stride: uncoalesced by construction, n of them in all.  (min, max, count) per block.
+//   3. iql_rr_finish_kernel: one block folds the block partials (min / max / integer sum: order-independent).
+// A return is never -0.0 (the sum starts at +0.0, and x + (-x) = +0.0), so `<` / `>` give Python's min / max; NaN
+// rewards are outside the contract (Python's min / max depend on the order there).
+// Tiles are walked with a block stride, so the grids stay bounded (RR_MAX_BLOCKS) for any n.
+#define RR_TILE 256
+#define RR_MAX_BLOCKS 4096
+struct RRResult { double min_ret, max_ret; long long episodes; };
+
+// inclusive prefix max over the block's 256 threads of values >= -1; s_w: 4 words of LDS, reusable on return
+__device__ __forceinline__ long long rr_block_scan_max(long long v, long long* s_w) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long u = __shfl_up(v, off, 64);
+    if (lane >= off && u > v) v = u;
+  }
+  if (lane == 63) s_w[w] = v;
+  __syncthreads();
+  for (int k = 0; k < w; ++k) if (s_w[k] > v) v = s_w[k];
+  __syncthreads();
+  return v;
+}
+
+__device__ __forceinline__ long long rr_terminal_or_minus1(const float* rows, long long ld, int dcol, long long row0,
+                                                           long long n, long long i) {
+  return (i < n && rows[(row0 + i) * ld + dcol] != 0.f) ? i : -1;
+}
+
+// partial[t] = the last terminal row of tile t (-1: none)
+__global__ __launch_bounds__(RR_TILE) void iql_rr_scan_reduce_kernel(const float* rows, long long ld, int dcol, long long row0,
+                                                                     long long n, long long ntiles, long long* partial) {
+  __shared__ long long s_w[4];
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    long long v = rr_terminal_or_minus1(rows, ld, dcol, row0, n, t * RR_TILE + threadIdx.x);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const long long u = __shfl_xor(v, o, 64); if (u > v) v = u; }
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[t] = max(max(s_w[0], s_w[1]), max(s_w[2], s_w[3]));
+    __syncthreads();
+  }
+}
+
+// one block: partial[t] <- max over tiles <= t (in place)
+__global__ __launch_bounds__(RR_TILE) void iql_rr_scan_partials_kernel(long long* partial, long long ntiles) {
+  __shared__ long long s_w[4];
+  __shared__ long long s_carry;
+  long long carry = -1;
+  for (long long base = 0; base < ntiles; base += RR_TILE) {
+    const long long t = base + threadIdx.x;
+    long long v = rr_block_scan_max((t < ntiles) ? partial[t] : -1, s_w);
+    if (carry > v) v = carry;
+    if (t < ntiles) partial[t] = v;
+    if (threadIdx.x == RR_TILE - 1) s_carry = v;
+    __syncthreads();
+    carry = s_carry;
+    __syncthreads();
+  }
+}
+
+// prev[i] = the last terminal row <= i of the whole range (-1: none)
+__global__ __launch_bounds__(RR_TILE) void iql_rr_scan_apply_kernel(const float* rows, long long ld, int dcol, long long row0,
+                                                                    long long n, long long ntiles, const long long* partial,
+                                                                    long long* prev) {
+  __shared__ long long s_w[4];
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = t * RR_TILE + threadIdx.x;
+    long long v = rr_block_scan_max(rr_terminal_or_minus1(rows, ld, dcol, row0, n, i), s_w);
+    const long long carry = t ? partial[t - 1] : -1;
+    if (carry > v) v = carry;
+    if (i < n) prev[i] = v;
+  }
+}
+
+__device__ __forceinline__ void rr_fold(double& mn, double& mx, long long& cnt, double mn2, double mx2, long long cnt2) {
+  if (mn2 < mn) mn = mn2;
+  if (mx2 > mx) mx = mx2;
+  cnt += cnt2;
+}
+
+// (min, max, count) of the block's 256 threads -> thread 0
+__device__ __forceinline__ void rr_block_fold(double& mn, double& mx, long long& cnt, RRResult* s_w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rr_fold(mn, mx, cnt, __shfl_xor(mn, o, 64), __shfl_xor(mx, o, 64), __shfl_xor(cnt, o, 64));
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = RRResult{mn, mx, cnt};
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 1; k < 4; ++k) rr_fold(mn, mx, cnt, s_w[k].min_ret, s_w[k].max_ret, s_w[k].episodes);
+}
+
+__global__ __launch_bounds__(RR_TILE) void iql_rr_episode_kernel(const float* rows, long long ld, int rcol, long long row0,
+                                                                 long long n, long long ntiles, long long T,
+                                                                 const long long* prev, RRResult* partial) {
+  __shared__ RRResult s_w[4];
+  double mn = __builtin_inf(), mx = -__builtin_inf();
+  long long cnt = 0;
+  const float* r = rows + row0 * ld + rcol;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long i = t * RR_TILE + threadIdx.x;
+    if (i >= n) continue;
+    const long long p = i ? prev[i - 1] : -1;
+    const long long o = i - p - 1;
+    if (prev[i] != i && (o + 1) % T != 0) continue;
+    double ret = 0.0;
+    long long j = p + 1 + (o / T) * T;
+    for (; j + 8 <= i + 1; j += 8) {       // eight loads in flight (each is a cache line of its own), added in row order
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = r[(j + k) * ld];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) ret += (double)v[k];
+    }
+    for (; j <= i; ++j) ret += (double)r[j * ld];       // ascending, one after another
+    rr_fold(mn, mx, cnt, ret, ret, 1);
+  }
+  rr_block_fold(mn, mx, cnt, s_w);
+  if (threadIdx.x == 0) partial[blockIdx.x] = RRResult{mn, mx, cnt};
+}
+
+__global__ __launch_bounds__(RR_TILE) void iql_rr_finish_kernel(const RRResult* partial, int nblocks, RRResult* out) {
+  __shared__ RRResult s_w[4];
+  double mn = __builtin_inf(), mx = -__builtin_inf();
+  long long cnt = 0;
+  for (int b = threadIdx.x; b < nblocks; b += RR_TILE) rr_fold(mn, mx, cnt, partial[b].min_ret, partial[b].max_ret, partial[b].episodes);
+  rr_block_fold(mn, mx, cnt, s_w);
+  if (threadIdx.x == 0) *out = RRResult{mn, mx, cnt};
+}
+
+// modify_reward's arithmetic on the reward column, float32 like numpy's in-place operators on a float32 array:
+// SHIFT = false: r = r / divide_by, then r = r * multiply_by (two roundings, IEEE division — `rewards /= max_ret - min_ret;
+// rewards *= max_episode_steps`);  SHIFT = true: r = r - a (antmaze's `rewards -= 1.0`).
+template <bool SHIFT>
+__global__ void iql_rows_reward_map_kernel(float* rows, long long ld, int rcol, long long row0, long long n, float a, float b) {
+#pragma clang fp contract(off)
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    float* p = rows + (row0 + i) * ld + rcol;
+    if (SHIFT) {
+      *p = *p - a;
+    } else {
+      const float q = *p / a;
+      *p = q * b;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // One online iteration's buffer work in one launch (iqlhip_online_step): the new transition `row_host` (pinned,
 // host-mapped, ld floats) is stored at ring row `pointer`, and the batch rows[idx_host[r]] (indices in pinned,
 // host-mapped memory, exactly as np.random.randint drew them) are gathered into xb.  A sampled index equal to

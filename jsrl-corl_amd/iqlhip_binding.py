@@ -128,6 +128,12 @@ SYMBOLS = [
                                        C.c_void_p]),
     ("iqlhip_rows_normalize", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    ("iqlhip_rows_return_range", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p]),
+    ("iqlhip_rows_reward_scale", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_float,
+                                           C.c_float, C.c_void_p]),
+    ("iqlhip_rows_reward_shift", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_float,
+                                           C.c_void_p]),
     ("iqlhip_draw_indices", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("iqlhip_debug_read", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64,
                                     C.POINTER(C.c_int64), C.c_void_p]),

@@ -9,9 +9,16 @@ Numerics: the normalisation is bit-identical to numpy's given the same mean / st
 float64-accumulated (deterministic, fixed order): within 1e-6 relative of a float64 evaluation, whereas numpy's own
 float32 axis-0 reduction (row after row) drifts by ~2e-4 at 1 M rows — tolerances stated in tests/test_hip_ingest.py.  There is no CPU fallback here: the numpy functions of the reference's
 surface (`compute_mean_std`, `normalize_states`) stay what they are for host arrays.
+
+Reward ingest (`normalize_reward: true`, finetune/iql.py:262-289): `return_reward_range_device` scans the done column for
+episode boundaries and sums every episode's rewards in float64 in row order, one thread per episode, so the (min, max)
+it returns are the reference's Python floats bit for bit; `ReplayBuffer.modify_reward_` rescales the stored rewards with
+them (load -> buf.modify_reward_(env_name, max_episode_steps)).  The host functions `return_reward_range` /
+`modify_reward` of the drop-in modules stay what they are for host datasets.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Tuple
 
 import numpy as np
@@ -46,3 +53,22 @@ def compute_mean_std_device(states: np.ndarray, eps: float, device: str = "cuda"
     x = torch.as_tensor(np.ascontiguousarray(states, dtype=np.float32)).to(device, non_blocking=False)
     mean, std = cols_mean_std(x, eps)
     return mean.cpu().numpy(), std.cpu().numpy()
+
+
+def return_reward_range_device(rows: torch.Tensor, state_dim: int, action_dim: int, n: int,
+                               max_episode_steps: int) -> Tuple[float, float]:
+    """return_reward_range (finetune/iql.py:262-274) over the first n rows of a packed device row store
+    [s | a | s' | r | d | pad]: (min, max) of the returns of the complete episodes, in storage order.  Raises ValueError
+    when there is no complete episode, like the reference's min([]).  Synchronises the current stream."""
+    if rows.device.type != "cuda":
+        raise RuntimeError("iqlhip: return_reward_range_device needs a GPU tensor (host datasets: iql.return_reward_range)")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.stride(1) != 1:
+        raise ValueError("expected a float32 [rows, ld] tensor with unit column stride")
+    if n < 1 or n > rows.shape[0]:
+        raise ValueError("n outside the row store")
+    out = (C.c_double * 2)()
+    episodes = C.c_int64(0)
+    with torch.cuda.device(rows.device):
+        hb.check(hb.lib().iqlhip_rows_return_range(rows.data_ptr(), rows.stride(0), state_dim, action_dim, 0, n,
+                                                   int(max_episode_steps), out, C.byref(episodes), _stream(rows.device)))
+    return float(out[0]), float(out[1])

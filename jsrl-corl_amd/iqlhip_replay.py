@@ -173,6 +173,42 @@ class ReplayBuffer:
             hb.check(hb.lib().iqlhip_rows_normalize(self._rows.data_ptr(), self._ld, self._state_dim, self._action_dim,
                                                     0, self._size, m.data_ptr(), s.data_ptr(), self._stream()))
 
+    def return_reward_range(self, max_episode_steps: int):
+        """return_reward_range (iql.py:262-274) of the stored rows [0, size) in storage order — a freshly loaded dataset,
+        not an online ring that has wrapped: (min, max) of the episode returns as Python floats, bit-identical to the
+        reference's (float64 sums in row order).  ValueError when the rows hold no complete episode."""
+        import iqlhip_ingest as ing
+        if not self._gpu:
+            raise RuntimeError("iqlhip: return_reward_range runs in libiqlhip.so and needs a GPU buffer")
+        if self._size < 1:
+            raise ValueError("replay buffer is empty")
+        return ing.return_reward_range_device(self._rows, self._state_dim, self._action_dim, self._size, max_episode_steps)
+
+    def modify_reward_(self, env_name: str, max_episode_steps: int = 1000) -> Dict:
+        """modify_reward (iql.py:277-289) applied IN PLACE to the reward column of the stored rows [0, size) in storage
+        order (a freshly loaded dataset, not a wrapped online ring).  Returns the reference's dict, for
+        modify_reward_online(reward, env_name, **d) on the host: max_ret / min_ret / max_episode_steps for halfcheetah,
+        hopper and walker2d (rewards divided by max_ret - min_ret, then multiplied by max_episode_steps, in fp32), {}
+        for antmaze (rewards - 1) and for any other name (nothing done)."""
+        if not self._gpu:
+            raise RuntimeError("iqlhip: modify_reward_ runs in libiqlhip.so and needs a GPU buffer")
+        locomotion = any(s in env_name for s in ("halfcheetah", "hopper", "walker2d"))
+        if not locomotion and "antmaze" not in env_name:
+            return {}
+        if self._size < 1:
+            raise ValueError("replay buffer is empty")
+        geometry = (self._rows.data_ptr(), self._ld, self._state_dim, self._action_dim, 0, self._size)
+        if not locomotion:
+            self._writes += 1
+            with torch.cuda.device(self._rows.device):
+                hb.check(hb.lib().iqlhip_rows_reward_shift(*geometry, 1.0, self._stream()))
+            return {}
+        min_ret, max_ret = self.return_reward_range(max_episode_steps)
+        self._writes += 1
+        with torch.cuda.device(self._rows.device):
+            hb.check(hb.lib().iqlhip_rows_reward_scale(*geometry, max_ret - min_ret, float(max_episode_steps), self._stream()))
+        return {"max_ret": max_ret, "min_ret": min_ret, "max_episode_steps": max_episode_steps}
+
     def _index_bound(self) -> int:
         return self._size
 

@@ -779,6 +779,61 @@ def dropin_surface_case(ref, ref_root, outdir):
     print("g16_dropin_surface ok:", imported, {k: len(v["events"]) for k, v in scen.items()})
 
 
+def reward_range_case(ref, outdir):
+    """G17: the reference's return_reward_range / modify_reward (finetune/iql.py:262-289) run on small reward / terminal
+    columns: inputs, (min_ret, max_ret) as float64 and the modified float32 rewards.  The `wide` cases draw rewards of
+    mixed sign over twelve binades of ten (1e-6 .. 1e6), where the order of a float64 sum shows in its last bits: the
+    generator asserts that summing an episode backwards changes a stored return, so the fixture tells an ordered sum
+    from an unordered one."""
+    rng = np.random.default_rng(170)
+
+    def wide(n):
+        return (rng.choice([-1.0, 1.0], size=n) * 10.0 ** rng.uniform(-6.0, 6.0, size=n)).astype(np.float32)
+
+    def flags(n, p):
+        return (rng.random(n) < p).astype(np.float32)
+
+    cases = []      # (name, rewards, terminals, T, env_name)
+    cases.append(("wide_hopper", wide(3000), flags(3000, 0.004), 1000, "hopper-medium-v2"))
+    cases.append(("wide_short_T7", wide(2049), flags(2049, 0.1), 7, "halfcheetah-medium-expert-v2"))
+    cases.append(("timeouts_only", rng.standard_normal(3 * 250 + 2).astype(np.float32), np.zeros(3 * 250 + 2, np.float32), 250,
+                  "walker2d-medium-replay-v2"))
+    d = flags(1200, 0.02)
+    d[[0, 99, 100, 199, 1199]] = 1.0       # first row, a timeout row, consecutive rows, last row
+    cases.append(("terminal_on_timeout", (rng.standard_normal(1200) * 3.0 + 1.0).astype(np.float32), d, 100, "hopper-expert-v2"))
+    cases.append(("antmaze", (rng.random(1000) < 0.02).astype(np.float32), flags(1000, 0.002), 1000, "antmaze-large-diverse-v2"))
+    cases.append(("other_env", wide(500), flags(500, 0.01), 1000, "pen-human-v1"))
+
+    out, names, order_matters = {}, [], False
+    for name, r, d, T, env in cases:
+        data = {"rewards": r.copy(), "terminals": d.copy()}
+        info = ref.modify_reward(data, env, T)
+        assert data["rewards"].dtype == np.float32 and np.array_equal(data["terminals"], d)
+        out[name + "_rewards"], out[name + "_terminals"], out[name + "_modified"] = r, d, data["rewards"]
+        out[name + "_T"], out[name + "_env_name"] = np.int64(T), np.array(env)
+        has_range = bool(info)
+        out[name + "_min_ret"] = np.float64(info["min_ret"] if has_range else np.nan)
+        out[name + "_max_ret"] = np.float64(info["max_ret"] if has_range else np.nan)
+        if has_range:
+            assert (info["min_ret"], info["max_ret"]) == ref.return_reward_range({"rewards": r, "terminals": d}, T)
+            assert info["max_episode_steps"] == T
+            # does a stored (extreme) return of a terminal-delimited episode change when its rows are added backwards?
+            ends = [i for i in range(len(r)) if d[i] != 0]
+            for lo, hi in zip([-1] + ends[:-1], ends):
+                if hi - lo <= T:
+                    fwd = bwd = 0.0
+                    for x in r[lo + 1: hi + 1]:
+                        fwd += float(x)
+                    for x in r[lo + 1: hi + 1][::-1]:
+                        bwd += float(x)
+                    if fwd in (info["min_ret"], info["max_ret"]) and fwd != bwd:
+                        order_matters = True
+        names.append(name)
+    assert order_matters, "no stored return depends on the order of its sum: the fixture cannot pin the order"
+    np.savez(os.path.join(outdir, "g17_reward_range.npz"), meta=np.array(json.dumps({"cases": names})), **out)
+    print("g17_reward_range ok", names)
+
+
 def round2_cases(ref, args):
     jsrl = import_reference_jsrl(args.ref)
     resume_case(ref, "g11_resume_S17A6_gauss", 17, 6, True, 110, 13, args.out)
@@ -795,13 +850,17 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--only", default=None, help="'act': only the G10 act fixtures; 'r2': only the round-2 fixtures "
-                                                 "(g11 resume, g12 JSRL hand-off, g13 JSRL host logic, g14 config-5 batch)")
+                                                 "(g11 resume, g12 JSRL hand-off, g13 JSRL host logic, g14 config-5 batch); "
+                                                 "'reward': only g17 (return_reward_range / modify_reward)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     torch.set_num_threads(1)
     ref = import_reference(args.ref)
     if args.only == "dropin":
         dropin_surface_case(ref, args.ref, args.out)
+        return
+    if args.only == "reward":
+        reward_range_case(ref, args.out)
         return
     if args.only == "r2":
         round2_cases(ref, args)
@@ -833,6 +892,7 @@ def main():
     lr_case(ref, args.out)
     statedict_case(ref, args.out)
     round2_cases(ref, args)
+    reward_range_case(ref, args.out)
 
 
 if __name__ == "__main__":
