@@ -29,12 +29,13 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 310          /* 0.3.1 */
+#define IQLHIP_VERSION 320          /* 0.3.2 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
 #define IQLHIP_MAX_WORLD 8          /* ranks of one data-parallel group (the GPUs of one node) */
 #define IQLHIP_GRAPH_STEPS 64       /* steps per captured hipGraph chunk of iqlhip_train_steps */
+#define IQLHIP_N_STATS 16           /* floats per step of the opt-in training statistics (iqlhip_set_step_stats) */
 
 enum {
   IQLHIP_OK = 0,
@@ -272,6 +273,34 @@ int iqlhip_xch_shutdown(iqlhip_ctx* ctx);
 int iqlhip_read_losses(iqlhip_ctx* ctx, float out[3], void* stream);
 int iqlhip_read_loss_ring(iqlhip_ctx* ctx, float* out, int32_t n_steps, void* stream);
 
+/* ---- per-step training statistics (opt-in) ----------------------------------------------------
+ * IQLHIP_N_STATS floats per step that describe the batch the step trained on, evaluated with the parameters BEFORE
+ * that step's update (the convention of the three losses).  With tq = min(tQ1, tQ2), adv = tq - V(s),
+ * y = r + (1 - d) * discount * V(s'), in this order:
+ *    0 v_mean          mean V(s)            1 next_v_mean     mean V(s')          2 q1_mean   mean Q1(s,a)
+ *    3 q2_mean         mean Q2(s,a)         4 target_q_mean   mean tq             5 td_target_mean   mean y
+ *    6 q_gap_mean      mean |Q1 - Q2|       7 adv_mean        8 adv_min           9 adv_max
+ *   10 adv_pos_frac    share of rows on the expectile's upper side (every row but those with adv < 0: the comparison
+ *                      the value loss makes)
+ *   11 exp_adv_mean    mean of min(exp(beta * adv), EXP_ADV_MAX), the actor loss's row weights
+ *   12 exp_adv_clamped_frac   share of rows whose weight sits on that clamp
+ *   13 grad_norm_vf / 14 grad_norm_qf (both Q nets) / 15 grad_norm_actor (+ log_std): L2 norms of the gradients as Adam
+ *      receives them
+ * Head values are the fixed-order sums of the four slice partials the step itself uses; sums run in a fixed order
+ * (deterministic).  Default off: nothing is launched, captured or allocated, and every result is bit-identical to a
+ * library without this feature.  Enabled, every entry point that runs a step records them (two extra launches per
+ * step between its backward and its update; iqlhip_train_steps keeps chunk graphs of their own per setting, and a
+ * ring indexed like the loss ring); parameters, losses and random streams do not change.  Not supported
+ * (IQLHIP_EUNSUPPORTED from the step entry points, before anything is launched): a context with a data-parallel
+ * exchange selected (the local slabs are not what Adam receives there), and steps that take the large-batch bf16
+ * path (more than 512 rows in bf16). */
+int iqlhip_set_step_stats(iqlhip_ctx* ctx, int enabled);
+/* The last step's statistics; synchronises `stream`.  IQLHIP_EINVAL when statistics are off. */
+int iqlhip_read_step_stats(iqlhip_ctx* ctx, float out[IQLHIP_N_STATS], void* stream);
+/* out[n_steps][IQLHIP_N_STATS]: the statistics of the first n_steps steps of the last iqlhip_train_steps call (like
+ * iqlhip_read_loss_ring); synchronises `stream`. */
+int iqlhip_read_stats_ring(iqlhip_ctx* ctx, float* out, int32_t n_steps, void* stream);
+
 /* ---- replay buffer storage (packed rows [s | a | s' | r | d | pad]) ------ */
 /* Row stride in floats for given dims (multiple of 4 floats = 16 B). */
 int64_t iqlhip_row_stride(int32_t state_dim, int32_t action_dim);
@@ -396,6 +425,10 @@ int iqlhip_group_train_steps_mixed(iqlhip_group* group, const float* const* rows
                                    const uint64_t* offsets, int32_t flags, void* stream);
 /* out[k][n][3]: the losses of the first n steps of the last group call; synchronises `stream`. */
 int iqlhip_group_read_losses(iqlhip_group* group, float* out, int32_t n, void* stream);
+/* out[n][K][IQLHIP_N_STATS]: the statistics of the first n steps of the last group step / train_steps / online_step
+ * call (iqlhip_set_step_stats is a per-member setting: the rows of members that had it off are NaN); a member's
+ * statistics are bit-identical to those of the same steps run alone.  Synchronises `stream`. */
+int iqlhip_group_read_step_stats(iqlhip_group* group, float* out, int32_t n, void* stream);
 /* One online-loop iteration per member (iqlhip_online_step for each member k, in one set of launches and one
  * synchronisation): row_host[k][ld] is stored at ring row pointer[k] of rows_dev[k] (capacity[k] rows, stride ld; no
  * two members' rings may overlap), the rows rows_dev[k][idx_host[k][0..n)] are gathered and one step runs on them with
@@ -456,7 +489,8 @@ int iqlhip_stream_synchronize(void* stream);
 /* ---- introspection (tests, profiling) ----------------------------------- */
 /* Copy a named library-owned scratch array to host (synchronous).  Names:
  * "h0","h1" (activations [4][max_batch][256]), "heads" (partial head sums),
- * "grads" (flat summed gradient, n_params), "loss_parts", "drop_bits" (the training steps' keep-bit words,
+ * "grads" (flat summed gradient, n_params), "loss_parts", "xb" (the library's packed staging batch [max_batch][row
+ * stride]: the rows of the last step that did not consume a packed block in place), "drop_bits" (the training steps' keep-bit words,
  * [2 layers][max_batch][8]), "act_drop_bits" (the last inference call's, [2 layers][max(max_batch, IQLHIP_ACT_ROWS)][8];
  * only after iqlhip_set_act_dropout with p > 0). */
 int iqlhip_debug_read(iqlhip_ctx* ctx, const char* name, float* host_out, int64_t max_floats, int64_t* n_out,

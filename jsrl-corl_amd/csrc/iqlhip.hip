@@ -114,9 +114,10 @@ struct GraphKey {
   int xch = 0;        // exchange mode the chunk was captured with
   int parity = 0;     // P2P exchange: which flat buffer step 0 of the chunk writes
   int head = 0;       // the chunk a call starts with: its graph begins with the call's set-up kernel (arguments set per replay)
+  int stats = 0;      // captured with the statistics launches (iqlhip_set_step_stats): never replayed under the other setting
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
-           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head;
+           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats;
   }
 };
 
@@ -236,6 +237,13 @@ struct iqlhip_ctx {
   unsigned long long* xstatus_host = nullptr;   // pinned landing pad of the status words
   unsigned long long xstep = 0;            // steps exchanged so far (the P2P flags count them)
   unsigned long long xtimeout_ticks = 500000000ull;   // 5 s of the 100 MHz wall clock
+  // per-step statistics (iqlhip_set_step_stats; allocated by the first call that enables them)
+  bool stats_on = false;
+  float* stats_part = nullptr;        // device [4 nets][stats_n_part]: sums of squares of 1024-element gradient windows
+  int stats_n_part = 0;
+  float* stats_last = nullptr;        // device [IQLHIP_N_STATS]: the last step's
+  float* stats_ring = nullptr;        // device [k_max][IQLHIP_N_STATS]: per step of the last iqlhip_train_steps call
+  float* stats_host = nullptr;        // pinned landing pad of the two read calls [k_max][IQLHIP_N_STATS]
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;         // 4 per recorded step
@@ -453,7 +461,8 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
   void* bufs[] = {c->sc.h0, c->sc.h1, c->sc.heads, c->sc.slab_a, c->sc.slab_b, c->sc.loss_parts, c->sc.losses,
                   c->flat_tmp, c->sched_call, c->sched_cur, c->hdr, c->stamps, c->xb, c->xb2, c->xb_act,
-                  c->heads_act, c->drop_bits, c->act_drop_bits, c->xstatus, c->xflat, c->wsh, c->tsh, c->pi_t, c->dh1g, c->slab_x, c->wimg};
+                  c->heads_act, c->drop_bits, c->act_drop_bits, c->xstatus, c->xflat, c->wsh, c->tsh, c->pi_t, c->dh1g, c->slab_x, c->wimg,
+                  c->stats_part, c->stats_last, c->stats_ring};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < 4; ++i) {
     if (c->sched_pin[i]) (void)hipHostFree(c->sched_pin[i]);
@@ -469,6 +478,7 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   if (c->on_loss_pin) (void)hipHostFree(c->on_loss_pin);
   if (c->done_pin) (void)hipHostFree(c->done_pin);
   if (c->on_act_pin) (void)hipHostFree(c->on_act_pin);
+  if (c->stats_host) (void)hipHostFree(c->stats_host);
   delete c;
   return IQLHIP_OK;
 }
@@ -985,6 +995,72 @@ static void launch_flatten(const iqlhip_ctx* c, const UpdParams& u, float* out, 
 }
 
 // ---------------------------------------------------------------------------
+// Per-step statistics (include/iqlhip.h "per-step training statistics"; kernels: iqlhip_kernels.h).
+static int stats_parts(const iqlhip_ctx* c) { return upd_blocks(c) / 8 * 2; }      // 1024-element windows of the longest segment
+extern "C" int iqlhip_set_step_stats(iqlhip_ctx* c, int enabled) {
+  if (!c) return fail(IQLHIP_EINVAL, "NULL ctx");
+  if (enabled && !c->stats_ring) {
+    DevGuard guard(c->device);
+    c->stats_n_part = stats_parts(c);
+    const size_t ring = (size_t)c->k_max * IQLHIP_N_STATS * sizeof(float);
+    HIPCHK(hipMalloc((void**)&c->stats_part, (size_t)4 * c->stats_n_part * sizeof(float)));
+    HIPCHK(hipMemset(c->stats_part, 0, (size_t)4 * c->stats_n_part * sizeof(float)));
+    HIPCHK(hipMalloc((void**)&c->stats_last, IQLHIP_N_STATS * sizeof(float)));
+    HIPCHK(hipMemset(c->stats_last, 0, IQLHIP_N_STATS * sizeof(float)));
+    HIPCHK(hipHostMalloc((void**)&c->stats_host, ring, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&c->stats_ring, ring));
+    HIPCHK(hipMemset(c->stats_ring, 0, ring));
+  }
+  c->stats_on = enabled != 0;
+  return IQLHIP_OK;
+}
+// The two cases statistics are not built for, checked by every step entry point before it launches anything.
+static int stats_check(const iqlhip_ctx* c, int rows) {
+  if (!c->stats_on) return IQLHIP_OK;
+  if (c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "step statistics are not supported with a data-parallel exchange (the local gradient slabs are not what Adam receives)");
+  if (use_lb(c, rows))
+    return fail(IQLHIP_EUNSUPPORTED, "step statistics are not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+  return IQLHIP_OK;
+}
+// The statistics launches' arguments for a step described by `p`; ring == nullptr: the eager steps (stats_last only).
+static StatsArgs make_stats(const iqlhip_ctx* c, const StepParams& p, float* ring, int ring_slot, int ring_cap,
+                            const unsigned long long* ring_hdr) {
+  StatsArgs a;
+  memset(&a, 0, sizeof a);
+  a.heads = p.sc.heads; a.xb = p.xb; a.ld = p.ld; a.rows = p.rows; a.rd_off = 2 * p.S + p.A;
+  a.beta = p.hy.beta; a.discount = p.hy.discount; a.exp_adv_max = p.hy.exp_adv_max;
+  a.gparts = c->stats_part; a.n_part = c->stats_n_part;
+  a.last = c->stats_last;
+  a.ring = ring; a.ring_slot = ring_slot; a.ring_cap = ring_cap; a.ring_hdr = ring_hdr;
+  return a;
+}
+static void launch_stats(const UpdParams& u, const StatsArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(iql_stats_gradsq_kernel, dim3(4 * a.n_part), dim3(256), 0, st, u, a.gparts, a.n_part);
+  hipLaunchKernelGGL(iql_step_stats_kernel, dim3(1), dim3(256), 0, st, a);
+}
+extern "C" int iqlhip_read_step_stats(iqlhip_ctx* c, float out[IQLHIP_N_STATS], void* stream) {
+  if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!c->stats_on) return fail(IQLHIP_EINVAL, "step statistics are off (iqlhip_set_step_stats)");
+  DevGuard guard(c->device);
+  HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_last, IQLHIP_N_STATS * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  memcpy(out, c->stats_host, IQLHIP_N_STATS * sizeof(float));
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_read_stats_ring(iqlhip_ctx* c, float* out, int32_t n_steps, void* stream) {
+  if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!c->stats_on) return fail(IQLHIP_EINVAL, "step statistics are off (iqlhip_set_step_stats)");
+  if (n_steps < 1 || n_steps > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
+  DevGuard guard(c->device);
+  const size_t bytes = (size_t)n_steps * IQLHIP_N_STATS * sizeof(float);
+  HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_ring, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  memcpy(out, c->stats_host, bytes);
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Gradient exchange between the ranks of a data-parallel group (include/iqlhip.h, "data-parallel gradient exchange").
 static RcclApi g_rccl;
 
@@ -1203,8 +1279,11 @@ static XchParams make_xch(const iqlhip_ctx* c, bool from_hdr) {
 // One step's launches after the batch has been staged: forward, backward and — by exchange mode — the update, or
 // flatten + all-reduce + update, or flatten + flag handshake + the update that reads every rank's buffer.
 // `k` = position inside the chunk (selects the P2P buffer together with `parity`, and the flag value hdr[XSTEP]+k+1).
+// `sa` (statistics enabled): the two statistics launches between the backward and the update — after the last reader
+// of `heads`, before the update kernel, which is the last reader of the slabs and, in a chunk, moves the header word
+// the ring slot is formed from.
 static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int mode, int parity, int k, bool from_hdr,
-                        hipStream_t st, hipEvent_t* ev) {
+                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr) {
   StepParams p = p_in;
   const int buf = (parity + k) & 1;
   // P2P with batches of <= 256 rows: no flatten kernel.  The backward writes its chunk slab (= the w1 / b1 / w2 / b2 /
@@ -1222,6 +1301,7 @@ static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int 
   if (ev) HIPCHK(hipEventRecord(ev[1], st));
   launch_bwd(c, p, st);
   if (ev) HIPCHK(hipEventRecord(ev[2], st));
+  if (sa) launch_stats(u, *sa, st);
   if (mode == IQLHIP_XCH_RCCL) {
     launch_flatten(c, u, c->xflat, false, st);
     NCCLCHK(g_rccl.AllReduce(c->xflat, c->xflat, (size_t)c->L.n_params + 4, RCCL_FLOAT32, RCCL_SUM, c->nccl_comm, st));
@@ -1344,6 +1424,7 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
   if (!c || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_batch(c, b);
   if (rc) return rc;
+  if ((rc = stats_check(c, b->rows))) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
   c->cont.valid = false;                 // (the staging buffers / keep-bits a following train_steps call might continue from)
@@ -1371,7 +1452,9 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
     c->ev_used += 4;
     HIPCHK(hipEventRecord(ev[0], st));
   }
-  rc = enqueue_step(c, p, u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev);
+  StatsArgs sa;
+  if (c->stats_on) sa = make_stats(c, p, nullptr, 0, 0, nullptr);
+  rc = enqueue_step(c, p, u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, c->stats_on ? &sa : nullptr);
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
   HIPCHK(hipGetLastError());
@@ -1412,6 +1495,7 @@ extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, in
   {                                       // (the reference's torch indexing raises on such an index; a gather would fault)
     int rc_i = check_host_indices(idx_host, n, capacity);
     if (rc_i) return rc_i;
+    if ((rc_i = stats_check(c, n))) return rc_i;
   }
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -1428,7 +1512,9 @@ extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, in
   u.losses_mirror = c->on_loss_pin;
   const unsigned long long done_val = ++c->done_seq;
   if (!act_state_host) { u.done_flag = c->done_pin; u.done_val = done_val; }      // (else the follow-up act() signals)
-  int rc = enqueue_step(c, p, u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr);
+  StatsArgs sa;
+  if (c->stats_on) sa = make_stats(c, p, nullptr, 0, 0, nullptr);
+  int rc = enqueue_step(c, p, u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr, c->stats_on ? &sa : nullptr);
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
   const int S = c->dims.state_dim, A = c->dims.action_dim;
@@ -1573,7 +1659,10 @@ static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_
     u.ring_slot = k;
     u.ring_hdr = c->hdr;
     if (k + 1 == K) { u.adv_hdr = c->hdr; u.adv_k = K; u.adv_rows = B; }
-    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr);
+    // (statistics: slot BASE + k of the ring, the loss ring's indexing; the chunk's key carries the setting)
+    StatsArgs sa;
+    if (c->stats_on) sa = make_stats(c, p, c->stats_ring, k, c->k_max, c->hdr);
+    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr);
     if (rc) return rc;
   }
   return IQLHIP_OK;
@@ -1710,6 +1799,7 @@ static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld,
   key.rows = rows_dev; key.ld = ld; key.B = B; key.K = K; key.params = c->params; key.drop_p = c->drop_p;
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
+  key.stats = c->stats_on ? 1 : 0;
   return key;
 }
 
@@ -1769,6 +1859,7 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
                                           void* stream) {
   int rc = check_train_args(c, rows_dev, ld, B);
   if (rc) return rc;
+  if ((rc = stats_check(c, B))) return rc;
   DevGuard guard(c->device);
   HIPCHK(hipDeviceSynchronize());       // a one-off set-up call: ordered after everything queued on any stream
   c->cont.valid = false;
@@ -1868,6 +1959,7 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
   if (rc) return rc;
   if (K < 1 || K > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
   if (size < 1) return fail(IQLHIP_EINVAL, "empty buffer");
+  if ((rc = stats_check(c, B))) return rc;
   double tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (g_trace) tr_t[0] = now_us();
   DevGuard guard(c->device);
@@ -2365,6 +2457,7 @@ extern "C" int iqlhip_debug_read(iqlhip_ctx* c, const char* name, float* host_ou
   else if (!strcmp(name, "h1")) { src = c->sc.h1; n = (int64_t)4 * MB * HID; }
   else if (!strcmp(name, "heads")) { src = c->sc.heads; n = (int64_t)MB * HEAD_LD + (int64_t)NSPLIT * MB * c->dims.action_dim; }
   else if (!strcmp(name, "loss_parts")) { src = c->sc.loss_parts; n = 4 * 64; }
+  else if (!strcmp(name, "xb")) { src = c->xb; n = (int64_t)MB * c->row_ld; }      // the packed batch of the last eager step
   else if (!strcmp(name, "drop_bits")) { src = (const float*)c->drop_bits; n = (int64_t)2 * MB * 8; }
   else if (!strcmp(name, "act_drop_bits")) {
     if (!c->act_drop_bits) return fail(IQLHIP_EINVAL, "no inference keep-bits: iqlhip_set_act_dropout has set no rate > 0");
@@ -2426,7 +2519,12 @@ struct iqlhip_group {
   // iqlhip_group_step / iqlhip_group_train_steps: the agents' records, the IQLHIP_GROUP_DROPOUT records (no rows
   // without the flag) and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS]
   Staging train;
-  Section<GroupRec> recs; Section<GroupDropRec> drops; Section<iqlhip_step_scalars> tabs;
+  Section<GroupRec> recs; Section<GroupDropRec> drops; Section<GroupStatsRec> srecs; Section<iqlhip_step_scalars> tabs;
+  // per-step statistics of the members that enabled them (iqlhip_set_step_stats): [k][IQLHIP_GROUP_MAX_STEPS][IQLHIP_N_STATS],
+  // allocated by the first call with such a member; stats_mask: who had them on in the last call
+  float* stats_ring_dev = nullptr;
+  float* stats_ring_pin = nullptr;
+  bool stats_mask[IQLHIP_MAX_GROUP] = {};
   float* ring_dev = nullptr;          // [k][IQLHIP_GROUP_MAX_STEPS][4] losses of the last call
   float* ring_pin = nullptr;
   int last_n = 0;                     // steps of the last call (rows of the ring that are valid)
@@ -2438,6 +2536,7 @@ struct iqlhip_group {
   Staging on;
   Section<GroupRec> on_recs; Section<StepParams> on_aps; Section<GroupOnlineRec> on_gathers; Section<GroupActRec> on_fins;
   Section<GroupDropRec> on_drops; Section<ActDropRec> on_adrops; Section<iqlhip_step_scalars> on_tabs;
+  Section<GroupStatsRec> on_srecs;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
   // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in act_host (the
@@ -2494,6 +2593,8 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   g->act.free();
   if (g->ring_dev) (void)hipFree(g->ring_dev);
   if (g->ring_pin) (void)hipHostFree(g->ring_pin);
+  if (g->stats_ring_dev) (void)hipFree(g->stats_ring_dev);
+  if (g->stats_ring_pin) (void)hipHostFree(g->stats_ring_pin);
   if (g->up_done) (void)hipEventDestroy(g->up_done);
   if (g->done_pin) (void)hipHostFree(g->done_pin);
   if (g->act_up) (void)hipEventDestroy(g->act_up);
@@ -2516,6 +2617,7 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     const size_t n_drop = (flags & IQLHIP_GROUP_DROPOUT) ? k : 0;      // (without the flag: the layouts of a plain group)
     g->recs = g->train.add<GroupRec>(k);
     g->drops = g->train.add<GroupDropRec>(n_drop);
+    g->srecs = g->train.add<GroupStatsRec>(k);
     g->tabs = g->train.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
     g->on_recs = g->on.add<GroupRec>(k);
     g->on_aps = g->on.add<StepParams>(k);
@@ -2524,6 +2626,7 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->on_drops = g->on.add<GroupDropRec>(n_drop);
     g->on_adrops = g->on.add<ActDropRec>(n_drop);
     g->on_tabs = g->on.add<iqlhip_step_scalars>(k);
+    g->on_srecs = g->on.add<GroupStatsRec>(k);
     g->act_packs = g->act.add<GroupPackRec>(k);
     g->act_ps = g->act.add<StepParams>(k);
     g->act_fins = g->act.add<GroupActRowsRec>(k);
@@ -2620,6 +2723,8 @@ static int group_check_call(iqlhip_group* g, const int32_t* rows) {
   for (int i = 0; i < g->k; ++i)
     if (g->m[0]->precision == 1 && rows[i] > LB_MIN_ROWS)
       return fail(IQLHIP_EUNSUPPORTED, "bf16 groups take batches of at most %d rows (the large-batch kernels have no group form)", LB_MIN_ROWS);
+  for (int i = 0; i < g->k; ++i)
+    if ((rc = stats_check(g->m[i], rows[i]))) return rc;
   return IQLHIP_OK;
 }
 
@@ -2709,12 +2814,42 @@ static int group_upload(iqlhip_group* g, int n, hipStream_t st) {
 static iqlhip_step_scalars* group_tab(const iqlhip_group* g, int i) { return g->train.host(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
 static const iqlhip_step_scalars* group_sched(const iqlhip_group* g, int i) { return g->train.device(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
 
-static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st) {
+// Per-step statistics in a group: one record per member (indexed like the GroupRecs; enabled = the member has them on)
+// built from the member's step record, its statistics going to row (member, step) of the group's statistics ring.
+// Returns whether any member has them on (none: nothing is launched); remembers who in stats_mask.
+static int group_stats_records(iqlhip_group* g, GroupStatsRec* sr, const GroupRec* recs_host, bool* any) {
+  *any = false;
+  for (int i = 0; i < g->k; ++i) *any = *any || g->m[i]->stats_on;
+  if (*any && !g->stats_ring_dev) {
+    const size_t ring = (size_t)g->k * IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS * sizeof(float);
+    HIPCHK(hipMalloc((void**)&g->stats_ring_dev, ring));
+    HIPCHK(hipMemset(g->stats_ring_dev, 0, ring));
+    HIPCHK(hipHostMalloc((void**)&g->stats_ring_pin, ring, hipHostMallocDefault));
+  }
+  for (int i = 0; i < g->k; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    memset(&sr[i], 0, sizeof sr[i]);
+    g->stats_mask[i] = c->stats_on;
+    if (!c->stats_on) continue;
+    sr[i].a = make_stats(c, recs_host[i].p, g->stats_ring_dev + (size_t)i * IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS, 0,
+                         IQLHIP_GROUP_MAX_STEPS, nullptr);
+    sr[i].enabled = 1;
+  }
+  return IQLHIP_OK;
+}
+
+// srecs: the device copy of the call's statistics records, or nullptr when no member has statistics on.
+static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st,
+                              const GroupStatsRec* srecs) {
   const iqlhip_ctx* c = g->m[0];
   const int K = g->k;
   const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K;
   hipLaunchKernelGGL(fwd_group_kernel(bf, dma, /*multi=*/q.fwd_l2 > 0), dim3(q.fwd_nb, K), dim3(256), fwd_lds(c, q.fwd_work), st, recs);
   hipLaunchKernelGGL(bwd_group_kernel(bf, q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs);
+  if (srecs) {      // (between the backward and the update, as in a solo step: enqueue_step)
+    hipLaunchKernelGGL(iql_stats_gradsq_group_kernel, dim3(4 * stats_parts(c), K), dim3(256), 0, st, recs, srecs, s);
+    hipLaunchKernelGGL(iql_step_stats_group_kernel, dim3(1, K), dim3(256), 0, st, recs, srecs, s);
+  }
   hipLaunchKernelGGL(iql_update_group_kernel, dim3(q.upd_nb, K), dim3(256), 0, st, recs, s);
 }
 
@@ -2766,10 +2901,13 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
     group_tab(g, i)[0] = sc[i];
   }
   const int n_draw = group_drop_records_packed(g, g->train.host(g->drops), rows.v);
+  bool stats = false;
+  rc = group_stats_records(g, g->train.host(g->srecs), g->train.host(g->recs), &stats);
+  if (rc) return rc;
   rc = group_upload(g, 1, st);
   if (rc) return rc;
   group_launch_dropmask(g, g->train.device(g->drops), n_draw, q.max_rows, st);
-  group_launch_step(g, g->train.device(g->recs), q, 0, st);
+  group_launch_step(g, g->train.device(g->recs), q, 0, st, stats ? g->train.device(g->srecs) : nullptr);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
@@ -2822,6 +2960,9 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
       draws = draws || d[i].active;
     }
   }
+  bool stats = false;
+  rc = group_stats_records(g, g->train.host(g->srecs), g->train.host(g->recs), &stats);
+  if (rc) return rc;
   rc = group_upload(g, n, st);
   if (rc) return rc;
   const iqlhip_ctx* c0 = g->m[0];
@@ -2835,7 +2976,7 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
       hipLaunchKernelGGL(iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0, st, recs, g->train.device(g->drops), s);
     else
       hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, recs, s);
-    group_launch_step(g, recs, q, s, st);
+    group_launch_step(g, recs, q, s, st, stats ? g->train.device(g->srecs) : nullptr);
   }
   if (g->flags & IQLHIP_GROUP_DROPOUT)      // (iqlhip_train_steps moves every context's position, whatever its rate)
     for (int i = 0; i < g->k; ++i) g->m[i]->drop_step += (unsigned long long)n;
@@ -2862,6 +3003,25 @@ extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, 
   if (n < 1 || n > g->last_n) return fail(IQLHIP_EINVAL, "n_steps %d outside [1,%d] (steps of the last group call)", n, g->last_n);
   DevGuard guard(g->device);
   return group_losses_out(g, out, n, (hipStream_t)stream);
+}
+
+extern "C" int iqlhip_group_read_step_stats(iqlhip_group* g, float* out, int32_t n, void* stream) {
+  if (!g || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n < 1 || n > g->last_n) return fail(IQLHIP_EINVAL, "n_steps %d outside [1,%d] (steps of the last group call)", n, g->last_n);
+  DevGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t row = (size_t)IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS;
+  for (int i = 0; i < g->k; ++i)
+    if (g->stats_mask[i])
+      HIPCHK(hipMemcpyAsync(g->stats_ring_pin + i * row, g->stats_ring_dev + i * row, (size_t)n * IQLHIP_N_STATS * sizeof(float),
+                            hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int s = 0; s < n; ++s)
+    for (int i = 0; i < g->k; ++i)
+      for (int j = 0; j < IQLHIP_N_STATS; ++j)
+        out[((size_t)s * g->k + i) * IQLHIP_N_STATS + j] =
+            g->stats_mask[i] ? g->stats_ring_pin[i * row + (size_t)s * IQLHIP_N_STATS + j] : __builtin_nanf("");
+  return IQLHIP_OK;
 }
 
 // One online iteration of every member (iqlhip_online_step for each, include/iqlhip.h) in one set of launches: ring
@@ -2943,6 +3103,9 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
     ++n_req;
   }
   const int n_draw = group_drop_records_packed(g, on.host(g->on_drops), n);
+  bool stats = false;
+  rc = group_stats_records(g, on.host(g->on_srecs), recs, &stats);
+  if (rc) return rc;
   // (a synchronous call: the previous one's upload has been read long ago)
   HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((q.max_rows * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
@@ -2953,7 +3116,7 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
     hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
   group_launch_dropmask(g, on.device(g->on_drops), n_draw, q.max_rows, st);
-  group_launch_step(g, on.device(g->on_recs), q, 0, st);
+  group_launch_step(g, on.device(g->on_recs), q, 0, st, stats ? on.device(g->on_srecs) : nullptr);
   const unsigned long long done_val = ++g->done_seq;
   if (n_req > 0) {
     // (bf16: the update has just rewritten the shadows from the new masters — the conversion refresh_shadows makes)

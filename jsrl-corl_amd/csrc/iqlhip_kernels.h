@@ -1125,6 +1125,159 @@ __global__ __launch_bounds__(256) void iql_gather_drop_group_kernel(const GroupR
                      (int)gridDim.x * 256);
 }
 
+// ---------------------------------------------------------------------------
+// Per-step training statistics (iqlhip_set_step_stats, opt-in): IQLHIP_N_STATS floats that describe the
+// batch a step trained on under the parameters before its update — 13 row statistics from the head partials the forward
+// left in `heads` and the batch's r / d columns, and the L2 norms of the three optimizer groups' gradients from the
+// slabs the backward left.  Two launches between a step's backward and its update kernel (the backward is the last
+// reader of `heads`, the update the last reader of the slabs, and — in a chunk — the kernel that moves the header word
+// the ring slot is formed from); both only read step state and write only the statistics scratch / ring.
+//   1. iql_stats_gradsq_kernel  block (net = blockIdx.x & 3, window w = blockIdx.x >> 2): the sum of squares of the
+//      net's gradient elements [seg_begin + 1024 w, + 1024) — the elements exactly as Adam receives them (slab_grad's
+//      sum, times grad_scale when that is not 1) — to gparts[net][w].
+//      Accumulation structure: a thread adds its 4 squares, 64 lanes combine by 6 xor-shuffles, 4 waves through LDS
+//      (block_sum_256): ONE fp32 value stands for at most m = 1024 terms, each of which passes through 11 additions.
+//   2. iql_step_stats_kernel    ONE block per agent: threads walk rows t, t + 256, ... in row order, combine like
+//      block_sum_256 (shuffles, then the four waves in fixed order); waves 0..2 then add the gparts of their optimizer
+//      group (V | Q1, Q2 | pi) in double — lane l takes partials l, l + 64, ..., then 6 xor-shuffles — and write the
+//      square roots.  No atomics, no inter-block order: the result depends on the inputs alone.
+struct StatsArgs {
+  const float* heads;                 // DevScratch::heads of the step
+  const float* xb;                    // the packed batch the step trained on
+  int ld, rows, rd_off;               // row stride, rows, column of r (d follows): 2 S + A
+  float beta, discount, exp_adv_max;
+  float* gparts;                      // [4 nets][n_part] sums of squares (written by launch 1, read by launch 2)
+  int n_part;                         // 1024-element windows of the longest net segment
+  float* last;                        // [IQLHIP_N_STATS] the last step's statistics
+  float* ring;                        // nullable: [ring_cap][IQLHIP_N_STATS], slot = ring_slot + step + ring_hdr[HDR_BASE]
+  int ring_slot, ring_cap;
+  const unsigned long long* ring_hdr; // nullable (chunk replay, cf. UpdParams::ring_hdr)
+};
+
+template <class T, class Op>
+__device__ __forceinline__ T block_reduce_256(T v, T* red /*>=4*/, Op op) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return op(op(red[0], red[1]), op(red[2], red[3]));
+}
+
+__device__ __forceinline__ void stats_gradsq_block(const UpdParams& u, int step, float* gparts, int n_part, float* red) {
+  const int net = (int)(blockIdx.x & 3u), w = (int)(blockIdx.x >> 2);
+  if (w >= n_part) return;                                      // (block-uniform)
+  const long long seg_b = u.L.net[net].seg_begin, seg_e = u.L.net[net].seg_end;
+  const long long e = seg_b + (long long)w * 1024 + 4 * (long long)threadIdx.x;
+  float ss = 0.f;
+  if (e < seg_e) {
+    const f32x4 gr = slab_grad<false>(u, e, net);
+    const float gs = u.sched ? u.sched[u.sched_idx + step].grad_scale : u.sc.grad_scale;
+    float g[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g[k] = (gs == 1.f) ? gr[k] : gr[k] * gs;      // (iqlhip_upd_body.inc's gk)
+    // (products and sums spelled out as separately rounded operations: the solo and the group kernel must agree bit for bit)
+    ss = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g[0], g[0]), __fmul_rn(g[1], g[1])), __fmul_rn(g[2], g[2])), __fmul_rn(g[3], g[3]));
+  }
+  ss = block_sum_256(ss, red);
+  if (threadIdx.x == 0) gparts[net * n_part + w] = ss;
+}
+
+__device__ __forceinline__ void step_stats_block(const StatsArgs& a, int step, float* red, float* outs /*16*/) {
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  float s[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s[k] = 0.f;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
+  int n_pos = 0, n_clamp = 0;
+  for (int row = tid; row < a.rows; row += 256) {
+    const unsigned o = (unsigned)row * (unsigned)HEAD_LD;
+    f32x4 h[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) h[i] = *(const f32x4*)(a.heads + (o + 4u * i));
+    const unsigned ox = (unsigned)row * (unsigned)a.ld + (unsigned)a.rd_off;
+    const float r = a.xb[ox], d = a.xb[ox + 1u];
+    // head = sum4 of the four slice partials, as row_finish forms it
+    const float nv = sum4(h[0]), v = sum4(h[1]), q1 = sum4(h[4]), q2 = sum4(h[5]);
+    const float tq = fminf(sum4(h[2]), sum4(h[3]));
+    const float adv = tq - v;                                   // row_finish's u
+    const float y = fmaf((1.f - d) * a.discount, nv, r);      // (one rounding; spelled out: the solo and the group kernel agree)
+    const float ex = expf(a.beta * adv);
+    s[0] += v; s[1] += nv; s[2] += q1; s[3] += q2; s[4] += tq; s[5] += y; s[6] += fabsf(q1 - q2); s[7] += adv;
+    s[8] += fminf(ex, a.exp_adv_max);
+    mn = fminf(mn, adv);
+    mx = fmaxf(mx, adv);
+    n_pos += (adv < 0.f) ? 0 : 1;                               // the side row_finish's weight takes (u < 0 is the other)
+    n_clamp += (ex >= a.exp_adv_max) ? 1 : 0;
+  }
+  const float nrows = (float)a.rows;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float t = block_sum_256(s[k], red);
+    if (tid == 0) outs[(k < 8) ? k : 11] = t / nrows;
+  }
+  mn = block_reduce_256(mn, red, [](float x, float y) { return fminf(x, y); });
+  mx = block_reduce_256(mx, red, [](float x, float y) { return fmaxf(x, y); });
+  int* const redi = (int*)red;
+  n_pos = block_reduce_256(n_pos, redi, [](int x, int y) { return x + y; });
+  n_clamp = block_reduce_256(n_clamp, redi, [](int x, int y) { return x + y; });
+  if (tid == 0) {
+    outs[8] = mn;
+    outs[9] = mx;
+    outs[10] = (float)n_pos / nrows;
+    outs[12] = (float)n_clamp / nrows;
+  }
+  // gradient norms: wave g adds optimizer group g's block partials in double, fixed order
+  if (wave < 3) {
+    const int first = (wave == 0) ? 0 : ((wave == 1) ? a.n_part : 3 * a.n_part);
+    const int cnt = (wave == 1) ? 2 * a.n_part : a.n_part;
+    double acc = 0.0;
+    for (int i = lane; i < cnt; i += 64) acc += (double)a.gparts[first + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) outs[13 + wave] = (float)sqrt(acc);
+  }
+  __syncthreads();
+  if (tid < IQLHIP_N_STATS) {
+    const float val = outs[tid];
+    a.last[tid] = val;
+    if (a.ring) {
+      const long long slot = (long long)a.ring_slot + step + (a.ring_hdr ? (long long)a.ring_hdr[HDR_BASE] : 0ll);
+      if (slot >= 0 && slot < (long long)a.ring_cap) a.ring[IQLHIP_N_STATS * slot + tid] = val;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void iql_stats_gradsq_kernel(UpdParams u, float* gparts, int n_part) {
+  __shared__ float red[4];
+  stats_gradsq_block(u, 0, gparts, n_part, red);
+}
+__global__ __launch_bounds__(256) void iql_step_stats_kernel(StatsArgs a) {
+  __shared__ float red[4];
+  __shared__ float outs[IQLHIP_N_STATS];
+  step_stats_block(a, 0, red, outs);
+}
+
+// Group forms (grid.y = member): a member that has not enabled statistics has enabled = 0 and its blocks exit; the
+// others run the solo bodies on their own records — bit-identical to their solo statistics.
+struct GroupStatsRec { StatsArgs a; int enabled; };
+__global__ __launch_bounds__(256) void iql_stats_gradsq_group_kernel(const GroupRec* __restrict__ recs,
+                                                                     const GroupStatsRec* __restrict__ srecs, int step) {
+  __shared__ float red[4];
+  const GroupStatsRec& s = srecs[blockIdx.y];
+  if (!s.enabled) return;
+  const GroupRec& r = recs[blockIdx.y];
+  stats_gradsq_block(r.u, min(max(step, 0), r.n_steps - 1), s.a.gparts, s.a.n_part, red);
+}
+__global__ __launch_bounds__(256) void iql_step_stats_group_kernel(const GroupRec* __restrict__ recs,
+                                                                   const GroupStatsRec* __restrict__ srecs, int step) {
+  __shared__ float red[4];
+  __shared__ float outs[IQLHIP_N_STATS];
+  const GroupStatsRec& s = srecs[blockIdx.y];
+  if (!s.enabled) return;
+  step_stats_block(s.a, min(max(step, 0), recs[blockIdx.y].n_steps - 1), red, outs);
+}
+
 // Policy inference (GaussianPolicy.act / DeterministicPolicy.act, algorithms/finetune/iql.py:371-379, 404-413):
 // states -> packed rows whose first S columns are the state (the rest zero), then iql_fwd_kernel with
 // only_inst = 6, then this finish kernel over the policy head partials:

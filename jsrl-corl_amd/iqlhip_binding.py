@@ -17,6 +17,11 @@ IQLHIP_HIDDEN = 256
 IQLHIP_ACT_ROWS = 4096      # rows per iqlhip_actor_forward call (include/iqlhip.h)
 IQLHIP_MAX_WORLD = 8
 IQLHIP_GRAPH_STEPS = 64
+IQLHIP_N_STATS = 16           # floats per step of the opt-in training statistics (include/iqlhip.h)
+# their names, in the library's order (ImplicitQLearning.set_step_stats)
+STAT_NAMES = ("v_mean", "next_v_mean", "q1_mean", "q2_mean", "target_q_mean", "td_target_mean", "q_gap_mean",
+              "adv_mean", "adv_min", "adv_max", "adv_pos_frac", "exp_adv_mean", "exp_adv_clamped_frac",
+              "grad_norm_vf", "grad_norm_qf", "grad_norm_actor")
 IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
 IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the actions are written
 IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train with actor dropout
@@ -164,6 +169,10 @@ SYMBOLS = [
     ("iqlhip_group_actor_forward", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_void_p),
                                              C.c_int64, C.c_int32, C.c_void_p]),
+    ("iqlhip_set_step_stats", C.c_int, [C.c_void_p, C.c_int]),
+    ("iqlhip_read_step_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
+    ("iqlhip_read_stats_ring", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
+    ("iqlhip_group_read_step_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

@@ -180,9 +180,21 @@ class ImplicitQLearningGroup:
             adam_next.append(t1)
         return scs, adam_next
 
+    def _group_stats(self, n: int) -> Optional[np.ndarray]:
+        """[n, K, 16] statistics of the first n steps of the last library group call (NaN rows: members that have not
+        called set_step_stats(True)); None when no member has."""
+        if not any(t._step_stats for t in self.trainers):
+            return None
+        K = len(self.trainers)
+        out = (C.c_float * (n * K * hb.IQLHIP_N_STATS))()
+        hb.check(hb.lib().iqlhip_group_read_step_stats(self._g, out, n, self.trainers[0]._stream()))
+        return np.frombuffer(out, dtype=np.float32).reshape(n, K, hb.IQLHIP_N_STATS).copy()
+
     def _commit_step(self, adam_next, out) -> List[Dict[str, float]]:
-        """Move every member's counters and schedule past the step the library has taken; out: its losses [K][3]."""
+        """Move every member's counters and schedule past the step the library has taken; out: its losses [K][3].
+        Members with step statistics on get their "stats/<name>" entries, as their solo train() would."""
         logs = []
+        stats = self._group_stats(1)
         for k, t in enumerate(self.trainers):
             t.total_it += 1
             t._adam_t = adam_next[k]
@@ -191,6 +203,8 @@ class ImplicitQLearningGroup:
             t._eager_next = None
             logs.append({"value_loss": float(out[3 * k]), "q_loss": float(out[3 * k + 1]),
                          "actor_loss": float(out[3 * k + 2])})
+            if t._step_stats:
+                logs[-1].update({"stats/" + name: float(stats[0, k, i]) for i, name in enumerate(hb.STAT_NAMES)})
         return logs
 
     def train(self, batches: Sequence) -> List[Dict[str, float]]:
@@ -227,12 +241,14 @@ class ImplicitQLearningGroup:
 
     # ------------------------------------------------------------------ device-drawn steps
     def train_steps(self, buffers, n_steps: int, batch_size, seeds: Sequence[int],
-                    return_losses: bool = True, chunk: int = K_MAX) -> Optional[np.ndarray]:
+                    return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
         """n_steps `sample -> train` iterations per member (ImplicitQLearning.train_steps for each): member k draws its
         rows from buffers[k] (or the one shared buffer) under seeds[k] — exactly the rows its own train_steps(buffer,
         n_steps, batch_size, seed=seeds[k]) would draw.  batch_size: an int, or one int per member (unequal sizes:
         mixed_batch groups only; member k then draws what its train_steps at batch_size[k] would).  Returns losses
-        [K, n_steps, 3] when return_losses, else None."""
+        [K, n_steps, 3] when return_losses, else None.  return_stats: returns the per-step statistics [n_steps, K, 16]
+        instead (hb.STAT_NAMES order; the rows of members that have not called set_step_stats(True) are NaN;
+        ValueError when no member has)."""
         K = len(self.trainers)
         bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
         seeds = [int(s) for s in seeds]
@@ -244,9 +260,13 @@ class ImplicitQLearningGroup:
         self._check_members()
         for B in Bs:
             self._check_batch_size(B)
+        if return_stats and not any(t._step_stats for t in self.trainers):
+            raise ValueError("iqlhip: train_steps(return_stats=True) needs set_step_stats(True) on at least one member")
         if K == 1:      # a group of one IS the solo call (chunk graphs, rows staged by idle forward blocks: faster)
             out = self.trainers[0].train_steps(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
-                                               chunk=chunk)
+                                               chunk=chunk, return_stats=return_stats)
+            if return_stats:
+                return out[1][:, None]
             return None if out is None else out[None]
         sizes, inv = [], []
         for t, buf, B in zip(self.trainers, bufs, Bs):
@@ -264,6 +284,7 @@ class ImplicitQLearningGroup:
         B_arr = (C.c_int32 * K)(*Bs)
         halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
         losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
+        stats = np.empty((n_steps, K, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
         done = 0
         while done < n_steps:
             k = min(chunk, n_steps - done)
@@ -285,8 +306,10 @@ class ImplicitQLearningGroup:
                 out = (C.c_float * (K * k * 3))()
                 hb.check(lib.iqlhip_group_read_losses(g, out, k, stream))
                 losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
+            if return_stats:
+                stats[done:done + k] = self._group_stats(k)
             done += k
-        return losses
+        return stats if return_stats else losses
 
     # ------------------------------------------------------------------ the online loop
     def online_step(self, buffers, states, actions, rewards, next_states, dones, batch_size,

@@ -35,6 +35,7 @@ from iqlhip_networks import (DeterministicPolicy, GaussianPolicy, LOG_STD_MAX, L
 TensorBatch = List[torch.Tensor]
 EXP_ADV_MAX = 100.0
 K_MAX = 1024  # steps per captured hipGraph chunk (library limit)
+STATS_BF16_MAX_ROWS = 512  # bf16 batches beyond this take the large-batch kernels, which keep no step statistics
 
 
 def _is_gpu(device) -> bool:
@@ -100,6 +101,8 @@ class ImplicitQLearning:
         self._act_dropout = False     # set_act_dropout: actor dropout inside the device inference forward (opt-in)
         self._act_dropout_sent = None  # (rate, key) the context's inference side holds; None: never sent (rate 0)
         self._act_key_stale = False   # set_dropout_seed since: the next inference call sends the new key
+        self._step_stats = False      # set_step_stats: per-step training statistics (opt-in)
+        self._step_stats_sent = False  # ... as the current context holds it
         if _is_gpu(device):
             self._attach(max_batch=256)
             register_actor_owner(self.actor, self)
@@ -189,6 +192,7 @@ class ImplicitQLearning:
         self._table_cache = None
         self._hyper_sent = self._hyper_tuple()
         self._dropout_sent = 0.0
+        self._step_stats_sent = False
         self._max_batch = max_batch
         if getattr(self, "_precision", "f32") == "bf16":     # survives a re-attach for a larger batch
             hb.check(hb.lib().iqlhip_set_precision(self._ctx, 1))
@@ -323,7 +327,37 @@ class ImplicitQLearning:
         if rows > self._max_batch:
             self._attach(max_batch=(rows + 255) // 256 * 256)
 
+    def set_step_stats(self, enabled: bool) -> None:
+        """Opt in to (or out of) per-step training statistics: the 16 numbers of hb.STAT_NAMES (Q / V / advantage
+        means, the advantage weights' clamp share, the three gradient norms), computed on the device
+        from the batch each step trained on.  Enabled, train() and online_step() add them to their dict as
+        "stats/<name>" and train_steps(..., return_stats=True) returns them per step.  Parameters, losses and random
+        streams are the same with and without.  Not supported under data parallelism or for bf16 batches of more
+        than 512 rows (NotImplementedError from the step).  Not part of the reference's surface."""
+        self._step_stats = bool(enabled)
+
+    def _check_step_stats(self, rows: int) -> None:
+        """The two cases statistics are not built for — refused before anything is launched."""
+        if not self._step_stats:
+            return
+        if self._dp_world > 1 or self._dp_exchange is not None:
+            raise NotImplementedError("iqlhip: step statistics are not supported under data parallelism (the local "
+                                      "gradient is not what Adam receives)")
+        if getattr(self, "_precision", "f32") == "bf16" and rows > STATS_BF16_MAX_ROWS:
+            raise NotImplementedError(f"iqlhip: step statistics are not supported for bf16 batches of more than "
+                                      f"{STATS_BF16_MAX_ROWS} rows (got {rows}): the large-batch path keeps its row "
+                                      "state in another layout")
+
+    def _stats_entries(self) -> Dict[str, float]:
+        """The last step's statistics as dict entries; nothing when they are off."""
+        if not self._step_stats:
+            return {}
+        out = (C.c_float * hb.IQLHIP_N_STATS)()
+        hb.check(hb.lib().iqlhip_read_step_stats(self._ctx, out, self._stream()))
+        return {"stats/" + name: float(out[i]) for i, name in enumerate(hb.STAT_NAMES)}
+
     def _prepare(self, rows: int) -> None:
+        self._check_step_stats(rows)
         self._require_gpu()
         if rows > self._max_batch:
             self._attach(max_batch=(rows + 255) // 256 * 256)
@@ -336,6 +370,9 @@ class ImplicitQLearning:
         if p_eff != self._dropout_sent:
             hb.check(hb.lib().iqlhip_set_dropout(self._ctx, p_eff, self._dropout_key()))
             self._dropout_sent = p_eff
+        if self._step_stats != self._step_stats_sent:
+            hb.check(hb.lib().iqlhip_set_step_stats(self._ctx, 1 if self._step_stats else 0))
+            self._step_stats_sent = self._step_stats
 
     def _dropout_key(self) -> int:
         """The key of this trainer's keep-bit streams: set_dropout_seed(seed), else torch.initial_seed(), per rank."""
@@ -462,7 +499,10 @@ class ImplicitQLearning:
             return None
         out = (C.c_float * 3)()
         hb.check(lib.iqlhip_read_losses(self._ctx, out, self._stream()))
-        return {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
+        log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
+        if self._step_stats:
+            log.update(self._stats_entries())
+        return log
 
     def train(self, batch: TensorBatch) -> Dict[str, float]:
         """One IQL gradient step (iql.py:542-563).  Returns the three losses as floats
@@ -535,6 +575,8 @@ class ImplicitQLearning:
         if rc:
             hb.check(rc)
         log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
+        if self._step_stats:
+            log.update(self._stats_entries())
         return log
 
     def online_step(self, replay_buffer, state, action, reward: float, next_state, done: bool,
@@ -598,6 +640,8 @@ class ImplicitQLearning:
         self._adam_t = adam_next
         self._advance_schedule(1)
         log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
+        if self._step_stats:
+            log.update(self._stats_entries())
         return log if act_next is None else (log, a_out)
 
     def _schedule_state(self):
@@ -742,7 +786,7 @@ class ImplicitQLearning:
         self._ts_token = None
 
     def train_steps(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0,
-                    return_losses: bool = True, chunk: int = K_MAX) -> Optional[np.ndarray]:
+                    return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
         """n_steps consecutive `sample -> train` iterations without host round trips
         (the offline loop body, algorithms/offline/iql.py:631-635): indices are drawn on
         the device (uniform with replacement, Philox keyed by (seed, total_it)); the library
@@ -751,8 +795,13 @@ class ImplicitQLearning:
         Adam / cosine-LR scalars are precomputed on the host (the next call's while the GPU
         runs this one's).  Under data parallelism every rank draws its own rows (rank-offset
         stream) and the gradient exchange runs inside the same stream / graph.  Returns losses
-        [n_steps,3] (value, q, actor) when return_losses, else None (fully asynchronous)."""
+        [n_steps,3] (value, q, actor) when return_losses, else None (fully asynchronous).
+        return_stats (needs set_step_stats(True), else ValueError): returns (losses, stats) instead, stats the
+        [n_steps, 16] per-step statistics in hb.STAT_NAMES order."""
+        if return_stats and not self._step_stats:
+            raise ValueError("iqlhip: train_steps(return_stats=True) needs set_step_stats(True) first")
         size, inv_batch = self._train_steps_args(replay_buffer, batch_size)
+        stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
         chunk = max(1, min(int(chunk), K_MAX))
         lib = hb.lib()
         rank = self._dp_rank if self._dp_world > 1 else 0
@@ -784,7 +833,11 @@ class ImplicitQLearning:
                 buf = (C.c_float * (3 * k))()
                 hb.check(lib.iqlhip_read_loss_ring(self._ctx, buf, k, stream))
                 losses[done - k: done] = np.frombuffer(buf, dtype=np.float32).reshape(k, 3)
-        return losses
+            if return_stats:
+                sbuf = (C.c_float * (hb.IQLHIP_N_STATS * k))()
+                hb.check(lib.iqlhip_read_stats_ring(self._ctx, sbuf, k, stream))
+                stats[done - k: done] = np.frombuffer(sbuf, dtype=np.float32).reshape(k, hb.IQLHIP_N_STATS)
+        return (losses, stats) if return_stats else losses
 
     def train_steps_dp(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0) -> None:
         """Data-parallel multi-step run without host syncs (= train_steps(..., return_losses=False))."""
