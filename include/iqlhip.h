@@ -157,7 +157,11 @@ int iqlhip_set_act_dropout(iqlhip_ctx* ctx, float p, uint64_t seed);
 int iqlhip_get_act_dropout_counter(const iqlhip_ctx* ctx, uint64_t* out);
 int iqlhip_set_act_dropout_counter(iqlhip_ctx* ctx, uint64_t n);
 /* Tests: inject keep-bits for the next steps instead of drawing them ([rows][8] uint32 per layer, bit j of
- * word w = hidden unit 32w + j); cleared by the next iqlhip_set_dropout. */
+ * word w = hidden unit 32w + j); cleared by the next iqlhip_set_dropout.  The single-step entry points (iqlhip_step and
+ * its forms, iqlhip_online_step, iqlhip_forward_backward) and the group calls use them.  iqlhip_train_steps and
+ * iqlhip_train_steps_prepare cannot (their steps alternate between two keep-bit halves and draw the next step's bits as
+ * they go): while injected masks are pending they return IQLHIP_EUNSUPPORTED before anything is launched or any
+ * position moves. */
 int iqlhip_debug_write_masks(iqlhip_ctx* ctx, const uint32_t* keep0_host, const uint32_t* keep1_host, int32_t rows,
                              void* stream);
 
@@ -394,7 +398,8 @@ int iqlhip_group_create(iqlhip_ctx* const* members, int k, iqlhip_group** out);
  * stream position.  Every training call draws member k's keep-bits exactly as its solo call would — key drop_seed,
  * the member's threshold, position drop_step — in the group's own launches, and moves the position as the solo call
  * does: iqlhip_group_step / iqlhip_group_online_step by one for a member that draws, iqlhip_group_train_steps by n
- * for every member.  Masks written by iqlhip_debug_write_masks are kept (no draw for that member).  The inference
+ * for every member with a rate above 0 (a rate of 0 never moves a position).  Masks written by
+ * iqlhip_debug_write_masks are kept (no draw for that member).  The inference
  * forwards are eval-mode for every member without an inference rate (iqlhip_set_act_dropout; a member with one needs
  * this flag too).  Unknown flag bits: IQLHIP_EINVAL, checked before any member is looked at; *out is
  * written on success only. */

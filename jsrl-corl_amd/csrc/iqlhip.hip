@@ -1792,6 +1792,16 @@ static int check_train_args(const iqlhip_ctx* c, const float* rows_dev, int64_t 
   return IQLHIP_OK;
 }
 
+// Masks written by iqlhip_debug_write_masks fill one of the two keep-bit halves, and the chunks' steps alternate between
+// the halves and draw the next step's bits as they go: the multi-step driver cannot honour injected masks, so it refuses
+// while they are pending — before anything is launched or any position moves.
+static int inject_check(const iqlhip_ctx* c) {
+  if (c->drop_inject)
+    return fail(IQLHIP_EUNSUPPORTED, "keep-bits injected by iqlhip_debug_write_masks are pending: iqlhip_train_steps draws "
+                "its own (call iqlhip_set_dropout first, or step with iqlhip_step)");
+  return IQLHIP_OK;
+}
+
 static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, int32_t K, float inv_batch,
                          int parity, int head = 0) {
   GraphKey key;
@@ -1835,7 +1845,7 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
     r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work);
     if (r) return r;
     cg->last = st;
-    c->drop_step += (unsigned long long)n;
+    if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
     if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)n;
     return IQLHIP_OK;
   }
@@ -1850,7 +1860,9 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
   }
   HIPCHK(hipGraphLaunch(gexec, st));
   cg->last = st;
-  c->drop_step += (unsigned long long)n;
+  // (the keep-bit position moves with the steps that draw: a rate of 0 leaves it alone, as iqlhip_step does — a caller
+  //  that switches the actor to eval() for some steps finds the stream where eager steps would have left it)
+  if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)n;
   return IQLHIP_OK;
 }
@@ -1860,6 +1872,7 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
   int rc = check_train_args(c, rows_dev, ld, B);
   if (rc) return rc;
   if ((rc = stats_check(c, B))) return rc;
+  if ((rc = inject_check(c))) return rc;
   DevGuard guard(c->device);
   HIPCHK(hipDeviceSynchronize());       // a one-off set-up call: ordered after everything queued on any stream
   c->cont.valid = false;
@@ -1960,6 +1973,7 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
   if (K < 1 || K > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
   if (size < 1) return fail(IQLHIP_EINVAL, "empty buffer");
   if ((rc = stats_check(c, B))) return rc;
+  if ((rc = inject_check(c))) return rc;
   double tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (g_trace) tr_t[0] = now_us();
   DevGuard guard(c->device);
@@ -2013,7 +2027,7 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
     rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work);
     if (rc) return rc;
     cg->last = st;
-    c->drop_step += (unsigned long long)head_k;
+    if (c->drop_p > 0.f) c->drop_step += (unsigned long long)head_k;
     if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)head_k;
     rem = K - head_k;
   } else if (g_no_head_graph) {
@@ -2978,8 +2992,8 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
       hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, recs, s);
     group_launch_step(g, recs, q, s, st, stats ? g->train.device(g->srecs) : nullptr);
   }
-  if (g->flags & IQLHIP_GROUP_DROPOUT)      // (iqlhip_train_steps moves every context's position, whatever its rate)
-    for (int i = 0; i < g->k; ++i) g->m[i]->drop_step += (unsigned long long)n;
+  if (g->flags & IQLHIP_GROUP_DROPOUT)      // (as iqlhip_train_steps: the position of every context with a rate above 0)
+    for (int i = 0; i < g->k; ++i) if (g->m[i]->drop_p > 0.f) g->m[i]->drop_step += (unsigned long long)n;
   HIPCHK(hipGetLastError());
   g->last_n = n;
   return IQLHIP_OK;

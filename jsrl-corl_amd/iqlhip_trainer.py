@@ -103,6 +103,7 @@ class ImplicitQLearning:
         self._act_key_stale = False   # set_dropout_seed since: the next inference call sends the new key
         self._step_stats = False      # set_step_stats: per-step training statistics (opt-in)
         self._step_stats_sent = False  # ... as the current context holds it
+        self._masks_injected = False  # inject_dropout_masks since the last iqlhip_set_dropout: train_steps refuses
         if _is_gpu(device):
             self._attach(max_batch=256)
             register_actor_owner(self.actor, self)
@@ -192,6 +193,7 @@ class ImplicitQLearning:
         self._table_cache = None
         self._hyper_sent = self._hyper_tuple()
         self._dropout_sent = 0.0
+        self._masks_injected = False
         self._step_stats_sent = False
         self._max_batch = max_batch
         if getattr(self, "_precision", "f32") == "bf16":     # survives a re-attach for a larger batch
@@ -370,6 +372,7 @@ class ImplicitQLearning:
         if p_eff != self._dropout_sent:
             hb.check(hb.lib().iqlhip_set_dropout(self._ctx, p_eff, self._dropout_key()))
             self._dropout_sent = p_eff
+            self._masks_injected = False      # (iqlhip_set_dropout clears injected masks)
         if self._step_stats != self._step_stats_sent:
             hb.check(hb.lib().iqlhip_set_step_stats(self._ctx, 1 if self._step_stats else 0))
             self._step_stats_sent = self._step_stats
@@ -777,10 +780,19 @@ class ImplicitQLearning:
             raise ValueError("replay buffer is empty")
         return size, dp.inv_batch(batch_size, self._dp_world)
 
+    def _refuse_injected_masks(self) -> None:
+        """train_steps draws its own keep-bits (two halves, the next step's drawn by the step before) and cannot use
+        masks written by inject_dropout_masks.  The library refuses too (IQLHIP_EUNSUPPORTED); raised here, before the
+        scalar table moves the Adam step counts and the actor's schedule."""
+        if getattr(self, "_masks_injected", False):
+            raise NotImplementedError("iqlhip: train_steps draws its own keep-bits and cannot use the masks written by "
+                                      "inject_dropout_masks; step with train(), or clear them (set_dropout_seed)")
+
     def prepare_train_steps(self, replay_buffer, batch_size: int) -> None:
         """Capture and upload the hipGraph chunk train_steps replays for this buffer / batch size now, so that no later
         train_steps call pays for it (it is captured lazily otherwise, by the first call of >= 64 steps)."""
         _, inv_batch = self._train_steps_args(replay_buffer, batch_size)
+        self._refuse_injected_masks()
         hb.check(hb.lib().iqlhip_train_steps_prepare(self._ctx, replay_buffer._rows.data_ptr(), replay_buffer._ld,
                                                       batch_size, inv_batch, self._stream()))
         self._ts_token = None
@@ -801,6 +813,7 @@ class ImplicitQLearning:
         if return_stats and not self._step_stats:
             raise ValueError("iqlhip: train_steps(return_stats=True) needs set_step_stats(True) first")
         size, inv_batch = self._train_steps_args(replay_buffer, batch_size)
+        self._refuse_injected_masks()
         stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
         chunk = max(1, min(int(chunk), K_MAX))
         lib = hb.lib()
@@ -1164,6 +1177,7 @@ class ImplicitQLearning:
         b1 = np.ascontiguousarray(pack_keep_bits(keep1))
         hb.check(hb.lib().iqlhip_debug_write_masks(self._ctx, b0.ctypes.data, b1.ctypes.data, keep0.shape[0],
                                                    self._stream()))
+        self._masks_injected = True
 
     def debug_read(self, name: str) -> np.ndarray:
         self._require_gpu()

@@ -324,3 +324,70 @@ def permutation_bounds(params, batch, hyper):
                 contrib[(net, t)] = min(contrib.get((net, t), np.inf), float(np.max(np.abs(v))))
     return {(net, t): (2.0 * PERM_DEPTH * FP32_U * float(np.max(v)), contrib[(net, t)])
             for net, ts in sums.items() for t, v in ts.items()}
+
+
+# ---------------------------------------------------------------------------
+# How iqlhip_train_steps (csrc/iqlhip.hip) composes a call, restated: the first 2 or 4 steps are launched directly
+# (through the idle-work records of the plain chunk of that size), the rest as replays of fixed chunk graphs.  Each
+# distinct chunk is one entry of the context's graph cache, keyed by what its captured kernel arguments froze.
+
+GRAPH_STEPS = 64
+GRAPH_CACHE_ENTRIES = 12      # chunk_graph evicts the least recently used entry beyond this
+
+
+def _n_chunks_for(rem):
+    n, rem = divmod(rem, GRAPH_STEPS)
+    for c in (16, 4, 2, 1):
+        n += rem // c
+        rem %= c
+    return n
+
+
+def train_steps_decomposition(K):
+    """(head, chunks): the steps launched directly at the head of a K-step call (4 when that leaves fewer chunk launches
+    behind it than 2 does, else 2; 1 for a one-step call) and the chunk sizes replayed after it, in launch order — the
+    even sizes below 64 ascending, the 64-step chunk as often as it fits, a one-step chunk last."""
+    assert K >= 1
+    head = 4 if (K >= 4 and _n_chunks_for(K - 4) < _n_chunks_for(K - 2)) else (2 if K >= 2 else 1)
+    n64, rem = divmod(K - head, GRAPH_STEPS)
+    small = []
+    for c in (16, 4, 2, 1):
+        while rem >= c:
+            small.append(c)
+            rem -= c
+    chunks = [c for c in reversed(small) if c != 1] + [GRAPH_STEPS] * n64 + [c for c in small if c == 1]
+    return head, chunks
+
+
+def train_steps_graph_keys(K, B, rows=0, drop_p=0.0, stats=False):
+    """The graph-cache keys a K-step call at batch size B asks for, in request order (without repeats): the GraphKey
+    fields that vary on one trainer without a data-parallel exchange — (rows, B, chunk steps, drop_p, inv_batch, stats).
+    The head's steps use the plain chunk of their size."""
+    head, chunks = train_steps_decomposition(K)
+    keys = []
+    for k in [head] + chunks:
+        key = (rows, int(B), int(k), float(np.float32(drop_p)), float(np.float32(1.0 / B)), int(bool(stats)))
+        if key not in keys:
+            keys.append(key)
+    return keys
+
+
+def graph_cache_requests(calls, capacity=GRAPH_CACHE_ENTRIES):
+    """Replays the LRU cache over a list of calls (each a list of keys): (distinct keys requested, evictions)."""
+    cache, distinct, evictions = [], set(), 0
+    for keys in calls:
+        for key in keys:
+            distinct.add(key)
+            if key in cache:
+                cache.remove(key)
+            elif len(cache) >= capacity:
+                cache.pop(0)
+                evictions += 1
+            cache.append(key)
+    return len(distinct), evictions
+
+
+# Case 6 of tests/test_hip_between_calls.py (rows written between two train_steps calls), shared with its CPU companion:
+# a 40-row buffer sampled 256 rows at a time, calls of 8 / 6 / 8 steps under one seed, and the rows the single-row
+# writers touch (add_transition's ring pointer stands at row 0; the in-place reward write goes to row 3).
+SMALL_BUFFER = {"N": 40, "B": 256, "segments": (8, 6, 8), "seed": 5, "pointer_row": 0, "reward_row": 3}

@@ -117,3 +117,46 @@ def head_values(tr, params, B):
     out = {"next_v": s[0], "v": s[1], "qt1": s[2], "qt2": s[3], "q1": s[4], "q2": s[5],
            "pre": ((pi[0] + pi[1]) + pi[2]) + pi[3]}
     return out
+
+
+# ---------------------------------------------------------------------------
+# Between-calls harness (tests/test_hip_between_calls.py): train_steps on a live trainer against eager steps on the
+# same device-drawn indices.  iqlhip_step uses no graph, no rows staged ahead and no continuation, so the eager twin
+# is independent of everything train_steps keeps between two calls.
+
+def draw_indices(n, size, seed, offset):
+    import iqlhip_binding as hb
+    idx = torch.empty(n, dtype=torch.int64, device="cuda")
+    hb.check(hb.lib().iqlhip_draw_indices(idx.data_ptr(), n, size, seed, offset, torch.cuda.current_stream().cuda_stream))
+    return idx
+
+
+def eager_segment(tr, buf, K, B, seed):
+    """K eager train() steps on the rows train_steps(buf, K, B, seed) draws at the trainer's current total_it:
+    losses float32 [K, 3]."""
+    idx = draw_indices(K * B, buf._index_bound(), seed, tr.total_it * ((B + 1) // 2))
+    out = np.empty((K, 3), dtype=np.float32)
+    for k in range(K):
+        log = tr.train(buf.gather(idx[k * B:(k + 1) * B]))
+        out[k] = [log["value_loss"], log["q_loss"], log["actor_loss"]]
+    return out
+
+
+def assert_same_trainer_state(a, b, what=""):
+    """Parameters, targets and Adam moments bitwise equal; the actor learning rate and the step counts equal."""
+    pa, pb = read_params(a), read_params(b)
+    for n in pa:
+        for k in pa[n]:
+            assert np.array_equal(pa[n][k], pb[n][k]), (what, "param", n, k)
+    ma, mb = read_moments(a), read_moments(b)
+    for mv in ma:
+        for n in ma[mv]:
+            for k in ma[mv][n]:
+                assert np.array_equal(ma[mv][n][k], mb[mv][n][k]), (what, mv, n, k)
+    assert a.actor_optimizer.param_groups[0]["lr"] == b.actor_optimizer.param_groups[0]["lr"], what
+    assert a.total_it == b.total_it and a._adam_t == b._adam_t, what
+
+
+def arenas(tr):
+    """The four flat arenas as one host array (parameters, targets, both Adam moments)."""
+    return torch.cat([tr._params_arena, tr._target_arena, tr._m_arena, tr._v_arena]).cpu().numpy()
