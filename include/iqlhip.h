@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 320          /* 0.3.2 */
+#define IQLHIP_VERSION 330          /* 0.3.3 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -304,6 +304,32 @@ int iqlhip_read_step_stats(iqlhip_ctx* ctx, float out[IQLHIP_N_STATS], void* str
 /* out[n_steps][IQLHIP_N_STATS]: the statistics of the first n_steps steps of the last iqlhip_train_steps call (like
  * iqlhip_read_loss_ring); synchronises `stream`. */
 int iqlhip_read_stats_ring(iqlhip_ctx* ctx, float* out, int32_t n_steps, void* stream);
+
+/* ---- gradient-norm clipping per optimizer group (opt-in) ---------------------------------------
+ * torch.nn.utils.clip_grad_norm_ (L2, error_if_nonfinite = False) between a step's backward and its Adam update,
+ * independently for the three optimizer groups, in this order: V | Q1 + Q2 | pi (with log_std).  Per group, in fp32:
+ *    total_norm = sqrt(sum of squares of the group's gradient as Adam would receive it)    (statistics 13..15)
+ *    coef       = min(max_norm / (total_norm + 1e-6f), 1.0f)
+ *    grad      *= coef            (one multiply per element, also when coef is 1)
+ * max_norm[g] <= 0 or +inf: no limit for that group (its coefficient is exactly 1); NaN: IQLHIP_EINVAL.  All three
+ * without a limit: the feature is off — nothing is allocated, launched or captured and every result is bit-identical
+ * to a library without it.  On, every entry point that runs a step clips (iqlhip_step and its forms,
+ * iqlhip_online_step, iqlhip_train_steps — which keeps chunk graphs of their own per on/off setting — and the group
+ * calls, where it is a per-member setting).  The limits live in device memory: changing them needs no re-capture; the
+ * new limits are queued (an asynchronous copy from pinned memory) on the stream of the context's last step call, so
+ * steps already queued there keep the old limits and every later one reads the new ones; a caller that moves to
+ * another stream orders the two itself, as for the arenas.
+ * The sum of squares runs in a fixed order (deterministic; the block partials are shared with the statistics).
+ * iqlhip_forward_backward keeps returning the UNCLIPPED gradient, and iqlhip_apply_update applies the caller's
+ * gradient as given.  Not supported (IQLHIP_EUNSUPPORTED from the step entry points, before anything is launched or
+ * any counter moves): a context with a data-parallel exchange selected (the norm would have to be taken after the
+ * exchange), and steps that take the large-batch bf16 path (more than 512 rows in bf16). */
+int iqlhip_set_grad_clip(iqlhip_ctx* ctx, const float max_norm[3]);
+/* The limits as the context holds them (+inf = no limit). */
+int iqlhip_get_grad_clip(const iqlhip_ctx* ctx, float max_norm[3]);
+/* {norm_v, norm_q, norm_pi, coef_v, coef_q, coef_pi} of the last step (the norms before clipping); synchronises
+ * `stream`.  IQLHIP_EINVAL when clipping is off. */
+int iqlhip_read_grad_clip(iqlhip_ctx* ctx, float out[6], void* stream);
 
 /* ---- replay buffer storage (packed rows [s | a | s' | r | d | pad]) ------ */
 /* Row stride in floats for given dims (multiple of 4 floats = 16 B). */

@@ -115,9 +115,10 @@ struct GraphKey {
   int parity = 0;     // P2P exchange: which flat buffer step 0 of the chunk writes
   int head = 0;       // the chunk a call starts with: its graph begins with the call's set-up kernel (arguments set per replay)
   int stats = 0;      // captured with the statistics launches (iqlhip_set_step_stats): never replayed under the other setting
+  int clip = 0;       // captured with the clip launches and the CLIP update kernel (iqlhip_set_grad_clip): likewise
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
-           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats;
+           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip;
   }
 };
 
@@ -244,6 +245,16 @@ struct iqlhip_ctx {
   float* stats_last = nullptr;        // device [IQLHIP_N_STATS]: the last step's
   float* stats_ring = nullptr;        // device [k_max][IQLHIP_N_STATS]: per step of the last iqlhip_train_steps call
   float* stats_host = nullptr;        // pinned landing pad of the two read calls [k_max][IQLHIP_N_STATS]
+  // gradient-norm clipping (iqlhip_set_grad_clip; allocated by the first call that enables it; shares stats_part)
+  bool clip_on = false;
+  float clip_max[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};   // V, Q, pi: +inf = no limit
+  float* clip_dev = nullptr;          // device [12]: limits at 0..2, the last step's coefficients at 4..6, its norms at 8..10
+  float* clip_host = nullptr;         // pinned [24]: staging of an upload of clip_dev at 0..11, landing pad of iqlhip_read_grad_clip at 12..
+  hipEvent_t clip_up = nullptr;       // the last upload of the limits has read clip_host
+  bool clip_up_pending = false;
+  // the stream of the context's last step call (note_stream): iqlhip_set_grad_clip queues the new limits there
+  hipStream_t last_stream = nullptr;
+  bool has_last_stream = false;
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;         // 4 per recorded step
@@ -462,7 +473,7 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   void* bufs[] = {c->sc.h0, c->sc.h1, c->sc.heads, c->sc.slab_a, c->sc.slab_b, c->sc.loss_parts, c->sc.losses,
                   c->flat_tmp, c->sched_call, c->sched_cur, c->hdr, c->stamps, c->xb, c->xb2, c->xb_act,
                   c->heads_act, c->drop_bits, c->act_drop_bits, c->xstatus, c->xflat, c->wsh, c->tsh, c->pi_t, c->dh1g, c->slab_x, c->wimg,
-                  c->stats_part, c->stats_last, c->stats_ring};
+                  c->stats_part, c->stats_last, c->stats_ring, c->clip_dev};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (int i = 0; i < 4; ++i) {
     if (c->sched_pin[i]) (void)hipHostFree(c->sched_pin[i]);
@@ -479,6 +490,8 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   if (c->done_pin) (void)hipHostFree(c->done_pin);
   if (c->on_act_pin) (void)hipHostFree(c->on_act_pin);
   if (c->stats_host) (void)hipHostFree(c->stats_host);
+  if (c->clip_host) (void)hipHostFree(c->clip_host);
+  if (c->clip_up) (void)hipEventDestroy(c->clip_up);
   delete c;
   return IQLHIP_OK;
 }
@@ -969,8 +982,16 @@ static UpdWords upd_words(const iqlhip_ctx* c, const UpdParams& u) {
 static auto upd_kernel(bool from_table, bool peer, bool lb) {
   return with_bools([](auto NLB, auto NT, auto NP) { return &iql_update_kernel<!NT.value, !NP.value, !NLB.value>; }, !lb, !from_table, !peer);
 }
-static void launch_upd(const iqlhip_ctx* c, UpdParams u, hipStream_t st) {
+// clip: the step's clip coefficients (iqlhip_set_grad_clip) — the CLIP kernel; nullptr: the kernels without.
+static void launch_upd(const iqlhip_ctx* c, UpdParams u, hipStream_t st, const float* clip = nullptr) {
   const UpdWords w = upd_words(c, u);
+  if (clip) {       // (never with an exchange or on the large-batch path: clip_check)
+    if (u.sched) hipLaunchKernelGGL(iql_update_clip_kernel<true>, dim3(upd_blocks(c)), dim3(256), 0, st, u.params, u.m, u.v, u.slab_a,
+                                    w.s0, w.s1, w.s2, w.s3, w.end, w.flags, clip, u);
+    else hipLaunchKernelGGL(iql_update_clip_kernel<false>, dim3(upd_blocks(c)), dim3(256), 0, st, u.params, u.m, u.v, u.slab_a,
+                            w.s0, w.s1, w.s2, w.s3, w.end, w.flags, clip, u);
+    return;
+  }
   // (u.slab_x: a large-batch bf16 step — the LB instantiations: gradient from the chunk-group slabs unless an exchange
   //  delivered it flat; the operand images of W0 / W1 written next to the bf16 shadows)
   hipLaunchKernelGGL(upd_kernel(/*from_table=*/u.sched != nullptr, /*peer=*/u.n_peer > 0, /*lb=*/u.slab_x != nullptr), dim3(upd_blocks(c)),
@@ -997,14 +1018,20 @@ static void launch_flatten(const iqlhip_ctx* c, const UpdParams& u, float* out, 
 // ---------------------------------------------------------------------------
 // Per-step statistics (include/iqlhip.h "per-step training statistics"; kernels: iqlhip_kernels.h).
 static int stats_parts(const iqlhip_ctx* c) { return upd_blocks(c) / 8 * 2; }      // 1024-element windows of the longest segment
+// The gradient block partials: one buffer for the statistics and the clip kernel (whoever is enabled first).
+static int ensure_gparts(iqlhip_ctx* c) {
+  if (c->stats_part) return IQLHIP_OK;
+  c->stats_n_part = stats_parts(c);
+  HIPCHK(hipMalloc((void**)&c->stats_part, (size_t)4 * c->stats_n_part * sizeof(float)));
+  HIPCHK(hipMemset(c->stats_part, 0, (size_t)4 * c->stats_n_part * sizeof(float)));
+  return IQLHIP_OK;
+}
 extern "C" int iqlhip_set_step_stats(iqlhip_ctx* c, int enabled) {
   if (!c) return fail(IQLHIP_EINVAL, "NULL ctx");
   if (enabled && !c->stats_ring) {
     DevGuard guard(c->device);
-    c->stats_n_part = stats_parts(c);
     const size_t ring = (size_t)c->k_max * IQLHIP_N_STATS * sizeof(float);
-    HIPCHK(hipMalloc((void**)&c->stats_part, (size_t)4 * c->stats_n_part * sizeof(float)));
-    HIPCHK(hipMemset(c->stats_part, 0, (size_t)4 * c->stats_n_part * sizeof(float)));
+    if (int rc = ensure_gparts(c)) return rc;
     HIPCHK(hipMalloc((void**)&c->stats_last, IQLHIP_N_STATS * sizeof(float)));
     HIPCHK(hipMemset(c->stats_last, 0, IQLHIP_N_STATS * sizeof(float)));
     HIPCHK(hipHostMalloc((void**)&c->stats_host, ring, hipHostMallocDefault));
@@ -1014,8 +1041,18 @@ extern "C" int iqlhip_set_step_stats(iqlhip_ctx* c, int enabled) {
   c->stats_on = enabled != 0;
   return IQLHIP_OK;
 }
+// Every step entry point, once its checks have passed: the stream its work is queued on.
+static void note_stream(iqlhip_ctx* c, void* stream) { c->last_stream = (hipStream_t)stream; c->has_last_stream = true; }
 // The two cases statistics are not built for, checked by every step entry point before it launches anything.
+// (... and the same two for gradient clipping: there the norm would have to be taken after the exchange, and the
+//  large-batch path keeps its gradient in other slabs)
 static int stats_check(const iqlhip_ctx* c, int rows) {
+  if (c->clip_on) {
+    if (c->xch_mode != IQLHIP_XCH_NONE)
+      return fail(IQLHIP_EUNSUPPORTED, "gradient clipping is not supported with a data-parallel exchange (the norm would have to be taken after the exchange)");
+    if (use_lb(c, rows))
+      return fail(IQLHIP_EUNSUPPORTED, "gradient clipping is not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+  }
   if (!c->stats_on) return IQLHIP_OK;
   if (c->xch_mode != IQLHIP_XCH_NONE)
     return fail(IQLHIP_EUNSUPPORTED, "step statistics are not supported with a data-parallel exchange (the local gradient slabs are not what Adam receives)");
@@ -1035,9 +1072,19 @@ static StatsArgs make_stats(const iqlhip_ctx* c, const StepParams& p, float* rin
   a.ring = ring; a.ring_slot = ring_slot; a.ring_cap = ring_cap; a.ring_hdr = ring_hdr;
   return a;
 }
-static void launch_stats(const UpdParams& u, const StatsArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(iql_stats_gradsq_kernel, dim3(4 * a.n_part), dim3(256), 0, st, u, a.gparts, a.n_part);
-  hipLaunchKernelGGL(iql_step_stats_kernel, dim3(1), dim3(256), 0, st, a);
+static ClipArgs make_clip(const iqlhip_ctx* c) {
+  ClipArgs a;
+  a.gparts = c->stats_part; a.n_part = c->stats_n_part;
+  a.limits = c->clip_dev; a.coef = c->clip_dev + 4; a.norm = c->clip_dev + 8;
+  return a;
+}
+// The launches between a step's backward and its update: the block partials once for both consumers, then the
+// statistics kernel (sa) and the clip coefficients (clip).
+static void launch_stats(const iqlhip_ctx* c, const UpdParams& u, const StatsArgs* sa, bool clip, hipStream_t st) {
+  if (!sa && !clip) return;
+  hipLaunchKernelGGL(iql_stats_gradsq_kernel, dim3(4 * c->stats_n_part), dim3(256), 0, st, u, c->stats_part, c->stats_n_part);
+  if (sa) hipLaunchKernelGGL(iql_step_stats_kernel, dim3(1), dim3(256), 0, st, *sa);
+  if (clip) hipLaunchKernelGGL(iql_clip_coef_kernel, dim3(1), dim3(256), 0, st, make_clip(c));
 }
 extern "C" int iqlhip_read_step_stats(iqlhip_ctx* c, float out[IQLHIP_N_STATS], void* stream) {
   if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
@@ -1057,6 +1104,63 @@ extern "C" int iqlhip_read_stats_ring(iqlhip_ctx* c, float* out, int32_t n_steps
   HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_ring, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   memcpy(out, c->stats_host, bytes);
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Gradient-norm clipping (include/iqlhip.h "gradient-norm clipping"; kernels: iqlhip_kernels.h).
+extern "C" int iqlhip_set_grad_clip(iqlhip_ctx* c, const float max_norm[3]) {
+  if (!c || !max_norm) return fail(IQLHIP_EINVAL, "NULL argument");
+  float lim[3];
+  bool on = false;
+  for (int g = 0; g < 3; ++g) {
+    if (max_norm[g] != max_norm[g]) return fail(IQLHIP_EINVAL, "max_norm[%d] is NaN", g);
+    lim[g] = (max_norm[g] > 0.f) ? max_norm[g] : __builtin_inff();      // (<= 0 and +inf: no limit)
+    on = on || lim[g] < __builtin_inff();
+  }
+  if (on || c->clip_dev) {
+    DevGuard guard(c->device);
+    const bool first = !c->clip_dev;
+    if (first) {
+      if (int rc = ensure_gparts(c)) return rc;
+      HIPCHK(hipHostMalloc((void**)&c->clip_host, 24 * sizeof(float), hipHostMallocDefault));
+      HIPCHK(hipMalloc((void**)&c->clip_dev, 12 * sizeof(float)));
+      HIPCHK(hipEventCreateWithFlags(&c->clip_up, hipEventDisableTiming));
+    }
+    // The limits (and, the first time, zeros for the rest of clip_dev) travel from pinned memory on the stream of the
+    // context's last step call: behind the steps queued there, in front of every later one, without stalling the
+    // device.  (A caller that moves to another stream orders the two itself, as for the arenas.)  No step call yet:
+    // nothing of this context is queued, a blocking copy.
+    if (c->clip_up_pending) HIPCHK(hipEventSynchronize(c->clip_up));      // (the staging words are free again)
+    c->clip_up_pending = false;
+    memset(c->clip_host, 0, 12 * sizeof(float));
+    for (int g = 0; g < 3; ++g) c->clip_host[g] = lim[g];
+    const size_t bytes = (first ? 12 : 3) * sizeof(float);
+    if (c->has_last_stream) {
+      HIPCHK(hipMemcpyAsync(c->clip_dev, c->clip_host, bytes, hipMemcpyHostToDevice, c->last_stream));
+      HIPCHK(hipEventRecord(c->clip_up, c->last_stream));
+      c->clip_up_pending = true;
+    } else {
+      HIPCHK(hipMemcpy(c->clip_dev, c->clip_host, bytes, hipMemcpyHostToDevice));
+    }
+  }
+  for (int g = 0; g < 3; ++g) c->clip_max[g] = lim[g];
+  c->clip_on = on;
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_get_grad_clip(const iqlhip_ctx* c, float max_norm[3]) {
+  if (!c || !max_norm) return fail(IQLHIP_EINVAL, "NULL argument");
+  for (int g = 0; g < 3; ++g) max_norm[g] = c->clip_max[g];
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_read_grad_clip(iqlhip_ctx* c, float out[6], void* stream) {
+  if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!c->clip_on) return fail(IQLHIP_EINVAL, "gradient clipping is off (iqlhip_set_grad_clip)");
+  DevGuard guard(c->device);
+  float* land = c->clip_host + 12;
+  HIPCHK(hipMemcpyAsync(land, c->clip_dev, 12 * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int g = 0; g < 3; ++g) { out[g] = land[8 + g]; out[3 + g] = land[4 + g]; }
   return IQLHIP_OK;
 }
 
@@ -1301,7 +1405,8 @@ static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int 
   if (ev) HIPCHK(hipEventRecord(ev[1], st));
   launch_bwd(c, p, st);
   if (ev) HIPCHK(hipEventRecord(ev[2], st));
-  if (sa) launch_stats(u, *sa, st);
+  // (clipping is refused with an exchange before any launch: below, mode is IQLHIP_XCH_NONE whenever clip_on)
+  launch_stats(c, u, sa, c->clip_on, st);
   if (mode == IQLHIP_XCH_RCCL) {
     launch_flatten(c, u, c->xflat, false, st);
     NCCLCHK(g_rccl.AllReduce(c->xflat, c->xflat, (size_t)c->L.n_params + 4, RCCL_FLOAT32, RCCL_SUM, c->nccl_comm, st));
@@ -1319,7 +1424,7 @@ static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int 
     u.peer_direct = direct ? 1 : 0;
     if (direct) for (int n = 0; n < 4; ++n) u.slab_b_off[n] = c->xslab_b_off[n];
   }
-  launch_upd(c, u, st);
+  launch_upd(c, u, st, c->clip_on ? c->clip_dev + 4 : nullptr);
   if (ev) HIPCHK(hipEventRecord(ev[3], st));
   return IQLHIP_OK;
 }
@@ -1425,6 +1530,7 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
   int rc = check_batch(c, b);
   if (rc) return rc;
   if ((rc = stats_check(c, b->rows))) return rc;
+  note_stream(c, stream);
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
   c->cont.valid = false;                 // (the staging buffers / keep-bits a following train_steps call might continue from)
@@ -1497,6 +1603,7 @@ extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, in
     if (rc_i) return rc_i;
     if ((rc_i = stats_check(c, n))) return rc_i;
   }
+  note_stream(c, stream);
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
   c->cont.valid = false;
@@ -1810,6 +1917,7 @@ static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld,
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
   key.stats = c->stats_on ? 1 : 0;
+  key.clip = c->clip_on ? 1 : 0;
   return key;
 }
 
@@ -1873,6 +1981,7 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
   if (rc) return rc;
   if ((rc = stats_check(c, B))) return rc;
   if ((rc = inject_check(c))) return rc;
+  note_stream(c, stream);
   DevGuard guard(c->device);
   HIPCHK(hipDeviceSynchronize());       // a one-off set-up call: ordered after everything queued on any stream
   c->cont.valid = false;
@@ -1974,6 +2083,7 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
   if (size < 1) return fail(IQLHIP_EINVAL, "empty buffer");
   if ((rc = stats_check(c, B))) return rc;
   if ((rc = inject_check(c))) return rc;
+  note_stream(c, stream);
   double tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (g_trace) tr_t[0] = now_us();
   DevGuard guard(c->device);
@@ -2534,6 +2644,11 @@ struct iqlhip_group {
   // without the flag) and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS]
   Staging train;
   Section<GroupRec> recs; Section<GroupDropRec> drops; Section<GroupStatsRec> srecs; Section<iqlhip_step_scalars> tabs;
+  // gradient clipping of the members that enabled it (iqlhip_set_grad_clip): their records, and the records the block
+  // partial launch runs under when some member clips (enabled = statistics or clipping); clip_ones: three floats of
+  // 1.0f, the coefficients a member without clipping reads (allocated by the first call with a clipping member)
+  Section<GroupClipRec> crecs; Section<GroupStatsRec> gqrecs;
+  float* clip_ones = nullptr;
   // per-step statistics of the members that enabled them (iqlhip_set_step_stats): [k][IQLHIP_GROUP_MAX_STEPS][IQLHIP_N_STATS],
   // allocated by the first call with such a member; stats_mask: who had them on in the last call
   float* stats_ring_dev = nullptr;
@@ -2551,6 +2666,7 @@ struct iqlhip_group {
   Section<GroupRec> on_recs; Section<StepParams> on_aps; Section<GroupOnlineRec> on_gathers; Section<GroupActRec> on_fins;
   Section<GroupDropRec> on_drops; Section<ActDropRec> on_adrops; Section<iqlhip_step_scalars> on_tabs;
   Section<GroupStatsRec> on_srecs;
+  Section<GroupClipRec> on_crecs; Section<GroupStatsRec> on_gqrecs;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
   // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in act_host (the
@@ -2609,6 +2725,7 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   if (g->ring_pin) (void)hipHostFree(g->ring_pin);
   if (g->stats_ring_dev) (void)hipFree(g->stats_ring_dev);
   if (g->stats_ring_pin) (void)hipHostFree(g->stats_ring_pin);
+  if (g->clip_ones) (void)hipFree(g->clip_ones);
   if (g->up_done) (void)hipEventDestroy(g->up_done);
   if (g->done_pin) (void)hipHostFree(g->done_pin);
   if (g->act_up) (void)hipEventDestroy(g->act_up);
@@ -2632,6 +2749,8 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->recs = g->train.add<GroupRec>(k);
     g->drops = g->train.add<GroupDropRec>(n_drop);
     g->srecs = g->train.add<GroupStatsRec>(k);
+    g->crecs = g->train.add<GroupClipRec>(k);      // (in front of the tables: group_upload copies up to their used rows)
+    g->gqrecs = g->train.add<GroupStatsRec>(k);
     g->tabs = g->train.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
     g->on_recs = g->on.add<GroupRec>(k);
     g->on_aps = g->on.add<StepParams>(k);
@@ -2641,6 +2760,8 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->on_adrops = g->on.add<ActDropRec>(n_drop);
     g->on_tabs = g->on.add<iqlhip_step_scalars>(k);
     g->on_srecs = g->on.add<GroupStatsRec>(k);
+    g->on_crecs = g->on.add<GroupClipRec>(k);
+    g->on_gqrecs = g->on.add<GroupStatsRec>(k);
     g->act_packs = g->act.add<GroupPackRec>(k);
     g->act_ps = g->act.add<StepParams>(k);
     g->act_fins = g->act.add<GroupActRowsRec>(k);
@@ -2852,19 +2973,57 @@ static int group_stats_records(iqlhip_group* g, GroupStatsRec* sr, const GroupRe
   return IQLHIP_OK;
 }
 
-// srecs: the device copy of the call's statistics records, or nullptr when no member has statistics on.
+// Gradient clipping in a group: one record per member (indexed like the GroupRecs) and the block-partial launch's
+// records (enabled = the member has statistics or clipping on).  A member with clipping off reads the group's 1.0f
+// coefficients.  Returns whether any member clips (none: the launches of a group without the feature).
+static int group_clip_records(iqlhip_group* g, GroupClipRec* cr, GroupStatsRec* gq, bool* any) {
+  *any = false;
+  for (int i = 0; i < g->k; ++i) *any = *any || g->m[i]->clip_on;
+  if (!*any) return IQLHIP_OK;
+  if (!g->clip_ones) {
+    const float ones[4] = {1.f, 1.f, 1.f, 1.f};
+    HIPCHK(hipMalloc((void**)&g->clip_ones, sizeof ones));
+    HIPCHK(hipMemcpy(g->clip_ones, ones, sizeof ones, hipMemcpyHostToDevice));
+  }
+  for (int i = 0; i < g->k; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    memset(&cr[i], 0, sizeof cr[i]);
+    memset(&gq[i], 0, sizeof gq[i]);
+    cr[i].coef_rd = g->clip_ones;
+    if (c->clip_on) {
+      cr[i].a = make_clip(c);
+      cr[i].coef_rd = cr[i].a.coef;
+      cr[i].enabled = 1;
+    }
+    if (c->clip_on || c->stats_on) {
+      gq[i].a.gparts = c->stats_part; gq[i].a.n_part = c->stats_n_part;
+      gq[i].enabled = 1;
+    }
+  }
+  return IQLHIP_OK;
+}
+
+// The device copies of a call's per-member statistics / clip records; nullptr: no member has the feature on.
+struct GroupAux { const GroupStatsRec* srecs = nullptr; const GroupClipRec* crecs = nullptr; const GroupStatsRec* gqrecs = nullptr; };
 static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st,
-                              const GroupStatsRec* srecs) {
+                              const GroupAux& aux) {
+  const GroupStatsRec* srecs = aux.srecs;
   const iqlhip_ctx* c = g->m[0];
   const int K = g->k;
   const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K;
   hipLaunchKernelGGL(fwd_group_kernel(bf, dma, /*multi=*/q.fwd_l2 > 0), dim3(q.fwd_nb, K), dim3(256), fwd_lds(c, q.fwd_work), st, recs);
   hipLaunchKernelGGL(bwd_group_kernel(bf, q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs);
-  if (srecs) {      // (between the backward and the update, as in a solo step: enqueue_step)
-    hipLaunchKernelGGL(iql_stats_gradsq_group_kernel, dim3(4 * stats_parts(c), K), dim3(256), 0, st, recs, srecs, s);
-    hipLaunchKernelGGL(iql_step_stats_group_kernel, dim3(1, K), dim3(256), 0, st, recs, srecs, s);
+  // (between the backward and the update, as in a solo step: enqueue_step; the block partials once for both consumers)
+  if (srecs || aux.crecs)
+    hipLaunchKernelGGL(iql_stats_gradsq_group_kernel, dim3(4 * stats_parts(c), K), dim3(256), 0, st, recs,
+                       aux.crecs ? aux.gqrecs : srecs, s);
+  if (srecs) hipLaunchKernelGGL(iql_step_stats_group_kernel, dim3(1, K), dim3(256), 0, st, recs, srecs, s);
+  if (aux.crecs) {
+    hipLaunchKernelGGL(iql_clip_coef_group_kernel, dim3(1, K), dim3(256), 0, st, aux.crecs);
+    hipLaunchKernelGGL(iql_update_clip_group_kernel, dim3(q.upd_nb, K), dim3(256), 0, st, recs, aux.crecs, s);
+  } else {
+    hipLaunchKernelGGL(iql_update_group_kernel, dim3(q.upd_nb, K), dim3(256), 0, st, recs, s);
   }
-  hipLaunchKernelGGL(iql_update_group_kernel, dim3(q.upd_nb, K), dim3(256), 0, st, recs, s);
 }
 
 // The policy forward of n_req requesting members (both act paths): record j of `ps` on grid.y = j, `lds` from fwd_lds.
@@ -2899,6 +3058,7 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
     if (!mixed && batches[i].rows != rows.v[0]) return fail(IQLHIP_EINVAL, "member %d: batch of %d rows, member 0: %d (one batch size per group)", i, batches[i].rows, rows.v[0]);
     if (batches[i].idx_dev && (rc = check_indexed(g->m[i], &batches[i]))) return rc;
   }
+  for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
   rc = group_staging_free(g);
@@ -2918,10 +3078,16 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
   bool stats = false;
   rc = group_stats_records(g, g->train.host(g->srecs), g->train.host(g->recs), &stats);
   if (rc) return rc;
+  bool clip = false;
+  rc = group_clip_records(g, g->train.host(g->crecs), g->train.host(g->gqrecs), &clip);
+  if (rc) return rc;
+  GroupAux aux;
+  if (stats) aux.srecs = g->train.device(g->srecs);
+  if (clip) { aux.crecs = g->train.device(g->crecs); aux.gqrecs = g->train.device(g->gqrecs); }
   rc = group_upload(g, 1, st);
   if (rc) return rc;
   group_launch_dropmask(g, g->train.device(g->drops), n_draw, q.max_rows, st);
-  group_launch_step(g, g->train.device(g->recs), q, 0, st, stats ? g->train.device(g->srecs) : nullptr);
+  group_launch_step(g, g->train.device(g->recs), q, 0, st, aux);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
@@ -2949,6 +3115,7 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
     if (size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty buffer", i);
     if (!tables[i]) return fail(IQLHIP_EINVAL, "member %d: NULL scalar table", i);
   }
+  for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
   rc = group_staging_free(g);
@@ -2977,6 +3144,12 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
   bool stats = false;
   rc = group_stats_records(g, g->train.host(g->srecs), g->train.host(g->recs), &stats);
   if (rc) return rc;
+  bool clip = false;
+  rc = group_clip_records(g, g->train.host(g->crecs), g->train.host(g->gqrecs), &clip);
+  if (rc) return rc;
+  GroupAux aux;
+  if (stats) aux.srecs = g->train.device(g->srecs);
+  if (clip) { aux.crecs = g->train.device(g->crecs); aux.gqrecs = g->train.device(g->gqrecs); }
   rc = group_upload(g, n, st);
   if (rc) return rc;
   const iqlhip_ctx* c0 = g->m[0];
@@ -2990,7 +3163,7 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
       hipLaunchKernelGGL(iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0, st, recs, g->train.device(g->drops), s);
     else
       hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, recs, s);
-    group_launch_step(g, recs, q, s, st, stats ? g->train.device(g->srecs) : nullptr);
+    group_launch_step(g, recs, q, s, st, aux);
   }
   if (g->flags & IQLHIP_GROUP_DROPOUT)      // (as iqlhip_train_steps: the position of every context with a rate above 0)
     for (int i = 0; i < g->k; ++i) if (g->m[i]->drop_p > 0.f) g->m[i]->drop_step += (unsigned long long)n;
@@ -3072,6 +3245,7 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
     rc = check_host_indices(idx_host + idx0[i], n[i], capacity[i]);
     if (rc) return rc;
   }
+  for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
   const iqlhip_ctx* c0 = g->m[0];
@@ -3120,6 +3294,12 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
   bool stats = false;
   rc = group_stats_records(g, on.host(g->on_srecs), recs, &stats);
   if (rc) return rc;
+  bool clip = false;
+  rc = group_clip_records(g, on.host(g->on_crecs), on.host(g->on_gqrecs), &clip);
+  if (rc) return rc;
+  GroupAux aux;
+  if (stats) aux.srecs = on.device(g->on_srecs);
+  if (clip) { aux.crecs = on.device(g->on_crecs); aux.gqrecs = on.device(g->on_gqrecs); }
   // (a synchronous call: the previous one's upload has been read long ago)
   HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((q.max_rows * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
@@ -3130,7 +3310,7 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
     hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
   group_launch_dropmask(g, on.device(g->on_drops), n_draw, q.max_rows, st);
-  group_launch_step(g, on.device(g->on_recs), q, 0, st, stats ? on.device(g->on_srecs) : nullptr);
+  group_launch_step(g, on.device(g->on_recs), q, 0, st, aux);
   const unsigned long long done_val = ++g->done_seq;
   if (n_req > 0) {
     // (bf16: the update has just rewritten the shadows from the new masters — the conversion refresh_shadows makes)

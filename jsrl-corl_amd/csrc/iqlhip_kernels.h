@@ -1014,6 +1014,21 @@ __global__ __launch_bounds__(256) void iql_update_kernel(float* q_p, float* q_m,
                                                          unsigned q_s1, unsigned q_s2, unsigned q_s3, unsigned q_end,
                                                          unsigned q_flags, UpdParams u) {
   constexpr int step = 0;         // (row of the scalar table / loss ring: group launches pass theirs)
+  constexpr bool CLIP = false;
+  const float* const q_clip = nullptr;
+#include "iqlhip_upd_body.inc"
+}
+// CLIP = true (iqlhip_set_grad_clip): the same body with the gradient additionally multiplied by the
+// optimizer group's clip coefficient q_clip[grp], which iql_clip_coef_kernel wrote in the launch before.  A kernel of
+// its own rather than a run-time argument of iql_update_kernel: the instantiations above keep their argument block and
+// their code.  q_clip follows the 14 preloaded dwords (it shares their 64-byte line of the argument block).  Only the
+// plain gradient source exists in this form: clipping is refused with an exchange and on the large-batch path.
+template <bool FROM_TABLE>
+__global__ __launch_bounds__(256) void iql_update_clip_kernel(float* q_p, float* q_m, float* q_v, const float* q_slab_a, unsigned q_s0,
+                                                              unsigned q_s1, unsigned q_s2, unsigned q_s3, unsigned q_end,
+                                                              unsigned q_flags, const float* q_clip, UpdParams u) {
+  constexpr int step = 0;
+  constexpr bool PEER = false, LB = false, CLIP = true;
 #include "iqlhip_upd_body.inc"
 }
 
@@ -1071,6 +1086,8 @@ __global__ __launch_bounds__(256) void iql_update_group_kernel(const GroupRec* _
   const unsigned q_s0 = r.u_s0, q_s1 = r.u_s1, q_s2 = r.u_s2, q_s3 = r.u_s3, q_end = r.u_end, q_flags = r.u_flags;
   const UpdParams& u = r.u;
   step = min(max(step, 0), r.n_steps - 1);
+  constexpr bool CLIP = false;
+  const float* const q_clip = nullptr;
 #include "iqlhip_upd_body.inc"
 }
 
@@ -1276,6 +1293,69 @@ __global__ __launch_bounds__(256) void iql_step_stats_group_kernel(const GroupRe
   const GroupStatsRec& s = srecs[blockIdx.y];
   if (!s.enabled) return;
   step_stats_block(s.a, min(max(step, 0), recs[blockIdx.y].n_steps - 1), red, outs);
+}
+
+// ---------------------------------------------------------------------------
+// Gradient-norm clipping per optimizer group (iqlhip_set_grad_clip, opt-in): torch's clip_grad_norm_
+// (L2, error_if_nonfinite = False) for the groups V | Q1 + Q2 | pi (+ log_std).  Launches of a step:
+//   backward -> iql_stats_gradsq_kernel (the block partials, shared with the statistics) -> [iql_step_stats_kernel]
+//            -> iql_clip_coef_kernel -> iql_update_clip_kernel
+// iql_clip_coef_kernel: ONE block; wave g adds group g's partials in double in step_stats_block's order (lane l takes
+// partials l, l + 64, ..., then 6 xor-shuffles), rounds the square root to fp32 — the value statistics 13..15 hold —
+// and lane 0 writes
+//   coef = min(max_norm / (norm + 1e-6f), 1.0f)       (fp32, one addition, one division; NaN stays NaN, as torch.clamp)
+// or exactly 1.0f for a group without a limit (+inf in `limits`).  The limits are device memory of the context: a graph
+// replay reads the current ones.  No atomics: the result depends on the inputs alone.
+struct ClipArgs {
+  const float* gparts;                // [4 nets][n_part] (iql_stats_gradsq_kernel)
+  int n_part;
+  const float* limits;                // [3] V, Q, pi: max_norm, +inf = no limit
+  float* coef;                        // [3] written here, read by the update kernel of the same step
+  float* norm;                        // [3] the norms before clipping
+};
+__device__ __forceinline__ void clip_coef_block(const ClipArgs& a) {
+  const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (wave < 3) {
+    const int first = (wave == 0) ? 0 : ((wave == 1) ? a.n_part : 3 * a.n_part);
+    const int cnt = (wave == 1) ? 2 * a.n_part : a.n_part;
+    double acc = 0.0;
+    for (int i = lane; i < cnt; i += 64) acc += (double)a.gparts[first + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) {
+      const float nrm = (float)sqrt(acc);
+      const float mx = a.limits[wave];
+      float cf = 1.f;
+      if (mx < __builtin_inff()) {
+        const float q = __fdiv_rn(mx, __fadd_rn(nrm, 1e-6f));
+        cf = (q > 1.f) ? 1.f : q;
+      }
+      a.coef[wave] = cf;
+      a.norm[wave] = nrm;
+    }
+  }
+}
+__global__ __launch_bounds__(256) void iql_clip_coef_kernel(ClipArgs a) { clip_coef_block(a); }
+
+// Group forms (grid.y = member).  A member with clipping off has enabled = 0: its clip block exits at once, and
+// coef_rd points at three floats of exactly 1.0f (the group's), so that the group update kernel — which picks the
+// member at run time and therefore always multiplies — computes x * 1.0f = x, the bits of the CLIP = false form.
+struct GroupClipRec { ClipArgs a; const float* coef_rd; int enabled; };
+__global__ __launch_bounds__(256) void iql_clip_coef_group_kernel(const GroupClipRec* __restrict__ crecs) {
+  const GroupClipRec& c = crecs[blockIdx.y];
+  if (!c.enabled) return;
+  clip_coef_block(c.a);
+}
+__global__ __launch_bounds__(256) void iql_update_clip_group_kernel(const GroupRec* __restrict__ recs,
+                                                                    const GroupClipRec* __restrict__ crecs, int step) {
+  constexpr bool FROM_TABLE = true, PEER = false, LB = false, CLIP = true;
+  const GroupRec& r = recs[blockIdx.y];
+  float* q_p = r.u_p; float* q_m = r.u_m; float* q_v = r.u_v; const float* q_slab_a = r.u_slab_a;
+  const unsigned q_s0 = r.u_s0, q_s1 = r.u_s1, q_s2 = r.u_s2, q_s3 = r.u_s3, q_end = r.u_end, q_flags = r.u_flags;
+  const float* const q_clip = crecs[blockIdx.y].coef_rd;
+  const UpdParams& u = r.u;
+  step = min(max(step, 0), r.n_steps - 1);
+#include "iqlhip_upd_body.inc"
 }
 
 // Policy inference (GaussianPolicy.act / DeterministicPolicy.act, algorithms/finetune/iql.py:371-379, 404-413):

@@ -1,8 +1,9 @@
 // Body of the update — included by iql_update_kernel and iql_update_group_kernel (iqlhip_kernels.h):
 // ONE body for the single-agent kernel and its trainer-group form, so the arithmetic exists once.  blockIdx.x / gridDim.x
 // are the block's index and grid size of ONE agent's launch in both (a group kernel's agent is blockIdx.y).
-// In scope: template flags FROM_TABLE, PEER, LB, the leading arguments q_*, `u` (UpdParams) and `step` (row of the
+// In scope: template flags FROM_TABLE, PEER, LB, CLIP, the leading arguments q_*, `u` (UpdParams) and `step` (row of the
 // scalar table and of the loss ring: 0 for iql_update_kernel, the bounded step index of a group launch).
+// CLIP (iqlhip_set_grad_clip): q_clip[3] holds the optimizer groups' clip coefficients of this step.
   // XCD-affine element map: block (x = blockIdx & 7, q = blockIdx >> 3) — XCD x under the round-robin workgroup
   // dispatch — owns net x & 3, and of that net's arena segment the 64-float stripes of parity x >> 2: window q of 2 048
   // floats, 16 stripes of 16 threads.  The backward's blocks of net n run on XCDs n and n + 4 and a dW1 tile of column
@@ -25,6 +26,8 @@
     const bool early_g = !PEER && !LB && (q_flags & UPD_EARLY_G) != 0u && (e - seg_b) < 65536;
     f32x4 gr = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (early_g) gr = *(const f32x4*)(q_slab_a + e);
+    float cf = 1.f;
+    if (CLIP) cf = q_clip[(net == IQLHIP_NET_V) ? 0 : ((net == IQLHIP_NET_PI) ? 2 : 1)];
     __builtin_amdgcn_sched_barrier(0);      // (the loads above are issued BEFORE the argument fetch below is waited for)
     // every kernel-argument word the optimizer path uses, fetched in ONE batch of scalar loads (hipcc otherwise sinks
     // each load next to its first use: five dependent scalar-cache misses in front of the gradient loads).  ONE asm
@@ -92,7 +95,8 @@
     for (int k = 0; k < 4; ++k) {
       // (the fused multiply-adds are spelled out: left to -ffp-contract the four instantiations of this kernel are free
       //  to fuse differently, and the exchange variants must stay bitwise equal to the plain one)
-      const float gk = (gs == 1.f) ? gr[k] : gr[k] * gs;
+      // (CLIP: one separately rounded multiply by the group's coefficient — never contracted into the subtraction below)
+      const float gk = CLIP ? __fmul_rn((gs == 1.f) ? gr[k] : gr[k] * gs, cf) : ((gs == 1.f) ? gr[k] : gr[k] * gs);
       m[k] = fmaf(omb1, gk - m[k], m[k]);
       v[k] = fmaf(omb2 * gk, gk, v[k] * b2);
       const float denom = sqrtf(v[k]) / bc2 + eps;

@@ -173,6 +173,9 @@ SYMBOLS = [
     ("iqlhip_read_step_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_read_stats_ring", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
     ("iqlhip_group_read_step_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
+    ("iqlhip_set_grad_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("iqlhip_get_grad_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("iqlhip_read_grad_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

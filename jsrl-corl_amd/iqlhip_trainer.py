@@ -103,6 +103,8 @@ class ImplicitQLearning:
         self._act_key_stale = False   # set_dropout_seed since: the next inference call sends the new key
         self._step_stats = False      # set_step_stats: per-step training statistics (opt-in)
         self._step_stats_sent = False  # ... as the current context holds it
+        self._grad_clip = None        # set_grad_clip: (vf, qf, actor) max norms, inf = no limit; None: off (opt-in)
+        self._grad_clip_sent = None   # ... as the current context holds it
         self._masks_injected = False  # inject_dropout_masks since the last iqlhip_set_dropout: train_steps refuses
         if _is_gpu(device):
             self._attach(max_batch=256)
@@ -195,6 +197,7 @@ class ImplicitQLearning:
         self._dropout_sent = 0.0
         self._masks_injected = False
         self._step_stats_sent = False
+        self._grad_clip_sent = None
         self._max_batch = max_batch
         if getattr(self, "_precision", "f32") == "bf16":     # survives a re-attach for a larger batch
             hb.check(hb.lib().iqlhip_set_precision(self._ctx, 1))
@@ -350,6 +353,64 @@ class ImplicitQLearning:
                                       f"{STATS_BF16_MAX_ROWS} rows (got {rows}): the large-batch path keeps its row "
                                       "state in another layout")
 
+    def set_grad_clip(self, max_norm) -> None:
+        """Opt in to (or, with None, out of) gradient-norm clipping on the device: what
+        `torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm)` between `loss.backward()` and `optimizer.step()`
+        does in the reference, for each of the three optimizers on its own.  max_norm: a float (all
+        three), a dict with any of "vf" / "qf" / "actor", or a (vf, qf, actor) triple; a value that is None, <= 0 or
+        inf leaves that optimizer unclipped.  train(), online_step(), train_steps(), train_on_buffer() and the group
+        calls honour it; flat_gradient() keeps returning the unclipped gradient.  A trainer setting like
+        set_step_stats: part of neither state_dict() nor the hyper-parameters.  Not supported under data parallelism
+        or for bf16 batches of more than 512 rows (NotImplementedError from the step)."""
+        self._require_gpu()
+        if max_norm is None:
+            self._grad_clip = None
+            return
+        if isinstance(max_norm, dict):
+            unknown = set(max_norm) - {"vf", "qf", "actor"}
+            if unknown:
+                raise ValueError(f"iqlhip: set_grad_clip: unknown optimizer(s) {sorted(unknown)} (vf, qf, actor)")
+            vals = [max_norm.get(k) for k in ("vf", "qf", "actor")]
+        elif isinstance(max_norm, (tuple, list)):
+            if len(max_norm) != 3:
+                raise ValueError("iqlhip: set_grad_clip takes a float, a dict or a (vf, qf, actor) triple")
+            vals = list(max_norm)
+        else:
+            vals = [max_norm] * 3
+        lim = []
+        for v in vals:
+            v = float("inf") if v is None else float(v)
+            if v != v:
+                raise ValueError("iqlhip: set_grad_clip: max_norm is NaN")
+            lim.append(v if v > 0.0 else float("inf"))
+        self._grad_clip = None if all(v == float("inf") for v in lim) else tuple(lim)
+
+    @property
+    def grad_clip(self) -> Optional[Tuple[float, float, float]]:
+        """The (vf, qf, actor) max norms in force (inf = that optimizer is not clipped), or None when clipping is off."""
+        return self._grad_clip
+
+    def last_grad_clip(self) -> Dict[str, float]:
+        """The last step's gradient norms before clipping and its clip coefficients, per optimizer."""
+        self._require_gpu()
+        if self._grad_clip is None or self._grad_clip_sent != self._grad_clip:
+            raise ValueError("iqlhip: last_grad_clip() needs set_grad_clip(...) and a step taken since")
+        out = (C.c_float * 6)()
+        hb.check(hb.lib().iqlhip_read_grad_clip(self._ctx, out, self._stream()))
+        keys = ("norm_vf", "norm_qf", "norm_actor", "coef_vf", "coef_qf", "coef_actor")
+        return {k: float(out[i]) for i, k in enumerate(keys)}
+
+    def _check_grad_clip(self, rows: int) -> None:
+        """The two cases clipping is not built for — refused before anything is launched."""
+        if self._grad_clip is None:
+            return
+        if self._dp_world > 1 or self._dp_exchange is not None:
+            raise NotImplementedError("iqlhip: gradient clipping is not supported under data parallelism (the norm "
+                                      "would have to be taken after the exchange)")
+        if getattr(self, "_precision", "f32") == "bf16" and rows > STATS_BF16_MAX_ROWS:
+            raise NotImplementedError(f"iqlhip: gradient clipping is not supported for bf16 batches of more than "
+                                      f"{STATS_BF16_MAX_ROWS} rows (got {rows})")
+
     def _stats_entries(self) -> Dict[str, float]:
         """The last step's statistics as dict entries; nothing when they are off."""
         if not self._step_stats:
@@ -360,6 +421,7 @@ class ImplicitQLearning:
 
     def _prepare(self, rows: int) -> None:
         self._check_step_stats(rows)
+        self._check_grad_clip(rows)
         self._require_gpu()
         if rows > self._max_batch:
             self._attach(max_batch=(rows + 255) // 256 * 256)
@@ -376,6 +438,10 @@ class ImplicitQLearning:
         if self._step_stats != self._step_stats_sent:
             hb.check(hb.lib().iqlhip_set_step_stats(self._ctx, 1 if self._step_stats else 0))
             self._step_stats_sent = self._step_stats
+        if self._grad_clip != self._grad_clip_sent:
+            lim = (C.c_float * 3)(*(self._grad_clip or (0.0, 0.0, 0.0)))
+            hb.check(hb.lib().iqlhip_set_grad_clip(self._ctx, lim))
+            self._grad_clip_sent = self._grad_clip
 
     def _dropout_key(self) -> int:
         """The key of this trainer's keep-bit streams: set_dropout_seed(seed), else torch.initial_seed(), per rank."""
