@@ -533,6 +533,9 @@ int iqlhip_debug_time_kernel(iqlhip_ctx* ctx, const iqlhip_batch* batch, int whi
 /* Diagnostic: queue a flag kernel on `stream` and spin on its host-mapped word (no synchronise call): microseconds
  * until the host sees the stream drained. */
 int iqlhip_debug_drain_spin(iqlhip_ctx* ctx, void* stream, double* spin_us);
+/* Tests: the device buffers, pinned buffers and events this process's contexts and groups hold right now (what
+ * iqlhip_destroy / iqlhip_group_destroy release; cached graphs and the P2P exchange block are not counted). */
+int64_t iqlhip_debug_live_buffers(void);
 /* Average device time (microseconds) of the kernels of the last iqlhip_step /
  * train_steps call measured with hipEvents on `stream`; 0 when timing is off. */
 int iqlhip_set_timing(iqlhip_ctx* ctx, int enabled);

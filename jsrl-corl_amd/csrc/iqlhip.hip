@@ -2,6 +2,7 @@
 // arena layout, scratch management, launches, hipGraph capture of K-step chunks.
 #include "iqlhip_kernels.h"
 #include "iqlhip_lb_kernels.h"
+#include "iqlhip_owned.h"
 
 #include <dlfcn.h>
 
@@ -40,6 +41,31 @@ static int fail(int code, const char* fmt, ...) {
   } while (0)
 
 static inline int64_t up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// Buffer and event ownership (iqlhip_owned.h) on the HIP runtime.  A context and a trainer group each have one Owned:
+// it is used at create time and when an opt-in feature is first enabled, never by a step.
+struct HipApi {
+  using err_t = hipError_t;
+  using event_t = hipEvent_t;
+  static constexpr err_t ok = hipSuccess;
+  static err_t dev_alloc(void** p, size_t n) { return hipMalloc(p, n); }
+  static err_t dev_fill(void* p, int byte, size_t n) { return hipMemset(p, byte, n); }
+  static err_t dev_free(void* p) { return hipFree(p); }
+  static err_t pin_alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+  static err_t pin_free(void* p) { return hipHostFree(p); }
+  static err_t event_create(event_t* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
+  static err_t event_destroy(event_t e) { return hipEventDestroy(e); }
+};
+using Owned = OwnedT<HipApi>;
+extern "C" int64_t iqlhip_debug_live_buffers(void) { return Owned::live().load(std::memory_order_relaxed); }
+// All of `allocate`'s allocations or none: on an error what it made is freed and its pointers are null again (the
+// error message stays), so the caller's "already allocated" test, whichever pointer it looks at, is false again.
+template <class F> static int all_or_nothing(Owned& own, F&& allocate) {
+  const size_t mark = own.mark();
+  const int rc = allocate();
+  if (rc) own.rollback(mark);
+  return rc;
+}
 
 // Runtime flags -> template arguments: with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...).
 // Every kernel family with bool template parameters has ONE selector built on it (flags -> instantiation), next to its
@@ -139,6 +165,7 @@ struct iqlhip_ctx {
   iqlhip_hyper hyper;
   iqlhip_layout L;
   int device = 0;
+  Owned own;                          // every buffer and event below that the library allocates, except where noted
   // bound (caller-owned)
   float *params = nullptr, *target = nullptr, *m = nullptr, *v = nullptr;
   // scratch (library-owned)
@@ -185,7 +212,7 @@ struct iqlhip_ctx {
   unsigned long long sched_want[4] = {0, 0, 0, 0};
   unsigned long long call_seq = 0;
   unsigned* setup_arrivals = nullptr;           // device: block counter of iql_call_setup_kernel
-  char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (a hipFree at the end of prepare
+  char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (freeing it at the end of prepare
                                                 //   idles the GPU right in front of the caller's first steps)
   hipStream_t sched_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // (the stream a slot's reader was queued on)
   int sched_slot = 0;
@@ -213,7 +240,7 @@ struct iqlhip_ctx {
   // graph cache (a few (K,B,buffer) shapes: the steady chunk, the tail chunk, ...)
   hipStream_t cap_stream = nullptr;
   struct CachedGraph { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long long stamp; hipStream_t last;
-                       IdleWork* work; /* [K] device records of the chunk's idle-block work */
+                       IdleWork* work; /* [K] device records of the chunk's idle-block work (freed with the graph, not by `own`) */
                        hipGraphNode_t setup_node; /* head chunks: the set-up kernel's node */ };
   // Continuation of the index stream across calls: the last forward of a call stages the rows (and keep-bits) of the
   // step that would come next; a following call that IS that step (same rows / size / batch / seed, counter position
@@ -228,7 +255,7 @@ struct iqlhip_ctx {
   float* xflat = nullptr;             // RCCL / split path: this rank's flat gradient [n_params + 4] (+ pad)
   void* nccl_comm = nullptr;
   // P2P: one exchange block per rank = [flags: IQLHIP_MAX_WORLD x 16 u64][flat 0][flat 1], exported through hipIpc
-  char* xblk = nullptr;
+  char* xblk = nullptr;               // (freed by iqlhip_xch_shutdown, not by `own`)
   size_t xblk_bytes = 0, xflat_off[2] = {0, 0};   // per parity buffer: [flat n_params+4 | slab_b (8 row tiles) | loss_parts]
   size_t xslabb_off[2] = {0, 0}, xloss_off[2] = {0, 0};
   long long xslab_b_off[4] = {0, 0, 0, 0};        // per-net offsets inside an exchange block's slab_b region (8 row tiles)
@@ -257,7 +284,7 @@ struct iqlhip_ctx {
   bool has_last_stream = false;
   // timing
   bool timing = false;
-  std::vector<hipEvent_t> ev;         // 4 per recorded step
+  std::vector<hipEvent_t> ev;         // 4 per recorded step (grown by ensure_events, destroyed by iqlhip_destroy)
   int ev_used = 0;
   float t_acc[4] = {0, 0, 0, 0};
   int t_n = 0;
@@ -325,29 +352,24 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   c->n_chunk_max = (MB + CHUNK_ROWS - 1) / CHUNK_ROWS;
   c->n_rt_max = (MB + RT_ROWS - 1) / RT_ROWS;
   c->sc.max_batch = MB;
-  auto dalloc = [&](float** p, size_t nfloat) -> hipError_t {
-    hipError_t e = hipMalloc((void**)p, nfloat * sizeof(float));
-    if (e != hipSuccess) return e;
-    return hipMemset(*p, 0, nfloat * sizeof(float));
-  };
+  Owned& own = c->own;
+  auto dalloc = [&](float** p, size_t nfloat) { return own.dev(p, nfloat * sizeof(float), 0); };
   HIPCHK(dalloc(&c->sc.h0, (size_t)4 * MB * HID));
   HIPCHK(dalloc(&c->sc.h1, (size_t)4 * MB * HID));
   HIPCHK(dalloc(&c->sc.heads, (size_t)MB * HEAD_LD + (size_t)NSPLIT * MB * A));
   c->row_ld = iqlhip_row_stride(dims->state_dim, A);
   HIPCHK(dalloc(&c->xb, (size_t)MB * c->row_ld));
   HIPCHK(dalloc(&c->xb2, (size_t)MB * c->row_ld));
-  HIPCHK(hipHostMalloc((void**)&c->losses_host, 4 * sizeof(float), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&c->on_row_pin, (size_t)c->row_ld * sizeof(float), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&c->on_idx_pin, (size_t)MB * sizeof(long long), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&c->on_loss_pin, 4 * sizeof(float), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&c->done_pin, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-  memset(c->done_pin, 0, 8 * sizeof(unsigned long long));
-  HIPCHK(hipHostMalloc((void**)&c->on_act_pin, (size_t)(IQLHIP_MAX_INPUT + IQLHIP_MAX_ACTION) * sizeof(float), hipHostMallocDefault));
+  HIPCHK(own.pin(&c->losses_host, 4 * sizeof(float)));
+  HIPCHK(own.pin(&c->on_row_pin, (size_t)c->row_ld * sizeof(float)));
+  HIPCHK(own.pin(&c->on_idx_pin, (size_t)MB * sizeof(long long)));
+  HIPCHK(own.pin(&c->on_loss_pin, 4 * sizeof(float)));
+  HIPCHK(own.pin(&c->done_pin, 8 * sizeof(unsigned long long), /*zero=*/true));
+  HIPCHK(own.pin(&c->on_act_pin, (size_t)(IQLHIP_MAX_INPUT + IQLHIP_MAX_ACTION) * sizeof(float)));
   c->act_cap = std::max(MB, IQLHIP_ACT_ROWS);
   HIPCHK(dalloc(&c->xb_act, (size_t)c->act_cap * c->row_ld));
   HIPCHK(dalloc(&c->heads_act, (size_t)c->act_cap * A * NSPLIT));
-  HIPCHK(hipMalloc((void**)&c->drop_bits, (size_t)4 * MB * 8 * sizeof(unsigned)));
-  HIPCHK(hipMemset(c->drop_bits, 0xFF, (size_t)4 * MB * 8 * sizeof(unsigned)));
+  HIPCHK(own.dev(&c->drop_bits, (size_t)4 * MB * 8 * sizeof(unsigned), 0xFF));
   HIPCHK(dalloc(&c->sc.slab_a, (size_t)c->n_chunk_max * c->L.n_params));
   size_t sb = 0;
   for (int n = 0; n < 4; ++n) {
@@ -363,28 +385,19 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   c->ring_cap = c->k_max;
   // the loss ring lives in host-mapped pinned memory: each step's update kernel posts its 3 words there, and the
   // end of a train_steps call is ONE stream synchronisation queued right behind the work — no device-to-host copy
-  HIPCHK(hipHostMalloc((void**)&c->loss_ring, (size_t)c->ring_cap * 4 * sizeof(float), hipHostMallocDefault));
-  memset(c->loss_ring, 0, (size_t)c->ring_cap * 4 * sizeof(float));
-  HIPCHK(hipMalloc((void**)&c->sched_cur, (size_t)GRAPH_STEPS * sizeof(iqlhip_step_scalars)));
-  HIPCHK(hipMalloc((void**)&c->sched_call, (size_t)c->k_max * sizeof(iqlhip_step_scalars)));
-  for (int i = 0; i < 4; ++i) {
-    HIPCHK(hipHostMalloc((void**)&c->sched_pin[i], (size_t)c->k_max * sizeof(iqlhip_step_scalars), hipHostMallocDefault));
-  }
-  HIPCHK(hipHostMalloc((void**)&c->sched_ack, 8 * sizeof(unsigned long long), hipHostMallocDefault));   // [4] slots + a dummy word
-  memset(c->sched_ack, 0, 8 * sizeof(unsigned long long));
-  HIPCHK(hipMalloc((void**)&c->setup_arrivals, 64));
-  HIPCHK(hipMemset(c->setup_arrivals, 0, 64));
-  HIPCHK(hipMalloc((void**)&c->hdr, HDR_WORDS * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(c->hdr, 0, HDR_WORDS * sizeof(unsigned long long)));
-  HIPCHK(hipMalloc((void**)&c->xstatus, 2 * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(c->xstatus, 0, 2 * sizeof(unsigned long long)));
-  HIPCHK(hipHostMalloc((void**)&c->xstatus_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-  c->xstatus_host[0] = c->xstatus_host[1] = 0ull;
+  HIPCHK(own.pin(&c->loss_ring, (size_t)c->ring_cap * 4 * sizeof(float), /*zero=*/true));
+  HIPCHK(own.dev(&c->sched_cur, (size_t)GRAPH_STEPS * sizeof(iqlhip_step_scalars)));
+  HIPCHK(own.dev(&c->sched_call, (size_t)c->k_max * sizeof(iqlhip_step_scalars)));
+  for (int i = 0; i < 4; ++i) HIPCHK(own.pin(&c->sched_pin[i], (size_t)c->k_max * sizeof(iqlhip_step_scalars)));
+  HIPCHK(own.pin(&c->sched_ack, 8 * sizeof(unsigned long long), /*zero=*/true));   // [4] slots + a dummy word
+  HIPCHK(own.dev(&c->setup_arrivals, 64, 0));
+  HIPCHK(own.dev(&c->hdr, HDR_WORDS * sizeof(unsigned long long), 0));
+  HIPCHK(own.dev(&c->xstatus, 2 * sizeof(unsigned long long), 0));
+  HIPCHK(own.pin(&c->xstatus_host, 2 * sizeof(unsigned long long), /*zero=*/true));
   HIPCHK(dalloc(&c->xflat, (size_t)up(c->L.n_params + 4, 64)));
   HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
 #ifdef IQL_STAMPS
-  HIPCHK(hipMalloc((void**)&c->stamps, 4096 * 16 * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(c->stamps, 0, 4096 * 16 * sizeof(unsigned long long)));
+  HIPCHK(own.dev(&c->stamps, 4096 * 16 * sizeof(unsigned long long), 0));
 #endif
   // LDS sizes
   const int kq = dims->state_dim + dims->action_dim;
@@ -451,12 +464,17 @@ extern "C" int iqlhip_create(const iqlhip_dims* dims, const iqlhip_hyper* hyper,
   return IQLHIP_OK;
 }
 
+// A cached chunk graph's three resources (their lifetime is the graph's, not the context's: the cache evicts); null
+// members: a graph whose construction stopped half-way.
+static void free_graph(iqlhip_ctx::CachedGraph& g) {
+  if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  if (g.graph) (void)hipGraphDestroy(g.graph);
+  if (g.work) (void)hipFree(g.work);
+}
 static void drop_graph(iqlhip_ctx* c) {
   for (auto& g : c->graphs) {
     if (g.last) (void)hipStreamSynchronize(g.last);   // a replay may still be executing
-    (void)hipGraphExecDestroy(g.exec);
-    (void)hipGraphDestroy(g.graph);
-    if (g.work) (void)hipFree(g.work);
+    free_graph(g);
   }
   c->graphs.clear();
   c->cont.valid = false;
@@ -470,28 +488,7 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   (void)iqlhip_xch_shutdown(c);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
-  void* bufs[] = {c->sc.h0, c->sc.h1, c->sc.heads, c->sc.slab_a, c->sc.slab_b, c->sc.loss_parts, c->sc.losses,
-                  c->flat_tmp, c->sched_call, c->sched_cur, c->hdr, c->stamps, c->xb, c->xb2, c->xb_act,
-                  c->heads_act, c->drop_bits, c->act_drop_bits, c->xstatus, c->xflat, c->wsh, c->tsh, c->pi_t, c->dh1g, c->slab_x, c->wimg,
-                  c->stats_part, c->stats_last, c->stats_ring, c->clip_dev};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-  for (int i = 0; i < 4; ++i) {
-    if (c->sched_pin[i]) (void)hipHostFree(c->sched_pin[i]);
-  }
-  if (c->sched_ack) (void)hipHostFree(c->sched_ack);
-  if (c->loss_ring) (void)hipHostFree(c->loss_ring);
-  if (c->xstatus_host) (void)hipHostFree(c->xstatus_host);
-  if (c->setup_arrivals) (void)hipFree(c->setup_arrivals);
-  if (c->prep_save) (void)hipFree(c->prep_save);
-  if (c->losses_host) (void)hipHostFree(c->losses_host);
-  if (c->on_row_pin) (void)hipHostFree(c->on_row_pin);
-  if (c->on_idx_pin) (void)hipHostFree(c->on_idx_pin);
-  if (c->on_loss_pin) (void)hipHostFree(c->on_loss_pin);
-  if (c->done_pin) (void)hipHostFree(c->done_pin);
-  if (c->on_act_pin) (void)hipHostFree(c->on_act_pin);
-  if (c->stats_host) (void)hipHostFree(c->stats_host);
-  if (c->clip_host) (void)hipHostFree(c->clip_host);
-  if (c->clip_up) (void)hipEventDestroy(c->clip_up);
+  c->own.release_all();
   delete c;
   return IQLHIP_OK;
 }
@@ -509,16 +506,18 @@ extern "C" int iqlhip_set_precision(iqlhip_ctx* c, int mode) {
   if (mode != c->precision) drop_graph(c);
   if (mode == 1 && !c->wsh) {
     DevGuard guard(c->device);
-    HIPCHK(hipMalloc((void**)&c->wsh, (size_t)up(c->L.n_params, 64) * sizeof(__bf16)));
-    HIPCHK(hipMalloc((void**)&c->tsh, (size_t)up(c->L.n_target, 64) * sizeof(__bf16)));
-    // scratch of the large-batch backward (iqlhip_lb_kernels.h)
-    const size_t MB = (size_t)c->dims.max_batch;
-    HIPCHK(hipMalloc((void**)&c->dh1g, (8 * MB * HID + MB * 32 + MB * LB_XLD + 4 * 65536 + 8192) * sizeof(__bf16)));
-    HIPCHK(hipMemset(c->dh1g, 0, (8 * MB * HID + MB * 32 + MB * LB_XLD + 4 * 65536 + 8192) * sizeof(__bf16)));
-    HIPCHK(hipMalloc((void**)&c->wimg, (size_t)6 * IMG_STRIDE * sizeof(__bf16)));
-    HIPCHK(hipMemset(c->wimg, 0, (size_t)6 * IMG_STRIDE * sizeof(__bf16)));
-    HIPCHK(hipMalloc((void**)&c->slab_x, (size_t)64 * c->L.n_params * sizeof(float)));
-    HIPCHK(hipMemset(c->slab_x, 0, (size_t)64 * c->L.n_params * sizeof(float)));
+    const int rc = all_or_nothing(c->own, [&]() -> int {
+      Owned& own = c->own;
+      HIPCHK(own.dev(&c->wsh, (size_t)up(c->L.n_params, 64) * sizeof(__bf16)));
+      HIPCHK(own.dev(&c->tsh, (size_t)up(c->L.n_target, 64) * sizeof(__bf16)));
+      // scratch of the large-batch backward (iqlhip_lb_kernels.h)
+      const size_t MB = (size_t)c->dims.max_batch;
+      HIPCHK(own.dev(&c->dh1g, (8 * MB * HID + MB * 32 + MB * LB_XLD + 4 * 65536 + 8192) * sizeof(__bf16), 0));
+      HIPCHK(own.dev(&c->wimg, (size_t)6 * IMG_STRIDE * sizeof(__bf16), 0));
+      HIPCHK(own.dev(&c->slab_x, (size_t)64 * c->L.n_params * sizeof(float), 0));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
   }
   c->precision = mode;
   return IQLHIP_OK;
@@ -555,9 +554,7 @@ extern "C" int iqlhip_set_act_dropout(iqlhip_ctx* c, float p, uint64_t seed) {
   if (!(p >= 0.f && p < 1.f)) return fail(IQLHIP_EINVAL, "dropout probability must be in [0,1)");
   if (p > 0.f && !c->act_drop_bits) {
     DevGuard guard(c->device);
-    const size_t bytes = (size_t)2 * c->act_cap * 8 * sizeof(unsigned);
-    HIPCHK(hipMalloc((void**)&c->act_drop_bits, bytes));
-    HIPCHK(hipMemset(c->act_drop_bits, 0xFF, bytes));
+    HIPCHK(c->own.dev(&c->act_drop_bits, (size_t)2 * c->act_cap * 8 * sizeof(unsigned), 0xFF));      // (one allocation: made whole or not at all)
   }
   c->act_drop_p = p;
   c->act_drop_seed = seed;
@@ -1015,6 +1012,16 @@ static void launch_flatten(const iqlhip_ctx* c, const UpdParams& u, float* out, 
   hipLaunchKernelGGL(flatten_kernel(sys, /*lb=*/u.slab_x != nullptr), dim3(nb), dim3(256), 0, st, u, out);
 }
 
+// A read-back: `bytes` from device memory into the pinned landing pad `pin` on `st`; sync: wait for the stream and, with
+// dst_host, copy them out.  (sync = false queues the copy only: callers with several pieces synchronise once.)
+static int read_back(void* dst_host, void* pin, const void* dev, size_t bytes, hipStream_t st, bool sync = true) {
+  HIPCHK(hipMemcpyAsync(pin, dev, bytes, hipMemcpyDeviceToHost, st));
+  if (!sync) return IQLHIP_OK;
+  HIPCHK(hipStreamSynchronize(st));
+  if (dst_host) memcpy(dst_host, pin, bytes);
+  return IQLHIP_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Per-step statistics (include/iqlhip.h "per-step training statistics"; kernels: iqlhip_kernels.h).
 static int stats_parts(const iqlhip_ctx* c) { return upd_blocks(c) / 8 * 2; }      // 1024-element windows of the longest segment
@@ -1022,43 +1029,52 @@ static int stats_parts(const iqlhip_ctx* c) { return upd_blocks(c) / 8 * 2; }   
 static int ensure_gparts(iqlhip_ctx* c) {
   if (c->stats_part) return IQLHIP_OK;
   c->stats_n_part = stats_parts(c);
-  HIPCHK(hipMalloc((void**)&c->stats_part, (size_t)4 * c->stats_n_part * sizeof(float)));
-  HIPCHK(hipMemset(c->stats_part, 0, (size_t)4 * c->stats_n_part * sizeof(float)));
+  HIPCHK(c->own.dev(&c->stats_part, (size_t)4 * c->stats_n_part * sizeof(float), 0));
   return IQLHIP_OK;
 }
 extern "C" int iqlhip_set_step_stats(iqlhip_ctx* c, int enabled) {
   if (!c) return fail(IQLHIP_EINVAL, "NULL ctx");
   if (enabled && !c->stats_ring) {
     DevGuard guard(c->device);
-    const size_t ring = (size_t)c->k_max * IQLHIP_N_STATS * sizeof(float);
-    if (int rc = ensure_gparts(c)) return rc;
-    HIPCHK(hipMalloc((void**)&c->stats_last, IQLHIP_N_STATS * sizeof(float)));
-    HIPCHK(hipMemset(c->stats_last, 0, IQLHIP_N_STATS * sizeof(float)));
-    HIPCHK(hipHostMalloc((void**)&c->stats_host, ring, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&c->stats_ring, ring));
-    HIPCHK(hipMemset(c->stats_ring, 0, ring));
+    const int rc = all_or_nothing(c->own, [&]() -> int {
+      const size_t ring = (size_t)c->k_max * IQLHIP_N_STATS * sizeof(float);
+      if (int rc_g = ensure_gparts(c)) return rc_g;
+      HIPCHK(c->own.dev(&c->stats_last, IQLHIP_N_STATS * sizeof(float), 0));
+      HIPCHK(c->own.pin(&c->stats_host, ring));
+      HIPCHK(c->own.dev(&c->stats_ring, ring, 0));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
   }
   c->stats_on = enabled != 0;
   return IQLHIP_OK;
 }
-// Every step entry point, once its checks have passed: the stream its work is queued on.
-static void note_stream(iqlhip_ctx* c, void* stream) { c->last_stream = (hipStream_t)stream; c->has_last_stream = true; }
-// The two cases statistics are not built for, checked by every step entry point before it launches anything.
-// (... and the same two for gradient clipping: there the norm would have to be taken after the exchange, and the
-//  large-batch path keeps its gradient in other slabs)
-static int stats_check(const iqlhip_ctx* c, int rows) {
-  if (c->clip_on) {
+// The two cases the opt-in features that look at a step's gradient are not built for.  Statistics: the local slabs are
+// not what Adam receives after an exchange; clipping: the norm would have to be taken after it; and the large-batch
+// path keeps its gradient in other slabs.
+static int optional_features_check(const iqlhip_ctx* c, int rows) {
+  const struct { bool on; const char* what; const char* xch_reason; } features[] = {
+      {c->clip_on, "gradient clipping is", "the norm would have to be taken after the exchange"},
+      {c->stats_on, "step statistics are", "the local gradient slabs are not what Adam receives"}};
+  for (const auto& f : features) {
+    if (!f.on) continue;
     if (c->xch_mode != IQLHIP_XCH_NONE)
-      return fail(IQLHIP_EUNSUPPORTED, "gradient clipping is not supported with a data-parallel exchange (the norm would have to be taken after the exchange)");
+      return fail(IQLHIP_EUNSUPPORTED, "%s not supported with a data-parallel exchange (%s)", f.what, f.xch_reason);
     if (use_lb(c, rows))
-      return fail(IQLHIP_EUNSUPPORTED, "gradient clipping is not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+      return fail(IQLHIP_EUNSUPPORTED, "%s not supported on the large-batch bf16 path (more than %d rows)", f.what, LB_MIN_ROWS);
   }
-  if (!c->stats_on) return IQLHIP_OK;
-  if (c->xch_mode != IQLHIP_XCH_NONE)
-    return fail(IQLHIP_EUNSUPPORTED, "step statistics are not supported with a data-parallel exchange (the local gradient slabs are not what Adam receives)");
-  if (use_lb(c, rows))
-    return fail(IQLHIP_EUNSUPPORTED, "step statistics are not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
   return IQLHIP_OK;
+}
+static int inject_check(const iqlhip_ctx* c);
+// The last check of every solo step entry point, before anything is launched or any counter moves: the opt-in features
+// (and, for the multi-step driver, pending injected masks); then the stream its work is queued on is remembered.
+// (The group entry points: group_check_call.)
+static void note_stream(iqlhip_ctx* c, void* stream) { c->last_stream = (hipStream_t)stream; c->has_last_stream = true; }
+static int step_entry(iqlhip_ctx* c, int rows, void* stream, bool multi_step) {
+  int rc = optional_features_check(c, rows);
+  if (!rc && multi_step) rc = inject_check(c);
+  if (!rc) note_stream(c, stream);
+  return rc;
 }
 // The statistics launches' arguments for a step described by `p`; ring == nullptr: the eager steps (stats_last only).
 static StatsArgs make_stats(const iqlhip_ctx* c, const StepParams& p, float* ring, int ring_slot, int ring_cap,
@@ -1090,21 +1106,14 @@ extern "C" int iqlhip_read_step_stats(iqlhip_ctx* c, float out[IQLHIP_N_STATS], 
   if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (!c->stats_on) return fail(IQLHIP_EINVAL, "step statistics are off (iqlhip_set_step_stats)");
   DevGuard guard(c->device);
-  HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_last, IQLHIP_N_STATS * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  memcpy(out, c->stats_host, IQLHIP_N_STATS * sizeof(float));
-  return IQLHIP_OK;
+  return read_back(out, c->stats_host, c->stats_last, IQLHIP_N_STATS * sizeof(float), (hipStream_t)stream);
 }
 extern "C" int iqlhip_read_stats_ring(iqlhip_ctx* c, float* out, int32_t n_steps, void* stream) {
   if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (!c->stats_on) return fail(IQLHIP_EINVAL, "step statistics are off (iqlhip_set_step_stats)");
   if (n_steps < 1 || n_steps > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
   DevGuard guard(c->device);
-  const size_t bytes = (size_t)n_steps * IQLHIP_N_STATS * sizeof(float);
-  HIPCHK(hipMemcpyAsync(c->stats_host, c->stats_ring, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  memcpy(out, c->stats_host, bytes);
-  return IQLHIP_OK;
+  return read_back(out, c->stats_host, c->stats_ring, (size_t)n_steps * IQLHIP_N_STATS * sizeof(float), (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1122,10 +1131,14 @@ extern "C" int iqlhip_set_grad_clip(iqlhip_ctx* c, const float max_norm[3]) {
     DevGuard guard(c->device);
     const bool first = !c->clip_dev;
     if (first) {
-      if (int rc = ensure_gparts(c)) return rc;
-      HIPCHK(hipHostMalloc((void**)&c->clip_host, 24 * sizeof(float), hipHostMallocDefault));
-      HIPCHK(hipMalloc((void**)&c->clip_dev, 12 * sizeof(float)));
-      HIPCHK(hipEventCreateWithFlags(&c->clip_up, hipEventDisableTiming));
+      const int rc = all_or_nothing(c->own, [&]() -> int {
+        if (int rc_g = ensure_gparts(c)) return rc_g;
+        HIPCHK(c->own.pin(&c->clip_host, 24 * sizeof(float)));
+        HIPCHK(c->own.dev(&c->clip_dev, 12 * sizeof(float)));
+        HIPCHK(c->own.event(&c->clip_up, hipEventDisableTiming));
+        return IQLHIP_OK;
+      });
+      if (rc) return rc;
     }
     // The limits (and, the first time, zeros for the rest of clip_dev) travel from pinned memory on the stream of the
     // context's last step call: behind the steps queued there, in front of every later one, without stalling the
@@ -1158,8 +1171,7 @@ extern "C" int iqlhip_read_grad_clip(iqlhip_ctx* c, float out[6], void* stream) 
   if (!c->clip_on) return fail(IQLHIP_EINVAL, "gradient clipping is off (iqlhip_set_grad_clip)");
   DevGuard guard(c->device);
   float* land = c->clip_host + 12;
-  HIPCHK(hipMemcpyAsync(land, c->clip_dev, 12 * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  if (int rc = read_back(nullptr, land, c->clip_dev, 12 * sizeof(float), (hipStream_t)stream)) return rc;
   for (int g = 0; g < 3; ++g) { out[g] = land[8 + g]; out[3 + g] = land[4 + g]; }
   return IQLHIP_OK;
 }
@@ -1366,6 +1378,15 @@ static int xch_poisoned(iqlhip_ctx* c, const unsigned long long* status_host) {
               "the replicas are no longer synchronised", status_host[0]);
 }
 
+// Synchronise `st`; with a P2P exchange the status words come back in front of that and a recorded timeout is the result.
+static bool xch_p2p(const iqlhip_ctx* c) { return c->xch_mode == IQLHIP_XCH_P2P && c->world > 1; }
+static int xch_status_after_sync(iqlhip_ctx* c, hipStream_t st) {
+  const bool p2p = xch_p2p(c);
+  if (p2p) HIPCHK(hipMemcpyAsync(c->xstatus_host, c->xstatus, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return p2p ? xch_poisoned(c, c->xstatus_host) : IQLHIP_OK;
+}
+
 static XchParams make_xch(const iqlhip_ctx* c, bool from_hdr) {
   XchParams x;
   memset(&x, 0, sizeof x);
@@ -1485,7 +1506,34 @@ static int wait_word(const unsigned long long* f, unsigned long long val, hipStr
   if (__atomic_load_n(f, __ATOMIC_ACQUIRE) != val) return fail(IQLHIP_EHIP, "the step's completion word was not written");
   return IQLHIP_OK;
 }
-static int wait_done(iqlhip_ctx* c, unsigned long long val, hipStream_t st) { return wait_word(c->done_pin, val, st); }
+// The synchronous tail of an eager step whose update mirrors its losses into on_loss_pin: with a P2P exchange the
+// ordinary synchronise (the exchange's status word has to come back too), else the completion word; then the losses.
+static int sync_losses(iqlhip_ctx* c, unsigned long long done_val, hipStream_t st, float out[3]) {
+  const int rc = xch_p2p(c) ? xch_status_after_sync(c, st) : wait_word(c->done_pin, done_val, st);
+  if (rc) return rc;
+  out[0] = c->on_loss_pin[0]; out[1] = c->on_loss_pin[1]; out[2] = c->on_loss_pin[2];
+  return IQLHIP_OK;
+}
+
+// The head of an eager step, once its caller has made its checks and staged or gathered the batch at `xb`: the staging
+// a following train_steps call might continue from is no longer that call's, the bf16 shadows are refreshed, the
+// step's keep-bits drawn (draw = false: iqlhip_debug_time_kernel, which moves no stream position), and the step's
+// records built.
+struct EagerStep {
+  StepParams p; UpdParams u; StatsArgs sa; bool with_stats;
+  const StatsArgs* stats() const { return with_stats ? &sa : nullptr; }
+};
+static void eager_begin(iqlhip_ctx* c, int rows, const iqlhip_step_scalars* sc, hipStream_t st, const float* xb, EagerStep& e,
+                        bool draw = true) {
+  c->cont.valid = false;
+  refresh_shadows(c, st);
+  if (draw && c->drop_p > 0.f && !c->drop_inject) launch_dropmask(c, c->drop_seed, c->drop_step++, nullptr, 0, st);
+  e.p = make_step(c, rows, sc->inv_batch);
+  e.p.xb = xb;
+  e.u = make_upd(c, sc, rows, nullptr);
+  e.with_stats = c->stats_on;
+  if (e.with_stats) e.sa = make_stats(c, e.p, nullptr, 0, 0, nullptr);
+}
 
 static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* out_sync, void* stream,
                      bool defer_wait = false);
@@ -1510,18 +1558,7 @@ extern "C" int iqlhip_step_begin(iqlhip_ctx* c, const iqlhip_batch* b, const iql
 }
 extern "C" int iqlhip_step_wait(iqlhip_ctx* c, float out[3], void* stream) {
   if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
-  hipStream_t st = (hipStream_t)stream;
-  if (c->xch_mode == IQLHIP_XCH_P2P && c->world > 1) {
-    HIPCHK(hipMemcpyAsync(c->xstatus_host, c->xstatus, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int rc = xch_poisoned(c, c->xstatus_host);
-    if (rc) return rc;
-  } else {
-    int rc = wait_done(c, c->done_seq, st);
-    if (rc) return rc;
-  }
-  out[0] = c->on_loss_pin[0]; out[1] = c->on_loss_pin[1]; out[2] = c->on_loss_pin[2];
-  return IQLHIP_OK;
+  return sync_losses(c, c->done_seq, (hipStream_t)stream, out);
 }
 
 static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* out_sync, void* stream,
@@ -1529,25 +1566,19 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
   if (!c || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_batch(c, b);
   if (rc) return rc;
-  if ((rc = stats_check(c, b->rows))) return rc;
-  note_stream(c, stream);
+  if ((rc = step_entry(c, b->rows, stream, /*multi_step=*/false))) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
-  c->cont.valid = false;                 // (the staging buffers / keep-bits a following train_steps call might continue from)
   const float* xb_cur = nullptr;
   rc = stage_batch(c, b, st, &xb_cur);
   if (rc) return rc;
-  refresh_shadows(c, st);
-  if (c->drop_p > 0.f && !c->drop_inject) launch_dropmask(c, c->drop_seed, c->drop_step++, nullptr, 0, st);
-  StepParams p = make_step(c, b->rows, sc->inv_batch);
-  p.xb = xb_cur;
-  UpdParams u = make_upd(c, sc, b->rows, nullptr);
-  const bool p2p_x = c->xch_mode == IQLHIP_XCH_P2P && c->world > 1;
+  EagerStep e;
+  eager_begin(c, b->rows, sc, st, xb_cur, e);
   unsigned long long done_val = 0;
   if (out_sync) {
-    u.losses_mirror = c->on_loss_pin;
-    u.done_flag = c->done_pin;
-    u.done_val = done_val = ++c->done_seq;
+    e.u.losses_mirror = c->on_loss_pin;
+    e.u.done_flag = c->done_pin;
+    e.u.done_val = done_val = ++c->done_seq;
   }
   hipEvent_t* ev = nullptr;
   if (c->timing) {
@@ -1558,25 +1589,11 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
     c->ev_used += 4;
     HIPCHK(hipEventRecord(ev[0], st));
   }
-  StatsArgs sa;
-  if (c->stats_on) sa = make_stats(c, p, nullptr, 0, 0, nullptr);
-  rc = enqueue_step(c, p, u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, c->stats_on ? &sa : nullptr);
+  rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, e.stats());
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
   HIPCHK(hipGetLastError());
-  if (out_sync && !defer_wait) {
-    if (p2p_x) {       // (the exchange's status word has to come back too: the ordinary synchronise)
-      HIPCHK(hipMemcpyAsync(c->xstatus_host, c->xstatus, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      rc = xch_poisoned(c, c->xstatus_host);
-      if (rc) return rc;
-    } else {
-      rc = wait_done(c, done_val, st);
-      if (rc) return rc;
-    }
-    out_sync[0] = c->on_loss_pin[0]; out_sync[1] = c->on_loss_pin[1]; out_sync[2] = c->on_loss_pin[2];
-  }
-  return IQLHIP_OK;
+  return (out_sync && !defer_wait) ? sync_losses(c, done_val, st, out_sync) : IQLHIP_OK;
 }
 
 static int actor_forward_impl(iqlhip_ctx* c, const float* states_dev, int64_t ld_s, int32_t rows, const float* noise_dev,
@@ -1601,27 +1618,21 @@ extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, in
   {                                       // (the reference's torch indexing raises on such an index; a gather would fault)
     int rc_i = check_host_indices(idx_host, n, capacity);
     if (rc_i) return rc_i;
-    if ((rc_i = stats_check(c, n))) return rc_i;
+    if ((rc_i = step_entry(c, n, stream, /*multi_step=*/false))) return rc_i;
   }
-  note_stream(c, stream);
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
-  c->cont.valid = false;
   memcpy(c->on_row_pin, row_host, (size_t)ld * sizeof(float));
   memcpy(c->on_idx_pin, idx_host, (size_t)n * sizeof(long long));
   const int total = n * (int)(ld / 4);
   hipLaunchKernelGGL(iql_online_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, st, rows_dev, (long long)ld,
                      (long long)pointer, (const float*)c->on_row_pin, (const long long*)c->on_idx_pin, c->xb, n);
-  refresh_shadows(c, st);
-  if (c->drop_p > 0.f && !c->drop_inject) launch_dropmask(c, c->drop_seed, c->drop_step++, nullptr, 0, st);
-  StepParams p = make_step(c, n, sc->inv_batch);
-  UpdParams u = make_upd(c, sc, n, nullptr);
-  u.losses_mirror = c->on_loss_pin;
+  EagerStep e;
+  eager_begin(c, n, sc, st, c->xb, e);
+  e.u.losses_mirror = c->on_loss_pin;
   const unsigned long long done_val = ++c->done_seq;
-  if (!act_state_host) { u.done_flag = c->done_pin; u.done_val = done_val; }      // (else the follow-up act() signals)
-  StatsArgs sa;
-  if (c->stats_on) sa = make_stats(c, p, nullptr, 0, 0, nullptr);
-  int rc = enqueue_step(c, p, u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr, c->stats_on ? &sa : nullptr);
+  if (!act_state_host) { e.u.done_flag = c->done_pin; e.u.done_val = done_val; }      // (else the follow-up act() signals)
+  int rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr, e.stats());
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
   const int S = c->dims.state_dim, A = c->dims.action_dim;
@@ -1635,21 +1646,12 @@ extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, in
              : actor_forward_impl(c, c->on_act_pin, S, 1, nullptr, 0, 0, 0, max_action, a_out, A, stream, c->done_pin, done_val);
     if (rc) return rc;
   }
-  // (a synchronous call: the pinned staging words are free again on return)
-  const bool p2p_x = c->xch_mode == IQLHIP_XCH_P2P && c->world > 1;
-  if (p2p_x) {
-    HIPCHK(hipMemcpyAsync(c->xstatus_host, c->xstatus, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int rx = xch_poisoned(c, c->xstatus_host);
-    if (rx) return rx;
-  } else {
-    // the completion word comes from the last kernel of the call; the whole call's kernels precede it in the stream
-    // EXCEPT that the update's flag is stored by its first block — the ring write and the gather (first launch) are
-    // long done by then, and the pinned words read below were written before the flag (release)
-    rc = wait_done(c, done_val, st);
-    if (rc) return rc;
-  }
-  out[0] = c->on_loss_pin[0]; out[1] = c->on_loss_pin[1]; out[2] = c->on_loss_pin[2];
+  // (a synchronous call: the pinned staging words are free again on return.)  Without an exchange the completion word
+  // comes from the last kernel of the call; the whole call's kernels precede it in the stream EXCEPT that the update's
+  // flag is stored by its first block — the ring write and the gather (first launch) are long done by then, and the
+  // pinned words read below were written before the flag (release)
+  rc = sync_losses(c, done_val, st, out);
+  if (rc) return rc;
   if (act_state_host) memcpy(act_out_host, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
@@ -1662,18 +1664,14 @@ extern "C" int iqlhip_forward_backward(iqlhip_ctx* c, const iqlhip_batch* b, con
   if (rc) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
-  c->cont.valid = false;                 // (the staging buffers / keep-bits a following train_steps call might continue from)
   const float* xb_cur = nullptr;
   rc = stage_batch(c, b, st, &xb_cur);
   if (rc) return rc;
-  refresh_shadows(c, st);
-  if (c->drop_p > 0.f && !c->drop_inject) launch_dropmask(c, c->drop_seed, c->drop_step++, nullptr, 0, st);
-  StepParams p = make_step(c, b->rows, sc->inv_batch);
-  p.xb = xb_cur;
-  UpdParams u = make_upd(c, sc, b->rows, nullptr);
-  launch_fwd(c, p, st);
-  launch_bwd(c, p, st);
-  launch_flatten(c, u, grads_dev, false, st);
+  EagerStep e;
+  eager_begin(c, b->rows, sc, st, xb_cur, e);
+  launch_fwd(c, e.p, st);
+  launch_bwd(c, e.p, st);
+  launch_flatten(c, e.u, grads_dev, false, st);
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
 }
@@ -1691,24 +1689,21 @@ extern "C" int iqlhip_apply_update(iqlhip_ctx* c, const float* grads_dev, const 
 extern "C" int iqlhip_read_losses(iqlhip_ctx* c, float out[3], void* stream) {
   if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   float* h = c->losses_host;
-  const bool p2p = c->xch_mode == IQLHIP_XCH_P2P && c->world > 1;
   HIPCHK(hipMemcpyAsync(h, c->sc.losses, 4 * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  if (p2p) HIPCHK(hipMemcpyAsync(c->xstatus_host, c->xstatus, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
-  return p2p ? xch_poisoned(c, c->xstatus_host) : IQLHIP_OK;
+  const int rc = xch_status_after_sync(c, (hipStream_t)stream);
+  if (rc == IQLHIP_OK || rc == IQLHIP_EEXCHANGE) { out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; }      // (the stream was synchronised)
+  return rc;
 }
 
 extern "C" int iqlhip_read_loss_ring(iqlhip_ctx* c, float* out, int32_t n_steps, void* stream) {
   if (!c || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (n_steps < 1 || n_steps > c->ring_cap) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->ring_cap);
-  const bool p2p = c->xch_mode == IQLHIP_XCH_P2P && c->world > 1;
   const float* h = c->loss_ring;
-  if (p2p) HIPCHK(hipMemcpyAsync(c->xstatus_host, c->xstatus, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  const int rc = xch_status_after_sync(c, (hipStream_t)stream);
+  if (rc != IQLHIP_OK && rc != IQLHIP_EEXCHANGE) return rc;
   for (int k = 0; k < n_steps; ++k)
     for (int j = 0; j < 3; ++j) out[3 * k + j] = h[4 * (size_t)k + j];
-  return p2p ? xch_poisoned(c, c->xstatus_host) : IQLHIP_OK;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1830,31 +1825,21 @@ static int launch_call_setup(iqlhip_ctx* c, hipStream_t st, const ChunkHdr& h, i
   return IQLHIP_OK;
 }
 
-static int chunk_graph(iqlhip_ctx* c, const GraphKey& key, hipGraphExec_t* out, iqlhip_ctx::CachedGraph** slot) {
-  for (auto& g : c->graphs)
-    if (g.key == key) { g.stamp = ++c->graph_clock; *out = g.exec; if (slot) *slot = &g; return IQLHIP_OK; }
-  if (c->graphs.size() >= 12) {   // evict the least recently used — after its last replay has finished
-    size_t lru = 0;
-    for (size_t i = 1; i < c->graphs.size(); ++i) if (c->graphs[i].stamp < c->graphs[lru].stamp) lru = i;
-    if (c->graphs[lru].last) HIPCHK(hipStreamSynchronize(c->graphs[lru].last));
-    (void)hipGraphExecDestroy(c->graphs[lru].exec);
-    (void)hipGraphDestroy(c->graphs[lru].graph);
-    if (c->graphs[lru].work) (void)hipFree(c->graphs[lru].work);
-    c->graphs.erase(c->graphs.begin() + lru);
-  }
+// Capture and instantiate the chunk graph of g.key into g, member by member (a failure leaves the ones made so far).
+static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
+  const GraphKey& key = g.key;
   // the chunk's idle-work records: device memory written once, here (their content is part of what the key freezes)
-  IdleWork* work = nullptr;
   {
     std::vector<IdleWork> hw((size_t)key.K);
     fill_idle_work(c, hw.data(), key.rows, key.B, key.K);
-    HIPCHK(hipMalloc((void**)&work, hw.size() * sizeof(IdleWork)));
-    hipError_t e = hipMemcpy(work, hw.data(), hw.size() * sizeof(IdleWork), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(work); return fail(IQLHIP_EHIP, "chunk_graph: hipMemcpy: %s", hipGetErrorString(e)); }
+    HIPCHK(hipMalloc((void**)&g.work, hw.size() * sizeof(IdleWork)));
+    hipError_t e = hipMemcpy(g.work, hw.data(), hw.size() * sizeof(IdleWork), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(IQLHIP_EHIP, "chunk_graph: hipMemcpy: %s", hipGetErrorString(e));
   }
   hipStream_t cs = c->cap_stream;
   // (relaxed: a collective library may make calls during capture that the stricter modes forbid)
   hipError_t e = hipStreamBeginCapture(cs, key.xch == IQLHIP_XCH_RCCL ? hipStreamCaptureModeRelaxed : hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) { (void)hipFree(work); return fail(IQLHIP_EHIP, "hipStreamBeginCapture: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
   int rc = IQLHIP_OK;
   if (key.head) {        // placeholder arguments: every replay sets the real ones (grid included)
     ChunkHdr h0;
@@ -1865,27 +1850,38 @@ static int chunk_graph(iqlhip_ctx* c, const GraphKey& key, hipGraphExec_t* out, 
     if (hipLaunchKernel((const void*)iql_call_setup_kernel, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
       rc = fail(IQLHIP_EHIP, "capture of the set-up kernel failed");
   }
-  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, work);
-  hipGraph_t graph = nullptr;
-  e = hipStreamEndCapture(cs, &graph);
-  if (rc) { if (graph) (void)hipGraphDestroy(graph); (void)hipFree(work); return rc; }
-  if (e != hipSuccess) { (void)hipFree(work); return fail(IQLHIP_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e)); }
-  hipGraphExec_t gexec = nullptr;
-  e = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-  if (e != hipSuccess) { (void)hipGraphDestroy(graph); (void)hipFree(work); return fail(IQLHIP_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-  hipGraphNode_t setup_node = nullptr;
+  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work);
+  e = hipStreamEndCapture(cs, &g.graph);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+  e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+  if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
   if (key.head) {
     size_t n_root = 1;
-    e = hipGraphGetRootNodes(graph, &setup_node, &n_root);
+    e = hipGraphGetRootNodes(g.graph, &g.setup_node, &n_root);
     hipGraphNodeType ty = hipGraphNodeTypeEmpty;
-    if (e == hipSuccess && n_root == 1) e = hipGraphNodeGetType(setup_node, &ty);
-    if (e != hipSuccess || n_root != 1 || ty != hipGraphNodeTypeKernel) {
-      (void)hipGraphExecDestroy(gexec); (void)hipGraphDestroy(graph); (void)hipFree(work);
+    if (e == hipSuccess && n_root == 1) e = hipGraphNodeGetType(g.setup_node, &ty);
+    if (e != hipSuccess || n_root != 1 || ty != hipGraphNodeTypeKernel)
       return fail(IQLHIP_EHIP, "head chunk graph: no single kernel root node");
-    }
   }
-  c->graphs.push_back({key, graph, gexec, ++c->graph_clock, nullptr, work, setup_node});
-  *out = gexec;
+  return IQLHIP_OK;
+}
+
+static int chunk_graph(iqlhip_ctx* c, const GraphKey& key, hipGraphExec_t* out, iqlhip_ctx::CachedGraph** slot) {
+  for (auto& g : c->graphs)
+    if (g.key == key) { g.stamp = ++c->graph_clock; *out = g.exec; if (slot) *slot = &g; return IQLHIP_OK; }
+  if (c->graphs.size() >= 12) {   // evict the least recently used — after its last replay has finished
+    size_t lru = 0;
+    for (size_t i = 1; i < c->graphs.size(); ++i) if (c->graphs[i].stamp < c->graphs[lru].stamp) lru = i;
+    if (c->graphs[lru].last) HIPCHK(hipStreamSynchronize(c->graphs[lru].last));
+    free_graph(c->graphs[lru]);
+    c->graphs.erase(c->graphs.begin() + lru);
+  }
+  iqlhip_ctx::CachedGraph ng{key, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  if (int rc = build_chunk_graph(c, ng)) { free_graph(ng); return rc; }      // (whatever of it was made; the message stays)
+  ng.stamp = ++c->graph_clock;
+  c->graphs.push_back(ng);
+  *out = ng.exec;
   if (slot) *slot = &c->graphs.back();
   return IQLHIP_OK;
 }
@@ -1979,9 +1975,7 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
                                           void* stream) {
   int rc = check_train_args(c, rows_dev, ld, B);
   if (rc) return rc;
-  if ((rc = stats_check(c, B))) return rc;
-  if ((rc = inject_check(c))) return rc;
-  note_stream(c, stream);
+  if ((rc = step_entry(c, B, stream, /*multi_step=*/true))) return rc;
   DevGuard guard(c->device);
   HIPCHK(hipDeviceSynchronize());       // a one-off set-up call: ordered after everything queued on any stream
   c->cont.valid = false;
@@ -1995,7 +1989,7 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
   // and restored after it; it reads row 0 only (size = 1); scratch, loss words and ring are transient anyway.  Under
   // data parallelism the rehearsal runs the exchange too — every rank must call prepare (the same number of times).
   const size_t np_b = (size_t)c->L.n_params * sizeof(float), nt_b = (size_t)c->L.n_target * sizeof(float);
-  if (!c->prep_save) HIPCHK(hipMalloc((void**)&c->prep_save, 3 * np_b + nt_b));     // (arena sizes are fixed per context)
+  if (!c->prep_save) HIPCHK(c->own.dev(&c->prep_save, 3 * np_b + nt_b));     // (arena sizes are fixed per context)
   char* const save = c->prep_save;
   auto copy_all = [&](bool restore) -> hipError_t {
     float* arenas[4] = {c->params, c->m, c->v, c->target};
@@ -2081,9 +2075,7 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
   if (rc) return rc;
   if (K < 1 || K > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
   if (size < 1) return fail(IQLHIP_EINVAL, "empty buffer");
-  if ((rc = stats_check(c, B))) return rc;
-  if ((rc = inject_check(c))) return rc;
-  note_stream(c, stream);
+  if ((rc = step_entry(c, B, stream, /*multi_step=*/true))) return rc;
   double tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (g_trace) tr_t[0] = now_us();
   DevGuard guard(c->device);
@@ -2392,6 +2384,8 @@ struct SampleStage {
   int device = -1;
   int64_t cap = 0;
   enum { SLOTS = 8 };
+  Owned own;                             // ack and arrivals, then (from slots_mark on) the index slots: re-made when they grow
+  size_t slots_mark = 0;
   int64_t* host[SLOTS] = {};             // pinned, host-mapped index slots the gather kernel reads in place
   unsigned long long want[SLOTS] = {};   // the call number whose kernel must have acknowledged the slot before reuse
   hipStream_t stream[SLOTS] = {};
@@ -2400,7 +2394,8 @@ struct SampleStage {
   unsigned long long seq = 0;
   int slot = 0;
 };
-SampleStage g_stage[16];
+// (process lifetime: never destroyed, so nothing is freed behind the runtime's back at exit)
+SampleStage* const g_stage = new SampleStage[16];
 }  // namespace
 
 // ReplayBuffer.sample in one call from ORDINARY host memory (the array np.random.randint returned): the indices are
@@ -2425,19 +2420,28 @@ extern "C" int iqlhip_rows_sample_packed(const float* rows_dev, int64_t ld, int6
   SampleStage& sg = g_stage[dev];
   if (sg.cap < n) {
     HIPCHK(hipDeviceSynchronize());          // nothing may still read the old staging
-    for (int i = 0; i < SampleStage::SLOTS; ++i) if (sg.host[i]) { (void)hipHostFree(sg.host[i]); sg.host[i] = nullptr; }
-    sg.cap = std::max<int64_t>(n, 1024);
-    for (int i = 0; i < SampleStage::SLOTS; ++i) {
-      HIPCHK(hipHostMalloc((void**)&sg.host[i], (size_t)sg.cap * sizeof(int64_t), hipHostMallocDefault));
-      sg.want[i] = 0;
-    }
     if (!sg.ack) {
-      HIPCHK(hipHostMalloc((void**)&sg.ack, SampleStage::SLOTS * sizeof(unsigned long long), hipHostMallocDefault));
-      memset(sg.ack, 0, SampleStage::SLOTS * sizeof(unsigned long long));
-      HIPCHK(hipMalloc((void**)&sg.arrivals, 64));
-      HIPCHK(hipMemset(sg.arrivals, 0, 64));
+      const int rc = all_or_nothing(sg.own, [&]() -> int {
+        HIPCHK(sg.own.pin(&sg.ack, SampleStage::SLOTS * sizeof(unsigned long long), /*zero=*/true));
+        HIPCHK(sg.own.dev(&sg.arrivals, 64, 0));
+        return IQLHIP_OK;
+      });
+      if (rc) return rc;
       HIPCHK(hipDeviceSynchronize());
+      sg.slots_mark = sg.own.mark();
     }
+    sg.own.rollback(sg.slots_mark);          // (the old slots)
+    sg.cap = 0;
+    const int64_t cap = std::max<int64_t>(n, 1024);
+    const int rc = all_or_nothing(sg.own, [&]() -> int {
+      for (int i = 0; i < SampleStage::SLOTS; ++i) {
+        HIPCHK(sg.own.pin(&sg.host[i], (size_t)cap * sizeof(int64_t)));
+        sg.want[i] = 0;
+      }
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
+    sg.cap = cap;
     sg.device = dev;
   }
   const int k = sg.slot;
@@ -2534,7 +2538,6 @@ extern "C" int iqlhip_debug_time_kernel(iqlhip_ctx* c, const iqlhip_batch* b, in
   int rc = check_batch(c, b);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  c->cont.valid = false;
   const float* xb_cur = nullptr;
   rc = stage_batch(c, b, st, &xb_cur);
   if (rc) return rc;
@@ -2542,14 +2545,15 @@ extern "C" int iqlhip_debug_time_kernel(iqlhip_ctx* c, const iqlhip_batch* b, in
   memset(&sc, 0, sizeof sc);
   sc.bc2_sqrt[0] = sc.bc2_sqrt[1] = sc.bc2_sqrt[2] = 1.f;
   sc.beta2 = 1.f; sc.eps = 1e-8f; sc.grad_scale = 1.f; sc.inv_batch = 1.f / b->rows;
-  StepParams p = make_step(c, b->rows, sc.inv_batch);
-  p.xb = xb_cur;
-  UpdParams u = make_upd(c, &sc, b->rows, nullptr);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Owned events;                          // (released on every way out; declared behind the two it nulls)
+  HIPCHK(events.event(&e0, hipEventDefault));
+  HIPCHK(events.event(&e1, hipEventDefault));
+  EagerStep e;
+  eager_begin(c, b->rows, &sc, st, xb_cur, e, /*draw=*/false);
+  const StepParams& p = e.p;
+  UpdParams& u = e.u;
   u.tau = 0.f; u.one_minus_tau = 1.f;
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0));
-  HIPCHK(hipEventCreate(&e1));
-  refresh_shadows(c, st);
   for (int w = 0; w < 3; ++w) { launch_fwd(c, p, st); launch_bwd(c, p, st); }
   HIPCHK(hipEventRecord(e0, st));
   c->lb_bwd_part = (which == 4) ? 1 : ((which == 5) ? 2 : 0);
@@ -2564,8 +2568,6 @@ extern "C" int iqlhip_debug_time_kernel(iqlhip_ctx* c, const iqlhip_batch* b, in
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, e0, e1));
   *avg_us = ms * 1e3f / repeat;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return IQLHIP_OK;
 }
 
@@ -2626,13 +2628,21 @@ struct Staging {
   template <class T> static T* at(char* base, Section<T> s) { return (T*)(base + s.off); }
   template <class T> T* host(Section<T> s) const { return at(pin, s); }
   template <class T> const T* device(Section<T> s) const { return at(dev, s); }
-  int alloc() {      // (the pinned copy starts zeroed: records are uploaded — and compared — whole, padding included)
-    HIPCHK(hipMalloc((void**)&dev, bytes));
-    HIPCHK(hipHostMalloc((void**)&pin, bytes, hipHostMallocDefault));
-    memset(pin, 0, bytes);
+  int alloc(Owned& own) {      // (the pinned copy starts zeroed: records are uploaded — and compared — whole, padding included)
+    HIPCHK(own.dev(&dev, bytes));
+    HIPCHK(own.pin(&pin, bytes, /*zero=*/true));
     return IQLHIP_OK;
   }
-  void free() { if (dev) (void)hipFree(dev); if (pin) (void)hipHostFree(pin); }
+};
+// The per-member records of the opt-in features that look at a step's gradient, as they lie in a staging: the
+// statistics records, the clip records, and the records the block-partial launch runs under when some member clips.
+struct AuxSections {
+  Section<GroupStatsRec> srecs; Section<GroupClipRec> crecs; Section<GroupStatsRec> gqrecs;
+  void add(Staging& s, size_t k) {
+    srecs = s.add<GroupStatsRec>(k);
+    crecs = s.add<GroupClipRec>(k);
+    gqrecs = s.add<GroupStatsRec>(k);
+  }
 };
 
 struct iqlhip_group {
@@ -2640,14 +2650,14 @@ struct iqlhip_group {
   int device = 0;
   int flags = 0;                      // IQLHIP_GROUP_*
   iqlhip_ctx* m[IQLHIP_MAX_GROUP] = {};
+  Owned own;                          // every buffer and event of the group (the members own theirs)
   // iqlhip_group_step / iqlhip_group_train_steps: the agents' records, the IQLHIP_GROUP_DROPOUT records (no rows
-  // without the flag) and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS]
+  // without the flag), the statistics / clip records and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS] — the tables
+  // last: group_upload copies up to their used rows
   Staging train;
-  Section<GroupRec> recs; Section<GroupDropRec> drops; Section<GroupStatsRec> srecs; Section<iqlhip_step_scalars> tabs;
-  // gradient clipping of the members that enabled it (iqlhip_set_grad_clip): their records, and the records the block
-  // partial launch runs under when some member clips (enabled = statistics or clipping); clip_ones: three floats of
-  // 1.0f, the coefficients a member without clipping reads (allocated by the first call with a clipping member)
-  Section<GroupClipRec> crecs; Section<GroupStatsRec> gqrecs;
+  Section<GroupRec> recs; Section<GroupDropRec> drops; AuxSections aux; Section<iqlhip_step_scalars> tabs;
+  // clip_ones: three floats of 1.0f, the coefficients a member without clipping reads (allocated by the first call
+  // with a clipping member)
   float* clip_ones = nullptr;
   // per-step statistics of the members that enabled them (iqlhip_set_step_stats): [k][IQLHIP_GROUP_MAX_STEPS][IQLHIP_N_STATS],
   // allocated by the first call with such a member; stats_mask: who had them on in the last call
@@ -2665,8 +2675,7 @@ struct iqlhip_group {
   Staging on;
   Section<GroupRec> on_recs; Section<StepParams> on_aps; Section<GroupOnlineRec> on_gathers; Section<GroupActRec> on_fins;
   Section<GroupDropRec> on_drops; Section<ActDropRec> on_adrops; Section<iqlhip_step_scalars> on_tabs;
-  Section<GroupStatsRec> on_srecs;
-  Section<GroupClipRec> on_crecs; Section<GroupStatsRec> on_gqrecs;
+  AuxSections on_aux;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
   // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in act_host (the
@@ -2718,17 +2727,7 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   if (!g) return fail(IQLHIP_EINVAL, "NULL group");
   DevGuard guard(g->device);
   (void)hipDeviceSynchronize();       // a group call may still be running on some stream
-  g->train.free();
-  g->on.free();
-  g->act.free();
-  if (g->ring_dev) (void)hipFree(g->ring_dev);
-  if (g->ring_pin) (void)hipHostFree(g->ring_pin);
-  if (g->stats_ring_dev) (void)hipFree(g->stats_ring_dev);
-  if (g->stats_ring_pin) (void)hipHostFree(g->stats_ring_pin);
-  if (g->clip_ones) (void)hipFree(g->clip_ones);
-  if (g->up_done) (void)hipEventDestroy(g->up_done);
-  if (g->done_pin) (void)hipHostFree(g->done_pin);
-  if (g->act_up) (void)hipEventDestroy(g->act_up);
+  g->own.release_all();
   delete g;
   return IQLHIP_OK;
 }
@@ -2748,9 +2747,7 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     const size_t n_drop = (flags & IQLHIP_GROUP_DROPOUT) ? k : 0;      // (without the flag: the layouts of a plain group)
     g->recs = g->train.add<GroupRec>(k);
     g->drops = g->train.add<GroupDropRec>(n_drop);
-    g->srecs = g->train.add<GroupStatsRec>(k);
-    g->crecs = g->train.add<GroupClipRec>(k);      // (in front of the tables: group_upload copies up to their used rows)
-    g->gqrecs = g->train.add<GroupStatsRec>(k);
+    g->aux.add(g->train, k);
     g->tabs = g->train.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
     g->on_recs = g->on.add<GroupRec>(k);
     g->on_aps = g->on.add<StepParams>(k);
@@ -2759,25 +2756,21 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->on_drops = g->on.add<GroupDropRec>(n_drop);
     g->on_adrops = g->on.add<ActDropRec>(n_drop);
     g->on_tabs = g->on.add<iqlhip_step_scalars>(k);
-    g->on_srecs = g->on.add<GroupStatsRec>(k);
-    g->on_crecs = g->on.add<GroupClipRec>(k);
-    g->on_gqrecs = g->on.add<GroupStatsRec>(k);
+    g->on_aux.add(g->on, k);
     g->act_packs = g->act.add<GroupPackRec>(k);
     g->act_ps = g->act.add<StepParams>(k);
     g->act_fins = g->act.add<GroupActRowsRec>(k);
     g->act_drops = g->act.add<ActDropRec>(n_drop);
     for (Staging* s : {&g->train, &g->on, &g->act})
-      if (int rc_s = s->alloc()) return rc_s;
+      if (int rc_s = s->alloc(g->own)) return rc_s;
     g->act_host.assign(g->act.bytes, 0);
     g->act_last.assign(g->act.bytes, 1);     // (differs from any first call's records: the first call uploads)
     const size_t ring = (size_t)k * IQLHIP_GROUP_MAX_STEPS * 4 * sizeof(float);
-    HIPCHK(hipMalloc((void**)&g->ring_dev, ring));
-    HIPCHK(hipMemset(g->ring_dev, 0, ring));
-    HIPCHK(hipHostMalloc((void**)&g->ring_pin, ring, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&g->done_pin, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    memset(g->done_pin, 0, 8 * sizeof(unsigned long long));
-    HIPCHK(hipEventCreateWithFlags(&g->up_done, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&g->act_up, hipEventDisableTiming));
+    HIPCHK(g->own.dev(&g->ring_dev, ring, 0));
+    HIPCHK(g->own.pin(&g->ring_pin, ring));
+    HIPCHK(g->own.pin(&g->done_pin, 8 * sizeof(unsigned long long), /*zero=*/true));
+    HIPCHK(g->own.event(&g->up_done, hipEventDisableTiming));
+    HIPCHK(g->own.event(&g->act_up, hipEventDisableTiming));
     const iqlhip_ctx* c = members[0];
     int rc_a = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_group_kernel(m & 1, m & 2, m & 4); });
     if (!rc_a) rc_a = set_max_lds(2, c->lds_bwd, [](unsigned m) { return bwd_group_kernel(m & 1, m & 2); });
@@ -2859,7 +2852,7 @@ static int group_check_call(iqlhip_group* g, const int32_t* rows) {
     if (g->m[0]->precision == 1 && rows[i] > LB_MIN_ROWS)
       return fail(IQLHIP_EUNSUPPORTED, "bf16 groups take batches of at most %d rows (the large-batch kernels have no group form)", LB_MIN_ROWS);
   for (int i = 0; i < g->k; ++i)
-    if ((rc = stats_check(g->m[i], rows[i]))) return rc;
+    if ((rc = optional_features_check(g->m[i], rows[i]))) return rc;
   return IQLHIP_OK;
 }
 
@@ -2949,44 +2942,47 @@ static int group_upload(iqlhip_group* g, int n, hipStream_t st) {
 static iqlhip_step_scalars* group_tab(const iqlhip_group* g, int i) { return g->train.host(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
 static const iqlhip_step_scalars* group_sched(const iqlhip_group* g, int i) { return g->train.device(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
 
-// Per-step statistics in a group: one record per member (indexed like the GroupRecs; enabled = the member has them on)
-// built from the member's step record, its statistics going to row (member, step) of the group's statistics ring.
-// Returns whether any member has them on (none: nothing is launched); remembers who in stats_mask.
-static int group_stats_records(iqlhip_group* g, GroupStatsRec* sr, const GroupRec* recs_host, bool* any) {
-  *any = false;
-  for (int i = 0; i < g->k; ++i) *any = *any || g->m[i]->stats_on;
-  if (*any && !g->stats_ring_dev) {
-    const size_t ring = (size_t)g->k * IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS * sizeof(float);
-    HIPCHK(hipMalloc((void**)&g->stats_ring_dev, ring));
-    HIPCHK(hipMemset(g->stats_ring_dev, 0, ring));
-    HIPCHK(hipHostMalloc((void**)&g->stats_ring_pin, ring, hipHostMallocDefault));
+// The device copies of a call's per-member statistics / clip records; nullptr: no member has the feature on.
+struct GroupAux { const GroupStatsRec* srecs = nullptr; const GroupClipRec* crecs = nullptr; const GroupStatsRec* gqrecs = nullptr; };
+// Build them in staging `s` at sections `x` from the members' step records (host side) and point `aux` at their device
+// copies.  Statistics: enabled = the member has them on, its rows going to (member, step) of the group's statistics
+// ring; stats_mask remembers who.  Clipping: a member with it off reads the group's 1.0f coefficients; the
+// block-partial launch's records are enabled for a member with either feature.  A feature no member has on leaves its
+// records alone (nothing of it is launched).
+static int group_aux(iqlhip_group* g, const Staging& s, const AuxSections& x, const GroupRec* recs_host, GroupAux* aux) {
+  bool stats = false, clip = false;
+  for (int i = 0; i < g->k; ++i) { stats = stats || g->m[i]->stats_on; clip = clip || g->m[i]->clip_on; }
+  if (stats && !g->stats_ring_dev) {
+    const int rc = all_or_nothing(g->own, [&]() -> int {
+      const size_t ring = (size_t)g->k * IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS * sizeof(float);
+      HIPCHK(g->own.dev(&g->stats_ring_dev, ring, 0));
+      HIPCHK(g->own.pin(&g->stats_ring_pin, ring));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
   }
+  if (clip && !g->clip_ones) {
+    const int rc = all_or_nothing(g->own, [&]() -> int {
+      const float ones[4] = {1.f, 1.f, 1.f, 1.f};
+      HIPCHK(g->own.dev(&g->clip_ones, sizeof ones));
+      HIPCHK(hipMemcpy(g->clip_ones, ones, sizeof ones, hipMemcpyHostToDevice));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
+  }
+  GroupStatsRec* sr = s.host(x.srecs);
+  GroupClipRec* cr = s.host(x.crecs);
+  GroupStatsRec* gq = s.host(x.gqrecs);
   for (int i = 0; i < g->k; ++i) {
     const iqlhip_ctx* c = g->m[i];
     memset(&sr[i], 0, sizeof sr[i]);
     g->stats_mask[i] = c->stats_on;
-    if (!c->stats_on) continue;
-    sr[i].a = make_stats(c, recs_host[i].p, g->stats_ring_dev + (size_t)i * IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS, 0,
-                         IQLHIP_GROUP_MAX_STEPS, nullptr);
-    sr[i].enabled = 1;
-  }
-  return IQLHIP_OK;
-}
-
-// Gradient clipping in a group: one record per member (indexed like the GroupRecs) and the block-partial launch's
-// records (enabled = the member has statistics or clipping on).  A member with clipping off reads the group's 1.0f
-// coefficients.  Returns whether any member clips (none: the launches of a group without the feature).
-static int group_clip_records(iqlhip_group* g, GroupClipRec* cr, GroupStatsRec* gq, bool* any) {
-  *any = false;
-  for (int i = 0; i < g->k; ++i) *any = *any || g->m[i]->clip_on;
-  if (!*any) return IQLHIP_OK;
-  if (!g->clip_ones) {
-    const float ones[4] = {1.f, 1.f, 1.f, 1.f};
-    HIPCHK(hipMalloc((void**)&g->clip_ones, sizeof ones));
-    HIPCHK(hipMemcpy(g->clip_ones, ones, sizeof ones, hipMemcpyHostToDevice));
-  }
-  for (int i = 0; i < g->k; ++i) {
-    const iqlhip_ctx* c = g->m[i];
+    if (c->stats_on) {
+      sr[i].a = make_stats(c, recs_host[i].p, g->stats_ring_dev + (size_t)i * IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS, 0,
+                           IQLHIP_GROUP_MAX_STEPS, nullptr);
+      sr[i].enabled = 1;
+    }
+    if (!clip) continue;
     memset(&cr[i], 0, sizeof cr[i]);
     memset(&gq[i], 0, sizeof gq[i]);
     cr[i].coef_rd = g->clip_ones;
@@ -3000,11 +2996,11 @@ static int group_clip_records(iqlhip_group* g, GroupClipRec* cr, GroupStatsRec* 
       gq[i].enabled = 1;
     }
   }
+  *aux = GroupAux();
+  if (stats) aux->srecs = s.device(x.srecs);
+  if (clip) { aux->crecs = s.device(x.crecs); aux->gqrecs = s.device(x.gqrecs); }
   return IQLHIP_OK;
 }
-
-// The device copies of a call's per-member statistics / clip records; nullptr: no member has the feature on.
-struct GroupAux { const GroupStatsRec* srecs = nullptr; const GroupClipRec* crecs = nullptr; const GroupStatsRec* gqrecs = nullptr; };
 static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st,
                               const GroupAux& aux) {
   const GroupStatsRec* srecs = aux.srecs;
@@ -3035,7 +3031,7 @@ static int group_losses_out(iqlhip_group* g, float* out, int n, hipStream_t st) 
   if (!out) return IQLHIP_OK;
   const size_t row = (size_t)IQLHIP_GROUP_MAX_STEPS * 4;
   for (int i = 0; i < g->k; ++i)
-    HIPCHK(hipMemcpyAsync(g->ring_pin + i * row, g->ring_dev + i * row, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (int rc = read_back(nullptr, g->ring_pin + i * row, g->ring_dev + i * row, (size_t)n * 4 * sizeof(float), st, /*sync=*/false)) return rc;
   HIPCHK(hipStreamSynchronize(st));
   for (int i = 0; i < g->k; ++i)
     for (int s = 0; s < n; ++s)
@@ -3075,15 +3071,8 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
     group_tab(g, i)[0] = sc[i];
   }
   const int n_draw = group_drop_records_packed(g, g->train.host(g->drops), rows.v);
-  bool stats = false;
-  rc = group_stats_records(g, g->train.host(g->srecs), g->train.host(g->recs), &stats);
-  if (rc) return rc;
-  bool clip = false;
-  rc = group_clip_records(g, g->train.host(g->crecs), g->train.host(g->gqrecs), &clip);
-  if (rc) return rc;
   GroupAux aux;
-  if (stats) aux.srecs = g->train.device(g->srecs);
-  if (clip) { aux.crecs = g->train.device(g->crecs); aux.gqrecs = g->train.device(g->gqrecs); }
+  if ((rc = group_aux(g, g->train, g->aux, g->train.host(g->recs), &aux))) return rc;
   rc = group_upload(g, 1, st);
   if (rc) return rc;
   group_launch_dropmask(g, g->train.device(g->drops), n_draw, q.max_rows, st);
@@ -3141,15 +3130,8 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
       draws = draws || d[i].active;
     }
   }
-  bool stats = false;
-  rc = group_stats_records(g, g->train.host(g->srecs), g->train.host(g->recs), &stats);
-  if (rc) return rc;
-  bool clip = false;
-  rc = group_clip_records(g, g->train.host(g->crecs), g->train.host(g->gqrecs), &clip);
-  if (rc) return rc;
   GroupAux aux;
-  if (stats) aux.srecs = g->train.device(g->srecs);
-  if (clip) { aux.crecs = g->train.device(g->crecs); aux.gqrecs = g->train.device(g->gqrecs); }
+  if ((rc = group_aux(g, g->train, g->aux, g->train.host(g->recs), &aux))) return rc;
   rc = group_upload(g, n, st);
   if (rc) return rc;
   const iqlhip_ctx* c0 = g->m[0];
@@ -3200,8 +3182,8 @@ extern "C" int iqlhip_group_read_step_stats(iqlhip_group* g, float* out, int32_t
   const size_t row = (size_t)IQLHIP_GROUP_MAX_STEPS * IQLHIP_N_STATS;
   for (int i = 0; i < g->k; ++i)
     if (g->stats_mask[i])
-      HIPCHK(hipMemcpyAsync(g->stats_ring_pin + i * row, g->stats_ring_dev + i * row, (size_t)n * IQLHIP_N_STATS * sizeof(float),
-                            hipMemcpyDeviceToHost, st));
+      if (int rc = read_back(nullptr, g->stats_ring_pin + i * row, g->stats_ring_dev + i * row,
+                             (size_t)n * IQLHIP_N_STATS * sizeof(float), st, /*sync=*/false)) return rc;
   HIPCHK(hipStreamSynchronize(st));
   for (int s = 0; s < n; ++s)
     for (int i = 0; i < g->k; ++i)
@@ -3291,15 +3273,8 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
     ++n_req;
   }
   const int n_draw = group_drop_records_packed(g, on.host(g->on_drops), n);
-  bool stats = false;
-  rc = group_stats_records(g, on.host(g->on_srecs), recs, &stats);
-  if (rc) return rc;
-  bool clip = false;
-  rc = group_clip_records(g, on.host(g->on_crecs), on.host(g->on_gqrecs), &clip);
-  if (rc) return rc;
   GroupAux aux;
-  if (stats) aux.srecs = on.device(g->on_srecs);
-  if (clip) { aux.crecs = on.device(g->on_crecs); aux.gqrecs = on.device(g->on_gqrecs); }
+  if ((rc = group_aux(g, on, g->on_aux, recs, &aux))) return rc;
   // (a synchronous call: the previous one's upload has been read long ago)
   HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((q.max_rows * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
