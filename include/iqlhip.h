@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 330          /* 0.3.3 */
+#define IQLHIP_VERSION 340          /* 0.3.4 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -197,6 +197,45 @@ int iqlhip_online_step(iqlhip_ctx* ctx, float* rows_dev, int64_t ld, int64_t cap
                        const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
                        float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
                        float* act_out_host, void* stream);
+
+/* ---- mixed offline / online batches -------------------------------------------------------------------------
+ * The batch of an online fine-tuning step mixed from two buffers, as the reference's Cal-QL loop builds it
+ * (algorithms/finetune/cal_ql.py: vstack(offline_buffer.sample(n_off), online_buffer.sample(n_on))): batch rows
+ * [0, n_off) come from the offline buffer, rows [n_off, n_off + n) from the online ring.  1 <= n_off and 1 <= n; both
+ * buffers have the same row stride and are different allocations.
+ *
+ * iqlhip_online_step_mixed: iqlhip_online_step's arguments and meaning — rows_dev / capacity / pointer / row_host are
+ * the online ring and its new transition, idx_host[0..n) the online indices, drawn over the ring's size AFTER the insert
+ * (an index equal to `pointer` reads the new row) — plus the offline part: rows_off_dev (size_off rows, read only) and
+ * idx_off_host[0..n_off).  The host draws the offline indices FIRST, then the online ones (the order of the two
+ * sample() calls).  Both arrays are range-checked on the host before anything is launched (IQLHIP_EINDEX; online
+ * indices against `capacity`, offline ones against size_off).  One step on n_off + n <= max_batch rows; sc->inv_batch
+ * is 1 / (n_off + n).  Bit for bit what add_transition, the two gathers, a concatenation and iqlhip_step give.
+ * IQLHIP_EUNSUPPORTED with a data-parallel exchange attached and for bf16 batches of more than 512 rows, like
+ * iqlhip_train_steps_mixed, before anything is launched. */
+int iqlhip_online_step_mixed(iqlhip_ctx* ctx, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                             const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
+                             float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
+                             float* act_out_host, void* stream, const float* rows_off_dev, int64_t size_off,
+                             const int64_t* idx_off_host, int32_t n_off);
+
+/* iqlhip_train_steps_mixed: iqlhip_train_steps with every step's batch mixed the same way.  The index stream is
+ * iqlhip_train_steps' own — index j = k * batch_rows + r of the call (step k, batch row r) takes the 64 random bits of
+ * counter stream_offset + j / 2, word pair j & 1, under `seed`, and a call consumes ceil(n_steps * batch_rows / 2)
+ * counters whatever n_off is — and only the mapping depends on the row: r < n_off gives floor(bits * size_off / 2^64) into
+ * rows_off_dev, r >= n_off gives floor(bits * size_on / 2^64) into rows_on_dev.  1 <= n_off <= batch_rows - 1.  Both sizes
+ * are per-call values (device header words), so the online ring may grow between calls; the captured chunk graphs
+ * depend on the two row pointers, batch_rows and n_off.  A mixed call neither continues a previous call's stream nor
+ * leaves rows staged for the next one (there is no flags argument): the plain call that follows gathers its own step 0.
+ * IQLHIP_EUNSUPPORTED with a data-parallel exchange attached, for bf16 batches of more than 512 rows, and with injected
+ * keep-bits pending.  Losses and statistics come from the rings as after iqlhip_train_steps.
+ * iqlhip_train_steps_mixed_prepare: iqlhip_train_steps_prepare for the chunk graphs of such calls. */
+int iqlhip_train_steps_mixed(iqlhip_ctx* ctx, const float* rows_off_dev, int64_t size_off, const float* rows_on_dev,
+                             int64_t size_on, int64_t ld, int32_t batch_rows, int32_t n_off,
+                             const iqlhip_step_scalars* sc, int32_t n_steps, uint64_t seed, uint64_t stream_offset,
+                             void* stream);
+int iqlhip_train_steps_mixed_prepare(iqlhip_ctx* ctx, const float* rows_off_dev, const float* rows_on_dev, int64_t ld,
+                                     int32_t batch_rows, int32_t n_off, float inv_batch, void* stream);
 
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is

@@ -142,11 +142,19 @@ struct GraphKey {
   int head = 0;       // the chunk a call starts with: its graph begins with the call's set-up kernel (arguments set per replay)
   int stats = 0;      // captured with the statistics launches (iqlhip_set_step_stats): never replayed under the other setting
   int clip = 0;       // captured with the clip launches and the CLIP update kernel (iqlhip_set_grad_clip): likewise
+  // two-source chunks (iqlhip_train_steps_mixed; rows = the offline buffer): the online buffer and the batch rows that
+  // are not its.  rows_on == nullptr: a plain chunk — never replayed for a mixed call on the same rows, nor the reverse
+  const float* rows_on = nullptr;
+  int32_t n_off = 0;
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
-           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip;
+           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip &&
+           rows_on == o.rows_on && n_off == o.n_off;
   }
 };
+// The second source of a mixed call, handed down to whatever forms a key, a set-up launch or an idle-work record
+// (nullptr everywhere: a plain call).  The online size is not here: it travels in the header (HDR_SIZE_ON).
+struct MixSrc { const float* rows_on; int n_off; };
 
 // The few RCCL entry points the in-stream all-reduce needs, resolved at run time from the librccl.so.1 the process
 // already has (PyTorch-ROCm brings one) or can load — the library has no link-time dependency on RCCL.
@@ -212,6 +220,7 @@ struct iqlhip_ctx {
   unsigned long long sched_want[4] = {0, 0, 0, 0};
   unsigned long long call_seq = 0;
   unsigned* setup_arrivals = nullptr;           // device: block counter of iql_call_setup_kernel
+  bool mixed_lds_set = false;                   // the mixed forward instantiations have their dynamic-LDS limit (check_mixed_args)
   char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (freeing it at the end of prepare
                                                 //   idles the GPU right in front of the caller's first steps)
   hipStream_t sched_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // (the stream a slot's reader was queued on)
@@ -824,7 +833,9 @@ static UpdParams make_upd(const iqlhip_ctx* c, const iqlhip_step_scalars* sc, in
 
 static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c->n_cus) ? c->lds_fwd_solo : c->lds_fwd; }
 
-static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
+static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);     // (end of file)
+static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, bool mixed = false) {
+  if (mixed) return launch_fwd_mixed_grid(c, p, nb, st);
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
   // (policy inference — iqlhip_actor_forward — has its own instantiations)
@@ -845,7 +856,7 @@ static int fwd_spb_l2(const iqlhip_ctx* c, int n_rt) {
 // Blocks of a forward grid (per agent) over n_rt row tiles at 2^l2 slices per block.  (Full-width blocks: each XCD of
 // a net's pair takes the row tiles of one parity — iql_fwd_kernel's block map.)
 static int fwd_blocks(int n_rt, int l2) { return (l2 == 2) ? 8 * 2 * ((n_rt + 1) / 2) : 8 * n_rt * (NSPLIT >> l2); }
-static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st) {
+static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st, bool mixed = false) {
   StepParams p = p_in;
   if (p.only_inst < 0 && use_lb(c, p.rows)) {
     const LbArgs a = lb_args(c, p.rows);
@@ -866,7 +877,7 @@ static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
   }
   const int n_rt = (p.rows + RT_ROWS - 1) / RT_ROWS;
   p.spb_l2 = fwd_spb_l2(c, n_rt);
-  launch_fwd_grid(c, p, fwd_blocks(n_rt, p.spb_l2), st);
+  launch_fwd_grid(c, p, fwd_blocks(n_rt, p.spb_l2), st, mixed);
 }
 // Column slices per (b) block of the backward (log2): one while the whole grid — 4 nets x (32 dW1 tiles per 256-row
 // chunk + 4 slices per row tile) — is at most two rounds of the chip (up to 512 rows: measured equal or better), else 4:
@@ -1406,9 +1417,9 @@ static XchParams make_xch(const iqlhip_ctx* c, bool from_hdr) {
 // `k` = position inside the chunk (selects the P2P buffer together with `parity`, and the flag value hdr[XSTEP]+k+1).
 // `sa` (statistics enabled): the two statistics launches between the backward and the update — after the last reader
 // of `heads`, before the update kernel, which is the last reader of the slabs and, in a chunk, moves the header word
-// the ring slot is formed from.
+// the ring slot is formed from.  `mixed`: a step of a two-source chunk (its forward is iql_fwd_mixed_kernel).
 static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int mode, int parity, int k, bool from_hdr,
-                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr) {
+                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, bool mixed = false) {
   StepParams p = p_in;
   const int buf = (parity + k) & 1;
   // P2P with batches of <= 256 rows: no flatten kernel.  The backward writes its chunk slab (= the w1 / b1 / w2 / b2 /
@@ -1422,7 +1433,7 @@ static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int 
     for (int n = 0; n < 4; ++n) p.sc.slab_b_off[n] = c->xslab_b_off[n];
     p.sc.loss_parts = (float*)(c->xblk + c->xloss_off[buf]);
   }
-  launch_fwd(c, p, st);
+  launch_fwd(c, p, st, mixed);
   if (ev) HIPCHK(hipEventRecord(ev[1], st));
   launch_bwd(c, p, st);
   if (ev) HIPCHK(hipEventRecord(ev[2], st));
@@ -1604,31 +1615,43 @@ static int actor_forward_impl(iqlhip_ctx* c, const float* states_dev, int64_t ld
 // One iteration of the online loop's device work (algorithms/finetune/iql.py:741-773: add_transition -> sample ->
 // train) in ONE call and four launches: ring write + gather straight from pinned host words, forward, backward, update
 // with the losses landing in pinned host words; then one stream synchronisation.
-extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
-                                  const float* row_host, const int64_t* idx_host, int32_t n,
-                                  const iqlhip_step_scalars* sc, float out[3], const float* act_state_host,
-                                  float max_action, uint64_t act_seed, float* act_out_host, void* stream) {
+// iqlhip_online_step (rows_off_dev == nullptr, n_off == 0) and iqlhip_online_step_mixed: the batch's first n_off rows
+// are rows_off_dev[idx_off_host[..]] (size_off rows, read only), the n behind them come from the ring.
+static int online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                       const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
+                       float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
+                       float* act_out_host, void* stream, const float* rows_off_dev, int64_t size_off,
+                       const int64_t* idx_off_host, int32_t n_off) {
   if (!c || !rows_dev || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (act_state_host && !act_out_host) return fail(IQLHIP_EINVAL, "act_state_host without act_out_host");
   if (!c->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_bind has not been called");
   if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
   if (((uintptr_t)rows_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
-  if (n < 1 || n > c->dims.max_batch) return fail(IQLHIP_EINVAL, "batch rows %d outside [1, max_batch=%d]", n, c->dims.max_batch);
+  const int B = n_off + n;                // rows of the step
+  if (n < 1 || n_off < 0 || n > c->dims.max_batch || n_off > c->dims.max_batch || B > c->dims.max_batch)
+    return fail(IQLHIP_EINVAL, "batch rows %d (+ %d offline) outside [1, max_batch=%d]", n, n_off, c->dims.max_batch);
   if (capacity < 1 || pointer < 0 || pointer >= capacity) return fail(IQLHIP_EINVAL, "ring pointer outside the buffer");
   {                                       // (the reference's torch indexing raises on such an index; a gather would fault)
     int rc_i = check_host_indices(idx_host, n, capacity);
+    if (!rc_i && n_off) rc_i = check_host_indices(idx_off_host, n_off, size_off);
     if (rc_i) return rc_i;
-    if ((rc_i = step_entry(c, n, stream, /*multi_step=*/false))) return rc_i;
+    if ((rc_i = step_entry(c, B, stream, /*multi_step=*/false))) return rc_i;
   }
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
   memcpy(c->on_row_pin, row_host, (size_t)ld * sizeof(float));
-  memcpy(c->on_idx_pin, idx_host, (size_t)n * sizeof(long long));
-  const int total = n * (int)(ld / 4);
-  hipLaunchKernelGGL(iql_online_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, st, rows_dev, (long long)ld,
-                     (long long)pointer, (const float*)c->on_row_pin, (const long long*)c->on_idx_pin, c->xb, n);
+  if (n_off) memcpy(c->on_idx_pin, idx_off_host, (size_t)n_off * sizeof(long long));      // [offline | online], batch order
+  memcpy(c->on_idx_pin + n_off, idx_host, (size_t)n * sizeof(long long));
+  const int total = B * (int)(ld / 4);
+  if (n_off)
+    hipLaunchKernelGGL(iql_online_gather2_kernel, dim3((total + 255) / 256), dim3(256), 0, st, rows_dev, rows_off_dev,
+                       (long long)ld, (long long)pointer, (const float*)c->on_row_pin, (const long long*)c->on_idx_pin,
+                       c->xb, n_off, B);
+  else
+    hipLaunchKernelGGL(iql_online_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, st, rows_dev, (long long)ld,
+                       (long long)pointer, (const float*)c->on_row_pin, (const long long*)c->on_idx_pin, c->xb, n);
   EagerStep e;
-  eager_begin(c, n, sc, st, c->xb, e);
+  eager_begin(c, B, sc, st, c->xb, e);
   e.u.losses_mirror = c->on_loss_pin;
   const unsigned long long done_val = ++c->done_seq;
   if (!act_state_host) { e.u.done_flag = c->done_pin; e.u.done_val = done_val; }      // (else the follow-up act() signals)
@@ -1655,6 +1678,32 @@ extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, in
   if (act_state_host) memcpy(act_out_host, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
+}
+extern "C" int iqlhip_online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                  const float* row_host, const int64_t* idx_host, int32_t n,
+                                  const iqlhip_step_scalars* sc, float out[3], const float* act_state_host,
+                                  float max_action, uint64_t act_seed, float* act_out_host, void* stream) {
+  return online_step(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, max_action,
+                     act_seed, act_out_host, stream, nullptr, 0, nullptr, 0);
+}
+extern "C" int iqlhip_online_step_mixed(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                        const float* row_host, const int64_t* idx_host, int32_t n,
+                                        const iqlhip_step_scalars* sc, float out[3], const float* act_state_host,
+                                        float max_action, uint64_t act_seed, float* act_out_host, void* stream,
+                                        const float* rows_off_dev, int64_t size_off, const int64_t* idx_off_host,
+                                        int32_t n_off) {
+  if (!rows_off_dev || !idx_off_host) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n_off < 1) return fail(IQLHIP_EINVAL, "n_off must be at least 1 (no offline rows: iqlhip_online_step)");
+  if (size_off < 1) return fail(IQLHIP_EINVAL, "empty offline buffer");
+  if (rows_off_dev == rows_dev) return fail(IQLHIP_EINVAL, "the offline and the online buffer are the same rows");
+  if (((uintptr_t)rows_off_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
+  // (the same scope as iqlhip_train_steps_mixed: no exchange, no large-batch bf16 step — before anything is launched)
+  if (c && c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "mixed batches are not supported with a data-parallel exchange");
+  if (c && n > 0 && n_off <= c->dims.max_batch && n <= c->dims.max_batch && use_lb(c, n_off + n))
+    return fail(IQLHIP_EUNSUPPORTED, "mixed batches are not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+  return online_step(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, max_action,
+                     act_seed, act_out_host, stream, rows_off_dev, size_off, idx_off_host, n_off);
 }
 
 extern "C" int iqlhip_forward_backward(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc,
@@ -1724,7 +1773,7 @@ extern "C" int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, ui
 // replay needs to differ in lives in device words that the set-up kernel writes once and each chunk's last update
 // kernel advances, so the chunks of a call follow each other with no host-side launch in between; the rows, scalars and
 // keep-bits of step k + 1 are staged by the idle eighth of step k's forward grid (IdleWork).
-static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_dev, int B, int K) {
+static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_dev, int B, int K, const MixSrc* mx) {
   const int MB = c->dims.max_batch;
   for (int k = 0; k < K; ++k) {
     IdleWork& i = w[k];
@@ -1740,11 +1789,12 @@ static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_d
     i.drop_thresh = drop_thresh(c->drop_p);
     i.n = B;
     i.k = k;
+    if (mx) { i.rows_on = mx->rows_on; i.n_off = mx->n_off; }
   }
 }
 
 static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_batch, int mode, int parity,
-                         const IdleWork* work_dev) {
+                         const IdleWork* work_dev, bool mixed = false) {
   const int MB = c->dims.max_batch;
   iqlhip_step_scalars sc0;
   memset(&sc0, 0, sizeof sc0);
@@ -1764,7 +1814,7 @@ static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_
     // (statistics: slot BASE + k of the ring, the loss ring's indexing; the chunk's key carries the setting)
     StatsArgs sa;
     if (c->stats_on) sa = make_stats(c, p, c->stats_ring, k, c->k_max, c->hdr);
-    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr);
+    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, mixed);
     if (rc) return rc;
   }
   return IQLHIP_OK;
@@ -1791,11 +1841,13 @@ struct SetupArgs {
   unsigned long long* hdr; ChunkHdr h; iqlhip_step_scalars* sched_call; const iqlhip_step_scalars* sched_src; int n_steps;
   const float* rows; long long ld; float* xb; int B; unsigned* drop_dst; int drop_words; unsigned drop_thresh;
   unsigned* arrivals; unsigned long long* ack; unsigned long long ack_val;
-  void* ptrs[15];
+  const float* rows_on; int n_off;        // (iql_call_setup_mixed_kernel's two more)
+  void* ptrs[17];
+  const void* func;                       // iql_call_setup_kernel, or its two-source form
   int nb;
 };
 static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int slot, int n_steps, const float* rows_dev,
-                            int B, bool gather, hipStream_t st) {
+                            int B, bool gather, hipStream_t st, const MixSrc* mx = nullptr) {
   const int MB = c->dims.max_batch;
   const bool drop = gather && c->drop_p > 0.f;
   if (slot >= 0) {
@@ -1809,8 +1861,10 @@ static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int 
   a.arrivals = c->setup_arrivals;
   a.ack = slot >= 0 ? c->sched_ack + slot : c->sched_ack + 4;        // (slot < 0: a capture-time placeholder, word 4 is a dummy)
   a.ack_val = slot >= 0 ? c->sched_want[slot] : 0ull;
-  void* p[15] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
-                 &a.drop_words, &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val};
+  a.rows_on = mx ? mx->rows_on : nullptr; a.n_off = mx ? mx->n_off : 0;
+  a.func = mx ? (const void*)iql_call_setup_mixed_kernel : (const void*)iql_call_setup_kernel;
+  void* p[17] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
+                 &a.drop_words, &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val, &a.rows_on, &a.n_off};
   memcpy(a.ptrs, p, sizeof p);
   long long want = ((long long)n_steps * 3 + 255) / 256;
   if (gather) want = std::max(want, ((long long)B * (c->row_ld / 4) + 255) / 256);
@@ -1818,20 +1872,22 @@ static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int 
   a.nb = (int)std::max<long long>(1, std::min<long long>(want, 256));
 }
 static int launch_call_setup(iqlhip_ctx* c, hipStream_t st, const ChunkHdr& h, int slot, int n_steps,
-                             const float* rows_dev, int B, bool gather) {
+                             const float* rows_dev, int B, bool gather, const MixSrc* mx = nullptr) {
   SetupArgs a;
-  fill_setup_args(c, a, h, slot, n_steps, rows_dev, B, gather, st);
-  HIPCHK(hipLaunchKernel((const void*)iql_call_setup_kernel, dim3(a.nb), dim3(256), a.ptrs, 0, st));
+  fill_setup_args(c, a, h, slot, n_steps, rows_dev, B, gather, st, mx);
+  HIPCHK(hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, st));
   return IQLHIP_OK;
 }
 
 // Capture and instantiate the chunk graph of g.key into g, member by member (a failure leaves the ones made so far).
 static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   const GraphKey& key = g.key;
+  const MixSrc key_mx{key.rows_on, key.n_off};
+  const MixSrc* mx = key.rows_on ? &key_mx : nullptr;
   // the chunk's idle-work records: device memory written once, here (their content is part of what the key freezes)
   {
     std::vector<IdleWork> hw((size_t)key.K);
-    fill_idle_work(c, hw.data(), key.rows, key.B, key.K);
+    fill_idle_work(c, hw.data(), key.rows, key.B, key.K, mx);
     HIPCHK(hipMalloc((void**)&g.work, hw.size() * sizeof(IdleWork)));
     hipError_t e = hipMemcpy(g.work, hw.data(), hw.size() * sizeof(IdleWork), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(IQLHIP_EHIP, "chunk_graph: hipMemcpy: %s", hipGetErrorString(e));
@@ -1844,13 +1900,13 @@ static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   if (key.head) {        // placeholder arguments: every replay sets the real ones (grid included)
     ChunkHdr h0;
     memset(&h0, 0, sizeof h0);
-    h0.w[HDR_SIZE] = 1ull;
+    h0.w[HDR_SIZE] = h0.w[HDR_SIZE_ON] = 1ull;
     SetupArgs a;
-    fill_setup_args(c, a, h0, -1, 0, key.rows, key.B, true, cs);
-    if (hipLaunchKernel((const void*)iql_call_setup_kernel, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
+    fill_setup_args(c, a, h0, -1, 0, key.rows, key.B, true, cs, mx);
+    if (hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
       rc = fail(IQLHIP_EHIP, "capture of the set-up kernel failed");
   }
-  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work);
+  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, mx != nullptr);
   e = hipStreamEndCapture(cs, &g.graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -1906,9 +1962,10 @@ static int inject_check(const iqlhip_ctx* c) {
 }
 
 static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, int32_t K, float inv_batch,
-                         int parity, int head = 0) {
+                         int parity, int head = 0, const MixSrc* mx = nullptr) {
   GraphKey key;
   key.head = head;
+  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; }
   key.rows = rows_dev; key.ld = ld; key.B = B; key.K = K; key.params = c->params; key.drop_p = c->drop_p;
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
@@ -1939,14 +1996,14 @@ static int n_chunks_for(int rem) {
   return n;
 }
 static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, int64_t ld, int B, int n, float inv_batch,
-                        const SetupArgs* head_args) {
+                        const SetupArgs* head_args, const MixSrc* mx = nullptr) {
   const int parity = (int)(c->xstep & 1ull);
   hipGraphExec_t gexec = nullptr;
   iqlhip_ctx::CachedGraph* cg = nullptr;
-  int r = chunk_graph(c, make_key(c, rows_dev, ld, B, n, inv_batch, parity, head_args ? 1 : 0), &gexec, &cg);
+  int r = chunk_graph(c, make_key(c, rows_dev, ld, B, n, inv_batch, parity, head_args ? 1 : 0, mx), &gexec, &cg);
   if (r) return r;
   if (g_direct_all && !head_args) {      // experiment: the chunk's kernels launched one by one instead of the graph replay
-    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work);
+    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, mx != nullptr);
     if (r) return r;
     cg->last = st;
     if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
@@ -1956,7 +2013,7 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
   if (head_args) {
     hipKernelNodeParams np;
     memset(&np, 0, sizeof np);
-    np.func = (void*)iql_call_setup_kernel;
+    np.func = const_cast<void*>(head_args->func);
     np.gridDim = dim3(head_args->nb);
     np.blockDim = dim3(256);
     np.kernelParams = const_cast<void**>(head_args->ptrs);
@@ -1971,10 +2028,11 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
   return IQLHIP_OK;
 }
 
-extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, float inv_batch,
-                                          void* stream) {
-  int rc = check_train_args(c, rows_dev, ld, B);
-  if (rc) return rc;
+// iqlhip_train_steps_prepare (mx == nullptr) and iqlhip_train_steps_mixed_prepare: the chunk graphs of the plain or of
+// the two-source kind.
+static int train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, float inv_batch, void* stream,
+                               const MixSrc* mx) {
+  int rc = IQLHIP_OK;
   if ((rc = step_entry(c, B, stream, /*multi_step=*/true))) return rc;
   DevGuard guard(c->device);
   HIPCHK(hipDeviceSynchronize());       // a one-off set-up call: ordered after everything queued on any stream
@@ -2025,18 +2083,18 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
     auto rehearse = [&](const Item& it) -> int {
       ChunkHdr h;
       memset(&h, 0, sizeof h);
-      h.w[HDR_SIZE] = 1ull;
+      h.w[HDR_SIZE] = h.w[HDR_SIZE_ON] = 1ull;
       h.w[HDR_DROP_STEP] = c->drop_step;
       h.w[HDR_DROP_SEED] = c->drop_seed;
       h.w[HDR_XSTEP] = c->xstep;
       if (it.head) {
         SetupArgs a;
-        fill_setup_args(c, a, h, slot, it.K, rows_dev, B, /*gather=*/true, cs);
-        return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, &a);
+        fill_setup_args(c, a, h, slot, it.K, rows_dev, B, /*gather=*/true, cs, mx);
+        return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, &a, mx);
       }
-      int r = launch_call_setup(c, cs, h, slot, it.K, rows_dev, B, /*gather=*/true);
+      int r = launch_call_setup(c, cs, h, slot, it.K, rows_dev, B, /*gather=*/true, mx);
       if (r) return r;
-      return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, nullptr);
+      return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, nullptr, mx);
     };
     for (int pass = 0; pass < passes && !rc; ++pass)
       for (const Item& it : items) { if (it.head && g_head_mode != 1) continue; rc = rehearse(it); if (rc) break; }
@@ -2049,12 +2107,12 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
     if (!rc && n_warm > 0 && c->xch_mode == IQLHIP_XCH_NONE) {
       ChunkHdr h;
       memset(&h, 0, sizeof h);
-      h.w[HDR_SIZE] = 1ull;
+      h.w[HDR_SIZE] = h.w[HDR_SIZE_ON] = 1ull;
       h.w[HDR_DROP_STEP] = c->drop_step;
       h.w[HDR_DROP_SEED] = c->drop_seed;
       for (int i = 0; i < n_warm && !rc; ++i) {
-        if ((i % (c->k_max / GRAPH_STEPS)) == 0) rc = launch_call_setup(c, cs, h, slot, c->k_max, rows_dev, B, /*gather=*/true);
-        if (!rc) rc = replay_chunk(c, cs, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr);
+        if ((i % (c->k_max / GRAPH_STEPS)) == 0) rc = launch_call_setup(c, cs, h, slot, c->k_max, rows_dev, B, /*gather=*/true, mx);
+        if (!rc) rc = replay_chunk(c, cs, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr, mx);
       }
     }
   } while (0);
@@ -2067,12 +2125,19 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
   return IQLHIP_OK;
 }
 
-extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
-                                  const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
-                                  int32_t flags, void* stream) {
-  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, float inv_batch,
+                                          void* stream) {
   int rc = check_train_args(c, rows_dev, ld, B);
   if (rc) return rc;
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, nullptr);
+}
+
+// iqlhip_train_steps (mx == nullptr) and iqlhip_train_steps_mixed (rows_dev / size: the offline buffer; size_on: the rows
+// the online part's draw covers) behind their argument checks.
+static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
+                       const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset, int32_t flags,
+                       void* stream, const MixSrc* mx, int64_t size_on) {
+  int rc = IQLHIP_OK;
   if (K < 1 || K > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
   if (size < 1) return fail(IQLHIP_EINVAL, "empty buffer");
   if ((rc = step_entry(c, B, stream, /*multi_step=*/true))) return rc;
@@ -2094,14 +2159,16 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
     ev0 = c->ev[c->ev_used]; ev1 = c->ev[c->ev_used + 1];
     HIPCHK(hipEventRecord(ev0, st));
   }
-  // does this call continue the previous one's index stream with its step 0 already staged?
-  const bool cont = (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.rows == rows_dev && c->cont.ld == ld &&
+  // does this call continue the previous one's index stream with its step 0 already staged?  (Never a mixed call: the
+  // rows its last forward staged are not what a plain call would draw, so it claims nothing and leaves no token.)
+  const bool cont = !mx && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.rows == rows_dev && c->cont.ld == ld &&
                     c->cont.size == size && c->cont.B == B && c->cont.seed == seed && c->cont.next_offset == stream_offset &&
                     c->cont.drop_p == c->drop_p && c->cont.drop_seed == c->drop_seed && c->cont.drop_step == c->drop_step;
   c->cont.valid = false;
   ChunkHdr h;
   memset(&h, 0, sizeof h);
   h.w[HDR_SIZE] = (unsigned long long)size;
+  h.w[HDR_SIZE_ON] = (unsigned long long)size_on;
   h.w[HDR_SEED] = (unsigned long long)seed;
   h.w[HDR_OFFSET] = (unsigned long long)stream_offset;     // index j of the call = counter offset + j / 2, pair word j & 1
   h.w[HDR_DROP_STEP] = c->drop_step;
@@ -2122,25 +2189,25 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
     const int parity = (int)(c->xstep & 1ull);
     hipGraphExec_t gexec = nullptr;
     iqlhip_ctx::CachedGraph* cg = nullptr;
-    rc = chunk_graph(c, make_key(c, rows_dev, ld, B, head_k, inv_batch, parity, 0), &gexec, &cg);     // (for its idle-work records)
+    rc = chunk_graph(c, make_key(c, rows_dev, ld, B, head_k, inv_batch, parity, 0, mx), &gexec, &cg);     // (for its idle-work records)
     if (rc) return rc;
-    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont);
+    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, mx);
     if (rc) return rc;
-    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work);
+    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, mx != nullptr);
     if (rc) return rc;
     cg->last = st;
     if (c->drop_p > 0.f) c->drop_step += (unsigned long long)head_k;
     if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)head_k;
     rem = K - head_k;
   } else if (g_no_head_graph) {
-    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont);
+    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, mx);
     if (rc) return rc;
     rem = K;
   } else {
     const int head_k = (K >= 2) ? 2 : 1;
     SetupArgs a;
-    fill_setup_args(c, a, h, slot, K, rows_dev, B, /*gather=*/!cont, st);
-    rc = replay_chunk(c, st, rows_dev, ld, B, head_k, inv_batch, &a);
+    fill_setup_args(c, a, h, slot, K, rows_dev, B, /*gather=*/!cont, st, mx);
+    rc = replay_chunk(c, st, rows_dev, ld, B, head_k, inv_batch, &a, mx);
     if (rc) return rc;
     rem = K - head_k;
   }
@@ -2149,12 +2216,12 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
   rem %= GRAPH_STEPS;
   int small[8], ns = 0;
   for (int cs_ : {16, 4, 2, 1}) while (rem >= cs_) { small[ns++] = cs_; rem -= cs_; }     // (<= 3 + 3 + 1 + 1 entries)
-  for (int i = ns - 1; i >= 0; --i) if (small[i] != 1) { rc = replay_chunk(c, st, rows_dev, ld, B, small[i], inv_batch, nullptr); if (rc) return rc; }
-  for (int i = 0; i < n64; ++i) { rc = replay_chunk(c, st, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr); if (rc) return rc; }
-  if (ns > 0 && small[ns - 1] == 1) { rc = replay_chunk(c, st, rows_dev, ld, B, 1, inv_batch, nullptr); if (rc) return rc; }
+  for (int i = ns - 1; i >= 0; --i) if (small[i] != 1) { rc = replay_chunk(c, st, rows_dev, ld, B, small[i], inv_batch, nullptr, mx); if (rc) return rc; }
+  for (int i = 0; i < n64; ++i) { rc = replay_chunk(c, st, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr, mx); if (rc) return rc; }
+  if (ns > 0 && small[ns - 1] == 1) { rc = replay_chunk(c, st, rows_dev, ld, B, 1, inv_batch, nullptr, mx); if (rc) return rc; }
   // what a following call must look like to start on the rows this call's last forward has staged: an even number of
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
-  if ((K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
+  if (!mx && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
     c->cont.next_offset = stream_offset + ((unsigned long long)K * (unsigned long long)B) / 2ull;
@@ -2173,6 +2240,15 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
     fprintf(stderr, "[iqlhip trace] train_steps K=%d cont=%d: entry->launch %.1f us, head chunk (set-up + launch) %.1f, rest %.1f\n",
             K, (int)cont, tr_t[1] - tr_t[0], tr_t[2] - tr_t[1], now_us() - tr_t[3]);
   return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
+                                  const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
+                                  int32_t flags, void* stream) {
+  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = check_train_args(c, rows_dev, ld, B);
+  if (rc) return rc;
+  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, nullptr, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -3414,4 +3490,101 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
   hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, g->done_pin, done_val);
   HIPCHK(hipGetLastError());
   return wait_word(g->done_pin, done_val, st);
+}
+
+// ---------------------------------------------------------------------------
+// Two-source multi-step calls (include/iqlhip.h "mixed offline / online batches"): iqlhip_train_steps with every batch's
+// first n_off rows drawn from one buffer and the rest from another.  The driver above does the work (MixSrc); here are
+// the forward instantiations of such chunks — selected and emitted behind every other kernel of the library, so the
+// code object of the plain calls' kernels lies where it always has (with_bools) — and the entry points' checks.
+// (The two kernels below are declared in iqlhip_kernels.h and defined here for the same reason.)
+// First launch of an iqlhip_train_steps_mixed call: the same, with step 0's rows drawn from the two buffers (a mixed
+// call always gathers them: B > 0; `rows` is the offline buffer).
+__global__ __launch_bounds__(256) void iql_call_setup_mixed_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                                   iqlhip_step_scalars* sched_call,
+                                                                   const iqlhip_step_scalars* sched_src, int n_steps,
+                                                                   const float* rows, long long ld, float* xb, int B,
+                                                                   unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                                   unsigned* arrivals, unsigned long long* ack,
+                                                                   unsigned long long ack_val, const float* rows_on,
+                                                                   int n_off) {
+  call_setup_head(hdr, h, sched_call, sched_src, n_steps, arrivals, ack, ack_val);
+  gather_rows_drawn2(rows, rows_on, ld, xb, B, n_off, h.w[HDR_SEED], h.w[HDR_OFFSET], h.w[HDR_POS], h.w[HDR_SIZE],
+                     h.w[HDR_SIZE_ON], (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+  if (drop_dst)
+    dropmask_words(drop_dst, drop_words, drop_thresh, h.w[HDR_DROP_SEED], h.w[HDR_DROP_STEP],
+                   ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+}
+
+// The same for a batch mixed from two buffers (iqlhip_online_step_mixed): batch rows [0, n_off) are
+// rows_off[idx_host[r]] (the offline buffer, read only), rows [n_off, n) come from the ring as above — idx_host holds the
+// n_off offline indices followed by the n - n_off online ones, the order the host drew them in.  A row's float4 count
+// does not divide 256, so a block may straddle n_off: its index cache holds indices of both kinds, and the row number
+// decides which buffer an index belongs to (an offline index that happens to equal `pointer` is an ordinary row).
+__global__ __launch_bounds__(256) void iql_online_gather2_kernel(float* rows, const float* rows_off, long long ld,
+                                                                 long long pointer, const float* row_host,
+                                                                 const long long* idx_host, float* xb, int n_off, int n) {
+  __shared__ long long s_idx[260];
+  const int q = (int)(ld >> 2);
+  const int e0 = (int)blockIdx.x * 256;
+  const int r_first = e0 / q;
+  const int r_last = min((e0 + 255) / q, n - 1);
+  if ((int)threadIdx.x <= r_last - r_first) s_idx[threadIdx.x] = idx_host[r_first + threadIdx.x];
+  if (blockIdx.x == 0 && (int)threadIdx.x < q)
+    *(f32x4*)(rows + pointer * ld + 4 * threadIdx.x) = *(const f32x4*)(row_host + 4 * threadIdx.x);
+  __syncthreads();
+  const int e = e0 + (int)threadIdx.x;
+  if (e < n * q) {
+    const int r = e / q, c4 = e - r * q;
+    const long long i = s_idx[r - r_first];
+    const float* src = (r < n_off) ? rows_off + i * ld : ((i == pointer) ? row_host : rows + i * ld);
+    *(f32x4*)(xb + (long long)r * ld + 4 * c4) = *(const f32x4*)(src + 4 * c4);
+  }
+}
+
+static auto fwd_mixed_kernel(bool bf, bool dma, bool multi) {
+  return with_bools([](auto MU, auto BF, auto DMA) { return &iql_fwd_mixed_kernel<BF.value, DMA.value, MU.value>; }, multi, bf, dma);
+}
+static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
+  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
+  hipLaunchKernelGGL(fwd_mixed_kernel(c->precision == 1, dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
+}
+static int check_mixed_args(iqlhip_ctx* c, const float* rows_off_dev, const float* rows_on_dev, int64_t ld, int32_t B,
+                            int32_t n_off) {
+  int rc = check_train_args(c, rows_off_dev, ld, B);
+  if (rc) return rc;
+  if (!rows_on_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (((uintptr_t)rows_on_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
+  if (rows_on_dev == rows_off_dev) return fail(IQLHIP_EINVAL, "the offline and the online buffer are the same rows");
+  if (n_off < 1 || n_off >= B) return fail(IQLHIP_EINVAL, "n_off %d outside [1, batch_rows - 1] (one buffer only: iqlhip_train_steps)", n_off);
+  if (c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "mixed batches are not supported with a data-parallel exchange");
+  if (use_lb(c, B))
+    return fail(IQLHIP_EUNSUPPORTED, "mixed batches are not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+  // (dynamic LDS of the mixed forward instantiations: once per context, here rather than with the other families)
+  if (!c->mixed_lds_set) {
+    DevGuard guard(c->device);
+    rc = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_mixed_kernel(m & 1, m & 2, m & 4); });
+    if (rc) return rc;
+    c->mixed_lds_set = true;
+  }
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_train_steps_mixed_prepare(iqlhip_ctx* c, const float* rows_off_dev, const float* rows_on_dev, int64_t ld,
+                                                int32_t B, int32_t n_off, float inv_batch, void* stream) {
+  int rc = check_mixed_args(c, rows_off_dev, rows_on_dev, ld, B, n_off);
+  if (rc) return rc;
+  const MixSrc mx{rows_on_dev, n_off};
+  return train_steps_prepare(c, rows_off_dev, ld, B, inv_batch, stream, &mx);
+}
+extern "C" int iqlhip_train_steps_mixed(iqlhip_ctx* c, const float* rows_off_dev, int64_t size_off, const float* rows_on_dev,
+                                        int64_t size_on, int64_t ld, int32_t B, int32_t n_off,
+                                        const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
+                                        void* stream) {
+  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = check_mixed_args(c, rows_off_dev, rows_on_dev, ld, B, n_off);
+  if (rc) return rc;
+  if (size_on < 1) return fail(IQLHIP_EINVAL, "empty online buffer");
+  const MixSrc mx{rows_on_dev, n_off};
+  return train_steps(c, rows_off_dev, ld, size_off, B, sc, K, seed, stream_offset, 0, stream, &mx, size_on);
 }

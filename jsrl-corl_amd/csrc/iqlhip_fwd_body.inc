@@ -1,7 +1,8 @@
 // Body of the forward — included by iql_fwd_kernel and iql_fwd_group_kernel (iqlhip_kernels.h):
 // ONE body for the single-agent kernel and its trainer-group form, so the arithmetic exists once.  blockIdx.x / gridDim.x
 // are the block's index and grid size of ONE agent's launch in both (a group kernel's agent is blockIdx.y).
-// In scope: template flags BF16, W0DMA, MULTI, ONE, the agent's `p` (StepParams) and ROW_EXIT: a block whose row tile
+// In scope: template flags BF16, W0DMA, MULTI, ONE, MIXED_IDLE (the idle blocks' work is a two-source chunk's), the
+// agent's `p` (StepParams) and ROW_EXIT: a block whose row tile
 // lies outside the agent's batch exits under every block map (iql_fwd_group_kernel only: its grid.x is the largest
 // member's; a single agent's one- and two-slice grids are sized exactly and compile without the test).
   RT_ENTRY();
@@ -25,7 +26,7 @@
   constexpr unsigned FWD_PAIR_A = 0x6541u, FWD_PAIR_B = 0x7320u;      // nibble (x & 3): V(s) Q1 Q2 pi | V(s') Qt1 Qt2 idle
   const int inst = ONE ? p.only_inst : (int)((((fr & 1) ? FWD_PAIR_B : FWD_PAIR_A) >> (4 * (fx & 3))) & 7u);
   if (inst >= 7) {     // the idle eighth of the grid: the chunk's bookkeeping for the NEXT step (graph chunks), else exits
-    if (p.g_work) idle_block_work(p.g_work, (fr >> 1) * 2 + fh, (int)(gridDim.x >> 3));
+    if (p.g_work) idle_block_work<MIXED_IDLE>(p.g_work, (fr >> 1) * 2 + fh, (int)(gridDim.x >> 3));
     return;
   }
   const int spb_l2 = MULTI ? (p.spb_l2 & 3) : 0;      // (MULTI = false: exactly the one-slice code, no loop)

@@ -273,8 +273,10 @@ __device__ __forceinline__ void gather_rows_flat(const float* rows, long long ld
 //   POS       indices drawn before this chunk (index j of the call = counter OFFSET + j / 2, word pair j & 1)
 //   BASE      steps of the call before this chunk (row of the call's scalar table, slot of the loss ring)
 //   DROP_*    dropout stream                        XSTEP          steps exchanged before this chunk (P2P flags)
+//   SIZE_ON   two-source calls (iqlhip_train_steps_mixed): rows the draw of a batch's online part covers — SIZE is
+//             then the offline buffer's; a header word, so the online ring may grow between calls (0 in a plain call)
 enum { HDR_SIZE = 0, HDR_SEED = 1, HDR_OFFSET = 2, HDR_DROP_STEP = 3, HDR_DROP_SEED = 4, HDR_BASE = 5, HDR_XSTEP = 6,
-       HDR_POS = 7, HDR_WORDS = 8 };
+       HDR_POS = 7, HDR_SIZE_ON = 8, HDR_WORDS = 9 };
 struct ChunkHdr { unsigned long long w[HDR_WORDS]; };
 
 // Philox4x32-10 (Salmon et al. 2011).
@@ -340,6 +342,24 @@ __device__ __forceinline__ void gather_rows_drawn(const float* rows, long long l
   }
 }
 
+// The same for a batch mixed from two buffers (iqlhip_train_steps_mixed): row r < n_off is drawn over [0, size_off) from
+// rows_off, row r >= n_off over [0, size_on) from rows_on — index j0 + r of the call's one stream either way, so the
+// counters a call consumes do not depend on the split.
+__device__ __forceinline__ void gather_rows_drawn2(const float* rows_off, const float* rows_on, long long ld, float* xb, int n,
+                                                   int n_off, unsigned long long seed, unsigned long long ctr0,
+                                                   unsigned long long j0, unsigned long long size_off,
+                                                   unsigned long long size_on, int first, int stride) {
+  const int q = (int)(ld >> 2);
+  const int total = n * q;
+  for (int e = first; e < total; e += stride) {
+    const int r = e / q, c4 = e - r * q;
+    const bool on = r >= n_off;
+    const long long i = draw_index(seed, ctr0, j0 + (unsigned long long)r, on ? size_on : size_off);
+    const float* src = on ? rows_on : rows_off;
+    *(f32x4*)(xb + (long long)r * ld + 4 * c4) = *(const f32x4*)(src + i * ld + 4 * c4);
+  }
+}
+
 // What the idle eighth of a captured step's forward grid does (StepParams::g_work; one record per step of a chunk,
 // written once when the chunk is captured):
 struct IdleWork {
@@ -354,15 +374,26 @@ struct IdleWork {
   unsigned drop_thresh;
   int n;                                  // rows per step
   int k;                                  // this step's number inside the chunk
+  // two-source chunks only (MIXED): `rows` is the offline buffer, rows_on the online one, batch rows >= n_off are its
+  const float* rows_on;
+  int n_off;
 };
+// MIXED: the idle work of a two-source chunk (iql_fwd_mixed_kernel) — a compile-time switch, so that the forward
+// kernels of plain calls hold no trace of it.
+template <bool MIXED = false>
 __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int nblk) {
   const IdleWork w = *wk;
   const unsigned long long size = w.hdr[HDR_SIZE], seed = w.hdr[HDR_SEED], ctr0 = w.hdr[HDR_OFFSET], pos = w.hdr[HDR_POS];
   const unsigned long long base = w.hdr[HDR_BASE], dseed = w.hdr[HDR_DROP_SEED], dstep = w.hdr[HDR_DROP_STEP];
   // the next step's rows: index j = POS + (k + 1) n + r of the call (for the chunk's last step that is step 0 of
   // whatever runs next: the following chunk, or the next call when it continues this one's stream)
-  gather_rows_drawn(w.rows, w.ld, w.xb_dst, w.n, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n,
-                    size, blk * 256 + (int)threadIdx.x, nblk * 256);
+  if (MIXED)
+    gather_rows_drawn2(w.rows, w.rows_on, w.ld, w.xb_dst, w.n, w.n_off, seed, ctr0,
+                       pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, size, w.hdr[HDR_SIZE_ON],
+                       blk * 256 + (int)threadIdx.x, nblk * 256);
+  else
+    gather_rows_drawn(w.rows, w.ld, w.xb_dst, w.n, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n,
+                      size, blk * 256 + (int)threadIdx.x, nblk * 256);
   // this step's optimiser scalars: row BASE + k of the call's table -> the slot this step's update kernel reads
   if (blk == nblk - 1 && threadIdx.x < sizeof(iqlhip_step_scalars) / sizeof(float))
     ((float*)w.sched_dst)[threadIdx.x] = ((const float*)(w.sched_call + base + (unsigned long long)w.k))[threadIdx.x];
@@ -407,6 +438,7 @@ __device__ __forceinline__ void l0_chunk_bf16(f32x4 (&acc)[2][4], const float (&
 template <bool BF16, bool W0DMA, bool MULTI, bool ONE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_kernel(StepParams p) {
   constexpr bool ROW_EXIT = false;      // (a grid of exactly this agent's row tiles)
+  constexpr bool MIXED_IDLE = false;
 #include "iqlhip_fwd_body.inc"
 }
 
@@ -805,13 +837,10 @@ __global__ __launch_bounds__(256) void iql_dropmask_kernel(unsigned* bits, int n
 // of the call's step 0 (indices drawn on the spot from the by-value header) and draw its dropout keep-bits.
 // The block that finishes last acknowledges the table read in a host-mapped word (`ack`): the host reuses the pinned
 // slot once it sees the call's number there — no event record in the stream, no HIP call on the host to test it.
-__global__ __launch_bounds__(256) void iql_call_setup_kernel(unsigned long long* hdr, ChunkHdr h,
-                                                             iqlhip_step_scalars* sched_call,
-                                                             const iqlhip_step_scalars* sched_src, int n_steps,
-                                                             const float* rows, long long ld, float* xb, int B,
-                                                             unsigned* drop_dst, int drop_words, unsigned drop_thresh,
-                                                             unsigned* arrivals, unsigned long long* ack,
-                                                             unsigned long long ack_val) {
+// (call_setup_head: the header, the table and the acknowledgement — shared with the two-source form below)
+__device__ __forceinline__ void call_setup_head(unsigned long long* hdr, const ChunkHdr& h, iqlhip_step_scalars* sched_call,
+                                                const iqlhip_step_scalars* sched_src, int n_steps, unsigned* arrivals,
+                                                unsigned long long* ack, unsigned long long ack_val) {
   if (blockIdx.x == 0 && threadIdx.x < HDR_WORDS) hdr[threadIdx.x] = h.w[threadIdx.x];
   const f32x4* s = (const f32x4*)sched_src;
   f32x4* d = (f32x4*)sched_call;
@@ -827,6 +856,15 @@ __global__ __launch_bounds__(256) void iql_call_setup_kernel(unsigned long long*
       __hip_atomic_store(ack, ack_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
+}
+__global__ __launch_bounds__(256) void iql_call_setup_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                             iqlhip_step_scalars* sched_call,
+                                                             const iqlhip_step_scalars* sched_src, int n_steps,
+                                                             const float* rows, long long ld, float* xb, int B,
+                                                             unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                             unsigned* arrivals, unsigned long long* ack,
+                                                             unsigned long long ack_val) {
+  call_setup_head(hdr, h, sched_call, sched_src, n_steps, arrivals, ack, ack_val);
   if (B > 0)
     gather_rows_drawn(rows, ld, xb, B, h.w[HDR_SEED], h.w[HDR_OFFSET], h.w[HDR_POS], h.w[HDR_SIZE],
                       (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
@@ -834,6 +872,15 @@ __global__ __launch_bounds__(256) void iql_call_setup_kernel(unsigned long long*
     dropmask_words(drop_dst, drop_words, drop_thresh, h.w[HDR_DROP_SEED], h.w[HDR_DROP_STEP],
                    ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
 }
+// (its two-source form, iql_call_setup_mixed_kernel, is defined with the other kernels of mixed calls: end of iqlhip.hip)
+__global__ __launch_bounds__(256) void iql_call_setup_mixed_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                                   iqlhip_step_scalars* sched_call,
+                                                                   const iqlhip_step_scalars* sched_src, int n_steps,
+                                                                   const float* rows, long long ld, float* xb, int B,
+                                                                   unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                                   unsigned* arrivals, unsigned long long* ack,
+                                                                   unsigned long long ack_val, const float* rows_on,
+                                                                   int n_off);
 
 // bf16 shadows rebuilt from the fp32 masters (start of every library call on the bf16 path: the caller owns the
 // masters and may have written them through its own tensors since the last update kernel ran).
@@ -1061,6 +1108,7 @@ template <bool BF16, bool W0DMA, bool MULTI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_group_kernel(const GroupRec* __restrict__ recs) {
   constexpr bool ONE = false;
   constexpr bool ROW_EXIT = true;       // (grid.x: the member with the most row tiles — the others' extra blocks exit)
+  constexpr bool MIXED_IDLE = false;
   const StepParams& p = recs[blockIdx.y].p;
 #include "iqlhip_fwd_body.inc"
 }
@@ -1800,6 +1848,11 @@ __global__ __launch_bounds__(256) void iql_online_gather_kernel(float* rows, lon
   }
 }
 
+// (iql_online_gather2_kernel, the form for a batch mixed from two buffers: end of iqlhip.hip)
+__global__ __launch_bounds__(256) void iql_online_gather2_kernel(float* rows, const float* rows_off, long long ld,
+                                                                 long long pointer, const float* row_host,
+                                                                 const long long* idx_host, float* xb, int n_off, int n);
+
 // ---------------------------------------------------------------------------
 // Trainer-group online iteration (iqlhip_group_online_step): the kernels above that a solo iqlhip_online_step
 // launches, in group form (grid.y = member), with their arguments in device records the host uploads once per call.
@@ -1870,6 +1923,7 @@ __global__ __launch_bounds__(256) void iql_online_gather_drop_group_kernel(const
 template <bool BF16, bool W0DMA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_act_fwd_group_kernel(const StepParams* __restrict__ ps) {
   constexpr bool MULTI = false, ONE = true, ROW_EXIT = false;      // (blocks past a member's rows store nothing)
+  constexpr bool MIXED_IDLE = false;
   const StepParams& p = ps[blockIdx.y];
 #include "iqlhip_fwd_body.inc"
 }
@@ -1938,4 +1992,14 @@ __global__ __launch_bounds__(256) void iql_actor_finish_rows_group_kernel(const 
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < r.n * r.A)
     actor_finish_elem(r.heads, e, r.A, r.max_action, r.log_std, r.ls_min, r.ls_max, nullptr, 0, r.seed, r.call, r.out, r.ld_out);
+}
+
+// ---------------------------------------------------------------------------
+// The training forward of a two-source chunk (iqlhip_train_steps_mixed): iql_fwd_kernel's body instantiated a second
+// time, with the idle blocks staging the next step's rows from two buffers (idle_block_work<true>).  A kernel of its
+// own rather than a run-time test in iql_fwd_kernel: the forward of plain calls stays as it is, instruction for instruction.
+template <bool BF16, bool W0DMA, bool MULTI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_mixed_kernel(StepParams p) {
+  constexpr bool ONE = false, ROW_EXIT = false, MIXED_IDLE = true;
+#include "iqlhip_fwd_body.inc"
 }

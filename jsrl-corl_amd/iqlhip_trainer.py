@@ -648,6 +648,45 @@ class ImplicitQLearning:
             log.update(self._stats_entries())
         return log
 
+    # ---- what online_step and online_step_mixed share: the packed host row, the act_next arguments, the commit
+    def _online_row(self, buf, state, action, reward, next_state, done) -> np.ndarray:
+        """The new transition as one packed host row [ld] (pad columns zero)."""
+        S, A = self._S, self._A
+        row = getattr(self, "_on_row", None)
+        if row is None or row.shape[0] != buf._ld:
+            row = self._on_row = np.zeros(buf._ld, dtype=np.float32)
+        row[:S] = np.asarray(state, dtype=np.float32).reshape(-1)
+        row[S: S + A] = np.asarray(action, dtype=np.float32).reshape(-1)
+        row[S + A: 2 * S + A] = np.asarray(next_state, dtype=np.float32).reshape(-1)
+        row[2 * S + A] = np.float32(reward)
+        row[2 * S + A + 1] = np.float32(done)
+        return row
+
+    def _act_next_args(self, act_next):
+        """(state in, action out, noise seed) of the call's act forward; (None, None, 0) without act_next."""
+        if act_next is None:
+            return None, None, 0
+        if self.acts_with_dropout() and not self._act_dropout:
+            raise NotImplementedError("act_next: the library's inference forward is eval-mode (no actor dropout) "
+                                      "unless set_act_dropout(True) was called")
+        self._prepare_act()
+        a_in = np.ascontiguousarray(np.asarray(act_next, dtype=np.float32).reshape(-1))
+        a_out = np.empty(self._A, dtype=np.float32)
+        return a_in, a_out, (self._act_seed() if (self.actor.training and self._gaussian) else 0)
+
+    def _online_commit(self, buf, pointer: int, new_size: int, adam_next, out, a_out):
+        """After the library call has succeeded: the ring's and the trainer's counters move, the result is built."""
+        buf._writes += 1
+        buf._pointer = (pointer + 1) % buf._buffer_size
+        buf._size = new_size
+        self.total_it += 1
+        self._adam_t = adam_next
+        self._advance_schedule(1)
+        log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
+        if self._step_stats:
+            log.update(self._stats_entries())
+        return log if a_out is None else (log, a_out)
+
     def online_step(self, replay_buffer, state, action, reward: float, next_state, done: bool,
                     batch_size: int, act_next: Optional[np.ndarray] = None):
         """One iteration of the online loop's buffer + training work in ONE library call (reference sequence:
@@ -666,15 +705,7 @@ class ImplicitQLearning:
             raise NotImplementedError("online_step runs the whole step in one library call: it needs an in-library "
                                       "exchange, enable_data_parallel(exchange='rccl'|'p2p') — with exchange='torch' "
                                       "use add_transition / sample / train")
-        S, A = self._S, self._A
-        row = getattr(self, "_on_row", None)
-        if row is None or row.shape[0] != buf._ld:
-            row = self._on_row = np.zeros(buf._ld, dtype=np.float32)
-        row[:S] = np.asarray(state, dtype=np.float32).reshape(-1)
-        row[S: S + A] = np.asarray(action, dtype=np.float32).reshape(-1)
-        row[S + A: 2 * S + A] = np.asarray(next_state, dtype=np.float32).reshape(-1)
-        row[2 * S + A] = np.float32(reward)
-        row[2 * S + A + 1] = np.float32(done)
+        row = self._online_row(buf, state, action, reward, next_state, done)
         # (the buffer's and the trainer's counters move only once the library call has succeeded)
         pointer = buf._pointer
         new_size = min(buf._size + 1, buf._buffer_size)
@@ -688,30 +719,111 @@ class ImplicitQLearning:
         sc = hb.StepScalars()
         self._fill_scalars(sc, adam_next, self._current_lrs(), dp.inv_batch(batch_size, self._dp_world))
         out = (C.c_float * 3)()
-        a_in = a_out = None
-        seed = 0
-        if act_next is not None:
-            if self.acts_with_dropout() and not self._act_dropout:
-                raise NotImplementedError("act_next: the library's inference forward is eval-mode (no actor dropout) "
-                                          "unless set_act_dropout(True) was called")
-            self._prepare_act()
-            a_in = np.ascontiguousarray(np.asarray(act_next, dtype=np.float32).reshape(-1))
-            a_out = np.empty(A, dtype=np.float32)
-            seed = self._act_seed() if (self.actor.training and self._gaussian) else 0
+        a_in, a_out, seed = self._act_next_args(act_next)
         hb.check(hb.lib().iqlhip_online_step(self._ctx, buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer,
                                              row.ctypes.data, idx.ctypes.data, batch_size, C.byref(sc), out,
                                              None if a_in is None else a_in.ctypes.data, float(self.actor.max_action),
                                              seed, None if a_out is None else a_out.ctypes.data, self._stream()))
-        buf._writes += 1
-        buf._pointer = (pointer + 1) % buf._buffer_size
-        buf._size = new_size
-        self.total_it += 1
-        self._adam_t = adam_next
-        self._advance_schedule(1)
-        log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
-        if self._step_stats:
-            log.update(self._stats_entries())
-        return log if act_next is None else (log, a_out)
+        return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+
+    # ---- batches mixed from an offline and an online buffer (iqlhip_mixed.py) ----------------------
+    def _mixed_args(self, offline_buffer, online_buffer, batch_size: int, mixing_ratio: float) -> Tuple[int, int]:
+        """The checks both mixed calls make before anything is launched or any counter moves; returns (n_off, n_on)."""
+        import iqlhip_mixed as mixed
+        self._require_gpu()
+        n_off, n_on = mixed.split(batch_size, mixing_ratio)
+        mixed.check_buffers(offline_buffer, online_buffer, self._dev, self._S, self._A)
+        if self._dp_world > 1 or self._dp_exchange is not None:
+            raise NotImplementedError("iqlhip: mixed batches are not supported under data parallelism")
+        if getattr(self, "_precision", "f32") == "bf16" and batch_size > STATS_BF16_MAX_ROWS:
+            raise NotImplementedError(f"iqlhip: mixed batches are not supported for bf16 batches of more than "
+                                      f"{STATS_BF16_MAX_ROWS} rows (got {batch_size}): the large-batch kernels stage "
+                                      "their rows from one buffer")
+        if offline_buffer._size < 1:
+            raise ValueError("iqlhip: the offline replay buffer is empty")
+        return n_off, n_on
+
+    def online_step_mixed(self, offline_buffer, online_buffer, state, action, reward: float, next_state, done: bool,
+                          batch_size: int, mixing_ratio: float = 0.5, act_next: Optional[np.ndarray] = None):
+        """online_step with the batch mixed from two buffers, as the reference's Cal-QL loop builds it
+        (algorithms/finetune/cal_ql.py: mixing_ratio): the transition goes into `online_buffer`, and the step trains on
+        `n_off = int(batch_size * mixing_ratio)` rows of `offline_buffer` followed by `batch_size - n_off` rows of
+        `online_buffer` — one library call.  Bit for bit `online_buffer.add_transition(...)`,
+        `offline_buffer.sample(n_off)`, `online_buffer.sample(n_on)`, `train(vstack of the two)`, the global numpy RNG
+        consumed in that order (the online draw over the size after the insert).  act_next, step statistics, clipping
+        and set_act_dropout behave as in online_step.  ValueError unless 1 <= n_off <= batch_size - 1 and both buffers
+        are distinct finetune ReplayBuffers of the trainer's dimensions on its GPU; NotImplementedError under data
+        parallelism and for bf16 batches of more than 512 rows."""
+        import iqlhip_mixed as mixed
+        n_off, n_on = self._mixed_args(offline_buffer, online_buffer, batch_size, mixing_ratio)
+        self._prepare(batch_size)
+        buf = online_buffer
+        row = self._online_row(buf, state, action, reward, next_state, done)
+        # (the buffer's and the trainer's counters move only once the library call has succeeded)
+        pointer = buf._pointer
+        new_size = min(buf._size + 1, buf._buffer_size)
+        idx_off, idx_on = mixed.draw_host_indices(offline_buffer._size, n_off, new_size, n_on)
+        adam_next = {g: t + 1 for g, t in self._adam_t.items()}
+        sc = hb.StepScalars()
+        self._fill_scalars(sc, adam_next, self._current_lrs(), 1.0 / batch_size)
+        out = (C.c_float * 3)()
+        a_in, a_out, seed = self._act_next_args(act_next)
+        hb.check(hb.lib().iqlhip_online_step_mixed(
+            self._ctx, buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer, row.ctypes.data, idx_on.ctypes.data,
+            n_on, C.byref(sc), out, None if a_in is None else a_in.ctypes.data, float(self.actor.max_action), seed,
+            None if a_out is None else a_out.ctypes.data, self._stream(), offline_buffer._rows.data_ptr(),
+            offline_buffer._size, idx_off.ctypes.data, n_off))
+        return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+
+    def prepare_train_steps_mixed(self, offline_buffer, online_buffer, batch_size: int, mixing_ratio: float = 0.5) -> None:
+        """prepare_train_steps for the chunk graphs train_steps_mixed replays on this pair of buffers and this split."""
+        n_off, _ = self._mixed_args(offline_buffer, online_buffer, batch_size, mixing_ratio)
+        self._prepare(batch_size)
+        self._refuse_injected_masks()
+        hb.check(hb.lib().iqlhip_train_steps_mixed_prepare(
+            self._ctx, offline_buffer._rows.data_ptr(), online_buffer._rows.data_ptr(), offline_buffer._ld, batch_size,
+            n_off, 1.0 / batch_size, self._stream()))
+        self._ts_token = None
+
+    def train_steps_mixed(self, offline_buffer, online_buffer, n_steps: int, batch_size: int, mixing_ratio: float = 0.5,
+                          seed: int = 0, return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
+        """train_steps with every batch mixed from two buffers: the bursts of updates online fine-tuning runs after an
+        episode (or an update-to-data ratio above 1) without a host round trip per step.  The device index stream is
+        train_steps' own (Philox keyed by (seed, total_it); index k * batch_size + r of a call belongs to step k, batch
+        row r); row r < n_off = int(batch_size * mixing_ratio) maps its 64 random bits over the offline buffer's size
+        into `offline_buffer`, row r >= n_off over the online buffer's size into `online_buffer`.  Both sizes are read
+        at the call, so the online buffer may grow between calls without a recapture.  Returns what train_steps
+        returns.  A mixed call never continues a previous call's staged rows and leaves none behind: plain train_steps
+        calls around it behave as if it had not happened, apart from the trained parameters.  Refusals as
+        online_step_mixed, plus injected dropout masks (as train_steps)."""
+        if return_stats and not self._step_stats:
+            raise ValueError("iqlhip: train_steps_mixed(return_stats=True) needs set_step_stats(True) first")
+        n_off, _ = self._mixed_args(offline_buffer, online_buffer, batch_size, mixing_ratio)
+        if online_buffer._size < 1:
+            raise ValueError("iqlhip: the online replay buffer is empty")
+        self._prepare(batch_size)
+        self._refuse_injected_masks()
+        inv_batch = 1.0 / batch_size
+        stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
+        losses = np.empty((n_steps, 3), dtype=np.float32) if return_losses else None
+        chunk = max(1, min(int(chunk), K_MAX))
+        lib, stream = hb.lib(), self._stream()
+        off_ptr, on_ptr, ld = offline_buffer._rows.data_ptr(), online_buffer._rows.data_ptr(), offline_buffer._ld
+        half = (batch_size + 1) // 2
+        self._ts_token = None                  # (the library drops its continue token too)
+        done = 0
+        while done < n_steps:
+            k = min(chunk, n_steps - done)
+            tab = self._scalar_table(k, inv_batch)
+            hb.check(lib.iqlhip_train_steps_mixed(self._ctx, off_ptr, offline_buffer._size, on_ptr, online_buffer._size,
+                                                  ld, batch_size, n_off, tab.ctypes.data, k, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  self.total_it * half, stream))
+            self.total_it += k
+            done += k
+            self._lookahead_table(min(chunk, n_steps - done) if done < n_steps else k, inv_batch)
+            self._read_rings(k, stream, None if losses is None else losses[done - k: done],
+                             None if stats is None else stats[done - k: done])
+        return (losses, stats) if return_stats else losses
 
     def _schedule_state(self):
         sch = self.actor_lr_schedule
@@ -854,6 +966,19 @@ class ImplicitQLearning:
             raise NotImplementedError("iqlhip: train_steps draws its own keep-bits and cannot use the masks written by "
                                       "inject_dropout_masks; step with train(), or clear them (set_dropout_seed)")
 
+    def _read_rings(self, k: int, stream, losses, stats) -> None:
+        """The last k steps' losses [k, 3] and statistics [k, 16] from the library's rings into the given arrays (None: not
+        wanted) — what train_steps and train_steps_mixed do after each library call."""
+        lib = hb.lib()
+        if losses is not None:
+            buf = (C.c_float * (3 * k))()
+            hb.check(lib.iqlhip_read_loss_ring(self._ctx, buf, k, stream))
+            losses[:] = np.frombuffer(buf, dtype=np.float32).reshape(k, 3)
+        if stats is not None:
+            sbuf = (C.c_float * (hb.IQLHIP_N_STATS * k))()
+            hb.check(lib.iqlhip_read_stats_ring(self._ctx, sbuf, k, stream))
+            stats[:] = np.frombuffer(sbuf, dtype=np.float32).reshape(k, hb.IQLHIP_N_STATS)
+
     def prepare_train_steps(self, replay_buffer, batch_size: int) -> None:
         """Capture and upload the hipGraph chunk train_steps replays for this buffer / batch size now, so that no later
         train_steps call pays for it (it is captured lazily otherwise, by the first call of >= 64 steps)."""
@@ -908,14 +1033,8 @@ class ImplicitQLearning:
             done += k
             # the GPU is busy with these k steps: compute the scalars of the next k now
             self._lookahead_table(min(chunk, n_steps - done) if done < n_steps else k, inv_batch)
-            if return_losses:
-                buf = (C.c_float * (3 * k))()
-                hb.check(lib.iqlhip_read_loss_ring(self._ctx, buf, k, stream))
-                losses[done - k: done] = np.frombuffer(buf, dtype=np.float32).reshape(k, 3)
-            if return_stats:
-                sbuf = (C.c_float * (hb.IQLHIP_N_STATS * k))()
-                hb.check(lib.iqlhip_read_stats_ring(self._ctx, sbuf, k, stream))
-                stats[done - k: done] = np.frombuffer(sbuf, dtype=np.float32).reshape(k, hb.IQLHIP_N_STATS)
+            self._read_rings(k, stream, None if losses is None else losses[done - k: done],
+                             None if stats is None else stats[done - k: done])
         return (losses, stats) if return_stats else losses
 
     def train_steps_dp(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0) -> None:
