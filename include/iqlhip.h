@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 340          /* 0.3.4 */
+#define IQLHIP_VERSION 350          /* 0.3.5 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -520,6 +520,32 @@ int iqlhip_group_online_step_mixed(iqlhip_group* group, float* const* rows_dev, 
                                    const int32_t* n, const iqlhip_step_scalars* sc, float* out,
                                    const float* act_state_host, const int32_t* act_mask, const float* max_action,
                                    const uint64_t* act_seed, float* act_out_host, void* stream);
+/* Group calls on batches mixed from two replay buffers ("mixed offline / online batches" above, for every member in one
+ * set of launches; "replay2" because _mixed already names the per-member batch sizes above).  One pair serves equal
+ * and unequal batch sizes: every count is per member.
+ * iqlhip_group_online_step_replay2 is iqlhip_online_step_mixed for each member k: n[k] is the step's whole row count,
+ * the first n_off[k] of member k's n[k] indices (idx_host, laid out as for iqlhip_group_online_step_mixed) address
+ * rows_off_dev[k] (size_off[k] rows, stride ld, read only; members may share one), the other n[k] - n_off[k] its ring.
+ * Checked before any device work, per member, on top of iqlhip_group_online_step_mixed's checks: NULL or misaligned
+ * offline rows, size_off[k] < 1, n_off[k] outside [1, n[k] - 1], a ring that overlaps any member's offline rows
+ * (IQLHIP_EINVAL); offline indices within size_off[k], online ones within capacity[k] (IQLHIP_EINDEX); an exchange or
+ * more than 512 bf16 rows (IQLHIP_EUNSUPPORTED, the group rules). */
+int iqlhip_group_online_step_replay2(iqlhip_group* group, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                     const int64_t* pointer, const float* row_host, const int64_t* idx_host,
+                                     const int32_t* n, const iqlhip_step_scalars* sc, float* out,
+                                     const float* act_state_host, const int32_t* act_mask, const float* max_action,
+                                     const uint64_t* act_seed, float* act_out_host, void* stream,
+                                     const float* const* rows_off_dev, const int64_t* size_off, const int32_t* n_off);
+/* iqlhip_group_train_steps_replay2 is iqlhip_train_steps_mixed for each member k: step s draws the indices j = s * B[k]
+ * + r, r < B[k], of the member's stream (seeds[k], offsets[k]); row r < n_off[k] maps its bits over size_off[k] into
+ * rows_off[k], the others over size_on[k] into rows_on[k].  Losses, statistics and scalar tables as
+ * iqlhip_group_train_steps.  Checked before any device work, per member, on top of iqlhip_group_train_steps_mixed's
+ * checks: NULL or misaligned rows_on[k], rows_on[k] == rows_off[k], an empty buffer, n_off[k] outside [1, B[k] - 1]
+ * (IQLHIP_EINVAL). */
+int iqlhip_group_train_steps_replay2(iqlhip_group* group, const float* const* rows_off, const int64_t* size_off,
+                                     const float* const* rows_on, const int64_t* size_on, int64_t ld, const int32_t* B,
+                                     const int32_t* n_off, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                     const uint64_t* offsets, void* stream);
 /* Policy inference for every member of a group in one set of launches.  Member k maps its rows[k] states
  * (row stride ld_s) to rows[k] actions (row stride ld_a), exactly as iqlhip_actor_forward (seeds[k] == 0: the mean)
  * or iqlhip_actor_sample (seeds[k] != 0: device N(0,1) noise, member k's act() call counter advances by one) on that

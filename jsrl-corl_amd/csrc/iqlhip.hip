@@ -3166,10 +3166,26 @@ extern "C" int iqlhip_group_step_mixed(iqlhip_group* g, const iqlhip_batch* batc
   return group_step(g, batches, sc, out, stream, /*mixed=*/true);
 }
 
+// The second source of a two-source group call, per member (the group form of MixSrc): iqlhip_group_train_steps_replay2
+// draws batch rows >= n_off[i] over [0, size[i]) from rows[i] — the online buffers; iqlhip_group_online_step_replay2
+// reads batch rows < n_off[i] from rows[i] — the offline buffers of size[i] rows.
+struct GroupMixSrc { const float* const* rows; const int64_t* size; const int32_t* n_off; };
+// What both two-source group calls check per member (before any device work): the other buffer's rows, its size, and a
+// split that leaves both parts of a batch of B rows non-empty.
+static int group_check_mix(const GroupMixSrc* mx, int i, int32_t B, const char* what) {
+  if (!mx->rows[i]) return fail(IQLHIP_EINVAL, "member %d: NULL %s buffer", i, what);
+  if (((uintptr_t)mx->rows[i]) & 15) return fail(IQLHIP_EINVAL, "member %d: packed rows must be 16-byte aligned", i);
+  if (mx->size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty %s buffer", i, what);
+  if (mx->n_off[i] < 1 || mx->n_off[i] >= B)
+    return fail(IQLHIP_EINVAL, "member %d: n_off %d outside [1, batch_rows - 1 = %d]", i, mx->n_off[i], B - 1);
+  return IQLHIP_OK;
+}
+
 // iqlhip_group_train_steps (B: one count k times) and iqlhip_group_train_steps_mixed: member i draws B[i] rows a step.
+// iqlhip_group_train_steps_replay2 (mx != nullptr): rows / size are the offline buffers, mx the online ones.
 static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size, const int32_t* B,
                              const void* const* tables, int32_t n, const uint64_t* seeds, const uint64_t* offsets,
-                             void* stream) {
+                             void* stream, const GroupMixSrc* mx = nullptr) {
   if (!g || !rows || !size || !B || !tables || !seeds || !offsets) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = group_check_call(g, B);
   if (rc) return rc;
@@ -3179,6 +3195,9 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
     if (rc) return rc;
     if (size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty buffer", i);
     if (!tables[i]) return fail(IQLHIP_EINVAL, "member %d: NULL scalar table", i);
+    if (!mx) continue;
+    if ((rc = group_check_mix(mx, i, B[i], "online"))) return rc;
+    if (mx->rows[i] == rows[i]) return fail(IQLHIP_EINVAL, "member %d: the offline and the online buffer are the same rows", i);
   }
   for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   DevGuard guard(g->device);
@@ -3194,6 +3213,7 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
     GroupRec& r = g->train.host(g->recs)[i];
     group_record(g, r, i, q, B[i], n, c->xb, &tab[0], group_sched(g, i));
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
+    if (mx) { r.rows_on = mx->rows[i]; r.size_on = mx->size[i]; r.n_off = mx->n_off[i]; }
     memcpy(group_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
   }
   // actor dropout: one record per member (indexed like the GroupRecs; active = the member draws), step s at drop_step + s
@@ -3218,9 +3238,11 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
   const GroupRec* recs = g->train.device(g->recs);
   for (int s = 0; s < n; ++s) {
     if (draws)
-      hipLaunchKernelGGL(iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0, st, recs, g->train.device(g->drops), s);
+      hipLaunchKernelGGL(mx ? iql_gather2_drop_group_kernel : iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0,
+                         st, recs, g->train.device(g->drops), s);
     else
-      hipLaunchKernelGGL(iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st, recs, s);
+      hipLaunchKernelGGL(mx ? iql_gather2_group_kernel : iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st,
+                         recs, s);
     group_launch_step(g, recs, q, s, st, aux);
   }
   if (g->flags & IQLHIP_GROUP_DROPOUT)      // (as iqlhip_train_steps: the position of every context with a rate above 0)
@@ -3241,6 +3263,14 @@ extern "C" int iqlhip_group_train_steps_mixed(iqlhip_group* g, const float* cons
                                               const uint64_t* offsets, int32_t flags, void* stream) {
   (void)flags;
   return group_train_steps(g, rows, ld, size, B, tables, n, seeds, offsets, stream);
+}
+extern "C" int iqlhip_group_train_steps_replay2(iqlhip_group* g, const float* const* rows_off, const int64_t* size_off,
+                                                const float* const* rows_on, const int64_t* size_on, int64_t ld,
+                                                const int32_t* B, const int32_t* n_off, const void* const* tables, int32_t n,
+                                                const uint64_t* seeds, const uint64_t* offsets, void* stream) {
+  if (!rows_on || !size_on || !n_off) return fail(IQLHIP_EINVAL, "NULL argument");
+  const GroupMixSrc mx{rows_on, size_on, n_off};
+  return group_train_steps(g, rows_off, ld, size_off, B, tables, n, seeds, offsets, stream, &mx);
 }
 
 extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, void* stream) {
@@ -3274,12 +3304,13 @@ extern "C" int iqlhip_group_read_step_stats(iqlhip_group* g, float* out, int32_t
 // pinned words, then — members that asked for one — the next action with the updated policy, and one completion word
 // the host spins on.  Everything is checked before any device work and before any counter moves.
 // iqlhip_group_online_step (n: one count k times) and iqlhip_group_online_step_mixed: member i steps on n[i] rows, its
-// indices at idx_host[n[0] + ... + n[i - 1]].
+// indices at idx_host[n[0] + ... + n[i - 1]].  iqlhip_group_online_step_replay2 (mx != nullptr): the first mx->n_off[i] of
+// member i's n[i] indices address its offline buffer mx->rows[i], the others its ring.
 static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
                              const int64_t* pointer, const float* row_host, const int64_t* idx_host, const int32_t* n,
                              const iqlhip_step_scalars* sc, float* out, const float* act_state_host,
                              const int32_t* act_mask, const float* max_action, const uint64_t* act_seed,
-                             float* act_out_host, void* stream) {
+                             float* act_out_host, void* stream, const GroupMixSrc* mx = nullptr) {
   if (!g || !rows_dev || !capacity || !pointer || !row_host || !idx_host || !n || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (act_state_host && (!max_action || !act_seed || !act_out_host))
     return fail(IQLHIP_EINVAL, "act_state_host without max_action, act_seed or act_out_host");
@@ -3300,9 +3331,20 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
       const uintptr_t b0 = (uintptr_t)rows_dev[j], b1 = b0 + (uintptr_t)(capacity[j] * ld) * sizeof(float);
       if (a0 < b1 && b0 < a1) return fail(IQLHIP_EINVAL, "members %d and %d share ring rows (one buffer per member)", j, i);
     }
-    rc = check_host_indices(idx_host + idx0[i], n[i], capacity[i]);
+    const int n_off = mx ? mx->n_off[i] : 0;
+    if (mx && (rc = group_check_mix(mx, i, n[i], "offline"))) return rc;
+    if (n_off && (rc = check_host_indices(idx_host + idx0[i], n_off, mx->size[i]))) return rc;
+    rc = check_host_indices(idx_host + idx0[i] + n_off, n[i] - n_off, capacity[i]);
     if (rc) return rc;
   }
+  if (mx)      // (a ring is written by the launch that reads the offline rows: no member's ring may lie in an offline buffer)
+    for (int i = 0; i < K; ++i)
+      for (int j = 0; j < K; ++j) {
+        const uintptr_t a0 = (uintptr_t)rows_dev[i], a1 = a0 + (uintptr_t)(capacity[i] * ld) * sizeof(float);
+        const uintptr_t b0 = (uintptr_t)mx->rows[j], b1 = b0 + (uintptr_t)(mx->size[j] * ld) * sizeof(float);
+        if (a0 < b1 && b0 < a1)
+          return fail(IQLHIP_EINVAL, "member %d's ring overlaps member %d's offline buffer (the offline rows are read only)", i, j);
+      }
   for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
@@ -3335,6 +3377,7 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
     o.rows = rows_dev[i]; o.row_pin = c->on_row_pin; o.idx_pin = c->on_idx_pin; o.xb = c->xb;
     o.act_pin = req ? c->on_act_pin : nullptr; o.xb_act = c->xb_act;
     o.ld = ld; o.pointer = pointer[i]; o.n = n[i]; o.S = S;
+    o.rows_off = mx ? mx->rows[i] : nullptr; o.n_off = mx ? mx->n_off[i] : 0;
     if (with_adrops) adrops[i] = act_drop_record(c, req ? 1 : 0);
     if (!req) continue;
     memcpy(c->on_act_pin, act_state_host + (size_t)i * S, (size_t)S * sizeof(float));
@@ -3355,10 +3398,11 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
   HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
   const int gather_nb = (int)((q.max_rows * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
   if (act_draws)
-    hipLaunchKernelGGL(iql_online_gather_drop_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers),
-                       on.device(g->on_adrops));
+    hipLaunchKernelGGL(mx ? iql_online_gather2_drop_group_kernel : iql_online_gather_drop_group_kernel, dim3(gather_nb, K),
+                       dim3(256), 0, st, on.device(g->on_gathers), on.device(g->on_adrops));
   else
-    hipLaunchKernelGGL(iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, on.device(g->on_gathers));
+    hipLaunchKernelGGL(mx ? iql_online_gather2_group_kernel : iql_online_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0,
+                       st, on.device(g->on_gathers));
   for (int i = 0; i < K; ++i) refresh_shadows(g->m[i], st);
   group_launch_dropmask(g, on.device(g->on_drops), n_draw, q.max_rows, st);
   group_launch_step(g, on.device(g->on_recs), q, 0, st, aux);
@@ -3399,6 +3443,18 @@ extern "C" int iqlhip_group_online_step_mixed(iqlhip_group* g, float* const* row
                                               void* stream) {
   return group_online_step(g, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, act_mask,
                            max_action, act_seed, act_out_host, stream);
+}
+extern "C" int iqlhip_group_online_step_replay2(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                                const int64_t* pointer, const float* row_host, const int64_t* idx_host,
+                                                const int32_t* n, const iqlhip_step_scalars* sc, float* out,
+                                                const float* act_state_host, const int32_t* act_mask,
+                                                const float* max_action, const uint64_t* act_seed, float* act_out_host,
+                                                void* stream, const float* const* rows_off_dev, const int64_t* size_off,
+                                                const int32_t* n_off) {
+  if (!rows_off_dev || !size_off || !n_off) return fail(IQLHIP_EINVAL, "NULL argument");
+  const GroupMixSrc mx{rows_off_dev, size_off, n_off};
+  return group_online_step(g, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, act_mask,
+                           max_action, act_seed, act_out_host, stream, &mx);
 }
 
 // Policy inference of every member (iqlhip_actor_forward / iqlhip_actor_sample for each, include/iqlhip.h) in one set
@@ -3587,4 +3643,74 @@ extern "C" int iqlhip_train_steps_mixed(iqlhip_ctx* c, const float* rows_off_dev
   if (size_on < 1) return fail(IQLHIP_EINVAL, "empty online buffer");
   const MixSrc mx{rows_on_dev, n_off};
   return train_steps(c, rows_off_dev, ld, size_off, B, sc, K, seed, stream_offset, 0, stream, &mx, size_on);
+}
+
+// ---------------------------------------------------------------------------
+// The two-source gathers in group form (iqlhip_group_online_step_replay2 / iqlhip_group_train_steps_replay2; grid.y =
+// member, the arguments in the member's record).  Everything behind them is the group launch sequence of the plain calls.
+// iql_online_gather2_kernel per member, as online_gather_member is iql_online_gather_kernel per member: the ring write,
+// the act state's packing, and the gather — batch rows [0, n_off) from the member's offline buffer, rows [n_off, n) from
+// its ring, by the member's pinned indices (its n_off offline ones first).  A block's 256 float4 slots cover several rows
+// and may straddle n_off: the index cache holds both kinds, and the ROW decides which buffer an index addresses — only an
+// online index equal to `pointer` reads the pinned row.  The grid is sized for the largest n: a block past a member's own
+// n reads no index and writes no row.
+__device__ __forceinline__ void online_gather2_member(const GroupOnlineRec& g) {
+  __shared__ long long s_idx[260];
+  float* rows = g.rows;
+  const float* row_host = g.row_pin;
+  const long long ld = g.ld, pointer = g.pointer;
+  const int n = g.n, n_off = g.n_off;
+  const int q = (int)(ld >> 2);
+  const int e0 = (int)blockIdx.x * 256;
+  const int r_first = e0 / q;
+  const int r_last = min((e0 + 255) / q, n - 1);
+  if ((int)threadIdx.x <= r_last - r_first) s_idx[threadIdx.x] = g.idx_pin[r_first + threadIdx.x];
+  if (blockIdx.x == 0) {
+    for (int c4 = (int)threadIdx.x; c4 < q; c4 += 256)
+      *(f32x4*)(rows + pointer * ld + 4 * c4) = *(const f32x4*)(row_host + 4 * c4);
+    if (g.act_pin)
+      for (int c = (int)threadIdx.x; c < (int)ld; c += 256) g.xb_act[c] = (c < g.S) ? g.act_pin[c] : 0.f;
+  }
+  __syncthreads();
+  const int e = e0 + (int)threadIdx.x;
+  if (e < n * q) {
+    const int r = e / q, c4 = e - r * q;
+    const long long i = s_idx[r - r_first];
+    const float* src = (r < n_off) ? g.rows_off + i * ld : ((i == pointer) ? row_host : rows + i * ld);
+    *(f32x4*)(g.xb + (long long)r * ld + 4 * c4) = *(const f32x4*)(src + 4 * c4);
+  }
+}
+__global__ __launch_bounds__(256) void iql_online_gather2_group_kernel(const GroupOnlineRec* __restrict__ recs) {
+  online_gather2_member(recs[blockIdx.y]);
+}
+// ... plus the act forwards' keep-bits from the far end of the grid (iql_online_gather_drop_group_kernel's split).
+__global__ __launch_bounds__(256) void iql_online_gather2_drop_group_kernel(const GroupOnlineRec* __restrict__ recs,
+                                                                            const ActDropRec* __restrict__ drops) {
+  online_gather2_member(recs[blockIdx.y]);
+  const ActDropRec& d = drops[blockIdx.y];
+  if (d.active)
+    act_drop_words(d, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+}
+
+// iql_gather_group_kernel / iql_gather_drop_group_kernel with every member's step drawn from its two buffers: index
+// j = s * B + r of the member's one stream, mapped over `size` into `rows` (offline) for r < n_off and over size_on into
+// rows_on for the others — gather_rows_drawn2, the draw of iqlhip_train_steps_mixed.
+__global__ __launch_bounds__(256) void iql_gather2_group_kernel(const GroupRec* __restrict__ recs, int step) {
+  const GroupRec& r = recs[blockIdx.y];
+  const int s = min(max(step, 0), r.n_steps - 1);
+  gather_rows_drawn2(r.rows, r.rows_on, r.ld, r.xb, r.B, r.n_off, r.seed, r.offset,
+                     (unsigned long long)s * (unsigned long long)r.B, (unsigned long long)r.size,
+                     (unsigned long long)r.size_on, (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+}
+__global__ __launch_bounds__(256) void iql_gather2_drop_group_kernel(const GroupRec* __restrict__ recs,
+                                                                     const GroupDropRec* __restrict__ drops, int step) {
+  const GroupRec& r = recs[blockIdx.y];
+  const int s = min(max(step, 0), r.n_steps - 1);
+  gather_rows_drawn2(r.rows, r.rows_on, r.ld, r.xb, r.B, r.n_off, r.seed, r.offset,
+                     (unsigned long long)s * (unsigned long long)r.B, (unsigned long long)r.size,
+                     (unsigned long long)r.size_on, (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+  const GroupDropRec& d = drops[blockIdx.y];
+  if (d.active)
+    group_drop_words(d, d.step0 + (unsigned long long)s, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x,
+                     (int)gridDim.x * 256);
 }

@@ -1102,6 +1102,11 @@ struct GroupRec {
   float* xb;
   int B;
   int n_steps;                        // steps of the call: bounds every index derived from a launch's step argument
+  // two-source batches (iqlhip_group_train_steps_replay2; read by the iql_gather2_*group kernels alone, null / 0 in every
+  // other call): `rows` / `size` are the offline buffer, batch rows r >= n_off are drawn over [0, size_on) from rows_on
+  const float* rows_on;
+  long long size_on;
+  int n_off;
 };
 
 template <bool BF16, bool W0DMA, bool MULTI>
@@ -1865,6 +1870,10 @@ struct GroupOnlineRec {
   float* xb_act;                      // its inference staging
   long long ld, pointer;
   int n, S;
+  // two-source batches (iqlhip_group_online_step_replay2; read by the iql_online_gather2_*group kernels alone): batch rows
+  // [0, n_off) are rows_off[idx_pin[r]] (the member's offline buffer, read only), rows [n_off, n) come from the ring
+  const float* rows_off;
+  int n_off;
 };
 // Per requesting member: the arguments iql_actor_finish_kernel takes (one row).
 struct GroupActRec {
@@ -1917,6 +1926,15 @@ __global__ __launch_bounds__(256) void iql_online_gather_drop_group_kernel(const
   if (d.active)
     act_drop_words(d, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
 }
+
+// (the group forms of the two-source gathers — iqlhip_group_online_step_replay2 / iqlhip_group_train_steps_replay2 — are
+//  defined with the other two-source kernels: end of iqlhip.hip)
+__global__ __launch_bounds__(256) void iql_online_gather2_group_kernel(const GroupOnlineRec* __restrict__ recs);
+__global__ __launch_bounds__(256) void iql_online_gather2_drop_group_kernel(const GroupOnlineRec* __restrict__ recs,
+                                                                            const ActDropRec* __restrict__ drops);
+__global__ __launch_bounds__(256) void iql_gather2_group_kernel(const GroupRec* __restrict__ recs, int step);
+__global__ __launch_bounds__(256) void iql_gather2_drop_group_kernel(const GroupRec* __restrict__ recs,
+                                                                     const GroupDropRec* __restrict__ drops, int step);
 
 // The policy-inference forward (iql_fwd_kernel<BF16, W0DMA, false, true>: only_inst = 6, blockIdx.x = row tile *
 // NSPLIT + column slice) for the members that asked for an action: grid.y = requesting member, ps[j] its StepParams.

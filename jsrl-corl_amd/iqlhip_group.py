@@ -46,6 +46,14 @@ train() then takes batches of different row counts, and train_steps() / online_s
 one int per member; the launches are the same in number, and member k still ends where its solo steps at its own
 size end.  Without mixed_batch=True unequal sizes are refused (ValueError), as before the option existed.
 
+Batches mixed from an offline and an online replay buffer (the reference's Cal-QL mixing_ratio; for one trainer
+ImplicitQLearning.online_step_mixed / train_steps_mixed) have group forms too — "replay mix", since "mixed" already
+names the batch sizes above:
+
+    logs = group.online_step_replay_mix(offline, rings, states, actions, rewards, next_states, dones, 256,
+                                        mixing_ratio=[0.25, 0.5, 0.5, 0.75])
+    losses = group.train_steps_replay_mix(offline, rings, 1000, 256, seeds=[0, 1, 2, 3], mixing_ratio=0.5)
+
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
@@ -420,6 +428,202 @@ class ImplicitQLearningGroup:
         if act_next is None:
             return logs
         return logs, [a_out[k].copy() if k in want else None for k in range(K)]
+
+    # ------------------------------------------------------------------ batches mixed from an offline and an online buffer
+    def _replay_mix_args(self, offline_buffers, online_buffers, batch_size, mixing_ratio, burst: bool):
+        """What both replay-mix calls check before anything is launched, drawn or moved.  Returns (offline buffers,
+        online buffers, batch sizes, n_off), each a list of K."""
+        import iqlhip_mixed as mixed
+        K = len(self.trainers)
+        offs = list(offline_buffers) if isinstance(offline_buffers, (list, tuple)) else [offline_buffers] * K
+        if not isinstance(online_buffers, (list, tuple)) or len(online_buffers) != K or len(offs) != K:
+            raise ValueError(f"iqlhip: a replay-mix call of a group of {K} needs online_buffers as a list of {K} entries "
+                             f"and {K} offline buffers (or one shared offline buffer)")
+        ons = list(online_buffers)
+        if isinstance(mixing_ratio, (int, float, np.integer, np.floating)):
+            ratios = [float(mixing_ratio)] * K
+        else:
+            ratios = [float(r) for r in mixing_ratio]
+            if len(ratios) != K:
+                raise ValueError(f"iqlhip: {len(ratios)} mixing ratios for a group of {K}")
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
+        self._check_members()
+        n_offs = [mixed.split(B, r)[0] for B, r in zip(Bs, ratios)]
+        for t, off, on in zip(self.trainers, offs, ons):
+            mixed.check_buffers(off, on, t._dev, t._S, t._A)
+        for B in Bs:
+            self._check_batch_size(B)
+        for i, (off, on) in enumerate(zip(offs, ons)):
+            if off._size < 1:
+                raise ValueError(f"iqlhip: the offline replay buffer is empty (member {i})")
+            if burst and on._size < 1:
+                raise ValueError(f"iqlhip: the online replay buffer is empty (member {i})")
+        for i, on in enumerate(ons):      # (a ring is written in the launch that reads the offline rows)
+            if any(on is b or on._rows.data_ptr() == b._rows.data_ptr() for b in ons[:i]):
+                raise ValueError(f"iqlhip: member {i} shares an online replay buffer with an earlier member (one ring "
+                                 "each)")
+            if any(on is b or on._rows.data_ptr() == b._rows.data_ptr() for b in offs):
+                raise ValueError(f"iqlhip: member {i}'s online replay buffer is a member's offline buffer (the offline "
+                                 "rows are read only)")
+        if len({b._ld for b in offs + ons}) != 1:
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        return offs, ons, Bs, n_offs
+
+    def online_step_replay_mix(self, offline_buffers, online_buffers, states, actions, rewards, next_states, dones,
+                               batch_size, mixing_ratio=0.5, act_next: Optional[Sequence] = None,
+                               rngs: Optional[Sequence[np.random.RandomState]] = None):
+        """online_step with every member's batch mixed from two buffers (ImplicitQLearning.online_step_mixed for each,
+        in member order, in ONE library call): member k stores its transition in online_buffers[k] and trains on
+        n_off[k] = int(batch_size[k] * mixing_ratio[k]) rows of offline_buffers[k] followed by batch_size[k] - n_off[k]
+        rows of its ring.  offline_buffers: one buffer shared by all members, or a list of K (only read);
+        online_buffers: K distinct rings, none of them any member's offline buffer.  batch_size: an int, or one int per
+        member (unequal sizes: mixed_batch groups only); mixing_ratio: a float, or one per member (any group).  The
+        host index draw is the solo call's — per member, the offline draw, then the online draw over the size after
+        the insert — from rngs[k], or from the global np.random in member order when rngs is None.  act_next, rngs and
+        the return value as online_step.  Everything is checked before anything is drawn, launched or moved."""
+        import iqlhip_mixed as mixed
+        K = len(self.trainers)
+        per = {"states": states, "actions": actions, "rewards": rewards, "next_states": next_states, "dones": dones}
+        if act_next is not None:
+            per["act_next"] = act_next
+        if rngs is not None:
+            per["rngs"] = rngs
+        for name, v in per.items():
+            if not isinstance(v, (list, tuple)) or len(v) != K:
+                raise ValueError(f"iqlhip: online_step_replay_mix of a group of {K} needs {name} as a list of {K} entries")
+        offs, ons, Bs, n_offs = self._replay_mix_args(offline_buffers, online_buffers, batch_size, mixing_ratio, burst=False)
+        if act_next is not None:         # (before any ring, counter or parameter moves)
+            self._check_eval_forward([k for k in range(K) if act_next[k] is not None],
+                                     "online_step_replay_mix(act_next=...)")
+        if K == 1 and rngs is None:      # a group of one IS the solo call
+            an = None if act_next is None else act_next[0]
+            res = self.trainers[0].online_step_mixed(offs[0], ons[0], states[0], actions[0], rewards[0], next_states[0],
+                                                     dones[0], Bs[0], mixing_ratio if np.isscalar(mixing_ratio)
+                                                     else mixing_ratio[0], act_next=an)
+            if act_next is None:
+                return [res]
+            if an is None:
+                return [res], [None]
+            return [res[0]], [res[1]]
+        for t, B in zip(self.trainers, Bs):
+            t._prepare(B)
+        ld = ons[0]._ld
+        t0 = self.trainers[0]
+        S, A = t0._S, t0._A
+        rows = np.zeros((K, ld), dtype=np.float32)
+        for k in range(K):
+            rows[k, :S] = np.asarray(states[k], dtype=np.float32).reshape(-1)
+            rows[k, S: S + A] = np.asarray(actions[k], dtype=np.float32).reshape(-1)
+            rows[k, S + A: 2 * S + A] = np.asarray(next_states[k], dtype=np.float32).reshape(-1)
+            rows[k, 2 * S + A] = np.float32(rewards[k])
+            rows[k, 2 * S + A + 1] = np.float32(dones[k])
+        want = [k for k in range(K) if act_next is not None and act_next[k] is not None]
+        a_in = a_out = mask = max_a = seeds = None
+        if want:
+            a_in = np.zeros((K, S), dtype=np.float32)
+            for k in want:
+                a_in[k] = np.asarray(act_next[k], dtype=np.float32).reshape(-1)
+            a_out = np.zeros((K, A), dtype=np.float32)
+            mask = np.array([k in want for k in range(K)], dtype=np.int32)
+            max_a = np.array([float(t.actor.max_action) for t in self.trainers], dtype=np.float32)
+            seeds = np.array([t._act_seed() if (t.actor.training and t._gaussian) else 0 for t in self.trainers],
+                             dtype=np.uint64)
+        # (the buffers' and the trainers' counters move only once the library call has succeeded)
+        pointers = [b._pointer for b in ons]
+        new_sizes = [min(b._size + 1, b._buffer_size) for b in ons]
+        idx = []                         # (per member: its offline indices, then its online ones — the batch order)
+        for k in range(K):
+            if rngs is None:
+                pair = mixed.draw_host_indices(offs[k]._size, n_offs[k], new_sizes[k], Bs[k] - n_offs[k])
+            else:
+                pair = mixed.draw_host_indices(offs[k]._size, n_offs[k], new_sizes[k], Bs[k] - n_offs[k], rng=rngs[k])
+            idx.extend(pair)
+        idx = np.ascontiguousarray(np.concatenate(idx), dtype=np.int64)
+        scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
+        out = (C.c_float * (3 * K))()
+
+        def addr(a):
+            return None if a is None else a.ctypes.data
+
+        rc = hb.lib().iqlhip_group_online_step_replay2(
+            self._group(), (C.c_void_p * K)(*[b._rows.data_ptr() for b in ons]), ld,
+            (C.c_int64 * K)(*[b._buffer_size for b in ons]), (C.c_int64 * K)(*pointers), rows.ctypes.data, idx.ctypes.data,
+            (C.c_int32 * K)(*Bs), scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds), addr(a_out), t0._stream(),
+            (C.c_void_p * K)(*[b._rows.data_ptr() for b in offs]), (C.c_int64 * K)(*[b._size for b in offs]),
+            (C.c_int32 * K)(*n_offs))
+        hb.check(rc)
+        for k, buf in enumerate(ons):
+            buf._writes += 1
+            buf._pointer = (pointers[k] + 1) % buf._buffer_size
+            buf._size = new_sizes[k]
+        logs = self._commit_step(adam_next, out)
+        if act_next is None:
+            return logs
+        return logs, [a_out[k].copy() if k in want else None for k in range(K)]
+
+    def train_steps_replay_mix(self, offline_buffers, online_buffers, n_steps: int, batch_size, seeds: Sequence[int],
+                               mixing_ratio=0.5, return_losses: bool = True, chunk: int = K_MAX,
+                               return_stats: bool = False):
+        """train_steps with every member's batches mixed from two buffers (ImplicitQLearning.train_steps_mixed for each):
+        member k draws train_steps_mixed's stream under seeds[k] — batch row r < n_off[k] over offline_buffers[k]'s
+        size, the others over online_buffers[k]'s, both sizes read at the call.  Buffers, batch_size and mixing_ratio as
+        online_step_replay_mix (the online buffers are only read here, but must hold rows); returns what train_steps
+        returns.  As the solo call, a burst neither continues nor leaves staged rows."""
+        K = len(self.trainers)
+        seeds = [int(s) for s in seeds]
+        if len(seeds) != K:
+            raise ValueError(f"iqlhip: a group of {K} needs {K} seeds")
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        offs, ons, Bs, n_offs = self._replay_mix_args(offline_buffers, online_buffers, batch_size, mixing_ratio, burst=True)
+        if return_stats and not any(t._step_stats for t in self.trainers):
+            raise ValueError("iqlhip: train_steps_replay_mix(return_stats=True) needs set_step_stats(True) on at least one "
+                             "member")
+        if K == 1:      # a group of one IS the solo call
+            out = self.trainers[0].train_steps_mixed(offs[0], ons[0], n_steps, Bs[0], mixing_ratio if np.isscalar(mixing_ratio)
+                                                     else mixing_ratio[0], seed=seeds[0], return_losses=return_losses,
+                                                     chunk=chunk, return_stats=return_stats)
+            if return_stats:
+                return out[1][:, None]
+            return None if out is None else out[None]
+        for t, B in zip(self.trainers, Bs):
+            t._prepare(B)
+        for t in self.trainers:
+            t._refuse_injected_masks()
+        inv = [1.0 / B for B in Bs]
+        chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
+        lib, stream = hb.lib(), self.trainers[0]._stream()
+        g = self._group()
+        rows_off = (C.c_void_p * K)(*[b._rows.data_ptr() for b in offs])
+        size_off = (C.c_int64 * K)(*[b._size for b in offs])
+        rows_on = (C.c_void_p * K)(*[b._rows.data_ptr() for b in ons])
+        size_on = (C.c_int64 * K)(*[b._size for b in ons])
+        seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
+        B_arr, n_off_arr = (C.c_int32 * K)(*Bs), (C.c_int32 * K)(*n_offs)
+        halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
+        losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
+        stats = np.empty((n_steps, K, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
+        done = 0
+        while done < n_steps:
+            k = min(chunk, n_steps - done)
+            offsets = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
+            tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
+            tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
+            rc = lib.iqlhip_group_train_steps_replay2(g, rows_off, size_off, rows_on, size_on, offs[0]._ld, B_arr, n_off_arr,
+                                                      tab_ptrs, k, seed_arr, offsets, stream)
+            for t in self.trainers:
+                t._ts_token = None
+            hb.check(rc)
+            for t in self.trainers:
+                t.total_it += k
+            if return_losses:
+                out = (C.c_float * (K * k * 3))()
+                hb.check(lib.iqlhip_group_read_losses(g, out, k, stream))
+                losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
+            if return_stats:
+                stats[done:done + k] = self._group_stats(k)
+            done += k
+        return stats if return_stats else losses
 
     # ------------------------------------------------------------------ policy inference
     def _actor_call(self, rows: Sequence[int], in_ptrs, ld_s: int, out_ptrs, ld_a: int, seeds, max_action,

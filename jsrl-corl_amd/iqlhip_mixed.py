@@ -46,11 +46,13 @@ def check_buffers(offline_buffer, online_buffer, device, state_dim: int, action_
         raise ValueError("iqlhip: the two buffers have different packed row strides")
 
 
-def draw_host_indices(size_off: int, n_off: int, size_on: int, n_on: int) -> Tuple[np.ndarray, np.ndarray]:
+def draw_host_indices(size_off: int, n_off: int, size_on: int, n_on: int, rng=None) -> Tuple[np.ndarray, np.ndarray]:
     """The reference's draw from the global numpy RNG, in its order: the offline sample() first, then the online one
-    (over the online buffer's size AFTER this iteration's insert).  int64 arrays (idx_off, idx_on)."""
+    (over the online buffer's size AFTER this iteration's insert).  int64 arrays (idx_off, idx_on).  rng: a
+    np.random.RandomState to draw from instead (a trainer group's member with a stream of its own)."""
     if size_off < 1:
         raise ValueError("iqlhip: the offline replay buffer is empty")
-    idx_off = np.random.randint(0, size_off, size=n_off)
-    idx_on = np.random.randint(0, size_on, size=n_on)
+    rng = np.random if rng is None else rng
+    idx_off = rng.randint(0, size_off, size=n_off)
+    idx_on = rng.randint(0, size_on, size=n_on)
     return idx_off.astype(np.int64, copy=False), idx_on.astype(np.int64, copy=False)
