@@ -29,12 +29,13 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 350          /* 0.3.5 */
+#define IQLHIP_VERSION 360          /* 0.3.6 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
 #define IQLHIP_MAX_WORLD 8          /* ranks of one data-parallel group (the GPUs of one node) */
 #define IQLHIP_GRAPH_STEPS 64       /* steps per captured hipGraph chunk of iqlhip_train_steps */
+#define IQLHIP_N_SCORE 8            /* floats per row of iqlhip_score_rows: v, next_v, q1, q2, target_q, adv, exp_adv, bc */
 #define IQLHIP_N_STATS 16           /* floats per step of the opt-in training statistics (iqlhip_set_step_stats) */
 
 enum {
@@ -440,6 +441,38 @@ int iqlhip_rows_reward_shift(float* rows_dev, int64_t ld, int32_t state_dim, int
  * max_episode_steps < 1, ld < iqlhip_row_stride(state_dim, action_dim). */
 /* Device-side index draw used by iqlhip_train_steps, exposed for tests. */
 int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed, uint64_t offset, void* stream);
+
+/* ---- scoring transitions without a step ----------------------------------------------------------
+ * What the networks think of n transitions, with no gradient step: per row IQLHIP_N_SCORE floats
+ *   v  next_v  q1  q2  target_q = min(qt1, qt2)  adv = target_q - v  exp_adv = min(exp(beta adv), exp_adv_max)
+ *   bc = the row's behaviour-cloning term (Gaussian policy: sum over action dims of -log_prob(a) with the clamped
+ *        log_std; deterministic: sum of (a - mu)^2)
+ * and over all n rows summary[11]: value_loss, q_loss (with the reference's / 2), actor_loss — the three losses of
+ * _update_v / _update_q / _update_policy (iql.py:482-534) as means over n — then the eight column means.
+ * Rows: packed replay rows [s | a | s' | r | d | pad] of stride ld (a multiple of 4, >= iqlhip_row_stride; 16-byte
+ * aligned), n_rows of them; either the range [row0, row0 + n) (idx_dev NULL) or the n rows idx_dev[0 .. n) names, in
+ * that order (row0 ignored).  out_dev: [n][IQLHIP_N_SCORE] floats, 16-byte aligned, or NULL (summary only); summary: 11
+ * host floats or NULL; not both NULL.  The policy is evaluated without dropout (actor.eval()).  Parameters are always
+ * the fp32 masters and the arithmetic fp32 MFMA, also in a context set to bf16 operands: a row's eight floats depend on
+ * the row and the parameters alone — not on n, chunk_rows, the row's place in the call or range / index addressing.
+ * The summary's sums are added per 32-row tile in fp32 and over tiles in double; they depend on how the call groups
+ * rows into tiles and chunks only in the last bits.
+ * chunk_rows: rows scored per launch sequence (0: the library's 65 536; larger values are cut to that; the scratch —
+ * head partials of one chunk — is allocated by the context's first call and sized by it, never by n).
+ * Before anything is launched: IQLHIP_EINVAL for n < 1, NULL rows, a range outside [0, n_rows], a negative chunk_rows
+ * or one that is no multiple of 32, misaligned pointers or stride, both outputs NULL; IQLHIP_ENOTBOUND before
+ * iqlhip_bind.  An index list is range-checked on the device in front of the forward (one small launch, then the call
+ * waits for its verdict): IQLHIP_EINDEX when an index lies outside [0, n_rows), and no row has been read.
+ * The call writes its own scratch, out_dev and summary — no parameter, moment or target, nothing of the step's
+ * staging, activations, slabs, chunk header, graph cache, random-stream counters, loss / statistics / clip rings.
+ * Legal on a data-parallel context (local, no exchange) and on a trainer group's member.  Synchronises `stream` when
+ * idx_dev or summary is given; otherwise it only queues work. */
+int iqlhip_score_rows(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int64_t n_rows, int64_t row0, int64_t n,
+                      const int64_t* idx_dev, float* out_dev, int32_t chunk_rows, float summary[11], void* stream);
+/* Five row-major device arrays (any row strides; b->rows of any size >= 1, b->idx_dev NULL) -> packed rows of stride
+ * iqlhip_row_stride at rows_out_dev, pad columns zero: what iqlhip_step does to a batch in front of its forward, into
+ * the caller's block — the way a five-tensor batch reaches iqlhip_score_rows. */
+int iqlhip_pack_rows(iqlhip_ctx* ctx, const iqlhip_batch* b, float* rows_out_dev, void* stream);
 
 /* ---- trainer groups -------------------------------------------------------------------------------------------
  * K independent agents (contexts) of the same shape stepped together: every kernel launch of a group step covers all

@@ -288,6 +288,14 @@ struct iqlhip_ctx {
   float* clip_host = nullptr;         // pinned [24]: staging of an upload of clip_dev at 0..11, landing pad of iqlhip_read_grad_clip at 12..
   hipEvent_t clip_up = nullptr;       // the last upload of the limits has read clip_host
   bool clip_up_pending = false;
+  // scoring without a step (iqlhip_score_rows; allocated by the first call, sized by a chunk of rows)
+  float* score_heads = nullptr;       // device [SCORE_CHUNK][HEAD_LD] scalar head partials
+  float* score_pi = nullptr;          // device [SCORE_CHUNK][A][NSPLIT] policy head partials
+  float* score_part = nullptr;        // device [SCORE_CHUNK / 32][SCORE_N_PART] tile partials
+  double* score_acc = nullptr;        // device [16]: the call's running sums
+  float* score_pin = nullptr;         // pinned, host-mapped [16]: the summary's landing words
+  unsigned long long* score_status = nullptr;   // pinned, host-mapped [2]: the index check's verdict, an offending index
+  bool score_lds_set = false;
   // the stream of the context's last step call (note_stream): iqlhip_set_grad_clip queues the new limits there
   hipStream_t last_stream = nullptr;
   bool has_last_stream = false;
@@ -3713,4 +3721,139 @@ __global__ __launch_bounds__(256) void iql_gather2_drop_group_kernel(const Group
   if (d.active)
     group_drop_words(d, d.step0 + (unsigned long long)s, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x,
                      (int)gridDim.x * 256);
+}
+
+// ---------------------------------------------------------------------------
+// Scoring transitions without a step (include/iqlhip.h "scoring transitions without a step"; kernels:
+// iqlhip_score_kernels.h).  The host walks the call in chunks of rows: forward (head partials into the scoring
+// scratch), row kernel (the eight columns, tile partials), finish kernel (running sums in double; the last chunk
+// writes the summary into host-mapped words).
+// (the kernels are included HERE, behind every other kernel of the file: the existing kernels keep their places in the
+//  code object, which the step time is sensitive to — see with_bools above)
+#include "iqlhip_score_kernels.h"
+#define SCORE_CHUNK 65536
+static size_t score_lds(const iqlhip_ctx* c) {
+  const int A = c->dims.action_dim, kq = c->dims.state_dim + A;
+  const size_t w0 = (kq <= W0_LDS_MAX_K) ? kq : ((c->dims.state_dim <= W0_LDS_MAX_K) ? c->dims.state_dim : 0);
+  return (size_t)(RT_ROWS * H0_LD + RT_ROWS * T64_LD + RT_ROWS * SCORE_XLD_MAX + (((A + 15) & ~15) * W2_LD + 32) + HID +
+                  (size_t)HID * w0) * sizeof(float);
+}
+static int ensure_score(iqlhip_ctx* c) {
+  if (!c->score_heads) {
+    const int rc = all_or_nothing(c->own, [&]() -> int {
+      Owned& own = c->own;
+      HIPCHK(own.dev(&c->score_heads, (size_t)SCORE_CHUNK * HEAD_LD * sizeof(float), 0));
+      HIPCHK(own.dev(&c->score_pi, (size_t)SCORE_CHUNK * c->dims.action_dim * NSPLIT * sizeof(float), 0));
+      HIPCHK(own.dev(&c->score_part, (size_t)(SCORE_CHUNK / RT_ROWS) * SCORE_N_PART * sizeof(float), 0));
+      HIPCHK(own.dev(&c->score_acc, 16 * sizeof(double), 0));
+      HIPCHK(own.pin(&c->score_pin, 16 * sizeof(float), /*zero=*/true));
+      HIPCHK(own.pin(&c->score_status, 2 * sizeof(unsigned long long), /*zero=*/true));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
+  }
+  if (!c->score_lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)&iql_score_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)score_lds(c)));
+    c->score_lds_set = true;
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_score_rows(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t n_rows, int64_t row0, int64_t n,
+                                 const int64_t* idx_dev, float* out_dev, int32_t chunk_rows, float* summary, void* stream) {
+  if (!c || !rows_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!c->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_bind has not been called");
+  if (!out_dev && !summary) return fail(IQLHIP_EINVAL, "nothing to write: out_dev and summary are both NULL");
+  if (n < 1) return fail(IQLHIP_EINVAL, "n = %lld rows to score", (long long)n);
+  if (n_rows < 1) return fail(IQLHIP_EINVAL, "n_rows = %lld", (long long)n_rows);
+  if (ld < c->row_ld || (ld & 3)) return fail(IQLHIP_EINVAL, "row stride %lld: need a multiple of 4 >= %lld", (long long)ld, (long long)c->row_ld);
+  if ((((uintptr_t)rows_dev) | ((uintptr_t)out_dev)) & 15) return fail(IQLHIP_EINVAL, "rows and out must be 16-byte aligned");
+  if (!idx_dev && (row0 < 0 || row0 > n_rows || n > n_rows - row0))
+    return fail(IQLHIP_EINVAL, "rows [%lld, %lld) outside the buffer's [0, %lld)", (long long)row0, (long long)(row0 + n), (long long)n_rows);
+  if (chunk_rows < 0 || (chunk_rows % RT_ROWS)) return fail(IQLHIP_EINVAL, "chunk_rows %d: need 0 or a positive multiple of %d", chunk_rows, RT_ROWS);
+  const int64_t chunk = (chunk_rows == 0) ? SCORE_CHUNK : std::min<int64_t>(chunk_rows, SCORE_CHUNK);
+  DevGuard guard(c->device);
+  int rc = ensure_score(c);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (idx_dev) {      // the whole list, in front of any forward: nothing reads a row before the verdict is in
+    c->score_status[0] = 0; c->score_status[1] = 0;
+    const int nb = (int)std::min<int64_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(iql_score_check_idx_kernel, dim3(nb), dim3(256), 0, st, (const long long*)idx_dev, (long long)n,
+                       (long long)n_rows, c->score_status);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    if (((volatile unsigned long long*)c->score_status)[0])
+      return fail(IQLHIP_EINDEX, "index %lld is out of bounds for dimension 0 with size %lld",
+                  (long long)((volatile unsigned long long*)c->score_status)[1], (long long)n_rows);
+  }
+  const iqlhip_layout& L = c->L;
+  const float* tb = c->target - L.target_src;
+  const int S = c->dims.state_dim, A = c->dims.action_dim;
+  ScoreParams p;
+  memset(&p, 0, sizeof p);
+  // instances: V(s'), V(s), Qt1, Qt2, Q1, Q2, pi (make_step's order) — the fp32 masters whatever the context's precision
+  p.inst[0] = net_ptrs(L.net[IQLHIP_NET_V], c->params);  p.xoff[0] = S + A;
+  p.inst[1] = net_ptrs(L.net[IQLHIP_NET_V], c->params);
+  p.inst[2] = net_ptrs(L.net[IQLHIP_NET_Q1], tb);
+  p.inst[3] = net_ptrs(L.net[IQLHIP_NET_Q2], tb);
+  p.inst[4] = net_ptrs(L.net[IQLHIP_NET_Q1], c->params);
+  p.inst[5] = net_ptrs(L.net[IQLHIP_NET_Q2], c->params);
+  p.inst[6] = net_ptrs(L.net[IQLHIP_NET_PI], c->params);
+  p.rows = rows_dev; p.ld = ld; p.A = A;
+  p.heads = c->score_heads; p.pi = c->score_pi;
+  ScoreRowsParams q;
+  memset(&q, 0, sizeof q);
+  q.rows = rows_dev; q.ld = ld; q.S = S; q.A = A; q.policy = c->dims.policy; q.hy = c->hyper;
+  q.log_std = (L.net[IQLHIP_NET_PI].log_std >= 0) ? c->params + L.net[IQLHIP_NET_PI].log_std : nullptr;
+  q.heads = c->score_heads; q.pi = c->score_pi; q.part = c->score_part;
+  const size_t lds = score_lds(c);
+  // two blocks per CU where their LDS allows it; a group = the 28 (instance, column slice) blocks of one tile stream
+  const int slots = c->n_cus * ((lds <= (size_t)80 * 1024) ? 2 : 1);
+  for (int64_t done = 0; done < n; done += chunk) {
+    const int m = (int)std::min<int64_t>(chunk, n - done);
+    const int n_tiles = (m + RT_ROWS - 1) / RT_ROWS;
+    p.idx = idx_dev ? (const long long*)idx_dev + done : nullptr;
+    p.row0 = row0 + done; p.n = m; p.n_tiles = n_tiles;
+    const int ngrp = std::max(1, std::min(n_tiles, slots / 28));
+    hipLaunchKernelGGL(iql_score_fwd_kernel, dim3(28 * ngrp), dim3(256), lds, st, p);
+    q.idx = p.idx; q.row0 = p.row0; q.n = m; q.n_tiles = n_tiles;
+    q.out = out_dev ? out_dev + (size_t)done * IQLHIP_N_SCORE : nullptr;
+    hipLaunchKernelGGL(iql_score_rows_kernel, dim3((n_tiles + 3) / 4), dim3(256), 0, st, q);
+    if (summary) {
+      const bool last = done + chunk >= n;
+      hipLaunchKernelGGL(iql_score_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)c->score_part, n_tiles, c->score_acc,
+                         done == 0 ? 1 : 0, (long long)n, last ? c->score_pin : (float*)nullptr);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  if (summary) {
+    HIPCHK(hipStreamSynchronize(st));
+    for (int j = 0; j < 11; ++j) summary[j] = ((volatile float*)c->score_pin)[j];
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_pack_rows(iqlhip_ctx* c, const iqlhip_batch* b, float* rows_out_dev, void* stream) {
+  if (!c || !b || !rows_out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (b->rows < 1) return fail(IQLHIP_EINVAL, "batch rows %d", b->rows);
+  if (b->idx_dev) return fail(IQLHIP_EINVAL, "iqlhip_pack_rows takes no index list");
+  if (!b->s_dev || !b->a_dev || !b->r_dev || !b->ns_dev || !b->d_dev) return fail(IQLHIP_EINVAL, "NULL batch tensor");
+  if (b->ld_s < c->dims.state_dim || b->ld_ns < c->dims.state_dim || b->ld_a < c->dims.action_dim || b->ld_r < 1 || b->ld_d < 1)
+    return fail(IQLHIP_EINVAL, "batch row strides smaller than the row widths");
+  if (((uintptr_t)rows_out_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
+  DevGuard guard(c->device);
+  const int64_t ld = c->row_ld;
+  const int64_t slice = 1 << 20;        // rows per launch: iql_pack_kernel counts elements in 32 bits
+  for (int64_t r0 = 0; r0 < b->rows; r0 += slice) {
+    const int m = (int)std::min<int64_t>(slice, b->rows - r0);
+    const int64_t total = (int64_t)m * ld;
+    hipLaunchKernelGGL(iql_pack_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65536)), dim3(256), 0,
+                       (hipStream_t)stream, rows_out_dev + r0 * ld, (int)ld, c->dims.state_dim, c->dims.action_dim, m,
+                       b->s_dev + r0 * b->ld_s, (long long)b->ld_s, b->a_dev + r0 * b->ld_a, (long long)b->ld_a,
+                       b->r_dev + r0 * b->ld_r, (long long)b->ld_r, b->ns_dev + r0 * b->ld_ns, (long long)b->ld_ns,
+                       b->d_dev + r0 * b->ld_d, (long long)b->ld_d);
+  }
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
 }

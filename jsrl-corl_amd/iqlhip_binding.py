@@ -22,6 +22,9 @@ IQLHIP_N_STATS = 16           # floats per step of the opt-in training statistic
 STAT_NAMES = ("v_mean", "next_v_mean", "q1_mean", "q2_mean", "target_q_mean", "td_target_mean", "q_gap_mean",
               "adv_mean", "adv_min", "adv_max", "adv_pos_frac", "exp_adv_mean", "exp_adv_clamped_frac",
               "grad_norm_vf", "grad_norm_qf", "grad_norm_actor")
+IQLHIP_N_SCORE = 8            # floats per row of iqlhip_score_rows (include/iqlhip.h)
+# their names, in the library's order (ImplicitQLearning.score_buffer)
+SCORE_NAMES = ("v", "next_v", "q1", "q2", "target_q", "adv", "exp_adv", "bc")
 IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
 IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the actions are written
 IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train with actor dropout
@@ -194,6 +197,9 @@ SYMBOLS = [
     ("iqlhip_set_grad_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("iqlhip_get_grad_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("iqlhip_read_grad_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
+    ("iqlhip_score_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
+    ("iqlhip_pack_rows", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

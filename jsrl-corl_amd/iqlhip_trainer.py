@@ -726,6 +726,79 @@ class ImplicitQLearning:
                                              seed, None if a_out is None else a_out.ctypes.data, self._stream()))
         return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
 
+    # ---- scoring without a step (iqlhip_score.py) -------------------------------------------------
+    def _score_call(self, rows_ptr: int, ld: int, n_rows: int, start: int, n: int, idx, out, summary: bool, chunk: int):
+        """The library call behind score_buffer / score / evaluate; every argument has been checked."""
+        if self._hyper_tuple() != self._hyper_sent:      # beta, discount, iql_tau: what the next step would send too
+            h = self._hyper_struct()
+            hb.check(hb.lib().iqlhip_set_hyper(self._ctx, C.byref(h)))
+            self._hyper_sent = self._hyper_tuple()
+        if idx is not None and not (isinstance(idx, torch.Tensor) and idx.device == self._dev):
+            idx = torch.as_tensor(idx).to(self._dev)
+        if idx is not None:
+            idx = idx.contiguous()
+        if out is None:
+            out = torch.empty((n, hb.IQLHIP_N_SCORE), dtype=torch.float32, device=self._dev)
+        words = (C.c_float * 11)() if summary else None
+        hb.check(hb.lib().iqlhip_score_rows(
+            self._ctx, rows_ptr, ld, n_rows, start, n, None if idx is None else idx.data_ptr(),
+            None if out is False else out.data_ptr(), chunk, words, self._stream()))
+        import iqlhip_score as score
+        return (None if out is False else out), (score.summary_dict(words) if summary else None)
+
+    def score_buffer(self, buffer, start: int = 0, n: Optional[int] = None, indices=None, out=None, summary: bool = True,
+                     chunk_rows: Optional[int] = None):
+        """What the networks think of transitions of `buffer`, without a gradient step: (scores, summary).  scores is an
+        [n, 8] float32 tensor on the buffer's device with the columns hb.SCORE_NAMES — v, next_v, q1, q2, target_q
+        (the target nets' minimum), adv, exp_adv (clamped at 100), bc (the row's behaviour-cloning term) — of the rows
+        [start, start + n) (n=None: to the buffer's end) or of the rows `indices` names, in its order (a 1-D int64
+        tensor or array, host or device).  out: a tensor to write into, or False to skip the per-row store.  summary: a
+        dict of value_loss, q_loss, actor_loss — train()'s three, as means over the n rows — and mean_<column>; None when
+        summary=False.  The policy is evaluated as actor.eval() would (no dropout); parameters are the fp32 masters and
+        the arithmetic fp32, also after set_precision("bf16").  A row's eight numbers do not depend on n, chunk_rows,
+        its place in the call or how it is addressed.  Nothing the trainer holds changes.  ValueError for a CPU buffer,
+        foreign dims or stride, an empty buffer or range, a range beyond len(buffer), a wrong out, both start / n and
+        indices; IndexError for an index outside the buffer; RuntimeError on a CPU trainer — all before any row is read.
+        Not part of the reference's surface."""
+        import iqlhip_score as score
+        self._require_gpu()
+        size = score.check_buffer(buffer, self._dev, self._S, self._A, hb.row_stride(self._S, self._A))
+        start, count, idx = score.resolve_rows(size, start, n, indices)
+        if out is not None and out is not False:
+            score.check_out(out, count, self._dev)
+        if out is False and not summary:
+            raise ValueError("iqlhip: nothing to compute (out=False and summary=False)")
+        chunk = score.check_chunk_rows(chunk_rows)
+        return self._score_call(buffer._rows.data_ptr(), buffer._ld, size, start, count, idx, out, summary, chunk)
+
+    def score(self, batch: TensorBatch, out=None, summary: bool = True, chunk_rows: Optional[int] = None):
+        """score_buffer for a five-tensor batch as train() takes it, of any length: the batch is packed into a temporary
+        block of rows and scored there."""
+        import iqlhip_score as score
+        self._require_gpu()
+        b, keep, B = self._batch_struct(batch)
+        if B < 1:
+            raise ValueError("iqlhip: an empty batch")
+        if out is not None and out is not False:
+            score.check_out(out, B, self._dev)
+        if out is False and not summary:
+            raise ValueError("iqlhip: nothing to compute (out=False and summary=False)")
+        chunk = score.check_chunk_rows(chunk_rows)
+        ld = hb.row_stride(self._S, self._A)
+        block = torch.empty((B, ld), dtype=torch.float32, device=self._dev)
+        hb.check(hb.lib().iqlhip_pack_rows(self._ctx, C.byref(b), block.data_ptr(), self._stream()))
+        res = self._score_call(block.data_ptr(), ld, B, 0, B, None, out, summary, chunk)
+        if not summary:      # (with a summary the call has waited for the stream; otherwise the block must outlive it)
+            block.record_stream(torch.cuda.current_stream(self._dev))
+        del keep
+        return res
+
+    def evaluate(self, batch: TensorBatch) -> Dict[str, float]:
+        """train()'s three keys for `batch`, computed without a step: nothing the trainer holds changes.  The policy is
+        in eval mode (no dropout), as actor.eval() would be."""
+        _, summary = self.score(batch, out=False, summary=True)
+        return {k: summary[k] for k in ("value_loss", "q_loss", "actor_loss")}
+
     # ---- batches mixed from an offline and an online buffer (iqlhip_mixed.py; DESIGN.md 6g) ----------------------
     def _mixed_args(self, offline_buffer, online_buffer, batch_size: int, mixing_ratio: float) -> Tuple[int, int]:
         """The checks both mixed calls make before anything is launched or any counter moves; returns (n_off, n_on)."""
