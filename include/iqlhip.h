@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 360          /* 0.3.6 */
+#define IQLHIP_VERSION 370          /* 0.3.7 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -466,7 +466,7 @@ int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed
  * The call writes its own scratch, out_dev and summary — no parameter, moment or target, nothing of the step's
  * staging, activations, slabs, chunk header, graph cache, random-stream counters, loss / statistics / clip rings.
  * Legal on a data-parallel context (local, no exchange) and on a trainer group's member.  Synchronises `stream` when
- * idx_dev or summary is given; otherwise it only queues work. */
+ * idx_dev or summary is given; otherwise it only queues work.  (All members of a group: iqlhip_group_score_rows.) */
 int iqlhip_score_rows(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int64_t n_rows, int64_t row0, int64_t n,
                       const int64_t* idx_dev, float* out_dev, int32_t chunk_rows, float summary[11], void* stream);
 /* Five row-major device arrays (any row strides; b->rows of any size >= 1, b->idx_dev NULL) -> packed rows of stride
@@ -593,6 +593,45 @@ int iqlhip_group_train_steps_replay2(iqlhip_group* group, const float* const* ro
 int iqlhip_group_actor_forward(iqlhip_group* group, const float* const* states, int64_t ld_s, const int32_t* rows,
                                const uint64_t* seeds, const float* max_action, float* const* actions, int64_t ld_a,
                                int32_t flags, void* stream);
+
+/* ---- group scoring (DESIGN.md 6h "group scoring") -----------------------------------------------------------------
+ * iqlhip_score_rows for every member of a group in one set of launches (grid.y = member): per chunk one forward, one
+ * row kernel, one spread kernel (spread_dev given) and one finish kernel (summary given), whatever K is (chunks of a
+ * few thousand rows and more: the forward as a few launches over some of the members each, where that fills the device).
+ * Rows: member k scores the n rows [row0, row0 + n) of rows_dev[k] (n_rows[k] packed rows of stride ld, as
+ * iqlhip_score_rows), or, with idx_dev, the n rows idx_dev[k][0 .. n) names, in that order.  rows_dev, n_rows, idx_dev
+ * and out_dev are host tables of K entries; pointers may repeat across members (one shared buffer, one shared index
+ * list).  One n for all members.
+ * Outputs: out_dev NULL, or K pointers, each NULL (no per-row store for that member) or a 16-byte aligned
+ * [n][IQLHIP_N_SCORE] array; summary NULL, or K x 11 host floats, member k's at summary + 11 k in iqlhip_score_rows'
+ * order; spread_dev NULL, or [n][2 * IQLHIP_N_SCORE] floats, 16-byte aligned.  At least one of the three (an out_dev
+ * table of K NULLs counts as none).
+ * Spread: spread[i][j] = the mean over members of member k's column j of ITS i-th row, spread[i][8 + j] the population
+ * standard deviation of the same K values, in fixed fp32 arithmetic, members in order 0 .. K - 1:
+ *   mean = (x_0 + x_1 + ...) / K        dev = sqrtf((sum_k (x_k - mean)^2) / K)       (two passes, no fused multiply-add)
+ * Meaningful when all members score the same rows; that is not checked.  Available with every out_dev entry NULL.
+ * Which groups: every kind — plain, IQLHIP_GROUP_DROPOUT, members of different batch sizes, bf16 members.  As in the
+ * solo call the policy runs without dropout, parameters are the fp32 masters, the arithmetic is fp32 MFMA; each member
+ * uses its own hyper (beta, iql_tau, discount, exp_adv_max).
+ * Bitwise: member k's eight floats of a row are those iqlhip_score_rows on member k's context writes for that row —
+ * whatever K, the member's place in the group, n, chunk_rows, the grid, range or index addressing.  Member k's summary
+ * is bit for bit the solo call's over the same rows cut into the same chunks (other cuts: the last bits, as there).
+ * chunk_rows: rows of a member per launch sequence; 0 = the cap floor(65 536 / K / 32) * 32, larger values are cut to
+ * it.  The scratch belongs to the group, is sized by that cap (the K members together take what one solo context's
+ * scratch takes, plus [K][cap][8] floats for the rows of members without an out), is allocated whole or not at all by
+ * the group's first scoring call and released by iqlhip_group_destroy.  The members' own scoring scratch, and
+ * everything else iqlhip_score_rows leaves alone, is left alone here too.
+ * Before anything is launched: IQLHIP_EINVAL for a NULL group, table or entry, n < 1, a range outside any member's
+ * [0, n_rows[k]], a bad ld, chunk_rows or alignment, nothing to write; IQLHIP_ENOTBOUND for an unbound member.  Index
+ * lists are checked on the device by ONE launch over all members and one host wait, no row read: IQLHIP_EINDEX, and
+ * iqlhip_last_error names the member and the index.
+ * Synchronises `stream` when idx_dev or summary is given; otherwise it only queues work.  The call's records travel in
+ * stream order, and an upload is skipped when they equal the last one's: a group's asynchronous scoring calls must all
+ * be queued on ONE stream (back to back they each use their own records); a call on another stream has no order
+ * against an upload still in flight, so synchronise before changing streams. */
+int iqlhip_group_score_rows(iqlhip_group* group, const float* const* rows_dev, int64_t ld, const int64_t* n_rows,
+                            int64_t row0, int64_t n, const int64_t* const* idx_dev, float* const* out_dev,
+                            float* spread_dev, int32_t chunk_rows, float* summary /* [K][11] or NULL */, void* stream);
 
 /* ---- policy inference ---------------------------------------------------- */
 /* GaussianPolicy.act (algorithms/finetune/iql.py:371-379), DeterministicPolicy.act (:404-413) and the batched policy

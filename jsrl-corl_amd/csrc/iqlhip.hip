@@ -2729,6 +2729,7 @@ struct AuxSections {
   }
 };
 
+struct ScoreParams; struct ScoreRowsParams; struct ScoreGroupAux;      // (iqlhip_score_kernels.h, included further down)
 struct iqlhip_group {
   int k = 0;
   int device = 0;
@@ -2771,6 +2772,23 @@ struct iqlhip_group {
   std::vector<char> act_host, act_last;
   hipEvent_t act_up = nullptr;
   bool act_pending = false;
+  // iqlhip_group_score_rows: the scratch of a chunk of every member — member i's regions start at i * score_chunk rows
+  // (score_chunk = the largest chunk a member scores: 65 536 / k rows, so the k members together take what one solo
+  // context's scratch takes) — and the call's records, which go the way the act records go (score_host / score_last /
+  // score_up).  All of it is allocated by the group's first scoring call; a group that never scores holds none.
+  int score_chunk = 0;
+  float* score_heads = nullptr;       // device [k][score_chunk][HEAD_LD]
+  float* score_pi = nullptr;          // device [k][score_chunk][A][NSPLIT]
+  float* score_part = nullptr;        // device [k][score_chunk / 32][SCORE_N_PART]
+  float* score_out = nullptr;         // device [k][score_chunk][IQLHIP_N_SCORE]: rows of members without an out (for the spread)
+  double* score_acc = nullptr;        // device [k][16]: the call's running sums
+  float* score_pin = nullptr;         // pinned, host-mapped [k][16]: the summaries' landing words
+  unsigned long long* score_status = nullptr;   // pinned, host-mapped [k][2]: the index check's verdicts
+  Staging score;
+  Section<ScoreParams> score_ps; Section<ScoreRowsParams> score_qs; Section<ScoreGroupAux> score_aux;
+  std::vector<char> score_host, score_last;
+  hipEvent_t score_up = nullptr;
+  bool score_pending = false;
 };
 
 static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
@@ -3830,6 +3848,201 @@ extern "C" int iqlhip_score_rows(iqlhip_ctx* c, const float* rows_dev, int64_t l
   if (summary) {
     HIPCHK(hipStreamSynchronize(st));
     for (int j = 0; j < 11; ++j) summary[j] = ((volatile float*)c->score_pin)[j];
+  }
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// iqlhip_score_rows for every member of a trainer group in one set of launches (include/iqlhip.h "group scoring").
+// Per chunk: one forward (a few for large chunks, see the loop), one row kernel, one spread kernel (when asked for) and one finish kernel (when a summary is
+// asked for), each with grid.y = member.  The members' records describe the whole call and are uploaded once; the
+// launches name the chunk.  Nothing of a member is written: parameters and targets are read, every intermediate lies
+// in the group's own scratch.
+static int64_t group_score_cap(int k) { return (int64_t)(SCORE_CHUNK / k / RT_ROWS) * RT_ROWS; }
+// what one more forward launch costs, in tiles of one block: about 12 us of launch and weight staging against 4.4 us a
+// tile (solo calls cut into smaller chunks, profiles/group_score_bench.txt)
+#define SCORE_LAUNCH_TILES 3
+static int ensure_group_score(iqlhip_group* g) {
+  const iqlhip_ctx* c0 = g->m[0];
+  if (!g->score_heads) {
+    const size_t K = (size_t)g->k, cap = (size_t)group_score_cap(g->k);
+    const size_t b_heads = K * cap * HEAD_LD * sizeof(float), b_pi = K * cap * c0->dims.action_dim * NSPLIT * sizeof(float),
+                 b_part = K * (cap / RT_ROWS) * SCORE_N_PART * sizeof(float), b_out = K * cap * IQLHIP_N_SCORE * sizeof(float);
+    Staging stg;
+    const int rc = all_or_nothing(g->own, [&]() -> int {
+      Owned& own = g->own;
+      HIPCHK(own.dev(&g->score_heads, b_heads, 0));
+      HIPCHK(own.dev(&g->score_pi, b_pi, 0));
+      HIPCHK(own.dev(&g->score_part, b_part, 0));
+      HIPCHK(own.dev(&g->score_out, b_out, 0));
+      HIPCHK(own.dev(&g->score_acc, K * 16 * sizeof(double), 0));
+      HIPCHK(own.pin(&g->score_pin, K * 16 * sizeof(float), /*zero=*/true));
+      HIPCHK(own.pin(&g->score_status, K * 2 * sizeof(unsigned long long), /*zero=*/true));
+      g->score_ps = stg.add<ScoreParams>(K);
+      g->score_qs = stg.add<ScoreRowsParams>(K);
+      g->score_aux = stg.add<ScoreGroupAux>(K);
+      if (int rc_s = stg.alloc(own)) return rc_s;
+      HIPCHK(own.event(&g->score_up, hipEventDisableTiming));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
+    g->score = stg;
+    g->score_chunk = (int)cap;
+    g->score_host.assign(stg.bytes, 0);
+    g->score_last.assign(stg.bytes, 1);      // (differs from any first call's records: the first call uploads)
+    g->score_pending = false;
+  }
+  // every call: the limit belongs to the kernel, not to the group, and another live group of other dims may have set its own
+  HIPCHK(hipFuncSetAttribute((const void*)&iql_score_fwd_group_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)score_lds(c0)));
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_score_rows(iqlhip_group* g, const float* const* rows_dev, int64_t ld, const int64_t* n_rows,
+                                       int64_t row0, int64_t n, const int64_t* const* idx_dev, float* const* out_dev,
+                                       float* spread_dev, int32_t chunk_rows, float* summary, void* stream) {
+  if (!g || !rows_dev || !n_rows) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n < 1) return fail(IQLHIP_EINVAL, "n = %lld rows to score", (long long)n);
+  if (chunk_rows < 0 || (chunk_rows % RT_ROWS)) return fail(IQLHIP_EINVAL, "chunk_rows %d: need 0 or a positive multiple of %d", chunk_rows, RT_ROWS);
+  if (((uintptr_t)spread_dev) & 15) return fail(IQLHIP_EINVAL, "spread must be 16-byte aligned");
+  int rc = group_check_members(g->m, g->k, g->flags);
+  if (rc) return rc;
+  const int K = g->k;
+  const iqlhip_ctx* c0 = g->m[0];
+  bool any_out = false;
+  for (int i = 0; i < K; ++i) {
+    if (!rows_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL rows", i);
+    if (idx_dev && !idx_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL index list", i);
+    float* o = out_dev ? out_dev[i] : nullptr;
+    if ((((uintptr_t)rows_dev[i]) | ((uintptr_t)o)) & 15) return fail(IQLHIP_EINVAL, "member %d: rows and out must be 16-byte aligned", i);
+    any_out = any_out || o;
+    if (n_rows[i] < 1) return fail(IQLHIP_EINVAL, "member %d: n_rows = %lld", i, (long long)n_rows[i]);
+    if (!idx_dev && (row0 < 0 || row0 > n_rows[i] || n > n_rows[i] - row0))
+      return fail(IQLHIP_EINVAL, "member %d: rows [%lld, %lld) outside the buffer's [0, %lld)", i, (long long)row0, (long long)(row0 + n), (long long)n_rows[i]);
+  }
+  if (!any_out && !spread_dev && !summary) return fail(IQLHIP_EINVAL, "nothing to write: out_dev, spread_dev and summary are all NULL");
+  if (ld < c0->row_ld || (ld & 3)) return fail(IQLHIP_EINVAL, "row stride %lld: need a multiple of 4 >= %lld", (long long)ld, (long long)c0->row_ld);
+  for (int i = 0; i < K; ++i)
+    if ((rc = group_check_bound(g, i))) return rc;
+  DevGuard guard(g->device);
+  if ((rc = ensure_group_score(g))) return rc;
+  const int64_t chunk = (chunk_rows == 0) ? g->score_chunk : std::min<int64_t>(chunk_rows, g->score_chunk);
+  hipStream_t st = (hipStream_t)stream;
+  const int S = c0->dims.state_dim, A = c0->dims.action_dim;
+  const size_t cap = (size_t)g->score_chunk;
+
+  // the members' records (written whole into score_host, whose padding bytes stay zero: equal records compare equal)
+  ScoreParams* ps = Staging::at(g->score_host.data(), g->score_ps);
+  ScoreRowsParams* qs = Staging::at(g->score_host.data(), g->score_qs);
+  ScoreGroupAux* aux = Staging::at(g->score_host.data(), g->score_aux);
+  ScoreSpreadSrc src;
+  long long src_step[IQLHIP_MAX_GROUP];
+  memset(&src, 0, sizeof src);
+  for (int i = 0; i < K; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    const iqlhip_layout& L = c->L;
+    const float* tb = c->target - L.target_src;
+    float* heads = g->score_heads + (size_t)i * cap * HEAD_LD;
+    float* pi = g->score_pi + (size_t)i * cap * A * NSPLIT;
+    ScoreParams& p = ps[i];
+    memset(&p, 0, sizeof p);
+    // instances: V(s'), V(s), Qt1, Qt2, Q1, Q2, pi (iqlhip_score_rows) — the fp32 masters whatever the members' precision
+    p.inst[0] = net_ptrs(L.net[IQLHIP_NET_V], c->params);  p.xoff[0] = S + A;
+    p.inst[1] = net_ptrs(L.net[IQLHIP_NET_V], c->params);
+    p.inst[2] = net_ptrs(L.net[IQLHIP_NET_Q1], tb);
+    p.inst[3] = net_ptrs(L.net[IQLHIP_NET_Q2], tb);
+    p.inst[4] = net_ptrs(L.net[IQLHIP_NET_Q1], c->params);
+    p.inst[5] = net_ptrs(L.net[IQLHIP_NET_Q2], c->params);
+    p.inst[6] = net_ptrs(L.net[IQLHIP_NET_PI], c->params);
+    p.rows = rows_dev[i]; p.ld = ld; p.A = A;
+    p.idx = idx_dev ? (const long long*)idx_dev[i] : nullptr;
+    p.row0 = row0;
+    p.heads = heads; p.pi = pi;
+    ScoreRowsParams& q = qs[i];
+    memset(&q, 0, sizeof q);
+    q.rows = rows_dev[i]; q.ld = ld; q.idx = p.idx; q.row0 = row0;
+    q.S = S; q.A = A; q.policy = c->dims.policy; q.hy = c->hyper;
+    q.log_std = (L.net[IQLHIP_NET_PI].log_std >= 0) ? c->params + L.net[IQLHIP_NET_PI].log_std : nullptr;
+    q.heads = heads; q.pi = pi;
+    q.part = g->score_part + (size_t)i * (cap / RT_ROWS) * SCORE_N_PART;
+    float* o = out_dev ? out_dev[i] : nullptr;
+    ScoreGroupAux& a = aux[i];
+    memset(&a, 0, sizeof a);
+    a.n_rows = n_rows[i];
+    a.status = g->score_status + 2 * i;
+    if (o) { q.out = o; a.out_step = IQLHIP_N_SCORE; }
+    else if (spread_dev) { q.out = g->score_out + (size_t)i * cap * IQLHIP_N_SCORE; a.out_step = 0; }
+    src.src[i] = q.out;
+    src_step[i] = a.out_step;
+  }
+  if (memcmp(g->score_host.data(), g->score_last.data(), g->score.bytes) != 0) {
+    if (g->score_pending) HIPCHK(hipEventSynchronize(g->score_up));    // the previous upload has read score.pin
+    g->score_pending = false;
+    memcpy(g->score.pin, g->score_host.data(), g->score.bytes);
+    HIPCHK(hipMemcpyAsync(g->score.dev, g->score.pin, g->score.bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(g->score_up, st));
+    g->score_pending = true;
+    g->score_last = g->score_host;
+  }
+  const ScoreParams* d_ps = g->score.device(g->score_ps);
+  const ScoreRowsParams* d_qs = g->score.device(g->score_qs);
+  const ScoreGroupAux* d_aux = g->score.device(g->score_aux);
+  if (idx_dev) {      // every member's whole list, in front of any forward: nothing reads a row before the verdict is in
+    memset(g->score_status, 0, (size_t)K * 2 * sizeof(unsigned long long));
+    const int nb = (int)std::min<int64_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(iql_score_check_idx_group_kernel<>, dim3(nb, K), dim3(256), 0, st, d_qs, d_aux, (long long)n, nb);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < K; ++i)
+      if (((volatile unsigned long long*)g->score_status)[2 * i])
+        return fail(IQLHIP_EINDEX, "member %d: index %lld is out of bounds for dimension 0 with size %lld", i,
+                    (long long)((volatile unsigned long long*)g->score_status)[2 * i + 1], (long long)n_rows[i]);
+  }
+  const size_t lds = score_lds(c0);
+  // two blocks per CU where their LDS allows it: `streams` tile streams of 28 blocks fill the device, as in the solo call
+  const int slots = c0->n_cus * ((lds <= (size_t)80 * 1024) ? 2 : 1);
+  const int streams = std::max(1, slots / 28);
+  for (int64_t done = 0; done < n; done += chunk) {
+    const int m = (int)std::min<int64_t>(chunk, n - done);
+    const int n_tiles = (m + RT_ROWS - 1) / RT_ROWS;
+    // The chunk's forward: ONE launch over all K members (streams / K tile streams each, rounded down) where that is
+    // cheapest — small chunks —, otherwise several launches over d members each, d dividing `streams`, so that every
+    // launch fills the device (K = 2 with 9 streams: 4 + 4 of them in one launch leave an eighth of the device idle,
+    // 9 and then 9 do not).  Costs in tile times of the slowest block; a launch's ramp is worth about
+    // SCORE_LAUNCH_TILES of them (profiles/group_score_bench.txt).  Any cut gives the same bits.
+    const int one_ngrp = std::max(1, std::min(n_tiles, streams / K));
+    const int64_t one_cost = (int64_t)((n_tiles + one_ngrp - 1) / one_ngrp) * ((28 * one_ngrp * K + slots - 1) / slots) + SCORE_LAUNCH_TILES;
+    int64_t cut_cost = 0;
+    for (int i0 = 0, d; i0 < K; i0 += d) {
+      for (d = std::min(K - i0, streams); streams % d; --d) {}
+      const int ngrp = std::min(n_tiles, streams / d);
+      cut_cost += (n_tiles + ngrp - 1) / ngrp + SCORE_LAUNCH_TILES;
+    }
+    const bool cut = cut_cost < one_cost;
+    for (int i0 = 0, d; i0 < K; i0 += d) {
+      d = K - i0;
+      if (cut)
+        for (d = std::min(d, streams); streams % d; --d) {}
+      const int ngrp = std::max(1, std::min(n_tiles, streams / d));
+      hipLaunchKernelGGL(iql_score_fwd_group_kernel<>, dim3(28 * ngrp, d), dim3(256), lds, st, d_ps + i0, (long long)done, m, ngrp);
+    }
+    hipLaunchKernelGGL(iql_score_rows_group_kernel<>, dim3((n_tiles + 3) / 4, K), dim3(256), 0, st, d_qs, d_aux, (long long)done, m);
+    if (spread_dev) {
+      ScoreSpreadSrc at = src;
+      for (int i = 0; i < K; ++i) at.src[i] = src.src[i] + done * src_step[i];
+      hipLaunchKernelGGL(iql_score_spread_group_kernel<>, dim3((m + 255) / 256), dim3(256), 0, st, at, K, m,
+                         spread_dev + (size_t)done * (2 * IQLHIP_N_SCORE));
+    }
+    if (summary) {
+      const bool last = done + chunk >= n;
+      hipLaunchKernelGGL(iql_score_finish_group_kernel<>, dim3(1, K), dim3(256), 0, st, d_qs, n_tiles, g->score_acc,
+                         done == 0 ? 1 : 0, (long long)n, last ? g->score_pin : (float*)nullptr);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  if (summary) {
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < K; ++i)
+      for (int j = 0; j < 11; ++j) summary[11 * i + j] = ((volatile float*)g->score_pin)[16 * i + j];
   }
   return IQLHIP_OK;
 }

@@ -25,6 +25,8 @@ STAT_NAMES = ("v_mean", "next_v_mean", "q1_mean", "q2_mean", "target_q_mean", "t
 IQLHIP_N_SCORE = 8            # floats per row of iqlhip_score_rows (include/iqlhip.h)
 # their names, in the library's order (ImplicitQLearning.score_buffer)
 SCORE_NAMES = ("v", "next_v", "q1", "q2", "target_q", "adv", "exp_adv", "bc")
+# the 16 columns of a group call's across-member spread (ImplicitQLearningGroup.score_buffer(spread=True))
+SPREAD_NAMES = tuple("mean_" + name for name in SCORE_NAMES) + tuple("std_" + name for name in SCORE_NAMES)
 IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
 IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the actions are written
 IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train with actor dropout
@@ -200,6 +202,9 @@ SYMBOLS = [
     ("iqlhip_score_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                     C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_pack_rows", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]),
+    ("iqlhip_group_score_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                          C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int32,
+                                          C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

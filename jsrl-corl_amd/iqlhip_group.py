@@ -54,6 +54,13 @@ names the batch sizes above:
                                         mixing_ratio=[0.25, 0.5, 0.5, 0.75])
     losses = group.train_steps_replay_mix(offline, rings, 1000, 256, seeds=[0, 1, 2, 3], mixing_ratio=0.5)
 
+Scoring without a step (ImplicitQLearning.score_buffer / score / evaluate) has group forms too: one set of launches
+for all members, each member's numbers bit for bit its solo call's, and — what no solo call can give — the
+across-member mean and standard deviation of every column per row:
+
+    scores, summaries, spread = group.score_buffer(buffer, indices=idx, spread=True)    # [K, n, 8], K dicts, [n, 16]
+    held_out = group.evaluate(batch)                                                     # K dicts of train()'s keys
+
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
@@ -700,3 +707,113 @@ class ImplicitQLearningGroup:
                 seeds.append(t._act_seed() if (n and sample and t._gaussian) else 0)
             self._actor_call(rows, ins, S, ptrs, A, seeds, mas)
         return outs
+
+    # ------------------------------------------------------------------ scoring without a step
+    def _score_call(self, row_ptrs, ld: int, sizes, start: int, n: int, idx_lists, out, summary: bool, spread,
+                    chunk: int):
+        """The library call behind score_buffer / score / evaluate; every argument has been checked."""
+        K = len(self.trainers)
+        t0 = self.trainers[0]
+        dev = t0._dev
+        for t in self.trainers:      # beta, discount, iql_tau of each member: what its next step would send too
+            if t._hyper_tuple() != t._hyper_sent:
+                h = t._hyper_struct()
+                hb.check(hb.lib().iqlhip_set_hyper(t._ctx, C.byref(h)))
+                t._hyper_sent = t._hyper_tuple()
+        idx_arr, keep = None, []
+        if idx_lists is not None:
+            ptrs = []
+            for k, idx in enumerate(idx_lists):
+                same = next((j for j in range(k) if idx_lists[j] is idx), None)
+                if same is not None:     # (one list for several members: one device copy)
+                    ptrs.append(ptrs[same])
+                    continue
+                if not (isinstance(idx, torch.Tensor) and idx.device == dev):
+                    idx = torch.as_tensor(idx).to(dev)
+                idx = idx.contiguous()
+                keep.append(idx)
+                ptrs.append(idx.data_ptr())
+            idx_arr = (C.c_void_p * K)(*ptrs)
+        if out is None:
+            out = torch.empty((K, n, hb.IQLHIP_N_SCORE), dtype=torch.float32, device=dev)
+        if spread is True:
+            spread = torch.empty((n, 2 * hb.IQLHIP_N_SCORE), dtype=torch.float32, device=dev)
+        elif spread is False:
+            spread = None
+        out_arr = None if out is False else (C.c_void_p * K)(*[out[k].data_ptr() for k in range(K)])
+        words = (C.c_float * (11 * K))() if summary else None
+        hb.check(hb.lib().iqlhip_group_score_rows(
+            self._group(), (C.c_void_p * K)(*row_ptrs), ld, (C.c_int64 * K)(*sizes), start, n, idx_arr, out_arr,
+            None if spread is None else spread.data_ptr(), chunk, words, t0._stream()))
+        del keep                     # (device copies of the lists: freed in stream order, behind the call's launches)
+        import iqlhip_score as score
+        summaries = [score.summary_dict(words[11 * k: 11 * k + 11]) for k in range(K)] if summary else None
+        return (None if out is False else out), summaries, spread
+
+    def score_buffer(self, buffers, start: int = 0, n: Optional[int] = None, indices=None, out=None, summary: bool = True,
+                     spread=False, chunk_rows: Optional[int] = None):
+        """ImplicitQLearning.score_buffer of every member in one set of launches: (scores, summaries, spread).
+        buffers: one replay buffer for all members, or a list of K.  The rows are the range [start, start + n) — it must
+        fit the smallest buffer; n=None: to its end — or the rows `indices` names: one list for all members, or a list
+        of K lists of equal length (1-D int64 tensors or arrays, host or device), member k's into buffers[k].
+        scores: a [K, n, 8] float32 device tensor (hb.SCORE_NAMES columns; out: a tensor to write into, or False: None);
+        scores[k] is bit for bit what trainers[k].score_buffer returns for those rows.  summaries: K dicts with
+        iqlhip_score.SUMMARY_KEYS, member k's equal to its solo call's at the same chunk_rows; None for summary=False.
+        spread: False, True or an [n, 16] tensor to write into: per row the mean over members of each of the eight
+        columns, then their population standard deviation (hb.SPREAD_NAMES), fp32, members in order; available with
+        out=False.  It is accepted only when all members score the same rows (one buffer with a range or one index
+        list): ValueError otherwise.  chunk_rows: rows of a member per launch sequence (at most 65 536 // K).  Each
+        member scores with its own hyper-parameters, in eval mode, with its fp32 masters.  Nothing any member holds
+        changes.  The refusals are score_buffer's, raised before anything is launched."""
+        import iqlhip_score as score
+        self._check_members()
+        K = len(self.trainers)
+        t0 = self.trainers[0]
+        bufs, one_buffer = score.group_buffers(buffers, K)
+        ld = hb.row_stride(t0._S, t0._A)
+        sizes = [score.check_buffer(b, t._dev, t._S, t._A, ld) for t, b in zip(self.trainers, bufs)]
+        start, count, idx_lists, one_list = score.group_rows(sizes, start, n, indices)
+        score.check_group_outputs(out, summary, spread, one_buffer and one_list, K, count, t0._dev)
+        chunk = score.check_chunk_rows(chunk_rows)
+        return self._score_call([b._rows.data_ptr() for b in bufs], ld, sizes, start, count, idx_lists, out, summary,
+                                spread, chunk)
+
+    def score(self, batches, out=None, summary: bool = True, spread=False, chunk_rows: Optional[int] = None):
+        """score_buffer for five-tensor batches as train() takes them: one batch for all members (packed once), or a
+        list of K batches of equal length (spread: the shared form only).  Returns (scores, summaries, spread)."""
+        import iqlhip_score as score
+        self._check_members()
+        K = len(self.trainers)
+        t0 = self.trainers[0]
+        shared = len(batches) > 0 and isinstance(batches[0], torch.Tensor)
+        blist = [batches] if shared else list(batches)
+        if not shared and len(blist) != K:
+            raise ValueError(f"iqlhip: {len(blist)} batches for a group of {K} (one shared batch, or one per member)")
+        structs, keep, Bs = [], [], []
+        for t, batch in zip(self.trainers, blist):
+            b, kp, B = t._batch_struct(batch)
+            structs.append(b)
+            keep.append(kp)
+            Bs.append(B)
+        if any(B != Bs[0] for B in Bs):
+            raise ValueError(f"iqlhip: the batches have {Bs} rows (one length for all members)")
+        B = Bs[0]
+        if B < 1:
+            raise ValueError("iqlhip: an empty batch")
+        score.check_group_outputs(out, summary, spread, shared, K, B, t0._dev)
+        chunk = score.check_chunk_rows(chunk_rows)
+        ld = hb.row_stride(t0._S, t0._A)
+        block = torch.empty((len(blist), B, ld), dtype=torch.float32, device=t0._dev)
+        for k, (t, b) in enumerate(zip(self.trainers, structs)):
+            hb.check(hb.lib().iqlhip_pack_rows(t._ctx, C.byref(b), block[k].data_ptr(), t0._stream()))
+        ptrs = [block[0 if shared else k].data_ptr() for k in range(K)]
+        res = self._score_call(ptrs, ld, [B] * K, 0, B, None, out, summary, spread, chunk)
+        if not summary:      # (with a summary the call has waited for the stream; otherwise the block must outlive it)
+            block.record_stream(torch.cuda.current_stream(t0._dev))
+        del keep
+        return res
+
+    def evaluate(self, batches) -> List[Dict[str, float]]:
+        """train()'s three keys of every member for its batch (or the one shared batch), computed without a step."""
+        _, summaries, _ = self.score(batches, out=False, summary=True)
+        return [{k: s[k] for k in ("value_loss", "q_loss", "actor_loss")} for s in summaries]
