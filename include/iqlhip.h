@@ -238,6 +238,48 @@ int iqlhip_train_steps_mixed(iqlhip_ctx* ctx, const float* rows_off_dev, int64_t
 int iqlhip_train_steps_mixed_prepare(iqlhip_ctx* ctx, const float* rows_off_dev, const float* rows_on_dev, int64_t ld,
                                      int32_t batch_rows, int32_t n_off, float inv_batch, void* stream);
 
+/* ---- weighted replay sampling ---------------------------------------------------------------------------------
+ * Rows drawn by weight instead of uniformly, on the device, from the index stream of iqlhip_train_steps unchanged.
+ * The distribution is defined in integers, so the device and a CPU restatement agree to the bit:
+ *   w[0..n) float32, all finite, all >= 0, at least one > 0, 1 <= n <= IQLHIP_WEIGHTS_MAX_ROWS;
+ *   e = floor(log2(max w)); q[i] = floor(w[i] * 2^(38 - e)) as uint64, taken from the fp32 bit pattern by shifts, so
+ *   max q lies in [2^38, 2^39) and a weight below max w * 2^-39 becomes 0: such a row is never drawn;
+ *   cum[i] = q[0] + ... + q[i]; total = cum[n - 1] < 2^63;
+ *   index j of a call takes the 64 random bits r of counter stream_offset + j / 2, word pair j & 1, under `seed` — what
+ *   iqlhip_draw_indices gives it — then t = mulhi64(r, total) and the index is the smallest i with cum[i] > t.
+ * With all weights equal that is floor(r * n / 2^64): the plain stream bit for bit.
+ *
+ * iqlhip_weights_build: validates w_dev[0..n) (device memory) and builds the table — cum plus the 64-ary search levels
+ * above it, 8 bytes per row plus 1/63 — in device memory of the current device; synchronises `stream`.  IQLHIP_EINVAL
+ * for a NaN, an infinity, a negative weight, all zeros or n out of range; nothing is returned then, and any table built
+ * before is untouched.  Every table gets a generation number no other table of the process has.
+ * iqlhip_weights_free: waits for the device, then frees the table (NULL: nothing).
+ * iqlhip_weights_info: n, total, the level count, the generation and — tests — a synchronous copy of cum[0..n) into
+ * cum_host (each may be NULL). */
+#define IQLHIP_WEIGHTS_MAX_ROWS (1 << 24)
+typedef struct iqlhip_weights iqlhip_weights;
+int iqlhip_weights_build(const float* w_dev, int64_t n, void* stream, iqlhip_weights** out);
+int iqlhip_weights_free(iqlhip_weights* table);
+int iqlhip_weights_info(const iqlhip_weights* table, int64_t* n, uint64_t* total, int32_t* levels, uint64_t* generation,
+                        uint64_t* cum_host);
+/* iqlhip_draw_indices with the weighted mapping: idx_dev[j], j < n_idx, of the stream (seed, offset).  One wave resolves
+ * one index by a 64-ary descent through the table. */
+int iqlhip_draw_indices_weighted(int64_t* idx_dev, int64_t n_idx, const iqlhip_weights* table, uint64_t seed,
+                                 uint64_t offset, void* stream);
+/* iqlhip_train_steps with every step's rows drawn by `table` (size must be the table's n): the idle blocks of each
+ * forward draw and gather the next step's rows, so a weighted call consumes exactly the counters a plain call does.
+ * IQLHIP_TS_CONTINUE is honoured only behind a weighted call on the same table GENERATION (and the conditions of
+ * iqlhip_train_steps); a plain call never continues a weighted one, nor the reverse.  The chunk graphs of weighted
+ * calls are a kind of their own, keyed by the table's address, n and level count as well.  IQLHIP_EUNSUPPORTED, before
+ * anything is launched or any counter moves: a data-parallel exchange attached, bf16 batches of more than 512 rows,
+ * injected keep-bits pending.  The table must outlive the call's queued work (iqlhip_weights_free waits for it).
+ * iqlhip_train_steps_weighted_prepare: iqlhip_train_steps_prepare for the chunk graphs of such calls. */
+int iqlhip_train_steps_weighted(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int64_t size, int32_t batch_rows,
+                                const iqlhip_step_scalars* sc, int32_t n_steps, uint64_t seed, uint64_t stream_offset,
+                                int32_t flags, void* stream, const iqlhip_weights* table);
+int iqlhip_train_steps_weighted_prepare(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int32_t batch_rows,
+                                        float inv_batch, void* stream, const iqlhip_weights* table);
+
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is
  * written to grads_dev for the caller's all-reduce, then the update consumes it. */

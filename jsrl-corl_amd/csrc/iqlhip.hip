@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -146,15 +147,21 @@ struct GraphKey {
   // are not its.  rows_on == nullptr: a plain chunk — never replayed for a mixed call on the same rows, nor the reverse
   const float* rows_on = nullptr;
   int32_t n_off = 0;
+  // weighted chunks (iqlhip_train_steps_weighted): the table the idle blocks draw by.  wt.tab == nullptr: not one
+  WTab wt{nullptr, 0u, 0};
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
            inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip &&
-           rows_on == o.rows_on && n_off == o.n_off;
+           rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n && wt.levels == o.wt.levels;
   }
 };
 // The second source of a mixed call, handed down to whatever forms a key, a set-up launch or an idle-work record
 // (nullptr everywhere: a plain call).  The online size is not here: it travels in the header (HDR_SIZE_ON).
-struct MixSrc { const float* rows_on; int n_off; };
+// A weighted call (iqlhip_train_steps_weighted) travels the same way: rows_on == nullptr, wt its table and wt_gen the
+// table's generation (what a following call must name to start on the rows this one staged).
+struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; };
+// Which forward a step of such a call launches: 0 iql_fwd_kernel, 1 iql_fwd_mixed_kernel, 2 iql_fwd_weighted_kernel.
+static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? 2 : 1); }
 
 // The few RCCL entry points the in-stream all-reduce needs, resolved at run time from the librccl.so.1 the process
 // already has (PyTorch-ROCm brings one) or can load — the library has no link-time dependency on RCCL.
@@ -220,6 +227,7 @@ struct iqlhip_ctx {
   unsigned long long sched_want[4] = {0, 0, 0, 0};
   unsigned long long call_seq = 0;
   unsigned* setup_arrivals = nullptr;           // device: block counter of iql_call_setup_kernel
+  bool weighted_lds_set = false;                // ... and the weighted ones (check_weighted_args)
   bool mixed_lds_set = false;                   // the mixed forward instantiations have their dynamic-LDS limit (check_mixed_args)
   char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (freeing it at the end of prepare
                                                 //   idles the GPU right in front of the caller's first steps)
@@ -255,7 +263,9 @@ struct iqlhip_ctx {
   // step that would come next; a following call that IS that step (same rows / size / batch / seed, counter position
   // where the previous call stopped, staging untouched in between) starts without gathering anything.
   struct { bool valid = false; const float* rows = nullptr; int64_t ld = 0, size = 0; int32_t B = 0; uint64_t seed = 0;
-           uint64_t next_offset = 0; float drop_p = 0.f; uint64_t drop_seed = 0, drop_step = 0; } cont;
+           uint64_t next_offset = 0; float drop_p = 0.f; uint64_t drop_seed = 0, drop_step = 0;
+           uint64_t wt_gen = 0;      // the table generation of a weighted call (0: a plain call)
+         } cont;
   std::vector<CachedGraph> graphs;
   unsigned long long graph_clock = 0;
   // data-parallel gradient exchange
@@ -842,8 +852,10 @@ static UpdParams make_upd(const iqlhip_ctx* c, const iqlhip_step_scalars* sc, in
 static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c->n_cus) ? c->lds_fwd_solo : c->lds_fwd; }
 
 static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);     // (end of file)
-static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, bool mixed = false) {
-  if (mixed) return launch_fwd_mixed_grid(c, p, nb, st);
+static void launch_fwd_weighted_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
+static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, int kind = 0) {
+  if (kind == 1) return launch_fwd_mixed_grid(c, p, nb, st);
+  if (kind == 2) return launch_fwd_weighted_grid(c, p, nb, st);
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
   // (policy inference — iqlhip_actor_forward — has its own instantiations)
@@ -864,7 +876,7 @@ static int fwd_spb_l2(const iqlhip_ctx* c, int n_rt) {
 // Blocks of a forward grid (per agent) over n_rt row tiles at 2^l2 slices per block.  (Full-width blocks: each XCD of
 // a net's pair takes the row tiles of one parity — iql_fwd_kernel's block map.)
 static int fwd_blocks(int n_rt, int l2) { return (l2 == 2) ? 8 * 2 * ((n_rt + 1) / 2) : 8 * n_rt * (NSPLIT >> l2); }
-static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st, bool mixed = false) {
+static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st, int kind = 0) {
   StepParams p = p_in;
   if (p.only_inst < 0 && use_lb(c, p.rows)) {
     const LbArgs a = lb_args(c, p.rows);
@@ -885,7 +897,7 @@ static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
   }
   const int n_rt = (p.rows + RT_ROWS - 1) / RT_ROWS;
   p.spb_l2 = fwd_spb_l2(c, n_rt);
-  launch_fwd_grid(c, p, fwd_blocks(n_rt, p.spb_l2), st, mixed);
+  launch_fwd_grid(c, p, fwd_blocks(n_rt, p.spb_l2), st, kind);
 }
 // Column slices per (b) block of the backward (log2): one while the whole grid — 4 nets x (32 dW1 tiles per 256-row
 // chunk + 4 slices per row tile) — is at most two rounds of the chip (up to 512 rows: measured equal or better), else 4:
@@ -1425,9 +1437,9 @@ static XchParams make_xch(const iqlhip_ctx* c, bool from_hdr) {
 // `k` = position inside the chunk (selects the P2P buffer together with `parity`, and the flag value hdr[XSTEP]+k+1).
 // `sa` (statistics enabled): the two statistics launches between the backward and the update — after the last reader
 // of `heads`, before the update kernel, which is the last reader of the slabs and, in a chunk, moves the header word
-// the ring slot is formed from.  `mixed`: a step of a two-source chunk (its forward is iql_fwd_mixed_kernel).
+// the ring slot is formed from.  `kind`: fwd_kind of the call (a two-source or a weighted chunk has a forward of its own).
 static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int mode, int parity, int k, bool from_hdr,
-                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, bool mixed = false) {
+                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, int kind = 0) {
   StepParams p = p_in;
   const int buf = (parity + k) & 1;
   // P2P with batches of <= 256 rows: no flatten kernel.  The backward writes its chunk slab (= the w1 / b1 / w2 / b2 /
@@ -1441,7 +1453,7 @@ static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int 
     for (int n = 0; n < 4; ++n) p.sc.slab_b_off[n] = c->xslab_b_off[n];
     p.sc.loss_parts = (float*)(c->xblk + c->xloss_off[buf]);
   }
-  launch_fwd(c, p, st, mixed);
+  launch_fwd(c, p, st, kind);
   if (ev) HIPCHK(hipEventRecord(ev[1], st));
   launch_bwd(c, p, st);
   if (ev) HIPCHK(hipEventRecord(ev[2], st));
@@ -1797,12 +1809,12 @@ static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_d
     i.drop_thresh = drop_thresh(c->drop_p);
     i.n = B;
     i.k = k;
-    if (mx) { i.rows_on = mx->rows_on; i.n_off = mx->n_off; }
+    if (mx) { i.rows_on = mx->rows_on; i.n_off = mx->n_off; i.wt = mx->wt; }
   }
 }
 
 static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_batch, int mode, int parity,
-                         const IdleWork* work_dev, bool mixed = false) {
+                         const IdleWork* work_dev, int kind = 0) {
   const int MB = c->dims.max_batch;
   iqlhip_step_scalars sc0;
   memset(&sc0, 0, sizeof sc0);
@@ -1822,7 +1834,7 @@ static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_
     // (statistics: slot BASE + k of the ring, the loss ring's indexing; the chunk's key carries the setting)
     StatsArgs sa;
     if (c->stats_on) sa = make_stats(c, p, c->stats_ring, k, c->k_max, c->hdr);
-    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, mixed);
+    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, kind);
     if (rc) return rc;
   }
   return IQLHIP_OK;
@@ -1850,8 +1862,9 @@ struct SetupArgs {
   const float* rows; long long ld; float* xb; int B; unsigned* drop_dst; int drop_words; unsigned drop_thresh;
   unsigned* arrivals; unsigned long long* ack; unsigned long long ack_val;
   const float* rows_on; int n_off;        // (iql_call_setup_mixed_kernel's two more)
+  WTab wt;                                // (iql_call_setup_weighted_kernel's one more, in their place)
   void* ptrs[17];
-  const void* func;                       // iql_call_setup_kernel, or its two-source form
+  const void* func;                       // iql_call_setup_kernel, its two-source or its weighted form
   int nb;
 };
 static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int slot, int n_steps, const float* rows_dev,
@@ -1870,12 +1883,17 @@ static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int 
   a.ack = slot >= 0 ? c->sched_ack + slot : c->sched_ack + 4;        // (slot < 0: a capture-time placeholder, word 4 is a dummy)
   a.ack_val = slot >= 0 ? c->sched_want[slot] : 0ull;
   a.rows_on = mx ? mx->rows_on : nullptr; a.n_off = mx ? mx->n_off : 0;
-  a.func = mx ? (const void*)iql_call_setup_mixed_kernel : (const void*)iql_call_setup_kernel;
+  const int kind = fwd_kind(mx);
+  a.wt = mx ? mx->wt : WTab{nullptr, 0u, 0};
+  a.func = kind == 2 ? (const void*)iql_call_setup_weighted_kernel
+                     : (kind == 1 ? (const void*)iql_call_setup_mixed_kernel : (const void*)iql_call_setup_kernel);
   void* p[17] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
                  &a.drop_words, &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val, &a.rows_on, &a.n_off};
+  if (kind == 2) { p[15] = &a.wt; p[16] = nullptr; }
   memcpy(a.ptrs, p, sizeof p);
   long long want = ((long long)n_steps * 3 + 255) / 256;
   if (gather) want = std::max(want, ((long long)B * (c->row_ld / 4) + 255) / 256);
+  if (gather && kind == 2) want = std::max(want, ((long long)B + 7) / 8);      // (a wave per row, two rows a pass)
   if (drop) want += (2 * MB * 8 + 255) / 256;
   a.nb = (int)std::max<long long>(1, std::min<long long>(want, 256));
 }
@@ -1890,8 +1908,8 @@ static int launch_call_setup(iqlhip_ctx* c, hipStream_t st, const ChunkHdr& h, i
 // Capture and instantiate the chunk graph of g.key into g, member by member (a failure leaves the ones made so far).
 static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   const GraphKey& key = g.key;
-  const MixSrc key_mx{key.rows_on, key.n_off};
-  const MixSrc* mx = key.rows_on ? &key_mx : nullptr;
+  const MixSrc key_mx{key.rows_on, key.n_off, key.wt};
+  const MixSrc* mx = (key.rows_on || key.wt.tab) ? &key_mx : nullptr;
   // the chunk's idle-work records: device memory written once, here (their content is part of what the key freezes)
   {
     std::vector<IdleWork> hw((size_t)key.K);
@@ -1914,7 +1932,7 @@ static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
     if (hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
       rc = fail(IQLHIP_EHIP, "capture of the set-up kernel failed");
   }
-  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, mx != nullptr);
+  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, fwd_kind(mx));
   e = hipStreamEndCapture(cs, &g.graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -1973,7 +1991,7 @@ static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld,
                          int parity, int head = 0, const MixSrc* mx = nullptr) {
   GraphKey key;
   key.head = head;
-  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; }
+  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; key.wt = mx->wt; }
   key.rows = rows_dev; key.ld = ld; key.B = B; key.K = K; key.params = c->params; key.drop_p = c->drop_p;
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
@@ -2011,7 +2029,7 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
   int r = chunk_graph(c, make_key(c, rows_dev, ld, B, n, inv_batch, parity, head_args ? 1 : 0, mx), &gexec, &cg);
   if (r) return r;
   if (g_direct_all && !head_args) {      // experiment: the chunk's kernels launched one by one instead of the graph replay
-    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, mx != nullptr);
+    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, fwd_kind(mx));
     if (r) return r;
     cg->last = st;
     if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
@@ -2169,7 +2187,11 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   }
   // does this call continue the previous one's index stream with its step 0 already staged?  (Never a mixed call: the
   // rows its last forward staged are not what a plain call would draw, so it claims nothing and leaves no token.)
-  const bool cont = !mx && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.rows == rows_dev && c->cont.ld == ld &&
+  // A weighted call continues a weighted call on the same table generation only, and a plain call a plain one.
+  const int kind = fwd_kind(mx);
+  const uint64_t wt_gen = kind == 2 ? mx->wt_gen : 0;
+  const bool cont = kind != 1 && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == wt_gen &&
+                    c->cont.rows == rows_dev && c->cont.ld == ld &&
                     c->cont.size == size && c->cont.B == B && c->cont.seed == seed && c->cont.next_offset == stream_offset &&
                     c->cont.drop_p == c->drop_p && c->cont.drop_seed == c->drop_seed && c->cont.drop_step == c->drop_step;
   c->cont.valid = false;
@@ -2201,7 +2223,7 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
     if (rc) return rc;
     rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, mx);
     if (rc) return rc;
-    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, mx != nullptr);
+    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, fwd_kind(mx));
     if (rc) return rc;
     cg->last = st;
     if (c->drop_p > 0.f) c->drop_step += (unsigned long long)head_k;
@@ -2229,8 +2251,9 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   if (ns > 0 && small[ns - 1] == 1) { rc = replay_chunk(c, st, rows_dev, ld, B, 1, inv_batch, nullptr, mx); if (rc) return rc; }
   // what a following call must look like to start on the rows this call's last forward has staged: an even number of
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
-  if (!mx && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
+  if (kind != 1 && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
+    c->cont.wt_gen = wt_gen;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
     c->cont.next_offset = stream_offset + ((unsigned long long)K * (unsigned long long)B) / 2ull;
     c->cont.drop_p = c->drop_p; c->cont.drop_seed = c->drop_seed; c->cont.drop_step = c->drop_step;
@@ -4069,4 +4092,164 @@ extern "C" int iqlhip_pack_rows(iqlhip_ctx* c, const iqlhip_batch* b, float* row
   }
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Weighted replay sampling (include/iqlhip.h "weighted replay sampling"; kernels: iqlhip_weighted_kernels.h, included
+// HERE, behind every other kernel of the file, as the scoring kernels are).  A table is an object of its own, not part
+// of a context: a replay buffer owns it, any context on its device may draw by it.  The multi-step driver above does
+// the rest (MixSrc::wt).
+#include "iqlhip_weighted_kernels.h"
+struct iqlhip_weights {
+  Owned own;                              // the table, and the build's scratch
+  int device = 0;
+  unsigned long long* tab = nullptr;      // level 0 = cum[0..n), then the search levels, each from a multiple of 64 entries
+  unsigned long long* tile_sums = nullptr;
+  unsigned* verdict = nullptr;            // iql_wt_validate_kernel's two words
+  int64_t n = 0;
+  int levels = 0;
+  uint64_t total = 0;
+  uint64_t gen = 0;                       // unique per built table: what IQLHIP_TS_CONTINUE compares
+};
+static std::atomic<uint64_t> g_weights_gen{0};
+
+// Sizes and offsets (in entries) of a table's levels over n rows; returns the level count.
+static int weights_levels(int64_t n, unsigned size[WT_MAX_LEVELS], unsigned off[WT_MAX_LEVELS], size_t* entries) {
+  unsigned s = (unsigned)n, o = 0;
+  int levels = 0;
+  for (int l = 0; l < WT_MAX_LEVELS; ++l) {
+    size[l] = s; off[l] = o;
+    o += (s + 63u) & ~63u;
+    if (!levels && s <= 64u) levels = l + 1;
+    s = (s + 63u) >> 6;
+  }
+  if (entries) *entries = o;
+  return levels;
+}
+static WTab weights_tab(const iqlhip_weights* t) { return WTab{t->tab, (unsigned)t->n, t->levels}; }
+
+extern "C" int iqlhip_weights_build(const float* w_dev, int64_t n, void* stream, iqlhip_weights** out) {
+  if (!w_dev || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n < 1 || n > IQLHIP_WEIGHTS_MAX_ROWS) return fail(IQLHIP_EINVAL, "n = %lld weights outside [1, 2^24]", (long long)n);
+  if (((uintptr_t)w_dev) & 3) return fail(IQLHIP_EINVAL, "weights must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  std::unique_ptr<iqlhip_weights> t(new iqlhip_weights);
+  HIPCHK(hipGetDevice(&t->device));
+  unsigned size[WT_MAX_LEVELS], off[WT_MAX_LEVELS];
+  size_t entries = 0;
+  t->n = n;
+  t->levels = weights_levels(n, size, off, &entries);
+  if (t->levels < 1) return fail(IQLHIP_EINVAL, "n = %lld weights need more than %d levels", (long long)n, WT_MAX_LEVELS);
+  const int n_tiles = (int)((n + WT_SCAN_TILE - 1) / WT_SCAN_TILE);        // <= WT_SCAN_TILE: one block scans their sums
+  // validation first: nothing but its two words exists until the weights have passed
+  HIPCHK(t->own.dev(&t->verdict, 2 * sizeof(unsigned), 0));
+  hipLaunchKernelGGL(iql_wt_validate_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, w_dev,
+                     (long long)n, t->verdict);
+  HIPCHK(hipGetLastError());
+  unsigned verdict[2] = {0u, 0u};
+  HIPCHK(hipMemcpyAsync(verdict, t->verdict, sizeof verdict, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (verdict[1] & 1u) return fail(IQLHIP_EINVAL, "weights hold a NaN or an infinity");
+  if (verdict[1] & 2u) return fail(IQLHIP_EINVAL, "weights hold a negative value");
+  if (!verdict[0]) return fail(IQLHIP_EINVAL, "all weights are zero");
+  // e = floor(log2(max w)) from the bit pattern; every q is the weight's significand shifted by (its exponent + 38 - e)
+  const unsigned ex = verdict[0] >> 23, frac = verdict[0] & 0x7FFFFFu;
+  const unsigned m = ex ? (frac | 0x800000u) : frac;
+  const int e = (ex ? (int)ex - 150 : -149) + (31 - __builtin_clz(m));
+  const int sh0 = 38 - e;
+  HIPCHK(t->own.dev(&t->tab, entries * sizeof(unsigned long long), 0));
+  HIPCHK(t->own.dev(&t->tile_sums, (size_t)n_tiles * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(iql_wt_tile_sums_kernel, dim3(n_tiles), dim3(256), 0, st, w_dev, (long long)n, sh0, t->tile_sums);
+  hipLaunchKernelGGL(iql_wt_scan_sums_kernel, dim3(1), dim3(256), 0, st, t->tile_sums, n_tiles);
+  hipLaunchKernelGGL(iql_wt_tile_scan_kernel, dim3(n_tiles), dim3(256), 0, st, w_dev, (long long)n, sh0,
+                     (const unsigned long long*)t->tile_sums, t->tab);
+  for (int l = 1; l < t->levels; ++l)
+    hipLaunchKernelGGL(iql_wt_level_kernel, dim3((size[l] + 255u) / 256u), dim3(256), 0, st,
+                       (const unsigned long long*)(t->tab + off[l - 1]), size[l - 1], t->tab + off[l], size[l]);
+  HIPCHK(hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, t->tab + (n - 1), sizeof total, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  t->total = total;
+  t->gen = ++g_weights_gen;
+  *out = t.release();
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_weights_free(iqlhip_weights* t) {
+  if (!t) return IQLHIP_OK;
+  DevGuard guard(t->device);
+  (void)hipDeviceSynchronize();           // a draw or a chunk that reads the table may still be queued
+  delete t;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_weights_info(const iqlhip_weights* t, int64_t* n, uint64_t* total, int32_t* levels, uint64_t* generation,
+                                   uint64_t* cum_host) {
+  if (!t) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n) *n = t->n;
+  if (total) *total = t->total;
+  if (levels) *levels = t->levels;
+  if (generation) *generation = t->gen;
+  if (cum_host) {
+    DevGuard guard(t->device);
+    HIPCHK(hipMemcpy(cum_host, t->tab, (size_t)t->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_draw_indices_weighted(int64_t* idx_dev, int64_t n_idx, const iqlhip_weights* table, uint64_t seed,
+                                            uint64_t offset, void* stream) {
+  if (!idx_dev || !table || n_idx < 1) return fail(IQLHIP_EINVAL, "bad argument");
+  const int nb = (int)std::min<int64_t>((n_idx + 7) / 8, 1024);      // a wave per index, two indices a pass
+  hipLaunchKernelGGL(iql_draw_indices_weighted_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (long long*)idx_dev,
+                     (long long)n_idx, weights_tab(table), (unsigned long long)seed, (unsigned long long)offset);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+static auto fwd_weighted_kernel(bool bf, bool dma, bool multi) {
+  return with_bools([](auto MU, auto BF, auto DMA) { return &iql_fwd_weighted_kernel<BF.value, DMA.value, MU.value>; }, multi, bf, dma);
+}
+static void launch_fwd_weighted_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
+  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
+  hipLaunchKernelGGL(fwd_weighted_kernel(c->precision == 1, dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
+}
+// Everything a weighted multi-step call is refused for, before anything is launched or any counter moves (pending
+// injected keep-bits: step_entry, as for iqlhip_train_steps).
+static int check_weighted_args(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
+                               const iqlhip_weights* table) {
+  int rc = check_train_args(c, rows_dev, ld, B);
+  if (rc) return rc;
+  if (!table) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (table->device != c->device) return fail(IQLHIP_EINVAL, "the table lives on device %d, the context on %d", table->device, c->device);
+  if (size != table->n) return fail(IQLHIP_EINVAL, "size %lld, but the table weighs %lld rows", (long long)size, (long long)table->n);
+  if (c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "weighted sampling is not supported with a data-parallel exchange");
+  if (use_lb(c, B))
+    return fail(IQLHIP_EUNSUPPORTED, "weighted sampling is not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+  if ((rc = inject_check(c))) return rc;
+  if (!c->weighted_lds_set) {
+    DevGuard guard(c->device);
+    rc = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_weighted_kernel(m & 1, m & 2, m & 4); });
+    if (rc) return rc;
+    c->weighted_lds_set = true;
+  }
+  return IQLHIP_OK;
+}
+extern "C" int iqlhip_train_steps_weighted_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, float inv_batch,
+                                                   void* stream, const iqlhip_weights* table) {
+  int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
+  if (rc) return rc;
+  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen};
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
+}
+extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
+                                           const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
+                                           int32_t flags, void* stream, const iqlhip_weights* table) {
+  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
+  if (rc) return rc;
+  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen};
+  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
 }

@@ -1,7 +1,7 @@
 // Body of the forward — included by iql_fwd_kernel and iql_fwd_group_kernel (iqlhip_kernels.h):
 // ONE body for the single-agent kernel and its trainer-group form, so the arithmetic exists once.  blockIdx.x / gridDim.x
 // are the block's index and grid size of ONE agent's launch in both (a group kernel's agent is blockIdx.y).
-// In scope: template flags BF16, W0DMA, MULTI, ONE, MIXED_IDLE (the idle blocks' work is a two-source chunk's), the
+// In scope: template flags BF16, W0DMA, MULTI, ONE, MIXED_IDLE (the idle blocks' work is a two-source chunk's; 2: a weighted chunk's), the
 // agent's `p` (StepParams) and ROW_EXIT: a block whose row tile
 // lies outside the agent's batch exits under every block map (iql_fwd_group_kernel only: its grid.x is the largest
 // member's; a single agent's one- and two-slice grids are sized exactly and compile without the test).

@@ -360,6 +360,13 @@ __device__ __forceinline__ void gather_rows_drawn2(const float* rows_off, const 
   }
 }
 
+// What a kernel needs of a weighted-sampling table (iqlhip_weighted_kernels.h; by value: kernel argument, IdleWork record).
+struct WTab {
+  const unsigned long long* tab;          // level 0 = cum[0..n), the search levels behind it
+  unsigned n;
+  int levels;
+};
+
 // What the idle eighth of a captured step's forward grid does (StepParams::g_work; one record per step of a chunk,
 // written once when the chunk is captured):
 struct IdleWork {
@@ -377,17 +384,25 @@ struct IdleWork {
   // two-source chunks only (MIXED): `rows` is the offline buffer, rows_on the online one, batch rows >= n_off are its
   const float* rows_on;
   int n_off;
+  // weighted chunks only (MODE 2): the cumulative table the next step's rows are drawn by
+  WTab wt;
 };
-// MIXED: the idle work of a two-source chunk (iql_fwd_mixed_kernel) — a compile-time switch, so that the forward
-// kernels of plain calls hold no trace of it.
-template <bool MIXED = false>
+// (defined in iqlhip_weighted_kernels.h, behind every kernel of this file)
+__device__ __forceinline__ void idle_gather_weighted(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
+                                                     unsigned long long j0, int blk, int nblk);
+// MODE: 1 = the idle work of a two-source chunk (iql_fwd_mixed_kernel), 2 = of a weighted chunk
+// (iql_fwd_weighted_kernel) — a compile-time switch, so that the forward kernels of plain calls hold no trace of either.
+template <int MODE = 0>
 __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int nblk) {
+  constexpr bool MIXED = MODE == 1;
   const IdleWork w = *wk;
   const unsigned long long size = w.hdr[HDR_SIZE], seed = w.hdr[HDR_SEED], ctr0 = w.hdr[HDR_OFFSET], pos = w.hdr[HDR_POS];
   const unsigned long long base = w.hdr[HDR_BASE], dseed = w.hdr[HDR_DROP_SEED], dstep = w.hdr[HDR_DROP_STEP];
   // the next step's rows: index j = POS + (k + 1) n + r of the call (for the chunk's last step that is step 0 of
   // whatever runs next: the following chunk, or the next call when it continues this one's stream)
-  if (MIXED)
+  if constexpr (MODE == 2)
+    idle_gather_weighted(w, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, blk, nblk);
+  else if (MIXED)
     gather_rows_drawn2(w.rows, w.rows_on, w.ld, w.xb_dst, w.n, w.n_off, seed, ctr0,
                        pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, size, w.hdr[HDR_SIZE_ON],
                        blk * 256 + (int)threadIdx.x, nblk * 256);
@@ -881,6 +896,14 @@ __global__ __launch_bounds__(256) void iql_call_setup_mixed_kernel(unsigned long
                                                                    unsigned* arrivals, unsigned long long* ack,
                                                                    unsigned long long ack_val, const float* rows_on,
                                                                    int n_off);
+// (and its weighted form: iqlhip_weighted_kernels.h, included there too)
+__global__ __launch_bounds__(256) void iql_call_setup_weighted_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                                      iqlhip_step_scalars* sched_call,
+                                                                      const iqlhip_step_scalars* sched_src, int n_steps,
+                                                                      const float* rows, long long ld, float* xb, int B,
+                                                                      unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                                      unsigned* arrivals, unsigned long long* ack,
+                                                                      unsigned long long ack_val, WTab wt);
 
 // bf16 shadows rebuilt from the fp32 masters (start of every library call on the bf16 path: the caller owns the
 // masters and may have written them through its own tensors since the last update kernel ran).

@@ -1,0 +1,270 @@
+// iqlhip_weighted_kernels.h — weighted replay sampling (include/iqlhip.h "weighted replay sampling").
+// Included by iqlhip.hip behind every other kernel of the library (the existing kernels keep their places in the code
+// object); needs iqlhip_kernels.h (philox4x32_10, ChunkHdr, call_setup_head, dropmask_words, f32x4).
+//
+// The distribution is defined in integers.  q[i] = floor(w[i] * 2^(38 - e)), e = floor(log2(max w)), taken from the
+// fp32 bit pattern by shifts; cum[i] = q[0] + ... + q[i] (uint64); a draw maps its 64 random bits r to
+// t = mulhi64(r, cum[n - 1]) and returns the smallest i with cum[i] > t.  Every step is exact, so the table and the
+// indices do not depend on how the scan is split into passes or on any floating-point mode.
+//
+// The table is ONE device allocation: level 0 = cum[0..n), level l + 1 = every 64th entry of level l
+// (L[k] = below[min(64 k + 63, size - 1)]), up to a level of <= 64 entries; each level starts on a multiple of 64
+// entries, so a node — 64 consecutive separators — is one aligned 512-byte read.
+#pragma once
+
+#define WT_MAX_LEVELS 4                 // n <= 2^24: 2^24, 2^18, 2^12, 64
+#define WT_SCAN_ITEMS 16                // entries per thread of a scan block
+#define WT_SCAN_TILE (256 * WT_SCAN_ITEMS)
+
+// (WTab — what a kernel needs of a table — is defined next to IdleWork, which holds one: iqlhip_kernels.h)
+
+// ---- building the table ----------------------------------------------------------------------------------------------
+// out[0]: the largest bit pattern among the finite, non-negative weights (their order is the order of their bits);
+// out[1]: bit 0 = some weight is NaN or infinite, bit 1 = some weight is negative (-0.0 counts as zero).
+__global__ __launch_bounds__(256) void iql_wt_validate_kernel(const float* __restrict__ w, long long n, unsigned* out) {
+  unsigned mx = 0u, bad = 0u;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const unsigned b = __float_as_uint(w[i]);
+    if ((b & 0x7F800000u) == 0x7F800000u) bad |= 1u;
+    else if ((b >> 31) && (b << 1)) bad |= 2u;
+    else mx = max(mx, b & 0x7FFFFFFFu);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
+    bad |= (unsigned)__shfl_xor((int)bad, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (mx) atomicMax(out, mx);
+    if (bad) atomicOr(out + 1, bad);
+  }
+}
+
+// q of one weight: its significand shifted by (its exponent + sh0), sh0 = 38 - e.  (No weight exceeds the largest one,
+// so a left shift never loses bits: q < 2^39.)
+__device__ __forceinline__ unsigned long long wt_quantise(float w, int sh0) {
+  const unsigned b = __float_as_uint(w) & 0x7FFFFFFFu;
+  const unsigned ex = b >> 23;
+  const unsigned long long m = ex ? (unsigned long long)((b & 0x7FFFFFu) | 0x800000u) : (unsigned long long)(b & 0x7FFFFFu);
+  const int s = (ex ? (int)ex - 150 : -149) + sh0;
+  if (s >= 0) return m << min(s, 39);
+  return (s > -24) ? (m >> (-s)) : 0ull;
+}
+
+// Inclusive scan of one value per thread over the block's 256 threads (s_wave: 4 words of LDS).
+__device__ __forceinline__ unsigned long long wt_block_scan(unsigned long long v, unsigned long long* s_wave,
+                                                            unsigned long long* block_total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) s_wave[wave] = v;
+  __syncthreads();
+  unsigned long long base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned long long t = s_wave[k];
+    if (k < wave) base += t;
+    tot += t;
+  }
+  __syncthreads();
+  *block_total = tot;
+  return v + base;
+}
+
+// Pass 1: bsum[b] = the sum of q over tile b (WT_SCAN_TILE weights).
+__global__ __launch_bounds__(256) void iql_wt_tile_sums_kernel(const float* __restrict__ w, long long n, int sh0,
+                                                               unsigned long long* __restrict__ bsum) {
+  __shared__ unsigned long long s_wave[4];
+  const long long i0 = (long long)blockIdx.x * WT_SCAN_TILE + (long long)threadIdx.x * WT_SCAN_ITEMS;
+  unsigned long long v = 0;
+#pragma unroll
+  for (int k = 0; k < WT_SCAN_ITEMS; ++k)
+    if (i0 + k < n) v += wt_quantise(w[i0 + k], sh0);
+  unsigned long long tot;
+  (void)wt_block_scan(v, s_wave, &tot);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// Pass 2 (one block): bsum -> its exclusive scan, in place; nb <= WT_SCAN_TILE tiles (n <= 2^24).
+__global__ __launch_bounds__(256) void iql_wt_scan_sums_kernel(unsigned long long* bsum, int nb) {
+  __shared__ unsigned long long s_wave[4];
+  const int i0 = (int)threadIdx.x * WT_SCAN_ITEMS;
+  unsigned long long x[WT_SCAN_ITEMS], v = 0;
+#pragma unroll
+  for (int k = 0; k < WT_SCAN_ITEMS; ++k) {
+    x[k] = (i0 + k < nb) ? bsum[i0 + k] : 0ull;
+    v += x[k];
+  }
+  unsigned long long tot;
+  unsigned long long run = wt_block_scan(v, s_wave, &tot) - v;      // exclusive prefix of this thread's first entry
+#pragma unroll
+  for (int k = 0; k < WT_SCAN_ITEMS; ++k) {
+    if (i0 + k < nb) bsum[i0 + k] = run;
+    run += x[k];
+  }
+}
+
+// Pass 3: cum[i] = (tiles before this one) + the inclusive scan inside the tile.
+__global__ __launch_bounds__(256) void iql_wt_tile_scan_kernel(const float* __restrict__ w, long long n, int sh0,
+                                                               const unsigned long long* __restrict__ bsum,
+                                                               unsigned long long* __restrict__ cum) {
+  __shared__ unsigned long long s_wave[4];
+  const long long i0 = (long long)blockIdx.x * WT_SCAN_TILE + (long long)threadIdx.x * WT_SCAN_ITEMS;
+  unsigned long long x[WT_SCAN_ITEMS], v = 0;
+#pragma unroll
+  for (int k = 0; k < WT_SCAN_ITEMS; ++k) {
+    x[k] = (i0 + k < n) ? wt_quantise(w[i0 + k], sh0) : 0ull;
+    v += x[k];
+  }
+  unsigned long long tot;
+  unsigned long long run = wt_block_scan(v, s_wave, &tot) - v + bsum[blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < WT_SCAN_ITEMS; ++k) {
+    run += x[k];
+    if (i0 + k < n) cum[i0 + k] = run;
+  }
+}
+
+// A search level from the one below: up[k] = below[min(64 k + 63, size_below - 1)], k < size_up.
+__global__ __launch_bounds__(256) void iql_wt_level_kernel(const unsigned long long* __restrict__ below, unsigned size_below,
+                                                           unsigned long long* __restrict__ up, unsigned size_up) {
+  const unsigned k = blockIdx.x * 256u + threadIdx.x;
+  if (k < size_up) up[k] = below[min(64u * k + 63u, size_below - 1u)];
+}
+
+// ---- the draw --------------------------------------------------------------------------------------------------------
+// The 64 random bits of index j of a call: draw_index's (iqlhip_kernels.h) — same counter, same tag, same word pair.
+__device__ __forceinline__ unsigned long long wt_draw_bits(unsigned long long seed, unsigned long long ctr0, unsigned long long j) {
+  const unsigned long long ctr = ctr0 + (j >> 1);
+  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x49514C48u /* "IQLH" */, 0u};
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return (j & 1ull) ? (((unsigned long long)c[3] << 32) | c[2]) : (((unsigned long long)c[1] << 32) | c[0]);
+}
+
+// U indices resolved by ONE wave, all of its lanes calling with the same arguments: a 64-ary descent from the top level.
+// At each level lane l reads separator l of the current node (one coalesced 512-byte read; lanes past the node's width
+// count as "greater"), and the child is the number of separators <= t — the population count of a 64-bit ballot, clamped
+// to the node's width so that no table content can lead outside the table.  The top node's last separator is
+// cum[n - 1], the total t is scaled by.  The U descents are independent: their reads of a level are in flight together.
+template <int U>
+__device__ __forceinline__ void draw_index_weighted(const WTab& wt, unsigned long long seed, unsigned long long ctr0,
+                                                    const unsigned long long (&j)[U], long long (&out)[U]) {
+  const unsigned lane = threadIdx.x & 63u;
+  unsigned size[WT_MAX_LEVELS], off[WT_MAX_LEVELS];
+  {
+    unsigned s = wt.n, o = 0;
+#pragma unroll
+    for (int l = 0; l < WT_MAX_LEVELS; ++l) {
+      size[l] = s; off[l] = o;
+      o += (s + 63u) & ~63u;
+      s = (s + 63u) >> 6;
+    }
+  }
+  unsigned long long r[U], t[U];
+  unsigned node[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) { r[u] = wt_draw_bits(seed, ctr0, j[u]); node[u] = 0u; t[u] = 0ull; }
+#pragma unroll
+  for (int l = WT_MAX_LEVELS - 1; l >= 0; --l) {
+    if (l < wt.levels) {
+      unsigned long long sep[U];
+      unsigned width[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const unsigned first = 64u * node[u];
+        width[u] = min(64u, size[l] - first);
+        sep[u] = (lane < width[u]) ? wt.tab[off[l] + first + lane] : ~0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (l == wt.levels - 1) {
+          const unsigned long long total = __shfl(sep[u], (int)width[u] - 1);
+          t[u] = __umul64hi(r[u], total);
+        }
+        const unsigned child = (unsigned)__popcll(__ballot(lane < width[u] && sep[u] <= t[u]));
+        node[u] = 64u * node[u] + min(child, width[u] - 1u);
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) out[u] = (long long)node[u];
+}
+
+// idx[j] = weighted index j of the stream (seed, offset), j < n_idx: one wave per index, two in flight per wave.
+__global__ __launch_bounds__(256) void iql_draw_indices_weighted_kernel(long long* idx, long long n_idx, WTab wt,
+                                                                        unsigned long long seed, unsigned long long offset) {
+  const long long wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  const long long n_waves = (long long)gridDim.x * 4;
+  for (long long j0 = wave; j0 < n_idx; j0 += 2 * n_waves) {
+    const long long j1 = j0 + n_waves;
+    const unsigned long long j[2] = {(unsigned long long)j0, (unsigned long long)(j1 < n_idx ? j1 : j0)};
+    long long i[2];
+    draw_index_weighted<2>(wt, seed, offset, j, i);
+    if ((threadIdx.x & 63) == 0) {
+      idx[j0] = i[0];
+      if (j1 < n_idx) idx[j1] = i[1];
+    }
+  }
+}
+
+// rows[weighted draw(j0 + r)] -> xb[r], r < n: gather_rows_drawn with the index of a row resolved by the wave that then
+// copies it — the index never leaves the wave's registers (no LDS, no scratch, no barrier).  wave / n_waves: this
+// wave's number and the count of waves sharing the work; two rows per pass, their descents in flight together.
+__device__ __forceinline__ void gather_rows_drawn_weighted(const float* rows, long long ld, float* xb, int n, const WTab& wt,
+                                                           unsigned long long seed, unsigned long long ctr0,
+                                                           unsigned long long j0, int wave, int n_waves) {
+  const int q = (int)(ld >> 2);
+  const int lane = (int)(threadIdx.x & 63);
+  for (int r0 = wave; r0 < n; r0 += 2 * n_waves) {
+    const int r1 = r0 + n_waves;
+    const bool two = r1 < n;
+    const unsigned long long j[2] = {j0 + (unsigned long long)r0, j0 + (unsigned long long)(two ? r1 : r0)};
+    long long i[2];
+    draw_index_weighted<2>(wt, seed, ctr0, j, i);
+    for (int c4 = lane; c4 < q; c4 += 64) {
+      const f32x4 a = *(const f32x4*)(rows + i[0] * ld + 4 * c4);
+      f32x4 b = a;
+      if (two) b = *(const f32x4*)(rows + i[1] * ld + 4 * c4);
+      *(f32x4*)(xb + (long long)r0 * ld + 4 * c4) = a;
+      if (two) *(f32x4*)(xb + (long long)r1 * ld + 4 * c4) = b;
+    }
+  }
+}
+
+// The idle work of a weighted chunk's forward (idle_block_work<2>): the next step's rows, drawn by weight.
+__device__ __forceinline__ void idle_gather_weighted(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
+                                                     unsigned long long j0, int blk, int nblk) {
+  const WTab wt = w.wt;
+  const int wave = __builtin_amdgcn_readfirstlane(blk * 4 + (int)(threadIdx.x >> 6));
+  gather_rows_drawn_weighted(w.rows, w.ld, w.xb_dst, w.n, wt, seed, ctr0, j0, wave, nblk * 4);
+}
+
+// First launch of an iqlhip_train_steps_weighted call: iql_call_setup_kernel with step 0's rows drawn by weight
+// (B == 0: the previous weighted call on this table left them staged).
+__global__ __launch_bounds__(256) void iql_call_setup_weighted_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                                      iqlhip_step_scalars* sched_call,
+                                                                      const iqlhip_step_scalars* sched_src, int n_steps,
+                                                                      const float* rows, long long ld, float* xb, int B,
+                                                                      unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                                      unsigned* arrivals, unsigned long long* ack,
+                                                                      unsigned long long ack_val, WTab wt) {
+  call_setup_head(hdr, h, sched_call, sched_src, n_steps, arrivals, ack, ack_val);
+  if (B > 0)
+    gather_rows_drawn_weighted(rows, ld, xb, B, wt, h.w[HDR_SEED], h.w[HDR_OFFSET], h.w[HDR_POS],
+                               __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6))), (int)gridDim.x * 4);
+  if (drop_dst)
+    dropmask_words(drop_dst, drop_words, drop_thresh, h.w[HDR_DROP_SEED], h.w[HDR_DROP_STEP],
+                   ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+}
+
+// The training forward of a weighted chunk: iql_fwd_kernel's body a third time, the idle blocks drawing the next step's
+// rows by weight (idle_block_work<2>).  A kernel of its own, as iql_fwd_mixed_kernel is: plain calls' forward stays as it is.
+template <bool BF16, bool W0DMA, bool MULTI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_weighted_kernel(StepParams p) {
+  constexpr bool ONE = false, ROW_EXIT = false;
+  constexpr int MIXED_IDLE = 2;
+#include "iqlhip_fwd_body.inc"
+}

@@ -153,6 +153,15 @@ SYMBOLS = [
     ("iqlhip_rows_reward_shift", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_float,
                                            C.c_void_p]),
     ("iqlhip_draw_indices", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    ("iqlhip_weights_build", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("iqlhip_weights_free", C.c_int, [C.c_void_p]),
+    ("iqlhip_weights_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_uint64), C.c_void_p]),
+    ("iqlhip_draw_indices_weighted", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    ("iqlhip_train_steps_weighted", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                              C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("iqlhip_train_steps_weighted_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p,
+                                                      C.c_void_p]),
     ("iqlhip_debug_read", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64,
                                     C.POINTER(C.c_int64), C.c_void_p]),
     ("iqlhip_debug_time_kernel", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.POINTER(C.c_float),

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 from typing import Dict, List
 
+import ctypes as C
 import os
 
 import numpy as np
@@ -332,6 +333,77 @@ class ReplayBuffer:
         global _last_block
         _last_block = (block_ptr, batch_size, self._state_dim, self._action_dim, self._ld, dev)
         return batch
+
+    # ---- weighted sampling on the device (iqlhip_weighted.py; not part of the reference's surface) ----
+    _weights = None              # the library's table (iqlhip_weights*), its n and its generation; None: no weights
+    _weights_n = None
+    _weights_gen = 0
+
+    @property
+    def sample_weights_n(self):
+        """Rows the sample weights were set for; None when the buffer has none."""
+        return self._weights_n
+
+    def _free_weights(self) -> None:
+        table, self._weights, self._weights_n, self._weights_gen = self._weights, None, None, 0
+        if table is not None:
+            hb.lib().iqlhip_weights_free(table)
+
+    def __del__(self):
+        try:
+            self._free_weights()
+        except Exception:
+            pass
+
+    def set_sample_weights(self, weights) -> None:
+        """One float32 weight per row position [0, _index_bound()): a torch tensor on the buffer's device or on the host,
+        or an ndarray; None clears them.  The library validates the values and builds its cumulative table on the device
+        (8 bytes per row plus 1/63).  ValueError for a CPU buffer, a wrong length, dtype or shape, a NaN, an infinity, a
+        negative value, all zeros, or more than 2^24 rows — the previous weights then stay in force.  A weight below
+        max(weights) * 2^-39 quantises to 0: that row is never drawn.  Only the *_weighted calls look at weights."""
+        import iqlhip_weighted as wtd
+        if weights is None:
+            self._free_weights()
+            return
+        if not self._gpu:
+            raise ValueError("iqlhip: sample weights need a ReplayBuffer that lives on the GPU")
+        n = self._index_bound()
+        kind = wtd.check_vector(weights, n)
+        dev = self._rows.device
+        if kind == "numpy" or weights.device.type == "cpu":
+            host = weights if kind == "numpy" else weights.numpy()
+            wtd.check_host_values(host)
+            w_dev = torch.tensor(host, dtype=torch.float32, device=dev)      # (a copy: the array may be read-only)
+        elif weights.device != dev:
+            raise ValueError(f"iqlhip: sample weights live on {weights.device}, the buffer on {dev}")
+        else:
+            w_dev = weights.contiguous()
+        table = C.c_void_p()
+        with torch.cuda.device(dev):
+            hb.check(hb.lib().iqlhip_weights_build(w_dev.data_ptr(), n, self._stream(), C.byref(table)))
+        gen = C.c_uint64()
+        hb.check(hb.lib().iqlhip_weights_info(table, None, None, None, C.byref(gen), None))
+        self._free_weights()
+        self._weights, self._weights_n, self._weights_gen = table, n, int(gen.value)
+
+    def draw_weighted_indices(self, n: int, seed: int, offset: int) -> torch.Tensor:
+        """Indices 0 .. n - 1 of the weighted index stream (seed, offset) — the stream train_steps_weighted consumes — as
+        a device int64 tensor."""
+        import iqlhip_weighted as wtd
+        wtd.check_call(self)
+        if n < 1:
+            raise ValueError("iqlhip: n must be at least 1")
+        dev = self._rows.device
+        idx = torch.empty(int(n), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            hb.check(hb.lib().iqlhip_draw_indices_weighted(idx.data_ptr(), int(n), self._weights,
+                                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                                           self._stream()))
+        return idx
+
+    def sample_weighted(self, batch_size: int, seed: int, offset: int) -> TensorBatch:
+        """A batch drawn by weight on the device: gather(draw_weighted_indices(batch_size, seed, offset))."""
+        return self.gather(self.draw_weighted_indices(batch_size, seed, offset))
 
     def add_transition(self, state: np.ndarray, action: np.ndarray, reward: float, next_state: np.ndarray,
                        done: bool):
