@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 370          /* 0.3.7 */
+#define IQLHIP_VERSION 380          /* 0.3.8 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -621,6 +621,22 @@ int iqlhip_group_train_steps_replay2(iqlhip_group* group, const float* const* ro
                                      const float* const* rows_on, const int64_t* size_on, int64_t ld, const int32_t* B,
                                      const int32_t* n_off, const void* const* tables, int32_t n, const uint64_t* seeds,
                                      const uint64_t* offsets, void* stream);
+/* iqlhip_group_train_steps_mixed with member k's rows drawn by wtabs[k] ("weighted replay sampling" above; a NULL
+ * entry: that member draws uniformly, exactly as iqlhip_group_train_steps_mixed would): iqlhip_train_steps_weighted for
+ * each member with a table, in the group's launches.  B is per member: one entry point serves equal and unequal batch
+ * sizes.  Members may share one table.  A weighted draw consumes the counters a plain one does: stream positions,
+ * dropout positions, losses, statistics and scalar tables all as iqlhip_group_train_steps_mixed; every member's solo
+ * continuation (IQLHIP_TS_CONTINUE) is invalidated, as after any group call.  Each step's rows are gathered by a launch
+ * of its own between the steps (one wave resolves an index and copies that row).  Checked before any device work or
+ * counter change, on top of iqlhip_group_train_steps_mixed's checks: wtabs == NULL, a table whose n differs from
+ * size[k] (so that every index it can resolve is < size[k]), a table on another device than the group (IQLHIP_EINVAL,
+ * naming the member); an exchange or more than 512 bf16 rows (IQLHIP_EUNSUPPORTED, the group rules).  Two-source
+ * (replay2) weighted batches do not exist.  Every table must outlive the call's queued work (iqlhip_weights_free waits
+ * for the device before it frees).  flags: reserved (0). */
+int iqlhip_group_train_steps_weighted(iqlhip_group* group, const float* const* rows, int64_t ld, const int64_t* size,
+                                      const int32_t* B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                      const uint64_t* offsets, int32_t flags, void* stream,
+                                      const iqlhip_weights* const* wtabs);
 /* Policy inference for every member of a group in one set of launches.  Member k maps its rows[k] states
  * (row stride ld_s) to rows[k] actions (row stride ld_a), exactly as iqlhip_actor_forward (seeds[k] == 0: the mean)
  * or iqlhip_actor_sample (seeds[k] != 0: device N(0,1) noise, member k's act() call counter advances by one) on that

@@ -2764,6 +2764,7 @@ struct iqlhip_group {
   // last: group_upload copies up to their used rows
   Staging train;
   Section<GroupRec> recs; Section<GroupDropRec> drops; AuxSections aux; Section<iqlhip_step_scalars> tabs;
+  Section<GroupWtRec> wts;            // iqlhip_group_train_steps_weighted: one table record per member (before the tables)
   // clip_ones: three floats of 1.0f, the coefficients a member without clipping reads (allocated by the first call
   // with a clipping member)
   float* clip_ones = nullptr;
@@ -2873,6 +2874,7 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->recs = g->train.add<GroupRec>(k);
     g->drops = g->train.add<GroupDropRec>(n_drop);
     g->aux.add(g->train, k);
+    g->wts = g->train.add<GroupWtRec>(k);
     g->tabs = g->train.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
     g->on_recs = g->on.add<GroupRec>(k);
     g->on_aps = g->on.add<StepParams>(k);
@@ -3230,12 +3232,24 @@ static int group_check_mix(const GroupMixSrc* mx, int i, int32_t B, const char* 
   return IQLHIP_OK;
 }
 
+// Weighted draws in a group call (iqlhip_group_train_steps_weighted): member i's table, wtabs[i] — NULL: it draws
+// uniformly.  (iqlhip_weights is defined with the weighted-sampling code at the end of the file.)
+static WTab weights_tab(const iqlhip_weights* t);
+static int weights_check_member(const iqlhip_weights* t, int member, int64_t size, int device);
+// Rows a wave of the weighted group gather resolves and copies per pass of its grid (gather_rows_drawn_weighted keeps
+// two descents in flight per wave): 2 = a wave per two rows of the largest member, 1 = a wave per row.
+#ifndef IQL_GROUP_WT_ROWS_PER_WAVE
+#define IQL_GROUP_WT_ROWS_PER_WAVE 2
+#endif
+
 // iqlhip_group_train_steps (B: one count k times) and iqlhip_group_train_steps_mixed: member i draws B[i] rows a step.
 // iqlhip_group_train_steps_replay2 (mx != nullptr): rows / size are the offline buffers, mx the online ones.
+// iqlhip_group_train_steps_weighted (wtabs != nullptr; never together with mx): member i's rows are drawn by wtabs[i].
 static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size, const int32_t* B,
                              const void* const* tables, int32_t n, const uint64_t* seeds, const uint64_t* offsets,
-                             void* stream, const GroupMixSrc* mx = nullptr) {
+                             void* stream, const GroupMixSrc* mx = nullptr, const iqlhip_weights* const* wtabs = nullptr) {
   if (!g || !rows || !size || !B || !tables || !seeds || !offsets) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (mx && wtabs) return fail(IQLHIP_EUNSUPPORTED, "weighted draws from two buffers are not supported");
   int rc = group_check_call(g, B);
   if (rc) return rc;
   if (n < 1 || n > IQLHIP_GROUP_MAX_STEPS) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", IQLHIP_GROUP_MAX_STEPS);
@@ -3244,6 +3258,7 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
     if (rc) return rc;
     if (size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty buffer", i);
     if (!tables[i]) return fail(IQLHIP_EINVAL, "member %d: NULL scalar table", i);
+    if (wtabs && wtabs[i] && (rc = weights_check_member(wtabs[i], i, size[i], g->device))) return rc;
     if (!mx) continue;
     if ((rc = group_check_mix(mx, i, B[i], "online"))) return rc;
     if (mx->rows[i] == rows[i]) return fail(IQLHIP_EINVAL, "member %d: the offline and the online buffer are the same rows", i);
@@ -3264,6 +3279,7 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
     if (mx) { r.rows_on = mx->rows[i]; r.size_on = mx->size[i]; r.n_off = mx->n_off[i]; }
     memcpy(group_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
+    if (wtabs) g->train.host(g->wts)[i].wt = wtabs[i] ? weights_tab(wtabs[i]) : WTab{nullptr, 0u, 0};
   }
   // actor dropout: one record per member (indexed like the GroupRecs; active = the member draws), step s at drop_step + s
   bool draws = false;
@@ -3285,8 +3301,18 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
   // (a grid with a thread per gathered float4 and per keep-bit word: the words come from its far end)
   const int drop_nb = gather_nb + (2 * q.max_rows * 8 + 255) / 256;
   const GroupRec* recs = g->train.device(g->recs);
+  // weighted: a wave resolves an index and copies that row — a wave per IQL_GROUP_WT_ROWS_PER_WAVE rows of the largest
+  // member, four waves a block; with keep-bits, their words fit behind the gather at the far end as above
+  const int wt_nb = (q.max_rows + 4 * IQL_GROUP_WT_ROWS_PER_WAVE - 1) / (4 * IQL_GROUP_WT_ROWS_PER_WAVE);
+  const int wt_drop_nb = wt_nb + (2 * q.max_rows * 8 + 255) / 256;
+  const GroupWtRec* wts = g->train.device(g->wts);
   for (int s = 0; s < n; ++s) {
-    if (draws)
+    if (wtabs && draws)
+      hipLaunchKernelGGL(iql_gather_weighted_drop_group_kernel, dim3(wt_drop_nb, g->k), dim3(256), 0, st, recs, wts,
+                         g->train.device(g->drops), s);
+    else if (wtabs)
+      hipLaunchKernelGGL(iql_gather_weighted_group_kernel, dim3(wt_nb, g->k), dim3(256), 0, st, recs, wts, s);
+    else if (draws)
       hipLaunchKernelGGL(mx ? iql_gather2_drop_group_kernel : iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0,
                          st, recs, g->train.device(g->drops), s);
     else
@@ -3320,6 +3346,14 @@ extern "C" int iqlhip_group_train_steps_replay2(iqlhip_group* g, const float* co
   if (!rows_on || !size_on || !n_off) return fail(IQLHIP_EINVAL, "NULL argument");
   const GroupMixSrc mx{rows_on, size_on, n_off};
   return group_train_steps(g, rows_off, ld, size_off, B, tables, n, seeds, offsets, stream, &mx);
+}
+extern "C" int iqlhip_group_train_steps_weighted(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
+                                                 const int32_t* B, const void* const* tables, int32_t n,
+                                                 const uint64_t* seeds, const uint64_t* offsets, int32_t flags, void* stream,
+                                                 const iqlhip_weights* const* wtabs) {
+  (void)flags;
+  if (!wtabs) return fail(IQLHIP_EINVAL, "NULL argument");
+  return group_train_steps(g, rows, ld, size, B, tables, n, seeds, offsets, stream, nullptr, wtabs);
 }
 
 extern "C" int iqlhip_group_read_losses(iqlhip_group* g, float* out, int32_t n, void* stream) {
@@ -4127,6 +4161,13 @@ static int weights_levels(int64_t n, unsigned size[WT_MAX_LEVELS], unsigned off[
   return levels;
 }
 static WTab weights_tab(const iqlhip_weights* t) { return WTab{t->tab, (unsigned)t->n, t->levels}; }
+// A group member's table (iqlhip_group_train_steps_weighted): on the group's device, and weighing exactly the size[k]
+// rows the member draws over — every index the descent can resolve is then < size[k].
+static int weights_check_member(const iqlhip_weights* t, int member, int64_t size, int device) {
+  if (t->device != device) return fail(IQLHIP_EINVAL, "member %d: the table lives on device %d, the group on %d", member, t->device, device);
+  if (size != t->n) return fail(IQLHIP_EINVAL, "member %d: size %lld, but the table weighs %lld rows", member, (long long)size, (long long)t->n);
+  return IQLHIP_OK;
+}
 
 extern "C" int iqlhip_weights_build(const float* w_dev, int64_t n, void* stream, iqlhip_weights** out) {
   if (!w_dev || !out) return fail(IQLHIP_EINVAL, "NULL argument");

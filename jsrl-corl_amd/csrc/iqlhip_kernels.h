@@ -1959,6 +1959,18 @@ __global__ __launch_bounds__(256) void iql_gather2_group_kernel(const GroupRec* 
 __global__ __launch_bounds__(256) void iql_gather2_drop_group_kernel(const GroupRec* __restrict__ recs,
                                                                      const GroupDropRec* __restrict__ drops, int step);
 
+// Weighted replay sampling in a group (iqlhip_group_train_steps_weighted): one record per member, an array of its own
+// next to the GroupRecs as GroupDropRec is — GroupRec is unchanged.  wt.tab == nullptr: the member draws uniformly.
+// (the kernels are defined with the other weighted kernels: iqlhip_weighted_kernels.h, end of iqlhip.hip)
+struct GroupWtRec {
+  WTab wt;
+};
+__global__ __launch_bounds__(256) void iql_gather_weighted_group_kernel(const GroupRec* __restrict__ recs,
+                                                                        const GroupWtRec* __restrict__ wts, int step);
+__global__ __launch_bounds__(256) void iql_gather_weighted_drop_group_kernel(const GroupRec* __restrict__ recs,
+                                                                             const GroupWtRec* __restrict__ wts,
+                                                                             const GroupDropRec* __restrict__ drops, int step);
+
 // The policy-inference forward (iql_fwd_kernel<BF16, W0DMA, false, true>: only_inst = 6, blockIdx.x = row tile *
 // NSPLIT + column slice) for the members that asked for an action: grid.y = requesting member, ps[j] its StepParams.
 template <bool BF16, bool W0DMA>

@@ -268,3 +268,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   constexpr int MIXED_IDLE = 2;
 #include "iqlhip_fwd_body.inc"
 }
+
+// ---- trainer groups (iqlhip_group_train_steps_weighted; DESIGN.md 6i "trainer groups") --------------------------------
+// (GroupWtRec — one record per member, an array of its own next to the GroupRecs, as GroupDropRec is — is defined with
+//  the group records: iqlhip_kernels.h.  GroupRec itself is unchanged.)
+// One member's rows of step s: by its table (one wave resolves an index and copies that row; `wave` is uniform across
+// the wave, so the descent's addresses stay scalar), or — no table — iql_gather_group_kernel's uniform draw with its
+// arguments.  The branch is uniform per block: a block serves one member.
+__device__ __forceinline__ void group_gather_weighted(const GroupRec& r, const GroupWtRec& w, int s) {
+  const unsigned long long j0 = (unsigned long long)s * (unsigned long long)r.B;
+  if (w.wt.tab) {
+    const WTab wt = w.wt;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    gather_rows_drawn_weighted(r.rows, r.ld, r.xb, r.B, wt, r.seed, r.offset, j0, wave, (int)gridDim.x * 4);
+  } else {
+    gather_rows_drawn(r.rows, r.ld, r.xb, r.B, r.seed, r.offset, j0, (unsigned long long)r.size,
+                      (int)blockIdx.x * 256 + (int)threadIdx.x, (int)gridDim.x * 256);
+  }
+}
+
+// iql_gather_group_kernel with member blockIdx.y's rows drawn by wts[blockIdx.y] (a null table: uniformly).
+__global__ __launch_bounds__(256) void iql_gather_weighted_group_kernel(const GroupRec* __restrict__ recs,
+                                                                        const GroupWtRec* __restrict__ wts, int step) {
+  const GroupRec& r = recs[blockIdx.y];
+  const int s = min(max(step, 0), r.n_steps - 1);
+  group_gather_weighted(r, wts[blockIdx.y], s);
+}
+
+// ... plus the step's keep-bit words of the members that draw some, from the far end of the grid
+// (iql_gather_drop_group_kernel's split).  Launched only when some member of the call draws keep-bits.
+__global__ __launch_bounds__(256) void iql_gather_weighted_drop_group_kernel(const GroupRec* __restrict__ recs,
+                                                                             const GroupWtRec* __restrict__ wts,
+                                                                             const GroupDropRec* __restrict__ drops, int step) {
+  const GroupRec& r = recs[blockIdx.y];
+  const int s = min(max(step, 0), r.n_steps - 1);
+  group_gather_weighted(r, wts[blockIdx.y], s);
+  const GroupDropRec& d = drops[blockIdx.y];
+  if (d.active)
+    group_drop_words(d, d.step0 + (unsigned long long)s, ((int)gridDim.x - 1 - (int)blockIdx.x) * 256 + (int)threadIdx.x,
+                     (int)gridDim.x * 256);
+}

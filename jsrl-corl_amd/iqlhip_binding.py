@@ -198,6 +198,10 @@ SYMBOLS = [
                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int64,
                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                                    C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    ("iqlhip_group_train_steps_weighted", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int32,
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p,
+                                                    C.POINTER(C.c_void_p)]),
     ("iqlhip_group_actor_forward", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_void_p),
                                              C.c_int64, C.c_int32, C.c_void_p]),

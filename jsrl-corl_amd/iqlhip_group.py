@@ -61,6 +61,13 @@ across-member mean and standard deviation of every column per row:
     scores, summaries, spread = group.score_buffer(buffer, indices=idx, spread=True)    # [K, n, 8], K dicts, [n, 16]
     held_out = group.evaluate(batch)                                                     # K dicts of train()'s keys
 
+Weighted replay sampling (ImplicitQLearning.train_steps_weighted) has a group form: every member draws by its buffer's
+own table, by one free-standing iqlhip_weighted.SampleWeights table, or by a table of its own over a shared buffer (a
+None entry: uniformly), and ends where its solo call ends:
+
+    tables = [SampleWeights(w_k) for w_k in per_member_weights]                          # K tables, one shared buffer
+    losses = group.train_steps_weighted(buffer, 1000, 256, seeds=[0, 1, 2, 3], weights=tables)
+
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
@@ -312,6 +319,94 @@ class ImplicitQLearningGroup:
             else:
                 rc = lib.iqlhip_group_train_steps(g, rows, bufs[0]._ld, size_arr, Bs[0], tab_ptrs, k, seed_arr, offs, 0,
                                                   stream)
+            for t in self.trainers:
+                t._ts_token = None
+            hb.check(rc)
+            for t in self.trainers:
+                t.total_it += k
+            if return_losses:
+                out = (C.c_float * (K * k * 3))()
+                hb.check(lib.iqlhip_group_read_losses(g, out, k, stream))
+                losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
+            if return_stats:
+                stats[done:done + k] = self._group_stats(k)
+            done += k
+        return stats if return_stats else losses
+
+    # ------------------------------------------------------------------ device-drawn steps, rows drawn by weight
+    def train_steps_weighted(self, buffers, n_steps: int, batch_size, seeds: Sequence[int], weights=None,
+                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
+        """train_steps with every member's rows drawn by a weight table (ImplicitQLearning.train_steps_weighted for
+        each).  buffers, batch_size, seeds, chunk and the return value as train_steps.  weights: None —
+        member k draws by buffers[k]'s own set_sample_weights table (ValueError for a buffer without one); one
+        iqlhip_weighted.SampleWeights — every member draws by it; a list of K entries, each a SampleWeights or None —
+        member k draws by its own table over the (possibly shared) buffer, a None member draws UNIFORMLY.  Afterwards
+        member k is bit for bit where its solo train_steps_weighted(buffers[k], n_steps, batch_size[k], seed=seeds[k],
+        weights=...) leaves it, a uniform member where its solo train_steps does.  Every table must stay alive until
+        the queued steps have run (SampleWeights.free and set_sample_weights wait for the device).  Everything is
+        checked before anything is launched or any counter moves; the refusals are train_steps' and
+        train_steps_weighted's."""
+        import iqlhip_weighted as wtd
+        K = len(self.trainers)
+        bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
+        seeds = [int(s) for s in seeds]
+        if len(bufs) != K or len(seeds) != K:
+            raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer) and {K} seeds")
+        if n_steps < 1:
+            raise ValueError("n_steps must be >= 1")
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
+        self._check_members()
+        for B in Bs:
+            self._check_batch_size(B)
+        entries = wtd.check_group_call(bufs, weights, K)
+        for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
+            if buf._rows.device != t._dev:
+                raise ValueError(f"iqlhip: the replay buffer must live on the trainer's GPU ({t._dev}; member {i})")
+        if return_stats and not any(t._step_stats for t in self.trainers):
+            raise ValueError("iqlhip: train_steps_weighted(return_stats=True) needs set_step_stats(True) on at least one "
+                             "member")
+        for t in self.trainers:
+            t._refuse_injected_masks()
+        if K == 1:      # a group of one IS the solo call
+            t, e = self.trainers[0], entries[0]
+            if e is None:
+                out = t.train_steps(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses, chunk=chunk,
+                                    return_stats=return_stats)
+            else:
+                out = t.train_steps_weighted(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
+                                             chunk=chunk, return_stats=return_stats,
+                                             weights=None if e is bufs[0] else e)
+            if return_stats:
+                return out[1][:, None]
+            return None if out is None else out[None]
+        sizes, inv = [], []
+        for t, buf, B in zip(self.trainers, bufs, Bs):
+            size, ib = t._train_steps_args(buf, B)
+            sizes.append(size)
+            inv.append(ib)
+        if len({b._ld for b in bufs}) != 1:
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
+        lib, stream = hb.lib(), self.trainers[0]._stream()
+        g = self._group()
+        rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
+        size_arr = (C.c_int64 * K)(*sizes)
+        seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
+        B_arr = (C.c_int32 * K)(*Bs)
+        # (member k's table: its buffer's own, its SampleWeights', or NULL — the uniform draw)
+        wt_arr = (C.c_void_p * K)(*[None if e is None else (e._table if isinstance(e, wtd.SampleWeights) else e._weights)
+                                    for e in entries])
+        halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
+        losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
+        stats = np.empty((n_steps, K, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
+        done = 0
+        while done < n_steps:
+            k = min(chunk, n_steps - done)
+            offs = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
+            tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
+            tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
+            rc = lib.iqlhip_group_train_steps_weighted(g, rows, bufs[0]._ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, 0,
+                                                       stream, wt_arr)
             for t in self.trainers:
                 t._ts_token = None
             hb.check(rc)

@@ -899,30 +899,36 @@ class ImplicitQLearning:
         return (losses, stats) if return_stats else losses
 
     # ---- rows drawn by weight on the device (iqlhip_weighted.py) -----------------------------------
-    def _weighted_args(self, replay_buffer, batch_size: int) -> int:
+    def _weighted_args(self, replay_buffer, batch_size: int, weights=None):
         """The checks both weighted calls make before anything is launched or any counter moves; returns the rows the
-        draw covers."""
+        draw covers, the library's table and its generation (weights: a SampleWeights used instead of the buffer's)."""
         import iqlhip_weighted as wtd
         self._require_gpu()
-        n = wtd.check_call(replay_buffer)
+        if weights is None:
+            n = wtd.check_call(replay_buffer)
+            table, gen = replay_buffer._weights, replay_buffer._weights_gen
+        else:
+            n = wtd.check_table(replay_buffer, weights)
+            table, gen = weights._table, weights.generation
         if replay_buffer._rows.device != self._dev:
             raise ValueError(f"iqlhip: the replay buffer must live on the trainer's GPU ({self._dev})")
         wtd.check_trainer(self._dp_world, self._dp_exchange, getattr(self, "_precision", "f32"), batch_size,
                           STATS_BF16_MAX_ROWS)
-        return n
+        return n, table, gen
 
-    def prepare_train_steps_weighted(self, replay_buffer, batch_size: int) -> None:
-        """prepare_train_steps for the chunk graphs train_steps_weighted replays on this buffer and its current weights."""
-        self._weighted_args(replay_buffer, batch_size)
+    def prepare_train_steps_weighted(self, replay_buffer, batch_size: int, weights=None) -> None:
+        """prepare_train_steps for the chunk graphs train_steps_weighted replays on this buffer and its current weights
+        (weights: a SampleWeights used instead of them)."""
+        _, table, _ = self._weighted_args(replay_buffer, batch_size, weights)
         self._prepare(batch_size)
         self._refuse_injected_masks()
         hb.check(hb.lib().iqlhip_train_steps_weighted_prepare(
             self._ctx, replay_buffer._rows.data_ptr(), replay_buffer._ld, batch_size, 1.0 / batch_size, self._stream(),
-            replay_buffer._weights))
+            table))
         self._ts_token = None
 
     def train_steps_weighted(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0,
-                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
+                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False, weights=None):
         """train_steps with every row drawn by the buffer's sample weights (ReplayBuffer.set_sample_weights) instead of
         uniformly: advantage-, return- or TD-error-weighted resampling without a host draw per iteration.  The index
         stream is train_steps' own (Philox keyed by (seed, total_it)); only the mapping of its 64 random bits to a row
@@ -930,10 +936,12 @@ class ImplicitQLearning:
         call, bit for bit.  The idle blocks of each step's forward draw and gather the next step's rows.  Returns what
         train_steps returns.  ValueError if the buffer has no weights or its index bound has changed since they were
         set; NotImplementedError under data parallelism, for bf16 batches of more than 512 rows and with injected
-        dropout masks pending.  No priority exponent and no importance-sampling correction of the loss."""
+        dropout masks pending.  No priority exponent and no importance-sampling correction of the loss.
+        weights: None, or an iqlhip_weighted.SampleWeights to draw by instead of the buffer's own table (its n must equal
+        the buffer's index bound: ValueError otherwise); a continuation then keys on that object's generation."""
         if return_stats and not self._step_stats:
             raise ValueError("iqlhip: train_steps_weighted(return_stats=True) needs set_step_stats(True) first")
-        size = self._weighted_args(replay_buffer, batch_size)
+        size, table, gen = self._weighted_args(replay_buffer, batch_size, weights)
         self._prepare(batch_size)
         self._refuse_injected_masks()
         inv_batch = 1.0 / batch_size
@@ -950,11 +958,10 @@ class ImplicitQLearning:
             tab = self._scalar_table(k, inv_batch)
             # (train_steps' token plus the table's generation: a plain call's token never equals it, nor the reverse;
             #  the library checks the generation too)
-            tok = (weakref.ref(replay_buffer), replay_buffer._writes, replay_buffer._rows._version, "weighted",
-                   replay_buffer._weights_gen)
+            tok = (weakref.ref(replay_buffer), replay_buffer._writes, replay_buffer._rows._version, "weighted", gen)
             flags = hb.TS_CONTINUE if self._ts_token == tok else 0
             rc = lib.iqlhip_train_steps_weighted(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed,
-                                                 self.total_it * half, flags, stream, replay_buffer._weights)
+                                                 self.total_it * half, flags, stream, table)
             if rc:
                 self._ts_token = None
                 hb.check(rc)

@@ -7,12 +7,18 @@ stream of `train_steps`, unchanged.  Row i is drawn with probability q[i] / sum(
 e = floor(log2(max w)): a weight below max(w) * 2^-39 quantises to 0 and its row is never drawn.
 
 Weights belong to row POSITIONS: writes into the buffer leave them alone; a change of the buffer's index bound makes the
-weighted calls refuse until weights are set again.  Every other call (train_steps, sample, online_step, groups, mixed
-batches) ignores them.
+weighted calls refuse until weights are set again.  Every other call (train_steps, sample, online_step, the groups'
+other calls, mixed batches) ignores them.
+
+`SampleWeights(w)` is the same table as an object of its own, bound to no buffer: K members of a trainer group that
+share one buffer can each draw by a table of their own (`ImplicitQLearningGroup.train_steps_weighted(weights=[...])`),
+and `ImplicitQLearning.train_steps_weighted(weights=...)` uses it instead of the buffer's.
 
 The argument checks live here, free of any GPU work, so they can be tested without one.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
@@ -76,3 +82,145 @@ def check_trainer(dp_world: int, dp_exchange, precision: str, batch_size: int, b
     if precision == "bf16" and batch_size > bf16_max_rows:
         raise NotImplementedError(f"iqlhip: weighted sampling is not supported for bf16 batches of more than "
                                   f"{bf16_max_rows} rows (got {batch_size}): the large-batch kernels draw uniformly")
+
+
+class SampleWeights:
+    """A weight table of its own: one float32 weight per row position of whatever buffer it is later used with (its
+    length must equal that buffer's index bound at the call).  weights: what set_sample_weights takes — a torch tensor
+    on a GPU or on the host, or an ndarray — with the same checks and the same ValueErrors; device: where the table
+    lives (default: a device tensor's own device, else "cuda"); stream: the raw stream handle the build runs on
+    (default: the device's current stream).  The table must stay alive while calls that use it are queued: free() — and
+    the destructor — wait for the device first."""
+    _table = None
+    _n = 0
+    _gen = 0
+    _device = None
+
+    def __init__(self, weights, device=None, stream=None):
+        import torch
+        import iqlhip_binding as hb
+        shape = tuple(getattr(weights, "shape", ()))
+        n = int(shape[0]) if shape else 1        # (n: the vector's own length; check_vector names what else is wrong)
+        kind = check_vector(weights, n)
+        on_gpu = kind == "torch" and weights.device.type != "cpu"
+        host = None
+        if not on_gpu:                       # (the value checks of a host vector come before any look at a device)
+            host = weights if kind == "numpy" else weights.numpy()
+            check_host_values(host)
+        if device is None:
+            dev = weights.device if on_gpu else torch.device("cuda", torch.cuda.current_device())
+        else:
+            dev = torch.device(device)
+            if dev.type != "cuda":
+                raise ValueError(f"iqlhip: sample weights live on a GPU, not on {dev}")
+            if dev.index is None:
+                dev = torch.device("cuda", torch.cuda.current_device())
+        if on_gpu:
+            if weights.device != dev:
+                raise ValueError(f"iqlhip: sample weights live on {weights.device}, the table is asked for on {dev}")
+            w_dev = weights.contiguous()
+        else:
+            w_dev = torch.tensor(host, dtype=torch.float32, device=dev)      # (a copy: the array may be read-only)
+        table = C.c_void_p()
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+            hb.check(hb.lib().iqlhip_weights_build(w_dev.data_ptr(), n, st, C.byref(table)))
+        gen = C.c_uint64()
+        hb.check(hb.lib().iqlhip_weights_info(table, None, None, None, C.byref(gen), None))
+        self._table, self._n, self._gen, self._device = table, n, int(gen.value), dev
+
+    @property
+    def n(self) -> int:
+        """Rows the table weighs."""
+        return self._n
+
+    @property
+    def generation(self) -> int:
+        """Unique per built table: what a continuation of train_steps_weighted compares."""
+        return self._gen
+
+    @property
+    def device(self):
+        return self._device
+
+    def free(self) -> None:
+        """Wait for the device, then free the table; the object refuses every later use."""
+        table, self._table = self._table, None
+        if table is not None:
+            import iqlhip_binding as hb
+            hb.lib().iqlhip_weights_free(table)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def draw_indices(self, n: int, seed: int, offset: int):
+        """Indices 0 .. n - 1 of the weighted index stream (seed, offset) as a device int64 tensor
+        (ReplayBuffer.draw_weighted_indices for this table)."""
+        import torch
+        import iqlhip_binding as hb
+        if self._table is None:
+            raise ValueError("iqlhip: the sample weights have been freed")
+        if n < 1:
+            raise ValueError("iqlhip: n must be at least 1")
+        idx = torch.empty(int(n), dtype=torch.int64, device=self._device)
+        with torch.cuda.device(self._device):
+            hb.check(hb.lib().iqlhip_draw_indices_weighted(idx.data_ptr(), int(n), self._table,
+                                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                                           torch.cuda.current_stream(self._device).cuda_stream))
+        return idx
+
+
+def check_table(buffer, weights, member=None) -> int:
+    """A SampleWeights used with `buffer` instead of the buffer's own table: the buffer lives on a GPU, the table is
+    alive, on the buffer's device, and weighs exactly the rows the buffer draws over.  Returns that number."""
+    who = "" if member is None else f" (member {member})"
+    if not isinstance(weights, SampleWeights):
+        raise ValueError(f"iqlhip: weights must be a SampleWeights, not {type(weights).__name__}{who}")
+    if not getattr(buffer, "_gpu", False):
+        raise ValueError(f"iqlhip: weighted sampling needs a ReplayBuffer that lives on the GPU{who}")
+    if weights._table is None:
+        raise ValueError(f"iqlhip: the sample weights have been freed{who}")
+    rows = getattr(buffer, "_rows", None)
+    if rows is not None and weights.device is not None and rows.device != weights.device:
+        raise ValueError(f"iqlhip: the sample weights live on {weights.device}, the buffer on {rows.device}{who}")
+    n = buffer._index_bound()
+    if weights.n != n:
+        raise ValueError(f"iqlhip: the sample weights cover {weights.n} rows, the buffer draws over {n}{who}")
+    return n
+
+
+def check_group_call(buffers, weights, K: int):
+    """Which table each of a group's K members draws by, checked before anything is launched.  buffers: K buffers, or
+    one shared by all members.  weights: None — every member uses its buffer's own table (check_call: ValueError for a
+    buffer without one); one SampleWeights — all members use it; a list of K entries, each a SampleWeights or None —
+    a None member draws uniformly.  Lengths are checked against each member's buffer's index bound.  Returns K
+    entries: the member's buffer (its own table), a SampleWeights, or None (uniform)."""
+    bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
+    if len(bufs) != K:
+        raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer), got {len(bufs)}")
+    if weights is None:
+        for i, b in enumerate(bufs):
+            try:
+                check_call(b)
+            except ValueError as e:
+                raise ValueError(f"{e} (member {i})") from None
+        return list(bufs)
+    if isinstance(weights, SampleWeights):
+        entries = [weights] * K
+    elif isinstance(weights, (list, tuple)):
+        entries = list(weights)
+        if len(entries) != K:
+            raise ValueError(f"iqlhip: {len(entries)} weight tables for a group of {K}")
+    else:
+        raise ValueError("iqlhip: weights must be None, a SampleWeights, or a list with a SampleWeights or None per "
+                         f"member, not {type(weights).__name__}")
+    for i, (b, w) in enumerate(zip(bufs, entries)):
+        if w is None:
+            if not getattr(b, "_gpu", False):
+                raise ValueError(f"iqlhip: train_steps needs a ReplayBuffer that lives on the GPU (member {i})")
+            continue
+        check_table(b, w, i)
+    return entries
