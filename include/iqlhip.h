@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 380          /* 0.3.8 */
+#define IQLHIP_VERSION 390          /* 0.3.9 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -481,6 +481,39 @@ int iqlhip_rows_reward_shift(float* rows_dev, int64_t ld, int32_t state_dim, int
                              float subtract, void* stream);
 /* The three calls above refuse, before any device work, with IQLHIP_EINVAL: a NULL pointer, n < 1, row0 < 0,
  * max_episode_steps < 1, ld < iqlhip_row_stride(state_dim, action_dim). */
+/* Per-row episode spans, returns and discounted return-to-go of n packed rows from row0, in storage order (a loaded
+ * dataset, not a wrapped ring) — get_return_to_go of the reference's finetune/cal_ql.py and the episode returns behind
+ * keep_best_trajectories of offline/any_percent_bc.py, as device arrays ([n] each; any may be NULL).  i is 0-based in
+ * the range; everything is integers and float64, so a CPU restatement (tests/returns_ref.py) agrees to the bit.
+ *   break        row i is a break iff d[i] != 0, or state_break_tol >= 0 and i + 1 < n and ss > tol * tol, where
+ *                ss = sum over columns c, ascending, of (double)dlt_c * (double)dlt_c, dlt_c = s[i+1][c] - s'[i][c] in
+ *                float32 (one rounding), the product and every addition rounded on its own (Cal-QL's
+ *                norm(obs[t+1] - next_obs[t]) > 1e-6; state_break_tol < 0: rule off)
+ *   episode end  with p(i) = the largest break j < i (-1 if none) and o = i - p(i) - 1: row i ends an episode iff it is a
+ *                break, or (o + 1) % max_episode_steps == 0, or IQLHIP_EP_KEEP_TAIL is set and i == n - 1; its episode
+ *                starts at p(i) + 1 + (o / max_episode_steps) * max_episode_steps.  Rule off and flag clear: exactly
+ *                iqlhip_rows_return_range's episodes.
+ *   tail rows    of a trailing run that ends no episode: ep_first = ep_last = -1, ep_return = return_to_go = 0.0
+ *   ep_first / ep_last   the row's episode, relative to row0
+ *   ep_return    the episode's float32 rewards added in float64 from 0.0, first row to last, one after another
+ *                (iqlhip_rows_return_range's value), on every row of the episode
+ *   return_to_go G[last] = (double)r[last]; G[i] = (double)r[i] + discount * G[i+1] down the episode, the product
+ *                rounded, then the sum: Cal-QL's recurrence bit for bit (a last reward of -0.0 stays -0.0)
+ *   sparse_value (host pointer; NULL: off) an episode whose (double)r[last] == *sparse_value gets
+ *                return_to_go = (double)r[last] / (1.0 - discount) on all its rows (ours: not claimed bit-equal to the
+ *                reference, whose branch mixes numpy scalar types)
+ *   episodes_out (host; may be NULL) the number of episodes; zero episodes is a result, not an error
+ * NaN rewards and NaN states are outside the contract.  One thread walks one episode in order; the spans and the
+ * ep_return broadcast are row-parallel.  Device scratch (9 B per row) is allocated and freed on `stream`; nothing stays
+ * attached to any context.  Synchronises `stream` only when episodes_out is given.  No column of the rows is written.
+ * IQLHIP_EINVAL before any device work: what the reward calls above refuse, max_episode_steps < 1, a NaN, infinite or
+ * negative discount, a NaN state_break_tol, unknown flag bits, all five outputs NULL, sparse_value with discount == 1. */
+#define IQLHIP_EP_KEEP_TAIL 1
+int iqlhip_rows_episode_returns(const float* rows_dev, int64_t ld, int32_t state_dim, int32_t action_dim, int64_t row0,
+                                int64_t n, int64_t max_episode_steps, double discount, double state_break_tol,
+                                int32_t flags, const double* sparse_value, double* ep_return_dev,
+                                double* return_to_go_dev, int64_t* ep_first_dev, int64_t* ep_last_dev,
+                                int64_t* episodes_out, void* stream);
 /* Device-side index draw used by iqlhip_train_steps, exposed for tests. */
 int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed, uint64_t offset, void* stream);
 

@@ -4294,3 +4294,71 @@ extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev,
   const MixSrc mx{nullptr, 0, weights_tab(table), table->gen};
   return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
 }
+
+// ---------------------------------------------------------------------------
+// Per-row episode spans, returns and return-to-go (include/iqlhip.h iqlhip_rows_episode_returns; DESIGN.md 6c-2;
+// kernels: iqlhip_episode_kernels.h, included HERE, behind every other kernel of the file, as the scoring and the
+// weighted-sampling kernels are).  Scratch lives for the call alone, like launch_return_range's.
+#include "iqlhip_episode_kernels.h"
+static_assert(EP_KEEP_TAIL == IQLHIP_EP_KEEP_TAIL, "kernel and header disagree on the tail flag");
+
+extern "C" int iqlhip_rows_episode_returns(const float* rows_dev, int64_t ld, int32_t S, int32_t A, int64_t row0, int64_t n,
+                                           int64_t max_episode_steps, double discount, double state_break_tol, int32_t flags,
+                                           const double* sparse_value, double* ep_return_dev, double* return_to_go_dev,
+                                           int64_t* ep_first_dev, int64_t* ep_last_dev, int64_t* episodes_out, void* stream) {
+  int rc = reward_args_ok(rows_dev, ld, S, A, row0, n, "rows_episode_returns");
+  if (rc) return rc;
+  if (max_episode_steps < 1) return fail(IQLHIP_EINVAL, "max_episode_steps must be at least 1");
+  if (!(discount >= 0.0) || std::isinf(discount)) return fail(IQLHIP_EINVAL, "discount must be finite and not negative");
+  if (std::isnan(state_break_tol)) return fail(IQLHIP_EINVAL, "state_break_tol is NaN");
+  if (flags & ~IQLHIP_EP_KEEP_TAIL) return fail(IQLHIP_EINVAL, "unknown flag bits 0x%x", (unsigned)(flags & ~IQLHIP_EP_KEEP_TAIL));
+  if (!ep_return_dev && !return_to_go_dev && !ep_first_dev && !ep_last_dev && !episodes_out)
+    return fail(IQLHIP_EINVAL, "no output requested");
+  if (sparse_value && discount == 1.0) return fail(IQLHIP_EINVAL, "the sparse option divides by 1 - discount: discount must not be 1");
+  hipStream_t st = (hipStream_t)stream;
+  const long long N = (long long)n, T = (long long)max_episode_steps;
+  const long long ntiles = (N + RR_TILE - 1) / RR_TILE;
+  const int nb = (int)std::min<long long>(ntiles, RR_MAX_BLOCKS);
+  const bool rule = state_break_tol >= 0.0;
+  const int keep_tail = flags & IQLHIP_EP_KEEP_TAIL;
+  // scratch: prev[n] | tile partials[ntiles] | episode count | flag bytes[n]
+  const size_t bytes = ((size_t)N + (size_t)ntiles + 1) * sizeof(long long) + (size_t)N;
+  char* scratch = nullptr;
+  HIPCHK(hipMallocAsync((void**)&scratch, bytes, st));
+  long long* prev = (long long*)scratch;
+  long long* tiles = prev + N;
+  unsigned long long* count = (unsigned long long*)(tiles + ntiles);
+  unsigned char* flag = (unsigned char*)(count + 1);
+  hipError_t e = hipMemsetAsync(count, 0, sizeof *count, st);
+  if (e == hipSuccess) {
+    if (rule)
+      hipLaunchKernelGGL(iql_ep_break_kernel<true>, dim3((unsigned)std::min<long long>((N + RR_TILE / EP_LANES - 1) / (RR_TILE / EP_LANES), EP_BREAK_MAX_BLOCKS)),
+                         dim3(RR_TILE), 0, st, rows_dev, (long long)ld, (int)S, (int)A, (long long)row0, N,
+                         state_break_tol * state_break_tol, flag);
+    else
+      hipLaunchKernelGGL(iql_ep_break_kernel<false>, dim3(nb), dim3(RR_TILE), 0, st, rows_dev, (long long)ld, (int)S, (int)A,
+                         (long long)row0, N, 0.0, flag);
+    hipLaunchKernelGGL(iql_ep_scan_reduce_kernel, dim3(nb), dim3(RR_TILE), 0, st, (const unsigned char*)flag, N, ntiles, tiles);
+    hipLaunchKernelGGL(iql_rr_scan_partials_kernel, dim3(1), dim3(RR_TILE), 0, st, tiles, ntiles);
+    hipLaunchKernelGGL(iql_ep_scan_apply_kernel, dim3(nb), dim3(RR_TILE), 0, st, (const unsigned char*)flag, N, ntiles,
+                       (const long long*)tiles, prev);
+    if (ep_return_dev || return_to_go_dev || episodes_out)
+      hipLaunchKernelGGL(iql_ep_walk_kernel, dim3(nb), dim3(RR_TILE), 0, st, rows_dev, (long long)ld, 2 * (int)S + (int)A,
+                         (long long)row0, N, ntiles, T, keep_tail, discount, sparse_value ? 1 : 0,
+                         sparse_value ? *sparse_value : 0.0, (const long long*)prev, ep_return_dev, return_to_go_dev, count);
+    if (ep_return_dev || return_to_go_dev || ep_first_dev || ep_last_dev)
+      hipLaunchKernelGGL(iql_ep_rows_kernel, dim3(nb), dim3(RR_TILE), 0, st, N, T, keep_tail, (const long long*)prev,
+                         ep_return_dev, return_to_go_dev, (long long*)ep_first_dev, (long long*)ep_last_dev);
+    e = hipGetLastError();
+  }
+  unsigned long long episodes = 0;
+  if (e == hipSuccess && episodes_out) {
+    e = hipMemcpyAsync(&episodes, count, sizeof episodes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  const hipError_t e_free = hipFreeAsync(scratch, st);
+  HIPCHK(e);
+  HIPCHK(e_free);
+  if (episodes_out) *episodes_out = (int64_t)episodes;
+  return IQLHIP_OK;
+}

@@ -35,6 +35,7 @@ IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
 XCH_NONE, XCH_RCCL, XCH_P2P = 0, 1, 2
 TS_CONTINUE = 1
+IQLHIP_EP_KEEP_TAIL = 1       # iqlhip_rows_episode_returns: the last row of the range ends an episode
 NET_V, NET_Q1, NET_Q2, NET_PI = 0, 1, 2, 3
 POLICY_GAUSSIAN, POLICY_DETERMINISTIC = 0, 1
 
@@ -152,6 +153,9 @@ SYMBOLS = [
                                            C.c_float, C.c_void_p]),
     ("iqlhip_rows_reward_shift", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_float,
                                            C.c_void_p]),
+    ("iqlhip_rows_episode_returns", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
     ("iqlhip_draw_indices", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("iqlhip_weights_build", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("iqlhip_weights_free", C.c_int, [C.c_void_p]),

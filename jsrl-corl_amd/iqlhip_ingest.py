@@ -15,6 +15,10 @@ episode boundaries and sums every episode's rewards in float64 in row order, one
 it returns are the reference's Python floats bit for bit; `ReplayBuffer.modify_reward_` rescales the stored rewards with
 them (load -> buf.modify_reward_(env_name, max_episode_steps)).  The host functions `return_reward_range` /
 `modify_reward` of the drop-in modules stay what they are for host datasets.
+
+Episode returns (`episode_returns_device`, `EpisodeReturns`): every row's episode span, episode return
+and discounted return-to-go as device tensors — get_return_to_go of finetune/cal_ql.py and the episodes of
+keep_best_trajectories of offline/any_percent_bc.py — for `set_sample_weights` or next to `score_buffer`'s columns.
 """
 from __future__ import annotations
 
@@ -72,3 +76,68 @@ def return_reward_range_device(rows: torch.Tensor, state_dim: int, action_dim: i
         hb.check(hb.lib().iqlhip_rows_return_range(rows.data_ptr(), rows.stride(0), state_dim, action_dim, 0, n,
                                                    int(max_episode_steps), out, C.byref(episodes), _stream(rows.device)))
     return float(out[0]), float(out[1])
+
+
+class EpisodeReturns:
+    """What `episode_returns_device` computed, as device tensors over the n rows it covered: `ep_return` and
+    `return_to_go` (float64 [n]), `ep_first` and `ep_last` (int64 [n], -1 on tail rows that belong to no episode), and
+    `episodes` (int)."""
+
+    def __init__(self, ep_return, return_to_go, ep_first, ep_last, episodes: int):
+        self.ep_return, self.return_to_go = ep_return, return_to_go
+        self.ep_first, self.ep_last = ep_first, ep_last
+        self.episodes = int(episodes)
+
+    def episode_table(self):
+        """(first[E], last[E], ep_return[E], return_to_go_at_first[E]): one entry per episode in row order, compacted on
+        the device at the rows that end an episode.  return_to_go at an episode's first row is its discounted return."""
+        n = self.ep_last.shape[0]
+        last = torch.nonzero(self.ep_last == torch.arange(n, device=self.ep_last.device)).reshape(-1)
+        first = self.ep_first[last]
+        return first, last, self.ep_return[last], self.return_to_go[first]
+
+    def top_fraction_weights(self, frac: float, by: str = "return_to_go") -> torch.Tensor:
+        """float32 [n] sampling weights: 1.0 on the rows of the best max(1, int(frac * E)) episodes, 0.0 elsewhere —
+        keep_best_trajectories (offline/any_percent_bc.py) as a distribution for set_sample_weights instead of a
+        rewritten dataset.  Episodes are ranked by `by` descending ("return_to_go": the value at the episode's first
+        row; or "ep_return"), ties going to the earlier episode."""
+        if by not in ("return_to_go", "ep_return"):
+            raise ValueError('by must be "return_to_go" or "ep_return"')
+        if self.episodes == 0:
+            raise ValueError("no episode to rank")
+        _, last, ret, g0 = self.episode_table()
+        order = torch.sort(g0 if by == "return_to_go" else ret, descending=True, stable=True).indices
+        keep = order[: max(1, int(frac * last.shape[0]))]
+        at_last = torch.zeros(self.ep_last.shape[0], dtype=torch.float32, device=self.ep_last.device)
+        at_last[last[keep]] = 1.0
+        w = at_last[self.ep_last.clamp(min=0)]
+        return torch.where(self.ep_last >= 0, w, torch.zeros_like(w))
+
+
+def episode_returns_device(rows: torch.Tensor, state_dim: int, action_dim: int, n: int, max_episode_steps: int,
+                           discount: float, state_break_tol=None, keep_tail: bool = False, sparse_value=None,
+                           row0: int = 0) -> EpisodeReturns:
+    """Per-row episode spans, returns and discounted return-to-go of rows [row0, row0 + n) of a packed device row store,
+    in storage order (iqlhip_rows_episode_returns; include/iqlhip.h states the arithmetic): get_return_to_go of the
+    reference's finetune/cal_ql.py (state_break_tol=1e-6, keep_tail=True) and the episodes of keep_best_trajectories of
+    offline/any_percent_bc.py (both off).  Reads only.  Synchronises the current stream."""
+    if rows.device.type != "cuda":
+        raise RuntimeError("iqlhip: episode_returns_device needs a GPU tensor")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.stride(1) != 1:
+        raise ValueError("expected a float32 [rows, ld] tensor with unit column stride")
+    if n < 1 or row0 < 0 or row0 + n > rows.shape[0]:
+        raise ValueError("[row0, row0 + n) outside the row store")
+    dev = rows.device
+    ep_return = torch.empty(n, dtype=torch.float64, device=dev)
+    return_to_go = torch.empty(n, dtype=torch.float64, device=dev)
+    ep_first = torch.empty(n, dtype=torch.int64, device=dev)
+    ep_last = torch.empty(n, dtype=torch.int64, device=dev)
+    episodes = C.c_int64(0)
+    sparse = None if sparse_value is None else C.byref(C.c_double(float(sparse_value)))
+    with torch.cuda.device(dev):
+        hb.check(hb.lib().iqlhip_rows_episode_returns(
+            rows.data_ptr(), rows.stride(0), state_dim, action_dim, int(row0), int(n), int(max_episode_steps),
+            float(discount), -1.0 if state_break_tol is None else float(state_break_tol),
+            hb.IQLHIP_EP_KEEP_TAIL if keep_tail else 0, sparse, ep_return.data_ptr(), return_to_go.data_ptr(),
+            ep_first.data_ptr(), ep_last.data_ptr(), C.byref(episodes), _stream(dev)))
+    return EpisodeReturns(ep_return, return_to_go, ep_first, ep_last, episodes.value)

@@ -210,6 +210,21 @@ class ReplayBuffer:
             hb.check(hb.lib().iqlhip_rows_reward_scale(*geometry, max_ret - min_ret, float(max_episode_steps), self._stream()))
         return {"max_ret": max_ret, "min_ret": min_ret, "max_episode_steps": max_episode_steps}
 
+    def episode_returns(self, max_episode_steps: int = 1000, discount: float = 0.99, state_break_tol=None,
+                        keep_tail: bool = False, sparse_value=None):
+        """Per-row episode spans, episode returns and discounted return-to-go of the stored rows [0, size) in storage
+        order (a freshly loaded dataset, not a wrapped online ring), as device tensors: an
+        iqlhip_ingest.EpisodeReturns.  state_break_tol=1e-6, keep_tail=True: get_return_to_go of the reference's
+        finetune/cal_ql.py; both off: the episodes of return_reward_range and of keep_best_trajectories.  Reads only:
+        rows staged ahead by train_steps stay valid."""
+        import iqlhip_ingest as ing
+        if not self._gpu:
+            raise RuntimeError("iqlhip: episode_returns runs in libiqlhip.so and needs a GPU buffer")
+        if self._size < 1:
+            raise ValueError("replay buffer is empty")
+        return ing.episode_returns_device(self._rows, self._state_dim, self._action_dim, self._size, max_episode_steps,
+                                          discount, state_break_tol, keep_tail, sparse_value)
+
     def _index_bound(self) -> int:
         return self._size
 

@@ -834,6 +834,56 @@ def reward_range_case(ref, outdir):
     print("g17_reward_range ok", names)
 
 
+def return_to_go_case(ref_root, outdir):
+    """G18: get_return_to_go of the reference's finetune/cal_ql.py (non-sparse branch) and keep_best_trajectories of
+    offline/any_percent_bc.py, both imported under other module names with the stubs of import_reference, run on a few
+    hundred rows: wide-magnitude mixed-sign rewards, terminals, one state discontinuity without a terminal, episodes cut
+    by the length rule and a tail that only `t == N - 1` ends.  Stored: the inputs, the returns-to-go as float64, and the
+    index set keep_best_trajectories keeps (on rewards whose episode returns are tie-free and well apart)."""
+    def load(name, *path):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(ref_root, "algorithms", *path))
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        return m
+
+    cal_ql, bc = load("ref_cal_ql", "finetune", "cal_ql.py"), load("ref_any_percent_bc", "offline", "any_percent_bc.py")
+    rng = np.random.default_rng(180)
+    n, S, T, discount = 400, 5, 60, 0.99
+    r = (rng.choice([-1.0, 1.0], size=n) * 10.0 ** rng.uniform(-6.0, 6.0, size=n)).astype(np.float32)
+    d = np.zeros(n, np.float32)
+    d[[30, 31, 150, 209, 330]] = 1.0        # consecutive terminals; 209 = 150 + 59 is not a length-rule row (151 + 59 is)
+    obs = rng.standard_normal((n + 1, S)).astype(np.float32).cumsum(0, dtype=np.float32)
+    s, ns = obs[:-1].copy(), obs[1:].copy()     # continuous: s[i+1] == s'[i]
+    s[101, 2] += np.float32(0.5)                # ... but for one jump between rows 100 and 101, with no terminal there
+    data = {"observations": s, "next_observations": ns, "rewards": r, "terminals": d}
+    env = types.SimpleNamespace(_max_episode_steps=T, ref_min_score=0.0)
+    cfg = types.SimpleNamespace(discount=discount, is_sparse_reward=False, reward_scale=1.0, reward_bias=0.0)
+    rtg = cal_ql.get_return_to_go(data, env, cfg)
+    assert len(rtg) == n and all(type(x) is float for x in rtg)
+    # keep_best_trajectories: rewards whose discounted episode returns are far apart (no ties, no near-ties in float32)
+    kr = (rng.standard_normal(n) * 0.1).astype(np.float32)
+    kd = np.zeros(n, np.float32)
+    kd[[24, 25, 90, 200, 260, 399]] = 1.0
+    ends = [i for i in range(n) if kd[i] != 0]
+    level = rng.permutation(len(ends) + 4).astype(np.float32)
+    e = 0
+    for i in range(n):
+        kr[i] += level[e]
+        e += int(kd[i] != 0)
+    kept = {}
+    for frac in (0.1, 0.34, 0.5, 1.0):
+        kdata = {"observations": np.arange(n, dtype=np.int64), "actions": np.zeros(n), "next_observations": np.zeros(n),
+                 "rewards": kr.copy(), "terminals": kd.copy()}
+        bc.keep_best_trajectories(kdata, frac, discount, T)
+        kept[frac] = np.sort(kdata["observations"])            # (the row indices it kept, through the observations column)
+    out = {"s": s, "ns": ns, "rewards": r, "terminals": d, "T": np.int64(T), "discount": np.float64(discount),
+           "tol": np.float64(1e-6), "return_to_go": np.asarray(rtg, np.float64), "keep_rewards": kr, "keep_terminals": kd}
+    for frac, idx in kept.items():
+        out[f"kept_{frac}"] = idx.astype(np.int64)
+    np.savez(os.path.join(outdir, "g18_return_to_go.npz"), meta=np.array(json.dumps({"fracs": list(kept)})), **out)
+    print("g18_return_to_go ok", {f: len(v) for f, v in kept.items()})
+
+
 def round2_cases(ref, args):
     jsrl = import_reference_jsrl(args.ref)
     resume_case(ref, "g11_resume_S17A6_gauss", 17, 6, True, 110, 13, args.out)
@@ -851,7 +901,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--only", default=None, help="'act': only the G10 act fixtures; 'r2': only the round-2 fixtures "
                                                  "(g11 resume, g12 JSRL hand-off, g13 JSRL host logic, g14 config-5 batch); "
-                                                 "'reward': only g17 (return_reward_range / modify_reward)")
+                                                 "'reward': only g17 (return_reward_range / modify_reward); "
+                                                 "'returns': only g18 (get_return_to_go / keep_best_trajectories)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     torch.set_num_threads(1)
@@ -861,6 +912,9 @@ def main():
         return
     if args.only == "reward":
         reward_range_case(ref, args.out)
+        return
+    if args.only == "returns":
+        return_to_go_case(args.ref, args.out)
         return
     if args.only == "r2":
         round2_cases(ref, args)
