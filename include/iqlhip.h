@@ -745,6 +745,61 @@ int iqlhip_actor_sample(iqlhip_ctx* ctx, const float* states_dev, int64_t ld_s, 
  * iqlhip_actor_forward when its buffers are host-mapped, i.e. the `.cpu()` of the reference's act() (iql.py:379). */
 int iqlhip_stream_synchronize(void* stream);
 
+/* ---- JSRL action selection (DESIGN.md 6k "JSRL action selection") ----------------------------------------------------
+ * jsrl_utils.learner_or_guide_action for K >= 1 (learner, guide, gate) triples of bound contexts in one set of launches:
+ * member k's states are packed once, ONE forward launch runs the policy instance of the learners and the guides and
+ * the value instance V(s) of the gates the call needs (the existing forward body behind a record table, as
+ * iqlhip_group_actor_forward runs it; contexts of different precision take one launch per precision), and ONE finish
+ * launch decides per row and writes action, flag and gate value.  Three launches for any K.
+ * A handle ties the triples together.  1 <= k <= IQLHIP_MAX_GROUP; all contexts on one device; learner and guide of a
+ * member have equal state_dim and action_dim (the policy kind may differ), its gate (gates == NULL or gates[k] == NULL:
+ * none) the same state_dim.  Learner and guide may be the same context, and a context may serve several members.  The
+ * handle owns the packed states and the head partials of every member (sized by the smallest act capacity of its
+ * triple), so the contexts' own inference scratch is left alone.  The contexts must outlive the handle.
+ * Selection, per row r of member k:  who[k][r] = 0: the guide acts; 1: the learner acts; 2: the gate decides,
+ *   h = V_gate(states[k][r])  (the value network of the gate context),   use_learner = (h <= gate_max[k])  in fp32.
+ * Every host-known part of the reference's horizon rules (time step against stage, goal distance, ep_agent_type <=
+ * agent_type_stage, the last stage, a NaN stage, the agent_type rule's host random draw) is folded into `who` by the
+ * caller; the device evaluates only the state-dependent gate.  who and gate_max are HOST arrays, read during the call.
+ * Actions: a learner row is exactly what iqlhip_actor_forward (seeds[k] == 0) or iqlhip_actor_sample (seeds[k] != 0) on
+ * the learner writes for that row of the same states array, with max_action_learner[k]; a guide row is the guide's
+ * eval-mode mean (iqlhip_actor_forward without noise) with max_action_guide[k].
+ * Counters: with seeds[k] != 0 and rows[k] > 0 the LEARNER's act() call counter advances by one per call, whatever the
+ * rows chose — also when `who` is 0 for every row: the gate's outcome is not known to the host, so "one call, one
+ * number" is the only rule that can be kept for all `who` alike.  The guide's and the gate's counters never move.
+ * use_learner[k] (NULL table or entry: not written) receives 0 / 1 per row.  gate_out[k] (NULL: not written) receives h
+ * for every row of a member with a gate.  The gate forward runs for a member that has a `2` or a gate_out entry; the
+ * learner forward for one that has a `1` or a `2`; the guide forward for one that has a `0` or a `2`.
+ * rows[k] == 0 skips member k (no launch, no counter).  Each context runs at its own precision, as in its solo call;
+ * the shadows of bf16 contexts are refreshed first.  flags & IQLHIP_GROUP_ACT_WAIT as in iqlhip_group_actor_forward;
+ * without it the call is asynchronous on `stream` (successive calls of one handle on one stream).
+ * Checked before any launch or counter change: IQLHIP_EINVAL for a NULL handle, table or entry (of a member with
+ * rows), dims that differ as said above, rows[k] above the smallest act capacity of the triple, a stride smaller than
+ * the row, a who value outside 0..2, who == 2 (or a gate_out entry) on a member without a gate, unknown flags;
+ * IQLHIP_ENOTBOUND for an unbound context; IQLHIP_EUNSUPPORTED when a learner or guide has an inference dropout rate
+ * (iqlhip_set_act_dropout): compose the solo calls for those. */
+typedef struct iqlhip_jsrl iqlhip_jsrl;
+int iqlhip_jsrl_create(iqlhip_ctx* const* learners, iqlhip_ctx* const* guides, iqlhip_ctx* const* gates, int k,
+                       iqlhip_jsrl** out);
+int iqlhip_jsrl_destroy(iqlhip_jsrl* jsrl);
+int iqlhip_jsrl_act(iqlhip_jsrl* jsrl, const float* const* states, int64_t ld_s, const int32_t* rows,
+                    const int8_t* const* who, const float* gate_max, const uint64_t* seeds,
+                    const float* max_action_learner, const float* max_action_guide, float* const* actions, int64_t ld_a,
+                    int32_t* const* use_learner, float* const* gate_out, int32_t flags, void* stream);
+/* One online iteration of a K = 1 handle's learner plus the next action's selection, under ONE synchronisation: the
+ * ring write, gather and step of iqlhip_online_step without an act (same arguments, same checks), then the one-row
+ * selection above with the just-updated learner — state, action, flag and h travel through host-mapped words.  Losses
+ * and everything the learner holds are bit for bit what iqlhip_online_step without act_state_host leaves; action,
+ * *use_learner_out and *gate_out (NULL: not returned, and no gate forward unless who == 2) are what iqlhip_jsrl_act
+ * gives when called afterwards with the same arguments.  act_seed != 0 advances the learner's act() counter by one (the
+ * rule above).  who == 2 or gate_out on a handle without a gate, K != 1, and every check of the two calls it stands
+ * for: before any launch or counter change. */
+int iqlhip_jsrl_online_step(iqlhip_jsrl* jsrl, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                            const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
+                            float out[3], const float* act_state_host, int8_t who, float gate_max, uint64_t act_seed,
+                            float max_action_learner, float max_action_guide, float* act_out_host,
+                            int32_t* use_learner_out, float* gate_out, void* stream);
+
 /* ---- introspection (tests, profiling) ----------------------------------- */
 /* Copy a named library-owned scratch array to host (synchronous).  Names:
  * "h0","h1" (activations [4][max_batch][256]), "heads" (partial head sums),

@@ -1637,13 +1637,15 @@ static int actor_forward_impl(iqlhip_ctx* c, const float* states_dev, int64_t ld
 // with the losses landing in pinned host words; then one stream synchronisation.
 // iqlhip_online_step (rows_off_dev == nullptr, n_off == 0) and iqlhip_online_step_mixed: the batch's first n_off rows
 // are rows_off_dev[idx_off_host[..]] (size_off rows, read only), the n behind them come from the ring.
-static int online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
-                       const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
-                       float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
-                       float* act_out_host, void* stream, const float* rows_off_dev, int64_t size_off,
-                       const int64_t* idx_off_host, int32_t n_off) {
+// The part every form of the online iteration shares (iqlhip_online_step, iqlhip_online_step_mixed,
+// iqlhip_jsrl_online_step): the checks, the ring write + gather and the step, queued on `stream`.  act_follows: the
+// call's completion word is left to the launch that follows the step (an act's finish); else the update stores it.
+static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                             const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
+                             const float* out, bool act_follows, void* stream, const float* rows_off_dev,
+                             int64_t size_off, const int64_t* idx_off_host, int32_t n_off,
+                             unsigned long long* done_val_out) {
   if (!c || !rows_dev || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
-  if (act_state_host && !act_out_host) return fail(IQLHIP_EINVAL, "act_state_host without act_out_host");
   if (!c->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_bind has not been called");
   if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
   if (((uintptr_t)rows_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
@@ -1674,10 +1676,26 @@ static int online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capac
   eager_begin(c, B, sc, st, c->xb, e);
   e.u.losses_mirror = c->on_loss_pin;
   const unsigned long long done_val = ++c->done_seq;
-  if (!act_state_host) { e.u.done_flag = c->done_pin; e.u.done_val = done_val; }      // (else the follow-up act() signals)
+  if (!act_follows) { e.u.done_flag = c->done_pin; e.u.done_val = done_val; }      // (else the follow-up act() signals)
   int rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr, e.stats());
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
+  *done_val_out = done_val;
+  return IQLHIP_OK;
+}
+static int online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                       const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
+                       float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
+                       float* act_out_host, void* stream, const float* rows_off_dev, int64_t size_off,
+                       const int64_t* idx_off_host, int32_t n_off) {
+  if (!c || !rows_dev || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (act_state_host && !act_out_host) return fail(IQLHIP_EINVAL, "act_state_host without act_out_host");
+  unsigned long long done_val = 0;
+  int rc = online_step_front(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host != nullptr,
+                             stream, rows_off_dev, size_off, idx_off_host, n_off, &done_val);
+  if (rc) return rc;
+  DevGuard guard(c->device);
+  hipStream_t st = (hipStream_t)stream;
   const int S = c->dims.state_dim, A = c->dims.action_dim;
   if (act_state_host) {
     // the NEXT iteration's actor.act(next_state) with the just-updated policy, in the same stream and under the
@@ -4360,5 +4378,330 @@ extern "C" int iqlhip_rows_episode_returns(const float* rows_dev, int64_t ld, in
   HIPCHK(e);
   HIPCHK(e_free);
   if (episodes_out) *episodes_out = (int64_t)episodes;
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// JSRL action selection (include/iqlhip.h iqlhip_jsrl_act; the finish kernels: iqlhip_jsrl_kernels.h,
+// included HERE, behind every other kernel of the file).  Pack (iql_pack_states_group_kernel), forward
+// (iql_act_fwd_group_kernel over the call's records) and finish, with the records uploaded as the group act uploads its.
+#include "iqlhip_jsrl_kernels.h"
+
+struct iqlhip_jsrl {
+  int k = 0;
+  int device = 0;
+  iqlhip_ctx* l[IQLHIP_MAX_GROUP] = {};      // learners
+  iqlhip_ctx* g[IQLHIP_MAX_GROUP] = {};      // guides
+  iqlhip_ctx* v[IQLHIP_MAX_GROUP] = {};      // gates (entries may be NULL)
+  int cap[IQLHIP_MAX_GROUP] = {};            // the smallest act capacity of the triple
+  Owned own;
+  // per member: the packed states (the learner's row stride; xb_v: the gate's own copy where its stride differs, else
+  // xb) and the head partials of the three roles
+  float* xb[IQLHIP_MAX_GROUP] = {};
+  float* xb_v[IQLHIP_MAX_GROUP] = {};
+  float* heads_l[IQLHIP_MAX_GROUP] = {};
+  float* heads_g[IQLHIP_MAX_GROUP] = {};
+  float* heads_v[IQLHIP_MAX_GROUP] = {};
+  // the call's records (built in `host`, uploaded through act.pin when their used part differs from the last upload's):
+  // packs [2 k], forwards [3 k], finishes [k], then the members' who bytes, back to back from `who`
+  Staging act;
+  Section<GroupPackRec> packs; Section<StepParams> ps; Section<JsrlFinRec> fins; Section<signed char> who;
+  std::vector<char> host, last;
+  size_t last_used = 0;
+  hipEvent_t up = nullptr;
+  bool pending = false;
+  unsigned long long* done_pin = nullptr;    // completion word of IQLHIP_GROUP_ACT_WAIT calls
+  unsigned long long done_seq = 0;
+  float* on_pin = nullptr;                   // iqlhip_jsrl_online_step: host-mapped [0] the flag (an int), [1] h
+};
+
+extern "C" int iqlhip_jsrl_destroy(iqlhip_jsrl* j) {
+  if (!j) return fail(IQLHIP_EINVAL, "NULL handle");
+  DevGuard guard(j->device);
+  (void)hipDeviceSynchronize();       // a call may still be running on some stream
+  j->own.release_all();
+  delete j;
+  return IQLHIP_OK;
+}
+
+static int jsrl_check_triples(iqlhip_ctx* const* learners, iqlhip_ctx* const* guides, iqlhip_ctx* const* gates, int k) {
+  if (!learners || !guides) return fail(IQLHIP_EINVAL, "NULL learner or guide table");
+  if (k < 1 || k > IQLHIP_MAX_GROUP) return fail(IQLHIP_EINVAL, "member count %d outside [1,%d]", k, IQLHIP_MAX_GROUP);
+  for (int i = 0; i < k; ++i) {
+    const iqlhip_ctx* l = learners[i];
+    const iqlhip_ctx* g = guides[i];
+    const iqlhip_ctx* v = gates ? gates[i] : nullptr;
+    if (!l || !g) return fail(IQLHIP_EINVAL, "member %d: NULL learner or guide", i);
+    if (l->device != learners[0]->device || g->device != l->device || (v && v->device != l->device))
+      return fail(IQLHIP_EINVAL, "member %d: contexts on different devices", i);
+    if (g->dims.state_dim != l->dims.state_dim || (v && v->dims.state_dim != l->dims.state_dim))
+      return fail(IQLHIP_EINVAL, "member %d: state_dim differs between learner, guide and gate", i);
+    if (g->dims.action_dim != l->dims.action_dim)
+      return fail(IQLHIP_EINVAL, "member %d: action_dim differs between learner and guide", i);
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_jsrl_create(iqlhip_ctx* const* learners, iqlhip_ctx* const* guides, iqlhip_ctx* const* gates, int k,
+                                  iqlhip_jsrl** out) {
+  if (!out) return fail(IQLHIP_EINVAL, "out is NULL");
+  int rc = jsrl_check_triples(learners, guides, gates, k);
+  if (rc) return rc;
+  iqlhip_jsrl* j = new iqlhip_jsrl();
+  j->k = k;
+  j->device = learners[0]->device;
+  DevGuard guard(j->device);
+  auto setup = [&]() -> int {
+    size_t who_bytes = 0, lds = 0;
+    for (int i = 0; i < k; ++i) {
+      iqlhip_ctx* l = j->l[i] = learners[i];
+      iqlhip_ctx* g = j->g[i] = guides[i];
+      iqlhip_ctx* v = j->v[i] = gates ? gates[i] : nullptr;
+      const int cap = j->cap[i] = std::min(std::min(l->act_cap, g->act_cap), v ? v->act_cap : l->act_cap);
+      const int A = l->dims.action_dim;
+      HIPCHK(j->own.dev(&j->xb[i], (size_t)cap * l->row_ld * sizeof(float), 0));
+      HIPCHK(j->own.dev(&j->heads_l[i], (size_t)cap * A * NSPLIT * sizeof(float), 0));
+      HIPCHK(j->own.dev(&j->heads_g[i], (size_t)cap * A * NSPLIT * sizeof(float), 0));
+      j->xb_v[i] = j->xb[i];
+      if (v) {
+        HIPCHK(j->own.dev(&j->heads_v[i], (size_t)cap * HEAD_LD * sizeof(float), 0));
+        if (v->row_ld != l->row_ld) HIPCHK(j->own.dev(&j->xb_v[i], (size_t)cap * v->row_ld * sizeof(float), 0));
+      }
+      who_bytes += (size_t)up(cap, 16);
+      for (const iqlhip_ctx* c : {(const iqlhip_ctx*)l, (const iqlhip_ctx*)g, (const iqlhip_ctx*)v})
+        if (c) lds = std::max(lds, c->lds_fwd_solo);
+    }
+    j->packs = j->act.add<GroupPackRec>(2 * (size_t)k);
+    j->ps = j->act.add<StepParams>(3 * (size_t)k);
+    j->fins = j->act.add<JsrlFinRec>(k);
+    j->who = j->act.add<signed char>(who_bytes);
+    if (int rc_s = j->act.alloc(j->own)) return rc_s;
+    j->host.assign(j->act.bytes, 0);
+    j->last.assign(j->act.bytes, 0);
+    HIPCHK(j->own.pin(&j->done_pin, 8 * sizeof(unsigned long long), /*zero=*/true));
+    HIPCHK(j->own.pin(&j->on_pin, 8 * sizeof(float), /*zero=*/true));
+    HIPCHK(j->own.event(&j->up, hipEventDisableTiming));
+    return set_max_lds(2, lds, [](unsigned m) { return act_fwd_group_kernel(m & 1, m & 2); });
+  };
+  rc = setup();
+  if (rc) {
+    const std::string msg = g_err;
+    iqlhip_jsrl_destroy(j);
+    g_err = msg;
+    return rc;
+  }
+  *out = j;
+  return IQLHIP_OK;
+}
+
+// What the host reads out of `who` before anything is launched: which forwards member i needs.
+struct JsrlPlan { bool need_l[IQLHIP_MAX_GROUP], need_g[IQLHIP_MAX_GROUP], need_v[IQLHIP_MAX_GROUP]; };
+
+// Every check of iqlhip_jsrl_act; moves and launches nothing.
+static int jsrl_check(const iqlhip_jsrl* j, const float* const* states, int64_t ld_s, const int32_t* rows,
+                      const int8_t* const* who, const float* gate_max, const uint64_t* seeds, const float* max_l,
+                      const float* max_g, float* const* actions, int64_t ld_a, float* const* gate_out, int32_t flags,
+                      JsrlPlan* plan) {
+  if (!j) return fail(IQLHIP_EINVAL, "NULL handle");
+  if (!states || !rows || !who || !seeds || !max_l || !max_g || !actions) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = jsrl_check_triples(j->l, j->g, j->v, j->k);
+  if (rc) return rc;
+  if (flags & ~IQLHIP_GROUP_ACT_WAIT) return fail(IQLHIP_EINVAL, "unknown flags 0x%x", (unsigned)flags);
+  for (int i = 0; i < j->k; ++i) {
+    const iqlhip_ctx* l = j->l[i];
+    const iqlhip_ctx* g = j->g[i];
+    const iqlhip_ctx* v = j->v[i];
+    if (!l->params || !g->params || (v && !v->params))
+      return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called on its learner, guide or gate", i);
+    if (l->act_drop_p > 0.f || g->act_drop_p > 0.f)
+      return fail(IQLHIP_EUNSUPPORTED, "member %d: inference dropout (iqlhip_set_act_dropout) is not supported here", i);
+    if (rows[i] < 0 || rows[i] > j->cap[i]) return fail(IQLHIP_EINVAL, "member %d: rows %d outside [0, %d]", i, rows[i], j->cap[i]);
+    plan->need_l[i] = plan->need_g[i] = plan->need_v[i] = false;
+    if (rows[i] == 0) continue;
+    if (!states[i] || !who[i] || !actions[i]) return fail(IQLHIP_EINVAL, "member %d: NULL states, who or actions", i);
+    if (ld_s < l->dims.state_dim || ld_a < l->dims.action_dim) return fail(IQLHIP_EINVAL, "row stride smaller than the row");
+    bool two = false;
+    for (int r = 0; r < rows[i]; ++r) {
+      const int w = who[i][r];
+      if (w < 0 || w > 2) return fail(IQLHIP_EINVAL, "member %d: who[%d] = %d outside 0..2", i, r, w);
+      if (w != 0) plan->need_l[i] = true;
+      if (w != 1) plan->need_g[i] = true;
+      if (w == 2) two = true;
+    }
+    const bool wants_h = gate_out && gate_out[i];
+    if ((two || wants_h) && !v) return fail(IQLHIP_EINVAL, "member %d: who == 2 or a gate_out entry on a member without a gate", i);
+    if (two && !gate_max) return fail(IQLHIP_EINVAL, "who == 2 without gate_max");
+    plan->need_v[i] = two || wants_h;
+  }
+  return IQLHIP_OK;
+}
+
+// The launches of a checked call.  done_flag: the completion word the finish stores behind its outputs (one member,
+// one block: iqlhip_jsrl_online_step); else IQLHIP_GROUP_ACT_WAIT's own word, or none.
+static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const* states, int64_t ld_s, const int32_t* rows,
+                        const int8_t* const* who, const float* gate_max, const uint64_t* seeds, const float* max_l,
+                        const float* max_g, float* const* actions, int64_t ld_a, int32_t* const* use_learner,
+                        float* const* gate_out, int32_t flags, hipStream_t st, unsigned long long* done_flag,
+                        unsigned long long done_val) {
+  const int K = j->k;
+  Staging& act = j->act;
+  GroupPackRec* packs = Staging::at(j->host.data(), j->packs);
+  StepParams* ps = Staging::at(j->host.data(), j->ps);
+  JsrlFinRec* fins = Staging::at(j->host.data(), j->fins);
+  signed char* who_host = Staging::at(j->host.data(), j->who);
+  const signed char* who_dev = act.device(j->who);
+  // forward records sorted by kernel variant (bit 0: bf16, bit 1: wide layer-0 staging by LDS-DMA): one launch each
+  struct Fwd { StepParams p; int variant; size_t lds; int rows; };
+  Fwd fwd[3 * IQLHIP_MAX_GROUP];
+  int n_fwd = 0, n_pack = 0, n_req = 0, max_rows = 0, max_pack = 0, max_fin = 0;
+  size_t who_off = 0;
+  auto add_fwd = [&](const iqlhip_ctx* c, int n, const float* xb, float* heads, int inst) {
+    Fwd& f = fwd[n_fwd++];
+    f.p = act_step_params(c, n);
+    f.p.xb = xb;
+    f.p.only_inst = inst;
+    f.p.slot[inst] = -1;
+    f.p.drop_bits = nullptr; f.p.drop_scale = 1.f;
+    f.p.sc.heads = heads; f.p.sc.max_batch = 0;
+    f.variant = (c->precision == 1 ? 1 : 0) | (c->w0_lds_k > W0_LDS_MAX_K ? 2 : 0);
+    f.lds = c->lds_fwd_solo;
+    f.rows = n;
+  };
+  for (int i = 0; i < K; ++i) {
+    if (rows[i] == 0) continue;
+    iqlhip_ctx* l = j->l[i];
+    const iqlhip_ctx* g = j->g[i];
+    const iqlhip_ctx* v = j->v[i];
+    const int n = rows[i], S = l->dims.state_dim, A = l->dims.action_dim;
+    GroupPackRec& pk = packs[n_pack++];
+    pk.xb = j->xb[i]; pk.s = states[i]; pk.ld_s = (long long)ld_s; pk.ld = (int)l->row_ld; pk.S = S; pk.n = n;
+    max_pack = std::max(max_pack, n * (int)l->row_ld);
+    if (plan.need_v[i] && j->xb_v[i] != j->xb[i]) {
+      GroupPackRec& pv = packs[n_pack++];
+      pv = pk; pv.xb = j->xb_v[i]; pv.ld = (int)v->row_ld;
+      max_pack = std::max(max_pack, n * (int)v->row_ld);
+    }
+    if (plan.need_l[i]) add_fwd(l, n, j->xb[i], j->heads_l[i], 6);
+    if (plan.need_g[i]) add_fwd(g, n, j->xb[i], j->heads_g[i], 6);
+    if (plan.need_v[i]) add_fwd(v, n, j->xb_v[i], j->heads_v[i], 1);
+    memcpy(who_host + who_off, who[i], (size_t)n);
+    JsrlFinRec& f = fins[n_req++];
+    f.heads_l = plan.need_l[i] ? j->heads_l[i] : nullptr;
+    f.heads_g = plan.need_g[i] ? j->heads_g[i] : nullptr;
+    f.heads_v = plan.need_v[i] ? j->heads_v[i] : nullptr;
+    f.log_std = (l->L.net[IQLHIP_NET_PI].log_std >= 0) ? l->params + l->L.net[IQLHIP_NET_PI].log_std : nullptr;
+    f.who = who_dev + who_off;
+    f.out = actions[i];
+    f.use_learner = use_learner ? use_learner[i] : nullptr;
+    f.gate_out = gate_out ? gate_out[i] : nullptr;
+    f.ld_out = (long long)ld_a; f.n = n; f.A = A;
+    f.gate_max = gate_max ? gate_max[i] : 0.f;
+    f.max_l = max_l[i]; f.max_g = max_g[i]; f.ls_min = l->hyper.log_std_min; f.ls_max = l->hyper.log_std_max;
+    f.seed = seeds[i];
+    f.call = seeds[i] != 0 ? l->act_calls++ : 0ull;      // (one call number per call, whatever the rows choose)
+    who_off += (size_t)up(n, 16);
+    max_rows = std::max(max_rows, n);
+    max_fin = std::max(max_fin, n * A);
+  }
+  if (n_req == 0) return IQLHIP_OK;
+  std::stable_sort(fwd, fwd + n_fwd, [](const Fwd& a, const Fwd& b) { return a.variant < b.variant; });
+  for (int q = 0; q < n_fwd; ++q) ps[q] = fwd[q].p;
+  const size_t used = j->who.off + who_off;
+  if (used != j->last_used || memcmp(j->host.data(), j->last.data(), used) != 0) {
+    if (j->pending) HIPCHK(hipEventSynchronize(j->up));    // the previous upload has read act.pin
+    j->pending = false;
+    memcpy(act.pin, j->host.data(), used);
+    HIPCHK(hipMemcpyAsync(act.dev, act.pin, used, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(j->up, st));
+    j->pending = true;
+    memcpy(j->last.data(), j->host.data(), used);
+    j->last_used = used;
+  }
+  const int pack_nb = std::min((max_pack + 255) / 256, 1024);
+  hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_pack), dim3(256), 0, st, act.device(j->packs));
+  for (int i = 0; i < K; ++i) {
+    if (rows[i] == 0) continue;
+    if (plan.need_l[i]) refresh_shadows(j->l[i], st);
+    if (plan.need_g[i] && j->g[i] != j->l[i]) refresh_shadows(j->g[i], st);
+    if (plan.need_v[i]) refresh_shadows(j->v[i], st);
+  }
+  for (int q0 = 0; q0 < n_fwd;) {
+    int q1 = q0, fr = 0;
+    size_t lds = 0;
+    for (; q1 < n_fwd && fwd[q1].variant == fwd[q0].variant; ++q1) { fr = std::max(fr, fwd[q1].rows); lds = std::max(lds, fwd[q1].lds); }
+    const int nbx = (fr + RT_ROWS - 1) / RT_ROWS * NSPLIT;
+    hipLaunchKernelGGL(act_fwd_group_kernel(fwd[q0].variant & 1, fwd[q0].variant & 2), dim3(nbx, q1 - q0), dim3(256), lds, st,
+                       act.device(j->ps) + q0);
+    q0 = q1;
+  }
+  if (done_flag) {
+    if (n_req != 1 || max_fin > 256) return fail(IQLHIP_EINVAL, "a completion flag needs a one-block finish launch");
+    hipLaunchKernelGGL(iql_jsrl_finish_done_kernel, dim3(1), dim3(256), 0, st, act.device(j->fins), done_flag, done_val);
+    HIPCHK(hipGetLastError());
+    return IQLHIP_OK;
+  }
+  hipLaunchKernelGGL(iql_jsrl_finish_kernel, dim3((max_fin + 255) / 256, n_req), dim3(256), 0, st, act.device(j->fins));
+  if (!(flags & IQLHIP_GROUP_ACT_WAIT)) {
+    HIPCHK(hipGetLastError());
+    return IQLHIP_OK;
+  }
+  const unsigned long long wait_val = ++j->done_seq;
+  hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, j->done_pin, wait_val);
+  HIPCHK(hipGetLastError());
+  return wait_word(j->done_pin, wait_val, st);
+}
+
+extern "C" int iqlhip_jsrl_act(iqlhip_jsrl* j, const float* const* states, int64_t ld_s, const int32_t* rows,
+                               const int8_t* const* who, const float* gate_max, const uint64_t* seeds,
+                               const float* max_action_learner, const float* max_action_guide, float* const* actions,
+                               int64_t ld_a, int32_t* const* use_learner, float* const* gate_out, int32_t flags,
+                               void* stream) {
+  JsrlPlan plan;
+  int rc = jsrl_check(j, states, ld_s, rows, who, gate_max, seeds, max_action_learner, max_action_guide, actions, ld_a,
+                      gate_out, flags, &plan);
+  if (rc) return rc;
+  DevGuard guard(j->device);
+  return jsrl_enqueue(j, plan, states, ld_s, rows, who, gate_max, seeds, max_action_learner, max_action_guide, actions,
+                      ld_a, use_learner, gate_out, flags, (hipStream_t)stream, nullptr, 0);
+}
+
+extern "C" int iqlhip_jsrl_online_step(iqlhip_jsrl* j, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                       const float* row_host, const int64_t* idx_host, int32_t n,
+                                       const iqlhip_step_scalars* sc, float out[3], const float* act_state_host,
+                                       int8_t who, float gate_max, uint64_t act_seed, float max_action_learner,
+                                       float max_action_guide, float* act_out_host, int32_t* use_learner_out,
+                                       float* gate_out, void* stream) {
+  if (!j || !act_state_host || !act_out_host) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (j->k != 1) return fail(IQLHIP_EINVAL, "the fused online step takes a handle of one member (this one has %d)", j->k);
+  iqlhip_ctx* c = j->l[0];
+  const int S = c->dims.state_dim, A = c->dims.action_dim;
+  // the selection's arguments: state, action, flag and h in host-mapped words
+  const float* states[1] = {c->on_act_pin};
+  float* actions[1] = {c->on_act_pin + IQLHIP_MAX_INPUT};
+  int32_t* flag[1] = {(int32_t*)j->on_pin};
+  float* hout[1] = {gate_out ? j->on_pin + 1 : nullptr};
+  const int32_t one[1] = {1};
+  const int8_t* whos[1] = {&who};
+  const uint64_t seeds[1] = {act_seed};
+  JsrlPlan plan;
+  int rc = jsrl_check(j, states, S, one, whos, &gate_max, seeds, &max_action_learner, &max_action_guide, actions, A, hout, 0,
+                      &plan);
+  if (rc) return rc;
+  unsigned long long done_val = 0;
+  rc = online_step_front(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, /*act_follows=*/true, stream,
+                         nullptr, 0, nullptr, 0, &done_val);
+  if (rc) return rc;
+  DevGuard guard(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  memcpy(c->on_act_pin, act_state_host, (size_t)S * sizeof(float));
+  rc = jsrl_enqueue(j, plan, states, S, one, whos, &gate_max, seeds, &max_action_learner, &max_action_guide, actions, A, flag,
+                    hout, 0, st, c->done_pin, done_val);
+  if (rc) return rc;
+  rc = sync_losses(c, done_val, st, out);
+  if (rc) return rc;
+  memcpy(act_out_host, c->on_act_pin + IQLHIP_MAX_INPUT, (size_t)A * sizeof(float));
+  if (use_learner_out) *use_learner_out = *(const int32_t*)j->on_pin;
+  if (gate_out) *gate_out = j->on_pin[1];
+  HIPCHK(hipGetLastError());
   return IQLHIP_OK;
 }

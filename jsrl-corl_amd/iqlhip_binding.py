@@ -222,6 +222,17 @@ SYMBOLS = [
     ("iqlhip_group_score_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64), C.c_int64,
                                           C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int32,
                                           C.POINTER(C.c_float), C.c_void_p]),
+    ("iqlhip_jsrl_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
+                                     C.POINTER(C.c_void_p)]),
+    ("iqlhip_jsrl_destroy", C.c_int, [C.c_void_p]),
+    ("iqlhip_jsrl_act", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                  C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
+                                  C.c_void_p]),
+    ("iqlhip_jsrl_online_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p, C.c_int8,
+                                          C.c_float, C.c_uint64, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 ]

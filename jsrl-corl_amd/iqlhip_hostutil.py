@@ -179,6 +179,77 @@ def eval_actors(envs, actors, device: str, n_episodes: int, seeds) -> List[Tuple
     return [(np.asarray(returns[k]), np.mean(successes[k])) for k in range(K)]
 
 
+# the reference's accumulator of an episode's horizons, per horizon function (jsrl_utils.HORIZON_FNS)
+_JSRL_ACCUMULATORS = {"time_step": np.mean, "agent_type": lambda v: 1, "goal_dist": np.max, "variance": np.mean}
+
+
+@torch.no_grad()
+def eval_actors_jsrl(envs, jsrl, configs, horizon_fn: str, n_episodes: int, seeds, goal_dist=None):
+    """jsrl_w_iql.eval_actor (guide and learner mixed per step) for every member of `jsrl` in lockstep, on ONE
+    jsrl.act per round: returns per member (episode returns, mean success, horizon, mean agent type).  configs[k] is
+    the member's JsrlTrainConfig; its ep_agent_type is maintained as the reference does (0 at an episode's first step,
+    then the mean of the episode's choices so far); the episode horizons are accumulated with the reference's
+    accumulator of `horizon_fn` — or, for a member without a guide and config.max_init_horizon, with max.  The
+    `variance` horizon is the gate's value, compared on the device with config.curriculum_stage."""
+    from iqlhip_jsrl import who_from_config
+    envs, configs, seeds = list(envs), list(configs), list(seeds)
+    K = len(envs)
+    if len(configs) != K or len(seeds) != K or len(jsrl.learners) != K:
+        raise ValueError(f"eval_actors_jsrl: {K} envs, {len(configs)} configs, {len(seeds)} seeds and "
+                         f"{len(jsrl.learners)} JSRL members (one each)")
+    accumulate = _JSRL_ACCUMULATORS[horizon_fn] if horizon_fn in _JSRL_ACCUMULATORS else None
+    if accumulate is None:
+        raise ValueError(f"eval_actors_jsrl: unknown horizon function {horizon_fn!r}")
+    for env, seed in zip(envs, seeds):
+        env.seed(seed)
+    jsrl.eval()
+    no_guide = [jsrl.guides[k] is None and bool(getattr(configs[k], "max_init_horizon", False)) for k in range(K)]
+    returns, successes, horizons, agent_types = ([[] for _ in range(K)] for _ in range(4))
+    state, ts, total, reached = [None] * K, [0] * K, [0.0] * K, [False] * K
+    ep_h, ep_types = [[] for _ in range(K)], [[] for _ in range(K)]
+    live = [k for k in range(K) if n_episodes > 0]
+    for k in live:
+        state[k] = envs[k].reset()
+    while live:
+        for k in live:
+            configs[k].ep_agent_type = 0 if ts[k] == 0 else np.mean(ep_types[k])
+        who, hz = who_from_config([configs[k] for k in live], horizon_fn, [ts[k] for k in live],
+                                  [state[k] for k in live], [envs[k] for k in live], goal_dist=goal_dist)
+        who_all, gate_max = [None] * K, [0.0] * K
+        for j, k in enumerate(live):
+            who_all[k] = who[j]
+            stage = configs[k].curriculum_stage
+            gate_max[k] = 0.0 if np.isnan(stage) else float(stage)
+        got = jsrl.act([state[k] if k in live else None for k in range(K)], who_all, gate_max)
+        still = []
+        for j, k in enumerate(live):
+            acts, use, h = got[k]
+            action, use_learner = acts[0], bool(use[0])
+            if getattr(configs[k], "discrete", False) and use_learner and jsrl.guides[k] is not None:
+                action = np.argmax(action)
+            ep_h[k].append(hz[j] if hz[j] is not None else h[0])
+            ep_types[k].append(1 if use_learner else 0)
+            state[k], reward, done, infos = envs[k].step(action)
+            total[k] += reward
+            ts[k] += 1
+            reached[k] = reached[k] or is_goal_reached(reward, infos)
+            if done:
+                successes[k].append(float(reached[k]))
+                returns[k].append(total[k])
+                horizons[k].append(np.max(ep_h[k]) if no_guide[k] else accumulate(ep_h[k]))
+                agent_types[k].append(np.mean(ep_types[k]))
+                if len(returns[k]) == n_episodes:
+                    continue
+                state[k], ts[k], total[k], reached[k] = envs[k].reset(), 0, 0.0, False
+                ep_h[k], ep_types[k] = [], []
+            still.append(k)
+        live = still
+    jsrl.train()
+    return [(np.asarray(returns[k]), np.mean(successes[k]),
+             (np.max(horizons[k]) if no_guide[k] else np.mean(horizons[k])) if horizons[k] else np.nan,
+             np.mean(agent_types[k])) for k in range(K)]
+
+
 def return_reward_range(dataset: Dict, max_episode_steps: int) -> Tuple[float, float]:
     """min / max episode return of a D4RL dataset (semantics of iql.py:262-274): an episode ends at a terminal
     flag or after max_episode_steps steps, whichever comes first; a trailing unfinished episode is not counted.

@@ -726,6 +726,15 @@ class ImplicitQLearning:
                                              seed, None if a_out is None else a_out.ctypes.data, self._stream()))
         return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
 
+    def online_step_jsrl(self, jsrl, replay_buffer, state, action, reward: float, next_state, done: bool,
+                         batch_size: int, act_next, who, gate_max=None):
+        """online_step(...) plus the guide-or-learner selection of the next action (jsrl_utils.learner_or_guide_action)
+        with the UPDATED learner, under one synchronisation: returns (log, action, use_learner, horizon).  `jsrl` is a
+        JsrlActors of one member whose learner is this trainer (iqlhip_jsrl.py)."""
+        from iqlhip_jsrl import online_step_jsrl
+        return online_step_jsrl(self, jsrl, replay_buffer, state, action, reward, next_state, done, batch_size,
+                                act_next, who, gate_max)
+
     # ---- scoring without a step (iqlhip_score.py; DESIGN.md 6h) -------------------------------------------------
     def _score_call(self, rows_ptr: int, ld: int, n_rows: int, start: int, n: int, idx, out, summary: bool, chunk: int):
         """The library call behind score_buffer / score / evaluate; every argument has been checked."""

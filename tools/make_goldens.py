@@ -884,6 +884,92 @@ def return_to_go_case(ref_root, outdir):
     print("g18_return_to_go ok", {f: len(v) for f, v in kept.items()})
 
 
+def jsrl_selection_case(ref, jsrl, outdir):
+    """G19: jsrl_utils.learner_or_guide_action(eval=True) run by the reference's own code on torch policies with synthetic
+    parameters — S = 17, A = 6 Gaussian and S = 29, A = 8 deterministic — for the time_step, goal_dist and variance
+    horizons (the latter with a synthetic StateDepFunction as config.vf; goal_dist with the distance supplied as data
+    through a stub of goal_dist_calc).  Recorded: the inputs (state, step, stage, stage index, n_curriculum_stages,
+    ep_agent_type, agent_type_stage, guide-is-None) and the outputs (action, use_learner, horizon).  The variance cases'
+    stage is the midpoint of the widest gap between the recorded variances, so no decision depends on rounding."""
+    import types as _types
+    FNS = ("time_step", "goal_dist", "variance")
+    out, meta = {}, {"kind": "jsrl_selection", "horizon_fns": list(FNS), "sets": []}
+
+    def policy(S, A, gaussian, max_action, seed):
+        params = synth.synth_params(S, A, seed=seed, gaussian=gaussian)
+        actor = (ref.GaussianPolicy if gaussian else ref.DeterministicPolicy)(S, A, max_action)
+        with torch.no_grad():
+            sd = dict(actor.named_parameters())
+            for ours, theirs in _pi_keys(actor).items():
+                if ours in params["pi"]:
+                    sd[theirs].copy_(torch.from_numpy(params["pi"][ours]))
+        actor.eval()
+        return actor
+
+    saved = jsrl.goal_dist_calc
+    jsrl.goal_dist_calc = lambda s, env: env.dist
+    try:
+        for tag, S, A, gaussian, ma_l, ma_g, seed in (("S17A6", 17, 6, True, 1.0, 1.0, 190), ("S29A8", 29, 8, False, 2.5, 2.0, 191)):
+            learner, guide = policy(S, A, gaussian, ma_l, seed), policy(S, A, gaussian, ma_g, seed + 10)
+            vparams = synth.synth_params(S, A, seed=seed + 20, gaussian=gaussian)["vf"]
+            vf = jsrl.StateDepFunction(S)
+            with torch.no_grad():
+                lin = [m for m in vf.modules() if isinstance(m, torch.nn.Linear)]
+                for i, (w, b) in enumerate((("w0", "b0"), ("w1", "b1"), ("w2", "b2"))):
+                    lin[i].weight.copy_(torch.from_numpy(vparams[w]))
+                    lin[i].bias.copy_(torch.from_numpy(vparams[b]))
+            vf.eval()
+            rng = np.random.default_rng(9100 + seed)
+            n_var = 12
+            var_states = rng.standard_normal((n_var, S)).astype(np.float32)
+            with torch.no_grad():
+                var = np.sort(np.array([float(vf(torch.Tensor(s))) for s in var_states]))
+            g = int(np.argmax(np.diff(var)))
+            var_stage = float(0.5 * (var[g] + var[g + 1]))
+            rows = []      # (fn, step, stage, stage_idx, n_stages, ep_agent_type, agent_type_stage, guide_none, dist)
+            for step, stage, idx, ept, ats, gnone in ((0, 150.0, 1, 0.0, 1.0, 0), (149, 150.0, 1, 0.0, 1.0, 0), (150, 150.0, 1, 0.5, 1.0, 0),
+                                                      (400, 150.0, 1, 0.9, 0.5, 0), (3, 300.0, 4, 0.2, 1.0, 0), (3, 300.0, 4, 0.7, 0.5, 0),
+                                                      (7, np.nan, 0, 5.0, 0.0, 0), (0, 300.0, 0, 0.0, 1.0, 1), (10, 0.0, 4, 0.3, 1.0, 0)):
+                rows.append((0, step, stage, idx, 5, ept, ats, gnone, 0.0))
+            for dist, stage, idx, ept, ats, gnone in ((0.4, 0.5, 1, 0.0, 1.0, 0), (0.5, 0.5, 1, 0.0, 1.0, 0), (0.6, 0.5, 1, 0.0, 1.0, 0),
+                                                      (0.1, 0.5, 1, 0.8, 0.5, 0), (9.0, 2.0, 4, 0.1, 1.0, 0), (9.0, np.nan, 0, 3.0, 0.0, 0),
+                                                      (9.0, 0.5, 1, 0.0, 1.0, 1)):
+                rows.append((1, 5, stage, idx, 5, ept, ats, gnone, dist))
+            for i in range(n_var):
+                rows.append((2, i, var_stage, 1, 5, 0.0, 1.0, 0, 0.0))
+            rows.append((2, 0, var_stage, 1, 5, 0.9, 0.5, 0, 0.0))       # a blocked agent type
+            rows.append((2, 1, var_stage, 4, 5, 0.1, 1.0, 0, 0.0))       # the last stage
+            rows.append((2, 2, np.nan, 0, 5, 4.0, 0.0, 0, 0.0))          # a NaN stage
+            rows.append((2, 3, var_stage, 1, 5, 0.0, 1.0, 1, 0.0))       # guide is None
+            n = len(rows)
+            states = rng.standard_normal((n, S)).astype(np.float32)
+            first_var = next(i for i, r in enumerate(rows) if r[0] == 2)
+            states[first_var:first_var + n_var] = var_states
+            actions = np.zeros((n, A), np.float32)
+            use = np.zeros(n, np.int32)
+            horizon = np.zeros(n, np.float64)
+            for i, (fn, step, stage, idx, ns, ept, ats, gnone, dist) in enumerate(rows):
+                jsrl.horizon_str = FNS[fn]
+                cfg = _types.SimpleNamespace(curriculum_stage=stage, curriculum_stage_idx=idx, n_curriculum_stages=ns,
+                                             ep_agent_type=ept, agent_type_stage=ats, vf=vf)
+                env = _types.SimpleNamespace(dist=dist)
+                with torch.no_grad():
+                    a, u, h = jsrl.learner_or_guide_action(states[i], step, env, learner, None if gnone else guide, cfg, "cpu", eval=True)
+                actions[i], use[i], horizon[i] = np.asarray(a, np.float32).reshape(-1), int(bool(u)), float(h)
+            out.update({f"{tag}.states": states, f"{tag}.rows": np.asarray(rows, dtype=np.float64), f"{tag}.actions": actions,
+                        f"{tag}.use_learner": use, f"{tag}.horizon": horizon})
+            meta["sets"].append({"tag": tag, "S": S, "A": A, "gaussian": gaussian, "max_action_learner": ma_l,
+                                 "max_action_guide": ma_g, "seed_learner": seed, "seed_guide": seed + 10, "seed_gate": seed + 20,
+                                 "var_stage": var_stage, "var_gap": float(var[g + 1] - var[g])})
+            print("g19", tag, "ok: rows", n, "learner rows", int(use.sum()), "variance gap", float(var[g + 1] - var[g]))
+    finally:
+        jsrl.goal_dist_calc = saved
+        jsrl.horizon_str = ""
+    meta["columns"] = ["horizon_fn", "step", "stage", "stage_idx", "n_curriculum_stages", "ep_agent_type", "agent_type_stage",
+                       "guide_is_none", "goal_dist"]
+    np.savez(os.path.join(outdir, "g19_jsrl_selection.npz"), meta=np.array(json.dumps(meta)), **out)
+
+
 def round2_cases(ref, args):
     jsrl = import_reference_jsrl(args.ref)
     resume_case(ref, "g11_resume_S17A6_gauss", 17, 6, True, 110, 13, args.out)
@@ -902,7 +988,8 @@ def main():
     ap.add_argument("--only", default=None, help="'act': only the G10 act fixtures; 'r2': only the round-2 fixtures "
                                                  "(g11 resume, g12 JSRL hand-off, g13 JSRL host logic, g14 config-5 batch); "
                                                  "'reward': only g17 (return_reward_range / modify_reward); "
-                                                 "'returns': only g18 (get_return_to_go / keep_best_trajectories)")
+                                                 "'returns': only g18 (get_return_to_go / keep_best_trajectories); "
+                                                 "'jsrl': only g19 (learner_or_guide_action)")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     torch.set_num_threads(1)
@@ -918,6 +1005,9 @@ def main():
         return
     if args.only == "r2":
         round2_cases(ref, args)
+        return
+    if args.only == "jsrl":
+        jsrl_selection_case(ref, import_reference_jsrl(args.ref), args.out)
         return
 
     act_case(ref, "g10_act_S17A6_gauss", 17, 6, True, 1.0, 90, args.out)
@@ -947,6 +1037,7 @@ def main():
     statedict_case(ref, args.out)
     round2_cases(ref, args)
     reward_range_case(ref, args.out)
+    jsrl_selection_case(ref, import_reference_jsrl(args.ref), args.out)
 
 
 if __name__ == "__main__":
