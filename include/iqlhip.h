@@ -262,6 +262,45 @@ int iqlhip_weights_build(const float* w_dev, int64_t n, void* stream, iqlhip_wei
 int iqlhip_weights_free(iqlhip_weights* table);
 int iqlhip_weights_info(const iqlhip_weights* table, int64_t* n, uint64_t* total, int32_t* levels, uint64_t* generation,
                         uint64_t* cum_host);
+/* ---- updatable tables: weights changed in place ---------------------------------------------------------------
+ * A second kind of table with the same 64-ary geometry (every level starts on a multiple of 64 entries, a node is one
+ * aligned 512-byte read, at most 4 levels) and other contents: every node holds the inclusive prefix sums of its OWN 64
+ * children's subtree totals — level-0 node k, entry l: q[64 k] + ... + q[64 k + l]; level l + 1, entry c of a node: the
+ * totals of that node's children 0 .. c; the top level is one node, its last entry is `total`.  The descent subtracts
+ * the chosen child's left neighbour from t at every level and so returns the smallest i with cum[i] > t, what a static
+ * table returns: for equal q[] both kinds give the same index for every (seed, offset, j).  Every call that takes a
+ * table takes either kind.  Changing q[i] touches one node per level.
+ *
+ * iqlhip_weights_build_updatable: a table over `capacity` rows (its n), 1 <= n <= capacity <= 2^24; rows n .. capacity
+ * weigh 0.  The scale is fixed for the table's life: e = floor(log2(max(max_weight, max w))), q = floor(w * 2^(38 - e));
+ * max_weight = 0 means the largest weight present, which gives the static table's q[].  Validation and errors as
+ * iqlhip_weights_build; synchronises `stream`.  12 bytes per row plus 1/63 of 8 (the tree, and a 4-byte stamp per row).
+ * iqlhip_weights_update: w[idx_dev[j]] = w_dev[j], j < m (int64 indices, float32 weights, device memory), queued on
+ * `stream` with no read-back, in integers throughout:
+ *   - q_new = floor(w * 2^(38 - e)) at the table's scale; a weight >= 2^(e + 1) saturates to 2^39 - 1;
+ *   - a NaN, an infinity, a negative weight (-0.0 is zero) or an index outside [0, bound), bound <= n, is skipped — its
+ *     row stays as it was — and leaves a bit in the table's sticky flag word: 1 non-finite, 2 negative, 4 index;
+ *   - of several valid entries for one row the one at the largest position j wins;
+ *   - afterwards every entry of the tree equals what a fresh build over the changed weights at the same scale holds
+ *     (integer adds commute: exact in any order).  total may reach 0: draws then stay inside [0, n) and mean nothing.
+ * An update is ordered on its stream against draws and steps queued there; a draw running concurrently on another
+ * stream is the caller's error.  Address, n and level count stay, so captured chunk graphs stay valid; the table's
+ * content VERSION (0 after the build) grows by 1 per call, and IQLHIP_TS_CONTINUE is honoured only behind a call on the
+ * same generation AND version (the rows staged for the next step were drawn by the old weights).
+ * iqlhip_weights_clear_flags: zeroes the flag word, on `stream`.
+ * iqlhip_weights_state: waits for the device, then reads the current total, the flag word, the version and — q_out
+ * not NULL — the n leaf values q[] rebuilt from the tree (either kind of table; each pointer may be NULL).
+ * iqlhip_weights_info on an updatable table: n = capacity; total is the one at build; cum_host receives level 0 as
+ * stored (node-local prefixes). */
+int iqlhip_weights_build_updatable(const float* w_dev, int64_t n, int64_t capacity, float max_weight, void* stream,
+                                   iqlhip_weights** out);
+int iqlhip_weights_update(iqlhip_weights* table, const int64_t* idx_dev, const float* w_dev, int64_t m, int64_t bound,
+                          void* stream);
+int iqlhip_weights_clear_flags(iqlhip_weights* table, void* stream);
+int iqlhip_weights_state(const iqlhip_weights* table, uint64_t* total, uint32_t* flags, uint64_t* version, uint64_t* q_out);
+#define IQLHIP_WEIGHTS_FLAG_NONFINITE 1
+#define IQLHIP_WEIGHTS_FLAG_NEGATIVE 2
+#define IQLHIP_WEIGHTS_FLAG_INDEX 4
 /* iqlhip_draw_indices with the weighted mapping: idx_dev[j], j < n_idx, of the stream (seed, offset).  One wave resolves
  * one index by a 64-ary descent through the table. */
 int iqlhip_draw_indices_weighted(int64_t* idx_dev, int64_t n_idx, const iqlhip_weights* table, uint64_t seed,

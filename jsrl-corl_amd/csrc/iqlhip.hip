@@ -152,14 +152,15 @@ struct GraphKey {
   bool operator==(const GraphKey& o) const {
     return rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
            inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip &&
-           rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n && wt.levels == o.wt.levels;
+           rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n && wt.levels == o.wt.levels && wt.local == o.wt.local;
   }
 };
 // The second source of a mixed call, handed down to whatever forms a key, a set-up launch or an idle-work record
 // (nullptr everywhere: a plain call).  The online size is not here: it travels in the header (HDR_SIZE_ON).
 // A weighted call (iqlhip_train_steps_weighted) travels the same way: rows_on == nullptr, wt its table and wt_gen the
-// table's generation (what a following call must name to start on the rows this one staged).
-struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; };
+// table's generation and wt_ver its content version (what a following call must name to start on the rows this one
+// staged: iqlhip_weights_update moves the version, the rows staged before it were drawn by the old weights).
+struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; uint64_t wt_ver = 0; };
 // Which forward a step of such a call launches: 0 iql_fwd_kernel, 1 iql_fwd_mixed_kernel, 2 iql_fwd_weighted_kernel.
 static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? 2 : 1); }
 
@@ -265,6 +266,7 @@ struct iqlhip_ctx {
   struct { bool valid = false; const float* rows = nullptr; int64_t ld = 0, size = 0; int32_t B = 0; uint64_t seed = 0;
            uint64_t next_offset = 0; float drop_p = 0.f; uint64_t drop_seed = 0, drop_step = 0;
            uint64_t wt_gen = 0;      // the table generation of a weighted call (0: a plain call)
+           uint64_t wt_ver = 0;      // ... and the table's content version at that call (iqlhip_weights_update adds 1)
          } cont;
   std::vector<CachedGraph> graphs;
   unsigned long long graph_clock = 0;
@@ -2207,8 +2209,9 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // rows its last forward staged are not what a plain call would draw, so it claims nothing and leaves no token.)
   // A weighted call continues a weighted call on the same table generation only, and a plain call a plain one.
   const int kind = fwd_kind(mx);
-  const uint64_t wt_gen = kind == 2 ? mx->wt_gen : 0;
+  const uint64_t wt_gen = kind == 2 ? mx->wt_gen : 0, wt_ver = kind == 2 ? mx->wt_ver : 0;
   const bool cont = kind != 1 && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == wt_gen &&
+                    c->cont.wt_ver == wt_ver &&
                     c->cont.rows == rows_dev && c->cont.ld == ld &&
                     c->cont.size == size && c->cont.B == B && c->cont.seed == seed && c->cont.next_offset == stream_offset &&
                     c->cont.drop_p == c->drop_p && c->cont.drop_seed == c->drop_seed && c->cont.drop_step == c->drop_step;
@@ -2271,7 +2274,7 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
   if (kind != 1 && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
-    c->cont.wt_gen = wt_gen;
+    c->cont.wt_gen = wt_gen; c->cont.wt_ver = wt_ver;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
     c->cont.next_offset = stream_offset + ((unsigned long long)K * (unsigned long long)B) / 2ull;
     c->cont.drop_p = c->drop_p; c->cont.drop_seed = c->drop_seed; c->cont.drop_step = c->drop_step;
@@ -4162,7 +4165,16 @@ struct iqlhip_weights {
   int levels = 0;
   uint64_t total = 0;
   uint64_t gen = 0;                       // unique per built table: what IQLHIP_TS_CONTINUE compares
+  // updatable tables (iqlhip_weights_build_updatable): node-local prefix sums, a scale fixed for the table's life
+  bool local = false;
+  int sh0 = 0;                            // 38 - e
+  unsigned sat_bits = 0;                  // the bit pattern of 2^(e + 1)
+  unsigned* stamp = nullptr;              // [n]: which entry of the running update sets a row (zero between updates)
+  unsigned* flags = nullptr;              // the sticky flag word
+  unsigned long long* delta = nullptr;    // [WT_UPDATE_SLICE]: q_new - q_old of a slice's entries
+  uint64_t version = 0;                   // content version: every iqlhip_weights_update adds 1
 };
+#define WT_UPDATE_SLICE 65536             // entries of an update handled per set of launches (the delta scratch: 512 KB)
 static std::atomic<uint64_t> g_weights_gen{0};
 
 // Sizes and offsets (in entries) of a table's levels over n rows; returns the level count.
@@ -4178,13 +4190,39 @@ static int weights_levels(int64_t n, unsigned size[WT_MAX_LEVELS], unsigned off[
   if (entries) *entries = o;
   return levels;
 }
-static WTab weights_tab(const iqlhip_weights* t) { return WTab{t->tab, (unsigned)t->n, t->levels}; }
+static WTab weights_tab(const iqlhip_weights* t) {
+  return WTab{t->tab, (unsigned)t->n, (unsigned short)t->levels, (unsigned short)(t->local ? 1 : 0)};
+}
 // A group member's table (iqlhip_group_train_steps_weighted): on the group's device, and weighing exactly the size[k]
 // rows the member draws over — every index the descent can resolve is then < size[k].
 static int weights_check_member(const iqlhip_weights* t, int member, int64_t size, int device) {
   if (t->device != device) return fail(IQLHIP_EINVAL, "member %d: the table lives on device %d, the group on %d", member, t->device, device);
   if (size != t->n) return fail(IQLHIP_EINVAL, "member %d: size %lld, but the table weighs %lld rows", member, (long long)size, (long long)t->n);
   return IQLHIP_OK;
+}
+
+// The validation both builds start with — nothing but its two words exists until the weights have passed; synchronises
+// st.  max_bits: the largest bit pattern among the weights (all finite, none negative, one at least above zero).
+static int weights_validate(iqlhip_weights* t, const float* w_dev, int64_t n, hipStream_t st, unsigned* max_bits) {
+  HIPCHK(t->own.dev(&t->verdict, 2 * sizeof(unsigned), 0));
+  hipLaunchKernelGGL(iql_wt_validate_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, w_dev,
+                     (long long)n, t->verdict);
+  HIPCHK(hipGetLastError());
+  unsigned verdict[2] = {0u, 0u};
+  HIPCHK(hipMemcpyAsync(verdict, t->verdict, sizeof verdict, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (verdict[1] & 1u) return fail(IQLHIP_EINVAL, "weights hold a NaN or an infinity");
+  if (verdict[1] & 2u) return fail(IQLHIP_EINVAL, "weights hold a negative value");
+  if (!verdict[0]) return fail(IQLHIP_EINVAL, "all weights are zero");
+  *max_bits = verdict[0];
+  return IQLHIP_OK;
+}
+// e = floor(log2(x)) of the positive finite float with these bits; every q is a weight's significand shifted by (its
+// exponent + 38 - e).
+static int weights_exponent(unsigned bits) {
+  const unsigned ex = bits >> 23, frac = bits & 0x7FFFFFu;
+  const unsigned m = ex ? (frac | 0x800000u) : frac;
+  return (ex ? (int)ex - 150 : -149) + (31 - __builtin_clz(m));
 }
 
 extern "C" int iqlhip_weights_build(const float* w_dev, int64_t n, void* stream, iqlhip_weights** out) {
@@ -4200,22 +4238,10 @@ extern "C" int iqlhip_weights_build(const float* w_dev, int64_t n, void* stream,
   t->levels = weights_levels(n, size, off, &entries);
   if (t->levels < 1) return fail(IQLHIP_EINVAL, "n = %lld weights need more than %d levels", (long long)n, WT_MAX_LEVELS);
   const int n_tiles = (int)((n + WT_SCAN_TILE - 1) / WT_SCAN_TILE);        // <= WT_SCAN_TILE: one block scans their sums
-  // validation first: nothing but its two words exists until the weights have passed
-  HIPCHK(t->own.dev(&t->verdict, 2 * sizeof(unsigned), 0));
-  hipLaunchKernelGGL(iql_wt_validate_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, w_dev,
-                     (long long)n, t->verdict);
-  HIPCHK(hipGetLastError());
-  unsigned verdict[2] = {0u, 0u};
-  HIPCHK(hipMemcpyAsync(verdict, t->verdict, sizeof verdict, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (verdict[1] & 1u) return fail(IQLHIP_EINVAL, "weights hold a NaN or an infinity");
-  if (verdict[1] & 2u) return fail(IQLHIP_EINVAL, "weights hold a negative value");
-  if (!verdict[0]) return fail(IQLHIP_EINVAL, "all weights are zero");
-  // e = floor(log2(max w)) from the bit pattern; every q is the weight's significand shifted by (its exponent + 38 - e)
-  const unsigned ex = verdict[0] >> 23, frac = verdict[0] & 0x7FFFFFu;
-  const unsigned m = ex ? (frac | 0x800000u) : frac;
-  const int e = (ex ? (int)ex - 150 : -149) + (31 - __builtin_clz(m));
-  const int sh0 = 38 - e;
+  unsigned max_bits = 0;
+  int rc = weights_validate(t.get(), w_dev, n, st, &max_bits);
+  if (rc) return rc;
+  const int sh0 = 38 - weights_exponent(max_bits);      // e = floor(log2(max w))
   HIPCHK(t->own.dev(&t->tab, entries * sizeof(unsigned long long), 0));
   HIPCHK(t->own.dev(&t->tile_sums, (size_t)n_tiles * sizeof(unsigned long long)));
   hipLaunchKernelGGL(iql_wt_tile_sums_kernel, dim3(n_tiles), dim3(256), 0, st, w_dev, (long long)n, sh0, t->tile_sums);
@@ -4253,6 +4279,109 @@ extern "C" int iqlhip_weights_info(const iqlhip_weights* t, int64_t* n, uint64_t
   if (cum_host) {
     DevGuard guard(t->device);
     HIPCHK(hipMemcpy(cum_host, t->tab, (size_t)t->n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  }
+  return IQLHIP_OK;
+}
+
+// ---- updatable tables: node-local prefix sums, changed in place (DESIGN.md 6i "updatable tables")
+extern "C" int iqlhip_weights_build_updatable(const float* w_dev, int64_t n, int64_t capacity, float max_weight, void* stream,
+                                              iqlhip_weights** out) {
+  if (!w_dev || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n < 1 || capacity < n || capacity > IQLHIP_WEIGHTS_MAX_ROWS)
+    return fail(IQLHIP_EINVAL, "n = %lld weights, capacity = %lld: need 1 <= n <= capacity <= 2^24", (long long)n, (long long)capacity);
+  if (((uintptr_t)w_dev) & 3) return fail(IQLHIP_EINVAL, "weights must be 4-byte aligned");
+  if (!(max_weight >= 0.f) || std::isinf(max_weight)) return fail(IQLHIP_EINVAL, "max_weight must be finite and not negative");
+  hipStream_t st = (hipStream_t)stream;
+  std::unique_ptr<iqlhip_weights> t(new iqlhip_weights);
+  HIPCHK(hipGetDevice(&t->device));
+  unsigned size[WT_MAX_LEVELS], off[WT_MAX_LEVELS];
+  size_t entries = 0;
+  t->n = capacity;
+  t->local = true;
+  t->levels = weights_levels(capacity, size, off, &entries);
+  if (t->levels < 1) return fail(IQLHIP_EINVAL, "capacity = %lld needs more than %d levels", (long long)capacity, WT_MAX_LEVELS);
+  unsigned max_bits = 0, given_bits = 0;
+  int rc = weights_validate(t.get(), w_dev, n, st, &max_bits);
+  if (rc) return rc;
+  memcpy(&given_bits, &max_weight, sizeof given_bits);
+  // the scale, fixed for the table's life: e = floor(log2(max(max_weight, max w))) (bit patterns of floats >= 0 order as they do)
+  const int e = weights_exponent(std::max(max_bits, given_bits & 0x7FFFFFFFu));
+  t->sh0 = 38 - e;
+  t->sat_bits = (e + 1 >= -126) ? ((unsigned)(e + 1 + 127) << 23) : (1u << (e + 1 + 149));      // 2^(e + 1); e = 127: infinity's
+  HIPCHK(t->own.dev(&t->tab, entries * sizeof(unsigned long long), 0));
+  HIPCHK(t->own.dev(&t->stamp, (size_t)capacity * sizeof(unsigned), 0));
+  HIPCHK(t->own.dev(&t->flags, sizeof(unsigned), 0));
+  HIPCHK(t->own.dev(&t->delta, (size_t)WT_UPDATE_SLICE * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(iql_wt_local_leaves_kernel, dim3((((unsigned)capacity + 63u) / 64u + 3u) / 4u), dim3(256), 0, st, w_dev,
+                     (long long)n, (unsigned)capacity, t->sh0, t->tab);
+  for (int l = 1; l < t->levels; ++l)
+    hipLaunchKernelGGL(iql_wt_local_level_kernel, dim3(((size[l] + 63u) / 64u + 3u) / 4u), dim3(256), 0, st,
+                       (const unsigned long long*)(t->tab + off[l - 1]), size[l - 1], t->tab + off[l], size[l]);
+  HIPCHK(hipGetLastError());
+  unsigned long long total = 0;
+  HIPCHK(hipMemcpyAsync(&total, t->tab + off[t->levels - 1] + size[t->levels - 1] - 1, sizeof total, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  t->total = total;                       // (at build: iqlhip_weights_state reads the current one)
+  t->gen = ++g_weights_gen;
+  *out = t.release();
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_weights_update(iqlhip_weights* t, const int64_t* idx_dev, const float* w_dev, int64_t m, int64_t bound,
+                                     void* stream) {
+  if (!t || (m > 0 && (!idx_dev || !w_dev))) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!t->local) return fail(IQLHIP_EINVAL, "the table is not updatable (iqlhip_weights_build_updatable)");
+  if (m < 0) return fail(IQLHIP_EINVAL, "m = %lld entries", (long long)m);
+  if (bound < 0 || bound > t->n) return fail(IQLHIP_EINVAL, "bound = %lld outside [0, %lld]", (long long)bound, (long long)t->n);
+  if ((((uintptr_t)idx_dev) & 7) || (((uintptr_t)w_dev) & 3)) return fail(IQLHIP_EINVAL, "indices must be 8-byte, weights 4-byte aligned");
+  DevGuard guard(t->device);
+  hipStream_t st = (hipStream_t)stream;
+  const WUpd u{t->tab, t->stamp, t->flags, (unsigned)t->n, t->levels, t->sh0, t->sat_bits};
+  // slice by slice, in order: a later slice's entry overrides an earlier one's as a later position does inside a slice
+  for (int64_t j0 = 0; j0 < m; j0 += WT_UPDATE_SLICE) {
+    const unsigned k = (unsigned)std::min<int64_t>(WT_UPDATE_SLICE, m - j0);
+    const long long* idx = (const long long*)idx_dev + j0;
+    const float* w = w_dev + j0;
+    hipLaunchKernelGGL(iql_wt_update_stamp_kernel, dim3((k + 255u) / 256u), dim3(256), 0, st, idx, w, k, (long long)bound, u);
+    hipLaunchKernelGGL(iql_wt_update_delta_kernel, dim3((k + 255u) / 256u), dim3(256), 0, st, idx, w, k, (long long)bound, u, t->delta);
+    hipLaunchKernelGGL(iql_wt_update_apply_kernel, dim3((k + 3u) / 4u), dim3(256), 0, st, idx, w, k, (long long)bound, u,
+                       (const unsigned long long*)t->delta);
+  }
+  HIPCHK(hipGetLastError());
+  ++t->version;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_weights_clear_flags(iqlhip_weights* t, void* stream) {
+  if (!t) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!t->local) return IQLHIP_OK;        // (a static table has no flag word: its build refuses bad weights)
+  DevGuard guard(t->device);
+  HIPCHK(hipMemsetAsync(t->flags, 0, sizeof(unsigned), (hipStream_t)stream));
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_weights_state(const iqlhip_weights* t, uint64_t* total, uint32_t* flags, uint64_t* version, uint64_t* q_out) {
+  if (!t) return fail(IQLHIP_EINVAL, "NULL argument");
+  DevGuard guard(t->device);
+  HIPCHK(hipDeviceSynchronize());         // an update may be queued on any stream
+  unsigned size[WT_MAX_LEVELS], off[WT_MAX_LEVELS];
+  (void)weights_levels(t->n, size, off, nullptr);
+  if (total)
+    HIPCHK(hipMemcpy(total, t->local ? t->tab + off[t->levels - 1] + size[t->levels - 1] - 1 : t->tab + (t->n - 1), sizeof(uint64_t),
+                     hipMemcpyDeviceToHost));
+  if (flags) {
+    *flags = 0u;
+    if (t->local) HIPCHK(hipMemcpy(flags, t->flags, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if (version) *version = t->version;
+  if (q_out) {
+    unsigned long long* q = nullptr;
+    HIPCHK(hipMalloc((void**)&q, (size_t)t->n * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(iql_wt_leaves_kernel, dim3(((unsigned)t->n + 255u) / 256u), dim3(256), 0, (hipStream_t) nullptr,
+                       (const unsigned long long*)t->tab, (unsigned)t->n, t->local ? 1 : 0, q);
+    const hipError_t e = hipMemcpy(q_out, q, (size_t)t->n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    (void)hipFree(q);
+    HIPCHK(e);
   }
   return IQLHIP_OK;
 }
@@ -4300,7 +4429,7 @@ extern "C" int iqlhip_train_steps_weighted_prepare(iqlhip_ctx* c, const float* r
                                                    void* stream, const iqlhip_weights* table) {
   int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
   if (rc) return rc;
-  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen};
+  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version};
   return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
 }
 extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
@@ -4309,7 +4438,7 @@ extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev,
   if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
   if (rc) return rc;
-  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen};
+  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version};
   return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
 }
 

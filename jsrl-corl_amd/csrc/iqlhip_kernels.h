@@ -364,8 +364,10 @@ __device__ __forceinline__ void gather_rows_drawn2(const float* rows_off, const 
 struct WTab {
   const unsigned long long* tab;          // level 0 = cum[0..n), the search levels behind it
   unsigned n;
-  int levels;
+  unsigned short levels;
+  unsigned short local;                   // 1: an updatable table — every node holds the prefix sums of its own 64 children
 };
+static_assert(sizeof(WTab) == 16, "WTab keeps its size: it lies inside IdleWork and among kernel arguments");
 
 // What the idle eighth of a captured step's forward grid does (StepParams::g_work; one record per step of a chunk,
 // written once when the chunk is captured):

@@ -10,6 +10,9 @@
 // The table is ONE device allocation: level 0 = cum[0..n), level l + 1 = every 64th entry of level l
 // (L[k] = below[min(64 k + 63, size - 1)]), up to a level of <= 64 entries; each level starts on a multiple of 64
 // entries, so a node — 64 consecutive separators — is one aligned 512-byte read.
+//
+// An UPDATABLE table (WTab::local) has the same geometry and node-local contents — see "updatable tables" below: the
+// descent then subtracts the chosen child's left neighbour from t at every level and returns the same index.
 #pragma once
 
 #define WT_MAX_LEVELS 4                 // n <= 2^24: 2^24, 2^18, 2^12, 64
@@ -135,6 +138,136 @@ __global__ __launch_bounds__(256) void iql_wt_level_kernel(const unsigned long l
   if (k < size_up) up[k] = below[min(64u * k + 63u, size_below - 1u)];
 }
 
+// ---- updatable tables (iqlhip_weights_build_updatable / iqlhip_weights_update; DESIGN.md 6i "updatable tables") -------
+// The same geometry, other contents: a node holds the inclusive prefix sums of its OWN 64 children's subtree totals
+// (level 0: of its 64 rows' q), so a changed q[i] touches one node per level — the entries at and behind the child's
+// position — and nothing else.  A node's total is its last entry; the top node's entries are global prefixes.
+
+// Inclusive scan over the 64 lanes of a wave.
+__device__ __forceinline__ unsigned long long wt_wave_scan(unsigned long long v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// Level 0, one wave per node: tab[64 k + l] = q[64 k] + ... + q[64 k + l]; rows n_w .. cap weigh nothing.
+__global__ __launch_bounds__(256) void iql_wt_local_leaves_kernel(const float* __restrict__ w, long long n_w, unsigned cap,
+                                                                  int sh0, unsigned long long* __restrict__ tab) {
+  const unsigned i = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u + (threadIdx.x & 63u);
+  const unsigned long long v = wt_wave_scan(((long long)i < n_w) ? wt_quantise(w[i], sh0) : 0ull);
+  if (i < cap) tab[i] = v;
+}
+
+// A level from the one below, one wave per node: up[64 k + c] = the totals of the node's children 0 .. c, the total of
+// child node j of `below` being its last entry, below[min(64 j + 63, size_below - 1)].
+__global__ __launch_bounds__(256) void iql_wt_local_level_kernel(const unsigned long long* __restrict__ below,
+                                                                 unsigned size_below, unsigned long long* __restrict__ up,
+                                                                 unsigned size_up) {
+  const unsigned k = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u + (threadIdx.x & 63u);
+  const unsigned long long v = wt_wave_scan((k < size_up) ? below[min(64u * k + 63u, size_below - 1u)] : 0ull);
+  if (k < size_up) up[k] = v;
+}
+
+#define WT_Q_SATURATED ((1ull << 39) - 1ull)
+#define WT_FLAG_NONFINITE 1u
+#define WT_FLAG_NEGATIVE 2u
+#define WT_FLAG_INDEX 4u
+
+// What an updatable table's kernels need beyond WTab: the fixed scale and the bookkeeping.
+struct WUpd {
+  unsigned long long* tab;
+  unsigned* stamp;                        // [n] 0, or (position of the entry that sets this row in the running update) + 1
+  unsigned* flags;                        // the sticky flag word
+  unsigned n;
+  int levels;
+  int sh0;                                // 38 - e, fixed when the table was built
+  unsigned sat_bits;                      // the bit pattern of 2^(e + 1): a weight at or above it saturates
+};
+
+// Why entry (i, w) of an update is skipped (0: it is applied).
+__device__ __forceinline__ unsigned wt_update_bad(long long i, float w, long long bound) {
+  const unsigned b = __float_as_uint(w);
+  unsigned bad = 0u;
+  if ((b & 0x7F800000u) == 0x7F800000u) bad |= WT_FLAG_NONFINITE;
+  else if ((b >> 31) && (b << 1)) bad |= WT_FLAG_NEGATIVE;
+  if (i < 0 || i >= bound) bad |= WT_FLAG_INDEX;
+  return bad;
+}
+
+// Update, launch 1: the last valid entry of every row wins (stamp[i] = max over its entries of j + 1); bad entries
+// only leave their flag bits.
+__global__ __launch_bounds__(256) void iql_wt_update_stamp_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
+                                                                  unsigned m, long long bound, WUpd t) {
+  const unsigned j = blockIdx.x * 256u + threadIdx.x;
+  unsigned bad = 0u;
+  if (j < m) {
+    const long long i = idx[j];
+    bad = wt_update_bad(i, w[j], bound);
+    if (!bad) atomicMax(t.stamp + i, j + 1u);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad |= (unsigned)__shfl_xor((int)bad, o);
+  if ((threadIdx.x & 63) == 0 && bad) atomicOr(t.flags, bad);
+}
+
+// Launch 2: delta[j] = q_new - q_old (two's complement) of every winner, q_old read back from its level-0 node —
+// nothing writes the tree in this launch.  Entries that lost or are skipped get 0.
+__global__ __launch_bounds__(256) void iql_wt_update_delta_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
+                                                                  unsigned m, long long bound, WUpd t,
+                                                                  unsigned long long* __restrict__ delta) {
+  const unsigned j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= m) return;
+  const long long i = idx[j];
+  const float wj = w[j];
+  unsigned long long d = 0ull;
+  if (!wt_update_bad(i, wj, bound) && t.stamp[i] == j + 1u) {
+    const unsigned long long upto = t.tab[i], before = (i & 63) ? t.tab[i - 1] : 0ull;
+    const unsigned long long q_new =
+        ((__float_as_uint(wj) & 0x7FFFFFFFu) >= t.sat_bits) ? WT_Q_SATURATED : wt_quantise(wj, t.sh0);
+    d = q_new - (upto - before);
+  }
+  delta[j] = d;
+}
+
+// Launch 3, one wave per entry: a winner adds its delta to the entries at and behind its position in its node of every
+// level (waves of different rows meet in the upper nodes: 64-bit atomic adds, which commute), and resets its stamp.
+__global__ __launch_bounds__(256) void iql_wt_update_apply_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
+                                                                  unsigned m, long long bound, WUpd t,
+                                                                  const unsigned long long* __restrict__ delta) {
+  const unsigned j = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  const unsigned lane = threadIdx.x & 63u;
+  if (j >= m) return;
+  const long long i = idx[j];
+  if (wt_update_bad(i, w[j], bound) || t.stamp[i] != j + 1u) return;
+  const unsigned long long d = delta[j];
+  if (d) {
+    unsigned size = t.n, off = 0u, at = (unsigned)i;
+#pragma unroll
+    for (int l = 0; l < WT_MAX_LEVELS; ++l) {
+      if (l < t.levels) {
+        const unsigned first = at & ~63u, width = min(64u, size - first);
+        if (lane >= (at & 63u) && lane < width) atomicAdd(t.tab + off + first + lane, d);
+      }
+      off += (size + 63u) & ~63u;
+      size = (size + 63u) >> 6;
+      at >>= 6;
+    }
+  }
+  if (lane == 0) t.stamp[i] = 0u;
+}
+
+// Leaf values back from the tree (iqlhip_weights_state): q[i] = tab[i] - tab[i - 1], or tab[i] where a node begins
+// (local) or at i == 0 (a static table's global cum).
+__global__ __launch_bounds__(256) void iql_wt_leaves_kernel(const unsigned long long* __restrict__ tab, unsigned n, int local,
+                                                            unsigned long long* __restrict__ q) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) q[i] = tab[i] - (((local ? (i & 63u) : i) != 0u) ? tab[i - 1] : 0ull);
+}
+
 // ---- the draw --------------------------------------------------------------------------------------------------------
 // The 64 random bits of index j of a call: draw_index's (iqlhip_kernels.h) — same counter, same tag, same word pair.
 __device__ __forceinline__ unsigned long long wt_draw_bits(unsigned long long seed, unsigned long long ctr0, unsigned long long j) {
@@ -169,7 +302,7 @@ __device__ __forceinline__ void draw_index_weighted(const WTab& wt, unsigned lon
   for (int u = 0; u < U; ++u) { r[u] = wt_draw_bits(seed, ctr0, j[u]); node[u] = 0u; t[u] = 0ull; }
 #pragma unroll
   for (int l = WT_MAX_LEVELS - 1; l >= 0; --l) {
-    if (l < wt.levels) {
+    if (l == 0 || size[l > 0 ? l - 1 : 0] > 64u) {      // l < wt.levels, told from the sizes the descent holds anyway
       unsigned long long sep[U];
       unsigned width[U];
 #pragma unroll
@@ -180,12 +313,16 @@ __device__ __forceinline__ void draw_index_weighted(const WTab& wt, unsigned lon
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        if (l == wt.levels - 1) {
+        if (size[l] <= 64u) {           // the top level: l == wt.levels - 1
           const unsigned long long total = __shfl(sep[u], (int)width[u] - 1);
           t[u] = __umul64hi(r[u], total);
         }
-        const unsigned child = (unsigned)__popcll(__ballot(lane < width[u] && sep[u] <= t[u]));
-        node[u] = 64u * node[u] + min(child, width[u] - 1u);
+        const unsigned child = min((unsigned)__popcll(__ballot(lane < width[u] && sep[u] <= t[u])), width[u] - 1u);
+        node[u] = 64u * node[u] + child;
+        if (wt.local) {                 // (uniform over the wave) node-local prefixes: t becomes relative to the child
+          const unsigned long long before = __shfl(sep[u], (int)max(child, 1u) - 1);
+          t[u] -= child ? before : 0ull;
+        }
       }
     }
   }

@@ -161,6 +161,12 @@ SYMBOLS = [
     ("iqlhip_weights_free", C.c_int, [C.c_void_p]),
     ("iqlhip_weights_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_uint64), C.c_void_p]),
+    ("iqlhip_weights_build_updatable", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p,
+                                                 C.POINTER(C.c_void_p)]),
+    ("iqlhip_weights_update", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    ("iqlhip_weights_clear_flags", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("iqlhip_weights_state", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                       C.c_void_p]),
     ("iqlhip_draw_indices_weighted", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("iqlhip_train_steps_weighted", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                               C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),

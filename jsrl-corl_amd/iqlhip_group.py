@@ -384,6 +384,14 @@ class ImplicitQLearningGroup:
             size, ib = t._train_steps_args(buf, B)
             sizes.append(size)
             inv.append(ib)
+        # (an updatable table spans a capacity, and that is the size its member's draw is given: rows beyond the index
+        #  bound weigh 0)
+        for i, e in enumerate(entries):
+            if isinstance(e, wtd.SampleWeights):
+                if e.updatable:
+                    sizes[i] = e.n
+            elif e is not None and e._weights_updatable:
+                sizes[i] = e.sample_weights_n
         if len({b._ld for b in bufs}) != 1:
             raise ValueError("iqlhip: the members' buffers have different row strides")
         chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))

@@ -353,6 +353,8 @@ class ReplayBuffer:
     _weights = None              # the library's table (iqlhip_weights*), its n and its generation; None: no weights
     _weights_n = None
     _weights_gen = 0
+    _weights_updatable = False   # an updatable table spans _buffer_size rows and is changed in place
+    _weights_version = 0         # its content version: update_sample_weights adds 1
 
     @property
     def sample_weights_n(self):
@@ -361,6 +363,7 @@ class ReplayBuffer:
 
     def _free_weights(self) -> None:
         table, self._weights, self._weights_n, self._weights_gen = self._weights, None, None, 0
+        self._weights_updatable, self._weights_version = False, 0
         if table is not None:
             hb.lib().iqlhip_weights_free(table)
 
@@ -370,12 +373,16 @@ class ReplayBuffer:
         except Exception:
             pass
 
-    def set_sample_weights(self, weights) -> None:
+    def set_sample_weights(self, weights, updatable: bool = False, max_weight=None) -> None:
         """One float32 weight per row position [0, _index_bound()): a torch tensor on the buffer's device or on the host,
         or an ndarray; None clears them.  The library validates the values and builds its cumulative table on the device
         (8 bytes per row plus 1/63).  ValueError for a CPU buffer, a wrong length, dtype or shape, a NaN, an infinity, a
         negative value, all zeros, or more than 2^24 rows — the previous weights then stay in force.  A weight below
-        max(weights) * 2^-39 quantises to 0: that row is never drawn.  Only the *_weighted calls look at weights."""
+        max(weights) * 2^-39 quantises to 0: that row is never drawn.  Only the *_weighted calls look at weights.
+        updatable=True builds a table that update_sample_weights changes in place: it spans the buffer's whole capacity
+        (rows beyond the index bound weigh 0), so the weighted calls keep working while add_transition moves the index
+        bound; its scale is fixed by max_weight (None: the largest weight given) — a later weight of
+        2^(floor(log2(max_weight)) + 1) or more saturates.  12 bytes per row instead of 8."""
         import iqlhip_weighted as wtd
         if weights is None:
             self._free_weights()
@@ -393,13 +400,46 @@ class ReplayBuffer:
             raise ValueError(f"iqlhip: sample weights live on {weights.device}, the buffer on {dev}")
         else:
             w_dev = weights.contiguous()
-        table = C.c_void_p()
+        if not updatable and max_weight is not None:
+            raise ValueError("iqlhip: max_weight belongs to an updatable table (updatable=True)")
         with torch.cuda.device(dev):
-            hb.check(hb.lib().iqlhip_weights_build(w_dev.data_ptr(), n, self._stream(), C.byref(table)))
-        gen = C.c_uint64()
-        hb.check(hb.lib().iqlhip_weights_info(table, None, None, None, C.byref(gen), None))
+            table, gen = wtd.build_table(w_dev, n, self._stream(), updatable, self._buffer_size if updatable else None,
+                                         max_weight)
         self._free_weights()
-        self._weights, self._weights_n, self._weights_gen = table, n, int(gen.value)
+        self._weights, self._weights_n, self._weights_gen = table, (self._buffer_size if updatable else n), gen
+        self._weights_updatable = bool(updatable)
+
+    def update_sample_weights(self, indices, weights) -> None:
+        """w[indices[j]] = weights[j] in the buffer's updatable table (set_sample_weights(..., updatable=True)): device
+        tensors (int64, float32) of one length, queued on the buffer's stream with no synchronisation.  Duplicate indices:
+        the last position wins.  A NaN, an infinity, a negative weight or an index outside [0, _index_bound()) is
+        skipped and leaves a bit in sample_weights_flags().  A ring write (add_transition) does NOT touch the table:
+        the overwritten — or newly filled — row keeps its old weight (0 for a row never weighed) until the caller
+        follows the write with update_sample_weights([row], [w])."""
+        import iqlhip_weighted as wtd
+        if self._weights is None or not self._weights_updatable:
+            raise ValueError("iqlhip: the replay buffer has no updatable sample weights "
+                             "(set_sample_weights(..., updatable=True))")
+        dev = self._rows.device
+        m = wtd.check_update_args(indices, weights, dev)
+        idx, w = indices.contiguous(), weights.contiguous()
+        with torch.cuda.device(dev):
+            hb.check(hb.lib().iqlhip_weights_update(self._weights, idx.data_ptr(), w.data_ptr(), m, self._index_bound(),
+                                                    self._stream()))
+        self._weights_version += 1
+
+    def sample_weights_flags(self) -> int:
+        """The table's sticky flag word (waits for the device): bit 0 a non-finite weight was skipped by an update, bit 1
+        a negative one, bit 2 an index out of range."""
+        import iqlhip_weighted as wtd
+        wtd.check_call(self)
+        return wtd.table_state(self._weights)[1]
+
+    def clear_sample_weights_flags(self) -> None:
+        import iqlhip_weighted as wtd
+        wtd.check_call(self)
+        with torch.cuda.device(self._rows.device):
+            hb.check(hb.lib().iqlhip_weights_clear_flags(self._weights, self._stream()))
 
     def draw_weighted_indices(self, n: int, seed: int, offset: int) -> torch.Tensor:
         """Indices 0 .. n - 1 of the weighted index stream (seed, offset) — the stream train_steps_weighted consumes — as

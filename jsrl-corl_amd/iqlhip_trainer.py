@@ -910,15 +910,16 @@ class ImplicitQLearning:
     # ---- rows drawn by weight on the device (iqlhip_weighted.py) -----------------------------------
     def _weighted_args(self, replay_buffer, batch_size: int, weights=None):
         """The checks both weighted calls make before anything is launched or any counter moves; returns the rows the
-        draw covers, the library's table and its generation (weights: a SampleWeights used instead of the buffer's)."""
+        draw covers, the library's table and its (generation, content version) (weights: a SampleWeights used instead of the
+        buffer's).  An updatable table spans a capacity: that is the size the library is given."""
         import iqlhip_weighted as wtd
         self._require_gpu()
         if weights is None:
             n = wtd.check_call(replay_buffer)
-            table, gen = replay_buffer._weights, replay_buffer._weights_gen
+            table, gen = replay_buffer._weights, (replay_buffer._weights_gen, replay_buffer._weights_version)
         else:
             n = wtd.check_table(replay_buffer, weights)
-            table, gen = weights._table, weights.generation
+            table, gen = weights._table, (weights.generation, weights.version)
         if replay_buffer._rows.device != self._dev:
             raise ValueError(f"iqlhip: the replay buffer must live on the trainer's GPU ({self._dev})")
         wtd.check_trainer(self._dp_world, self._dp_exchange, getattr(self, "_precision", "f32"), batch_size,
@@ -947,7 +948,10 @@ class ImplicitQLearning:
         set; NotImplementedError under data parallelism, for bf16 batches of more than 512 rows and with injected
         dropout masks pending.  No priority exponent and no importance-sampling correction of the loss.
         weights: None, or an iqlhip_weighted.SampleWeights to draw by instead of the buffer's own table (its n must equal
-        the buffer's index bound: ValueError otherwise); a continuation then keys on that object's generation."""
+        the buffer's index bound: ValueError otherwise); a continuation then keys on that object's generation.
+        An updatable table (set_sample_weights(..., updatable=True), SampleWeights(..., updatable=True)) is taken like a
+        static one and is not refused when the index bound has moved; an update of it between two calls ends the
+        continuation (the rows staged for the next step were drawn by the old weights), the chunk graphs stay."""
         if return_stats and not self._step_stats:
             raise ValueError("iqlhip: train_steps_weighted(return_stats=True) needs set_step_stats(True) first")
         size, table, gen = self._weighted_args(replay_buffer, batch_size, weights)

@@ -14,6 +14,11 @@ other calls, mixed batches) ignores them.
 share one buffer can each draw by a table of their own (`ImplicitQLearningGroup.train_steps_weighted(weights=[...])`),
 and `ImplicitQLearning.train_steps_weighted(weights=...)` uses it instead of the buffer's.
 
+Updatable tables (`set_sample_weights(w, updatable=True)`, `SampleWeights(w, updatable=True)`; DESIGN.md 6i "updatable
+tables") can be changed in place, a few hundred rows in a few microseconds: `update_sample_weights(indices, weights)` /
+`SampleWeights.update`.  Such a table spans the buffer's whole capacity, rows beyond the index bound weigh 0, and its
+scale is fixed when it is built (`max_weight`), so the weighted calls keep working while the ring fills.
+
 The argument checks live here, free of any GPU work, so they can be tested without one.
 """
 from __future__ import annotations
@@ -60,14 +65,75 @@ def check_host_values(w: np.ndarray) -> None:
         raise ValueError("iqlhip: all sample weights are zero")
 
 
+def check_updatable_args(n: int, capacity, max_weight):
+    """capacity and max_weight of an updatable table over n weights: n <= capacity <= 2^24 (None: n), max_weight finite
+    and >= 0 (None or 0: the largest weight present).  Returns (capacity, max_weight); ValueError otherwise."""
+    capacity = n if capacity is None else int(capacity)
+    if capacity < n:
+        raise ValueError(f"iqlhip: capacity {capacity} is smaller than the {n} sample weights")
+    if capacity > MAX_ROWS:
+        raise ValueError(f"iqlhip: weighted sampling covers at most 2^24 rows (capacity {capacity})")
+    max_weight = 0.0 if max_weight is None else float(max_weight)
+    if not (0.0 <= max_weight < float("inf")):
+        raise ValueError(f"iqlhip: max_weight must be finite and not negative (got {max_weight})")
+    return capacity, max_weight
+
+
+def check_update_args(indices, weights, device=None) -> int:
+    """The shape, dtype and device checks of an update: two 1-D device tensors of one length, int64 indices and float32
+    weights (no look at the values: bad ones are skipped and flagged on the device).  Returns that length."""
+    import torch
+    if not isinstance(indices, torch.Tensor) or not isinstance(weights, torch.Tensor):
+        raise ValueError("iqlhip: an update takes torch tensors (indices int64, weights float32)")
+    if indices.dtype != torch.int64:
+        raise ValueError(f"iqlhip: update indices must be int64 (got {indices.dtype})")
+    if weights.dtype != torch.float32:
+        raise ValueError(f"iqlhip: update weights must be float32 (got {weights.dtype})")
+    if indices.ndim != 1 or weights.ndim != 1:
+        raise ValueError("iqlhip: update indices and weights must be one-dimensional")
+    if indices.shape[0] != weights.shape[0]:
+        raise ValueError(f"iqlhip: {indices.shape[0]} update indices for {weights.shape[0]} weights")
+    if device is not None and (indices.device != device or weights.device != device):
+        raise ValueError(f"iqlhip: update indices and weights must live on the table's device ({device})")
+    return int(indices.shape[0])
+
+
+def build_table(w_dev, n: int, stream, updatable: bool = False, capacity=None, max_weight=None):
+    """The library's table over the device vector w_dev[0..n): (handle, generation)."""
+    import iqlhip_binding as hb
+    table = C.c_void_p()
+    if updatable:
+        capacity, max_weight = check_updatable_args(n, capacity, max_weight)
+        hb.check(hb.lib().iqlhip_weights_build_updatable(w_dev.data_ptr(), n, capacity, max_weight, stream, C.byref(table)))
+    else:
+        hb.check(hb.lib().iqlhip_weights_build(w_dev.data_ptr(), n, stream, C.byref(table)))
+    gen = C.c_uint64()
+    hb.check(hb.lib().iqlhip_weights_info(table, None, None, None, C.byref(gen), None))
+    return table, int(gen.value)
+
+
+def table_state(table, n: int = 0, leaves: bool = False):
+    """(total, flags, version, q) of a table, after waiting for the device; q: the n leaf values as a uint64 ndarray
+    (leaves=True) or None."""
+    import iqlhip_binding as hb
+    total, flags, version = C.c_uint64(), C.c_uint32(), C.c_uint64()
+    q = np.empty(n, dtype=np.uint64) if leaves else None
+    hb.check(hb.lib().iqlhip_weights_state(table, C.byref(total), C.byref(flags), C.byref(version),
+                                           q.ctypes.data if leaves else None))
+    return int(total.value), int(flags.value), int(version.value), q
+
+
 def check_call(buffer) -> int:
     """What every weighted call checks on the buffer before anything is launched: it lives on a GPU, has weights, and
-    still draws over the number of rows they were set for.  Returns that number."""
+    still draws over the number of rows they were set for (an updatable table spans the buffer's capacity and stays
+    valid while the index bound moves: rows beyond it weigh 0).  Returns the number of rows the table weighs."""
     if not getattr(buffer, "_gpu", False):
         raise ValueError("iqlhip: weighted sampling needs a ReplayBuffer that lives on the GPU")
     n = buffer.sample_weights_n
     if n is None:
         raise ValueError("iqlhip: the replay buffer has no sample weights (set_sample_weights)")
+    if getattr(buffer, "_weights_updatable", False):
+        return n
     if buffer._index_bound() != n:
         raise ValueError(f"iqlhip: the sample weights were set for {n} rows, the buffer now draws over "
                          f"{buffer._index_bound()}: call set_sample_weights again")
@@ -95,13 +161,25 @@ class SampleWeights:
     _n = 0
     _gen = 0
     _device = None
+    _updatable = False
+    _version = 0
 
-    def __init__(self, weights, device=None, stream=None):
+    def __init__(self, weights, device=None, stream=None, updatable: bool = False, capacity=None, max_weight=None):
+        """updatable=True: a table that update() changes in place.  capacity: rows it spans (default: len(weights));
+        rows beyond the given weights weigh 0.  max_weight: fixes the scale for the table's life — weights are
+        quantised to multiples of 2^(floor(log2(max(max_weight, max(weights)))) - 38), and a later weight of twice that
+        power of two or more saturates; None: the largest weight given.  ValueError for capacity or max_weight without
+        updatable=True."""
         import torch
         import iqlhip_binding as hb
         shape = tuple(getattr(weights, "shape", ()))
         n = int(shape[0]) if shape else 1        # (n: the vector's own length; check_vector names what else is wrong)
         kind = check_vector(weights, n)
+        if not updatable and (capacity is not None or max_weight is not None):
+            raise ValueError("iqlhip: capacity and max_weight belong to an updatable table (updatable=True)")
+        rows = n
+        if updatable:
+            rows, max_weight = check_updatable_args(n, capacity, max_weight)
         on_gpu = kind == "torch" and weights.device.type != "cpu"
         host = None
         if not on_gpu:                       # (the value checks of a host vector come before any look at a device)
@@ -121,18 +199,71 @@ class SampleWeights:
             w_dev = weights.contiguous()
         else:
             w_dev = torch.tensor(host, dtype=torch.float32, device=dev)      # (a copy: the array may be read-only)
-        table = C.c_void_p()
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-            hb.check(hb.lib().iqlhip_weights_build(w_dev.data_ptr(), n, st, C.byref(table)))
-        gen = C.c_uint64()
-        hb.check(hb.lib().iqlhip_weights_info(table, None, None, None, C.byref(gen), None))
-        self._table, self._n, self._gen, self._device = table, n, int(gen.value), dev
+            table, gen = build_table(w_dev, n, st, updatable, rows, max_weight)
+        self._table, self._n, self._gen, self._device = table, rows, gen, dev
+        self._updatable, self._version = bool(updatable), 0
 
     @property
     def n(self) -> int:
-        """Rows the table weighs."""
+        """Rows the table weighs (an updatable table: its capacity)."""
         return self._n
+
+    @property
+    def updatable(self) -> bool:
+        return self._updatable
+
+    @property
+    def version(self) -> int:
+        """Content version: 0 after the build, plus 1 per update() (a continuation of train_steps_weighted keys on the
+        generation and on it)."""
+        return self._version
+
+    def _alive(self):
+        if self._table is None:
+            raise ValueError("iqlhip: the sample weights have been freed")
+        return self._table
+
+    def update(self, indices, weights, bound=None) -> None:
+        """w[indices[j]] = weights[j] on the device, queued on the current stream, no synchronisation: int64 indices
+        and float32 weights, device tensors of one length.  Duplicates: the last position wins.  A NaN, an infinity, a
+        negative weight or an index outside [0, bound) (default: the table's n) is skipped and leaves a bit in flags();
+        a weight beyond the table's scale saturates.  A draw running on ANOTHER stream at the same time is the caller's
+        error.  ValueError on a table that is not updatable."""
+        import torch
+        import iqlhip_binding as hb
+        table = self._alive()
+        if not self._updatable:
+            raise ValueError("iqlhip: these sample weights are not updatable (SampleWeights(..., updatable=True))")
+        m = check_update_args(indices, weights, self._device)
+        bound = self._n if bound is None else int(bound)
+        if not 0 <= bound <= self._n:
+            raise ValueError(f"iqlhip: bound {bound} outside [0, {self._n}]")
+        idx, w = indices.contiguous(), weights.contiguous()
+        with torch.cuda.device(self._device):
+            hb.check(hb.lib().iqlhip_weights_update(table, idx.data_ptr(), w.data_ptr(), m, bound,
+                                                    torch.cuda.current_stream(self._device).cuda_stream))
+        self._version += 1
+
+    def flags(self) -> int:
+        """The sticky flag word (waits for the device): bit 0 a non-finite weight was skipped, bit 1 a negative one,
+        bit 2 an index out of range.  0 for a static table."""
+        return table_state(self._alive())[1]
+
+    def total(self) -> int:
+        """sum(q) as the table holds it now (waits for the device)."""
+        return table_state(self._alive())[0]
+
+    def leaves(self) -> np.ndarray:
+        """q[0..n) rebuilt from the tree, a uint64 ndarray (waits for the device; tests)."""
+        return table_state(self._alive(), self._n, leaves=True)[3]
+
+    def clear_flags(self) -> None:
+        import torch
+        import iqlhip_binding as hb
+        with torch.cuda.device(self._device):
+            hb.check(hb.lib().iqlhip_weights_clear_flags(self._alive(), torch.cuda.current_stream(self._device).cuda_stream))
 
     @property
     def generation(self) -> int:
@@ -187,6 +318,11 @@ def check_table(buffer, weights, member=None) -> int:
     if rows is not None and weights.device is not None and rows.device != weights.device:
         raise ValueError(f"iqlhip: the sample weights live on {weights.device}, the buffer on {rows.device}{who}")
     n = buffer._index_bound()
+    if weights.updatable:           # (spans a capacity: rows beyond the index bound weigh 0 unless the caller set them)
+        if not n <= weights.n <= buffer._buffer_size:
+            raise ValueError(f"iqlhip: the updatable sample weights span {weights.n} rows, the buffer draws over {n} of "
+                             f"{buffer._buffer_size}{who}")
+        return weights.n
     if weights.n != n:
         raise ValueError(f"iqlhip: the sample weights cover {weights.n} rows, the buffer draws over {n}{who}")
     return n
