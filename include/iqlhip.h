@@ -176,6 +176,22 @@ int iqlhip_bind(iqlhip_ctx* ctx, float* params_dev, float* target_dev, float* ex
  * three groups; Polyak.  Losses land in device words read by iqlhip_read_losses. */
 int iqlhip_step(iqlhip_ctx* ctx, const iqlhip_batch* batch, const iqlhip_step_scalars* sc, void* stream);
 
+/* iqlhip_step with per-row loss weights c = row_w_dev[0 .. rows) (fp32, device; importance-sampling correction of a
+ * weighted or prioritised draw):
+ *   value_loss = 1/B sum_r c_r |tau - 1(u_r < 0)| u_r^2     q_loss = 1/B sum_r c_r (e1_r^2 + e2_r^2) / 2
+ *   actor_loss = 1/B sum_r c_r exp_adv_r bc_r
+ * and every gradient follows from these.  A row-weighted variant of the fp32 backward forms them: each row's finished
+ * unweighted terms are multiplied by c_r last, so weights of exactly 1.0f give iqlhip_step's bits.  The forward and the
+ * update are iqlhip_step's; actor dropout, step statistics (unweighted definitions) and gradient clipping (norms of the
+ * weighted gradient) apply as there.  td_out_dev: NULL, or [rows][2] fp32 (8-byte aligned) that receives the rows'
+ * TD errors (q1 - y, q2 - y) — the pre-update values the loss used.  Asynchronous like iqlhip_step; the (weighted)
+ * losses are read through iqlhip_read_losses.
+ * IQLHIP_EINVAL: row_w_dev NULL.  IQLHIP_EUNSUPPORTED, before anything is launched or any counter moves: bf16 precision
+ * (and with it the large-batch path), a data-parallel exchange attached.  The weights' VALUES are not inspected: NaN
+ * or negative weights are the caller's business. */
+int iqlhip_step_rw(iqlhip_ctx* ctx, const iqlhip_batch* batch, const iqlhip_step_scalars* sc, const float* row_w_dev,
+                   float* td_out_dev, void* stream);
+
 /* The same step WITH the host synchronisation train() ends on (the three .item() calls of iql.py:491,509,535 as one):
  * the losses land in host-mapped pinned words followed by a completion word the host spins on — no stream synchronise
  * (12-17 us of host time after the GPU has finished, profiles/r03_sync_cost.txt).  Returns when out[3] = {value, q, actor}
@@ -305,6 +321,15 @@ int iqlhip_weights_state(const iqlhip_weights* table, uint64_t* total, uint32_t*
  * one index by a 64-ary descent through the table. */
 int iqlhip_draw_indices_weighted(int64_t* idx_dev, int64_t n_idx, const iqlhip_weights* table, uint64_t seed,
                                  uint64_t offset, void* stream);
+/* The same indices, bit for bit, plus the importance-sampling weights of the drawn rows for iqlhip_step_rw (DESIGN.md
+ * §6j): c_dev[j] = (q_min / q_j)^is_beta, q_j the quantised weight of row idx_dev[j] (the table integer
+ * iqlhip_weights_state returns) and q_min the smallest q among the batch_rows consecutive indices j belongs to (groups
+ * [k batch_rows, (k + 1) batch_rows); a short last group is normalised over the rows it has).  Per-batch max
+ * normalisation: the table total and the row count cancel, c in (0, 1], the rarest row of every batch has c = 1.0f and
+ * is_beta = 0 gives 1.0f throughout.  Computed in fp32 through log2 / exp2 (relative error about 2e-6 at a 2^20 weight
+ * range).  IQLHIP_EINVAL: a NULL pointer, n_idx or batch_rows < 1, is_beta negative or not finite. */
+int iqlhip_draw_indices_weighted_is(int64_t* idx_dev, float* c_dev, int64_t n_idx, const iqlhip_weights* table, uint64_t seed,
+                                    uint64_t offset, int64_t batch_rows, float is_beta, void* stream);
 /* iqlhip_train_steps with every step's rows drawn by `table` (size must be the table's n): the idle blocks of each
  * forward draw and gather the next step's rows, so a weighted call consumes exactly the counters a plain call does.
  * IQLHIP_TS_CONTINUE is honoured only behind a weighted call on the same table GENERATION (and the conditions of
@@ -318,6 +343,21 @@ int iqlhip_train_steps_weighted(iqlhip_ctx* ctx, const float* rows_dev, int64_t 
                                 int32_t flags, void* stream, const iqlhip_weights* table);
 int iqlhip_train_steps_weighted_prepare(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int32_t batch_rows,
                                         float inv_batch, void* stream, const iqlhip_weights* table);
+/* iqlhip_train_steps_weighted with the importance-sampling correction of iqlhip_step_rw applied inside the chunk graphs
+ * (DESIGN.md §6j): every step's loss terms are weighted by c_r = (q_min / q_r)^is_beta over that step's batch — bit for
+ * bit the c that iqlhip_draw_indices_weighted_is(..., batch_rows, is_beta) returns for the same indices, so a call equals
+ * the eager loop draw -> gather -> iqlhip_step_rw bit for bit, and is_beta = 0 equals iqlhip_train_steps_weighted.  The
+ * idle blocks and the set-up kernel stage each drawn row's q next to the rows; one idle block of step t's forward forms
+ * c before backward t (the row-weighted kernel) reads it: no launch more than a weighted call has.  is_beta is a value of
+ * the CALL: the set-up kernel writes it to a device word, so another is_beta neither re-captures a chunk nor ends a
+ * continuation.  The chunk graphs are a kind of their own (their own _prepare); such a call continues only such a call.
+ * Everything iqlhip_train_steps_weighted refuses, and: IQLHIP_EINVAL for an is_beta that is negative or not finite,
+ * IQLHIP_EUNSUPPORTED at bf16 precision. */
+int iqlhip_train_steps_weighted_is(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int64_t size, int32_t batch_rows,
+                                   const iqlhip_step_scalars* sc, int32_t n_steps, uint64_t seed, uint64_t stream_offset,
+                                   int32_t flags, void* stream, const iqlhip_weights* table, float is_beta);
+int iqlhip_train_steps_weighted_is_prepare(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int32_t batch_rows,
+                                           float inv_batch, void* stream, const iqlhip_weights* table);
 
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is
@@ -325,6 +365,10 @@ int iqlhip_train_steps_weighted_prepare(iqlhip_ctx* ctx, const float* rows_dev, 
 int iqlhip_forward_backward(iqlhip_ctx* ctx, const iqlhip_batch* batch, const iqlhip_step_scalars* sc,
                             float* grads_dev, void* stream);
 int iqlhip_apply_update(iqlhip_ctx* ctx, const float* grads_dev, const iqlhip_step_scalars* sc, void* stream);
+/* Tests and debugging: iqlhip_forward_backward with iqlhip_step_rw's row weights (same arguments, same refusals) — the
+ * flat gradient of the weighted losses, the tail words their sums; what the parity tests compare per tensor. */
+int iqlhip_forward_backward_rw(iqlhip_ctx* ctx, const iqlhip_batch* batch, const iqlhip_step_scalars* sc,
+                               const float* row_w_dev, float* td_out_dev, float* grads_dev, void* stream);
 int64_t iqlhip_grad_words(const iqlhip_ctx* ctx);   /* n_params + 4 */
 
 /* n_steps consecutive `sample -> train` iterations without host round trips: row indices are drawn on the device

@@ -89,6 +89,11 @@ static auto fwd_kernel(bool bf, bool dma, bool multi) {
 static auto bwd_kernel(bool bf, bool full, bool multi) {
   return with_bools([](auto MU, auto BF, auto FU) { return &iql_bwd_kernel<BF.value, FU.value, MU.value>; }, multi, bf, full);
 }
+// The row-weighted fp32 backward (iqlhip_step_rw).  Its selector is DEFINED at the end of this file: the instantiations are
+// then emitted behind every other kernel, and everything that existed keeps its place in the code object (see above).
+using BwdRwFn = void (*)(const float*, const float*, const float*, const float*, const float*, unsigned, unsigned, unsigned,
+                         unsigned, StepParams, const float*, float*);
+static BwdRwFn bwd_rw_kernel(bool full, bool multi);
 static auto bwd_rows_kernel(bool csplit) {
   return with_bools([](auto CS) { return &iql_bwd_rows_kernel<CS.value>; }, csplit);
 }
@@ -149,8 +154,10 @@ struct GraphKey {
   int32_t n_off = 0;
   // weighted chunks (iqlhip_train_steps_weighted): the table the idle blocks draw by.  wt.tab == nullptr: not one
   WTab wt{nullptr, 0u, 0};
+  // ... with importance-sampling weights (iqlhip_train_steps_weighted_is): another forward and the row-weighted backward
+  int is = 0;
   bool operator==(const GraphKey& o) const {
-    return rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
+    return is == o.is && rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
            inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip &&
            rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n && wt.levels == o.wt.levels && wt.local == o.wt.local;
   }
@@ -160,9 +167,13 @@ struct GraphKey {
 // A weighted call (iqlhip_train_steps_weighted) travels the same way: rows_on == nullptr, wt its table and wt_gen the
 // table's generation and wt_ver its content version (what a following call must name to start on the rows this one
 // staged: iqlhip_weights_update moves the version, the rows staged before it were drawn by the old weights).
-struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; uint64_t wt_ver = 0; };
-// Which forward a step of such a call launches: 0 iql_fwd_kernel, 1 iql_fwd_mixed_kernel, 2 iql_fwd_weighted_kernel.
-static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? 2 : 1); }
+// is: a weighted call with importance-sampling weights (iqlhip_train_steps_weighted_is), is_beta its exponent — a value
+// of the CALL (the set-up kernel writes it to a device word), never part of a key.
+struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; uint64_t wt_ver = 0;
+                int is = 0; float is_beta = 0.f; };
+// Which forward a step of such a call launches: 0 iql_fwd_kernel, 1 iql_fwd_mixed_kernel, 2 iql_fwd_weighted_kernel,
+// 3 iql_fwd_weighted_is_kernel (and then the row-weighted backward).
+static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? (mx->is ? 3 : 2) : 1); }
 
 // The few RCCL entry points the in-stream all-reduce needs, resolved at run time from the librccl.so.1 the process
 // already has (PyTorch-ROCm brings one) or can load — the library has no link-time dependency on RCCL.
@@ -229,6 +240,10 @@ struct iqlhip_ctx {
   unsigned long long call_seq = 0;
   unsigned* setup_arrivals = nullptr;           // device: block counter of iql_call_setup_kernel
   bool weighted_lds_set = false;                // ... and the weighted ones (check_weighted_args)
+  bool weighted_is_lds_set = false;
+  // weighted calls with importance-sampling weights: [2][max_batch] staged q of the two staging parities, [max_batch] c of
+  // the running step, the call's beta (one allocation, made by the first such call; addresses frozen in chunk graphs)
+  float* is_buf = nullptr;
   bool mixed_lds_set = false;                   // the mixed forward instantiations have their dynamic-LDS limit (check_mixed_args)
   char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (freeing it at the end of prepare
                                                 //   idles the GPU right in front of the caller's first steps)
@@ -266,6 +281,7 @@ struct iqlhip_ctx {
   struct { bool valid = false; const float* rows = nullptr; int64_t ld = 0, size = 0; int32_t B = 0; uint64_t seed = 0;
            uint64_t next_offset = 0; float drop_p = 0.f; uint64_t drop_seed = 0, drop_step = 0;
            uint64_t wt_gen = 0;      // the table generation of a weighted call (0: a plain call)
+           int is = 0;               // 1: that call staged the rows' q as well (iqlhip_train_steps_weighted_is)
            uint64_t wt_ver = 0;      // ... and the table's content version at that call (iqlhip_weights_update adds 1)
          } cont;
   std::vector<CachedGraph> graphs;
@@ -470,6 +486,7 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   if (!rc) rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_one_kernel(m & 1, m & 2); });
   if (!rc) rc = set_max_lds(3, c->lds_bwd, [](unsigned m) { return bwd_kernel(m & 1, m & 2, m & 4); });
   if (!rc) rc = set_max_lds(1, c->lds_bwd_lb, [](unsigned m) { return bwd_rows_kernel(m & 1); });
+  if (!rc) rc = set_max_lds(2, c->lds_bwd, [](unsigned m) { return bwd_rw_kernel(m & 1, m & 2); });
   return rc;
 }
 
@@ -855,9 +872,11 @@ static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c
 
 static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);     // (end of file)
 static void launch_fwd_weighted_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
+static void launch_fwd_weighted_is_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
 static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, int kind = 0) {
   if (kind == 1) return launch_fwd_mixed_grid(c, p, nb, st);
   if (kind == 2) return launch_fwd_weighted_grid(c, p, nb, st);
+  if (kind == 3) return launch_fwd_weighted_is_grid(c, p, nb, st);
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
   // (policy inference — iqlhip_actor_forward — has its own instantiations)
@@ -927,7 +946,10 @@ static BwdWords bwd_words(const iqlhip_ctx* c, const StepParams& p, int n_chunk,
   w.rts = (unsigned)n_rt | (spb_l2 << 10);
   return w;
 }
-static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st) {
+// rw (iqlhip_step_rw): the step's per-row loss weights and, nullable, where its TD errors go — the row-weighted kernel;
+// its callers have refused bf16 and the large-batch path.
+struct RowWeights { const float* w; float* td; };
+static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st, const RowWeights* rw = nullptr) {
   StepParams p = p_in;
   if (use_lb(c, p.rows)) {
     const LbArgs a = lb_args(c, p.rows);
@@ -957,6 +979,11 @@ static void launch_bwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t 
   p.spb_l2 = (l2 << 2) | (n_don << 8);
   const bool full = (p.rows % CHUNK_ROWS) == 0;      // every tile of every block lies inside the batch: no clamps
   const BwdWords w = bwd_words(c, p, n_chunk, n_rt, (unsigned)p.spb_l2);
+  if (rw) {
+    hipLaunchKernelGGL(bwd_rw_kernel(full, /*multi=*/l2 > 0), dim3(bwd_blocks(n_chunk, n_rt, l2, n_don)), dim3(256), c->lds_bwd, st,
+                       w.heads, w.xb, w.h1, w.h0, w.params, w.dims, w.ldB, w.mbc, w.rts, p, rw->w, rw->td);
+    return;
+  }
   hipLaunchKernelGGL(bwd_kernel(c->precision == 1, full, /*multi=*/l2 > 0), dim3(bwd_blocks(n_chunk, n_rt, l2, n_don)), dim3(256),
                      c->lds_bwd, st, w.heads, w.xb, w.h1, w.h0, w.params, w.dims, w.ldB, w.mbc, w.rts, p);
 }
@@ -1441,7 +1468,8 @@ static XchParams make_xch(const iqlhip_ctx* c, bool from_hdr) {
 // of `heads`, before the update kernel, which is the last reader of the slabs and, in a chunk, moves the header word
 // the ring slot is formed from.  `kind`: fwd_kind of the call (a two-source or a weighted chunk has a forward of its own).
 static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int mode, int parity, int k, bool from_hdr,
-                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, int kind = 0) {
+                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, int kind = 0,
+                        const RowWeights* rw = nullptr) {
   StepParams p = p_in;
   const int buf = (parity + k) & 1;
   // P2P with batches of <= 256 rows: no flatten kernel.  The backward writes its chunk slab (= the w1 / b1 / w2 / b2 /
@@ -1457,7 +1485,7 @@ static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int 
   }
   launch_fwd(c, p, st, kind);
   if (ev) HIPCHK(hipEventRecord(ev[1], st));
-  launch_bwd(c, p, st);
+  launch_bwd(c, p, st, rw);
   if (ev) HIPCHK(hipEventRecord(ev[2], st));
   // (clipping is refused with an exchange before any launch: below, mode is IQLHIP_XCH_NONE whenever clip_on)
   launch_stats(c, u, sa, c->clip_on, st);
@@ -1569,7 +1597,7 @@ static void eager_begin(iqlhip_ctx* c, int rows, const iqlhip_step_scalars* sc, 
 }
 
 static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* out_sync, void* stream,
-                     bool defer_wait = false);
+                     bool defer_wait = false, const RowWeights* rw = nullptr);
 
 extern "C" int iqlhip_step(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, void* stream) {
   return step_impl(c, b, sc, nullptr, stream);
@@ -1594,11 +1622,31 @@ extern "C" int iqlhip_step_wait(iqlhip_ctx* c, float out[3], void* stream) {
   return sync_losses(c, c->done_seq, (hipStream_t)stream, out);
 }
 
+// The cases the row-weighted backward is not built for; checked before anything is launched or any counter moves.
+static int row_weights_check(const iqlhip_ctx* c, int rows, const RowWeights& rw) {
+  if (!rw.w) return fail(IQLHIP_EINVAL, "NULL row weights");
+  if ((((uintptr_t)rw.w) & 3) || (((uintptr_t)rw.td) & 7)) return fail(IQLHIP_EINVAL, "row weights must be 4-byte, TD errors 8-byte aligned");
+  if (c->precision == 1) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported at bf16 precision");
+  if (use_lb(c, rows)) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported on the large-batch path");
+  if (c->xch_mode != IQLHIP_XCH_NONE) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported with a data-parallel exchange");
+  return IQLHIP_OK;
+}
+
+// iqlhip_step with every row's loss terms multiplied by row_w_dev[row] (fp32, `rows` values on the device): the
+// row-weighted backward, everything else the plain step's launches.  td_out_dev (nullable, [rows][2] fp32) receives the
+// rows' pre-update TD errors (q1 - y, q2 - y).  NaN or negative weights are the caller's business.
+extern "C" int iqlhip_step_rw(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, const float* row_w_dev,
+                              float* td_out_dev, void* stream) {
+  const RowWeights rw = {row_w_dev, td_out_dev};
+  return step_impl(c, b, sc, nullptr, stream, false, &rw);
+}
+
 static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* out_sync, void* stream,
-                     bool defer_wait) {
+                     bool defer_wait, const RowWeights* rw) {
   if (!c || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_batch(c, b);
   if (rc) return rc;
+  if (rw && (rc = row_weights_check(c, b->rows, *rw))) return rc;
   if ((rc = step_entry(c, b->rows, stream, /*multi_step=*/false))) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -1622,7 +1670,7 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
     c->ev_used += 4;
     HIPCHK(hipEventRecord(ev[0], st));
   }
-  rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, e.stats());
+  rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, e.stats(), 0, rw);
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
   HIPCHK(hipGetLastError());
@@ -1746,11 +1794,24 @@ extern "C" int iqlhip_online_step_mixed(iqlhip_ctx* c, float* rows_dev, int64_t 
                      act_seed, act_out_host, stream, rows_off_dev, size_off, idx_off_host, n_off);
 }
 
+static int forward_backward_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* grads_dev,
+                                 void* stream, const RowWeights* rw);
 extern "C" int iqlhip_forward_backward(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc,
                                        float* grads_dev, void* stream) {
+  return forward_backward_impl(c, b, sc, grads_dev, stream, nullptr);
+}
+// iqlhip_forward_backward with iqlhip_step_rw's row weights: the gradient of the weighted losses.
+extern "C" int iqlhip_forward_backward_rw(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc,
+                                          const float* row_w_dev, float* td_out_dev, float* grads_dev, void* stream) {
+  const RowWeights rw = {row_w_dev, td_out_dev};
+  return forward_backward_impl(c, b, sc, grads_dev, stream, &rw);
+}
+static int forward_backward_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_scalars* sc, float* grads_dev,
+                                 void* stream, const RowWeights* rw) {
   if (!c || !sc || !grads_dev) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_batch(c, b);
   if (rc) return rc;
+  if (rw && (rc = row_weights_check(c, b->rows, *rw))) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
   const float* xb_cur = nullptr;
@@ -1759,7 +1820,7 @@ extern "C" int iqlhip_forward_backward(iqlhip_ctx* c, const iqlhip_batch* b, con
   EagerStep e;
   eager_begin(c, b->rows, sc, st, xb_cur, e);
   launch_fwd(c, e.p, st);
-  launch_bwd(c, e.p, st);
+  launch_bwd(c, e.p, st, rw);
   launch_flatten(c, e.u, grads_dev, false, st);
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
@@ -1830,6 +1891,12 @@ static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_d
     i.n = B;
     i.k = k;
     if (mx) { i.rows_on = mx->rows_on; i.n_off = mx->n_off; i.wt = mx->wt; }
+    if (mx && mx->is) {       // step k's q lie in half k & 1 (where the step before staged them), step k + 1's go to the other
+      i.q_src = c->is_buf + (size_t)(k & 1) * MB;
+      i.q_dst = c->is_buf + (size_t)((k + 1) & 1) * MB;
+      i.c_dst = c->is_buf + 2 * (size_t)MB;
+      i.is_beta = c->is_buf + 3 * (size_t)MB;
+    }
   }
 }
 
@@ -1854,7 +1921,10 @@ static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_
     // (statistics: slot BASE + k of the ring, the loss ring's indexing; the chunk's key carries the setting)
     StatsArgs sa;
     if (c->stats_on) sa = make_stats(c, p, c->stats_ring, k, c->k_max, c->hdr);
-    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, kind);
+    // (kind 3: the step's c, written by an idle block of its forward, is the row-weighted backward's weight vector)
+    const RowWeights rw = {c->is_buf ? c->is_buf + 2 * (size_t)MB : nullptr, nullptr};
+    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, kind,
+                          kind == 3 ? &rw : nullptr);
     if (rc) return rc;
   }
   return IQLHIP_OK;
@@ -1883,7 +1953,8 @@ struct SetupArgs {
   unsigned* arrivals; unsigned long long* ack; unsigned long long ack_val;
   const float* rows_on; int n_off;        // (iql_call_setup_mixed_kernel's two more)
   WTab wt;                                // (iql_call_setup_weighted_kernel's one more, in their place)
-  void* ptrs[17];
+  float* q_dst; float* beta_dev; float beta;        // (iql_call_setup_weighted_is_kernel's three behind wt)
+  void* ptrs[20];
   const void* func;                       // iql_call_setup_kernel, its two-source or its weighted form
   int nb;
 };
@@ -1905,15 +1976,17 @@ static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int 
   a.rows_on = mx ? mx->rows_on : nullptr; a.n_off = mx ? mx->n_off : 0;
   const int kind = fwd_kind(mx);
   a.wt = mx ? mx->wt : WTab{nullptr, 0u, 0};
-  a.func = kind == 2 ? (const void*)iql_call_setup_weighted_kernel
+  a.q_dst = c->is_buf; a.beta_dev = c->is_buf ? c->is_buf + 3 * (size_t)MB : nullptr; a.beta = mx ? mx->is_beta : 0.f;
+  a.func = kind == 3 ? (const void*)iql_call_setup_weighted_is_kernel : kind == 2 ? (const void*)iql_call_setup_weighted_kernel
                      : (kind == 1 ? (const void*)iql_call_setup_mixed_kernel : (const void*)iql_call_setup_kernel);
-  void* p[17] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
+  void* p[20] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
                  &a.drop_words, &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val, &a.rows_on, &a.n_off};
-  if (kind == 2) { p[15] = &a.wt; p[16] = nullptr; }
+  if (kind >= 2) { p[15] = &a.wt; p[16] = nullptr; }
+  if (kind == 3) { p[16] = &a.q_dst; p[17] = &a.beta_dev; p[18] = &a.beta; }
   memcpy(a.ptrs, p, sizeof p);
   long long want = ((long long)n_steps * 3 + 255) / 256;
   if (gather) want = std::max(want, ((long long)B * (c->row_ld / 4) + 255) / 256);
-  if (gather && kind == 2) want = std::max(want, ((long long)B + 7) / 8);      // (a wave per row, two rows a pass)
+  if (gather && kind >= 2) want = std::max(want, ((long long)B + 7) / 8);      // (a wave per row, two rows a pass)
   if (drop) want += (2 * MB * 8 + 255) / 256;
   a.nb = (int)std::max<long long>(1, std::min<long long>(want, 256));
 }
@@ -1928,7 +2001,7 @@ static int launch_call_setup(iqlhip_ctx* c, hipStream_t st, const ChunkHdr& h, i
 // Capture and instantiate the chunk graph of g.key into g, member by member (a failure leaves the ones made so far).
 static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   const GraphKey& key = g.key;
-  const MixSrc key_mx{key.rows_on, key.n_off, key.wt};
+  const MixSrc key_mx{key.rows_on, key.n_off, key.wt, 0, 0, key.is, 0.f};
   const MixSrc* mx = (key.rows_on || key.wt.tab) ? &key_mx : nullptr;
   // the chunk's idle-work records: device memory written once, here (their content is part of what the key freezes)
   {
@@ -2011,7 +2084,7 @@ static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld,
                          int parity, int head = 0, const MixSrc* mx = nullptr) {
   GraphKey key;
   key.head = head;
-  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; key.wt = mx->wt; }
+  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; key.wt = mx->wt; key.is = mx->is; }
   key.rows = rows_dev; key.ld = ld; key.B = B; key.K = K; key.params = c->params; key.drop_p = c->drop_p;
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
@@ -2209,8 +2282,9 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // rows its last forward staged are not what a plain call would draw, so it claims nothing and leaves no token.)
   // A weighted call continues a weighted call on the same table generation only, and a plain call a plain one.
   const int kind = fwd_kind(mx);
-  const uint64_t wt_gen = kind == 2 ? mx->wt_gen : 0, wt_ver = kind == 2 ? mx->wt_ver : 0;
-  const bool cont = kind != 1 && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == wt_gen &&
+  const uint64_t wt_gen = kind >= 2 ? mx->wt_gen : 0, wt_ver = kind >= 2 ? mx->wt_ver : 0;
+  const int is_call = kind == 3 ? 1 : 0;      // (the rows a call without staged q left cannot start a call that needs them)
+  const bool cont = kind != 1 && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == wt_gen && c->cont.is == is_call &&
                     c->cont.wt_ver == wt_ver &&
                     c->cont.rows == rows_dev && c->cont.ld == ld &&
                     c->cont.size == size && c->cont.B == B && c->cont.seed == seed && c->cont.next_offset == stream_offset &&
@@ -2274,7 +2348,7 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
   if (kind != 1 && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
-    c->cont.wt_gen = wt_gen; c->cont.wt_ver = wt_ver;
+    c->cont.wt_gen = wt_gen; c->cont.wt_ver = wt_ver; c->cont.is = is_call;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
     c->cont.next_offset = stream_offset + ((unsigned long long)K * (unsigned long long)B) / 2ull;
     c->cont.drop_p = c->drop_p; c->cont.drop_seed = c->drop_seed; c->cont.drop_step = c->drop_step;
@@ -4442,6 +4516,29 @@ extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev,
   return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
 }
 
+// ... with importance-sampling weights (include/iqlhip.h iqlhip_train_steps_weighted_is): chunk graphs of a
+// kind of their own — iql_fwd_weighted_is_kernel, whose idle blocks also stage the drawn rows' q and form the step's c,
+// and the row-weighted backward.  The kernels: iqlhip_isweight_kernels.h, behind every other kernel (end of file).
+static int weighted_is_setup(iqlhip_ctx* c, int32_t B, float is_beta);
+extern "C" int iqlhip_train_steps_weighted_is_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B,
+                                                      float inv_batch, void* stream, const iqlhip_weights* table) {
+  int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
+  if (!rc) rc = weighted_is_setup(c, B, 0.f);
+  if (rc) return rc;
+  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version, 1, 0.f};
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
+}
+extern "C" int iqlhip_train_steps_weighted_is(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
+                                              const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
+                                              int32_t flags, void* stream, const iqlhip_weights* table, float is_beta) {
+  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
+  if (!rc) rc = weighted_is_setup(c, B, is_beta);
+  if (rc) return rc;
+  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version, 1, is_beta};
+  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
+}
+
 // ---------------------------------------------------------------------------
 // Per-row episode spans, returns and return-to-go (include/iqlhip.h iqlhip_rows_episode_returns; DESIGN.md 6c-2;
 // kernels: iqlhip_episode_kernels.h, included HERE, behind every other kernel of the file, as the scoring and the
@@ -4833,4 +4930,53 @@ extern "C" int iqlhip_jsrl_online_step(iqlhip_jsrl* j, float* rows_dev, int64_t 
   if (gate_out) *gate_out = j->on_pin[1];
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Importance-sampling weights of a weighted draw (include/iqlhip.h "iqlhip_draw_indices_weighted_is").
+#include "iqlhip_isweight_kernels.h"
+
+extern "C" int iqlhip_draw_indices_weighted_is(int64_t* idx_dev, float* c_dev, int64_t n_idx, const iqlhip_weights* table,
+                                               uint64_t seed, uint64_t offset, int64_t batch_rows, float is_beta, void* stream) {
+  if (!idx_dev || !c_dev || !table || n_idx < 1) return fail(IQLHIP_EINVAL, "bad argument");
+  if (batch_rows < 1) return fail(IQLHIP_EINVAL, "batch_rows %lld < 1", (long long)batch_rows);
+  if (!(is_beta >= 0.f) || !std::isfinite(is_beta)) return fail(IQLHIP_EINVAL, "is_beta must be finite and >= 0");
+  const int64_t n_groups = (n_idx + batch_rows - 1) / batch_rows;
+  if (n_groups > 0x7FFFFFFF) return fail(IQLHIP_EINVAL, "more than 2^31 - 1 batches in one draw");
+  const int nb = (int)std::min<int64_t>((n_idx + 7) / 8, 1024);      // a wave per index, two indices a pass
+  hipLaunchKernelGGL(iql_draw_indices_weighted_q_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (long long*)idx_dev, c_dev,
+                     (long long)n_idx, weights_tab(table), (unsigned long long)seed, (unsigned long long)offset);
+  hipLaunchKernelGGL(iql_is_weights_kernel, dim3((unsigned)n_groups), dim3(256), 0, (hipStream_t)stream, c_dev, (long long)n_idx,
+                     (long long)batch_rows, is_beta);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+static auto fwd_weighted_is_kernel(bool dma, bool multi) {      // (fp32 only: the row-weighted backward is)
+  return with_bools([](auto MU, auto DMA) { return &iql_fwd_weighted_is_kernel<DMA.value, MU.value>; }, multi, dma);
+}
+static void launch_fwd_weighted_is_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
+  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
+  hipLaunchKernelGGL(fwd_weighted_is_kernel(dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
+}
+// What a weighted call with importance-sampling weights needs beyond check_weighted_args, before anything is launched
+// or any counter moves: fp32, a valid exponent, the staging buffers and the forward's LDS allowance.
+static int weighted_is_setup(iqlhip_ctx* c, int32_t B, float is_beta) {
+  (void)B;
+  if (!(is_beta >= 0.f) || !std::isfinite(is_beta)) return fail(IQLHIP_EINVAL, "is_beta must be finite and >= 0");
+  if (c->precision == 1) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported at bf16 precision");
+  DevGuard guard(c->device);
+  if (!c->is_buf) HIPCHK(c->own.dev(&c->is_buf, (3 * (size_t)c->dims.max_batch + 4) * sizeof(float), 0));
+  if (!c->weighted_is_lds_set) {
+    int rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_weighted_is_kernel(m & 1, m & 2); });
+    if (rc) return rc;
+    c->weighted_is_lds_set = true;
+  }
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// (declared next to the other selectors; here so that its instantiations are the code object's last)
+static BwdRwFn bwd_rw_kernel(bool full, bool multi) {
+  return with_bools([](auto MU, auto FU) -> BwdRwFn { return &iql_bwd_rw_kernel<FU.value, MU.value>; }, multi, full);
 }

@@ -3,6 +3,8 @@
 // are the block's index and grid size of ONE agent's launch in both (a group kernel's agent is blockIdx.y).
 // In scope: template flags BF16, FULL, MULTI, the leading arguments q_*, `p` (StepParams) and KPF (the un-waited
 // argument-line prefetch, which reads the kernel-argument block itself: iql_bwd_kernel only).
+// RW (iql_bwd_rw_kernel only; elsewhere false, and rw_w / rw_td null constants): per-row loss weights rw_w[row] and the
+// optional TD-error output rw_td[row][2].
   RT_ENTRY();
   const int bid = blockIdx.x;
   const int x = bid & 7;
@@ -132,6 +134,8 @@
     const float lsr = pi_ls_issue_hot(q_params + ao.log_std, q_xb, h_pol, h_A);
     const bool is_pi = (net == IQLHIP_NET_PI);
     row_issue_hot(q_heads, q_xb, h_ld, h_S, h_A, BROW(prow), in);           // scalar partials, r, d (the policy needs h[1..3] for w)
+    float rwc = 1.f;                                                        // RW: this row's loss weight
+    if constexpr (RW) rwc = rw_w[(unsigned)BROW(prow)];
     // Policy: its per-(row, dim) inputs are loaded as (row, dim) work items — thread (r8 = tid >> 3, sub = tid & 7)
     // takes rows r8 + 32c, c = 0..7, and action dim sub (+ 8e) — so that one load instruction touches 6-8 cache
     // lines.  With thread = row every such load touched 48-64 lines; the 16 of them held the load queue for 8.5 k
@@ -196,7 +200,20 @@
       if (!is_pi) {
         float* dyrow = dYs + tid * DYA;
         for (int dd = 0; dd < Dp; ++dd) dyrow[dd] = 0.f;
-        if (row < B) row_finish(p, net, in, dyrow, lossA, lossB);
+        if constexpr (RW) {
+          // the finished unweighted values times the row's weight, last: a weight of 1.0f leaves their bits
+          if (row < B) {
+            float dy0;
+            row_finish(p, net, in, &dy0, lossA, lossB);
+            dyrow[0] = dy0 * rwc;
+            lossA *= rwc;
+            lossB *= rwc;
+            // the chunk's Q1 loss block owns the TD errors of its 256 rows (thread = row)
+            if (rw_td != nullptr && loss_block && net == IQLHIP_NET_Q1) *(f32x2*)(rw_td + 2u * (unsigned)row) = row_td_errors(p, in);
+          }
+        } else {
+          if (row < B) row_finish(p, net, in, dyrow, lossA, lossB);
+        }
       } else {
         // phase 1 (thread = row): the advantage weight (iql.py:519); rows >= B get w = 0, hence dY = 0
         float wrow = 0.f;
@@ -204,6 +221,7 @@
           const float tq = fminf(sum4(in.h[2]), sum4(in.h[3]));
           const float u = tq - sum4(in.h[1]);
           wrow = fminf(expf(p.hy.beta * u), p.hy.exp_adv_max);
+          if constexpr (RW) wrow *= rwc;       // feeds pi_items8, the log_std gradient and the actor loss sum
         }
         STAMP(p, 5);
         wS[tid] = wrow;
@@ -572,6 +590,11 @@
     for (int i = 0; i < 6; ++i) in.h[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     in.r = 0.f; in.d = 0.f;
     if (wave == 0 && net != IQLHIP_NET_PI) row_issue_hot(q_heads, q_xb, h_ld, h_S, h_A, prow, in);
+    float rwc = 1.f;                      // RW: the loss weight of the row this thread forms dY for
+    if constexpr (RW) {
+      if (net != IQLHIP_NET_PI) { if (wave == 0) rwc = rw_w[(unsigned)prow]; }
+      else rwc = rw_w[(unsigned)BROW(row0 + (tid >> 3))];
+    }
     // policy: the loss arithmetic of the 32 rows is spread over all 256 threads — thread (row tid>>3,
     // dims (tid&7) + 8c) — instead of 32 threads walking all dims while 224 wait at the barrier
     const int prl = tid >> 3, psub = tid & 7;
@@ -635,7 +658,8 @@
     if (net == IQLHIP_NET_PI) {
       const float tq = fminf(sum4(ph[1]), sum4(ph[2]));
       const float u = tq - sum4(ph[0]);
-      const float w = fminf(expf(p.hy.beta * u), p.hy.exp_adv_max);
+      float w = fminf(expf(p.hy.beta * u), p.hy.exp_adv_max);
+      if constexpr (RW) w *= rwc;
       const bool rvalid = (row0 + prl) < B;
       const bool gauss = (h_pol == IQLHIP_POLICY_GAUSSIAN);
 #pragma unroll
@@ -659,7 +683,10 @@
       float la, lbv;
       float* dyrow = dYs + tid * DYLD;
       for (int dd = 0; dd < Dp; ++dd) dyrow[dd] = 0.f;
-      if (row < B) row_finish(p, net, in, dyrow, la, lbv);
+      if (row < B) {
+        row_finish(p, net, in, dyrow, la, lbv);
+        if constexpr (RW) dyrow[0] *= rwc;
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
     H1V_LOAD(4, 8);

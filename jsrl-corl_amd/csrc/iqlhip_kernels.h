@@ -386,14 +386,26 @@ struct IdleWork {
   // two-source chunks only (MIXED): `rows` is the offline buffer, rows_on the online one, batch rows >= n_off are its
   const float* rows_on;
   int n_off;
-  // weighted chunks only (MODE 2): the cumulative table the next step's rows are drawn by
+  // weighted chunks only (MODE 2 and 3): the cumulative table the next step's rows are drawn by
   WTab wt;
+  // weighted chunks with importance-sampling weights only (MODE 3): the next step's staged q (fp32, the
+  // other parity's half), this step's (staged by the step before or by the set-up kernel), this step's c — read by its
+  // row-weighted backward — and the device word that holds the call's beta
+  float* q_dst;
+  const float* q_src;
+  float* c_dst;
+  const float* is_beta;
 };
 // (defined in iqlhip_weighted_kernels.h, behind every kernel of this file)
 __device__ __forceinline__ void idle_gather_weighted(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
                                                      unsigned long long j0, int blk, int nblk);
+// (defined in iqlhip_isweight_kernels.h, behind every kernel of this file)
+__device__ __forceinline__ void idle_gather_weighted_q(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
+                                                       unsigned long long j0, int blk, int nblk);
+__device__ __forceinline__ void idle_is_weights(const IdleWork& w);
 // MODE: 1 = the idle work of a two-source chunk (iql_fwd_mixed_kernel), 2 = of a weighted chunk
-// (iql_fwd_weighted_kernel) — a compile-time switch, so that the forward kernels of plain calls hold no trace of either.
+// (iql_fwd_weighted_kernel), 3 = of a weighted chunk with importance-sampling weights (iql_fwd_weighted_is_kernel) — a
+// compile-time switch, so that the forward kernels of plain calls hold no trace of any.
 template <int MODE = 0>
 __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int nblk) {
   constexpr bool MIXED = MODE == 1;
@@ -402,7 +414,10 @@ __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int
   const unsigned long long base = w.hdr[HDR_BASE], dseed = w.hdr[HDR_DROP_SEED], dstep = w.hdr[HDR_DROP_STEP];
   // the next step's rows: index j = POS + (k + 1) n + r of the call (for the chunk's last step that is step 0 of
   // whatever runs next: the following chunk, or the next call when it continues this one's stream)
-  if constexpr (MODE == 2)
+  if constexpr (MODE == 3) {
+    idle_gather_weighted_q(w, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, blk, nblk);
+    if (blk == nblk - 1) idle_is_weights(w);       // THIS step's c, from the q the step before staged: one block
+  } else if constexpr (MODE == 2)
     idle_gather_weighted(w, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, blk, nblk);
   else if (MIXED)
     gather_rows_drawn2(w.rows, w.rows_on, w.ld, w.xb_dst, w.n, w.n_off, seed, ctr0,
@@ -567,6 +582,13 @@ __device__ __forceinline__ void row_finish(const StepParams& p, int net, const R
   lossB = e2 * e2;
   dyrow[0] = ((net == IQLHIP_NET_Q1) ? e1 : e2) * invB;
 }
+// The row's TD errors (q1 - y, q2 - y) as row_finish forms them: the same expressions in the same order, so the stored
+// values are the ones the loss used (row-weighted backward only: iql_bwd_rw_kernel).
+__device__ __forceinline__ f32x2 row_td_errors(const StepParams& p, const RowIn& in) {
+  const float nv = sum4(in.h[0]);
+  const float y = in.r + ((1.f - in.d) * p.hy.discount) * nv;
+  return (f32x2){sum4(in.h[4]) - y, sum4(in.h[5]) - y};
+}
 
 __device__ __forceinline__ float block_sum_256(float v, float* red /*>=4 floats*/) {
 #pragma unroll
@@ -659,6 +681,25 @@ __global__ __launch_bounds__(256) void iql_bwd_kernel(const float* q_heads, cons
                                                       const float* q_params, unsigned q_dims, unsigned q_ldB, unsigned q_mbc,
                                                       unsigned q_rts, StepParams p) {
   constexpr bool KPF = true;      // (the argument-line prefetch below reads this kernel's argument block)
+  constexpr bool RW = false;      // (no per-row loss weights: iql_bwd_rw_kernel below is the form with them)
+  const float* const rw_w = nullptr;
+  float* const rw_td = nullptr;
+#include "iqlhip_bwd_body.inc"
+}
+// RW = true (iqlhip_step_rw): the same body, fp32 only, with every row's loss terms and head gradients
+// multiplied by rw_w[row] — one multiply per row, applied LAST to the finished unweighted value, so a weight of 1.0f
+// reproduces the plain kernel's bits — and, when rw_td is given, the row's TD errors (q1 - y, q2 - y) stored to
+// rw_td[row][2] by the chunk's Q1 loss block (one block per row, one 8-byte vector store per row).
+// A kernel of its own rather than a fourth flag of iql_bwd_kernel: the plain instantiations keep their symbols, their
+// argument block and their place in the code object, so plain calls launch exactly the kernels they always did.  The two
+// extra arguments follow `p`; the argument-line prefetch is left out (KPF: its safety is checked per instantiation).
+template <bool FULL, bool MULTI>
+__global__ __launch_bounds__(256) void iql_bwd_rw_kernel(const float* q_heads, const float* q_xb, const float* q_h1, const float* q_h0,
+                                                         const float* q_params, unsigned q_dims, unsigned q_ldB, unsigned q_mbc,
+                                                         unsigned q_rts, StepParams p, const float* rw_w, float* rw_td) {
+  constexpr bool BF16 = false;
+  constexpr bool KPF = false;
+  constexpr bool RW = true;
 #include "iqlhip_bwd_body.inc"
 }
 
@@ -906,6 +947,15 @@ __global__ __launch_bounds__(256) void iql_call_setup_weighted_kernel(unsigned l
                                                                       unsigned* drop_dst, int drop_words, unsigned drop_thresh,
                                                                       unsigned* arrivals, unsigned long long* ack,
                                                                       unsigned long long ack_val, WTab wt);
+// (and the weighted form that stages the rows' q and publishes the call's beta: iqlhip_isweight_kernels.h)
+__global__ __launch_bounds__(256) void iql_call_setup_weighted_is_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                                         iqlhip_step_scalars* sched_call,
+                                                                         const iqlhip_step_scalars* sched_src, int n_steps,
+                                                                         const float* rows, long long ld, float* xb, int B,
+                                                                         unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                                         unsigned* arrivals, unsigned long long* ack,
+                                                                         unsigned long long ack_val, WTab wt, float* q_dst,
+                                                                         float* beta_dev, float beta);
 
 // bf16 shadows rebuilt from the fp32 masters (start of every library call on the bf16 path: the caller owns the
 // masters and may have written them through its own tensors since the last update kernel ran).
@@ -1149,6 +1199,9 @@ template <bool BF16, bool FULL>
 __global__ __launch_bounds__(256) void iql_bwd_group_kernel(const GroupRec* __restrict__ recs) {
   constexpr bool MULTI = false;
   constexpr bool KPF = false;     // (arguments in a device record, not in the kernel-argument block)
+  constexpr bool RW = false;      // (per-row loss weights: solo steps only)
+  const float* const rw_w = nullptr;
+  float* const rw_td = nullptr;
   const GroupRec& r = recs[blockIdx.y];
   const float* q_heads = r.q_heads; const float* q_xb = r.q_xb; const float* q_h1 = r.q_h1; const float* q_h0 = r.q_h0;
   const float* q_params = r.q_params;

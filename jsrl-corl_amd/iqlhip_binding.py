@@ -97,6 +97,11 @@ SYMBOLS = [
     ("iqlhip_set_counters", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("iqlhip_debug_write_masks", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("iqlhip_step", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.c_void_p]),
+    ("iqlhip_step_rw", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("iqlhip_forward_backward_rw", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    ("iqlhip_draw_indices_weighted_is", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                  C.c_int64, C.c_float, C.c_void_p]),
     ("iqlhip_step_sync", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_step_begin", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.c_void_p]),
     ("iqlhip_step_wait", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_void_p]),
@@ -170,6 +175,11 @@ SYMBOLS = [
     ("iqlhip_draw_indices_weighted", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("iqlhip_train_steps_weighted", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                               C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("iqlhip_train_steps_weighted_is", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                 C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_float]),
+    ("iqlhip_train_steps_weighted_is_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
+                                                         C.c_void_p, C.c_void_p]),
     ("iqlhip_train_steps_weighted_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p,
                                                       C.c_void_p]),
     ("iqlhip_debug_read", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64,

@@ -441,14 +441,20 @@ class ReplayBuffer:
         with torch.cuda.device(self._rows.device):
             hb.check(hb.lib().iqlhip_weights_clear_flags(self._weights, self._stream()))
 
-    def draw_weighted_indices(self, n: int, seed: int, offset: int) -> torch.Tensor:
+    def draw_weighted_indices(self, n: int, seed: int, offset: int, is_beta=None, batch_size=None):
         """Indices 0 .. n - 1 of the weighted index stream (seed, offset) — the stream train_steps_weighted consumes — as
-        a device int64 tensor."""
+        a device int64 tensor.  With is_beta: (idx, c), c the float32 importance-sampling weights of the drawn rows,
+        (q_min / q_row) ** is_beta normalised per batch of batch_size consecutive indices (default: all n) — what
+        trainer.train(batch, loss_weights=c) takes."""
         import iqlhip_weighted as wtd
         wtd.check_call(self)
         if n < 1:
             raise ValueError("iqlhip: n must be at least 1")
         dev = self._rows.device
+        if is_beta is not None:
+            return wtd.draw_with_is(self._weights, dev, n, seed, offset, is_beta, batch_size, self._stream())
+        if batch_size is not None:
+            raise ValueError("iqlhip: batch_size only means something together with is_beta")
         idx = torch.empty(int(n), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             hb.check(hb.lib().iqlhip_draw_indices_weighted(idx.data_ptr(), int(n), self._weights,

@@ -49,6 +49,20 @@ except AttributeError:                                        # pragma: no cover
         return torch.cuda.current_stream(index).cuda_stream
 
 
+def check_loss_weights(loss_weights, B: int, device) -> torch.Tensor:
+    """train(batch, loss_weights=...): a float32 tensor of shape [B] or [B, 1] on the trainer's device -> contiguous [B].
+    Nothing is converted or moved silently: a wrong dtype, shape or device is the caller's mistake."""
+    if not isinstance(loss_weights, torch.Tensor):
+        raise TypeError(f"iqlhip: loss_weights must be a torch.Tensor, not {type(loss_weights).__name__}")
+    if loss_weights.dtype != torch.float32:
+        raise TypeError(f"iqlhip: loss_weights must be float32, not {loss_weights.dtype}")
+    if tuple(loss_weights.shape) not in ((B,), (B, 1)):
+        raise ValueError(f"iqlhip: loss_weights must have shape [{B}] or [{B}, 1], not {list(loss_weights.shape)}")
+    if loss_weights.device != torch.device(device):
+        raise ValueError(f"iqlhip: loss_weights live on {loss_weights.device}, the trainer on {device}")
+    return loss_weights.reshape(B).contiguous()
+
+
 def _mlp_tensors(module: nn.Module) -> Dict[str, nn.Parameter]:
     lin = linear_layers(module)
     if len(lin) != 3:
@@ -542,7 +556,7 @@ class ImplicitQLearning:
         return b, keep, B
 
     # ------------------------------------------------------------------ the step
-    def _run_step(self, b: "hb.Batch", B: int, sync: bool):
+    def _run_step(self, b: "hb.Batch", B: int, sync: bool, rw=None):
         self.total_it += 1
         for g in self._adam_t:
             self._adam_t[g] += 1
@@ -560,6 +574,15 @@ class ImplicitQLearning:
             # in-library exchange (RCCL all-reduce or direct peer reads) inside iqlhip_step
             self._fill_scalars(sc, self._adam_t, self._current_lrs(), dp.inv_batch(B, self._dp_world))
             hb.check(lib.iqlhip_step(self._ctx, C.byref(b), C.byref(sc), self._stream()))
+        elif rw is not None:
+            # per-row loss weights: the row-weighted backward (iqlhip_step_rw); refused before any counter has moved
+            self._fill_scalars(sc, self._adam_t, self._current_lrs(), 1.0 / B)
+            rc = lib.iqlhip_step_rw(self._ctx, C.byref(b), C.byref(sc), rw[0], rw[1], self._stream())
+            if rc:
+                self.total_it -= 1
+                for g in self._adam_t:
+                    self._adam_t[g] -= 1
+                hb.check(rc)
         else:
             self._fill_scalars(sc, self._adam_t, self._current_lrs(), 1.0 / B)
             hb.check(lib.iqlhip_step(self._ctx, C.byref(b), C.byref(sc), self._stream()))
@@ -573,10 +596,54 @@ class ImplicitQLearning:
             log.update(self._stats_entries())
         return log
 
-    def train(self, batch: TensorBatch) -> Dict[str, float]:
+    def _loss_weight_args(self, B: int, loss_weights, return_td: bool):
+        """(row-weight pointer, TD pointer or None, tensors to keep alive) of a weighted step, checked on the host."""
+        if self._dp_world > 1 or self._dp_exchange is not None:
+            raise NotImplementedError("iqlhip: per-row loss weights (loss_weights / return_td) are not supported under "
+                                      "data parallelism")
+        if getattr(self, "_precision", "f32") == "bf16":
+            raise NotImplementedError("iqlhip: per-row loss weights (loss_weights / return_td) are not supported at bf16 "
+                                      "precision: the row-weighted backward is an fp32 kernel")
+        if loss_weights is None:
+            ones = getattr(self, "_rw_ones", None)
+            if ones is None or ones.numel() < B:
+                ones = self._rw_ones = torch.ones(max(B, 256), dtype=torch.float32, device=self._dev)
+            w = ones
+        else:
+            w = check_loss_weights(loss_weights, B, self._dev)
+        td = None
+        if return_td:
+            td = torch.empty((B, 2), dtype=torch.float32, device=self._dev)
+        return w, td
+
+    def last_td_errors(self) -> torch.Tensor:
+        """[B, 2] float32 on the device: (q1 - y, q2 - y) of every row of the last train(..., return_td=True) step — the
+        pre-update values its loss used.  Valid until the trainer's next step."""
+        td = getattr(self, "_last_td", None)
+        if td is not None and getattr(self, "_last_td_it", None) != self.total_it:
+            td = self._last_td = None          # (a later step of any kind — train, train_steps*, online_step* — has run)
+        if td is None:
+            raise RuntimeError("iqlhip: no TD errors: the trainer's last step was not a train(..., return_td=True)")
+        return td
+
+    def train(self, batch: TensorBatch, loss_weights=None, return_td: bool = False) -> Dict[str, float]:
         """One IQL gradient step (iql.py:542-563).  Returns the three losses as floats
-        (one host sync instead of the reference's three .item() calls)."""
+        (one host sync instead of the reference's three .item() calls).
+
+        loss_weights ([B] or [B, 1] float32 on the trainer's device): every row's loss terms are multiplied by its
+        weight — the importance-sampling correction of a weighted draw (buffer.draw_weighted_indices(..., is_beta=...)
+        returns such weights); the returned losses are the weighted ones.  return_td: the rows' TD errors are kept for
+        last_td_errors() (without loss_weights the weights are ones).  fp32 only, no data parallelism."""
         self._require_gpu()
+        if loss_weights is not None or return_td:
+            self._last_td = None
+            b, keep, B = self._batch_struct(batch)
+            w, td = self._loss_weight_args(B, loss_weights, return_td)
+            self._prepare(B)
+            log = self._run_step(b, B, sync=True, rw=(w.data_ptr(), None if td is None else td.data_ptr()))
+            self._last_td, self._last_td_it = td, self.total_it
+            del keep, w
+            return log
         fast = self._fresh_block_batch(batch)
         if fast is not None:
             return self._train_fresh_block(*fast)
@@ -926,19 +993,33 @@ class ImplicitQLearning:
                           STATS_BF16_MAX_ROWS)
         return n, table, gen
 
-    def prepare_train_steps_weighted(self, replay_buffer, batch_size: int, weights=None) -> None:
+    def _is_beta_arg(self, is_beta) -> float:
+        """train_steps_weighted(..., is_beta=...): a finite float >= 0; fp32 only (the row-weighted backward is)."""
+        import iqlhip_weighted as wtd
+        beta, _ = wtd.check_is_args(1, is_beta, None)
+        if getattr(self, "_precision", "f32") == "bf16":
+            raise NotImplementedError("iqlhip: is_beta (per-row loss weights) is not supported at bf16 precision: the "
+                                      "row-weighted backward is an fp32 kernel")
+        return beta
+
+    def prepare_train_steps_weighted(self, replay_buffer, batch_size: int, weights=None, is_beta=None) -> None:
         """prepare_train_steps for the chunk graphs train_steps_weighted replays on this buffer and its current weights
-        (weights: a SampleWeights used instead of them)."""
+        (weights: a SampleWeights used instead of them).  is_beta not None (any valid value): the graphs of calls with
+        is_beta, which are a kind of their own."""
         _, table, _ = self._weighted_args(replay_buffer, batch_size, weights)
+        if is_beta is not None:
+            self._is_beta_arg(is_beta)
         self._prepare(batch_size)
         self._refuse_injected_masks()
-        hb.check(hb.lib().iqlhip_train_steps_weighted_prepare(
+        fn = hb.lib().iqlhip_train_steps_weighted_prepare if is_beta is None else hb.lib().iqlhip_train_steps_weighted_is_prepare
+        hb.check(fn(
             self._ctx, replay_buffer._rows.data_ptr(), replay_buffer._ld, batch_size, 1.0 / batch_size, self._stream(),
             table))
         self._ts_token = None
 
     def train_steps_weighted(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0,
-                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False, weights=None):
+                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False, weights=None,
+                             is_beta=None):
         """train_steps with every row drawn by the buffer's sample weights (ReplayBuffer.set_sample_weights) instead of
         uniformly: advantage-, return- or TD-error-weighted resampling without a host draw per iteration.  The index
         stream is train_steps' own (Philox keyed by (seed, total_it)); only the mapping of its 64 random bits to a row
@@ -946,7 +1027,12 @@ class ImplicitQLearning:
         call, bit for bit.  The idle blocks of each step's forward draw and gather the next step's rows.  Returns what
         train_steps returns.  ValueError if the buffer has no weights or its index bound has changed since they were
         set; NotImplementedError under data parallelism, for bf16 batches of more than 512 rows and with injected
-        dropout masks pending.  No priority exponent and no importance-sampling correction of the loss.
+        dropout masks pending.  No priority exponent; without is_beta no importance-sampling correction of the loss.
+        is_beta (None: today's call; else a float >= 0, annealed by the caller from call to call): every step's loss
+        terms are weighted by c = (q_min / q_row) ** is_beta over that step's batch — bit for bit the eager loop
+        draw_weighted_indices(B, ..., is_beta=is_beta) -> gather -> train(batch, loss_weights=c); the returned losses are
+        the weighted ones.  Another is_beta on the next call neither re-captures a chunk nor ends a continuation.  fp32
+        only (NotImplementedError at bf16 precision).
         weights: None, or an iqlhip_weighted.SampleWeights to draw by instead of the buffer's own table (its n must equal
         the buffer's index bound: ValueError otherwise); a continuation then keys on that object's generation.
         An updatable table (set_sample_weights(..., updatable=True), SampleWeights(..., updatable=True)) is taken like a
@@ -955,6 +1041,7 @@ class ImplicitQLearning:
         if return_stats and not self._step_stats:
             raise ValueError("iqlhip: train_steps_weighted(return_stats=True) needs set_step_stats(True) first")
         size, table, gen = self._weighted_args(replay_buffer, batch_size, weights)
+        beta = None if is_beta is None else self._is_beta_arg(is_beta)
         self._prepare(batch_size)
         self._refuse_injected_masks()
         inv_batch = 1.0 / batch_size
@@ -970,11 +1057,17 @@ class ImplicitQLearning:
             k = min(chunk, n_steps - done)
             tab = self._scalar_table(k, inv_batch)
             # (train_steps' token plus the table's generation: a plain call's token never equals it, nor the reverse;
-            #  the library checks the generation too)
-            tok = (weakref.ref(replay_buffer), replay_buffer._writes, replay_buffer._rows._version, "weighted", gen)
+            #  the library checks the generation too;
+            #  a call with is_beta continues only such a call — its value is not part of the token)
+            tok = (weakref.ref(replay_buffer), replay_buffer._writes, replay_buffer._rows._version,
+                   "weighted" if beta is None else "weighted_is", gen)
             flags = hb.TS_CONTINUE if self._ts_token == tok else 0
-            rc = lib.iqlhip_train_steps_weighted(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed,
-                                                 self.total_it * half, flags, stream, table)
+            if beta is None:
+                rc = lib.iqlhip_train_steps_weighted(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed,
+                                                     self.total_it * half, flags, stream, table)
+            else:
+                rc = lib.iqlhip_train_steps_weighted_is(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k,
+                                                        seed, self.total_it * half, flags, stream, table, beta)
             if rc:
                 self._ts_token = None
                 hb.check(rc)
@@ -1533,14 +1626,20 @@ class ImplicitQLearning:
         hb.check(hb.lib().iqlhip_debug_read(self._ctx, name.encode(), buf, cap, C.byref(n), self._stream()))
         return np.frombuffer(buf, dtype=np.float32)[: n.value].copy()
 
-    def flat_gradient(self, batch: TensorBatch) -> np.ndarray:
-        """Forward+backward only; returns the flat gradient (+4 tail words) as numpy (tests)."""
+    def flat_gradient(self, batch: TensorBatch, loss_weights=None) -> np.ndarray:
+        """Forward+backward only; returns the flat gradient (+4 tail words) as numpy (tests).  loss_weights: train()'s."""
         b, keep, B = self._batch_struct(batch)
         self._prepare(B)
         sc = hb.StepScalars()
         t1 = {g: max(1, v) for g, v in self._adam_t.items()}
         self._fill_scalars(sc, t1, self._current_lrs(), dp.inv_batch(B, self._dp_world))
         flat = self._dp_flat()
+        if loss_weights is not None:
+            w, _ = self._loss_weight_args(B, loss_weights, False)
+            hb.check(hb.lib().iqlhip_forward_backward_rw(self._ctx, C.byref(b), C.byref(sc), w.data_ptr(), None, flat.data_ptr(),
+                                                         self._stream()))
+            torch.cuda.synchronize(self._dev)
+            return flat.cpu().numpy()
         hb.check(hb.lib().iqlhip_forward_backward(self._ctx, C.byref(b), C.byref(sc), flat.data_ptr(), self._stream()))
         torch.cuda.synchronize(self._dev)
         return flat.cpu().numpy()

@@ -287,21 +287,58 @@ class SampleWeights:
         except Exception:
             pass
 
-    def draw_indices(self, n: int, seed: int, offset: int):
+    def draw_indices(self, n: int, seed: int, offset: int, is_beta=None, batch_size=None):
         """Indices 0 .. n - 1 of the weighted index stream (seed, offset) as a device int64 tensor
-        (ReplayBuffer.draw_weighted_indices for this table)."""
+        (ReplayBuffer.draw_weighted_indices for this table).  With is_beta: (idx, c), see draw_with_is."""
         import torch
         import iqlhip_binding as hb
         if self._table is None:
             raise ValueError("iqlhip: the sample weights have been freed")
         if n < 1:
             raise ValueError("iqlhip: n must be at least 1")
+        if is_beta is not None:
+            return draw_with_is(self._table, self._device, n, seed, offset, is_beta, batch_size,
+                                torch.cuda.current_stream(self._device).cuda_stream)
+        if batch_size is not None:
+            raise ValueError("iqlhip: batch_size only means something together with is_beta")
         idx = torch.empty(int(n), dtype=torch.int64, device=self._device)
         with torch.cuda.device(self._device):
             hb.check(hb.lib().iqlhip_draw_indices_weighted(idx.data_ptr(), int(n), self._table,
                                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
                                                            torch.cuda.current_stream(self._device).cuda_stream))
         return idx
+
+
+def check_is_args(n: int, is_beta, batch_size) -> tuple:
+    """(is_beta, batch_size) of a draw with importance-sampling weights, checked on the host: is_beta a finite float
+    >= 0, batch_size (default: all n indices are one batch) an integer in [1, n]."""
+    import math
+    try:
+        beta = float(is_beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"iqlhip: is_beta must be a number, not {type(is_beta).__name__}")
+    if not math.isfinite(beta) or beta < 0.0:
+        raise ValueError(f"iqlhip: is_beta must be finite and >= 0 (got {is_beta})")
+    bs = int(n) if batch_size is None else int(batch_size)
+    if bs < 1 or bs > int(n):
+        raise ValueError(f"iqlhip: batch_size {batch_size} outside [1, n={n}]")
+    return beta, bs
+
+
+def draw_with_is(table, device, n: int, seed: int, offset: int, is_beta, batch_size, stream):
+    """(idx, c): the indices of the weighted stream and the importance-sampling weights of the drawn rows,
+    c = (q_min / q_row) ** is_beta with q_min the smallest quantised weight among the batch_size consecutive indices of the
+    row's batch — float32 on the device, in (0, 1], what trainer.train(batch, loss_weights=c) takes."""
+    import torch
+    import iqlhip_binding as hb
+    beta, bs = check_is_args(n, is_beta, batch_size)
+    idx = torch.empty(int(n), dtype=torch.int64, device=device)
+    c = torch.empty(int(n), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        hb.check(hb.lib().iqlhip_draw_indices_weighted_is(idx.data_ptr(), c.data_ptr(), int(n), table,
+                                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                                          bs, beta, stream))
+    return idx, c
 
 
 def check_table(buffer, weights, member=None) -> int:
