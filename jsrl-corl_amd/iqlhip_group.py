@@ -87,6 +87,10 @@ from iqlhip_trainer import K_MAX, ImplicitQLearning
 BF16_MAX_ROWS = 512      # bf16 batches beyond this run the large-batch kernels, which have no group form
 
 
+def _addr(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data
+
+
 class ImplicitQLearningGroup:
     _mixed_batch = False      # (the option's default: online_step / train_steps read it before they look at a member)
 
@@ -262,46 +266,48 @@ class ImplicitQLearningGroup:
         return self._commit_step(adam_next, out)
 
     # ------------------------------------------------------------------ device-drawn steps
-    def train_steps(self, buffers, n_steps: int, batch_size, seeds: Sequence[int],
-                    return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
-        """n_steps `sample -> train` iterations per member (ImplicitQLearning.train_steps for each): member k draws its
-        rows from buffers[k] (or the one shared buffer) under seeds[k] — exactly the rows its own train_steps(buffer,
-        n_steps, batch_size, seed=seeds[k]) would draw.  batch_size: an int, or one int per member (unequal sizes:
-        mixed_batch groups only; member k then draws what its train_steps at batch_size[k] would).  Returns losses
-        [K, n_steps, 3] when return_losses, else None.  return_stats: returns the per-step statistics [n_steps, K, 16]
-        instead (hb.STAT_NAMES order; the rows of members that have not called set_step_stats(True) are NaN;
-        ValueError when no member has)."""
+    def _burst_args(self, buffers, seeds, n_steps: int):
+        """What every burst checks first: (K buffers — a list of K or the one shared buffer; None for a replay-mix call,
+        whose buffers _replay_mix_args takes — and K integer seeds), n_steps >= 1."""
         K = len(self.trainers)
-        bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
         seeds = [int(s) for s in seeds]
-        if len(bufs) != K or len(seeds) != K:
-            raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer) and {K} seeds")
+        if buffers is None:
+            bufs = None
+            if len(seeds) != K:
+                raise ValueError(f"iqlhip: a group of {K} needs {K} seeds")
+        else:
+            bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
+            if len(bufs) != K or len(seeds) != K:
+                raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer) and {K} seeds")
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
-        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
-        self._check_members()
-        for B in Bs:
-            self._check_batch_size(B)
-        if return_stats and not any(t._step_stats for t in self.trainers):
-            raise ValueError("iqlhip: train_steps(return_stats=True) needs set_step_stats(True) on at least one member")
-        if K == 1:      # a group of one IS the solo call (chunk graphs, rows staged by idle forward blocks: faster)
-            out = self.trainers[0].train_steps(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
-                                               chunk=chunk, return_stats=return_stats)
-            if return_stats:
-                return out[1][:, None]
-            return None if out is None else out[None]
-        sizes, inv = [], []
-        for t, buf, B in zip(self.trainers, bufs, Bs):
-            size, ib = t._train_steps_args(buf, B)
-            sizes.append(size)
-            inv.append(ib)
-        if len({b._ld for b in bufs}) != 1:
-            raise ValueError("iqlhip: the members' buffers have different row strides")
+        return bufs, seeds
+
+    @staticmethod
+    def _solo_burst_result(out, return_stats: bool):
+        """What a group of one returns for its member's solo burst `out`: statistics [n, 16] as [n, 1, 16], losses
+        [n, 3] as [1, n, 3]."""
+        if return_stats:
+            return out[1][:, None]
+        return None if out is None else out[None]
+
+    def _members_steps_args(self, bufs, Bs):
+        """Every member's train_steps checks on its buffer; returns (index bounds, 1 / batch rows), each a list of K."""
+        pairs = [t._train_steps_args(buf, B) for t, buf, B in zip(self.trainers, bufs, Bs)]
+        return [size for size, _ in pairs], [ib for _, ib in pairs]
+
+    def _run_burst(self, n_steps: int, Bs, inv, seeds, chunk: int, return_losses: bool, return_stats: bool, call):
+        """The multi-step loop behind train_steps, train_steps_weighted and train_steps_replay_mix, whose checks have
+        all passed: n_steps in library calls of at most `chunk` steps.  Bs, inv, seeds: every member's batch size, one
+        over it and seed.  call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream) makes the kind's one library call for the
+        next k steps — tab_ptrs the members' scalar tables, offs their places in their Philox streams — and returns
+        its code.  A group call never continues staged rows and leaves none: every member's token is dropped, also by
+        a call that fails.  Returns the statistics [n_steps, K, 16] when return_stats, else losses [K, n_steps, 3]
+        (None unless return_losses)."""
+        K = len(self.trainers)
         chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
         lib, stream = hb.lib(), self.trainers[0]._stream()
         g = self._group()
-        rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
-        size_arr = (C.c_int64 * K)(*sizes)
         seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
         B_arr = (C.c_int32 * K)(*Bs)
         halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
@@ -313,12 +319,7 @@ class ImplicitQLearningGroup:
             offs = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
             tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
             tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
-            if self._mixed_batch:
-                rc = lib.iqlhip_group_train_steps_mixed(g, rows, bufs[0]._ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs,
-                                                        0, stream)
-            else:
-                rc = lib.iqlhip_group_train_steps(g, rows, bufs[0]._ld, size_arr, Bs[0], tab_ptrs, k, seed_arr, offs, 0,
-                                                  stream)
+            rc = call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream)
             for t in self.trainers:
                 t._ts_token = None
             hb.check(rc)
@@ -332,6 +333,41 @@ class ImplicitQLearningGroup:
                 stats[done:done + k] = self._group_stats(k)
             done += k
         return stats if return_stats else losses
+
+    def train_steps(self, buffers, n_steps: int, batch_size, seeds: Sequence[int],
+                    return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
+        """n_steps `sample -> train` iterations per member (ImplicitQLearning.train_steps for each): member k draws its
+        rows from buffers[k] (or the one shared buffer) under seeds[k] — exactly the rows its own train_steps(buffer,
+        n_steps, batch_size, seed=seeds[k]) would draw.  batch_size: an int, or one int per member (unequal sizes:
+        mixed_batch groups only; member k then draws what its train_steps at batch_size[k] would).  Returns losses
+        [K, n_steps, 3] when return_losses, else None.  return_stats: returns the per-step statistics [n_steps, K, 16]
+        instead (hb.STAT_NAMES order; the rows of members that have not called set_step_stats(True) are NaN;
+        ValueError when no member has)."""
+        K = len(self.trainers)
+        bufs, seeds = self._burst_args(buffers, seeds, n_steps)
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
+        self._check_members()
+        for B in Bs:
+            self._check_batch_size(B)
+        if return_stats and not any(t._step_stats for t in self.trainers):
+            raise ValueError("iqlhip: train_steps(return_stats=True) needs set_step_stats(True) on at least one member")
+        if K == 1:      # a group of one IS the solo call (chunk graphs, rows staged by idle forward blocks: faster)
+            return self._solo_burst_result(
+                self.trainers[0].train_steps(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
+                                             chunk=chunk, return_stats=return_stats), return_stats)
+        sizes, inv = self._members_steps_args(bufs, Bs)
+        if len({b._ld for b in bufs}) != 1:
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        lib, ld = hb.lib(), bufs[0]._ld
+        rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
+        size_arr = (C.c_int64 * K)(*sizes)
+
+        def call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream):
+            if self._mixed_batch:
+                return lib.iqlhip_group_train_steps_mixed(g, rows, ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, 0,
+                                                          stream)
+            return lib.iqlhip_group_train_steps(g, rows, ld, size_arr, Bs[0], tab_ptrs, k, seed_arr, offs, 0, stream)
+        return self._run_burst(n_steps, Bs, inv, seeds, chunk, return_losses, return_stats, call)
 
     # ------------------------------------------------------------------ device-drawn steps, rows drawn by weight
     def train_steps_weighted(self, buffers, n_steps: int, batch_size, seeds: Sequence[int], weights=None,
@@ -348,12 +384,7 @@ class ImplicitQLearningGroup:
         train_steps_weighted's."""
         import iqlhip_weighted as wtd
         K = len(self.trainers)
-        bufs = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers] * K
-        seeds = [int(s) for s in seeds]
-        if len(bufs) != K or len(seeds) != K:
-            raise ValueError(f"iqlhip: a group of {K} needs {K} buffers (or one shared buffer) and {K} seeds")
-        if n_steps < 1:
-            raise ValueError("n_steps must be >= 1")
+        bufs, seeds = self._burst_args(buffers, seeds, n_steps)
         Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
         self._check_members()
         for B in Bs:
@@ -376,14 +407,8 @@ class ImplicitQLearningGroup:
                 out = t.train_steps_weighted(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
                                              chunk=chunk, return_stats=return_stats,
                                              weights=None if e is bufs[0] else e)
-            if return_stats:
-                return out[1][:, None]
-            return None if out is None else out[None]
-        sizes, inv = [], []
-        for t, buf, B in zip(self.trainers, bufs, Bs):
-            size, ib = t._train_steps_args(buf, B)
-            sizes.append(size)
-            inv.append(ib)
+            return self._solo_burst_result(out, return_stats)
+        sizes, inv = self._members_steps_args(bufs, Bs)
         # (an updatable table spans a capacity, and that is the size its member's draw is given: rows beyond the index
         #  bound weigh 0)
         for i, e in enumerate(entries):
@@ -394,42 +419,65 @@ class ImplicitQLearningGroup:
                 sizes[i] = e.sample_weights_n
         if len({b._ld for b in bufs}) != 1:
             raise ValueError("iqlhip: the members' buffers have different row strides")
-        chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
-        lib, stream = hb.lib(), self.trainers[0]._stream()
-        g = self._group()
+        fn, ld = hb.lib().iqlhip_group_train_steps_weighted, bufs[0]._ld
         rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
         size_arr = (C.c_int64 * K)(*sizes)
-        seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
-        B_arr = (C.c_int32 * K)(*Bs)
         # (member k's table: its buffer's own, its SampleWeights', or NULL — the uniform draw)
         wt_arr = (C.c_void_p * K)(*[None if e is None else (e._table if isinstance(e, wtd.SampleWeights) else e._weights)
                                     for e in entries])
-        halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
-        losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
-        stats = np.empty((n_steps, K, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
-        done = 0
-        while done < n_steps:
-            k = min(chunk, n_steps - done)
-            offs = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
-            tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
-            tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
-            rc = lib.iqlhip_group_train_steps_weighted(g, rows, bufs[0]._ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, 0,
-                                                       stream, wt_arr)
-            for t in self.trainers:
-                t._ts_token = None
-            hb.check(rc)
-            for t in self.trainers:
-                t.total_it += k
-            if return_losses:
-                out = (C.c_float * (K * k * 3))()
-                hb.check(lib.iqlhip_group_read_losses(g, out, k, stream))
-                losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
-            if return_stats:
-                stats[done:done + k] = self._group_stats(k)
-            done += k
-        return stats if return_stats else losses
+
+        def call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream):
+            return fn(g, rows, ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, 0, stream, wt_arr)
+        return self._run_burst(n_steps, Bs, inv, seeds, chunk, return_losses, return_stats, call)
 
     # ------------------------------------------------------------------ the online loop
+    def _online_rows(self, ld: int, states, actions, rewards, next_states, dones, act_next):
+        """The host side of an online call's arguments: the K transitions as packed rows [K, ld]; the members that ask
+        for their next action; and the act_next arrays in the library's argument order — (states in, member mask,
+        max_action, sampling seeds, actions out), all None when no member asks."""
+        K, t0 = len(self.trainers), self.trainers[0]
+        S, A = t0._S, t0._A
+        rows = np.zeros((K, ld), dtype=np.float32)
+        for k in range(K):
+            rows[k, :S] = np.asarray(states[k], dtype=np.float32).reshape(-1)
+            rows[k, S: S + A] = np.asarray(actions[k], dtype=np.float32).reshape(-1)
+            rows[k, S + A: 2 * S + A] = np.asarray(next_states[k], dtype=np.float32).reshape(-1)
+            rows[k, 2 * S + A] = np.float32(rewards[k])
+            rows[k, 2 * S + A + 1] = np.float32(dones[k])
+        want = [k for k in range(K) if act_next is not None and act_next[k] is not None]
+        a_in = a_out = mask = max_a = seeds = None
+        if want:
+            a_in = np.zeros((K, S), dtype=np.float32)
+            for k in want:
+                a_in[k] = np.asarray(act_next[k], dtype=np.float32).reshape(-1)
+            a_out = np.zeros((K, A), dtype=np.float32)
+            mask = np.array([k in want for k in range(K)], dtype=np.int32)
+            max_a = np.array([float(t.actor.max_action) for t in self.trainers], dtype=np.float32)
+            seeds = np.array([t._act_seed() if (t.actor.training and t._gaussian) else 0 for t in self.trainers],
+                             dtype=np.uint64)
+        return rows, want, (a_in, mask, max_a, seeds, a_out)
+
+    def _online_commit(self, bufs, pointers, new_sizes, adam_next, out, act_next, want, a_out):
+        """Behind an online call that succeeded: every ring past its insert, every member past its step.  Returns the
+        logs, or (logs, actions) when the call took act_next."""
+        for k, buf in enumerate(bufs):
+            buf._writes += 1
+            buf._pointer = (pointers[k] + 1) % buf._buffer_size
+            buf._size = new_sizes[k]
+        logs = self._commit_step(adam_next, out)
+        if act_next is None:
+            return logs
+        return logs, [a_out[k].copy() if k in want else None for k in range(len(bufs))]
+
+    @staticmethod
+    def _solo_online_result(res, act_next):
+        """What a group of one returns for its member's solo online call `res`, made with act_next[0]."""
+        if act_next is None:
+            return [res]
+        if act_next[0] is None:
+            return [res], [None]
+        return [res[0]], [res[1]]
+
     def online_step(self, buffers, states, actions, rewards, next_states, dones, batch_size,
                     act_next: Optional[Sequence] = None, rngs: Optional[Sequence[np.random.RandomState]] = None):
         """One iteration of the online loop for every member in ONE library call (ImplicitQLearning.online_step for
@@ -460,15 +508,9 @@ class ImplicitQLearningGroup:
         if act_next is not None:         # (before any ring, counter or parameter moves)
             self._check_eval_forward([k for k in range(K) if act_next[k] is not None], "online_step(act_next=...)")
         if K == 1 and rngs is None:      # a group of one IS the solo call
-            tr = self.trainers[0]
-            an = None if act_next is None else act_next[0]
-            res = tr.online_step(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], Bs[0],
-                                 act_next=an)
-            if act_next is None:
-                return [res]
-            if an is None:
-                return [res], [None]
-            return [res[0]], [res[1]]
+            return self._solo_online_result(
+                self.trainers[0].online_step(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], Bs[0],
+                                             act_next=None if act_next is None else act_next[0]), act_next)
         from iqlhip_replay import ReplayBuffer
         for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
             t._prepare(Bs[i])
@@ -483,26 +525,7 @@ class ImplicitQLearningGroup:
         ld = bufs[0]._ld
         if any(b._ld != ld for b in bufs):
             raise ValueError("iqlhip: the members' buffers have different row strides")
-        t0 = self.trainers[0]
-        S, A = t0._S, t0._A
-        rows = np.zeros((K, ld), dtype=np.float32)
-        for k in range(K):
-            rows[k, :S] = np.asarray(states[k], dtype=np.float32).reshape(-1)
-            rows[k, S: S + A] = np.asarray(actions[k], dtype=np.float32).reshape(-1)
-            rows[k, S + A: 2 * S + A] = np.asarray(next_states[k], dtype=np.float32).reshape(-1)
-            rows[k, 2 * S + A] = np.float32(rewards[k])
-            rows[k, 2 * S + A + 1] = np.float32(dones[k])
-        want = [k for k in range(K) if act_next is not None and act_next[k] is not None]
-        a_in = a_out = mask = max_a = seeds = None
-        if want:
-            a_in = np.zeros((K, S), dtype=np.float32)
-            for k in want:
-                a_in[k] = np.asarray(act_next[k], dtype=np.float32).reshape(-1)
-            a_out = np.zeros((K, A), dtype=np.float32)
-            mask = np.array([k in want for k in range(K)], dtype=np.int32)
-            max_a = np.array([float(t.actor.max_action) for t in self.trainers], dtype=np.float32)
-            seeds = np.array([t._act_seed() if (t.actor.training and t._gaussian) else 0 for t in self.trainers],
-                             dtype=np.uint64)
+        rows, want, act = self._online_rows(ld, states, actions, rewards, next_states, dones, act_next)
         # (the buffers' and the trainers' counters move only once the library call has succeeded)
         pointers = [b._pointer for b in bufs]
         new_sizes = [min(b._size + 1, b._buffer_size) for b in bufs]
@@ -516,28 +539,15 @@ class ImplicitQLearningGroup:
         ring_ptrs = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
         caps = (C.c_int64 * K)(*[b._buffer_size for b in bufs])
         ptrs = (C.c_int64 * K)(*pointers)
-
-        def addr(a):
-            return None if a is None else a.ctypes.data
-
-        g = self._group()
+        g, stream = self._group(), self.trainers[0]._stream()
         if self._mixed_batch:
             rc = hb.lib().iqlhip_group_online_step_mixed(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
-                                                         (C.c_int32 * K)(*Bs), scs, out, addr(a_in), addr(mask),
-                                                         addr(max_a), addr(seeds), addr(a_out), t0._stream())
+                                                         (C.c_int32 * K)(*Bs), scs, out, *map(_addr, act), stream)
         else:
             rc = hb.lib().iqlhip_group_online_step(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
-                                                   Bs[0], scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds),
-                                                   addr(a_out), t0._stream())
+                                                   Bs[0], scs, out, *map(_addr, act), stream)
         hb.check(rc)
-        for k, buf in enumerate(bufs):
-            buf._writes += 1
-            buf._pointer = (pointers[k] + 1) % buf._buffer_size
-            buf._size = new_sizes[k]
-        logs = self._commit_step(adam_next, out)
-        if act_next is None:
-            return logs
-        return logs, [a_out[k].copy() if k in want else None for k in range(K)]
+        return self._online_commit(bufs, pointers, new_sizes, adam_next, out, act_next, want, act[4])
 
     # ------------------------------------------------------------------ batches mixed from an offline and an online buffer
     def _replay_mix_args(self, offline_buffers, online_buffers, batch_size, mixing_ratio, burst: bool):
@@ -606,38 +616,15 @@ class ImplicitQLearningGroup:
             self._check_eval_forward([k for k in range(K) if act_next[k] is not None],
                                      "online_step_replay_mix(act_next=...)")
         if K == 1 and rngs is None:      # a group of one IS the solo call
-            an = None if act_next is None else act_next[0]
-            res = self.trainers[0].online_step_mixed(offs[0], ons[0], states[0], actions[0], rewards[0], next_states[0],
-                                                     dones[0], Bs[0], mixing_ratio if np.isscalar(mixing_ratio)
-                                                     else mixing_ratio[0], act_next=an)
-            if act_next is None:
-                return [res]
-            if an is None:
-                return [res], [None]
-            return [res[0]], [res[1]]
+            return self._solo_online_result(
+                self.trainers[0].online_step_mixed(offs[0], ons[0], states[0], actions[0], rewards[0], next_states[0],
+                                                   dones[0], Bs[0], mixing_ratio if np.isscalar(mixing_ratio)
+                                                   else mixing_ratio[0], act_next=None if act_next is None else act_next[0]),
+                act_next)
         for t, B in zip(self.trainers, Bs):
             t._prepare(B)
         ld = ons[0]._ld
-        t0 = self.trainers[0]
-        S, A = t0._S, t0._A
-        rows = np.zeros((K, ld), dtype=np.float32)
-        for k in range(K):
-            rows[k, :S] = np.asarray(states[k], dtype=np.float32).reshape(-1)
-            rows[k, S: S + A] = np.asarray(actions[k], dtype=np.float32).reshape(-1)
-            rows[k, S + A: 2 * S + A] = np.asarray(next_states[k], dtype=np.float32).reshape(-1)
-            rows[k, 2 * S + A] = np.float32(rewards[k])
-            rows[k, 2 * S + A + 1] = np.float32(dones[k])
-        want = [k for k in range(K) if act_next is not None and act_next[k] is not None]
-        a_in = a_out = mask = max_a = seeds = None
-        if want:
-            a_in = np.zeros((K, S), dtype=np.float32)
-            for k in want:
-                a_in[k] = np.asarray(act_next[k], dtype=np.float32).reshape(-1)
-            a_out = np.zeros((K, A), dtype=np.float32)
-            mask = np.array([k in want for k in range(K)], dtype=np.int32)
-            max_a = np.array([float(t.actor.max_action) for t in self.trainers], dtype=np.float32)
-            seeds = np.array([t._act_seed() if (t.actor.training and t._gaussian) else 0 for t in self.trainers],
-                             dtype=np.uint64)
+        rows, want, act = self._online_rows(ld, states, actions, rewards, next_states, dones, act_next)
         # (the buffers' and the trainers' counters move only once the library call has succeeded)
         pointers = [b._pointer for b in ons]
         new_sizes = [min(b._size + 1, b._buffer_size) for b in ons]
@@ -651,25 +638,14 @@ class ImplicitQLearningGroup:
         idx = np.ascontiguousarray(np.concatenate(idx), dtype=np.int64)
         scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
         out = (C.c_float * (3 * K))()
-
-        def addr(a):
-            return None if a is None else a.ctypes.data
-
         rc = hb.lib().iqlhip_group_online_step_replay2(
             self._group(), (C.c_void_p * K)(*[b._rows.data_ptr() for b in ons]), ld,
             (C.c_int64 * K)(*[b._buffer_size for b in ons]), (C.c_int64 * K)(*pointers), rows.ctypes.data, idx.ctypes.data,
-            (C.c_int32 * K)(*Bs), scs, out, addr(a_in), addr(mask), addr(max_a), addr(seeds), addr(a_out), t0._stream(),
+            (C.c_int32 * K)(*Bs), scs, out, *map(_addr, act), self.trainers[0]._stream(),
             (C.c_void_p * K)(*[b._rows.data_ptr() for b in offs]), (C.c_int64 * K)(*[b._size for b in offs]),
             (C.c_int32 * K)(*n_offs))
         hb.check(rc)
-        for k, buf in enumerate(ons):
-            buf._writes += 1
-            buf._pointer = (pointers[k] + 1) % buf._buffer_size
-            buf._size = new_sizes[k]
-        logs = self._commit_step(adam_next, out)
-        if act_next is None:
-            return logs
-        return logs, [a_out[k].copy() if k in want else None for k in range(K)]
+        return self._online_commit(ons, pointers, new_sizes, adam_next, out, act_next, want, act[4])
 
     def train_steps_replay_mix(self, offline_buffers, online_buffers, n_steps: int, batch_size, seeds: Sequence[int],
                                mixing_ratio=0.5, return_losses: bool = True, chunk: int = K_MAX,
@@ -680,60 +656,30 @@ class ImplicitQLearningGroup:
         online_step_replay_mix (the online buffers are only read here, but must hold rows); returns what train_steps
         returns.  As the solo call, a burst neither continues nor leaves staged rows."""
         K = len(self.trainers)
-        seeds = [int(s) for s in seeds]
-        if len(seeds) != K:
-            raise ValueError(f"iqlhip: a group of {K} needs {K} seeds")
-        if n_steps < 1:
-            raise ValueError("n_steps must be >= 1")
+        _, seeds = self._burst_args(None, seeds, n_steps)
         offs, ons, Bs, n_offs = self._replay_mix_args(offline_buffers, online_buffers, batch_size, mixing_ratio, burst=True)
         if return_stats and not any(t._step_stats for t in self.trainers):
             raise ValueError("iqlhip: train_steps_replay_mix(return_stats=True) needs set_step_stats(True) on at least one "
                              "member")
         if K == 1:      # a group of one IS the solo call
-            out = self.trainers[0].train_steps_mixed(offs[0], ons[0], n_steps, Bs[0], mixing_ratio if np.isscalar(mixing_ratio)
-                                                     else mixing_ratio[0], seed=seeds[0], return_losses=return_losses,
-                                                     chunk=chunk, return_stats=return_stats)
-            if return_stats:
-                return out[1][:, None]
-            return None if out is None else out[None]
+            return self._solo_burst_result(
+                self.trainers[0].train_steps_mixed(offs[0], ons[0], n_steps, Bs[0], mixing_ratio if np.isscalar(mixing_ratio)
+                                                   else mixing_ratio[0], seed=seeds[0], return_losses=return_losses,
+                                                   chunk=chunk, return_stats=return_stats), return_stats)
         for t, B in zip(self.trainers, Bs):
             t._prepare(B)
         for t in self.trainers:
             t._refuse_injected_masks()
-        inv = [1.0 / B for B in Bs]
-        chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
-        lib, stream = hb.lib(), self.trainers[0]._stream()
-        g = self._group()
+        fn, ld = hb.lib().iqlhip_group_train_steps_replay2, offs[0]._ld
         rows_off = (C.c_void_p * K)(*[b._rows.data_ptr() for b in offs])
         size_off = (C.c_int64 * K)(*[b._size for b in offs])
         rows_on = (C.c_void_p * K)(*[b._rows.data_ptr() for b in ons])
         size_on = (C.c_int64 * K)(*[b._size for b in ons])
-        seed_arr = (C.c_uint64 * K)(*[s & 0xFFFFFFFFFFFFFFFF for s in seeds])
-        B_arr, n_off_arr = (C.c_int32 * K)(*Bs), (C.c_int32 * K)(*n_offs)
-        halves = [(B + 1) // 2 for B in Bs]      # (Philox counters a step's draw of B indices consumes)
-        losses = np.empty((K, n_steps, 3), dtype=np.float32) if return_losses else None
-        stats = np.empty((n_steps, K, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
-        done = 0
-        while done < n_steps:
-            k = min(chunk, n_steps - done)
-            offsets = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
-            tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
-            tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
-            rc = lib.iqlhip_group_train_steps_replay2(g, rows_off, size_off, rows_on, size_on, offs[0]._ld, B_arr, n_off_arr,
-                                                      tab_ptrs, k, seed_arr, offsets, stream)
-            for t in self.trainers:
-                t._ts_token = None
-            hb.check(rc)
-            for t in self.trainers:
-                t.total_it += k
-            if return_losses:
-                out = (C.c_float * (K * k * 3))()
-                hb.check(lib.iqlhip_group_read_losses(g, out, k, stream))
-                losses[:, done:done + k] = np.frombuffer(out, dtype=np.float32).reshape(K, k, 3)
-            if return_stats:
-                stats[done:done + k] = self._group_stats(k)
-            done += k
-        return stats if return_stats else losses
+        n_off_arr = (C.c_int32 * K)(*n_offs)
+
+        def call(g, B_arr, tab_ptrs, k, seed_arr, offsets, stream):
+            return fn(g, rows_off, size_off, rows_on, size_on, ld, B_arr, n_off_arr, tab_ptrs, k, seed_arr, offsets, stream)
+        return self._run_burst(n_steps, Bs, [1.0 / B for B in Bs], seeds, chunk, return_losses, return_stats, call)
 
     # ------------------------------------------------------------------ policy inference
     def _actor_call(self, rows: Sequence[int], in_ptrs, ld_s: int, out_ptrs, ld_a: int, seeds, max_action,

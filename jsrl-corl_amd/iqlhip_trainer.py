@@ -952,27 +952,15 @@ class ImplicitQLearning:
             raise ValueError("iqlhip: the online replay buffer is empty")
         self._prepare(batch_size)
         self._refuse_injected_masks()
-        inv_batch = 1.0 / batch_size
-        stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
-        losses = np.empty((n_steps, 3), dtype=np.float32) if return_losses else None
-        chunk = max(1, min(int(chunk), K_MAX))
-        lib, stream = hb.lib(), self._stream()
+        fn, stream = hb.lib().iqlhip_train_steps_mixed, self._stream()
         off_ptr, on_ptr, ld = offline_buffer._rows.data_ptr(), online_buffer._rows.data_ptr(), offline_buffer._ld
-        half = (batch_size + 1) // 2
-        self._ts_token = None                  # (the library drops its continue token too)
-        done = 0
-        while done < n_steps:
-            k = min(chunk, n_steps - done)
-            tab = self._scalar_table(k, inv_batch)
-            hb.check(lib.iqlhip_train_steps_mixed(self._ctx, off_ptr, offline_buffer._size, on_ptr, online_buffer._size,
-                                                  ld, batch_size, n_off, tab.ctypes.data, k, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                  self.total_it * half, stream))
-            self.total_it += k
-            done += k
-            self._lookahead_table(min(chunk, n_steps - done) if done < n_steps else k, inv_batch)
-            self._read_rings(k, stream, None if losses is None else losses[done - k: done],
-                             None if stats is None else stats[done - k: done])
-        return (losses, stats) if return_stats else losses
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+        def call(tab, k, offset, flags):
+            return fn(self._ctx, off_ptr, offline_buffer._size, on_ptr, online_buffer._size, ld, batch_size, n_off,
+                      tab.ctypes.data, k, seed, offset, stream)
+        # (no token: the library drops its continue token too)
+        return self._run_burst(n_steps, batch_size, 1.0 / batch_size, chunk, return_losses, return_stats, stream, call)
 
     # ---- rows drawn by weight on the device (iqlhip_weighted.py) -----------------------------------
     def _weighted_args(self, replay_buffer, batch_size: int, weights=None):
@@ -1044,40 +1032,25 @@ class ImplicitQLearning:
         beta = None if is_beta is None else self._is_beta_arg(is_beta)
         self._prepare(batch_size)
         self._refuse_injected_masks()
-        inv_batch = 1.0 / batch_size
-        stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
-        losses = np.empty((n_steps, 3), dtype=np.float32) if return_losses else None
-        chunk = max(1, min(int(chunk), K_MAX))
         lib, stream = hb.lib(), self._stream()
         rows_ptr, ld = replay_buffer._rows.data_ptr(), replay_buffer._ld
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        half = (batch_size + 1) // 2
-        done = 0
-        while done < n_steps:
-            k = min(chunk, n_steps - done)
-            tab = self._scalar_table(k, inv_batch)
-            # (train_steps' token plus the table's generation: a plain call's token never equals it, nor the reverse;
-            #  the library checks the generation too;
-            #  a call with is_beta continues only such a call — its value is not part of the token)
-            tok = (weakref.ref(replay_buffer), replay_buffer._writes, replay_buffer._rows._version,
-                   "weighted" if beta is None else "weighted_is", gen)
-            flags = hb.TS_CONTINUE if self._ts_token == tok else 0
-            if beta is None:
-                rc = lib.iqlhip_train_steps_weighted(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed,
-                                                     self.total_it * half, flags, stream, table)
-            else:
-                rc = lib.iqlhip_train_steps_weighted_is(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k,
-                                                        seed, self.total_it * half, flags, stream, table, beta)
-            if rc:
-                self._ts_token = None
-                hb.check(rc)
-            self._ts_token = tok
-            self.total_it += k
-            done += k
-            self._lookahead_table(min(chunk, n_steps - done) if done < n_steps else k, inv_batch)
-            self._read_rings(k, stream, None if losses is None else losses[done - k: done],
-                             None if stats is None else stats[done - k: done])
-        return (losses, stats) if return_stats else losses
+        buf_ref = weakref.ref(replay_buffer)
+        if beta is None:
+            fn, kind, tail = lib.iqlhip_train_steps_weighted, "weighted", (stream, table)
+        else:
+            fn, kind, tail = lib.iqlhip_train_steps_weighted_is, "weighted_is", (stream, table, beta)
+
+        def call(tab, k, offset, flags):
+            return fn(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed, offset, flags, *tail)
+
+        # (train_steps' token plus the table's generation: a plain call's token never equals it, nor the reverse;
+        #  the library checks the generation too;
+        #  a call with is_beta continues only such a call — its value is not part of the token)
+        def token():
+            return (buf_ref, replay_buffer._writes, replay_buffer._rows._version, kind, gen)
+        return self._run_burst(n_steps, batch_size, 1.0 / batch_size, chunk, return_losses, return_stats, stream, call,
+                               token)
 
     def _schedule_state(self):
         sch = self.actor_lr_schedule
@@ -1233,6 +1206,42 @@ class ImplicitQLearning:
             hb.check(lib.iqlhip_read_stats_ring(self._ctx, sbuf, k, stream))
             stats[:] = np.frombuffer(sbuf, dtype=np.float32).reshape(k, hb.IQLHIP_N_STATS)
 
+    def _run_burst(self, n_steps: int, batch_size: int, inv_batch: float, chunk: int, return_losses: bool,
+                   return_stats: bool, stream, call, token=None):
+        """The multi-step loop behind train_steps, train_steps_mixed and train_steps_weighted, whose checks have all
+        passed: n_steps in library calls of at most `chunk` steps.  call(tab, k, offset, flags) makes the kind's one
+        library call for the next k steps — tab their scalar table, offset their place in the Philox stream — and
+        returns its code.  token: None for a kind that never continues staged rows (the trainer's token is dropped and
+        TS_CONTINUE never passed), or a callable giving the continuation token of the chunk about to run (evaluated per
+        chunk: it reads the buffer's write counts); the call gets TS_CONTINUE iff that equals the token the previous
+        successful call left.  A failed call leaves no token.  Returns losses [n_steps, 3] (None unless return_losses),
+        or (losses, stats) when return_stats."""
+        stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
+        losses = np.empty((n_steps, 3), dtype=np.float32) if return_losses else None
+        chunk = max(1, min(int(chunk), K_MAX))
+        half = (batch_size + 1) // 2
+        if token is None:
+            self._ts_token = None
+        done, tok, flags = 0, None, 0
+        while done < n_steps:
+            k = min(chunk, n_steps - done)
+            tab = self._scalar_table(k, inv_batch)
+            if token is not None:
+                tok = token()
+                flags = hb.TS_CONTINUE if self._ts_token == tok else 0
+            rc = call(tab, k, self.total_it * half, flags)
+            if rc:
+                self._ts_token = None
+                hb.check(rc)
+            self._ts_token = tok
+            self.total_it += k
+            done += k
+            # the GPU is busy with these k steps: compute the scalars of the next k now
+            self._lookahead_table(min(chunk, n_steps - done) if done < n_steps else k, inv_batch)
+            self._read_rings(k, stream, None if losses is None else losses[done - k: done],
+                             None if stats is None else stats[done - k: done])
+        return (losses, stats) if return_stats else losses
+
     def prepare_train_steps(self, replay_buffer, batch_size: int) -> None:
         """Capture and upload the hipGraph chunk train_steps replays for this buffer / batch size now, so that no later
         train_steps call pays for it (it is captured lazily otherwise, by the first call of >= 64 steps)."""
@@ -1259,37 +1268,22 @@ class ImplicitQLearning:
             raise ValueError("iqlhip: train_steps(return_stats=True) needs set_step_stats(True) first")
         size, inv_batch = self._train_steps_args(replay_buffer, batch_size)
         self._refuse_injected_masks()
-        stats = np.empty((n_steps, hb.IQLHIP_N_STATS), dtype=np.float32) if return_stats else None
-        chunk = max(1, min(int(chunk), K_MAX))
-        lib = hb.lib()
+        fn = hb.lib().iqlhip_train_steps
         rank = self._dp_rank if self._dp_world > 1 else 0
         seed = dp.rank_seed(seed, rank)
-        losses = np.empty((n_steps, 3), dtype=np.float32) if return_losses else None
         rows_ptr, ld, stream = replay_buffer._rows.data_ptr(), replay_buffer._ld, self._stream()
-        half = (batch_size + 1) // 2
-        done = 0
-        while done < n_steps:
-            k = min(chunk, n_steps - done)
-            tab = self._scalar_table(k, inv_batch)
-            # IQLHIP_TS_CONTINUE: nothing has written this buffer's rows since our previous call on it (the buffer
-            # counts its writes); the library itself checks that this call starts where that one's index stream ended
-            # (a weak reference: the token must not keep a multi-GB buffer alive; the tensor's version counter sees in-place
-            #  writes through the reference-named views _states / _rewards / ..., which alias the packed rows)
-            tok = (weakref.ref(replay_buffer), replay_buffer._writes, replay_buffer._rows._version)
-            flags = hb.TS_CONTINUE if self._ts_token == tok else 0
-            rc = lib.iqlhip_train_steps(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k,
-                                        seed, self.total_it * half, flags, stream)
-            if rc:
-                self._ts_token = None
-                hb.check(rc)
-            self._ts_token = tok
-            self.total_it += k
-            done += k
-            # the GPU is busy with these k steps: compute the scalars of the next k now
-            self._lookahead_table(min(chunk, n_steps - done) if done < n_steps else k, inv_batch)
-            self._read_rings(k, stream, None if losses is None else losses[done - k: done],
-                             None if stats is None else stats[done - k: done])
-        return (losses, stats) if return_stats else losses
+        buf_ref = weakref.ref(replay_buffer)
+
+        def call(tab, k, offset, flags):
+            return fn(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed, offset, flags, stream)
+
+        # IQLHIP_TS_CONTINUE: nothing has written this buffer's rows since our previous call on it (the buffer
+        # counts its writes); the library itself checks that this call starts where that one's index stream ended
+        # (a weak reference: the token must not keep a multi-GB buffer alive; the tensor's version counter sees in-place
+        #  writes through the reference-named views _states / _rewards / ..., which alias the packed rows)
+        def token():
+            return (buf_ref, replay_buffer._writes, replay_buffer._rows._version)
+        return self._run_burst(n_steps, batch_size, inv_batch, chunk, return_losses, return_stats, stream, call, token)
 
     def train_steps_dp(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0) -> None:
         """Data-parallel multi-step run without host syncs (= train_steps(..., return_losses=False))."""
