@@ -358,6 +358,45 @@ int iqlhip_train_steps_weighted_is(iqlhip_ctx* ctx, const float* rows_dev, int64
                                    int32_t flags, void* stream, const iqlhip_weights* table, float is_beta);
 int iqlhip_train_steps_weighted_is_prepare(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int32_t batch_rows,
                                            float inv_batch, void* stream, const iqlhip_weights* table);
+/* ---- prioritised replay: TD errors as new priorities (DESIGN.md §6j "Prioritised replay inside the chunk graphs") ----
+ * The priority of a row with TD errors (e1, e2) = (q1 - y, q2 - y) is
+ *     td_priority = (max(|e1|, |e2|) + eps)^alpha = exp2(alpha * log2(max(|e1|, |e2|) + eps)),
+ * one device function for every caller, computed in fp32 through the hardware's log2 / exp2 (the intrinsics of the
+ * importance-sampling weights); alpha = 0 gives 1.0f exactly.
+ * iqlhip_weights_update_td: iqlhip_weights_update with w[j] = td_priority(td_dev[j][0], td_dev[j][1]) formed on the fly
+ * (td_dev: [m][2] fp32 on the device, 8-byte aligned — what iqlhip_step_rw's td_out_dev receives; no intermediate weight
+ * array).  Everything else is iqlhip_weights_update's: the last duplicate wins; a NaN or an infinity in either TD error
+ * (flag 1) or an index outside [0, bound) (flag 4) is skipped; a priority beyond the table's scale saturates; slices of
+ * 65 536 entries in order; asynchronous; the version grows by 1.  IQLHIP_EINVAL: a static table, alpha or eps negative or
+ * not finite, and alpha = 0 together with eps = 0 — a zero TD error would give log2(0) * 0 = NaN and the row would be
+ * skipped and flagged instead of getting the priority 1 that alpha = 0 means (eps = 0 with alpha > 0 is fine: a zero TD
+ * error gives priority 0).
+ * iqlhip_train_steps_prioritized: iqlhip_train_steps_weighted_is whose steps write their TD errors back into `table` (an
+ * updatable one) as new priorities, inside the chunk graphs.  Per call:
+ *     idx_0 = draw of step 0 by the table as it stands (the set-up kernel)
+ *     for t = 0 .. n_steps - 1:
+ *         idx_{t+1} = draw of step t + 1 (the idle blocks of forward t: it sees the updates of steps < t)
+ *         step t on rows idx_t, loss terms weighted by c_t = (q_min / q_r)^is_beta with the q read at the draw
+ *         table[idx_t] <- td_priority(TD errors of step t)              (in front of forward t + 1)
+ * — bit for bit the eager loop iqlhip_draw_indices_weighted_is (step t + 1) -> iqlhip_step_rw with td_out (step t) ->
+ * iqlhip_weights_update_td (step t), in this order.  The one-step lag keeps the draw off the critical path: the
+ * priorities of step t first affect the draw of step t + 2.  The update is three more launches per step on the same
+ * stream (a linear chain; m = batch_rows, bound = n).  alpha, eps and is_beta are values of the call (device words the
+ * set-up kernel writes): changing them re-captures nothing.  IQLHIP_TS_CONTINUE: honoured only behind a prioritised call
+ * (same table generation and version, and the conditions of iqlhip_train_steps) and means "this call goes on with that
+ * call's lag-1 chain": its step 0 runs on the rows that call's last forward drew, one update behind.  A caller that wants
+ * a call's result to depend on the table alone passes it only between the pieces of one burst (the Python layer does).
+ * The call moves the table's version by 1: a weighted call that follows gathers afresh.  Everything
+ * iqlhip_train_steps_weighted_is refuses, and IQLHIP_EINVAL for a static table and for alpha / eps as above — all before
+ * anything is launched or any counter moves.  _prepare rehearses the chunk graphs with their update launches switched
+ * off by the call's device word: it neither trains nor touches the table. */
+int iqlhip_weights_update_td(iqlhip_weights* table, const int64_t* idx_dev, const float* td_dev, int64_t m, int64_t bound,
+                             float alpha, float eps, void* stream);
+int iqlhip_train_steps_prioritized(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int64_t size, int32_t batch_rows,
+                                   const iqlhip_step_scalars* sc, int32_t n_steps, uint64_t seed, uint64_t stream_offset,
+                                   int32_t flags, void* stream, iqlhip_weights* table, float is_beta, float alpha, float eps);
+int iqlhip_train_steps_prioritized_prepare(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int32_t batch_rows,
+                                           float inv_batch, void* stream, iqlhip_weights* table);
 
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is

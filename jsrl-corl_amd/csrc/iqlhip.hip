@@ -135,6 +135,9 @@ struct DevGuard {
 // What a captured chunk graph depends on through frozen kernel arguments.  The number of steps of a call is NOT part
 // of it: a call is composed of replays of the fixed chunk graphs (64, 16, 4, 2 steps and one), nothing is ever
 // captured per call length (kernel boundaries inside a graph are ~0.5 us shorter than between directly launched kernels).
+// What the table update inside a prioritised chunk needs of its updatable table beyond WTab (the launches' WUpd).
+struct PrioSrc { unsigned* stamp = nullptr; unsigned* flags = nullptr; unsigned long long* delta = nullptr; int sh0 = 0;
+                 unsigned sat_bits = 0; };
 struct GraphKey {
   const float* rows = nullptr;
   int64_t ld = 0;
@@ -154,10 +157,14 @@ struct GraphKey {
   int32_t n_off = 0;
   // weighted chunks (iqlhip_train_steps_weighted): the table the idle blocks draw by.  wt.tab == nullptr: not one
   WTab wt{nullptr, 0u, 0};
-  // ... with importance-sampling weights (iqlhip_train_steps_weighted_is): another forward and the row-weighted backward
+  // ... with importance-sampling weights (iqlhip_train_steps_weighted_is): another forward and the row-weighted backward;
+  // 2: a prioritised chunk (iqlhip_train_steps_prioritized) — that plus the table update behind every step, `up` what its
+  // launches are captured with
   int is = 0;
+  PrioSrc up;
   bool operator==(const GraphKey& o) const {
-    return is == o.is && rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
+    return is == o.is && up.stamp == o.up.stamp && up.flags == o.up.flags && up.delta == o.up.delta && up.sh0 == o.up.sh0 &&
+           up.sat_bits == o.up.sat_bits && rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
            inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip &&
            rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n && wt.levels == o.wt.levels && wt.local == o.wt.local;
   }
@@ -169,11 +176,14 @@ struct GraphKey {
 // staged: iqlhip_weights_update moves the version, the rows staged before it were drawn by the old weights).
 // is: a weighted call with importance-sampling weights (iqlhip_train_steps_weighted_is), is_beta its exponent — a value
 // of the CALL (the set-up kernel writes it to a device word), never part of a key.
+// is == 2: a prioritised call (iqlhip_train_steps_prioritized): `up` its table's update record (part of the key), alpha,
+// eps and live (0: a rehearsal, whose update launches leave the table alone) values of the call like is_beta.
 struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; uint64_t wt_ver = 0;
-                int is = 0; float is_beta = 0.f; };
+                int is = 0; float is_beta = 0.f; PrioSrc up{}; float alpha = 0.f, eps = 0.f; unsigned live = 1u; };
 // Which forward a step of such a call launches: 0 iql_fwd_kernel, 1 iql_fwd_mixed_kernel, 2 iql_fwd_weighted_kernel,
-// 3 iql_fwd_weighted_is_kernel (and then the row-weighted backward).
-static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? (mx->is ? 3 : 2) : 1); }
+// 3 iql_fwd_weighted_is_kernel (and then the row-weighted backward), 4 iql_fwd_prio_kernel (the row-weighted backward
+// storing the TD errors, and then the table update).
+static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? (mx->is == 2 ? 4 : mx->is ? 3 : 2) : 1); }
 
 // The few RCCL entry points the in-stream all-reduce needs, resolved at run time from the librccl.so.1 the process
 // already has (PyTorch-ROCm brings one) or can load — the library has no link-time dependency on RCCL.
@@ -244,6 +254,10 @@ struct iqlhip_ctx {
   // weighted calls with importance-sampling weights: [2][max_batch] staged q of the two staging parities, [max_batch] c of
   // the running step, the call's beta (one allocation, made by the first such call; addresses frozen in chunk graphs)
   float* is_buf = nullptr;
+  // prioritised calls: [2][max_batch] int64 staged indices of the two staging parities, [max_batch][2] fp32 TD errors of
+  // the running step, the call's alpha, eps and live word (one allocation, made by the first such call; frozen in graphs)
+  char* prio_buf = nullptr;
+  bool prio_lds_set = false;
   bool mixed_lds_set = false;                   // the mixed forward instantiations have their dynamic-LDS limit (check_mixed_args)
   char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (freeing it at the end of prepare
                                                 //   idles the GPU right in front of the caller's first steps)
@@ -873,9 +887,11 @@ static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c
 static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);     // (end of file)
 static void launch_fwd_weighted_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
 static void launch_fwd_weighted_is_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
+static void launch_fwd_prio_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);         // (end of file)
 static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, int kind = 0) {
   if (kind == 1) return launch_fwd_mixed_grid(c, p, nb, st);
   if (kind == 2) return launch_fwd_weighted_grid(c, p, nb, st);
+  if (kind == 4) return launch_fwd_prio_grid(c, p, nb, st);
   if (kind == 3) return launch_fwd_weighted_is_grid(c, p, nb, st);
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
@@ -1874,6 +1890,12 @@ extern "C" int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, ui
 // replay needs to differ in lives in device words that the set-up kernel writes once and each chunk's last update
 // kernel advances, so the chunks of a call follow each other with no host-side launch in between; the rows, scalars and
 // keep-bits of step k + 1 are staged by the idle eighth of step k's forward grid (IdleWork).
+// The parts of iqlhip_ctx::prio_buf: the staged indices of staging parity h, the running step's TD errors, the call's words.
+static long long* prio_idx(const iqlhip_ctx* c, int h) { return (long long*)c->prio_buf + (size_t)h * c->dims.max_batch; }
+static float* prio_td(const iqlhip_ctx* c) { return (float*)(c->prio_buf + 16 * (size_t)c->dims.max_batch); }
+static float* prio_words(const iqlhip_ctx* c) { return prio_td(c) + 2 * (size_t)c->dims.max_batch; }
+// The table update behind step k of a prioritised chunk (end of file: its kernels are the library's last).
+static void launch_prio_update(const iqlhip_ctx* c, const MixSrc& mx, int B, int k, hipStream_t st);
 static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_dev, int B, int K, const MixSrc* mx) {
   const int MB = c->dims.max_batch;
   for (int k = 0; k < K; ++k) {
@@ -1897,11 +1919,13 @@ static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_d
       i.c_dst = c->is_buf + 2 * (size_t)MB;
       i.is_beta = c->is_buf + 3 * (size_t)MB;
     }
+    if (mx && mx->is == 2) i.idx_dst = prio_idx(c, (k + 1) & 1);      // (as q_dst: step k + 1's half)
   }
 }
 
 static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_batch, int mode, int parity,
-                         const IdleWork* work_dev, int kind = 0) {
+                         const IdleWork* work_dev, const MixSrc* mx = nullptr) {
+  const int kind = fwd_kind(mx);
   const int MB = c->dims.max_batch;
   iqlhip_step_scalars sc0;
   memset(&sc0, 0, sizeof sc0);
@@ -1921,11 +1945,14 @@ static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_
     // (statistics: slot BASE + k of the ring, the loss ring's indexing; the chunk's key carries the setting)
     StatsArgs sa;
     if (c->stats_on) sa = make_stats(c, p, c->stats_ring, k, c->k_max, c->hdr);
-    // (kind 3: the step's c, written by an idle block of its forward, is the row-weighted backward's weight vector)
-    const RowWeights rw = {c->is_buf ? c->is_buf + 2 * (size_t)MB : nullptr, nullptr};
+    // (kind 3 and 4: the step's c, written by an idle block of its forward, is the row-weighted backward's weight vector;
+    //  kind 4: the backward stores the rows' TD errors, the new priorities of the rows staged in half k & 1 — the update's
+    //  launches follow the step on the same stream, a linear chain in front of the next forward, which draws by the table)
+    const RowWeights rw = {c->is_buf ? c->is_buf + 2 * (size_t)MB : nullptr, kind == 4 ? prio_td(c) : nullptr};
     int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, kind,
-                          kind == 3 ? &rw : nullptr);
+                          kind >= 3 ? &rw : nullptr);
     if (rc) return rc;
+    if (kind == 4) launch_prio_update(c, *mx, B, k, st);
   }
   return IQLHIP_OK;
 }
@@ -1954,7 +1981,8 @@ struct SetupArgs {
   const float* rows_on; int n_off;        // (iql_call_setup_mixed_kernel's two more)
   WTab wt;                                // (iql_call_setup_weighted_kernel's one more, in their place)
   float* q_dst; float* beta_dev; float beta;        // (iql_call_setup_weighted_is_kernel's three behind wt)
-  void* ptrs[20];
+  long long* idx_dst; float* prio_words; float alpha; float eps; unsigned live;      // (iql_call_setup_prio_kernel's five behind those)
+  void* ptrs[24];
   const void* func;                       // iql_call_setup_kernel, its two-source or its weighted form
   int nb;
 };
@@ -1977,12 +2005,15 @@ static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int 
   const int kind = fwd_kind(mx);
   a.wt = mx ? mx->wt : WTab{nullptr, 0u, 0};
   a.q_dst = c->is_buf; a.beta_dev = c->is_buf ? c->is_buf + 3 * (size_t)MB : nullptr; a.beta = mx ? mx->is_beta : 0.f;
-  a.func = kind == 3 ? (const void*)iql_call_setup_weighted_is_kernel : kind == 2 ? (const void*)iql_call_setup_weighted_kernel
+  a.idx_dst = c->prio_buf ? prio_idx(c, 0) : nullptr; a.prio_words = c->prio_buf ? prio_words(c) : nullptr;
+  a.alpha = mx ? mx->alpha : 0.f; a.eps = mx ? mx->eps : 0.f; a.live = mx ? mx->live : 0u;
+  a.func = kind == 4 ? (const void*)iql_call_setup_prio_kernel : kind == 3 ? (const void*)iql_call_setup_weighted_is_kernel : kind == 2 ? (const void*)iql_call_setup_weighted_kernel
                      : (kind == 1 ? (const void*)iql_call_setup_mixed_kernel : (const void*)iql_call_setup_kernel);
-  void* p[20] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
+  void* p[24] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
                  &a.drop_words, &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val, &a.rows_on, &a.n_off};
   if (kind >= 2) { p[15] = &a.wt; p[16] = nullptr; }
-  if (kind == 3) { p[16] = &a.q_dst; p[17] = &a.beta_dev; p[18] = &a.beta; }
+  if (kind >= 3) { p[16] = &a.q_dst; p[17] = &a.beta_dev; p[18] = &a.beta; }
+  if (kind == 4) { p[19] = &a.idx_dst; p[20] = &a.prio_words; p[21] = &a.alpha; p[22] = &a.eps; p[23] = &a.live; }
   memcpy(a.ptrs, p, sizeof p);
   long long want = ((long long)n_steps * 3 + 255) / 256;
   if (gather) want = std::max(want, ((long long)B * (c->row_ld / 4) + 255) / 256);
@@ -2001,7 +2032,7 @@ static int launch_call_setup(iqlhip_ctx* c, hipStream_t st, const ChunkHdr& h, i
 // Capture and instantiate the chunk graph of g.key into g, member by member (a failure leaves the ones made so far).
 static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   const GraphKey& key = g.key;
-  const MixSrc key_mx{key.rows_on, key.n_off, key.wt, 0, 0, key.is, 0.f};
+  const MixSrc key_mx{key.rows_on, key.n_off, key.wt, 0, 0, key.is, 0.f, key.up};
   const MixSrc* mx = (key.rows_on || key.wt.tab) ? &key_mx : nullptr;
   // the chunk's idle-work records: device memory written once, here (their content is part of what the key freezes)
   {
@@ -2025,7 +2056,7 @@ static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
     if (hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
       rc = fail(IQLHIP_EHIP, "capture of the set-up kernel failed");
   }
-  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, fwd_kind(mx));
+  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, mx);
   e = hipStreamEndCapture(cs, &g.graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -2084,7 +2115,7 @@ static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld,
                          int parity, int head = 0, const MixSrc* mx = nullptr) {
   GraphKey key;
   key.head = head;
-  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; key.wt = mx->wt; key.is = mx->is; }
+  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; key.wt = mx->wt; key.is = mx->is; key.up = mx->up; }
   key.rows = rows_dev; key.ld = ld; key.B = B; key.K = K; key.params = c->params; key.drop_p = c->drop_p;
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
@@ -2122,7 +2153,7 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
   int r = chunk_graph(c, make_key(c, rows_dev, ld, B, n, inv_batch, parity, head_args ? 1 : 0, mx), &gexec, &cg);
   if (r) return r;
   if (g_direct_all && !head_args) {      // experiment: the chunk's kernels launched one by one instead of the graph replay
-    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, fwd_kind(mx));
+    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, mx);
     if (r) return r;
     cg->last = st;
     if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
@@ -2283,7 +2314,9 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // A weighted call continues a weighted call on the same table generation only, and a plain call a plain one.
   const int kind = fwd_kind(mx);
   const uint64_t wt_gen = kind >= 2 ? mx->wt_gen : 0, wt_ver = kind >= 2 ? mx->wt_ver : 0;
-  const int is_call = kind == 3 ? 1 : 0;      // (the rows a call without staged q left cannot start a call that needs them)
+  // (the rows a call without staged q left cannot start a call that needs them, nor those of one without staged indices;
+  //  a prioritised call continues only a prioritised one: its rows were drawn one update behind, the lag-1 chain)
+  const int is_call = kind == 4 ? 2 : kind == 3 ? 1 : 0;
   const bool cont = kind != 1 && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == wt_gen && c->cont.is == is_call &&
                     c->cont.wt_ver == wt_ver &&
                     c->cont.rows == rows_dev && c->cont.ld == ld &&
@@ -2318,7 +2351,7 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
     if (rc) return rc;
     rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, mx);
     if (rc) return rc;
-    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, fwd_kind(mx));
+    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, mx);
     if (rc) return rc;
     cg->last = st;
     if (c->drop_p > 0.f) c->drop_step += (unsigned long long)head_k;
@@ -2348,7 +2381,8 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
   if (kind != 1 && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
-    c->cont.wt_gen = wt_gen; c->cont.wt_ver = wt_ver; c->cont.is = is_call;
+    // (a prioritised call moves its table's version by 1 itself: iqlhip_train_steps_prioritized)
+    c->cont.wt_gen = wt_gen; c->cont.wt_ver = wt_ver + (kind == 4 ? 1 : 0); c->cont.is = is_call;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
     c->cont.next_offset = stream_offset + ((unsigned long long)K * (unsigned long long)B) / 2ull;
     c->cont.drop_p = c->drop_p; c->cont.drop_seed = c->drop_seed; c->cont.drop_step = c->drop_step;
@@ -4979,4 +5013,108 @@ static int weighted_is_setup(iqlhip_ctx* c, int32_t B, float is_beta) {
 // (declared next to the other selectors; here so that its instantiations are the code object's last)
 static BwdRwFn bwd_rw_kernel(bool full, bool multi) {
   return with_bools([](auto MU, auto FU) -> BwdRwFn { return &iql_bwd_rw_kernel<FU.value, MU.value>; }, multi, full);
+}
+
+// ---------------------------------------------------------------------------
+// Prioritised replay (include/iqlhip.h "iqlhip_weights_update_td", "iqlhip_train_steps_prioritized"; DESIGN.md 6j
+// "Prioritised replay inside the chunk graphs"; kernels: iqlhip_prio_kernels.h, the code object's last).
+#include "iqlhip_prio_kernels.h"
+
+// alpha and eps of a priority: finite, not negative, and not both zero (a zero TD error would then give log2(0) * 0, a NaN
+// — the row would be skipped and flagged instead of getting the priority 1 that alpha = 0 means).
+static int prio_exponents_check(float alpha, float eps) {
+  if (!(alpha >= 0.f) || !std::isfinite(alpha)) return fail(IQLHIP_EINVAL, "alpha must be finite and >= 0");
+  if (!(eps >= 0.f) || !std::isfinite(eps)) return fail(IQLHIP_EINVAL, "eps must be finite and >= 0");
+  if (alpha == 0.f && eps == 0.f) return fail(IQLHIP_EINVAL, "alpha = 0 needs eps > 0 (a zero TD error would give log2(0) * 0)");
+  return IQLHIP_OK;
+}
+// The three launches of an update of m entries with TD errors as the weight source.
+static void launch_update_td(const WUpd& u, const long long* idx, const float* td, unsigned m, long long bound,
+                             unsigned long long* delta, const PrioArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(iql_wt_update_stamp_td_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, td, m, bound, u, a);
+  hipLaunchKernelGGL(iql_wt_update_delta_td_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, td, m, bound, u, delta, a);
+  hipLaunchKernelGGL(iql_wt_update_apply_td_kernel, dim3((m + 3u) / 4u), dim3(256), 0, st, idx, td, m, bound, u,
+                     (const unsigned long long*)delta, a);
+}
+
+extern "C" int iqlhip_weights_update_td(iqlhip_weights* t, const int64_t* idx_dev, const float* td_dev, int64_t m, int64_t bound,
+                                        float alpha, float eps, void* stream) {
+  if (!t || (m > 0 && (!idx_dev || !td_dev))) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!t->local) return fail(IQLHIP_EINVAL, "the table is not updatable (iqlhip_weights_build_updatable)");
+  if (m < 0) return fail(IQLHIP_EINVAL, "m = %lld entries", (long long)m);
+  if (bound < 0 || bound > t->n) return fail(IQLHIP_EINVAL, "bound = %lld outside [0, %lld]", (long long)bound, (long long)t->n);
+  if ((((uintptr_t)idx_dev) & 7) || (((uintptr_t)td_dev) & 7)) return fail(IQLHIP_EINVAL, "indices and TD errors must be 8-byte aligned");
+  if (int rc = prio_exponents_check(alpha, eps)) return rc;
+  DevGuard guard(t->device);
+  hipStream_t st = (hipStream_t)stream;
+  const WUpd u{t->tab, t->stamp, t->flags, (unsigned)t->n, t->levels, t->sh0, t->sat_bits};
+  const PrioArgs a{nullptr, alpha, eps};
+  // slice by slice, in order, as iqlhip_weights_update
+  for (int64_t j0 = 0; j0 < m; j0 += WT_UPDATE_SLICE) {
+    const unsigned k = (unsigned)std::min<int64_t>(WT_UPDATE_SLICE, m - j0);
+    launch_update_td(u, (const long long*)idx_dev + j0, td_dev + 2 * j0, k, (long long)bound, t->delta, a, st);
+  }
+  HIPCHK(hipGetLastError());
+  ++t->version;
+  return IQLHIP_OK;
+}
+
+static auto fwd_prio_kernel(bool dma, bool multi) {      // (fp32 only: the row-weighted backward is)
+  return with_bools([](auto MU, auto DMA) { return &iql_fwd_prio_kernel<DMA.value, MU.value>; }, multi, dma);
+}
+static void launch_fwd_prio_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
+  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
+  hipLaunchKernelGGL(fwd_prio_kernel(dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
+}
+// Step k of a prioritised chunk has run: table[idx of staging half k & 1] <- td_priority(its TD errors), alpha, eps and the
+// live word read from the call's device words.  m, bound and every pointer are constants of the chunk graph.
+static void launch_prio_update(const iqlhip_ctx* c, const MixSrc& mx, int B, int k, hipStream_t st) {
+  const WUpd u{const_cast<unsigned long long*>(mx.wt.tab), mx.up.stamp, mx.up.flags, mx.wt.n, (int)mx.wt.levels, mx.up.sh0,
+               mx.up.sat_bits};
+  const PrioArgs a{prio_words(c), 0.f, 0.f};
+  launch_update_td(u, prio_idx(c, k & 1), prio_td(c), (unsigned)B, (long long)mx.wt.n, mx.up.delta, a, st);
+}
+// What a prioritised call needs beyond check_weighted_args and weighted_is_setup, before anything is launched or any
+// counter moves: an updatable table, valid exponents, the staging buffer and the forward's LDS allowance.
+static int prio_setup(iqlhip_ctx* c, const iqlhip_weights* table, int32_t B, float alpha, float eps) {
+  if (!table->local) return fail(IQLHIP_EINVAL, "the table is not updatable (iqlhip_weights_build_updatable)");
+  if (int rc = prio_exponents_check(alpha, eps)) return rc;
+  if (B > WT_UPDATE_SLICE) return fail(IQLHIP_EUNSUPPORTED, "prioritised calls take batches of at most %d rows", WT_UPDATE_SLICE);
+  DevGuard guard(c->device);
+  if (!c->prio_buf) HIPCHK(c->own.dev(&c->prio_buf, 24 * (size_t)c->dims.max_batch + 4 * sizeof(float), 0));
+  if (!c->prio_lds_set) {
+    int rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_prio_kernel(m & 1, m & 2); });
+    if (rc) return rc;
+    c->prio_lds_set = true;
+  }
+  return IQLHIP_OK;
+}
+static MixSrc prio_src(const iqlhip_weights* t, float is_beta, float alpha, float eps, unsigned live) {
+  MixSrc mx{nullptr, 0, weights_tab(t), t->gen, t->version, 2, is_beta};
+  mx.up = PrioSrc{t->stamp, t->flags, t->delta, t->sh0, t->sat_bits};
+  mx.alpha = alpha; mx.eps = eps; mx.live = live;
+  return mx;
+}
+extern "C" int iqlhip_train_steps_prioritized_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B,
+                                                      float inv_batch, void* stream, iqlhip_weights* table) {
+  int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
+  if (!rc) rc = weighted_is_setup(c, B, 0.f);
+  if (!rc) rc = prio_setup(c, table, B, 1.f, 1.f);
+  if (rc) return rc;
+  const MixSrc mx = prio_src(table, 0.f, 1.f, 1.f, /*live=*/0u);      // (the rehearsal's updates leave the table alone)
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
+}
+extern "C" int iqlhip_train_steps_prioritized(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
+                                              const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
+                                              int32_t flags, void* stream, iqlhip_weights* table, float is_beta, float alpha,
+                                              float eps) {
+  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
+  if (!rc) rc = weighted_is_setup(c, B, is_beta);
+  if (!rc) rc = prio_setup(c, table, B, alpha, eps);
+  if (rc) return rc;
+  const MixSrc mx = prio_src(table, is_beta, alpha, eps, /*live=*/1u);
+  rc = train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
+  if (!rc) ++table->version;      // the table's content has moved (a failed call leaves no continuation behind anyway)
+  return rc;
 }

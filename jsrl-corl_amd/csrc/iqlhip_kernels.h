@@ -395,6 +395,9 @@ struct IdleWork {
   const float* q_src;
   float* c_dst;
   const float* is_beta;
+  // prioritised chunks only (MODE 4): where the next step's drawn indices are staged, next to its q (int64,
+  // the other parity's half) — what that step's in-graph table update reads
+  long long* idx_dst;
 };
 // (defined in iqlhip_weighted_kernels.h, behind every kernel of this file)
 __device__ __forceinline__ void idle_gather_weighted(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
@@ -403,8 +406,12 @@ __device__ __forceinline__ void idle_gather_weighted(const IdleWork& w, unsigned
 __device__ __forceinline__ void idle_gather_weighted_q(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
                                                        unsigned long long j0, int blk, int nblk);
 __device__ __forceinline__ void idle_is_weights(const IdleWork& w);
+// (defined in iqlhip_prio_kernels.h, behind every kernel of this file)
+__device__ __forceinline__ void idle_gather_weighted_qi(const IdleWork& w, unsigned long long seed, unsigned long long ctr0,
+                                                        unsigned long long j0, int blk, int nblk);
 // MODE: 1 = the idle work of a two-source chunk (iql_fwd_mixed_kernel), 2 = of a weighted chunk
-// (iql_fwd_weighted_kernel), 3 = of a weighted chunk with importance-sampling weights (iql_fwd_weighted_is_kernel) — a
+// (iql_fwd_weighted_kernel), 3 = of a weighted chunk with importance-sampling weights (iql_fwd_weighted_is_kernel),
+// 4 = of a prioritised chunk (iql_fwd_prio_kernel: mode 3 plus the drawn indices) — a
 // compile-time switch, so that the forward kernels of plain calls hold no trace of any.
 template <int MODE = 0>
 __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int nblk) {
@@ -414,7 +421,10 @@ __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int
   const unsigned long long base = w.hdr[HDR_BASE], dseed = w.hdr[HDR_DROP_SEED], dstep = w.hdr[HDR_DROP_STEP];
   // the next step's rows: index j = POS + (k + 1) n + r of the call (for the chunk's last step that is step 0 of
   // whatever runs next: the following chunk, or the next call when it continues this one's stream)
-  if constexpr (MODE == 3) {
+  if constexpr (MODE == 4) {
+    idle_gather_weighted_qi(w, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, blk, nblk);
+    if (blk == nblk - 1) idle_is_weights(w);
+  } else if constexpr (MODE == 3) {
     idle_gather_weighted_q(w, seed, ctr0, pos + (unsigned long long)(w.k + 1) * (unsigned long long)w.n, blk, nblk);
     if (blk == nblk - 1) idle_is_weights(w);       // THIS step's c, from the q the step before staged: one block
   } else if constexpr (MODE == 2)
@@ -956,6 +966,16 @@ __global__ __launch_bounds__(256) void iql_call_setup_weighted_is_kernel(unsigne
                                                                          unsigned* arrivals, unsigned long long* ack,
                                                                          unsigned long long ack_val, WTab wt, float* q_dst,
                                                                          float* beta_dev, float beta);
+// (and the prioritised form that stages the rows' indices too and publishes alpha and eps: iqlhip_prio_kernels.h)
+__global__ __launch_bounds__(256) void iql_call_setup_prio_kernel(unsigned long long* hdr, ChunkHdr h,
+                                                                  iqlhip_step_scalars* sched_call,
+                                                                  const iqlhip_step_scalars* sched_src, int n_steps,
+                                                                  const float* rows, long long ld, float* xb, int B,
+                                                                  unsigned* drop_dst, int drop_words, unsigned drop_thresh,
+                                                                  unsigned* arrivals, unsigned long long* ack,
+                                                                  unsigned long long ack_val, WTab wt, float* q_dst,
+                                                                  float* beta_dev, float beta, long long* idx_dst,
+                                                                  float* prio_words, float alpha, float eps, unsigned live);
 
 // bf16 shadows rebuilt from the fp32 masters (start of every library call on the bf16 path: the caller owns the
 // masters and may have written them through its own tensors since the last update kernel ran).

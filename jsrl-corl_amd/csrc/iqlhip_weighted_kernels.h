@@ -198,31 +198,46 @@ __device__ __forceinline__ unsigned wt_update_bad(long long i, float w, long lon
   return bad;
 }
 
+// The three launches of an update take their weights from a SOURCE, a compile-time switch: WtVec — entry j's weight is
+// w[j] (iqlhip_weights_update) — or WtTd (iqlhip_prio_kernels.h) — it is td_priority of entry j's TD errors, formed on the
+// fly (iqlhip_weights_update_td, the prioritised chunk graphs).  The kernels below are the WtVec instantiations.
+// (The bodies' pointer parameters carry no __restrict__ — the kernels' own do: with it on both, the compiler hoists the
+//  kernel-argument loads of the WtVec kernels, which are to keep the code they had as plain kernels.)
+struct WtVec {
+  const float* __restrict__ w;
+  __device__ __forceinline__ float operator()(unsigned j) const { return w[j]; }
+};
+
 // Update, launch 1: the last valid entry of every row wins (stamp[i] = max over its entries of j + 1); bad entries
 // only leave their flag bits.
-__global__ __launch_bounds__(256) void iql_wt_update_stamp_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
-                                                                  unsigned m, long long bound, WUpd t) {
+template <class WS>
+__device__ __forceinline__ void wt_update_stamp(const long long* idx, const WS& w, unsigned m, long long bound,
+                                                const WUpd& t) {
   const unsigned j = blockIdx.x * 256u + threadIdx.x;
   unsigned bad = 0u;
   if (j < m) {
     const long long i = idx[j];
-    bad = wt_update_bad(i, w[j], bound);
+    bad = wt_update_bad(i, w(j), bound);
     if (!bad) atomicMax(t.stamp + i, j + 1u);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) bad |= (unsigned)__shfl_xor((int)bad, o);
   if ((threadIdx.x & 63) == 0 && bad) atomicOr(t.flags, bad);
 }
+__global__ __launch_bounds__(256) void iql_wt_update_stamp_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
+                                                                  unsigned m, long long bound, WUpd t) {
+  wt_update_stamp(idx, WtVec{w}, m, bound, t);
+}
 
 // Launch 2: delta[j] = q_new - q_old (two's complement) of every winner, q_old read back from its level-0 node —
 // nothing writes the tree in this launch.  Entries that lost or are skipped get 0.
-__global__ __launch_bounds__(256) void iql_wt_update_delta_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
-                                                                  unsigned m, long long bound, WUpd t,
-                                                                  unsigned long long* __restrict__ delta) {
+template <class WS>
+__device__ __forceinline__ void wt_update_delta(const long long* idx, const WS& w, unsigned m, long long bound,
+                                                const WUpd& t, unsigned long long* delta) {
   const unsigned j = blockIdx.x * 256u + threadIdx.x;
   if (j >= m) return;
   const long long i = idx[j];
-  const float wj = w[j];
+  const float wj = w(j);
   unsigned long long d = 0ull;
   if (!wt_update_bad(i, wj, bound) && t.stamp[i] == j + 1u) {
     const unsigned long long upto = t.tab[i], before = (i & 63) ? t.tab[i - 1] : 0ull;
@@ -232,17 +247,22 @@ __global__ __launch_bounds__(256) void iql_wt_update_delta_kernel(const long lon
   }
   delta[j] = d;
 }
+__global__ __launch_bounds__(256) void iql_wt_update_delta_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
+                                                                  unsigned m, long long bound, WUpd t,
+                                                                  unsigned long long* __restrict__ delta) {
+  wt_update_delta(idx, WtVec{w}, m, bound, t, delta);
+}
 
 // Launch 3, one wave per entry: a winner adds its delta to the entries at and behind its position in its node of every
 // level (waves of different rows meet in the upper nodes: 64-bit atomic adds, which commute), and resets its stamp.
-__global__ __launch_bounds__(256) void iql_wt_update_apply_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
-                                                                  unsigned m, long long bound, WUpd t,
-                                                                  const unsigned long long* __restrict__ delta) {
+template <class WS>
+__device__ __forceinline__ void wt_update_apply(const long long* idx, const WS& w, unsigned m, long long bound,
+                                                const WUpd& t, const unsigned long long* delta) {
   const unsigned j = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
   const unsigned lane = threadIdx.x & 63u;
   if (j >= m) return;
   const long long i = idx[j];
-  if (wt_update_bad(i, w[j], bound) || t.stamp[i] != j + 1u) return;
+  if (wt_update_bad(i, w(j), bound) || t.stamp[i] != j + 1u) return;
   const unsigned long long d = delta[j];
   if (d) {
     unsigned size = t.n, off = 0u, at = (unsigned)i;
@@ -258,6 +278,11 @@ __global__ __launch_bounds__(256) void iql_wt_update_apply_kernel(const long lon
     }
   }
   if (lane == 0) t.stamp[i] = 0u;
+}
+__global__ __launch_bounds__(256) void iql_wt_update_apply_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
+                                                                  unsigned m, long long bound, WUpd t,
+                                                                  const unsigned long long* __restrict__ delta) {
+  wt_update_apply(idx, WtVec{w}, m, bound, t, delta);
 }
 
 // Leaf values back from the tree (iqlhip_weights_state): q[i] = tab[i] - tab[i - 1], or tab[i] where a node begins

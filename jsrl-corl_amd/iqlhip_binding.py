@@ -182,6 +182,13 @@ SYMBOLS = [
                                                          C.c_void_p, C.c_void_p]),
     ("iqlhip_train_steps_weighted_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p,
                                                       C.c_void_p]),
+    ("iqlhip_weights_update_td", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float,
+                                           C.c_void_p]),
+    ("iqlhip_train_steps_prioritized", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                 C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_float, C.c_float, C.c_float]),
+    ("iqlhip_train_steps_prioritized_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
+                                                         C.c_void_p, C.c_void_p]),
     ("iqlhip_debug_read", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64,
                                     C.POINTER(C.c_int64), C.c_void_p]),
     ("iqlhip_debug_time_kernel", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.POINTER(C.c_float),

@@ -428,6 +428,24 @@ class ReplayBuffer:
                                                     self._stream()))
         self._weights_version += 1
 
+    def update_sample_weights_td(self, indices, td, alpha, eps) -> None:
+        """update_sample_weights with weights[j] = (max(|td[j, 0]|, |td[j, 1]|) + eps) ** alpha formed on the device inside
+        the update's own launches: td is the [m, 2] float32 tensor trainer.last_td_errors() returns for the batch
+        gathered at `indices` — the priority refresh of prioritised replay without any torch arithmetic in between.
+        ValueError for alpha or eps negative, not finite or both 0."""
+        import iqlhip_weighted as wtd
+        if self._weights is None or not self._weights_updatable:
+            raise ValueError("iqlhip: the replay buffer has no updatable sample weights "
+                             "(set_sample_weights(..., updatable=True))")
+        dev = self._rows.device
+        m = wtd.check_td_args(indices, td, dev)
+        alpha, eps = wtd.check_priority_args(alpha, eps)
+        idx, e = indices.contiguous(), td.contiguous()
+        with torch.cuda.device(dev):
+            hb.check(hb.lib().iqlhip_weights_update_td(self._weights, idx.data_ptr(), e.data_ptr(), m, self._index_bound(),
+                                                       alpha, eps, self._stream()))
+        self._weights_version += 1
+
     def sample_weights_flags(self) -> int:
         """The table's sticky flag word (waits for the device): bit 0 a non-finite weight was skipped by an update, bit 1
         a negative one, bit 2 an index out of range."""

@@ -1052,6 +1052,78 @@ class ImplicitQLearning:
         return self._run_burst(n_steps, batch_size, 1.0 / batch_size, chunk, return_losses, return_stats, stream, call,
                                token)
 
+    # ---- prioritised replay inside the chunk graphs (DESIGN.md 6j "Prioritised replay inside the chunk graphs") -------
+    def _prioritized_args(self, replay_buffer, batch_size: int, weights, alpha, eps, is_beta):
+        """The checks both prioritised calls make before anything is launched or any counter moves: train_steps_weighted's,
+        an updatable table, valid alpha / eps / is_beta, fp32.  Returns (rows the table spans, table, alpha, eps, beta)."""
+        import iqlhip_weighted as wtd
+        size, table, _ = self._weighted_args(replay_buffer, batch_size, weights)
+        updatable = replay_buffer._weights_updatable if weights is None else weights.updatable
+        if not updatable:
+            raise ValueError("iqlhip: prioritised replay needs updatable sample weights "
+                             "(set_sample_weights(..., updatable=True) / SampleWeights(..., updatable=True))")
+        alpha, eps = wtd.check_priority_args(alpha, eps)
+        beta = self._is_beta_arg(is_beta)
+        return size, table, alpha, eps, beta
+
+    def prepare_train_steps_prioritized(self, replay_buffer, batch_size: int, weights=None) -> None:
+        """prepare_train_steps for the chunk graphs train_steps_prioritized replays on this buffer and its updatable
+        weights (weights: a SampleWeights used instead).  Trains nothing and leaves the table as it is: the rehearsal's
+        update launches are switched off on the device."""
+        _, table, _, _, _ = self._prioritized_args(replay_buffer, batch_size, weights, 1.0, 1.0, 0.0)
+        self._prepare(batch_size)
+        self._refuse_injected_masks()
+        hb.check(hb.lib().iqlhip_train_steps_prioritized_prepare(
+            self._ctx, replay_buffer._rows.data_ptr(), replay_buffer._ld, batch_size, 1.0 / batch_size, self._stream(), table))
+        self._ts_token = None
+
+    def train_steps_prioritized(self, replay_buffer, n_steps: int, batch_size: int, seed: int = 0, alpha: float = 0.6,
+                                eps: float = 1e-3, is_beta: float = 0.0, chunk: int = K_MAX, return_losses: bool = True,
+                                return_stats: bool = False, weights=None):
+        """Prioritised experience replay without a host round trip: train_steps_weighted(..., is_beta=) whose steps write
+        their TD errors back into the (updatable) table as new priorities, (max(|q1 - y|, |q2 - y|) + eps) ** alpha, inside
+        the chunk graphs.  Per call: step 0's rows are drawn from the table as it stands; while step t runs, the rows of
+        step t + 1 are drawn (they see the updates of steps < t: a lag of one step, which keeps the draw off the critical
+        path); then table[rows of t] <- priorities of t.  Bit for bit the eager loop
+            idx, c = draw(0);  for t: nxt = draw(t + 1); train(gather(idx), loss_weights=c, return_td=True);
+                                      update_sample_weights_td(idx, last_td_errors(), alpha, eps); idx, c = nxt
+        whatever `chunk` is.  A call never starts on rows an earlier call staged: its step 0 is always a fresh draw, so
+        the result depends on how steps are cut into calls (3 + 2 steps differ from 5) but not on history; inside a call,
+        pieces of `chunk` steps go on with the lag-1 chain (chunk is rounded down to an even number, at least 2: a piece
+        must end on the staging half the next one starts on; with an odd batch_size the index stream skips half a counter
+        between library calls, as in train_steps, so every piece then starts with a fresh draw).  alpha, eps and is_beta are per call and re-capture
+        nothing.  The table's version moves with every library call: a train_steps_weighted call that follows gathers
+        afresh.  Returns what train_steps returns.  ValueError for a static table, for alpha, eps or is_beta negative or
+        not finite, for alpha = eps = 0; NotImplementedError at bf16 precision, under data parallelism and with injected
+        dropout masks pending — all before anything moves.  Not covered: trainer groups, mixed batches, online_step*,
+        priorities of newly added rows (follow add_transition with update_sample_weights), annealing inside a call."""
+        if return_stats and not self._step_stats:
+            raise ValueError("iqlhip: train_steps_prioritized(return_stats=True) needs set_step_stats(True) first")
+        size, table, alpha, eps, beta = self._prioritized_args(replay_buffer, batch_size, weights, alpha, eps, is_beta)
+        self._prepare(batch_size)
+        self._refuse_injected_masks()
+        fn, stream = hb.lib().iqlhip_train_steps_prioritized, self._stream()
+        rows_ptr, ld = replay_buffer._rows.data_ptr(), replay_buffer._ld
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+
+        def call(tab, k, offset, flags):
+            rc = fn(self._ctx, rows_ptr, ld, size, batch_size, tab.ctypes.data, k, seed, offset, flags, stream, table, beta,
+                    alpha, eps)
+            if rc == 0:                    # (the library moved the table's content version: the Python mirror follows)
+                if weights is None:
+                    replay_buffer._weights_version += 1
+                else:
+                    weights._version += 1
+            return rc
+
+        # the token names THIS Python call: no earlier call's token ever equals it, so the first piece draws afresh and
+        # only the pieces of this call continue each other
+        self._prio_calls = getattr(self, "_prio_calls", 0) + 1
+        tok = ("prioritized", self._prio_calls)
+        chunk = max(2, min(int(chunk), K_MAX) & ~1)
+        return self._run_burst(n_steps, batch_size, 1.0 / batch_size, chunk, return_losses, return_stats, stream, call,
+                               lambda: tok)
+
     def _schedule_state(self):
         sch = self.actor_lr_schedule
         lr = float(self.actor_optimizer.param_groups[0]["lr"])

@@ -98,6 +98,44 @@ def check_update_args(indices, weights, device=None) -> int:
     return int(indices.shape[0])
 
 
+def check_td_args(indices, td, device=None) -> int:
+    """The shape, dtype and device checks of an update by TD errors: int64 indices [m] and float32 TD errors [m, 2] (what
+    trainer.last_td_errors() returns), device tensors (no look at the values).  Returns m."""
+    import torch
+    if not isinstance(indices, torch.Tensor) or not isinstance(td, torch.Tensor):
+        raise ValueError("iqlhip: an update by TD errors takes torch tensors (indices int64, td float32 [m, 2])")
+    if indices.dtype != torch.int64:
+        raise ValueError(f"iqlhip: update indices must be int64 (got {indices.dtype})")
+    if td.dtype != torch.float32:
+        raise ValueError(f"iqlhip: TD errors must be float32 (got {td.dtype})")
+    if indices.ndim != 1 or td.ndim != 2 or td.shape[1] != 2:
+        raise ValueError(f"iqlhip: update indices must be [m] and TD errors [m, 2] (got {tuple(indices.shape)} and "
+                         f"{tuple(td.shape)})")
+    if indices.shape[0] != td.shape[0]:
+        raise ValueError(f"iqlhip: {indices.shape[0]} update indices for {td.shape[0]} rows of TD errors")
+    if device is not None and (indices.device != device or td.device != device):
+        raise ValueError(f"iqlhip: update indices and TD errors must live on the table's device ({device})")
+    return int(indices.shape[0])
+
+
+def check_priority_args(alpha, eps) -> tuple:
+    """(alpha, eps) of the priority (max(|e1|, |e2|) + eps) ** alpha, checked on the host as the library checks them:
+    finite floats >= 0, and not both 0 (a zero TD error would give log2(0) * 0).  ValueError otherwise."""
+    import math
+    out = []
+    for name, v in (("alpha", alpha), ("eps", eps)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"iqlhip: {name} must be a number, not {type(v).__name__}")
+        if not math.isfinite(f) or f < 0.0:
+            raise ValueError(f"iqlhip: {name} must be finite and >= 0 (got {v})")
+        out.append(f)
+    if out[0] == 0.0 and out[1] == 0.0:
+        raise ValueError("iqlhip: alpha = 0 needs eps > 0 (a zero TD error would give log2(0) * 0)")
+    return out[0], out[1]
+
+
 def build_table(w_dev, n: int, stream, updatable: bool = False, capacity=None, max_weight=None):
     """The library's table over the device vector w_dev[0..n): (handle, generation)."""
     import iqlhip_binding as hb
@@ -244,6 +282,28 @@ class SampleWeights:
         with torch.cuda.device(self._device):
             hb.check(hb.lib().iqlhip_weights_update(table, idx.data_ptr(), w.data_ptr(), m, bound,
                                                     torch.cuda.current_stream(self._device).cuda_stream))
+        self._version += 1
+
+    def update_td(self, indices, td, alpha, eps, bound=None) -> None:
+        """update() with weights[j] = (max(|td[j, 0]|, |td[j, 1]|) + eps) ** alpha formed on the device inside the update's
+        own launches (no torch arithmetic, no intermediate tensor): td is the [m, 2] float32 tensor
+        trainer.last_td_errors() returns, indices the rows of that step's batch.  A NaN or an infinity in a TD error is
+        skipped and flagged like a non-finite weight.  ValueError for a static table and for alpha or eps negative, not
+        finite or both 0."""
+        import torch
+        import iqlhip_binding as hb
+        table = self._alive()
+        if not self._updatable:
+            raise ValueError("iqlhip: these sample weights are not updatable (SampleWeights(..., updatable=True))")
+        m = check_td_args(indices, td, self._device)
+        alpha, eps = check_priority_args(alpha, eps)
+        bound = self._n if bound is None else int(bound)
+        if not 0 <= bound <= self._n:
+            raise ValueError(f"iqlhip: bound {bound} outside [0, {self._n}]")
+        idx, e = indices.contiguous(), td.contiguous()
+        with torch.cuda.device(self._device):
+            hb.check(hb.lib().iqlhip_weights_update_td(table, idx.data_ptr(), e.data_ptr(), m, bound, alpha, eps,
+                                                       torch.cuda.current_stream(self._device).cuda_stream))
         self._version += 1
 
     def flags(self) -> int:
