@@ -132,12 +132,35 @@ struct DevGuard {
   ~DevGuard() { if (switched) (void)hipSetDevice(prev); }
 };
 
-// What a captured chunk graph depends on through frozen kernel arguments.  The number of steps of a call is NOT part
-// of it: a call is composed of replays of the fixed chunk graphs (64, 16, 4, 2 steps and one), nothing is ever
-// captured per call length (kernel boundaries inside a graph are ~0.5 us shorter than between directly launched kernels).
 // What the table update inside a prioritised chunk needs of its updatable table beyond WTab (the launches' WUpd).
 struct PrioSrc { unsigned* stamp = nullptr; unsigned* flags = nullptr; unsigned long long* delta = nullptr; int sh0 = 0;
                  unsigned sat_bits = 0; };
+// The five kinds of chunk graph, one per pair of entry points (iqlhip_train_steps, _mixed, _weighted, _weighted_is,
+// _prioritized).  The values are the kernels' too: idle_block_work<MODE> of a kind's forward is numbered the same way.
+// What a kind implies for the driver stands in ONE place: kind_info(), in front of the multi-step driver.
+enum class ChunkKind : int { Plain = 0, Mixed = 1, Weighted = 2, WeightedIs = 3, Prio = 4 };
+constexpr int N_CHUNK_KINDS = 5;
+// What a chunk graph of a kind freezes beyond a plain chunk's: part of its key.  Mixed (GraphKey::rows = the offline
+// buffer): the online buffer and the batch rows that are not its; the three weighted kinds: the table the idle blocks
+// draw by; Prio: what the update launches behind every step are captured with.
+struct ChunkSrc {
+  ChunkKind kind = ChunkKind::Plain;
+  const float* rows_on = nullptr; int32_t n_off = 0; WTab wt{nullptr, 0u, 0}; PrioSrc up;
+  bool operator==(const ChunkSrc& o) const {
+    return kind == o.kind && rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n &&
+           wt.levels == o.wt.levels && wt.local == o.wt.local && up.stamp == o.up.stamp && up.flags == o.up.flags &&
+           up.delta == o.up.delta && up.sh0 == o.up.sh0 && up.sat_bits == o.up.sat_bits;
+  }
+};
+// ... and the values of ONE call, which the set-up kernel writes to device words and no graph freezes: the table's
+// generation and content version (what a following call must name to start on the rows this one staged:
+// iqlhip_weights_update moves the version), the importance-sampling exponent, the priority's alpha and eps, and live
+// (0: a rehearsal, whose update launches leave the table alone).  A mixed call's online size travels in the header
+// (HDR_SIZE_ON).  Named constructors: mixed_call, weighted_call, prio_call; ChunkCall() is a plain call.
+struct ChunkCall { ChunkSrc src; uint64_t wt_gen = 0, wt_ver = 0; float is_beta = 0.f, alpha = 0.f, eps = 0.f; unsigned live = 1u; };
+// What a captured chunk graph depends on through frozen kernel arguments.  The number of steps of a call is NOT part
+// of it: a call is composed of replays of the fixed chunk graphs (64, 16, 4, 2 steps and one), nothing is ever
+// captured per call length (kernel boundaries inside a graph are ~0.5 us shorter than between directly launched kernels).
 struct GraphKey {
   const float* rows = nullptr;
   int64_t ld = 0;
@@ -151,39 +174,12 @@ struct GraphKey {
   int head = 0;       // the chunk a call starts with: its graph begins with the call's set-up kernel (arguments set per replay)
   int stats = 0;      // captured with the statistics launches (iqlhip_set_step_stats): never replayed under the other setting
   int clip = 0;       // captured with the clip launches and the CLIP update kernel (iqlhip_set_grad_clip): likewise
-  // two-source chunks (iqlhip_train_steps_mixed; rows = the offline buffer): the online buffer and the batch rows that
-  // are not its.  rows_on == nullptr: a plain chunk — never replayed for a mixed call on the same rows, nor the reverse
-  const float* rows_on = nullptr;
-  int32_t n_off = 0;
-  // weighted chunks (iqlhip_train_steps_weighted): the table the idle blocks draw by.  wt.tab == nullptr: not one
-  WTab wt{nullptr, 0u, 0};
-  // ... with importance-sampling weights (iqlhip_train_steps_weighted_is): another forward and the row-weighted backward;
-  // 2: a prioritised chunk (iqlhip_train_steps_prioritized) — that plus the table update behind every step, `up` what its
-  // launches are captured with
-  int is = 0;
-  PrioSrc up;
+  ChunkSrc src;       // the chunk's kind and what it freezes: a chunk of one kind is never replayed for a call of another
   bool operator==(const GraphKey& o) const {
-    return is == o.is && up.stamp == o.up.stamp && up.flags == o.up.flags && up.delta == o.up.delta && up.sh0 == o.up.sh0 &&
-           up.sat_bits == o.up.sat_bits && rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
-           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip &&
-           rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n && wt.levels == o.wt.levels && wt.local == o.wt.local;
+    return src == o.src && rows == o.rows && ld == o.ld && B == o.B && K == o.K && params == o.params && drop_p == o.drop_p &&
+           inv_batch == o.inv_batch && xch == o.xch && parity == o.parity && head == o.head && stats == o.stats && clip == o.clip;
   }
 };
-// The second source of a mixed call, handed down to whatever forms a key, a set-up launch or an idle-work record
-// (nullptr everywhere: a plain call).  The online size is not here: it travels in the header (HDR_SIZE_ON).
-// A weighted call (iqlhip_train_steps_weighted) travels the same way: rows_on == nullptr, wt its table and wt_gen the
-// table's generation and wt_ver its content version (what a following call must name to start on the rows this one
-// staged: iqlhip_weights_update moves the version, the rows staged before it were drawn by the old weights).
-// is: a weighted call with importance-sampling weights (iqlhip_train_steps_weighted_is), is_beta its exponent — a value
-// of the CALL (the set-up kernel writes it to a device word), never part of a key.
-// is == 2: a prioritised call (iqlhip_train_steps_prioritized): `up` its table's update record (part of the key), alpha,
-// eps and live (0: a rehearsal, whose update launches leave the table alone) values of the call like is_beta.
-struct MixSrc { const float* rows_on; int n_off; WTab wt{nullptr, 0u, 0}; uint64_t wt_gen = 0; uint64_t wt_ver = 0;
-                int is = 0; float is_beta = 0.f; PrioSrc up{}; float alpha = 0.f, eps = 0.f; unsigned live = 1u; };
-// Which forward a step of such a call launches: 0 iql_fwd_kernel, 1 iql_fwd_mixed_kernel, 2 iql_fwd_weighted_kernel,
-// 3 iql_fwd_weighted_is_kernel (and then the row-weighted backward), 4 iql_fwd_prio_kernel (the row-weighted backward
-// storing the TD errors, and then the table update).
-static int fwd_kind(const MixSrc* mx) { return !mx ? 0 : (mx->wt.tab ? (mx->is == 2 ? 4 : mx->is ? 3 : 2) : 1); }
 
 // The few RCCL entry points the in-stream all-reduce needs, resolved at run time from the librccl.so.1 the process
 // already has (PyTorch-ROCm brings one) or can load — the library has no link-time dependency on RCCL.
@@ -249,16 +245,14 @@ struct iqlhip_ctx {
   unsigned long long sched_want[4] = {0, 0, 0, 0};
   unsigned long long call_seq = 0;
   unsigned* setup_arrivals = nullptr;           // device: block counter of iql_call_setup_kernel
-  bool weighted_lds_set = false;                // ... and the weighted ones (check_weighted_args)
-  bool weighted_is_lds_set = false;
+  // the forward instantiations of a chunk kind have their dynamic-LDS limit (ensure_fwd_lds; Plain: at creation)
+  bool fwd_lds_set[N_CHUNK_KINDS] = {false, false, false, false, false};
   // weighted calls with importance-sampling weights: [2][max_batch] staged q of the two staging parities, [max_batch] c of
   // the running step, the call's beta (one allocation, made by the first such call; addresses frozen in chunk graphs)
   float* is_buf = nullptr;
   // prioritised calls: [2][max_batch] int64 staged indices of the two staging parities, [max_batch][2] fp32 TD errors of
   // the running step, the call's alpha, eps and live word (one allocation, made by the first such call; frozen in graphs)
   char* prio_buf = nullptr;
-  bool prio_lds_set = false;
-  bool mixed_lds_set = false;                   // the mixed forward instantiations have their dynamic-LDS limit (check_mixed_args)
   char* prep_save = nullptr;                    // device: prepare's copy of the four arenas, kept (freeing it at the end of prepare
                                                 //   idles the GPU right in front of the caller's first steps)
   hipStream_t sched_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // (the stream a slot's reader was queued on)
@@ -295,7 +289,7 @@ struct iqlhip_ctx {
   struct { bool valid = false; const float* rows = nullptr; int64_t ld = 0, size = 0; int32_t B = 0; uint64_t seed = 0;
            uint64_t next_offset = 0; float drop_p = 0.f; uint64_t drop_seed = 0, drop_step = 0;
            uint64_t wt_gen = 0;      // the table generation of a weighted call (0: a plain call)
-           int is = 0;               // 1: that call staged the rows' q as well (iqlhip_train_steps_weighted_is)
+           int cont_class = 0;       // KindInfo::cont_class of that call: what it staged besides the rows
            uint64_t wt_ver = 0;      // ... and the table's content version at that call (iqlhip_weights_update adds 1)
          } cont;
   std::vector<CachedGraph> graphs;
@@ -501,6 +495,7 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   if (!rc) rc = set_max_lds(3, c->lds_bwd, [](unsigned m) { return bwd_kernel(m & 1, m & 2, m & 4); });
   if (!rc) rc = set_max_lds(1, c->lds_bwd_lb, [](unsigned m) { return bwd_rows_kernel(m & 1); });
   if (!rc) rc = set_max_lds(2, c->lds_bwd, [](unsigned m) { return bwd_rw_kernel(m & 1, m & 2); });
+  c->fwd_lds_set[(int)ChunkKind::Plain] = !rc;      // (the other kinds: ensure_fwd_lds, at their first call)
   return rc;
 }
 
@@ -884,20 +879,25 @@ static UpdParams make_upd(const iqlhip_ctx* c, const iqlhip_step_scalars* sc, in
 
 static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c->n_cus) ? c->lds_fwd_solo : c->lds_fwd; }
 
-static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);     // (end of file)
-static void launch_fwd_weighted_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
-static void launch_fwd_weighted_is_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);  // (end of file)
-static void launch_fwd_prio_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st);         // (end of file)
-static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, int kind = 0) {
-  if (kind == 1) return launch_fwd_mixed_grid(c, p, nb, st);
-  if (kind == 2) return launch_fwd_weighted_grid(c, p, nb, st);
-  if (kind == 4) return launch_fwd_prio_grid(c, p, nb, st);
-  if (kind == 3) return launch_fwd_weighted_is_grid(c, p, nb, st);
+// The training forward of a chunk kind: every one takes a StepParams.  Defined at the end of the file, behind the last
+// kind's selector — the selectors stand where their kernels are to lie in the code object (with_bools).
+static const void* fwd_kernel_of(ChunkKind kind, bool bf, bool dma, bool multi);
+static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, ChunkKind kind = ChunkKind::Plain) {
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
   // (policy inference — iqlhip_actor_forward — has its own instantiations)
-  const auto kernel = (p.only_inst >= 0) ? fwd_one_kernel(bf, dma) : fwd_kernel(bf, dma, multi);
-  hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
+  const void* kernel = (p.only_inst >= 0) ? (const void*)fwd_one_kernel(bf, dma) : fwd_kernel_of(kind, bf, dma, multi);
+  void* args[] = {const_cast<StepParams*>(&p)};
+  (void)hipLaunchKernel(kernel, dim3(nb), dim3(256), args, fwd_lds(c, nb), st);
+}
+// The dynamic-LDS allowance of a kind's forward instantiations, once per context: at the kind's first call, from its
+// argument check (the plain family has it from the context's creation).
+static int ensure_fwd_lds(iqlhip_ctx* c, ChunkKind kind) {
+  if (c->fwd_lds_set[(int)kind]) return IQLHIP_OK;
+  DevGuard guard(c->device);
+  if (int rc = set_max_lds(3, c->lds_fwd_solo, [kind](unsigned m) { return fwd_kernel_of(kind, m & 1, m & 2, m & 4); })) return rc;
+  c->fwd_lds_set[(int)kind] = true;
+  return IQLHIP_OK;
 }
 
 // Column slices per forward block (log2).  One block per (instance, row tile, slice) while that grid fits the chip in
@@ -913,7 +913,7 @@ static int fwd_spb_l2(const iqlhip_ctx* c, int n_rt) {
 // Blocks of a forward grid (per agent) over n_rt row tiles at 2^l2 slices per block.  (Full-width blocks: each XCD of
 // a net's pair takes the row tiles of one parity — iql_fwd_kernel's block map.)
 static int fwd_blocks(int n_rt, int l2) { return (l2 == 2) ? 8 * 2 * ((n_rt + 1) / 2) : 8 * n_rt * (NSPLIT >> l2); }
-static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st, int kind = 0) {
+static void launch_fwd(const iqlhip_ctx* c, const StepParams& p_in, hipStream_t st, ChunkKind kind = ChunkKind::Plain) {
   StepParams p = p_in;
   if (p.only_inst < 0 && use_lb(c, p.rows)) {
     const LbArgs a = lb_args(c, p.rows);
@@ -1482,9 +1482,9 @@ static XchParams make_xch(const iqlhip_ctx* c, bool from_hdr) {
 // `k` = position inside the chunk (selects the P2P buffer together with `parity`, and the flag value hdr[XSTEP]+k+1).
 // `sa` (statistics enabled): the two statistics launches between the backward and the update — after the last reader
 // of `heads`, before the update kernel, which is the last reader of the slabs and, in a chunk, moves the header word
-// the ring slot is formed from.  `kind`: fwd_kind of the call (a two-source or a weighted chunk has a forward of its own).
+// the ring slot is formed from.  `kind`: the chunk's (every kind but Plain has a forward of its own).
 static int enqueue_step(iqlhip_ctx* c, const StepParams& p_in, UpdParams u, int mode, int parity, int k, bool from_hdr,
-                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, int kind = 0,
+                        hipStream_t st, hipEvent_t* ev, const StatsArgs* sa = nullptr, ChunkKind kind = ChunkKind::Plain,
                         const RowWeights* rw = nullptr) {
   StepParams p = p_in;
   const int buf = (parity + k) & 1;
@@ -1686,7 +1686,7 @@ static int step_impl(iqlhip_ctx* c, const iqlhip_batch* b, const iqlhip_step_sca
     c->ev_used += 4;
     HIPCHK(hipEventRecord(ev[0], st));
   }
-  rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, e.stats(), 0, rw);
+  rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, ev, e.stats(), ChunkKind::Plain, rw);
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
   HIPCHK(hipGetLastError());
@@ -1894,9 +1894,37 @@ extern "C" int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, ui
 static long long* prio_idx(const iqlhip_ctx* c, int h) { return (long long*)c->prio_buf + (size_t)h * c->dims.max_batch; }
 static float* prio_td(const iqlhip_ctx* c) { return (float*)(c->prio_buf + 16 * (size_t)c->dims.max_batch); }
 static float* prio_words(const iqlhip_ctx* c) { return prio_td(c) + 2 * (size_t)c->dims.max_batch; }
+// What a chunk kind implies for the driver.  A sixth kind is added HERE (and gets a forward in fwd_kernel_of, a named
+// constructor and its pair of entry points); the driver below reads these fields and tests no kind itself.
+//   setup, n_args   the call's set-up kernel and how many arguments it takes (fill_setup_args checks its count against it)
+//   arg_groups      argument groups behind the fifteen common ones: {rows_on, n_off} (Mixed) or {wt}; {q_dst, beta_dev,
+//                   beta}; {idx_dst, prio_words, alpha, eps, live}
+//   rw_bwd          the row-weighted backward, its weights the c an idle block of the forward formed from the staged q
+//   td_store        ... which stores the rows' TD errors;  table_update: the table update behind every step
+//   wave_per_row    the set-up kernel draws step 0's rows by weight, a wave per row: its grid has a floor
+//   continues       a call may start on the rows the previous one staged and stages for the next — one of the same
+//   cont_class      only (what is staged besides the rows: nothing, q, q and indices)
+//   moves_version   a finished call has moved its table's content version by 1
+struct KindInfo { const void* setup; int n_args, arg_groups; bool rw_bwd, td_store, table_update, wave_per_row, continues;
+                  int cont_class; bool moves_version; };
+template <class... A> static KindInfo kind_row(void (*setup)(A...), int groups, bool rw, bool td, bool update, bool wave,
+                                               bool cont, int cont_class, bool version) {
+  return {(const void*)setup, (int)sizeof...(A), groups, rw, td, update, wave, cont, cont_class, version};
+}
+static const KindInfo& kind_info(ChunkKind kind) {
+  static const KindInfo info[N_CHUNK_KINDS] = {
+      //                                         groups rw_bwd td  update   wave   cont  class version
+      kind_row(iql_call_setup_kernel,             0, false, false, false, false, true,  0, false),      // Plain
+      kind_row(iql_call_setup_mixed_kernel,       1, false, false, false, false, false, 0, false),      // Mixed
+      kind_row(iql_call_setup_weighted_kernel,    1, false, false, false, true,  true,  0, false),      // Weighted
+      kind_row(iql_call_setup_weighted_is_kernel, 2, true,  false, false, true,  true,  1, false),      // WeightedIs
+      kind_row(iql_call_setup_prio_kernel,        3, true,  true,  true,  true,  true,  2, true)};       // Prio
+  return info[(int)kind];
+}
 // The table update behind step k of a prioritised chunk (end of file: its kernels are the library's last).
-static void launch_prio_update(const iqlhip_ctx* c, const MixSrc& mx, int B, int k, hipStream_t st);
-static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_dev, int B, int K, const MixSrc* mx) {
+static void launch_prio_update(const iqlhip_ctx* c, const ChunkSrc& src, int B, int k, hipStream_t st);
+static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_dev, int B, int K, const ChunkSrc& src) {
+  const KindInfo& ki = kind_info(src.kind);
   const int MB = c->dims.max_batch;
   for (int k = 0; k < K; ++k) {
     IdleWork& i = w[k];
@@ -1912,20 +1940,20 @@ static void fill_idle_work(const iqlhip_ctx* c, IdleWork* w, const float* rows_d
     i.drop_thresh = drop_thresh(c->drop_p);
     i.n = B;
     i.k = k;
-    if (mx) { i.rows_on = mx->rows_on; i.n_off = mx->n_off; i.wt = mx->wt; }
-    if (mx && mx->is) {       // step k's q lie in half k & 1 (where the step before staged them), step k + 1's go to the other
+    i.rows_on = src.rows_on; i.n_off = src.n_off; i.wt = src.wt;
+    if (ki.rw_bwd) {          // step k's q lie in half k & 1 (where the step before staged them), step k + 1's go to the other
       i.q_src = c->is_buf + (size_t)(k & 1) * MB;
       i.q_dst = c->is_buf + (size_t)((k + 1) & 1) * MB;
       i.c_dst = c->is_buf + 2 * (size_t)MB;
       i.is_beta = c->is_buf + 3 * (size_t)MB;
     }
-    if (mx && mx->is == 2) i.idx_dst = prio_idx(c, (k + 1) & 1);      // (as q_dst: step k + 1's half)
+    if (ki.table_update) i.idx_dst = prio_idx(c, (k + 1) & 1);      // (as q_dst: step k + 1's half)
   }
 }
 
 static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_batch, int mode, int parity,
-                         const IdleWork* work_dev, const MixSrc* mx = nullptr) {
-  const int kind = fwd_kind(mx);
+                         const IdleWork* work_dev, const ChunkSrc& src) {
+  const KindInfo& ki = kind_info(src.kind);
   const int MB = c->dims.max_batch;
   iqlhip_step_scalars sc0;
   memset(&sc0, 0, sizeof sc0);
@@ -1945,14 +1973,14 @@ static int enqueue_chunk(iqlhip_ctx* c, hipStream_t st, int B, int K, float inv_
     // (statistics: slot BASE + k of the ring, the loss ring's indexing; the chunk's key carries the setting)
     StatsArgs sa;
     if (c->stats_on) sa = make_stats(c, p, c->stats_ring, k, c->k_max, c->hdr);
-    // (kind 3 and 4: the step's c, written by an idle block of its forward, is the row-weighted backward's weight vector;
-    //  kind 4: the backward stores the rows' TD errors, the new priorities of the rows staged in half k & 1 — the update's
+    // (WeightedIs and Prio: the step's c, written by an idle block of its forward, is the row-weighted backward's weight
+    //  vector; Prio: the backward stores the rows' TD errors, the new priorities of the rows staged in half k & 1 — the update's
     //  launches follow the step on the same stream, a linear chain in front of the next forward, which draws by the table)
-    const RowWeights rw = {c->is_buf ? c->is_buf + 2 * (size_t)MB : nullptr, kind == 4 ? prio_td(c) : nullptr};
-    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, kind,
-                          kind >= 3 ? &rw : nullptr);
+    const RowWeights rw = {c->is_buf ? c->is_buf + 2 * (size_t)MB : nullptr, ki.td_store ? prio_td(c) : nullptr};
+    int rc = enqueue_step(c, p, u, mode, parity, k, /*from_hdr=*/true, st, nullptr, c->stats_on ? &sa : nullptr, src.kind,
+                          ki.rw_bwd ? &rw : nullptr);
     if (rc) return rc;
-    if (kind == 4) launch_prio_update(c, *mx, B, k, st);
+    if (ki.table_update) launch_prio_update(c, src, B, k, st);
   }
   return IQLHIP_OK;
 }
@@ -1978,16 +2006,18 @@ struct SetupArgs {
   unsigned long long* hdr; ChunkHdr h; iqlhip_step_scalars* sched_call; const iqlhip_step_scalars* sched_src; int n_steps;
   const float* rows; long long ld; float* xb; int B; unsigned* drop_dst; int drop_words; unsigned drop_thresh;
   unsigned* arrivals; unsigned long long* ack; unsigned long long ack_val;
-  const float* rows_on; int n_off;        // (iql_call_setup_mixed_kernel's two more)
-  WTab wt;                                // (iql_call_setup_weighted_kernel's one more, in their place)
-  float* q_dst; float* beta_dev; float beta;        // (iql_call_setup_weighted_is_kernel's three behind wt)
-  long long* idx_dst; float* prio_words; float alpha; float eps; unsigned live;      // (iql_call_setup_prio_kernel's five behind those)
+  const float* rows_on; int n_off;        // the kinds' argument groups (KindInfo::arg_groups): Mixed's two ...
+  WTab wt;                                // ... or, in their place, the table of the three weighted kinds
+  float* q_dst; float* beta_dev; float beta;        // WeightedIs and Prio
+  long long* idx_dst; float* prio_words; float alpha; float eps; unsigned live;      // Prio
   void* ptrs[24];
-  const void* func;                       // iql_call_setup_kernel, its two-source or its weighted form
+  const void* func;                       // KindInfo::setup of the call's kind
   int nb;
 };
-static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int slot, int n_steps, const float* rows_dev,
-                            int B, bool gather, hipStream_t st, const MixSrc* mx = nullptr) {
+static int fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int slot, int n_steps, const float* rows_dev,
+                           int B, bool gather, hipStream_t st, const ChunkCall& call) {
+  const ChunkSrc& src = call.src;
+  const KindInfo& ki = kind_info(src.kind);
   const int MB = c->dims.max_batch;
   const bool drop = gather && c->drop_p > 0.f;
   if (slot >= 0) {
@@ -2001,43 +2031,63 @@ static void fill_setup_args(iqlhip_ctx* c, SetupArgs& a, const ChunkHdr& h, int 
   a.arrivals = c->setup_arrivals;
   a.ack = slot >= 0 ? c->sched_ack + slot : c->sched_ack + 4;        // (slot < 0: a capture-time placeholder, word 4 is a dummy)
   a.ack_val = slot >= 0 ? c->sched_want[slot] : 0ull;
-  a.rows_on = mx ? mx->rows_on : nullptr; a.n_off = mx ? mx->n_off : 0;
-  const int kind = fwd_kind(mx);
-  a.wt = mx ? mx->wt : WTab{nullptr, 0u, 0};
-  a.q_dst = c->is_buf; a.beta_dev = c->is_buf ? c->is_buf + 3 * (size_t)MB : nullptr; a.beta = mx ? mx->is_beta : 0.f;
+  a.rows_on = src.rows_on; a.n_off = src.n_off; a.wt = src.wt;
+  a.q_dst = c->is_buf; a.beta_dev = c->is_buf ? c->is_buf + 3 * (size_t)MB : nullptr; a.beta = call.is_beta;
   a.idx_dst = c->prio_buf ? prio_idx(c, 0) : nullptr; a.prio_words = c->prio_buf ? prio_words(c) : nullptr;
-  a.alpha = mx ? mx->alpha : 0.f; a.eps = mx ? mx->eps : 0.f; a.live = mx ? mx->live : 0u;
-  a.func = kind == 4 ? (const void*)iql_call_setup_prio_kernel : kind == 3 ? (const void*)iql_call_setup_weighted_is_kernel : kind == 2 ? (const void*)iql_call_setup_weighted_kernel
-                     : (kind == 1 ? (const void*)iql_call_setup_mixed_kernel : (const void*)iql_call_setup_kernel);
-  void* p[24] = {&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst,
-                 &a.drop_words, &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val, &a.rows_on, &a.n_off};
-  if (kind >= 2) { p[15] = &a.wt; p[16] = nullptr; }
-  if (kind >= 3) { p[16] = &a.q_dst; p[17] = &a.beta_dev; p[18] = &a.beta; }
-  if (kind == 4) { p[19] = &a.idx_dst; p[20] = &a.prio_words; p[21] = &a.alpha; p[22] = &a.eps; p[23] = &a.live; }
-  memcpy(a.ptrs, p, sizeof p);
+  a.alpha = call.alpha; a.eps = call.eps; a.live = call.live;
+  a.func = ki.setup;
+  // the pointer array: the fifteen common arguments, then the kind's groups in order
+  int n = 0;
+  auto append = [&](std::initializer_list<void*> group) { for (void* q : group) a.ptrs[n++] = q; };
+  append({&a.hdr, &a.h, &a.sched_call, &a.sched_src, &a.n_steps, &a.rows, &a.ld, &a.xb, &a.B, &a.drop_dst, &a.drop_words,
+          &a.drop_thresh, &a.arrivals, &a.ack, &a.ack_val});
+  if (ki.arg_groups >= 1) src.kind == ChunkKind::Mixed ? append({&a.rows_on, &a.n_off}) : append({&a.wt});
+  if (ki.arg_groups >= 2) append({&a.q_dst, &a.beta_dev, &a.beta});
+  if (ki.arg_groups >= 3) append({&a.idx_dst, &a.prio_words, &a.alpha, &a.eps, &a.live});
+  if (n != ki.n_args) return fail(IQLHIP_EINVAL, "set-up kernel of chunk kind %d: %d arguments appended, it takes %d", (int)src.kind, n, ki.n_args);
   long long want = ((long long)n_steps * 3 + 255) / 256;
   if (gather) want = std::max(want, ((long long)B * (c->row_ld / 4) + 255) / 256);
-  if (gather && kind >= 2) want = std::max(want, ((long long)B + 7) / 8);      // (a wave per row, two rows a pass)
+  if (gather && ki.wave_per_row) want = std::max(want, ((long long)B + 7) / 8);      // (a wave per row, two rows a pass)
   if (drop) want += (2 * MB * 8 + 255) / 256;
   a.nb = (int)std::max<long long>(1, std::min<long long>(want, 256));
+  return IQLHIP_OK;
 }
 static int launch_call_setup(iqlhip_ctx* c, hipStream_t st, const ChunkHdr& h, int slot, int n_steps,
-                             const float* rows_dev, int B, bool gather, const MixSrc* mx = nullptr) {
+                             const float* rows_dev, int B, bool gather, const ChunkCall& call) {
   SetupArgs a;
-  fill_setup_args(c, a, h, slot, n_steps, rows_dev, B, gather, st, mx);
+  if (int rc = fill_setup_args(c, a, h, slot, n_steps, rows_dev, B, gather, st, call)) return rc;
   HIPCHK(hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, st));
   return IQLHIP_OK;
+}
+
+// The header a call's set-up kernel writes: what the index draw covers and where it stands, and the context's keep-bit
+// and exchange positions (c == nullptr: none of them — the placeholder a head chunk graph is captured with).
+static ChunkHdr call_hdr(const iqlhip_ctx* c, int64_t size, int64_t size_on, uint64_t seed, uint64_t offset) {
+  ChunkHdr h;
+  memset(&h, 0, sizeof h);
+  h.w[HDR_SIZE] = (unsigned long long)size;
+  h.w[HDR_SIZE_ON] = (unsigned long long)size_on;
+  h.w[HDR_SEED] = (unsigned long long)seed;
+  h.w[HDR_OFFSET] = (unsigned long long)offset;      // index j of the call = counter offset + j / 2, pair word j & 1
+  if (c) { h.w[HDR_DROP_STEP] = c->drop_step; h.w[HDR_DROP_SEED] = c->drop_seed; h.w[HDR_XSTEP] = c->xstep; }
+  return h;
+}
+// The n steps of chunk graph `cg` have been queued on `st`: the host's positions follow.  (The keep-bit position moves
+// with the steps that draw: a rate of 0 leaves it alone, as iqlhip_step does — a caller that switches the actor to
+// eval() for some steps finds the stream where eager steps would have left it.)
+static void chunk_queued(iqlhip_ctx* c, iqlhip_ctx::CachedGraph* cg, hipStream_t st, int n) {
+  cg->last = st;
+  if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
+  if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)n;
 }
 
 // Capture and instantiate the chunk graph of g.key into g, member by member (a failure leaves the ones made so far).
 static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   const GraphKey& key = g.key;
-  const MixSrc key_mx{key.rows_on, key.n_off, key.wt, 0, 0, key.is, 0.f, key.up};
-  const MixSrc* mx = (key.rows_on || key.wt.tab) ? &key_mx : nullptr;
   // the chunk's idle-work records: device memory written once, here (their content is part of what the key freezes)
   {
     std::vector<IdleWork> hw((size_t)key.K);
-    fill_idle_work(c, hw.data(), key.rows, key.B, key.K, mx);
+    fill_idle_work(c, hw.data(), key.rows, key.B, key.K, key.src);
     HIPCHK(hipMalloc((void**)&g.work, hw.size() * sizeof(IdleWork)));
     hipError_t e = hipMemcpy(g.work, hw.data(), hw.size() * sizeof(IdleWork), hipMemcpyHostToDevice);
     if (e != hipSuccess) return fail(IQLHIP_EHIP, "chunk_graph: hipMemcpy: %s", hipGetErrorString(e));
@@ -2048,15 +2098,14 @@ static int build_chunk_graph(iqlhip_ctx* c, iqlhip_ctx::CachedGraph& g) {
   if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamBeginCapture: %s", hipGetErrorString(e));
   int rc = IQLHIP_OK;
   if (key.head) {        // placeholder arguments: every replay sets the real ones (grid included)
-    ChunkHdr h0;
-    memset(&h0, 0, sizeof h0);
-    h0.w[HDR_SIZE] = h0.w[HDR_SIZE_ON] = 1ull;
+    ChunkCall placeholder;
+    placeholder.src = key.src;
     SetupArgs a;
-    fill_setup_args(c, a, h0, -1, 0, key.rows, key.B, true, cs, mx);
-    if (hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
+    rc = fill_setup_args(c, a, call_hdr(nullptr, 1, 1, 0, 0), -1, 0, key.rows, key.B, true, cs, placeholder);
+    if (!rc && hipLaunchKernel(a.func, dim3(a.nb), dim3(256), a.ptrs, 0, cs) != hipSuccess)
       rc = fail(IQLHIP_EHIP, "capture of the set-up kernel failed");
   }
-  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, mx);
+  if (!rc) rc = enqueue_chunk(c, cs, key.B, key.K, key.inv_batch, key.xch, key.parity, g.work, key.src);
   e = hipStreamEndCapture(cs, &g.graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(IQLHIP_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -2112,10 +2161,10 @@ static int inject_check(const iqlhip_ctx* c) {
 }
 
 static GraphKey make_key(const iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, int32_t K, float inv_batch,
-                         int parity, int head = 0, const MixSrc* mx = nullptr) {
+                         int parity, int head, const ChunkSrc& src) {
   GraphKey key;
   key.head = head;
-  if (mx) { key.rows_on = mx->rows_on; key.n_off = mx->n_off; key.wt = mx->wt; key.is = mx->is; key.up = mx->up; }
+  key.src = src;
   key.rows = rows_dev; key.ld = ld; key.B = B; key.K = K; key.params = c->params; key.drop_p = c->drop_p;
   key.inv_batch = inv_batch; key.xch = c->xch_mode;
   key.parity = (c->xch_mode == IQLHIP_XCH_P2P) ? parity : 0;
@@ -2139,25 +2188,28 @@ static const int g_head_mode = [] {
 static const bool g_direct_head = g_head_mode == 0;
 static const bool g_no_head_graph = g_head_mode == 2;
 static const bool g_direct_all = getenv("IQLHIP_DIRECT_ALL") != nullptr;           // diagnostic: no graph replays at all
-static int n_chunks_for(int rem) {
-  int n = rem / GRAPH_STEPS;
+// What is left of a call behind its head, as chunk graphs: n64 of 64 steps, and the rest in sizes 16, 4, 2 and 1,
+// largest first (<= 3 + 3 + 1 + 1 entries).
+struct ChunkPlan { int n64 = 0; int small[8]; int ns = 0; };
+static ChunkPlan plan_chunks(int rem) {
+  ChunkPlan pl;
+  pl.n64 = rem / GRAPH_STEPS;
   rem %= GRAPH_STEPS;
-  for (int cs_ : {16, 4, 2, 1}) { n += rem / cs_; rem %= cs_; }
-  return n;
+  for (int cs_ : {16, 4, 2, 1}) while (rem >= cs_) { pl.small[pl.ns++] = cs_; rem -= cs_; }
+  return pl;
 }
+static int n_chunks_for(int rem) { const ChunkPlan pl = plan_chunks(rem); return pl.n64 + pl.ns; }
 static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, int64_t ld, int B, int n, float inv_batch,
-                        const SetupArgs* head_args, const MixSrc* mx = nullptr) {
+                        const SetupArgs* head_args, const ChunkSrc& src) {
   const int parity = (int)(c->xstep & 1ull);
   hipGraphExec_t gexec = nullptr;
   iqlhip_ctx::CachedGraph* cg = nullptr;
-  int r = chunk_graph(c, make_key(c, rows_dev, ld, B, n, inv_batch, parity, head_args ? 1 : 0, mx), &gexec, &cg);
+  int r = chunk_graph(c, make_key(c, rows_dev, ld, B, n, inv_batch, parity, head_args ? 1 : 0, src), &gexec, &cg);
   if (r) return r;
   if (g_direct_all && !head_args) {      // experiment: the chunk's kernels launched one by one instead of the graph replay
-    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, mx);
+    r = enqueue_chunk(c, st, B, n, inv_batch, c->xch_mode, parity, cg->work, src);
     if (r) return r;
-    cg->last = st;
-    if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
-    if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)n;
+    chunk_queued(c, cg, st, n);
     return IQLHIP_OK;
   }
   if (head_args) {
@@ -2170,18 +2222,14 @@ static int replay_chunk(iqlhip_ctx* c, hipStream_t st, const float* rows_dev, in
     HIPCHK(hipGraphExecKernelNodeSetParams(gexec, cg->setup_node, &np));
   }
   HIPCHK(hipGraphLaunch(gexec, st));
-  cg->last = st;
-  // (the keep-bit position moves with the steps that draw: a rate of 0 leaves it alone, as iqlhip_step does — a caller
-  //  that switches the actor to eval() for some steps finds the stream where eager steps would have left it)
-  if (c->drop_p > 0.f) c->drop_step += (unsigned long long)n;
-  if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)n;
+  chunk_queued(c, cg, st, n);
   return IQLHIP_OK;
 }
 
-// iqlhip_train_steps_prepare (mx == nullptr) and iqlhip_train_steps_mixed_prepare: the chunk graphs of the plain or of
-// the two-source kind.
+// The five *_prepare entry points behind their argument checks: the chunk graphs of the call's kind, captured and
+// rehearsed.
 static int train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, float inv_batch, void* stream,
-                               const MixSrc* mx) {
+                               const ChunkCall& call) {
   int rc = IQLHIP_OK;
   if ((rc = step_entry(c, B, stream, /*multi_step=*/true))) return rc;
   DevGuard guard(c->device);
@@ -2231,20 +2279,15 @@ static int train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld,
     struct Item { int K; int head; };
     const Item items[] = {{2, 1}, {GRAPH_STEPS, 0}, {16, 0}, {4, 0}, {2, 0}, {1, 0}};
     auto rehearse = [&](const Item& it) -> int {
-      ChunkHdr h;
-      memset(&h, 0, sizeof h);
-      h.w[HDR_SIZE] = h.w[HDR_SIZE_ON] = 1ull;
-      h.w[HDR_DROP_STEP] = c->drop_step;
-      h.w[HDR_DROP_SEED] = c->drop_seed;
-      h.w[HDR_XSTEP] = c->xstep;
+      const ChunkHdr h = call_hdr(c, 1, 1, 0, 0);
       if (it.head) {
         SetupArgs a;
-        fill_setup_args(c, a, h, slot, it.K, rows_dev, B, /*gather=*/true, cs, mx);
-        return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, &a, mx);
+        if (int r = fill_setup_args(c, a, h, slot, it.K, rows_dev, B, /*gather=*/true, cs, call)) return r;
+        return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, &a, call.src);
       }
-      int r = launch_call_setup(c, cs, h, slot, it.K, rows_dev, B, /*gather=*/true, mx);
+      int r = launch_call_setup(c, cs, h, slot, it.K, rows_dev, B, /*gather=*/true, call);
       if (r) return r;
-      return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, nullptr, mx);
+      return replay_chunk(c, cs, rows_dev, ld, B, it.K, inv_batch, nullptr, call.src);
     };
     for (int pass = 0; pass < passes && !rc; ++pass)
       for (const Item& it : items) { if (it.head && g_head_mode != 1) continue; rc = rehearse(it); if (rc) break; }
@@ -2255,14 +2298,10 @@ static int train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld,
     // (profiles/r03_first_call.txt).  IQLHIP_PREPARE_WARM_CHUNKS: how many (default 16 = 1 024 steps, ~22 ms; 0 = none).
     static const int n_warm = getenv("IQLHIP_PREPARE_WARM_CHUNKS") ? std::max(0, atoi(getenv("IQLHIP_PREPARE_WARM_CHUNKS"))) : 16;
     if (!rc && n_warm > 0 && c->xch_mode == IQLHIP_XCH_NONE) {
-      ChunkHdr h;
-      memset(&h, 0, sizeof h);
-      h.w[HDR_SIZE] = h.w[HDR_SIZE_ON] = 1ull;
-      h.w[HDR_DROP_STEP] = c->drop_step;
-      h.w[HDR_DROP_SEED] = c->drop_seed;
+      const ChunkHdr h = call_hdr(c, 1, 1, 0, 0);      // (no exchange here: the header's exchange step is not read)
       for (int i = 0; i < n_warm && !rc; ++i) {
-        if ((i % (c->k_max / GRAPH_STEPS)) == 0) rc = launch_call_setup(c, cs, h, slot, c->k_max, rows_dev, B, /*gather=*/true, mx);
-        if (!rc) rc = replay_chunk(c, cs, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr, mx);
+        if ((i % (c->k_max / GRAPH_STEPS)) == 0) rc = launch_call_setup(c, cs, h, slot, c->k_max, rows_dev, B, /*gather=*/true, call);
+        if (!rc) rc = replay_chunk(c, cs, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr, call.src);
       }
     }
   } while (0);
@@ -2279,14 +2318,16 @@ extern "C" int iqlhip_train_steps_prepare(iqlhip_ctx* c, const float* rows_dev, 
                                           void* stream) {
   int rc = check_train_args(c, rows_dev, ld, B);
   if (rc) return rc;
-  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, nullptr);
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, ChunkCall());
 }
 
-// iqlhip_train_steps (mx == nullptr) and iqlhip_train_steps_mixed (rows_dev / size: the offline buffer; size_on: the rows
-// the online part's draw covers) behind their argument checks.
+// The five iqlhip_train_steps* entry points behind their argument checks (a mixed call: rows_dev / size are the offline
+// buffer, size_on the rows the online part's draw covers; 0 for every other kind).
 static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
                        const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset, int32_t flags,
-                       void* stream, const MixSrc* mx, int64_t size_on) {
+                       void* stream, const ChunkCall& call, int64_t size_on) {
+  const ChunkSrc& src = call.src;
+  const KindInfo& ki = kind_info(src.kind);
   int rc = IQLHIP_OK;
   if (K < 1 || K > c->k_max) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", c->k_max);
   if (size < 1) return fail(IQLHIP_EINVAL, "empty buffer");
@@ -2312,26 +2353,15 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // does this call continue the previous one's index stream with its step 0 already staged?  (Never a mixed call: the
   // rows its last forward staged are not what a plain call would draw, so it claims nothing and leaves no token.)
   // A weighted call continues a weighted call on the same table generation only, and a plain call a plain one.
-  const int kind = fwd_kind(mx);
-  const uint64_t wt_gen = kind >= 2 ? mx->wt_gen : 0, wt_ver = kind >= 2 ? mx->wt_ver : 0;
-  // (the rows a call without staged q left cannot start a call that needs them, nor those of one without staged indices;
-  //  a prioritised call continues only a prioritised one: its rows were drawn one update behind, the lag-1 chain)
-  const int is_call = kind == 4 ? 2 : kind == 3 ? 1 : 0;
-  const bool cont = kind != 1 && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == wt_gen && c->cont.is == is_call &&
-                    c->cont.wt_ver == wt_ver &&
+  // (the rows a call without staged q left cannot start a call that needs them, nor those of one without staged indices:
+  //  cont_class; a prioritised call continues only a prioritised one: its rows were drawn one update behind, the lag-1 chain)
+  const bool cont = ki.continues && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == call.wt_gen &&
+                    c->cont.cont_class == ki.cont_class && c->cont.wt_ver == call.wt_ver &&
                     c->cont.rows == rows_dev && c->cont.ld == ld &&
                     c->cont.size == size && c->cont.B == B && c->cont.seed == seed && c->cont.next_offset == stream_offset &&
                     c->cont.drop_p == c->drop_p && c->cont.drop_seed == c->drop_seed && c->cont.drop_step == c->drop_step;
   c->cont.valid = false;
-  ChunkHdr h;
-  memset(&h, 0, sizeof h);
-  h.w[HDR_SIZE] = (unsigned long long)size;
-  h.w[HDR_SIZE_ON] = (unsigned long long)size_on;
-  h.w[HDR_SEED] = (unsigned long long)seed;
-  h.w[HDR_OFFSET] = (unsigned long long)stream_offset;     // index j of the call = counter offset + j / 2, pair word j & 1
-  h.w[HDR_DROP_STEP] = c->drop_step;
-  h.w[HDR_DROP_SEED] = c->drop_seed;
-  h.w[HDR_XSTEP] = c->xstep;
+  const ChunkHdr h = call_hdr(c, size, size_on, seed, stream_offset);
   refresh_shadows(c, st);
   if (g_trace) tr_t[1] = now_us();
   // The call's HEAD — the set-up kernel and the first 2 or 4 steps (1 for a one-step call) — is launched kernel by
@@ -2347,42 +2377,37 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
     const int parity = (int)(c->xstep & 1ull);
     hipGraphExec_t gexec = nullptr;
     iqlhip_ctx::CachedGraph* cg = nullptr;
-    rc = chunk_graph(c, make_key(c, rows_dev, ld, B, head_k, inv_batch, parity, 0, mx), &gexec, &cg);     // (for its idle-work records)
+    rc = chunk_graph(c, make_key(c, rows_dev, ld, B, head_k, inv_batch, parity, 0, src), &gexec, &cg);     // (for its idle-work records)
     if (rc) return rc;
-    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, mx);
+    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, call);
     if (rc) return rc;
-    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, mx);
+    rc = enqueue_chunk(c, st, B, head_k, inv_batch, c->xch_mode, parity, cg->work, src);
     if (rc) return rc;
-    cg->last = st;
-    if (c->drop_p > 0.f) c->drop_step += (unsigned long long)head_k;
-    if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += (unsigned long long)head_k;
+    chunk_queued(c, cg, st, head_k);
     rem = K - head_k;
   } else if (g_no_head_graph) {
-    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, mx);
+    rc = launch_call_setup(c, st, h, slot, K, rows_dev, B, /*gather=*/!cont, call);
     if (rc) return rc;
     rem = K;
   } else {
     const int head_k = (K >= 2) ? 2 : 1;
     SetupArgs a;
-    fill_setup_args(c, a, h, slot, K, rows_dev, B, /*gather=*/!cont, st, mx);
-    rc = replay_chunk(c, st, rows_dev, ld, B, head_k, inv_batch, &a, mx);
+    if ((rc = fill_setup_args(c, a, h, slot, K, rows_dev, B, /*gather=*/!cont, st, call))) return rc;
+    rc = replay_chunk(c, st, rows_dev, ld, B, head_k, inv_batch, &a, src);
     if (rc) return rc;
     rem = K - head_k;
   }
   if (g_trace) tr_t[2] = tr_t[3] = now_us();
-  const int n64 = rem / GRAPH_STEPS;
-  rem %= GRAPH_STEPS;
-  int small[8], ns = 0;
-  for (int cs_ : {16, 4, 2, 1}) while (rem >= cs_) { small[ns++] = cs_; rem -= cs_; }     // (<= 3 + 3 + 1 + 1 entries)
-  for (int i = ns - 1; i >= 0; --i) if (small[i] != 1) { rc = replay_chunk(c, st, rows_dev, ld, B, small[i], inv_batch, nullptr, mx); if (rc) return rc; }
-  for (int i = 0; i < n64; ++i) { rc = replay_chunk(c, st, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr, mx); if (rc) return rc; }
-  if (ns > 0 && small[ns - 1] == 1) { rc = replay_chunk(c, st, rows_dev, ld, B, 1, inv_batch, nullptr, mx); if (rc) return rc; }
+  const ChunkPlan pl = plan_chunks(rem);
+  for (int i = pl.ns - 1; i >= 0; --i) if (pl.small[i] != 1) { rc = replay_chunk(c, st, rows_dev, ld, B, pl.small[i], inv_batch, nullptr, src); if (rc) return rc; }
+  for (int i = 0; i < pl.n64; ++i) { rc = replay_chunk(c, st, rows_dev, ld, B, GRAPH_STEPS, inv_batch, nullptr, src); if (rc) return rc; }
+  if (pl.ns > 0 && pl.small[pl.ns - 1] == 1) { rc = replay_chunk(c, st, rows_dev, ld, B, 1, inv_batch, nullptr, src); if (rc) return rc; }
   // what a following call must look like to start on the rows this call's last forward has staged: an even number of
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
-  if (kind != 1 && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
+  if (ki.continues && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
     // (a prioritised call moves its table's version by 1 itself: iqlhip_train_steps_prioritized)
-    c->cont.wt_gen = wt_gen; c->cont.wt_ver = wt_ver + (kind == 4 ? 1 : 0); c->cont.is = is_call;
+    c->cont.wt_gen = call.wt_gen; c->cont.wt_ver = call.wt_ver + (ki.moves_version ? 1 : 0); c->cont.cont_class = ki.cont_class;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
     c->cont.next_offset = stream_offset + ((unsigned long long)K * (unsigned long long)B) / 2ull;
     c->cont.drop_p = c->drop_p; c->cont.drop_seed = c->drop_seed; c->cont.drop_step = c->drop_step;
@@ -2408,7 +2433,7 @@ extern "C" int iqlhip_train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t 
   if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_train_args(c, rows_dev, ld, B);
   if (rc) return rc;
-  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, nullptr, 0);
+  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, ChunkCall(), 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -3346,7 +3371,7 @@ extern "C" int iqlhip_group_step_mixed(iqlhip_group* g, const iqlhip_batch* batc
   return group_step(g, batches, sc, out, stream, /*mixed=*/true);
 }
 
-// The second source of a two-source group call, per member (the group form of MixSrc): iqlhip_group_train_steps_replay2
+// The second source of a two-source group call, per member (the group form of a Mixed ChunkSrc): iqlhip_group_train_steps_replay2
 // draws batch rows >= n_off[i] over [0, size[i]) from rows[i] — the online buffers; iqlhip_group_online_step_replay2
 // reads batch rows < n_off[i] from rows[i] — the offline buffers of size[i] rows.
 struct GroupMixSrc { const float* const* rows; const int64_t* size; const int32_t* n_off; };
@@ -3762,7 +3787,7 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
 
 // ---------------------------------------------------------------------------
 // Two-source multi-step calls (include/iqlhip.h "mixed offline / online batches"): iqlhip_train_steps with every batch's
-// first n_off rows drawn from one buffer and the rest from another.  The driver above does the work (MixSrc); here are
+// first n_off rows drawn from one buffer and the rest from another.  The driver above does the work (ChunkKind::Mixed); here are
 // the forward instantiations of such chunks — selected and emitted behind every other kernel of the library, so the
 // code object of the plain calls' kernels lies where it always has (with_bools) — and the entry points' checks.
 // (The two kernels below are declared in iqlhip_kernels.h and defined here for the same reason.)
@@ -3813,10 +3838,6 @@ __global__ __launch_bounds__(256) void iql_online_gather2_kernel(float* rows, co
 static auto fwd_mixed_kernel(bool bf, bool dma, bool multi) {
   return with_bools([](auto MU, auto BF, auto DMA) { return &iql_fwd_mixed_kernel<BF.value, DMA.value, MU.value>; }, multi, bf, dma);
 }
-static void launch_fwd_mixed_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
-  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
-  hipLaunchKernelGGL(fwd_mixed_kernel(c->precision == 1, dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
-}
 static int check_mixed_args(iqlhip_ctx* c, const float* rows_off_dev, const float* rows_on_dev, int64_t ld, int32_t B,
                             int32_t n_off) {
   int rc = check_train_args(c, rows_off_dev, ld, B);
@@ -3829,21 +3850,18 @@ static int check_mixed_args(iqlhip_ctx* c, const float* rows_off_dev, const floa
     return fail(IQLHIP_EUNSUPPORTED, "mixed batches are not supported with a data-parallel exchange");
   if (use_lb(c, B))
     return fail(IQLHIP_EUNSUPPORTED, "mixed batches are not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
-  // (dynamic LDS of the mixed forward instantiations: once per context, here rather than with the other families)
-  if (!c->mixed_lds_set) {
-    DevGuard guard(c->device);
-    rc = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_mixed_kernel(m & 1, m & 2, m & 4); });
-    if (rc) return rc;
-    c->mixed_lds_set = true;
-  }
-  return IQLHIP_OK;
+  return ensure_fwd_lds(c, ChunkKind::Mixed);
+}
+static ChunkCall mixed_call(const float* rows_on_dev, int32_t n_off) {
+  ChunkCall call;
+  call.src.kind = ChunkKind::Mixed; call.src.rows_on = rows_on_dev; call.src.n_off = n_off;
+  return call;
 }
 extern "C" int iqlhip_train_steps_mixed_prepare(iqlhip_ctx* c, const float* rows_off_dev, const float* rows_on_dev, int64_t ld,
                                                 int32_t B, int32_t n_off, float inv_batch, void* stream) {
   int rc = check_mixed_args(c, rows_off_dev, rows_on_dev, ld, B, n_off);
   if (rc) return rc;
-  const MixSrc mx{rows_on_dev, n_off};
-  return train_steps_prepare(c, rows_off_dev, ld, B, inv_batch, stream, &mx);
+  return train_steps_prepare(c, rows_off_dev, ld, B, inv_batch, stream, mixed_call(rows_on_dev, n_off));
 }
 extern "C" int iqlhip_train_steps_mixed(iqlhip_ctx* c, const float* rows_off_dev, int64_t size_off, const float* rows_on_dev,
                                         int64_t size_on, int64_t ld, int32_t B, int32_t n_off,
@@ -3853,8 +3871,7 @@ extern "C" int iqlhip_train_steps_mixed(iqlhip_ctx* c, const float* rows_off_dev
   int rc = check_mixed_args(c, rows_off_dev, rows_on_dev, ld, B, n_off);
   if (rc) return rc;
   if (size_on < 1) return fail(IQLHIP_EINVAL, "empty online buffer");
-  const MixSrc mx{rows_on_dev, n_off};
-  return train_steps(c, rows_off_dev, ld, size_off, B, sc, K, seed, stream_offset, 0, stream, &mx, size_on);
+  return train_steps(c, rows_off_dev, ld, size_off, B, sc, K, seed, stream_offset, 0, stream, mixed_call(rows_on_dev, n_off), size_on);
 }
 
 // ---------------------------------------------------------------------------
@@ -4261,7 +4278,7 @@ extern "C" int iqlhip_pack_rows(iqlhip_ctx* c, const iqlhip_batch* b, float* row
 // Weighted replay sampling (include/iqlhip.h "weighted replay sampling"; kernels: iqlhip_weighted_kernels.h, included
 // HERE, behind every other kernel of the file, as the scoring kernels are).  A table is an object of its own, not part
 // of a context: a replay buffer owns it, any context on its device may draw by it.  The multi-step driver above does
-// the rest (MixSrc::wt).
+// the rest (ChunkSrc::wt).
 #include "iqlhip_weighted_kernels.h"
 struct iqlhip_weights {
   Owned own;                              // the table, and the build's scratch
@@ -4507,10 +4524,6 @@ extern "C" int iqlhip_draw_indices_weighted(int64_t* idx_dev, int64_t n_idx, con
 static auto fwd_weighted_kernel(bool bf, bool dma, bool multi) {
   return with_bools([](auto MU, auto BF, auto DMA) { return &iql_fwd_weighted_kernel<BF.value, DMA.value, MU.value>; }, multi, bf, dma);
 }
-static void launch_fwd_weighted_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
-  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
-  hipLaunchKernelGGL(fwd_weighted_kernel(c->precision == 1, dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
-}
 // Everything a weighted multi-step call is refused for, before anything is launched or any counter moves (pending
 // injected keep-bits: step_entry, as for iqlhip_train_steps).
 static int check_weighted_args(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
@@ -4525,20 +4538,20 @@ static int check_weighted_args(iqlhip_ctx* c, const float* rows_dev, int64_t ld,
   if (use_lb(c, B))
     return fail(IQLHIP_EUNSUPPORTED, "weighted sampling is not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
   if ((rc = inject_check(c))) return rc;
-  if (!c->weighted_lds_set) {
-    DevGuard guard(c->device);
-    rc = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_weighted_kernel(m & 1, m & 2, m & 4); });
-    if (rc) return rc;
-    c->weighted_lds_set = true;
-  }
-  return IQLHIP_OK;
+  return ensure_fwd_lds(c, ChunkKind::Weighted);
+}
+// A call of one of the three kinds that draw by `t`: Weighted, WeightedIs (is_beta its exponent) or — prio_call — Prio.
+static ChunkCall weighted_call(const iqlhip_weights* t, ChunkKind kind = ChunkKind::Weighted, float is_beta = 0.f) {
+  ChunkCall call;
+  call.src.kind = kind; call.src.wt = weights_tab(t);
+  call.wt_gen = t->gen; call.wt_ver = t->version; call.is_beta = is_beta;
+  return call;
 }
 extern "C" int iqlhip_train_steps_weighted_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B, float inv_batch,
                                                    void* stream, const iqlhip_weights* table) {
   int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
   if (rc) return rc;
-  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version};
-  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, weighted_call(table));
 }
 extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
                                            const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
@@ -4546,31 +4559,37 @@ extern "C" int iqlhip_train_steps_weighted(iqlhip_ctx* c, const float* rows_dev,
   if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
   if (rc) return rc;
-  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version};
-  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
+  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, weighted_call(table), 0);
 }
 
 // ... with importance-sampling weights (include/iqlhip.h iqlhip_train_steps_weighted_is): chunk graphs of a
 // kind of their own — iql_fwd_weighted_is_kernel, whose idle blocks also stage the drawn rows' q and form the step's c,
 // and the row-weighted backward.  The kernels: iqlhip_isweight_kernels.h, behind every other kernel (end of file).
-static int weighted_is_setup(iqlhip_ctx* c, int32_t B, float is_beta);
+// What such a call needs beyond check_weighted_args, before anything is launched or any counter moves: fp32, a valid
+// exponent, the staging buffers and the forward's LDS allowance.
+static int weighted_is_setup(iqlhip_ctx* c, float is_beta) {
+  if (!(is_beta >= 0.f) || !std::isfinite(is_beta)) return fail(IQLHIP_EINVAL, "is_beta must be finite and >= 0");
+  if (c->precision == 1) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported at bf16 precision");
+  DevGuard guard(c->device);
+  if (!c->is_buf) HIPCHK(c->own.dev(&c->is_buf, (3 * (size_t)c->dims.max_batch + 4) * sizeof(float), 0));
+  return ensure_fwd_lds(c, ChunkKind::WeightedIs);
+}
 extern "C" int iqlhip_train_steps_weighted_is_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B,
                                                       float inv_batch, void* stream, const iqlhip_weights* table) {
   int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
-  if (!rc) rc = weighted_is_setup(c, B, 0.f);
+  if (!rc) rc = weighted_is_setup(c, 0.f);
   if (rc) return rc;
-  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version, 1, 0.f};
-  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, weighted_call(table, ChunkKind::WeightedIs));
 }
 extern "C" int iqlhip_train_steps_weighted_is(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
                                               const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
                                               int32_t flags, void* stream, const iqlhip_weights* table, float is_beta) {
   if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
-  if (!rc) rc = weighted_is_setup(c, B, is_beta);
+  if (!rc) rc = weighted_is_setup(c, is_beta);
   if (rc) return rc;
-  const MixSrc mx{nullptr, 0, weights_tab(table), table->gen, table->version, 1, is_beta};
-  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
+  return train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream,
+                     weighted_call(table, ChunkKind::WeightedIs, is_beta), 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -4989,25 +5008,6 @@ extern "C" int iqlhip_draw_indices_weighted_is(int64_t* idx_dev, float* c_dev, i
 static auto fwd_weighted_is_kernel(bool dma, bool multi) {      // (fp32 only: the row-weighted backward is)
   return with_bools([](auto MU, auto DMA) { return &iql_fwd_weighted_is_kernel<DMA.value, MU.value>; }, multi, dma);
 }
-static void launch_fwd_weighted_is_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
-  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
-  hipLaunchKernelGGL(fwd_weighted_is_kernel(dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
-}
-// What a weighted call with importance-sampling weights needs beyond check_weighted_args, before anything is launched
-// or any counter moves: fp32, a valid exponent, the staging buffers and the forward's LDS allowance.
-static int weighted_is_setup(iqlhip_ctx* c, int32_t B, float is_beta) {
-  (void)B;
-  if (!(is_beta >= 0.f) || !std::isfinite(is_beta)) return fail(IQLHIP_EINVAL, "is_beta must be finite and >= 0");
-  if (c->precision == 1) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported at bf16 precision");
-  DevGuard guard(c->device);
-  if (!c->is_buf) HIPCHK(c->own.dev(&c->is_buf, (3 * (size_t)c->dims.max_batch + 4) * sizeof(float), 0));
-  if (!c->weighted_is_lds_set) {
-    int rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_weighted_is_kernel(m & 1, m & 2); });
-    if (rc) return rc;
-    c->weighted_is_lds_set = true;
-  }
-  return IQLHIP_OK;
-}
 
 // ---------------------------------------------------------------------------
 // (declared next to the other selectors; here so that its instantiations are the code object's last)
@@ -5062,17 +5062,24 @@ extern "C" int iqlhip_weights_update_td(iqlhip_weights* t, const int64_t* idx_de
 static auto fwd_prio_kernel(bool dma, bool multi) {      // (fp32 only: the row-weighted backward is)
   return with_bools([](auto MU, auto DMA) { return &iql_fwd_prio_kernel<DMA.value, MU.value>; }, multi, dma);
 }
-static void launch_fwd_prio_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st) {
-  const bool dma = c->w0_lds_k > W0_LDS_MAX_K;
-  hipLaunchKernelGGL(fwd_prio_kernel(dma, (p.spb_l2 & 3) > 0), dim3(nb), dim3(256), fwd_lds(c, nb), st, p);
+// (declared in front of launch_fwd_grid; here, behind the last kind's selector)
+static const void* fwd_kernel_of(ChunkKind kind, bool bf, bool dma, bool multi) {
+  switch (kind) {
+    case ChunkKind::Plain: return (const void*)fwd_kernel(bf, dma, multi);
+    case ChunkKind::Mixed: return (const void*)fwd_mixed_kernel(bf, dma, multi);
+    case ChunkKind::Weighted: return (const void*)fwd_weighted_kernel(bf, dma, multi);
+    case ChunkKind::WeightedIs: return (const void*)fwd_weighted_is_kernel(dma, multi);      // (fp32 only, as Prio)
+    case ChunkKind::Prio: return (const void*)fwd_prio_kernel(dma, multi);
+  }
+  return nullptr;
 }
 // Step k of a prioritised chunk has run: table[idx of staging half k & 1] <- td_priority(its TD errors), alpha, eps and the
 // live word read from the call's device words.  m, bound and every pointer are constants of the chunk graph.
-static void launch_prio_update(const iqlhip_ctx* c, const MixSrc& mx, int B, int k, hipStream_t st) {
-  const WUpd u{const_cast<unsigned long long*>(mx.wt.tab), mx.up.stamp, mx.up.flags, mx.wt.n, (int)mx.wt.levels, mx.up.sh0,
-               mx.up.sat_bits};
+static void launch_prio_update(const iqlhip_ctx* c, const ChunkSrc& src, int B, int k, hipStream_t st) {
+  const WUpd u{const_cast<unsigned long long*>(src.wt.tab), src.up.stamp, src.up.flags, src.wt.n, (int)src.wt.levels, src.up.sh0,
+               src.up.sat_bits};
   const PrioArgs a{prio_words(c), 0.f, 0.f};
-  launch_update_td(u, prio_idx(c, k & 1), prio_td(c), (unsigned)B, (long long)mx.wt.n, mx.up.delta, a, st);
+  launch_update_td(u, prio_idx(c, k & 1), prio_td(c), (unsigned)B, (long long)src.wt.n, src.up.delta, a, st);
 }
 // What a prioritised call needs beyond check_weighted_args and weighted_is_setup, before anything is launched or any
 // counter moves: an updatable table, valid exponents, the staging buffer and the forward's LDS allowance.
@@ -5082,27 +5089,22 @@ static int prio_setup(iqlhip_ctx* c, const iqlhip_weights* table, int32_t B, flo
   if (B > WT_UPDATE_SLICE) return fail(IQLHIP_EUNSUPPORTED, "prioritised calls take batches of at most %d rows", WT_UPDATE_SLICE);
   DevGuard guard(c->device);
   if (!c->prio_buf) HIPCHK(c->own.dev(&c->prio_buf, 24 * (size_t)c->dims.max_batch + 4 * sizeof(float), 0));
-  if (!c->prio_lds_set) {
-    int rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_prio_kernel(m & 1, m & 2); });
-    if (rc) return rc;
-    c->prio_lds_set = true;
-  }
-  return IQLHIP_OK;
+  return ensure_fwd_lds(c, ChunkKind::Prio);
 }
-static MixSrc prio_src(const iqlhip_weights* t, float is_beta, float alpha, float eps, unsigned live) {
-  MixSrc mx{nullptr, 0, weights_tab(t), t->gen, t->version, 2, is_beta};
-  mx.up = PrioSrc{t->stamp, t->flags, t->delta, t->sh0, t->sat_bits};
-  mx.alpha = alpha; mx.eps = eps; mx.live = live;
-  return mx;
+static ChunkCall prio_call(const iqlhip_weights* t, float is_beta, float alpha, float eps, unsigned live) {
+  ChunkCall call = weighted_call(t, ChunkKind::Prio, is_beta);
+  call.src.up = PrioSrc{t->stamp, t->flags, t->delta, t->sh0, t->sat_bits};
+  call.alpha = alpha; call.eps = eps; call.live = live;
+  return call;
 }
 extern "C" int iqlhip_train_steps_prioritized_prepare(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int32_t B,
                                                       float inv_batch, void* stream, iqlhip_weights* table) {
   int rc = check_weighted_args(c, rows_dev, ld, table ? table->n : 0, B, table);
-  if (!rc) rc = weighted_is_setup(c, B, 0.f);
+  if (!rc) rc = weighted_is_setup(c, 0.f);
   if (!rc) rc = prio_setup(c, table, B, 1.f, 1.f);
   if (rc) return rc;
-  const MixSrc mx = prio_src(table, 0.f, 1.f, 1.f, /*live=*/0u);      // (the rehearsal's updates leave the table alone)
-  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, &mx);
+  // (live = 0: the rehearsal's updates leave the table alone)
+  return train_steps_prepare(c, rows_dev, ld, B, inv_batch, stream, prio_call(table, 0.f, 1.f, 1.f, /*live=*/0u));
 }
 extern "C" int iqlhip_train_steps_prioritized(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t size, int32_t B,
                                               const iqlhip_step_scalars* sc, int32_t K, uint64_t seed, uint64_t stream_offset,
@@ -5110,11 +5112,11 @@ extern "C" int iqlhip_train_steps_prioritized(iqlhip_ctx* c, const float* rows_d
                                               float eps) {
   if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = check_weighted_args(c, rows_dev, ld, size, B, table);
-  if (!rc) rc = weighted_is_setup(c, B, is_beta);
+  if (!rc) rc = weighted_is_setup(c, is_beta);
   if (!rc) rc = prio_setup(c, table, B, alpha, eps);
   if (rc) return rc;
-  const MixSrc mx = prio_src(table, is_beta, alpha, eps, /*live=*/1u);
-  rc = train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream, &mx, 0);
+  rc = train_steps(c, rows_dev, ld, size, B, sc, K, seed, stream_offset, flags, stream,
+                   prio_call(table, is_beta, alpha, eps, /*live=*/1u), 0);
   if (!rc) ++table->version;      // the table's content has moved (a failed call leaves no continuation behind anyway)
   return rc;
 }

@@ -374,6 +374,72 @@ def test_results_are_identical_with_and_without_the_continue_flag(dropout):
     H.assert_same_trainer_state(a.tr, n.tr, "flag always vs never")
 
 
+KINDS = ("plain", "mixed", "weighted", "weighted_is", "prioritized")
+
+
+class _KindTwin:
+    """One trainer driven through the C ABI by all five kinds of multi-step call: one offline buffer whose updatable
+    table the three weighted kinds share (it spans the buffer: plain and weighted calls name the same size), one online
+    buffer for the mixed calls."""
+    N, B, K, IS_BETA, ALPHA, EPS = 300, 8, 2, 0.5, 0.6, 1e-3
+
+    def __init__(self):
+        self.tr = _build()
+        self.buf, self.online = _new_buffer(self.N, 41), _new_buffer(self.N, 42)
+        w = np.random.RandomState(2).rand(self.N).astype(np.float32) ** 4 + np.float32(1e-3)       # skewed
+        self.buf.set_sample_weights(w, updatable=True, max_weight=64.0)
+
+    def call(self, kind, seed, flag):
+        """K steps of `kind` at the trainer's position in the index stream; returns their losses."""
+        _, hb, _ = _hip()
+        tr, buf, lib, B, K = self.tr, self.buf, hb.lib(), self.B, self.K
+        tr._prepare(B)
+        tab = tr._scalar_table(K, 1.0 / B)
+        off = tr.total_it * (B // 2)
+        head = (tr._ctx, buf._rows.data_ptr(), buf._ld, self.N, B, tab.ctypes.data, K, seed, off, flag, tr._stream())
+        if kind == "plain":
+            hb.check(lib.iqlhip_train_steps(*head))
+        elif kind == "mixed":              # (no flags argument: a mixed call never continues)
+            hb.check(lib.iqlhip_train_steps_mixed(tr._ctx, buf._rows.data_ptr(), self.N, self.online._rows.data_ptr(), self.N,
+                                                  buf._ld, B, B // 2, tab.ctypes.data, K, seed, off, tr._stream()))
+        elif kind == "weighted":
+            hb.check(lib.iqlhip_train_steps_weighted(*head, buf._weights))
+        elif kind == "weighted_is":
+            hb.check(lib.iqlhip_train_steps_weighted_is(*head, buf._weights, self.IS_BETA))
+        else:
+            hb.check(lib.iqlhip_train_steps_prioritized(*head, buf._weights, self.IS_BETA, self.ALPHA, self.EPS))
+        out = (C.c_float * (3 * K))()
+        hb.check(lib.iqlhip_read_loss_ring(tr._ctx, out, K, tr._stream()))
+        tr.total_it += K
+        return np.frombuffer(out, dtype=np.float32).reshape(K, 3).copy()
+
+
+def test_every_pair_of_kinds_continues_only_its_own():
+    """Every ordered pair (first, second) of the five kinds of multi-step call, two steps each at 8 rows, through the C
+    ABI with IQLHIP_TS_CONTINUE on every call.  The second call is contiguous with the first in everything the token
+    compares (rows, stride, size, batch, seed, counter position, no dropout), so only the library's knowledge of the
+    KIND decides whether it starts on the rows the first one staged.  The twin makes the same calls with the flag only
+    where include/iqlhip.h documents a continuation: first == second, and not the mixed kind (prioritised ->
+    prioritised is one: the first call's own version bump is in its token).  Second call's losses and the trainer
+    state, bit for bit.  Each pair has a seed of its own, so no first call continues the pair before it."""
+    _, hb, H = _hip()
+    a, t = _KindTwin(), _KindTwin()
+    assert a.buf._index_bound() == a.N == a.buf.sample_weights_n
+    pair = 0
+    for first in KINDS:
+        for second in KINDS:
+            seed = 100 + pair
+            pair += 1
+            documented = hb.TS_CONTINUE if (first == second and first != "mixed") else 0
+            fa, ft = a.call(first, seed, hb.TS_CONTINUE), t.call(first, seed, 0)
+            sa, st = a.call(second, seed, hb.TS_CONTINUE), t.call(second, seed, documented)
+            assert np.all(np.isfinite(sa)), (first, second)
+            assert np.array_equal(fa, ft), (first, second, fa, ft)
+            assert np.array_equal(sa, st), (first, second, sa, st)
+            assert np.array_equal(H.arenas(a.tr), H.arenas(t.tr)), (first, second)
+    H.assert_same_trainer_state(a.tr, t.tr, "flag always vs where documented")
+
+
 # ------------------------------------------------------------------------------------------------ 7. injected masks
 def test_train_steps_refuses_pending_injected_masks():
     """iqlhip_train_steps draws its own keep-bits (two halves, the next step's drawn by the step before) and cannot use
