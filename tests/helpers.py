@@ -245,6 +245,27 @@ def uses_large_batch_kernels(S, A, B):
     return B > 512 and S + A + 1 <= 80
 
 
+def bwd_spb_l2(n_chunk, n_rt, n_cus=256):
+    """bwd_spb_l2: the backward's column slices per (b) block (log2); > 0 selects the MULTI instantiations."""
+    return 0 if 4 * (32 * n_chunk + 4 * n_rt) <= 2 * n_cus else 2
+
+
+def bwd_instantiation(S, A, B, precision, row_weighted=False, n_cus=256):
+    """launch_bwd's choice for a step of B rows, by name: the large-batch pair (row kernel with or without its column
+    split + the GEMM kernel) for a bf16 step that use_lb takes, else iql_bwd_kernel<BF16, FULL, MULTI> — FULL: the batch
+    is whole 256-row chunks; MULTI: bwd_spb_l2 > 0 — or, with row weights (fp32 only), iql_bwd_rw_kernel<FULL, MULTI>."""
+    n_rt, n_chunk = (B + 31) // 32, (B + 255) // 256
+    bf = precision == "bf16"
+    if bf and uses_large_batch_kernels(S, A, B):
+        assert not row_weighted
+        return f"iql_bwd_rows_kernel<CSPLIT={int(((n_rt + 1) & ~1) <= 32)}> + iql_bwd_gemm_kernel"
+    full, multi = int(B % 256 == 0), int(bwd_spb_l2(n_chunk, n_rt, n_cus) > 0)
+    if row_weighted:
+        assert not bf
+        return f"iql_bwd_rw_kernel<FULL={full}, MULTI={multi}>"
+    return f"iql_bwd_kernel<BF16={int(bf)}, FULL={full}, MULTI={multi}>"
+
+
 # ---------------------------------------------------------------------------
 # Row-permutation checks.  Every IQL loss is a mean of per-row terms (adv is detached, there is no batch statistic), so a
 # batch's gradient is the sum of its rows' terms and must not change, beyond fp32 summation order, when the rows are
