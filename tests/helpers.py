@@ -266,6 +266,34 @@ def bwd_instantiation(S, A, B, precision, row_weighted=False, n_cus=256):
     return f"iql_bwd_kernel<BF16={int(bf)}, FULL={full}, MULTI={multi}>"
 
 
+def row_f4(S, A):
+    """float4s of one packed replay row (s, a, ns, r, d: 2 S + A + 2 floats, padded to a multiple of 4): what a gather's
+    loop over a row copies, 64 per pass of a wave, and what the forward's xr registers hold of a 32-row tile."""
+    return (2 * S + A + 2 + 3) // 4
+
+
+# The five chunk-graph kinds of the multi-step driver (ChunkKind in csrc/iqlhip.hip) and the training forward of each.
+CHUNK_KINDS = ("plain", "mixed", "weighted", "weighted_is", "prioritized")
+_FWD_OF_KIND = {"plain": "iql_fwd_kernel", "mixed": "iql_fwd_mixed_kernel", "weighted": "iql_fwd_weighted_kernel",
+                "weighted_is": "iql_fwd_weighted_is_kernel", "prioritized": "iql_fwd_prio_kernel"}
+
+
+def fwd_instantiation(kind, S, A, B, precision, n_cus=256):
+    """launch_fwd_grid / fwd_kernel_of's choice for a training step of B rows inside a chunk of `kind`, by name:
+    iql_fwd*_kernel<BF16, W0DMA, MULTI> — W0DMA: w0_lds_k > 64 (some instance stages layer 0 by LDS-DMA); MULTI:
+    fwd_spb_l2 > 0 — without BF16 for the two fp32-only kinds.  A bf16 step that use_lb takes runs iql_fwd_lb_kernel<NKB>
+    instead (plain kind only: the others refuse such a batch; its policy-spread flag is not restated here)."""
+    bf = precision == "bf16"
+    if bf and uses_large_batch_kernels(S, A, B):
+        assert kind == "plain", (kind, B)
+        return f"iql_fwd_lb_kernel<NKB={1 if S + A <= 32 else 2 if S + A <= 64 else 3}>"
+    dma, multi = int(w0_lds_k(S, A) > 64), int(fwd_spb_l2((B + 31) // 32, n_cus) > 0)
+    if kind in ("weighted_is", "prioritized"):
+        assert not bf, kind
+        return f"{_FWD_OF_KIND[kind]}<W0DMA={dma}, MULTI={multi}>"
+    return f"{_FWD_OF_KIND[kind]}<BF16={int(bf)}, W0DMA={dma}, MULTI={multi}>"
+
+
 # ---------------------------------------------------------------------------
 # Row-permutation checks.  Every IQL loss is a mean of per-row terms (adv is detached, there is no batch statistic), so a
 # batch's gradient is the sum of its rows' terms and must not change, beyond fp32 summation order, when the rows are

@@ -73,9 +73,13 @@ BF16_EDGE_CASES = [
     (40, 17, 256, True, False, 57),      # A = 17: 15 padded action dims; kq = 57 staged through registers
     (3, 9, 33, True, False, 12),         # 9 action dims; one row past a row tile
     (17, 6, 512, True, False, 23),       # the largest batch of the small-batch path
+    (72, 28, 256, True, False, 72),      # kq = 100 > 96, S = 72: V and pi staged by LDS-DMA, the critics from global
+    (127, 1, 300, True, False, 0),       # the widest packed row (65 float4: the forward's ninth row-tile register); A = 1
     # small-batch bf16 kernels above 512 rows: S + A + 1 > 80 rules the large-batch kernels out
     (100, 28, 1024, True, False, 0),     # S + A + 1 = 129; W0 from global
     (52, 28, 1024, True, False, 80),     # S + A + 1 = 81, one past the large-batch limit; kq = 80 staged by LDS-DMA
+    (72, 28, 1024, True, False, 72),     # S + A + 1 = 101; split staging inside the LDS-DMA kernel
+    (127, 1, 1024, True, False, 0),      # S + A + 1 = 129; the widest packed row over 32 row tiles
     # large-batch kernels (iqlhip_lb_kernels.h)
     (17, 6, 513, True, True, 23),        # one row past the switch: 17 row tiles, the last holds one row
     (26, 6, 1024, True, True, 32),       # kq = 32: the widest iql_fwd_lb_kernel<NKB = 1>

@@ -27,9 +27,10 @@ def _hip():
     return iql, hb, H, wtd
 
 
-def _pair(i, dropout=0.0, bf16=False, drop_seed=None, stats=False, clip=None, count=2):
+def _pair(i, dropout=0.0, bf16=False, drop_seed=None, stats=False, clip=None, count=2, dims=(S, A)):
     """Member i and its twin(s): the same parameters, hyper-parameters, learning rates and opt-in settings."""
     H = _hip()[2]
+    S, A = dims
     params = synth.synth_params(S, A, seed=300 + i)
     hyper = {"iql_tau": 0.6 + 0.1 * (i % 4), "beta": 2.0 + i, "discount": 0.99, "tau": 0.005 * (1 + i)}
     lrs = {"v": 3e-4 * (1 + i), "q": 2e-4 * (1 + i), "pi": 1e-4 * (1 + i)}
@@ -52,13 +53,14 @@ def _pairs(K, **kw):
 
 
 @functools.lru_cache(maxsize=None)
-def _data(n):
-    return synth.synth_transitions(n, S, A, seed=22)
+def _data(n, dims=(S, A)):
+    return synth.synth_transitions(n, dims[0], dims[1], seed=22)
 
 
-def _buffer(n, poison=False):
+def _buffer(n, poison=False, dims=(S, A)):
     iql = _hip()[0]
-    data = {k: v.copy() for k, v in _data(n).items()}
+    S, A = dims
+    data = {k: v.copy() for k, v in _data(n, dims).items()}
     if poison:      # (states AND rewards: a NaN pre-activation alone dies in the ReLU's max(x, 0); a NaN reward reaches the losses)
         for key in ("observations", "next_observations", "rewards"):
             data[key][1::2] = np.nan
@@ -121,6 +123,35 @@ def test_shared_buffer_and_shared_table_equal_solo_calls_bitwise(B):
         _assert_same(members[i], twins[i], f"member {i}")
         assert members[i].total_it == steps
     assert not np.array_equal(got[0], got[1])
+
+
+@pytest.mark.parametrize("dims", [(127, 1), (72, 28)])
+def test_wide_rows_and_split_staging_equal_solo_calls_bitwise(dims):
+    """iql_gather_weighted_group_kernel copies a row with the solo gathers' loop, 64 float4 per pass of a wave: at
+    (127, 1) a packed row has 65 (tests/chunk_kind_shapes.py), the only shape that takes a second pass; at (72, 28) the
+    group's forward stages V and pi by LDS-DMA while the critics read W0 from global.  300 rows: ten row tiles per member,
+    two backward chunks."""
+    from helpers import row_f4, w0_lds_k
+    iql = _hip()[0]
+    assert (row_f4(*dims), w0_lds_k(*dims)) == {(127, 1): (65, 0), (72, 28): (44, 72)}[dims]
+    K, n, steps, B, seeds = 3, 2000, 3, 300, [77, 78, 79]
+    buf = _buffer(n, dims=dims)
+    buf.set_sample_weights(_skewed(n))
+    pairs = [_pair(i, dims=dims) for i in range(K)]
+    members, twins = [p[0] for p in pairs], [p[1] for p in pairs]
+    got = iql.ImplicitQLearningGroup(members).train_steps_weighted(buf, steps, B, seeds)
+    assert got.shape == (K, steps, 3)
+    for i in range(K):
+        _assert_losses(got[i], twins[i].train_steps_weighted(buf, steps, B, seed=seeds[i]), f"member {i}")
+        _assert_same(members[i], twins[i], f"member {i}")
+        assert members[i].total_it == steps
+    assert not np.array_equal(got[0], got[1])
+    # the solo call gathers through the same device function as the group: member 0 is also rebuilt from eager steps on
+    # the integer reference's rows (gathered by ReplayBuffer.gather), which share nothing with either
+    from burst_twins import eager_weighted_segment
+    eager = _pair(0, count=1, dims=dims)[0]
+    _assert_losses(got[0], eager_weighted_segment(eager, buf, _skewed(n), steps, B, seeds[0]), "member 0, eager rebuild")
+    _hip()[2].assert_same_trainer_state(members[0], eager, "member 0, eager rebuild")
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2

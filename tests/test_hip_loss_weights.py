@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import synth
+from burst_twins import eager_is_segment as _eager_is, fourth_power_weights      # (shared with the shape table's tests)
 from helpers import assert_losses, check_step_against_golden, load_golden, rel_err, single_step_inputs, step_batch
 from loss_weights_ref import GOLDENS
 
@@ -205,20 +206,8 @@ def _burst_buffer():
     import iql
     buf = iql.ReplayBuffer(BURST_S, BURST_A, BURST_N, "cuda")
     buf.load_d4rl_dataset(synth.synth_transitions(BURST_N, BURST_S, BURST_A, seed=5))
-    w = np.random.RandomState(2).rand(BURST_N).astype(np.float32) ** 4 + np.float32(1e-3)
-    w[::7] = 0.0
-    buf.set_sample_weights(w)
+    buf.set_sample_weights(fourth_power_weights(BURST_N))
     return buf
-
-
-def _eager_is(tr, buf, K, B, seed, beta):
-    """K eager iterations on the rows train_steps_weighted(buf, K, B, seed) draws at the trainer's current total_it:
-    draw with is_beta -> gather -> train(batch, loss_weights=c); losses float32 [K, 3]."""
-    idx, c = buf.draw_weighted_indices(K * B, seed, tr.total_it * ((B + 1) // 2), is_beta=beta, batch_size=B)
-    out = np.empty((K, 3), dtype=np.float32)
-    for k in range(K):
-        out[k] = _losses(tr.train(buf.gather(idx[k * B:(k + 1) * B]), loss_weights=c[k * B:(k + 1) * B]))
-    return out
 
 
 @pytest.mark.parametrize("B", [64, 300])

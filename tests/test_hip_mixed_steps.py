@@ -12,6 +12,7 @@ import torch
 
 import mixed_ref
 import synth
+from burst_twins import eager_mixed_segment, mixing_ratio as _ratio      # (the twin, shared with the shape table's tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,12 +28,6 @@ def _hip():
     import iql
     import iqlhip_binding as hb
     return iql, hb, H
-
-
-def _ratio(B, n_off):
-    r = (n_off + 0.5) / B
-    assert int(B * r) == n_off
-    return r
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,33 +62,6 @@ def _build(dropout=0.0, bf16=False, stats=False, clip=None):
     tr.set_step_stats(stats)
     tr.set_grad_clip(clip)
     return tr
-
-
-def _gather_into(buf, idx, block):
-    hb = _hip()[1]
-    n = idx.shape[0]
-    host = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).pin_memory()
-    scratch = torch.empty(n, dtype=torch.int64, device="cuda")
-    hb.check(hb.lib().iqlhip_rows_gather_packed_h(buf._rows.data_ptr(), buf._ld, buf._buffer_size, host.data_ptr(),
-                                                  scratch.data_ptr(), n, block.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream))
-    torch.cuda.current_stream().synchronize()        # (host / scratch are free again)
-
-
-def eager_mixed_segment(tr, off, on, K, B, n_off, seed, with_stats=False):
-    """K eager train() steps on the batches train_steps_mixed draws at the trainer's current total_it."""
-    idx_off, idx_on = mixed_ref.mixed_indices(K, B, n_off, off._size, on._size, seed, mixed_ref.call_offset(tr.total_it, B))
-    ld = off._ld
-    losses, stats = np.empty((K, 3), dtype=np.float32), []
-    for k in range(K):
-        block = torch.empty((B, ld), dtype=torch.float32, device="cuda")
-        _gather_into(off, idx_off[k], block[:n_off])
-        _gather_into(on, idx_on[k], block[n_off:])
-        log = tr.train([block[:, :S], block[:, S: S + A], block[:, 2 * S + A: 2 * S + A + 1], block[:, S + A: 2 * S + A],
-                        block[:, 2 * S + A + 1: 2 * S + A + 2]])
-        losses[k] = [log["value_loss"], log["q_loss"], log["actor_loss"]]
-        stats.append([v for name, v in log.items() if name.startswith("stats/")])
-    return (losses, np.array(stats, dtype=np.float32)) if with_stats else losses
 
 
 def _assert_steps_equal(lg, le, what=""):

@@ -463,6 +463,10 @@ def test_slices_per_block_layouts_are_bit_identical(S, A, B, bf16, monkeypatch):
                     assert np.array_equal(mom[which][n][k], ref[2][which][n][k]), (key, which, n, k)
 
 
+_EDGE_W0_LDS_K = {(100, 28): 0, (96, 32): 0, (50, 10): 60, (65, 31): 65, (64, 32): 64, (72, 28): 72, (127, 1): 0,
+                  (39, 28): 67, (17, 6): 23}
+
+
 @pytest.mark.parametrize("S,A,B,gaussian", [
     (100, 28, 64, True),     # k_in = 128 (limit): layer-0 weights streamed from global, 8 k-tiles in dW0
     (96, 32, 40, False),     # action_dim = 32 (limit): two 16-wide head tiles, four pi chunks
@@ -470,8 +474,13 @@ def test_slices_per_block_layouts_are_bit_identical(S, A, B, bf16, monkeypatch):
     (17, 6, 1, True),        # single row
     (17, 6, 257, True),      # one row past a 256-row chunk
     (50, 10, 300, True),     # k_in = 60 (V: 50): LDS-staged W0 through the generic k loop
-    (65, 31, 70, True),      # k_in = 96: the widest layer-0 copy by LDS-DMA; 31 action dims (ragged last chunk of 8)
-    (64, 32, 256, False),    # k_in = 96 and action_dim = 32 together, deterministic policy
+    (65, 31, 70, True),      # k_in = 96 does not fit LDS beside a 32-wide head tile: w0_lds_k = 65, V and pi staged by
+                             # LDS-DMA, the critics from global; 31 action dims (ragged last chunk of 8)
+    (64, 32, 256, False),    # k_in = 96 and action_dim = 32 together, deterministic policy: w0_lds_k = 64, V and pi staged
+                             # through registers (the widest such copy), the critics from global
+    (72, 28, 70, True),      # k_in = 100 > 96, S = 72 fits: split staging inside the LDS-DMA kernel, 44 float4 per row
+    (127, 1, 40, True),      # the widest packed row: 260 floats, 65 float4 (a 32-row tile fills the forward's ninth
+    (127, 1, 300, True),     # register); A = 1; every W0 from global; 300 rows: ragged chunk and several column slices
     (40, 17, 256, True),     # 17 action dims: Dp = 32 with 15 padding dims; Q inputs 57 wide (register-staged)
     (3, 9, 33, True),        # 9 action dims: second 8-dim group holds a single dim
     (39, 28, 1024, True),    # config 5 per-GPU shape: 4 chunks, 32 row tiles
@@ -480,7 +489,10 @@ def test_slices_per_block_layouts_are_bit_identical(S, A, B, bf16, monkeypatch):
 ])
 def test_edge_shapes_match_oracle(S, A, B, gaussian):
     from oracle import iql_oracle as O
+    from helpers import w0_lds_k
     build, _, _, read_params, to_tb, unflat = _hip()
+    if (S, A) in _EDGE_W0_LDS_K:           # the staging the case's comment names, checked against the host rule's restatement
+        assert w0_lds_k(S, A) == _EDGE_W0_LDS_K[(S, A)]
     params = synth.synth_params(S, A, seed=7 * S + A, gaussian=gaussian)
     d = synth.synth_transitions(B, S, A, seed=S + A + B)
     batch = {"s": d["observations"], "a": d["actions"], "r": d["rewards"], "ns": d["next_observations"],
@@ -605,6 +617,27 @@ def test_actor_forward_chunks_ragged_and_after_training():
         assert abs(float(np.corrcoef(zs[:-1, 0], zs[1:, 0])[0, 1])) < 0.08  # consecutive rows uncorrelated (5 sigma)
     again = tr.actor_forward(torch.from_numpy(x).cuda(), sample=True).cpu().numpy()
     assert not np.array_equal(again, smp)                                   # the call counter advances the stream
+
+
+@pytest.mark.parametrize("S,A,gaussian", [(72, 28, True), (127, 1, True)])
+def test_actor_forward_at_the_staging_edges_against_the_float64_policy(S, A, gaussian):
+    """The one-instance forward (the ONE = true instantiations of the training forward's body) where layer-0 staging
+    splits — (72, 28): the policy staged by LDS-DMA in the kernel whose critics are not — and at the widest state,
+    (127, 1): W0 from global, one action dim.  Against the policy forward in float64, at
+    test_actor_forward_chunks_ragged_and_after_training's bound (abs 2e-6 on an action in [-1, 1]: tanh at about an ulp);
+    one row, a ragged tile, several tiles."""
+    import torch
+    from oracle import iql_oracle as O
+    from hip_helpers import build_hip_trainer
+    params = synth.synth_params(S, A, seed=7 * S + A, gaussian=gaussian)
+    tr = build_hip_trainer(params, S, A, gaussian, _HYPER, _LRS, 1000)
+    rng = np.random.default_rng(S + A)
+    for n in (1, 33, 300):
+        x = rng.standard_normal((n, S)).astype(np.float32)
+        got = tr.actor_forward(torch.from_numpy(x).cuda()).cpu().numpy()
+        want = O.actor_act(params["pi"], x, 1.0, dtype=np.float64)
+        assert got.shape == (n, A) and got.dtype == np.float32
+        assert np.max(np.abs(got - want)) <= 2e-6, (n, float(np.max(np.abs(got - want))))
 
 
 def test_actor_act_falls_back_to_torch_where_the_library_cannot_serve():

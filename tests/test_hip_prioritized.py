@@ -18,6 +18,8 @@ import torch
 
 import prioritized_ref as PR
 import synth
+from burst_twins import (eager_prioritized_segment as _eager, fourth_power_weights,      # (shared with the shape table's tests)
+                         table_of as _table)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,9 +40,7 @@ def _losses(log):
 
 
 def _weights(n=N):
-    w = np.random.RandomState(2).rand(n).astype(np.float32) ** 4 + np.float32(1e-3)
-    w[::7] = 0.0
-    return w
+    return fourth_power_weights(n)
 
 
 def _buffer(w=None, n=N, updatable=True):
@@ -54,32 +54,6 @@ def _buffer(w=None, n=N, updatable=True):
     else:
         buf.set_sample_weights(w)
     return buf
-
-
-def _table(buf):
-    """(leaves, total) of the buffer's table."""
-    import iqlhip_weighted as wtd
-    total, _, _, q = wtd.table_state(buf._weights, buf.sample_weights_n, leaves=True)
-    return q, total
-
-
-def _eager(tr, buf, K, B, seed, alpha, eps, beta, lag=True):
-    """K iterations of the eager loop on the rows train_steps_prioritized(buf, K, B, seed) draws at the trainer's current
-    total_it (B even: step t's indices are a draw of their own at offset + t B / 2).  lag=False: the update of step t
-    comes BEFORE the draw of step t + 1 — the order the burst does not have."""
-    assert B % 2 == 0
-    off0 = tr.total_it * (B // 2)
-
-    def draw(t):
-        return buf.draw_weighted_indices(B, seed, off0 + t * (B // 2), is_beta=beta)
-    out = np.empty((K, 3), dtype=np.float32)
-    idx, c = draw(0)
-    for t in range(K):
-        nxt = draw(t + 1) if lag else None
-        out[t] = _losses(tr.train(buf.gather(idx), loss_weights=c, return_td=True))
-        buf.update_sample_weights_td(idx, tr.last_td_errors(), alpha, eps)
-        idx, c = nxt if lag else draw(t + 1)
-    return out
 
 
 def _assert_burst_equals_eager(burst_buf, eager_buf, burst, eager, lb, le, what):

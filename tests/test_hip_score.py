@@ -113,7 +113,9 @@ def _check_against_oracle(tag, tr, params, data, hyper, sizes):
 
 
 @pytest.mark.parametrize("gaussian", [True, False])
-@pytest.mark.parametrize("S,A", [(11, 3), (17, 6), (39, 28), (100, 28), (20, 32)])
+@pytest.mark.parametrize("S,A", [(11, 3), (17, 6), (39, 28), (100, 28), (20, 32),
+                                 (72, 28),      # layer-0 staging split inside the LDS-DMA kernel: V and pi staged, critics not
+                                 (127, 1)])     # the widest packed row (65 float4), one action dim
 def test_eight_columns_and_summary_against_the_oracle(S, A, gaussian):
     tr, params = _trainer(S, A, gaussian, seed=5)
     data = synth.synth_transitions(max(SIZES), S, A, seed=77)

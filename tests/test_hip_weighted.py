@@ -11,6 +11,7 @@ import torch
 
 import synth
 import weighted_ref as W
+from burst_twins import eager_weighted_segment, skewed_weights      # (the twin, shared with the shape table's tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -73,11 +74,7 @@ def _weights(n):
 @functools.lru_cache(maxsize=None)
 def _skewed():
     """Weights over the N_ROWS rows of the training tests: log-normal, a tenth of them zero."""
-    rng = np.random.RandomState(8)
-    w = np.exp(2.0 * rng.randn(N_ROWS)).astype(np.float32)
-    w[rng.rand(N_ROWS) < 0.1] = 0.0
-    w.setflags(write=False)
-    return w
+    return skewed_weights(N_ROWS, of=N_ROWS)
 
 
 def _build(dropout=0.0, bf16=False, stats=False, clip=None):
@@ -107,17 +104,6 @@ def _levels(n):
         n = (n + 63) // 64
         k += 1
     return k
-
-
-def eager_weighted_segment(tr, buf, w, K, B, seed, with_stats=False):
-    """K eager train() steps on the rows train_steps_weighted(buf, K, B, seed) draws at the trainer's total_it."""
-    idx = W.draw_indices(K * B, w, seed, tr.total_it * ((B + 1) // 2))
-    losses, stats = np.empty((K, 3), dtype=np.float32), []
-    for k in range(K):
-        log = tr.train(buf.gather(torch.from_numpy(idx[k * B:(k + 1) * B])))
-        losses[k] = [log["value_loss"], log["q_loss"], log["actor_loss"]]
-        stats.append([v for name, v in log.items() if name.startswith("stats/")])
-    return (losses, np.array(stats, dtype=np.float32)) if with_stats else losses
 
 
 def _assert_steps_equal(lg, le, what=""):
