@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 390          /* 0.3.9 */
+#define IQLHIP_VERSION 400          /* 0.4.0 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -682,7 +682,9 @@ int iqlhip_pack_rows(iqlhip_ctx* ctx, const iqlhip_batch* b, float* rows_out_dev
  * _train_steps / _online_step, a size per member through their _mixed forms (the same launches: each launch's grid is
  * the largest member's, a member's record bounds its own work); small-batch kernels only (bf16: at most 512 rows per
  * member).  A group call invalidates each member's train_steps continuation
- * (the staging buffer is overwritten).  The members must outlive the group; a context that is destroyed or re-created
+ * (the staging buffer is overwritten); the group's own bursts with importance-sampling weights may continue each other
+ * (IQLHIP_GROUP_TS_CONTINUE).  Per-row loss weights, importance-sampling weights and prioritised replay are fp32 only, in
+ * a group as alone.  The members must outlive the group; a context that is destroyed or re-created
  * means a new group. */
 #define IQLHIP_MAX_GROUP 16
 #define IQLHIP_GROUP_MAX_STEPS 1024   /* steps per iqlhip_group_train_steps call */
@@ -792,6 +794,44 @@ int iqlhip_group_train_steps_weighted(iqlhip_group* group, const float* const* r
                                       const int32_t* B, const void* const* tables, int32_t n, const uint64_t* seeds,
                                       const uint64_t* offsets, int32_t flags, void* stream,
                                       const iqlhip_weights* const* wtabs);
+/* Per-row loss weights, importance-sampling weights and prioritised replay for every member in the group's launches
+ * (DESIGN.md 6j "trainer groups").  fp32 only; everything below is refused before anything is launched and before any
+ * counter moves, the message naming the member.
+ * iqlhip_group_step_rw is iqlhip_group_step_mixed with member k's loss terms weighted by row_w_dev[k][0 .. rows_k) and
+ * its TD errors (q1 - y, q2 - y) stored to td_out_dev[k] ([rows_k][2] fp32, 8-byte aligned): member k ends bit for bit
+ * where iqlhip_step_rw leaves it.  row_w_dev[k] == NULL: weights of 1.0f (a vector the group keeps); td_out_dev[k] ==
+ * NULL: nothing is stored for that member.  Both ARRAYS must be given (IQLHIP_EINVAL); a bf16 member: IQLHIP_EUNSUPPORTED.
+ * iqlhip_group_train_steps_weighted_is is iqlhip_group_train_steps_weighted whose steps weight member k's loss terms by
+ * c = (q_min / q_row)^is_beta[k] — iqlhip_train_steps_weighted_is for each member with a table.  A member without one
+ * (wtabs[k] == NULL) draws uniformly with c = 1 and ends where iqlhip_train_steps leaves it.
+ * iqlhip_group_train_steps_prioritized is iqlhip_train_steps_prioritized for each member, lag of one step included.  Per
+ * call: the rows of step 0 by every member's table as it stands; then per step s: the rows of step s + 1 into the members'
+ * other staging halves (they see the updates of steps < s), step s with its loss weights, and wtabs[k][rows of s] <-
+ * td_priority(TD errors of s; alpha[k], eps[k]) for all members in three launches.  One linear chain on `stream`.
+ * flags: IQLHIP_GROUP_TS_CONTINUE — the call may start on the rows this group's previous call staged.  It is honoured
+ * per member under the rules of IQLHIP_TS_CONTINUE: the previous call on the member was this group's, of the same kind
+ * and of an even number of steps, on the same rows / size / B[k] / seed with offsets[k] where it stopped (an odd B[k]
+ * never is: the member draws afresh), its table at the generation and version that call left, dropout settings and
+ * position unchanged.  Any other group or solo call on a member invalidates its staged rows.  At most
+ * IQLHIP_GROUP_MAX_STEPS steps per call; a caller that wants a result to depend on the tables alone passes the flag only
+ * between the pieces of one burst (the Python layer does).  A prioritised call moves every table's version by 1.
+ * Refused on top of iqlhip_group_train_steps_weighted's checks: unknown flag bits, a NULL is_beta / alpha / eps array, an
+ * is_beta[k] that is negative or not finite (IQLHIP_EINVAL); a bf16 member, pending injected keep-bits
+ * (IQLHIP_EUNSUPPORTED).  The prioritised call also: a NULL wtabs[k], a static table, alpha[k] / eps[k] negative, not
+ * finite or both 0, one table given to two members — their updates would race, and "what the solo call leaves" would mean
+ * nothing; sharing the ROWS is fine — (IQLHIP_EINVAL); more than 65 536 rows per batch (IQLHIP_EUNSUPPORTED). */
+#define IQLHIP_GROUP_TS_CONTINUE 1
+int iqlhip_group_step_rw(iqlhip_group* group, const iqlhip_batch* batches, const iqlhip_step_scalars* sc,
+                         const float* const* row_w_dev, float* const* td_out_dev, float* out, void* stream);
+int iqlhip_group_train_steps_weighted_is(iqlhip_group* group, const float* const* rows, int64_t ld, const int64_t* size,
+                                         const int32_t* B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                         const uint64_t* offsets, int32_t flags, void* stream,
+                                         const iqlhip_weights* const* wtabs, const float* is_beta);
+int iqlhip_group_train_steps_prioritized(iqlhip_group* group, const float* const* rows, int64_t ld, const int64_t* size,
+                                         const int32_t* B, const void* const* tables, int32_t n, const uint64_t* seeds,
+                                         const uint64_t* offsets, int32_t flags, void* stream,
+                                         iqlhip_weights* const* wtabs, const float* is_beta, const float* alpha,
+                                         const float* eps);
 /* Policy inference for every member of a group in one set of launches.  Member k maps its rows[k] states
  * (row stride ld_s) to rows[k] actions (row stride ld_a), exactly as iqlhip_actor_forward (seeds[k] == 0: the mean)
  * or iqlhip_actor_sample (seeds[k] != 0: device N(0,1) noise, member k's act() call counter advances by one) on that

@@ -291,6 +291,7 @@ struct iqlhip_ctx {
            uint64_t wt_gen = 0;      // the table generation of a weighted call (0: a plain call)
            int cont_class = 0;       // KindInfo::cont_class of that call: what it staged besides the rows
            uint64_t wt_ver = 0;      // ... and the table's content version at that call (iqlhip_weights_update adds 1)
+           const void* owner = nullptr;      // who staged: nullptr a solo call, else the trainer group whose call did
          } cont;
   std::vector<CachedGraph> graphs;
   unsigned long long graph_clock = 0;
@@ -2355,7 +2356,7 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // A weighted call continues a weighted call on the same table generation only, and a plain call a plain one.
   // (the rows a call without staged q left cannot start a call that needs them, nor those of one without staged indices:
   //  cont_class; a prioritised call continues only a prioritised one: its rows were drawn one update behind, the lag-1 chain)
-  const bool cont = ki.continues && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && c->cont.wt_gen == call.wt_gen &&
+  const bool cont = ki.continues && (flags & IQLHIP_TS_CONTINUE) && c->cont.valid && !c->cont.owner && c->cont.wt_gen == call.wt_gen &&
                     c->cont.cont_class == ki.cont_class && c->cont.wt_ver == call.wt_ver &&
                     c->cont.rows == rows_dev && c->cont.ld == ld &&
                     c->cont.size == size && c->cont.B == B && c->cont.seed == seed && c->cont.next_offset == stream_offset &&
@@ -2406,6 +2407,7 @@ static int train_steps(iqlhip_ctx* c, const float* rows_dev, int64_t ld, int64_t
   // steps ends on staging buffer 0, where a chunk's step 0 reads; the next counter follows from the rows drawn
   if (ki.continues && (K & 1) == 0 && (((unsigned long long)K * (unsigned long long)B) & 1ull) == 0) {
     c->cont.valid = true;
+    c->cont.owner = nullptr;
     // (a prioritised call moves its table's version by 1 itself: iqlhip_train_steps_prioritized)
     c->cont.wt_gen = call.wt_gen; c->cont.wt_ver = call.wt_ver + (ki.moves_version ? 1 : 0); c->cont.cont_class = ki.cont_class;
     c->cont.rows = rows_dev; c->cont.ld = ld; c->cont.size = size; c->cont.B = B; c->cont.seed = seed;
@@ -2907,6 +2909,7 @@ struct AuxSections {
 };
 
 struct ScoreParams; struct ScoreRowsParams; struct ScoreGroupAux;      // (iqlhip_score_kernels.h, included further down)
+struct GroupRwRec; struct GroupPrioRec;                                // (iqlhip_group_prio_kernels.h, the file's last include)
 struct iqlhip_group {
   int k = 0;
   int device = 0;
@@ -2967,6 +2970,18 @@ struct iqlhip_group {
   std::vector<char> score_host, score_last;
   hipEvent_t score_up = nullptr;
   bool score_pending = false;
+  // iqlhip_group_step_rw, iqlhip_group_train_steps_weighted_is / _prioritized (DESIGN.md 6j "trainer groups"): a staging
+  // of their own, allocated by the group's first such call — the plain calls upload what they always did.  The agents'
+  // records twice — set h has the pointers of staging half h: a burst's step s runs under set s & 1, an eager step under
+  // set 0 — the dropout records (k, whatever the flags), the statistics / clip records per set, the row-weight and the
+  // draw / update records, and the scalar tables last (group_rw_upload copies up to their used rows).
+  // rw_ones: max over the members' max_batch floats of 1.0f, the weights of a member given none.
+  Staging rw;
+  Section<GroupRec> rw_recs[2]; Section<GroupDropRec> rw_drops; AuxSections rw_aux[2];
+  Section<GroupRwRec> rw_rws; Section<GroupPrioRec> rw_prs; Section<iqlhip_step_scalars> rw_tabs;
+  float* rw_ones = nullptr;
+  hipEvent_t rw_up = nullptr;
+  bool rw_pending = false;
 };
 
 static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
@@ -3282,14 +3297,18 @@ static int group_aux(iqlhip_group* g, const Staging& s, const AuxSections& x, co
   if (clip) { aux->crecs = s.device(x.crecs); aux->gqrecs = s.device(x.gqrecs); }
   return IQLHIP_OK;
 }
+// rws != nullptr: the row-weighted backward under those records (end of file: its instantiations are the library's last).
+static void launch_bwd_group_rw(const iqlhip_ctx* c, const GroupRec* recs, const GroupRwRec* rws, const GroupGeom& q, int K,
+                                hipStream_t st);
 static void group_launch_step(iqlhip_group* g, const GroupRec* recs, const GroupGeom& q, int s, hipStream_t st,
-                              const GroupAux& aux) {
+                              const GroupAux& aux, const GroupRwRec* rws = nullptr) {
   const GroupStatsRec* srecs = aux.srecs;
   const iqlhip_ctx* c = g->m[0];
   const int K = g->k;
   const bool bf = c->precision == 1, dma = c->w0_lds_k > W0_LDS_MAX_K;
   hipLaunchKernelGGL(fwd_group_kernel(bf, dma, /*multi=*/q.fwd_l2 > 0), dim3(q.fwd_nb, K), dim3(256), fwd_lds(c, q.fwd_work), st, recs);
-  hipLaunchKernelGGL(bwd_group_kernel(bf, q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs);
+  if (rws) launch_bwd_group_rw(c, recs, rws, q, K, st);
+  else hipLaunchKernelGGL(bwd_group_kernel(bf, q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs);
   // (between the backward and the update, as in a solo step: enqueue_step; the block partials once for both consumers)
   if (srecs || aux.crecs)
     hipLaunchKernelGGL(iql_stats_gradsq_group_kernel, dim3(4 * stats_parts(c), K), dim3(256), 0, st, recs,
@@ -3320,9 +3339,23 @@ static int group_losses_out(iqlhip_group* g, float* out, int n, hipStream_t st) 
   return IQLHIP_OK;
 }
 
+// The row-weighted calls' staging (iqlhip_group::rw; defined with their entry points at the end of the file): everything
+// they need beyond the members' own buffers, made by the group's first such call; the wait for the previous upload's read
+// of the pinned copy; the upload; member i's scalar table in it; and the step's row-weight records from the caller's arrays.
+struct GroupRwArgs { const float* const* w; float* const* td; };
+static int group_rw_ready(iqlhip_group* g);
+static int group_rw_staging_free(iqlhip_group* g);
+static int group_rw_upload(iqlhip_group* g, int n, hipStream_t st);
+static iqlhip_step_scalars* group_rw_tab(const iqlhip_group* g, int i);
+static const iqlhip_step_scalars* group_rw_sched(const iqlhip_group* g, int i);
+static int group_rw_check_eager(const iqlhip_group* g, const int32_t* rows, const GroupRwArgs& a);
+static const GroupRwRec* group_rw_records(iqlhip_group* g, const GroupRwArgs& a);
+
 // iqlhip_group_step (mixed = false: every batch has batches[0]'s rows) and iqlhip_group_step_mixed.
+// iqlhip_group_step_rw (rwa != nullptr; mixed): the same step from the row-weighted calls' staging, its backward the
+// row-weighted one.
 static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out, void* stream,
-                      bool mixed) {
+                      bool mixed, const GroupRwArgs* rwa = nullptr) {
   if (!g || !batches || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
   GroupRows rows = group_rows_all(batches[0].rows);
   if (mixed)
@@ -3335,11 +3368,16 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
     if (!mixed && batches[i].rows != rows.v[0]) return fail(IQLHIP_EINVAL, "member %d: batch of %d rows, member 0: %d (one batch size per group)", i, batches[i].rows, rows.v[0]);
     if (batches[i].idx_dev && (rc = check_indexed(g->m[i], &batches[i]))) return rc;
   }
-  for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
+  if (rwa && (rc = group_rw_check_eager(g, rows.v, *rwa))) return rc;
   DevGuard guard(g->device);
+  if (rwa && (rc = group_rw_ready(g))) return rc;
+  for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   hipStream_t st = (hipStream_t)stream;
-  rc = group_staging_free(g);
+  rc = rwa ? group_rw_staging_free(g) : group_staging_free(g);
   if (rc) return rc;
+  const Staging& stg = rwa ? g->rw : g->train;
+  const Section<GroupRec> s_recs = rwa ? g->rw_recs[0] : g->recs;
+  const Section<GroupDropRec> s_drops = rwa ? g->rw_drops : g->drops;
   const GroupGeom q = group_geom(g, rows.v);
   for (int i = 0; i < g->k; ++i) {
     iqlhip_ctx* c = g->m[i];
@@ -3348,16 +3386,17 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
     rc = stage_batch(c, &batches[i], st, &xb);
     if (rc) return rc;
     refresh_shadows(c, st);
-    group_record(g, g->train.host(g->recs)[i], i, q, rows.v[i], 1, xb, &sc[i], group_sched(g, i));
-    group_tab(g, i)[0] = sc[i];
+    group_record(g, stg.host(s_recs)[i], i, q, rows.v[i], 1, xb, &sc[i], rwa ? group_rw_sched(g, i) : group_sched(g, i));
+    (rwa ? group_rw_tab(g, i) : group_tab(g, i))[0] = sc[i];
   }
-  const int n_draw = group_drop_records_packed(g, g->train.host(g->drops), rows.v);
+  const int n_draw = group_drop_records_packed(g, stg.host(s_drops), rows.v);
   GroupAux aux;
-  if ((rc = group_aux(g, g->train, g->aux, g->train.host(g->recs), &aux))) return rc;
-  rc = group_upload(g, 1, st);
+  if ((rc = group_aux(g, stg, rwa ? g->rw_aux[0] : g->aux, stg.host(s_recs), &aux))) return rc;
+  const GroupRwRec* rws = rwa ? group_rw_records(g, *rwa) : nullptr;
+  rc = rwa ? group_rw_upload(g, 1, st) : group_upload(g, 1, st);
   if (rc) return rc;
-  group_launch_dropmask(g, g->train.device(g->drops), n_draw, q.max_rows, st);
-  group_launch_step(g, g->train.device(g->recs), q, 0, st, aux);
+  group_launch_dropmask(g, stg.device(s_drops), n_draw, q.max_rows, st);
+  group_launch_step(g, stg.device(s_recs), q, 0, st, aux, rws);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
@@ -5119,4 +5158,261 @@ extern "C" int iqlhip_train_steps_prioritized(iqlhip_ctx* c, const float* rows_d
                    prio_call(table, is_beta, alpha, eps, /*live=*/1u), 0);
   if (!rc) ++table->version;      // the table's content has moved (a failed call leaves no continuation behind anyway)
   return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Trainer groups: per-row loss weights, importance-sampling weights and prioritised replay (include/iqlhip.h
+// "iqlhip_group_step_rw", "iqlhip_group_train_steps_weighted_is", "iqlhip_group_train_steps_prioritized"; DESIGN.md 6j
+// "trainer groups"; kernels: iqlhip_group_prio_kernels.h, the code object's last).
+#include "iqlhip_group_prio_kernels.h"
+
+static auto bwd_group_rw_kernel(bool full) {      // (fp32 only, one-slice (b) blocks: iql_bwd_group_kernel's form)
+  return with_bools([](auto FU) { return &iql_bwd_group_rw_kernel<FU.value>; }, full);
+}
+static void launch_bwd_group_rw(const iqlhip_ctx* c, const GroupRec* recs, const GroupRwRec* rws, const GroupGeom& q, int K,
+                                hipStream_t st) {
+  hipLaunchKernelGGL(bwd_group_rw_kernel(q.full), dim3(q.bwd_nb, K), dim3(256), c->lds_bwd, st, recs, rws);
+}
+
+static int group_rw_ready(iqlhip_group* g) {
+  if (g->rw.dev) return IQLHIP_OK;
+  const int k = g->k;
+  Staging s;
+  for (int h = 0; h < 2; ++h) g->rw_recs[h] = s.add<GroupRec>(k);
+  g->rw_drops = s.add<GroupDropRec>(k);
+  for (int h = 0; h < 2; ++h) g->rw_aux[h].add(s, k);
+  g->rw_rws = s.add<GroupRwRec>(k);
+  g->rw_prs = s.add<GroupPrioRec>(k);
+  g->rw_tabs = s.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
+  g->rw.bytes = s.bytes;
+  int max_batch = 0;
+  for (int i = 0; i < k; ++i) max_batch = std::max(max_batch, (int)g->m[i]->dims.max_batch);
+  const int rc = all_or_nothing(g->own, [&]() -> int {
+    if (int rc_s = g->rw.alloc(g->own)) return rc_s;
+    HIPCHK(g->own.event(&g->rw_up, hipEventDisableTiming));
+    HIPCHK(g->own.dev(&g->rw_ones, (size_t)max_batch * sizeof(float)));
+    const std::vector<float> ones((size_t)max_batch, 1.f);
+    HIPCHK(hipMemcpy(g->rw_ones, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
+    return set_max_lds(1, g->m[0]->lds_bwd, [](unsigned m) { return bwd_group_rw_kernel(m & 1); });
+  });
+  if (rc) g->rw.dev = g->rw.pin = nullptr;
+  return rc;
+}
+static int group_rw_staging_free(iqlhip_group* g) {
+  if (g->rw_pending) HIPCHK(hipEventSynchronize(g->rw_up));
+  g->rw_pending = false;
+  return IQLHIP_OK;
+}
+static int group_rw_upload(iqlhip_group* g, int n, hipStream_t st) {
+  const size_t bytes = g->rw_tabs.off + ((size_t)(g->k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars);
+  HIPCHK(hipMemcpyAsync(g->rw.dev, g->rw.pin, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(g->rw_up, st));
+  g->rw_pending = true;
+  return IQLHIP_OK;
+}
+static iqlhip_step_scalars* group_rw_tab(const iqlhip_group* g, int i) { return g->rw.host(g->rw_tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
+static const iqlhip_step_scalars* group_rw_sched(const iqlhip_group* g, int i) { return g->rw.device(g->rw_tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
+
+// `rc` of a solo check as member i's refusal: the message names the member.
+static int member_fail(int i, int rc) {
+  if (!rc) return rc;
+  const std::string msg = g_err;
+  return fail(rc, "member %d: %s", i, msg.c_str());
+}
+// What no row-weighted group call is built for (the solo refusals, row_weights_check): bf16.  (An exchange and the
+// large-batch path: the group rules, group_check_call.)
+static int group_rw_check_member(const iqlhip_group* g, int i) {
+  if (g->m[i]->precision == 1) return fail(IQLHIP_EUNSUPPORTED, "member %d: per-row loss weights are not supported at bf16 precision", i);
+  return IQLHIP_OK;
+}
+static int group_rw_check_eager(const iqlhip_group* g, const int32_t* rows, const GroupRwArgs& a) {
+  (void)rows;
+  if (!a.w || !a.td) return fail(IQLHIP_EINVAL, "NULL argument");
+  for (int i = 0; i < g->k; ++i) {
+    if (int rc = group_rw_check_member(g, i)) return rc;
+    if ((((uintptr_t)a.w[i]) & 3) || (((uintptr_t)a.td[i]) & 7))
+      return fail(IQLHIP_EINVAL, "member %d: row weights must be 4-byte, TD errors 8-byte aligned", i);
+  }
+  return IQLHIP_OK;
+}
+static const GroupRwRec* group_rw_records(iqlhip_group* g, const GroupRwArgs& a) {
+  GroupRwRec* r = g->rw.host(g->rw_rws);
+  for (int i = 0; i < g->k; ++i) r[i] = GroupRwRec{a.w[i] ? a.w[i] : g->rw_ones, a.td[i]};
+  return g->rw.device(g->rw_rws);
+}
+
+extern "C" int iqlhip_group_step_rw(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc,
+                                    const float* const* row_w_dev, float* const* td_out_dev, float* out, void* stream) {
+  if (!row_w_dev || !td_out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  const GroupRwArgs a{row_w_dev, td_out_dev};
+  return group_step(g, batches, sc, out, stream, /*mixed=*/true, &a);
+}
+
+// iqlhip_group_train_steps_weighted_is (alpha == nullptr) and iqlhip_group_train_steps_prioritized.  Per call: the rows of
+// step 0 (members that continue have theirs staged), then per step s: the rows, q and indices of step s + 1 into the other
+// staging half, the loss weights of step s from its half's q, the step under record set s & 1 with the row-weighted
+// backward, and — prioritised — the table updates from its TD errors.  One linear chain on `stream` (the
+// hazard table).
+static int group_train_steps_rw(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size, const int32_t* B,
+                                const void* const* tables, int32_t n, const uint64_t* seeds, const uint64_t* offsets,
+                                int32_t flags, void* stream, iqlhip_weights* const* wtabs, const float* is_beta,
+                                const float* alpha, const float* eps) {
+  const bool prio = alpha != nullptr;
+  if (!g || !rows || !size || !B || !tables || !seeds || !offsets || !wtabs || !is_beta || (prio && !eps))
+    return fail(IQLHIP_EINVAL, "NULL argument");
+  if (flags & ~IQLHIP_GROUP_TS_CONTINUE) return fail(IQLHIP_EINVAL, "unknown flags 0x%x", (unsigned)flags);
+  int rc = group_check_call(g, B);
+  if (rc) return rc;
+  if (n < 1 || n > IQLHIP_GROUP_MAX_STEPS) return fail(IQLHIP_EINVAL, "n_steps outside [1,%d]", IQLHIP_GROUP_MAX_STEPS);
+  for (int i = 0; i < g->k; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    if ((rc = member_fail(i, check_train_args(c, rows[i], ld, B[i])))) return rc;
+    if (size[i] < 1) return fail(IQLHIP_EINVAL, "member %d: empty buffer", i);
+    if (!tables[i]) return fail(IQLHIP_EINVAL, "member %d: NULL scalar table", i);
+    if ((rc = group_rw_check_member(g, i))) return rc;
+    if ((rc = member_fail(i, inject_check(c)))) return rc;
+    if (!(is_beta[i] >= 0.f) || !std::isfinite(is_beta[i])) return fail(IQLHIP_EINVAL, "member %d: is_beta must be finite and >= 0", i);
+    const iqlhip_weights* t = wtabs[i];
+    if (!t) {
+      if (prio) return fail(IQLHIP_EINVAL, "member %d: NULL table (a prioritised call updates every member's table)", i);
+      continue;
+    }
+    if ((rc = weights_check_member(t, i, size[i], g->device))) return rc;
+    if (!prio) continue;
+    if (!t->local) return fail(IQLHIP_EINVAL, "member %d: the table is not updatable (iqlhip_weights_build_updatable)", i);
+    if ((rc = member_fail(i, prio_exponents_check(alpha[i], eps[i])))) return rc;
+    if (B[i] > WT_UPDATE_SLICE) return fail(IQLHIP_EUNSUPPORTED, "member %d: prioritised calls take batches of at most %d rows", i, WT_UPDATE_SLICE);
+    for (int j = 0; j < i; ++j)
+      if (wtabs[j] == t)
+        return fail(IQLHIP_EINVAL, "member %d: the table of member %d again (a prioritised call updates a table per member; "
+                    "their updates would race)", i, j);
+  }
+  DevGuard guard(g->device);
+  if ((rc = group_rw_ready(g))) return rc;
+  for (int i = 0; i < g->k; ++i) {      // the members' staging halves: the buffers their solo calls of these kinds use
+    iqlhip_ctx* c = g->m[i];
+    if (!c->is_buf) HIPCHK(c->own.dev(&c->is_buf, (3 * (size_t)c->dims.max_batch + 4) * sizeof(float), 0));
+    if (wtabs[i] && !c->prio_buf) HIPCHK(c->own.dev(&c->prio_buf, 24 * (size_t)c->dims.max_batch + 4 * sizeof(float), 0));
+  }
+  for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = group_rw_staging_free(g))) return rc;
+  const GroupGeom q = group_geom(g, B);
+  const int cont_class = prio ? 2 : 1;      // (KindInfo::cont_class of the solo kinds: what lies staged besides the rows)
+  GroupRec* recs_host[2] = {g->rw.host(g->rw_recs[0]), g->rw.host(g->rw_recs[1])};
+  bool all_cont = true;
+  for (int i = 0; i < g->k; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    const iqlhip_weights* t = wtabs[i];
+    const int MB = c->dims.max_batch;
+    // does member i start on the rows this group's previous call staged for it?  (the solo rules: train_steps)
+    const bool cont = (flags & IQLHIP_GROUP_TS_CONTINUE) && t && c->cont.valid && c->cont.owner == g &&
+                      c->cont.cont_class == cont_class && c->cont.wt_gen == t->gen && c->cont.wt_ver == t->version &&
+                      c->cont.rows == rows[i] && c->cont.ld == ld && c->cont.size == size[i] && c->cont.B == B[i] &&
+                      c->cont.seed == seeds[i] && c->cont.next_offset == offsets[i] && c->cont.drop_p == c->drop_p &&
+                      c->cont.drop_seed == c->drop_seed && c->cont.drop_step == c->drop_step;
+    c->cont.valid = false;
+    all_cont = all_cont && cont;
+    refresh_shadows(c, st);
+    const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
+    GroupRec& r = recs_host[0][i];
+    group_record(g, r, i, q, B[i], n, c->xb, &tab[0], group_rw_sched(g, i));
+    r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
+    GroupRec& r1 = recs_host[1][i];      // the other half's set: the rows and the keep-bits the odd steps read
+    r1 = r;
+    r1.p.xb = c->xb2; r1.q_xb = c->xb2; r1.xb = c->xb2;
+    if (r1.p.drop_bits) r1.p.drop_bits = c->drop_bits + (size_t)2 * MB * 8;
+    memcpy(group_rw_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
+    GroupPrioRec& w = g->rw.host(g->rw_prs)[i];
+    memset(&w, 0, sizeof w);
+    w.wt = t ? weights_tab(t) : WTab{nullptr, 0u, 0, 0};
+    w.xb[0] = c->xb; w.xb[1] = c->xb2;
+    w.q[0] = c->is_buf; w.q[1] = c->is_buf + MB;
+    if (t) { w.idx[0] = prio_idx(c, 0); w.idx[1] = prio_idx(c, 1); }
+    w.drop_bits[0] = c->drop_bits; w.drop_bits[1] = c->drop_bits + (size_t)2 * MB * 8;
+    w.c = c->is_buf + 2 * (size_t)MB;
+    w.beta = is_beta[i];
+    w.skip0 = cont ? 1 : 0;
+    if (prio) {
+      w.up = WUpd{t->tab, t->stamp, t->flags, (unsigned)t->n, t->levels, t->sh0, t->sat_bits};
+      w.delta = t->delta;
+      w.td = prio_td(c);
+      w.bound = (long long)t->n;
+      w.m = (unsigned)B[i];
+      w.alpha = alpha[i]; w.eps = eps[i];
+    }
+    g->rw.host(g->rw_rws)[i] = GroupRwRec{w.c, prio ? prio_td(c) : nullptr};
+  }
+  // actor dropout: every member's record inside its GroupPrioRec (active = the member draws), step s at drop_step + s into
+  // half s & 1 (GroupPrioRec::drop_bits)
+  bool draws = false;
+  for (int i = 0; i < g->k; ++i) {
+    GroupDropRec& d = g->rw.host(g->rw_prs)[i].drop;
+    d = group_drop_record(g->m[i], B[i]);
+    d.active = ((g->flags & IQLHIP_GROUP_DROPOUT) && group_draws(g->m[i])) ? 1 : 0;
+    draws = draws || d.active;
+  }
+  GroupAux aux[2];
+  for (int h = 0; h < 2; ++h)
+    if ((rc = group_aux(g, g->rw, g->rw_aux[h], recs_host[h], &aux[h]))) return rc;
+  if ((rc = group_rw_upload(g, n, st))) return rc;
+  const GroupRec* recs[2] = {g->rw.device(g->rw_recs[0]), g->rw.device(g->rw_recs[1])};
+  const GroupPrioRec* prs = g->rw.device(g->rw_prs);
+  const GroupRwRec* rws = g->rw.device(g->rw_rws);
+  // (grids sized by the largest member, as iqlhip_group_train_steps_weighted's: a wave per IQL_GROUP_WT_ROWS_PER_WAVE rows,
+  //  the keep-bit words behind the gather at the far end; every record bounds its own member's rows and words)
+  const int wt_nb = (q.max_rows + 4 * IQL_GROUP_WT_ROWS_PER_WAVE - 1) / (4 * IQL_GROUP_WT_ROWS_PER_WAVE);
+  const int wt_drop_nb = wt_nb + (2 * q.max_rows * 8 + 255) / 256;
+  auto gather = [&](int s) {
+    if (draws)
+      hipLaunchKernelGGL(iql_gather_weighted_qi_drop_group_kernel, dim3(wt_drop_nb, g->k), dim3(256), 0, st, recs[0], prs, s);
+    else
+      hipLaunchKernelGGL(iql_gather_weighted_qi_group_kernel, dim3(wt_nb, g->k), dim3(256), 0, st, recs[0], prs, s);
+  };
+  const unsigned upd_nb = ((unsigned)q.max_rows + 255u) / 256u, apply_nb = ((unsigned)q.max_rows + 3u) / 4u;
+  if (!all_cont || draws) gather(0);
+  for (int s = 0; s < n; ++s) {
+    if (s + 1 < n || (n & 1) == 0) gather(s + 1);      // (step n of an even call: what a continuing call starts on)
+    hipLaunchKernelGGL(iql_is_weights_group_kernel, dim3(1, g->k), dim3(256), 0, st, recs[0], prs, s);
+    group_launch_step(g, recs[s & 1], q, s, st, aux[s & 1], rws);
+    if (prio) {
+      hipLaunchKernelGGL(iql_wt_update_stamp_td_group_kernel, dim3(upd_nb, g->k), dim3(256), 0, st, prs, s & 1);
+      hipLaunchKernelGGL(iql_wt_update_delta_td_group_kernel, dim3(upd_nb, g->k), dim3(256), 0, st, prs, s & 1);
+      hipLaunchKernelGGL(iql_wt_update_apply_td_group_kernel, dim3(apply_nb, g->k), dim3(256), 0, st, prs, s & 1);
+    }
+  }
+  if (g->flags & IQLHIP_GROUP_DROPOUT)      // (as iqlhip_train_steps: the position of every context with a rate above 0)
+    for (int i = 0; i < g->k; ++i) if (g->m[i]->drop_p > 0.f) g->m[i]->drop_step += (unsigned long long)n;
+  for (int i = 0; i < g->k; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    iqlhip_weights* t = wtabs[i];
+    if (t && (n & 1) == 0) {        // an even call ends on staging half 0, where a call's step 0 reads
+      c->cont.valid = true;
+      c->cont.owner = g;
+      c->cont.wt_gen = t->gen; c->cont.wt_ver = t->version + (prio ? 1 : 0); c->cont.cont_class = cont_class;
+      c->cont.rows = rows[i]; c->cont.ld = ld; c->cont.size = size[i]; c->cont.B = B[i]; c->cont.seed = seeds[i];
+      c->cont.next_offset = offsets[i] + ((unsigned long long)n * (unsigned long long)B[i]) / 2ull;
+      c->cont.drop_p = c->drop_p; c->cont.drop_seed = c->drop_seed; c->cont.drop_step = c->drop_step;
+    }
+    if (prio) ++t->version;         // the table's content has moved (iqlhip_train_steps_prioritized)
+  }
+  HIPCHK(hipGetLastError());
+  g->last_n = n;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_train_steps_weighted_is(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
+                                                    const int32_t* B, const void* const* tables, int32_t n,
+                                                    const uint64_t* seeds, const uint64_t* offsets, int32_t flags,
+                                                    void* stream, const iqlhip_weights* const* wtabs, const float* is_beta) {
+  return group_train_steps_rw(g, rows, ld, size, B, tables, n, seeds, offsets, flags, stream,
+                              const_cast<iqlhip_weights* const*>(wtabs), is_beta, nullptr, nullptr);
+}
+extern "C" int iqlhip_group_train_steps_prioritized(iqlhip_group* g, const float* const* rows, int64_t ld, const int64_t* size,
+                                                    const int32_t* B, const void* const* tables, int32_t n,
+                                                    const uint64_t* seeds, const uint64_t* offsets, int32_t flags,
+                                                    void* stream, iqlhip_weights* const* wtabs, const float* is_beta,
+                                                    const float* alpha, const float* eps) {
+  if (!alpha || !eps) return fail(IQLHIP_EINVAL, "NULL argument");
+  return group_train_steps_rw(g, rows, ld, size, B, tables, n, seeds, offsets, flags, stream, wtabs, is_beta, alpha, eps);
 }

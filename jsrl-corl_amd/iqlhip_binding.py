@@ -31,6 +31,7 @@ IQLHIP_MAX_GROUP = 16         # members of one trainer group (include/iqlhip.h)
 IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the actions are written
 IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train with actor dropout
 IQLHIP_GROUP_MAX_STEPS = 1024  # steps per iqlhip_group_train_steps call
+IQLHIP_GROUP_TS_CONTINUE = 1   # iqlhip_group_train_steps_weighted_is / _prioritized: go on with the previous call's staged rows
 IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
 XCH_NONE, XCH_RCCL, XCH_P2P = 0, 1, 2
@@ -229,6 +230,17 @@ SYMBOLS = [
                                                     C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int32,
                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p,
                                                     C.POINTER(C.c_void_p)]),
+    ("iqlhip_group_step_rw", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(StepScalars), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_void_p]),
+    ("iqlhip_group_train_steps_weighted_is", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
+                                                       C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int32,
+                                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p,
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_float)]),
+    ("iqlhip_group_train_steps_prioritized", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
+                                                       C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int32,
+                                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p,
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                       C.POINTER(C.c_float)]),
     ("iqlhip_group_actor_forward", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_void_p),
                                              C.c_int64, C.c_int32, C.c_void_p]),

@@ -68,6 +68,16 @@ None entry: uniformly), and ends where its solo call ends:
     tables = [SampleWeights(w_k) for w_k in per_member_weights]                          # K tables, one shared buffer
     losses = group.train_steps_weighted(buffer, 1000, 256, seeds=[0, 1, 2, 3], weights=tables)
 
+Per-row loss weights, importance-sampling weights and prioritised replay (ImplicitQLearning.train(loss_weights=,
+return_td=), train_steps_weighted(is_beta=), train_steps_prioritized) have group forms, fp32 only: a sweep
+over seeds or over alpha / eps / is_beta stays in the group, every member's table refreshed by its own TD errors:
+
+    logs = group.train(batches, loss_weights=[c_0, c_1, None, c_3], return_td=True);  tds = group.last_td_errors()
+    losses = group.train_steps_weighted(buffer, 1000, 256, seeds, weights=tables, is_beta=[0.4, 0.6, 0.8, 1.0])
+    tables = [SampleWeights(w, updatable=True, max_weight=64.0) for _ in trainers]           # one table per member
+    losses = group.train_steps_prioritized(buffer, 1000, 256, seeds, alpha=[0.4, 0.6, 0.8, 1.0], is_beta=0.5,
+                                           weights=tables)
+
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
 runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
@@ -233,10 +243,36 @@ class ImplicitQLearningGroup:
                 logs[-1].update({"stats/" + name: float(stats[0, k, i]) for i, name in enumerate(hb.STAT_NAMES)})
         return logs
 
-    def train(self, batches: Sequence) -> List[Dict[str, float]]:
+    def _loss_weight_args(self, Bs, loss_weights, return_td: bool):
+        """Every member's (weights or None, TD tensor or None) of a row-weighted step, checked on the host: loss_weights
+        is None or K entries, each None (weights of one) or what ImplicitQLearning.train(loss_weights=) takes."""
+        from iqlhip_trainer import check_loss_weights
+        K = len(self.trainers)
+        lws = [None] * K if loss_weights is None else list(loss_weights)
+        if len(lws) != K:
+            raise ValueError(f"iqlhip: {len(lws)} loss_weights entries for a group of {K} (a tensor or None per member)")
+        pairs = []
+        for t, B, lw in zip(self.trainers, Bs, lws):
+            if getattr(t, "_precision", "f32") == "bf16":
+                raise NotImplementedError("iqlhip: per-row loss weights (loss_weights / return_td) are not supported at "
+                                          "bf16 precision: the row-weighted backward is an fp32 kernel")
+            w = None if lw is None else check_loss_weights(lw, B, t._dev)
+            td = torch.empty((B, 2), dtype=torch.float32, device=t._dev) if return_td else None
+            pairs.append((w, td))
+        return pairs
+
+    def last_td_errors(self) -> List[torch.Tensor]:
+        """K tensors [B_k, 2] on the device: every member's ImplicitQLearning.last_td_errors() — (q1 - y, q2 - y) of the
+        rows of the last train(..., return_td=True) step.  RuntimeError once a member has stepped again."""
+        return [t.last_td_errors() for t in self.trainers]
+
+    def train(self, batches: Sequence, loss_weights=None, return_td: bool = False) -> List[Dict[str, float]]:
         """One step per member on its own batch (ImplicitQLearning.train for each, in one set of launches).  All batches
         have the same number of rows, unless the group was built with mixed_batch=True.  Returns one losses dict per
-        member."""
+        member.
+        loss_weights: None, or K entries — member k's [B_k] float32 device tensor, or None for weights of one — that
+        multiply every row's loss terms (ImplicitQLearning.train(batch, loss_weights=) for each member; the returned
+        losses are the weighted ones).  return_td: every member's TD errors are kept for last_td_errors().  fp32 only."""
         batches = list(batches)
         K = len(self.trainers)
         if len(batches) != K:
@@ -248,7 +284,11 @@ class ImplicitQLearningGroup:
                 raise ValueError(f"iqlhip: batch {i} has {B} rows, batch 0 has {Bs[0]} (one batch size per group)")
         for B in Bs:
             self._check_batch_size(B)
+        rw = loss_weights is not None or return_td
+        pairs = self._loss_weight_args(Bs, loss_weights, return_td) if rw else None
         if K == 1:      # a group of one IS the solo step (whose eager path returns through host-mapped words: faster)
+            if rw:
+                return [self.trainers[0].train(batches[0], loss_weights=pairs[0][0], return_td=return_td)]
             return [self.trainers[0].train(batches[0])]
         for t, B in zip(self.trainers, Bs):
             t._prepare(B)
@@ -260,10 +300,21 @@ class ImplicitQLearningGroup:
         scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
         out = (C.c_float * (3 * K))()
         g = self._group()
-        step = hb.lib().iqlhip_group_step_mixed if self._mixed_batch else hb.lib().iqlhip_group_step
-        hb.check(step(g, structs, scs, out, self.trainers[0]._stream()))
+        if rw:
+            for t in self.trainers:
+                t._last_td = None
+            w_ptrs = (C.c_void_p * K)(*[None if w is None else w.data_ptr() for w, _ in pairs])
+            td_ptrs = (C.c_void_p * K)(*[None if td is None else td.data_ptr() for _, td in pairs])
+            hb.check(hb.lib().iqlhip_group_step_rw(g, structs, scs, w_ptrs, td_ptrs, out, self.trainers[0]._stream()))
+        else:
+            step = hb.lib().iqlhip_group_step_mixed if self._mixed_batch else hb.lib().iqlhip_group_step
+            hb.check(step(g, structs, scs, out, self.trainers[0]._stream()))
         del keep
-        return self._commit_step(adam_next, out)
+        logs = self._commit_step(adam_next, out)
+        if rw:
+            for t, (_, td) in zip(self.trainers, pairs):
+                t._last_td, t._last_td_it = td, t.total_it
+        return logs
 
     # ------------------------------------------------------------------ device-drawn steps
     def _burst_args(self, buffers, seeds, n_steps: int):
@@ -296,14 +347,17 @@ class ImplicitQLearningGroup:
         pairs = [t._train_steps_args(buf, B) for t, buf, B in zip(self.trainers, bufs, Bs)]
         return [size for size, _ in pairs], [ib for _, ib in pairs]
 
-    def _run_burst(self, n_steps: int, Bs, inv, seeds, chunk: int, return_losses: bool, return_stats: bool, call):
+    def _run_burst(self, n_steps: int, Bs, inv, seeds, chunk: int, return_losses: bool, return_stats: bool, call,
+                   continues: bool = False):
         """The multi-step loop behind train_steps, train_steps_weighted and train_steps_replay_mix, whose checks have
         all passed: n_steps in library calls of at most `chunk` steps.  Bs, inv, seeds: every member's batch size, one
         over it and seed.  call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream) makes the kind's one library call for the
         next k steps — tab_ptrs the members' scalar tables, offs their places in their Philox streams — and returns
         its code.  A group call never continues staged rows and leaves none: every member's token is dropped, also by
-        a call that fails.  Returns the statistics [n_steps, K, 16] when return_stats, else losses [K, n_steps, 3]
-        (None unless return_losses)."""
+        a call that fails.  continues (the bursts with importance-sampling weights): call takes an eighth argument, the
+        library call's flags — IQLHIP_GROUP_TS_CONTINUE for every piece of this Python call but the first, so the pieces
+        go on with each other's staged rows and nothing an earlier Python call staged is ever continued.  Returns the
+        statistics [n_steps, K, 16] when return_stats, else losses [K, n_steps, 3] (None unless return_losses)."""
         K = len(self.trainers)
         chunk = max(1, min(int(chunk), K_MAX, hb.IQLHIP_GROUP_MAX_STEPS))
         lib, stream = hb.lib(), self.trainers[0]._stream()
@@ -319,7 +373,10 @@ class ImplicitQLearningGroup:
             offs = (C.c_uint64 * K)(*[t.total_it * half for t, half in zip(self.trainers, halves)])
             tabs = [np.ascontiguousarray(t._scalar_table(k, ib)) for t, ib in zip(self.trainers, inv)]
             tab_ptrs = (C.c_void_p * K)(*[tb.ctypes.data for tb in tabs])
-            rc = call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream)
+            if continues:
+                rc = call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream, hb.IQLHIP_GROUP_TS_CONTINUE if done else 0)
+            else:
+                rc = call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream)
             for t in self.trainers:
                 t._ts_token = None
             hb.check(rc)
@@ -371,7 +428,7 @@ class ImplicitQLearningGroup:
 
     # ------------------------------------------------------------------ device-drawn steps, rows drawn by weight
     def train_steps_weighted(self, buffers, n_steps: int, batch_size, seeds: Sequence[int], weights=None,
-                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False):
+                             return_losses: bool = True, chunk: int = K_MAX, return_stats: bool = False, is_beta=None):
         """train_steps with every member's rows drawn by a weight table (ImplicitQLearning.train_steps_weighted for
         each).  buffers, batch_size, seeds, chunk and the return value as train_steps.  weights: None —
         member k draws by buffers[k]'s own set_sample_weights table (ValueError for a buffer without one); one
@@ -381,11 +438,19 @@ class ImplicitQLearningGroup:
         weights=...) leaves it, a uniform member where its solo train_steps does.  Every table must stay alive until
         the queued steps have run (SampleWeights.free and set_sample_weights wait for the device).  Everything is
         checked before anything is launched or any counter moves; the refusals are train_steps' and
-        train_steps_weighted's."""
+        train_steps_weighted's.
+        is_beta (None: the call above, unchanged; else a float >= 0 or K of them): member k's loss terms are weighted by
+        c = (q_min / q_row) ** is_beta[k] over each step's batch — its solo train_steps_weighted(..., is_beta=is_beta[k]),
+        bit for bit; a uniform member gets c = 1 and still ends where its solo train_steps does.  fp32 only."""
         import iqlhip_weighted as wtd
         K = len(self.trainers)
         bufs, seeds = self._burst_args(buffers, seeds, n_steps)
         Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
+        betas = None
+        if is_beta is not None:
+            betas = wtd.check_group_is_beta(K, is_beta)
+            for t in self.trainers:
+                t._is_beta_arg(0.0)          # (fp32 only: NotImplementedError for a bf16 member)
         self._check_members()
         for B in Bs:
             self._check_batch_size(B)
@@ -406,7 +471,8 @@ class ImplicitQLearningGroup:
             else:
                 out = t.train_steps_weighted(bufs[0], n_steps, Bs[0], seed=seeds[0], return_losses=return_losses,
                                              chunk=chunk, return_stats=return_stats,
-                                             weights=None if e is bufs[0] else e)
+                                             weights=None if e is bufs[0] else e,
+                                             is_beta=None if betas is None else betas[0])
             return self._solo_burst_result(out, return_stats)
         sizes, inv = self._members_steps_args(bufs, Bs)
         # (an updatable table spans a capacity, and that is the size its member's draw is given: rows beyond the index
@@ -426,9 +492,84 @@ class ImplicitQLearningGroup:
         wt_arr = (C.c_void_p * K)(*[None if e is None else (e._table if isinstance(e, wtd.SampleWeights) else e._weights)
                                     for e in entries])
 
+        if betas is not None:
+            fn_is, beta_arr = hb.lib().iqlhip_group_train_steps_weighted_is, (C.c_float * K)(*betas)
+
+            def call_is(g, B_arr, tab_ptrs, k, seed_arr, offs, stream, flags):
+                return fn_is(g, rows, ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, flags, stream, wt_arr, beta_arr)
+            return self._run_burst(n_steps, Bs, inv, seeds, chunk, return_losses, return_stats, call_is, continues=True)
+
         def call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream):
             return fn(g, rows, ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, 0, stream, wt_arr)
         return self._run_burst(n_steps, Bs, inv, seeds, chunk, return_losses, return_stats, call)
+
+    # ------------------------------------------------------------------ prioritised replay (DESIGN.md 6j "trainer groups")
+    def train_steps_prioritized(self, buffers, n_steps: int, batch_size, seeds: Sequence[int], alpha=0.6, eps=1e-3,
+                                is_beta=0.0, weights=None, chunk: int = K_MAX, return_losses: bool = True,
+                                return_stats: bool = False):
+        """ImplicitQLearning.train_steps_prioritized for every member in one set of launches: prioritised replay whose
+        steps write their TD errors back into the member's own updatable table, lag of one step included, with no host
+        round trip.  buffers, batch_size, seeds and the return value as train_steps_weighted.  weights: None — member k
+        updates buffers[k]'s own updatable table — or a list of K updatable SampleWeights.  Every member needs a table of
+        its OWN (ValueError for a None entry and for one table given to two members: their updates would race); sharing
+        a buffer's rows is fine.  alpha, eps, is_beta: a float, or K of them — a sweep over the exponents is one call.
+        chunk is rounded as in the solo call (down to an even number, at least 2); inside one call the pieces go on with
+        the lag-1 chain, a member with an odd batch size draws afresh in every piece, and a call never starts on rows
+        an earlier call staged.  Afterwards member k — parameters, Adam state, losses, statistics, its table — is bit for
+        bit where its solo train_steps_prioritized(buffers[k], n_steps, batch_size[k], seed=seeds[k], alpha=alpha[k],
+        eps=eps[k], is_beta=is_beta[k], chunk=chunk, weights=...) leaves it.  The tables' versions move as there.
+        ValueError for a static table, for alpha, eps or is_beta negative or not finite, for alpha = eps = 0;
+        NotImplementedError at bf16 precision, under data parallelism and with injected dropout masks pending — all
+        before anything is launched or any counter moves."""
+        import iqlhip_weighted as wtd
+        K = len(self.trainers)
+        bufs, seeds = self._burst_args(buffers, seeds, n_steps)
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
+        alphas, epss = wtd.check_group_priority_args(K, alpha, eps)
+        betas = wtd.check_group_is_beta(K, is_beta)
+        for t in self.trainers:
+            t._is_beta_arg(0.0)              # (fp32 only: NotImplementedError for a bf16 member)
+        self._check_members()
+        for B in Bs:
+            self._check_batch_size(B)
+        entries = wtd.check_group_prioritized(bufs, weights, K)
+        for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
+            if buf._rows.device != t._dev:
+                raise ValueError(f"iqlhip: the replay buffer must live on the trainer's GPU ({t._dev}; member {i})")
+        if return_stats and not any(t._step_stats for t in self.trainers):
+            raise ValueError("iqlhip: train_steps_prioritized(return_stats=True) needs set_step_stats(True) on at least "
+                             "one member")
+        for t in self.trainers:
+            t._refuse_injected_masks()
+        if K == 1:      # a group of one IS the solo call
+            e = entries[0]
+            out = self.trainers[0].train_steps_prioritized(
+                bufs[0], n_steps, Bs[0], seed=seeds[0], alpha=alphas[0], eps=epss[0], is_beta=betas[0], chunk=chunk,
+                return_losses=return_losses, return_stats=return_stats, weights=None if e is bufs[0] else e)
+            return self._solo_burst_result(out, return_stats)
+        _, inv = self._members_steps_args(bufs, Bs)
+        # (an updatable table spans a capacity, and that is the size its member's draw is given)
+        sizes = [e.n if isinstance(e, wtd.SampleWeights) else e.sample_weights_n for e in entries]
+        if len({b._ld for b in bufs}) != 1:
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        fn, ld = hb.lib().iqlhip_group_train_steps_prioritized, bufs[0]._ld
+        rows = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
+        size_arr = (C.c_int64 * K)(*sizes)
+        wt_arr = (C.c_void_p * K)(*[e._table if isinstance(e, wtd.SampleWeights) else e._weights for e in entries])
+        beta_arr, alpha_arr, eps_arr = (C.c_float * K)(*betas), (C.c_float * K)(*alphas), (C.c_float * K)(*epss)
+
+        def call(g, B_arr, tab_ptrs, k, seed_arr, offs, stream, flags):
+            rc = fn(g, rows, ld, size_arr, B_arr, tab_ptrs, k, seed_arr, offs, flags, stream, wt_arr, beta_arr, alpha_arr,
+                    eps_arr)
+            if rc == 0:                    # (the library moved every table's content version: the Python mirrors follow)
+                for e in entries:
+                    if isinstance(e, wtd.SampleWeights):
+                        e._version += 1
+                    else:
+                        e._weights_version += 1
+            return rc
+        chunk = max(2, min(int(chunk), K_MAX) & ~1)
+        return self._run_burst(n_steps, Bs, inv, seeds, chunk, return_losses, return_stats, call, continues=True)
 
     # ------------------------------------------------------------------ the online loop
     def _online_rows(self, ld: int, states, actions, rewards, next_states, dones, act_next):

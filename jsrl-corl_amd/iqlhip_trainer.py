@@ -1095,7 +1095,7 @@ class ImplicitQLearning:
         nothing.  The table's version moves with every library call: a train_steps_weighted call that follows gathers
         afresh.  Returns what train_steps returns.  ValueError for a static table, for alpha, eps or is_beta negative or
         not finite, for alpha = eps = 0; NotImplementedError at bf16 precision, under data parallelism and with injected
-        dropout masks pending — all before anything moves.  Not covered: trainer groups, mixed batches, online_step*,
+        dropout masks pending — all before anything moves.  Not covered: mixed batches, online_step*,
         priorities of newly added rows (follow add_transition with update_sample_weights), annealing inside a call."""
         if return_stats and not self._step_stats:
             raise ValueError("iqlhip: train_steps_prioritized(return_stats=True) needs set_step_stats(True) first")

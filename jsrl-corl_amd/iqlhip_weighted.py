@@ -136,6 +136,41 @@ def check_priority_args(alpha, eps) -> tuple:
     return out[0], out[1]
 
 
+def per_member(value, K: int, name: str) -> list:
+    """A group call's per-member number: one value for all K members, or a list / tuple / array of K.  Returns K
+    entries as given (the caller checks their values); ValueError for another length."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        vals = list(value)
+        if len(vals) != K:
+            raise ValueError(f"iqlhip: {len(vals)} values of {name} for a group of {K}")
+        return vals
+    return [value] * K
+
+
+def check_group_priority_args(K: int, alpha, eps) -> tuple:
+    """(alphas, epss) of a prioritised group call, each K floats: alpha and eps are one number for all members or K of
+    them, every pair checked by check_priority_args (the ValueError names the member)."""
+    alphas, epss = per_member(alpha, K, "alpha"), per_member(eps, K, "eps")
+    out = []
+    for i, (a, e) in enumerate(zip(alphas, epss)):
+        try:
+            out.append(check_priority_args(a, e))
+        except ValueError as err:
+            raise ValueError(f"{err} (member {i})") from None
+    return [a for a, _ in out], [e for _, e in out]
+
+
+def check_group_is_beta(K: int, is_beta) -> list:
+    """is_beta of a group call as K floats: one number or K of them, each finite and >= 0 (the ValueError names the member)."""
+    out = []
+    for i, b in enumerate(per_member(is_beta, K, "is_beta")):
+        try:
+            out.append(check_is_args(1, b, None)[0])
+        except ValueError as err:
+            raise ValueError(f"{err} (member {i})") from None
+    return out
+
+
 def build_table(w_dev, n: int, stream, updatable: bool = False, capacity=None, max_weight=None):
     """The library's table over the device vector w_dev[0..n): (handle, generation)."""
     import iqlhip_binding as hb
@@ -456,4 +491,24 @@ def check_group_call(buffers, weights, K: int):
                 raise ValueError(f"iqlhip: train_steps needs a ReplayBuffer that lives on the GPU (member {i})")
             continue
         check_table(b, w, i)
+    return entries
+
+
+def check_group_prioritized(buffers, weights, K: int):
+    """check_group_call for a prioritised group call, which updates every member's table: each of the K members needs an
+    UPDATABLE table (no None entry), and no two members the same one — their updates would race, and "where the solo call
+    leaves the member" would mean nothing.  Sharing a buffer's rows is fine; its own table can then serve one member only.
+    Returns the K entries (a buffer — its own table — or a SampleWeights).  ValueError otherwise, before any library call."""
+    entries = check_group_call(buffers, weights, K)
+    for i, e in enumerate(entries):
+        if e is None:
+            raise ValueError(f"iqlhip: prioritised replay needs a table for every member (member {i} has none)")
+        updatable = e.updatable if isinstance(e, SampleWeights) else getattr(e, "_weights_updatable", False)
+        if not updatable:
+            raise ValueError("iqlhip: prioritised replay needs updatable sample weights "
+                             f"(set_sample_weights(..., updatable=True) / SampleWeights(..., updatable=True); member {i})")
+        for j in range(i):
+            if entries[j] is e:
+                raise ValueError(f"iqlhip: member {i} draws by the table of member {j}: a prioritised call updates one "
+                                 "table per member (give each member a SampleWeights of its own)")
     return entries
