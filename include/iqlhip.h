@@ -397,6 +397,47 @@ int iqlhip_train_steps_prioritized(iqlhip_ctx* ctx, const float* rows_dev, int64
                                    int32_t flags, void* stream, iqlhip_weights* table, float is_beta, float alpha, float eps);
 int iqlhip_train_steps_prioritized_prepare(iqlhip_ctx* ctx, const float* rows_dev, int64_t ld, int32_t batch_rows,
                                            float inv_batch, void* stream, iqlhip_weights* table);
+/* ---- tracking tables: new rows enter at the largest priority seen (DESIGN.md §6j "Online prioritised replay") ----
+ * iqlhip_weights_build_tracking: iqlhip_weights_build_updatable plus one device word q_max (uint64, at the table's fixed
+ * scale), max(max_i q[i], q(new_row_weight)) after the build; new_row_weight finite and > 0 (IQLHIP_EINVAL otherwise), it
+ * saturates like any weight.  Every update that is APPLIED raises q_max to max(q_max, q_new): iqlhip_weights_update,
+ * iqlhip_weights_update_td and the update launches of iqlhip_train_steps_prioritized's chunk graphs (their second
+ * launch is then a tracking instantiation; "tracking or not" is part of what identifies such a chunk graph).  An entry
+ * that lost to a later duplicate or was skipped (non-finite, negative, out of bound) raises nothing; q_max never falls;
+ * an integer maximum, so the order of application does not matter.  _prepare's rehearsal leaves q_max as it leaves the
+ * tree.  Whether a table tracks is fixed at its build; tables built by iqlhip_weights_build_updatable launch the kernels
+ * they always did.  The group calls refuse a tracking table (IQLHIP_EUNSUPPORTED, naming the member).
+ * iqlhip_weights_max: waits for the device, then reads q_max and w_max = q_max * 2^(e - 38) (each pointer may be NULL).
+ * iqlhip_weights_insert_max: q[row] = q_max in one launch of one wave, queued on `stream` with no read-back; afterwards
+ * every entry of the tree equals a fresh build over the changed weights at the same scale; the version grows by 1.
+ * IQLHIP_EINVAL (both): a table that does not track; (insert) bound outside [0, n] or row outside [0, bound). */
+int iqlhip_weights_build_tracking(const float* w_dev, int64_t n, int64_t capacity, float max_weight, float new_row_weight,
+                                  void* stream, iqlhip_weights** out);
+int iqlhip_weights_max(const iqlhip_weights* table, uint64_t* q_max, float* w_max);
+int iqlhip_weights_insert_max(iqlhip_weights* table, int64_t row, int64_t bound, void* stream);
+/* iqlhip_online_step with prioritised replay, one call per iteration of the online loop, everything queued on `stream`
+ * and one synchronisation at the end:
+ *   1. row_host -> ring row `pointer`, and table[pointer] <- q_max (one launch: iqlhip_weights_insert_max's wave in it);
+ *   2. n indices of the stream (seed, stream_offset) by the table — behind the insert, so the new row can be drawn —, the
+ *      rows gathered, c = (q_min / q_row)^is_beta over the n rows (iqlhip_draw_indices_weighted_is's arithmetic);
+ *   3. iqlhip_step_rw on those rows with row weights c, TD errors kept;
+ *   4. iqlhip_weights_update_td on the drawn indices with those TD errors (m = n, bound = capacity);
+ *   5. act_state_host != NULL: the next action by the updated policy, as iqlhip_online_step.
+ * Bit for bit the sequence ring write + iqlhip_weights_insert_max(pointer), iqlhip_draw_indices_weighted_is(n indices,
+ * batch_rows = n), gather, iqlhip_step_rw, iqlhip_weights_update_td, act — parameters, Adam state, losses, statistics, TD
+ * errors, action, and the table's leaves, total, flags, q_max; its version grows by 2.  The stream consumes
+ * ceil(n / 2) counters from stream_offset.  Before anything is launched or any counter moves: IQLHIP_EINVAL for a static or
+ * non-tracking table, a table whose n is not `capacity` or on another device, alpha / eps / is_beta as
+ * iqlhip_train_steps_prioritized, and iqlhip_online_step's own; IQLHIP_EUNSUPPORTED at bf16 precision, with a data-parallel
+ * exchange, with injected keep-bits pending.
+ * iqlhip_online_prioritized_batch: the last such step's n drawn indices and TD errors ([n][2]) copied to device memory
+ * on `stream` (either pointer may be NULL). */
+int iqlhip_online_step_prioritized(iqlhip_ctx* ctx, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                   const float* row_host, int32_t n, const iqlhip_step_scalars* sc, float out[3],
+                                   const float* act_state_host, float max_action, uint64_t act_seed, float* act_out_host,
+                                   void* stream, iqlhip_weights* table, uint64_t seed, uint64_t stream_offset, float is_beta,
+                                   float alpha, float eps);
+int iqlhip_online_prioritized_batch(iqlhip_ctx* ctx, int32_t n, int64_t* idx_out_dev, float* td_out_dev, void* stream);
 
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is

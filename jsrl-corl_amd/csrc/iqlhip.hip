@@ -133,8 +133,10 @@ struct DevGuard {
 };
 
 // What the table update inside a prioritised chunk needs of its updatable table beyond WTab (the launches' WUpd).
+// q_max: the maximum word of a tracking table (iqlhip_weights_build_tracking), else null — the update launches of a chunk
+// graph are captured as the tracking instantiations or as the plain ones, so it is part of what identifies the graph.
 struct PrioSrc { unsigned* stamp = nullptr; unsigned* flags = nullptr; unsigned long long* delta = nullptr; int sh0 = 0;
-                 unsigned sat_bits = 0; };
+                 unsigned sat_bits = 0; unsigned long long* q_max = nullptr; };
 // The five kinds of chunk graph, one per pair of entry points (iqlhip_train_steps, _mixed, _weighted, _weighted_is,
 // _prioritized).  The values are the kernels' too: idle_block_work<MODE> of a kind's forward is numbered the same way.
 // What a kind implies for the driver stands in ONE place: kind_info(), in front of the multi-step driver.
@@ -149,7 +151,7 @@ struct ChunkSrc {
   bool operator==(const ChunkSrc& o) const {
     return kind == o.kind && rows_on == o.rows_on && n_off == o.n_off && wt.tab == o.wt.tab && wt.n == o.wt.n &&
            wt.levels == o.wt.levels && wt.local == o.wt.local && up.stamp == o.up.stamp && up.flags == o.up.flags &&
-           up.delta == o.up.delta && up.sh0 == o.up.sh0 && up.sat_bits == o.up.sat_bits;
+           up.delta == o.up.delta && up.sh0 == o.up.sh0 && up.sat_bits == o.up.sat_bits && up.q_max == o.up.q_max;
   }
 };
 // ... and the values of ONE call, which the set-up kernel writes to device words and no graph freezes: the table's
@@ -1707,12 +1709,20 @@ static int actor_forward_impl(iqlhip_ctx* c, const float* states_dev, int64_t ld
 // The part every form of the online iteration shares (iqlhip_online_step, iqlhip_online_step_mixed,
 // iqlhip_jsrl_online_step): the checks, the ring write + gather and the step, queued on `stream`.  act_follows: the
 // call's completion word is left to the launch that follows the step (an act's finish); else the update stores it.
+// pr != nullptr — iqlhip_online_step_prioritized (its own checks made, its buffers there): no host indices; the ring write
+// carries the insert at the table's maximum, the rows are drawn by the table on the device, the step is the row-weighted
+// one and the table update by its TD errors follows it (online_prio_gather / online_prio_update, defined with the
+// tracking tables at the end of the file).
+struct OnlinePrio { iqlhip_weights* table; uint64_t seed, offset; float is_beta, alpha, eps; };
+static void online_prio_gather(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t pointer, int32_t n, const OnlinePrio& pr,
+                               hipStream_t st, RowWeights* rw);
+static void online_prio_update(iqlhip_ctx* c, int32_t n, const OnlinePrio& pr, hipStream_t st);
 static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
                              const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
                              const float* out, bool act_follows, void* stream, const float* rows_off_dev,
                              int64_t size_off, const int64_t* idx_off_host, int32_t n_off,
-                             unsigned long long* done_val_out) {
-  if (!c || !rows_dev || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+                             unsigned long long* done_val_out, const OnlinePrio* pr = nullptr) {
+  if (!c || !rows_dev || !row_host || (!idx_host && !pr) || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (!c->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_bind has not been called");
   if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
   if (((uintptr_t)rows_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
@@ -1721,7 +1731,7 @@ static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t
     return fail(IQLHIP_EINVAL, "batch rows %d (+ %d offline) outside [1, max_batch=%d]", n, n_off, c->dims.max_batch);
   if (capacity < 1 || pointer < 0 || pointer >= capacity) return fail(IQLHIP_EINVAL, "ring pointer outside the buffer");
   {                                       // (the reference's torch indexing raises on such an index; a gather would fault)
-    int rc_i = check_host_indices(idx_host, n, capacity);
+    int rc_i = pr ? IQLHIP_OK : check_host_indices(idx_host, n, capacity);      // (pr: the device draws; the descent is clamped)
     if (!rc_i && n_off) rc_i = check_host_indices(idx_off_host, n_off, size_off);
     if (rc_i) return rc_i;
     if ((rc_i = step_entry(c, B, stream, /*multi_step=*/false))) return rc_i;
@@ -1730,9 +1740,12 @@ static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t
   hipStream_t st = (hipStream_t)stream;
   memcpy(c->on_row_pin, row_host, (size_t)ld * sizeof(float));
   if (n_off) memcpy(c->on_idx_pin, idx_off_host, (size_t)n_off * sizeof(long long));      // [offline | online], batch order
-  memcpy(c->on_idx_pin + n_off, idx_host, (size_t)n * sizeof(long long));
+  if (!pr) memcpy(c->on_idx_pin + n_off, idx_host, (size_t)n * sizeof(long long));
   const int total = B * (int)(ld / 4);
-  if (n_off)
+  RowWeights rw = {nullptr, nullptr};
+  if (pr)
+    online_prio_gather(c, rows_dev, ld, pointer, n, *pr, st, &rw);
+  else if (n_off)
     hipLaunchKernelGGL(iql_online_gather2_kernel, dim3((total + 255) / 256), dim3(256), 0, st, rows_dev, rows_off_dev,
                        (long long)ld, (long long)pointer, (const float*)c->on_row_pin, (const long long*)c->on_idx_pin,
                        c->xb, n_off, B);
@@ -1744,9 +1757,11 @@ static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t
   e.u.losses_mirror = c->on_loss_pin;
   const unsigned long long done_val = ++c->done_seq;
   if (!act_follows) { e.u.done_flag = c->done_pin; e.u.done_val = done_val; }      // (else the follow-up act() signals)
-  int rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr, e.stats());
+  int rc = enqueue_step(c, e.p, e.u, c->xch_mode, (int)(c->xstep & 1ull), 0, /*from_hdr=*/false, st, nullptr, e.stats(),
+                        ChunkKind::Plain, pr ? &rw : nullptr);
   if (rc) return rc;
   if (c->xch_mode != IQLHIP_XCH_NONE) c->xstep += 1;
+  if (pr) online_prio_update(c, n, *pr, st);      // table[drawn rows] <- the priorities of the step's TD errors
   *done_val_out = done_val;
   return IQLHIP_OK;
 }
@@ -1754,12 +1769,12 @@ static int online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capac
                        const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
                        float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
                        float* act_out_host, void* stream, const float* rows_off_dev, int64_t size_off,
-                       const int64_t* idx_off_host, int32_t n_off) {
-  if (!c || !rows_dev || !row_host || !idx_host || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
+                       const int64_t* idx_off_host, int32_t n_off, const OnlinePrio* pr = nullptr) {
+  if (!c || !rows_dev || !row_host || (!idx_host && !pr) || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (act_state_host && !act_out_host) return fail(IQLHIP_EINVAL, "act_state_host without act_out_host");
   unsigned long long done_val = 0;
   int rc = online_step_front(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host != nullptr,
-                             stream, rows_off_dev, size_off, idx_off_host, n_off, &done_val);
+                             stream, rows_off_dev, size_off, idx_off_host, n_off, &done_val, pr);
   if (rc) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -4337,6 +4352,8 @@ struct iqlhip_weights {
   unsigned* flags = nullptr;              // the sticky flag word
   unsigned long long* delta = nullptr;    // [WT_UPDATE_SLICE]: q_new - q_old of a slice's entries
   uint64_t version = 0;                   // content version: every iqlhip_weights_update adds 1
+  // tracking tables (iqlhip_weights_build_tracking): the largest q an applied update or the build has seen; never falls
+  unsigned long long* q_max = nullptr;    // one device word at the table's scale; null: the table does not track
 };
 #define WT_UPDATE_SLICE 65536             // entries of an update handled per set of launches (the delta scratch: 512 KB)
 static std::atomic<uint64_t> g_weights_gen{0};
@@ -4448,8 +4465,15 @@ extern "C" int iqlhip_weights_info(const iqlhip_weights* t, int64_t* n, uint64_t
 }
 
 // ---- updatable tables: node-local prefix sums, changed in place (DESIGN.md 6i "updatable tables")
-extern "C" int iqlhip_weights_build_updatable(const float* w_dev, int64_t n, int64_t capacity, float max_weight, void* stream,
-                                              iqlhip_weights** out) {
+// What a tracking table adds (iqlhip_weights_build_tracking; their kernels are the code object's last, so these are
+// defined behind them, at the end of the file): the maximum word and its first value; the tracking instantiation of an
+// update's second launch.
+static int weights_track_init(iqlhip_weights* t, unsigned max_bits, float new_row_weight, hipStream_t st);
+static void launch_update_delta_track(const long long* idx, const float* w, unsigned m, long long bound, const WUpd& u,
+                                      unsigned long long* delta, unsigned long long* q_max, hipStream_t st);
+// track: iqlhip_weights_build_tracking (new_row_weight checked there); else the table iqlhip_weights_build_updatable always built.
+static int weights_build_local(const float* w_dev, int64_t n, int64_t capacity, float max_weight, bool track, float new_row_weight,
+                               void* stream, iqlhip_weights** out) {
   if (!w_dev || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (n < 1 || capacity < n || capacity > IQLHIP_WEIGHTS_MAX_ROWS)
     return fail(IQLHIP_EINVAL, "n = %lld weights, capacity = %lld: need 1 <= n <= capacity <= 2^24", (long long)n, (long long)capacity);
@@ -4481,6 +4505,7 @@ extern "C" int iqlhip_weights_build_updatable(const float* w_dev, int64_t n, int
   for (int l = 1; l < t->levels; ++l)
     hipLaunchKernelGGL(iql_wt_local_level_kernel, dim3(((size[l] + 63u) / 64u + 3u) / 4u), dim3(256), 0, st,
                        (const unsigned long long*)(t->tab + off[l - 1]), size[l - 1], t->tab + off[l], size[l]);
+  if (track && (rc = weights_track_init(t.get(), max_bits, new_row_weight, st))) return rc;
   HIPCHK(hipGetLastError());
   unsigned long long total = 0;
   HIPCHK(hipMemcpyAsync(&total, t->tab + off[t->levels - 1] + size[t->levels - 1] - 1, sizeof total, hipMemcpyDeviceToHost, st));
@@ -4489,6 +4514,15 @@ extern "C" int iqlhip_weights_build_updatable(const float* w_dev, int64_t n, int
   t->gen = ++g_weights_gen;
   *out = t.release();
   return IQLHIP_OK;
+}
+extern "C" int iqlhip_weights_build_updatable(const float* w_dev, int64_t n, int64_t capacity, float max_weight, void* stream,
+                                              iqlhip_weights** out) {
+  return weights_build_local(w_dev, n, capacity, max_weight, /*track=*/false, 0.f, stream, out);
+}
+extern "C" int iqlhip_weights_build_tracking(const float* w_dev, int64_t n, int64_t capacity, float max_weight,
+                                             float new_row_weight, void* stream, iqlhip_weights** out) {
+  if (!(new_row_weight > 0.f) || std::isinf(new_row_weight)) return fail(IQLHIP_EINVAL, "new_row_weight must be finite and > 0");
+  return weights_build_local(w_dev, n, capacity, max_weight, /*track=*/true, new_row_weight, stream, out);
 }
 
 extern "C" int iqlhip_weights_update(iqlhip_weights* t, const int64_t* idx_dev, const float* w_dev, int64_t m, int64_t bound,
@@ -4507,7 +4541,10 @@ extern "C" int iqlhip_weights_update(iqlhip_weights* t, const int64_t* idx_dev, 
     const long long* idx = (const long long*)idx_dev + j0;
     const float* w = w_dev + j0;
     hipLaunchKernelGGL(iql_wt_update_stamp_kernel, dim3((k + 255u) / 256u), dim3(256), 0, st, idx, w, k, (long long)bound, u);
-    hipLaunchKernelGGL(iql_wt_update_delta_kernel, dim3((k + 255u) / 256u), dim3(256), 0, st, idx, w, k, (long long)bound, u, t->delta);
+    if (t->q_max)
+      launch_update_delta_track(idx, w, k, (long long)bound, u, t->delta, t->q_max, st);
+    else
+      hipLaunchKernelGGL(iql_wt_update_delta_kernel, dim3((k + 255u) / 256u), dim3(256), 0, st, idx, w, k, (long long)bound, u, t->delta);
     hipLaunchKernelGGL(iql_wt_update_apply_kernel, dim3((k + 3u) / 4u), dim3(256), 0, st, idx, w, k, (long long)bound, u,
                        (const unsigned long long*)t->delta);
   }
@@ -5068,10 +5105,17 @@ static int prio_exponents_check(float alpha, float eps) {
   return IQLHIP_OK;
 }
 // The three launches of an update of m entries with TD errors as the weight source.
+// q_max != nullptr (a tracking table): the second launch is its tracking instantiation (defined behind its kernel, at the
+// end of the file).
+static void launch_update_delta_td_track(const long long* idx, const float* td, unsigned m, long long bound, const WUpd& u,
+                                         unsigned long long* delta, const PrioArgs& a, unsigned long long* q_max, hipStream_t st);
 static void launch_update_td(const WUpd& u, const long long* idx, const float* td, unsigned m, long long bound,
-                             unsigned long long* delta, const PrioArgs& a, hipStream_t st) {
+                             unsigned long long* delta, const PrioArgs& a, hipStream_t st, unsigned long long* q_max = nullptr) {
   hipLaunchKernelGGL(iql_wt_update_stamp_td_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, td, m, bound, u, a);
-  hipLaunchKernelGGL(iql_wt_update_delta_td_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, td, m, bound, u, delta, a);
+  if (q_max)
+    launch_update_delta_td_track(idx, td, m, bound, u, delta, a, q_max, st);
+  else
+    hipLaunchKernelGGL(iql_wt_update_delta_td_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, td, m, bound, u, delta, a);
   hipLaunchKernelGGL(iql_wt_update_apply_td_kernel, dim3((m + 3u) / 4u), dim3(256), 0, st, idx, td, m, bound, u,
                      (const unsigned long long*)delta, a);
 }
@@ -5091,7 +5135,7 @@ extern "C" int iqlhip_weights_update_td(iqlhip_weights* t, const int64_t* idx_de
   // slice by slice, in order, as iqlhip_weights_update
   for (int64_t j0 = 0; j0 < m; j0 += WT_UPDATE_SLICE) {
     const unsigned k = (unsigned)std::min<int64_t>(WT_UPDATE_SLICE, m - j0);
-    launch_update_td(u, (const long long*)idx_dev + j0, td_dev + 2 * j0, k, (long long)bound, t->delta, a, st);
+    launch_update_td(u, (const long long*)idx_dev + j0, td_dev + 2 * j0, k, (long long)bound, t->delta, a, st, t->q_max);
   }
   HIPCHK(hipGetLastError());
   ++t->version;
@@ -5118,7 +5162,7 @@ static void launch_prio_update(const iqlhip_ctx* c, const ChunkSrc& src, int B, 
   const WUpd u{const_cast<unsigned long long*>(src.wt.tab), src.up.stamp, src.up.flags, src.wt.n, (int)src.wt.levels, src.up.sh0,
                src.up.sat_bits};
   const PrioArgs a{prio_words(c), 0.f, 0.f};
-  launch_update_td(u, prio_idx(c, k & 1), prio_td(c), (unsigned)B, (long long)src.wt.n, src.up.delta, a, st);
+  launch_update_td(u, prio_idx(c, k & 1), prio_td(c), (unsigned)B, (long long)src.wt.n, src.up.delta, a, st, src.up.q_max);
 }
 // What a prioritised call needs beyond check_weighted_args and weighted_is_setup, before anything is launched or any
 // counter moves: an updatable table, valid exponents, the staging buffer and the forward's LDS allowance.
@@ -5132,7 +5176,7 @@ static int prio_setup(iqlhip_ctx* c, const iqlhip_weights* table, int32_t B, flo
 }
 static ChunkCall prio_call(const iqlhip_weights* t, float is_beta, float alpha, float eps, unsigned live) {
   ChunkCall call = weighted_call(t, ChunkKind::Prio, is_beta);
-  call.src.up = PrioSrc{t->stamp, t->flags, t->delta, t->sh0, t->sat_bits};
+  call.src.up = PrioSrc{t->stamp, t->flags, t->delta, t->sh0, t->sat_bits, t->q_max};
   call.alpha = alpha; call.eps = eps; call.live = live;
   return call;
 }
@@ -5280,6 +5324,9 @@ static int group_train_steps_rw(iqlhip_group* g, const float* const* rows, int64
     if ((rc = weights_check_member(t, i, size[i], g->device))) return rc;
     if (!prio) continue;
     if (!t->local) return fail(IQLHIP_EINVAL, "member %d: the table is not updatable (iqlhip_weights_build_updatable)", i);
+    if (t->q_max)
+      return fail(IQLHIP_EUNSUPPORTED, "member %d: a table that tracks its maximum (iqlhip_weights_build_tracking) is not "
+                  "supported in trainer groups", i);
     if ((rc = member_fail(i, prio_exponents_check(alpha[i], eps[i])))) return rc;
     if (B[i] > WT_UPDATE_SLICE) return fail(IQLHIP_EUNSUPPORTED, "member %d: prioritised calls take batches of at most %d rows", i, WT_UPDATE_SLICE);
     for (int j = 0; j < i; ++j)
@@ -5415,4 +5462,118 @@ extern "C" int iqlhip_group_train_steps_prioritized(iqlhip_group* g, const float
                                                     const float* alpha, const float* eps) {
   if (!alpha || !eps) return fail(IQLHIP_EINVAL, "NULL argument");
   return group_train_steps_rw(g, rows, ld, size, B, tables, n, seeds, offsets, flags, stream, wtabs, is_beta, alpha, eps);
+}
+
+// ---------------------------------------------------------------------------
+// Online prioritised replay: tables that track their maximum, new rows entering at it, and the prioritised online
+// iteration in one call (include/iqlhip.h "tracking tables", "iqlhip_online_step_prioritized"; DESIGN.md 6j "Online
+// prioritised replay"; kernels: iqlhip_online_prio_kernels.h, the code object's last).
+#include "iqlhip_online_prio_kernels.h"
+
+static WUpd weights_upd(const iqlhip_weights* t) {
+  return WUpd{t->tab, t->stamp, t->flags, (unsigned)t->n, t->levels, t->sh0, t->sat_bits};
+}
+static int weights_track_init(iqlhip_weights* t, unsigned max_bits, float new_row_weight, hipStream_t st) {
+  HIPCHK(t->own.dev(&t->q_max, sizeof(unsigned long long), 0));
+  hipLaunchKernelGGL(iql_wt_qmax_init_kernel, dim3(1), dim3(64), 0, st, max_bits, new_row_weight, t->sh0, t->sat_bits, t->q_max);
+  return IQLHIP_OK;
+}
+static void launch_update_delta_track(const long long* idx, const float* w, unsigned m, long long bound, const WUpd& u,
+                                      unsigned long long* delta, unsigned long long* q_max, hipStream_t st) {
+  hipLaunchKernelGGL(iql_wt_update_delta_track_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, w, m, bound, u, delta, q_max);
+}
+static void launch_update_delta_td_track(const long long* idx, const float* td, unsigned m, long long bound, const WUpd& u,
+                                         unsigned long long* delta, const PrioArgs& a, unsigned long long* q_max, hipStream_t st) {
+  hipLaunchKernelGGL(iql_wt_update_delta_td_track_kernel, dim3((m + 255u) / 256u), dim3(256), 0, st, idx, td, m, bound, u, delta, a,
+                     q_max);
+}
+
+extern "C" int iqlhip_weights_max(const iqlhip_weights* t, uint64_t* q_max, float* w_max) {
+  if (!t) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!t->q_max) return fail(IQLHIP_EINVAL, "the table does not track its maximum (iqlhip_weights_build_tracking)");
+  DevGuard guard(t->device);
+  HIPCHK(hipDeviceSynchronize());         // an update may be queued on any stream
+  unsigned long long q = 0;
+  HIPCHK(hipMemcpy(&q, t->q_max, sizeof q, hipMemcpyDeviceToHost));
+  if (q_max) *q_max = q;
+  if (w_max) *w_max = (float)std::ldexp((double)q, -t->sh0);      // q = floor(w * 2^sh0): exact in a double (q < 2^39)
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_weights_insert_max(iqlhip_weights* t, int64_t row, int64_t bound, void* stream) {
+  if (!t) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!t->q_max) return fail(IQLHIP_EINVAL, "the table does not track its maximum (iqlhip_weights_build_tracking)");
+  if (bound < 0 || bound > t->n) return fail(IQLHIP_EINVAL, "bound = %lld outside [0, %lld]", (long long)bound, (long long)t->n);
+  if (row < 0 || row >= bound) return fail(IQLHIP_EINVAL, "row = %lld outside [0, %lld)", (long long)row, (long long)bound);
+  DevGuard guard(t->device);
+  hipLaunchKernelGGL(iql_wt_insert_max_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, weights_upd(t),
+                     (const unsigned long long*)t->q_max, (unsigned)row);
+  HIPCHK(hipGetLastError());
+  ++t->version;
+  return IQLHIP_OK;
+}
+
+// The launches of iqlhip_online_step_prioritized in front of the step (online_step_front): the ring write with the insert,
+// the draw with the gather, and the batch's loss weights — iqlhip_draw_indices_weighted_is's second kernel on the staged
+// q, in place.  Indices: prio_buf's first staging half; c: is_buf's c region; TD errors: prio_buf's.
+static void online_prio_gather(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t pointer, int32_t n, const OnlinePrio& pr,
+                               hipStream_t st, RowWeights* rw) {
+  const iqlhip_weights* t = pr.table;
+  float* cw = c->is_buf + 2 * (size_t)c->dims.max_batch;
+  hipLaunchKernelGGL(iql_online_ring_insert_kernel, dim3(1), dim3(256), 0, st, rows_dev, (long long)ld, (long long)pointer,
+                     (const float*)c->on_row_pin, weights_upd(t), (const unsigned long long*)t->q_max);
+  hipLaunchKernelGGL(iql_online_draw_gather_kernel, dim3((unsigned)(n + 7) / 8u), dim3(256), 0, st, (const float*)rows_dev,
+                     (long long)ld, c->xb, cw, prio_idx(c, 0), (int)n, weights_tab(t), (unsigned long long)pr.seed,
+                     (unsigned long long)pr.offset);
+  hipLaunchKernelGGL(iql_is_weights_kernel, dim3(1), dim3(256), 0, st, cw, (long long)n, (long long)n, pr.is_beta);
+  *rw = RowWeights{cw, prio_td(c)};
+}
+// ... and behind it: iqlhip_weights_update_td's launches on the staged indices and the step's TD errors.
+static void online_prio_update(iqlhip_ctx* c, int32_t n, const OnlinePrio& pr, hipStream_t st) {
+  const iqlhip_weights* t = pr.table;
+  const PrioArgs a{nullptr, pr.alpha, pr.eps};
+  launch_update_td(weights_upd(t), prio_idx(c, 0), prio_td(c), (unsigned)n, (long long)t->n, t->delta, a, st, t->q_max);
+}
+
+extern "C" int iqlhip_online_step_prioritized(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                              const float* row_host, int32_t n, const iqlhip_step_scalars* sc, float out[3],
+                                              const float* act_state_host, float max_action, uint64_t act_seed,
+                                              float* act_out_host, void* stream, iqlhip_weights* table, uint64_t seed,
+                                              uint64_t stream_offset, float is_beta, float alpha, float eps) {
+  if (!c || !table) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!table->local) return fail(IQLHIP_EINVAL, "the table is not updatable (iqlhip_weights_build_tracking)");
+  if (!table->q_max) return fail(IQLHIP_EINVAL, "the table does not track its maximum (iqlhip_weights_build_tracking)");
+  if (table->device != c->device) return fail(IQLHIP_EINVAL, "the table lives on device %d, the context on %d", table->device, c->device);
+  if (capacity != table->n) return fail(IQLHIP_EINVAL, "capacity %lld, but the table weighs %lld rows", (long long)capacity, (long long)table->n);
+  if (int rc = prio_exponents_check(alpha, eps)) return rc;
+  if (!(is_beta >= 0.f) || !std::isfinite(is_beta)) return fail(IQLHIP_EINVAL, "is_beta must be finite and >= 0");
+  if (c->precision == 1) return fail(IQLHIP_EUNSUPPORTED, "per-row loss weights are not supported at bf16 precision");
+  if (c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "the prioritised online step is not supported with a data-parallel exchange");
+  if (n > WT_UPDATE_SLICE) return fail(IQLHIP_EUNSUPPORTED, "prioritised calls take batches of at most %d rows", WT_UPDATE_SLICE);
+  if (int rc = inject_check(c)) return rc;
+  {                                       // the staging buffers of the prioritised calls (prio_setup's)
+    DevGuard guard(c->device);
+    if (!c->is_buf) HIPCHK(c->own.dev(&c->is_buf, (3 * (size_t)c->dims.max_batch + 4) * sizeof(float), 0));
+    if (!c->prio_buf) HIPCHK(c->own.dev(&c->prio_buf, 24 * (size_t)c->dims.max_batch + 4 * sizeof(float), 0));
+  }
+  const OnlinePrio pr{table, seed, stream_offset, is_beta, alpha, eps};
+  const int rc = online_step(c, rows_dev, ld, capacity, pointer, row_host, nullptr, n, sc, out, act_state_host, max_action, act_seed,
+                             act_out_host, stream, nullptr, 0, nullptr, 0, &pr);
+  if (!rc) table->version += 2;           // the insert and the update: what the two eager calls add
+  return rc;
+}
+
+// The batch of the context's last prioritised online step, copied on `stream`: its n drawn indices and its rows' TD errors
+// ([n][2]); either pointer may be null.
+extern "C" int iqlhip_online_prioritized_batch(iqlhip_ctx* c, int32_t n, int64_t* idx_out_dev, float* td_out_dev, void* stream) {
+  if (!c) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!c->prio_buf) return fail(IQLHIP_EINVAL, "no prioritised step has run on this context");
+  if (n < 1 || n > c->dims.max_batch) return fail(IQLHIP_EINVAL, "n outside [1, max_batch]");
+  DevGuard guard(c->device);
+  if (idx_out_dev)
+    HIPCHK(hipMemcpyAsync(idx_out_dev, prio_idx(c, 0), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (td_out_dev)
+    HIPCHK(hipMemcpyAsync(td_out_dev, prio_td(c), (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return IQLHIP_OK;
 }

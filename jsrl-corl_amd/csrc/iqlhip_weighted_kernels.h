@@ -231,21 +231,36 @@ __global__ __launch_bounds__(256) void iql_wt_update_stamp_kernel(const long lon
 
 // Launch 2: delta[j] = q_new - q_old (two's complement) of every winner, q_old read back from its level-0 node —
 // nothing writes the tree in this launch.  Entries that lost or are skipped get 0.
-template <class WS>
+// TRACK (a tracking table, iqlhip_weights_build_tracking): the largest q_new among the launch's winners is also raised
+// into the table's maximum word — a maximum over the wave first, then one 64-bit atomic maximum per wave that has a
+// winner.  Entries that lost or are skipped raise nothing.  TRACK = false is the code the kernels always had.
+template <class WS, bool TRACK = false>
 __device__ __forceinline__ void wt_update_delta(const long long* idx, const WS& w, unsigned m, long long bound,
-                                                const WUpd& t, unsigned long long* delta) {
+                                                const WUpd& t, unsigned long long* delta, unsigned long long* q_max = nullptr) {
   const unsigned j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= m) return;
-  const long long i = idx[j];
-  const float wj = w(j);
-  unsigned long long d = 0ull;
-  if (!wt_update_bad(i, wj, bound) && t.stamp[i] == j + 1u) {
-    const unsigned long long upto = t.tab[i], before = (i & 63) ? t.tab[i - 1] : 0ull;
-    const unsigned long long q_new =
-        ((__float_as_uint(wj) & 0x7FFFFFFFu) >= t.sat_bits) ? WT_Q_SATURATED : wt_quantise(wj, t.sh0);
-    d = q_new - (upto - before);
+  if (!TRACK && j >= m) return;
+  unsigned long long won = 0ull;
+  if (j < m) {
+    const long long i = idx[j];
+    const float wj = w(j);
+    unsigned long long d = 0ull;
+    if (!wt_update_bad(i, wj, bound) && t.stamp[i] == j + 1u) {
+      const unsigned long long upto = t.tab[i], before = (i & 63) ? t.tab[i - 1] : 0ull;
+      const unsigned long long q_new =
+          ((__float_as_uint(wj) & 0x7FFFFFFFu) >= t.sat_bits) ? WT_Q_SATURATED : wt_quantise(wj, t.sh0);
+      d = q_new - (upto - before);
+      won = q_new;
+    }
+    delta[j] = d;
   }
-  delta[j] = d;
+  if (TRACK) {      // (every lane of the wave is here: no lane has returned)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long u = __shfl_xor(won, o);
+      won = u > won ? u : won;
+    }
+    if ((threadIdx.x & 63) == 0 && won) atomicMax(q_max, won);
+  }
 }
 __global__ __launch_bounds__(256) void iql_wt_update_delta_kernel(const long long* __restrict__ idx, const float* __restrict__ w,
                                                                   unsigned m, long long bound, WUpd t,

@@ -190,6 +190,15 @@ SYMBOLS = [
                                                  C.c_float, C.c_float, C.c_float]),
     ("iqlhip_train_steps_prioritized_prepare", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
                                                          C.c_void_p, C.c_void_p]),
+    ("iqlhip_weights_build_tracking", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_void_p,
+                                                C.POINTER(C.c_void_p)]),
+    ("iqlhip_weights_max", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("iqlhip_weights_insert_max", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    ("iqlhip_online_step_prioritized", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                 C.c_int32, C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p, C.c_float,
+                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                 C.c_float, C.c_float, C.c_float]),
+    ("iqlhip_online_prioritized_batch", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("iqlhip_debug_read", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64,
                                     C.POINTER(C.c_int64), C.c_void_p]),
     ("iqlhip_debug_time_kernel", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_int, C.POINTER(C.c_float),

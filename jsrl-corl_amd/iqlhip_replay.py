@@ -355,6 +355,7 @@ class ReplayBuffer:
     _weights_gen = 0
     _weights_updatable = False   # an updatable table spans _buffer_size rows and is changed in place
     _weights_version = 0         # its content version: update_sample_weights adds 1
+    _weights_tracks = False      # the table tracks its largest priority: add_transition enters the new row at it
 
     @property
     def sample_weights_n(self):
@@ -363,7 +364,7 @@ class ReplayBuffer:
 
     def _free_weights(self) -> None:
         table, self._weights, self._weights_n, self._weights_gen = self._weights, None, None, 0
-        self._weights_updatable, self._weights_version = False, 0
+        self._weights_updatable, self._weights_version, self._weights_tracks = False, 0, False
         if table is not None:
             hb.lib().iqlhip_weights_free(table)
 
@@ -373,7 +374,8 @@ class ReplayBuffer:
         except Exception:
             pass
 
-    def set_sample_weights(self, weights, updatable: bool = False, max_weight=None) -> None:
+    def set_sample_weights(self, weights, updatable: bool = False, max_weight=None, track_max: bool = False,
+                           new_row_weight=None) -> None:
         """One float32 weight per row position [0, _index_bound()): a torch tensor on the buffer's device or on the host,
         or an ndarray; None clears them.  The library validates the values and builds its cumulative table on the device
         (8 bytes per row plus 1/63).  ValueError for a CPU buffer, a wrong length, dtype or shape, a NaN, an infinity, a
@@ -382,11 +384,15 @@ class ReplayBuffer:
         updatable=True builds a table that update_sample_weights changes in place: it spans the buffer's whole capacity
         (rows beyond the index bound weigh 0), so the weighted calls keep working while add_transition moves the index
         bound; its scale is fixed by max_weight (None: the largest weight given) — a later weight of
-        2^(floor(log2(max_weight)) + 1) or more saturates.  12 bytes per row instead of 8."""
+        2^(floor(log2(max_weight)) + 1) or more saturates.  12 bytes per row instead of 8.
+        track_max=True (with updatable=True: ValueError otherwise): the table keeps the largest priority an applied
+        update or the build has seen, at least new_row_weight (default 1.0, finite and > 0), and add_transition enters
+        every new row at it — prioritised replay's rule that a new transition is trained on at least once."""
         import iqlhip_weighted as wtd
         if weights is None:
             self._free_weights()
             return
+        new_row_weight = wtd.check_tracking_args(updatable, track_max, new_row_weight)
         if not self._gpu:
             raise ValueError("iqlhip: sample weights need a ReplayBuffer that lives on the GPU")
         n = self._index_bound()
@@ -404,18 +410,45 @@ class ReplayBuffer:
             raise ValueError("iqlhip: max_weight belongs to an updatable table (updatable=True)")
         with torch.cuda.device(dev):
             table, gen = wtd.build_table(w_dev, n, self._stream(), updatable, self._buffer_size if updatable else None,
-                                         max_weight)
+                                         max_weight, new_row_weight)
         self._free_weights()
         self._weights, self._weights_n, self._weights_gen = table, (self._buffer_size if updatable else n), gen
-        self._weights_updatable = bool(updatable)
+        self._weights_updatable, self._weights_tracks = bool(updatable), bool(track_max)
+
+    @property
+    def sample_weights_track_max(self) -> bool:
+        """Whether the buffer's table tracks its largest priority (set_sample_weights(..., track_max=True))."""
+        return self._weights_tracks
+
+    def sample_weights_max(self) -> tuple:
+        """(q_max, w_max) of the buffer's tracking table (waits for the device): the priority a new row enters at."""
+        import iqlhip_weighted as wtd
+        if self._weights is None or not self._weights_tracks:
+            raise ValueError("iqlhip: the replay buffer's sample weights do not track their maximum "
+                             "(set_sample_weights(..., updatable=True, track_max=True))")
+        return wtd.table_max(self._weights)
+
+    def insert_max_sample_weight(self, row: int) -> None:
+        """w[row] = the table's largest priority, queued on the buffer's stream with no synchronisation (what
+        add_transition does for the row it writes).  row in [0, capacity): ValueError otherwise, and without a tracking
+        table."""
+        import iqlhip_weighted as wtd
+        if self._weights is None or not self._weights_tracks:
+            raise ValueError("iqlhip: the replay buffer's sample weights do not track their maximum "
+                             "(set_sample_weights(..., updatable=True, track_max=True))")
+        row, bound = wtd.check_insert_args(row, None, self._buffer_size)
+        with torch.cuda.device(self._rows.device):
+            hb.check(hb.lib().iqlhip_weights_insert_max(self._weights, row, bound, self._stream()))
+        self._weights_version += 1
 
     def update_sample_weights(self, indices, weights) -> None:
         """w[indices[j]] = weights[j] in the buffer's updatable table (set_sample_weights(..., updatable=True)): device
         tensors (int64, float32) of one length, queued on the buffer's stream with no synchronisation.  Duplicate indices:
         the last position wins.  A NaN, an infinity, a negative weight or an index outside [0, _index_bound()) is
-        skipped and leaves a bit in sample_weights_flags().  A ring write (add_transition) does NOT touch the table:
-        the overwritten — or newly filled — row keeps its old weight (0 for a row never weighed) until the caller
-        follows the write with update_sample_weights([row], [w])."""
+        skipped and leaves a bit in sample_weights_flags().  A ring write (add_transition) touches the table only if
+        it tracks its maximum (set_sample_weights(..., track_max=True)): the written row then enters at the largest
+        priority seen so far.  Otherwise the overwritten — or newly filled — row keeps its old weight (0 for a row never
+        weighed) until the caller follows the write with update_sample_weights([row], [w])."""
         import iqlhip_weighted as wtd
         if self._weights is None or not self._weights_updatable:
             raise ValueError("iqlhip: the replay buffer has no updatable sample weights "
@@ -518,6 +551,8 @@ class ReplayBuffer:
                     done_ev.record()
         else:
             self._rows[self._pointer].copy_(torch.from_numpy(row))
+        if self._weights_tracks:             # behind the ring write, on the same stream: the new row at the running maximum
+            self.insert_max_sample_weight(self._pointer)
         self._pointer = (self._pointer + 1) % self._buffer_size
         self._size = min(self._size + 1, self._buffer_size)
 

@@ -624,7 +624,22 @@ class ImplicitQLearning:
             td = self._last_td = None          # (a later step of any kind — train, train_steps*, online_step* — has run)
         if td is None:
             raise RuntimeError("iqlhip: no TD errors: the trainer's last step was not a train(..., return_td=True)")
+        if isinstance(td, tuple):              # (online_step_prioritized: the library holds them; copied when asked for)
+            rows = td[1]
+            td = torch.empty((rows, 2), dtype=torch.float32, device=self._dev)
+            hb.check(hb.lib().iqlhip_online_prioritized_batch(self._ctx, rows, None, td.data_ptr(), self._stream()))
+            self._last_td = td
         return td
+
+    def last_prioritized_indices(self) -> torch.Tensor:
+        """[B] int64 on the device: the rows the last online_step_prioritized drew, in batch order (the rows of
+        last_td_errors()).  Valid until the trainer's next step."""
+        mark = getattr(self, "_last_prio_idx", None)
+        if mark is None or mark[0] != self.total_it:
+            raise RuntimeError("iqlhip: no drawn indices: the trainer's last step was not an online_step_prioritized")
+        idx = torch.empty(mark[1], dtype=torch.int64, device=self._dev)
+        hb.check(hb.lib().iqlhip_online_prioritized_batch(self._ctx, mark[1], idx.data_ptr(), None, self._stream()))
+        return idx
 
     def train(self, batch: TensorBatch, loss_weights=None, return_td: bool = False) -> Dict[str, float]:
         """One IQL gradient step (iql.py:542-563).  Returns the three losses as floats
@@ -792,6 +807,64 @@ class ImplicitQLearning:
                                              None if a_in is None else a_in.ctypes.data, float(self.actor.max_action),
                                              seed, None if a_out is None else a_out.ctypes.data, self._stream()))
         return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+
+    def online_step_prioritized(self, replay_buffer, state, action, reward: float, next_state, done: bool,
+                                batch_size: int, seed: int, offset: Optional[int] = None, alpha: float = 0.6,
+                                eps: float = 1e-6, is_beta: float = 0.4, act_next: Optional[np.ndarray] = None):
+        """online_step with prioritised replay, in ONE library call and under one synchronisation.  The buffer's table
+        must track its maximum (set_sample_weights(..., updatable=True, track_max=True)).  Bit for bit the sequence
+            buf.add_transition(...)                  # the new row enters at the table's largest priority
+            idx, c = buf.draw_weighted_indices(B, seed, offset, is_beta=is_beta, batch_size=B)
+            log = trainer.train(buf.gather(idx), loss_weights=c, return_td=True)
+            buf.update_sample_weights_td(idx, trainer.last_td_errors(), alpha, eps)
+            a = trainer.actor.act(act_next, device)  # with act_next
+        The draw runs behind the insert, so the new row can be drawn.  offset: the Philox counter the draw starts at;
+        None continues a per-buffer counter that advances by ceil(batch_size / 2) per call (the counters one draw
+        consumes); an explicit offset is used and sets the counter.  Returns online_step's result; last_td_errors()
+        and last_prioritized_indices() work after the call.  ValueError for a buffer without a tracking table and for
+        alpha, eps or is_beta negative, not finite (or alpha = eps = 0); NotImplementedError at bf16 precision, under
+        data parallelism and with injected dropout masks pending — all before anything moves."""
+        import iqlhip_weighted as wtd
+        from iqlhip_replay import ReplayBuffer
+        self._require_gpu()
+        buf = replay_buffer
+        if not getattr(buf, "_gpu", False) or buf._rows.device != self._dev:
+            raise ValueError("online_step_prioritized needs a ReplayBuffer on the trainer's GPU")
+        if type(buf)._index_bound is not ReplayBuffer._index_bound or type(buf).add_transition is not ReplayBuffer.add_transition:
+            raise NotImplementedError("online_step_prioritized needs the finetune ReplayBuffer (the offline flavour has "
+                                      "no add_transition)")
+        wtd.check_call(buf)
+        if not buf._weights_updatable or not buf._weights_tracks:
+            raise ValueError("iqlhip: online_step_prioritized needs sample weights that track their maximum "
+                             "(set_sample_weights(..., updatable=True, track_max=True))")
+        if self._dp_world > 1 or self._dp_exchange is not None:
+            raise NotImplementedError("iqlhip: online_step_prioritized is not supported under data parallelism")
+        alpha, eps = wtd.check_priority_args(alpha, eps)
+        beta = self._is_beta_arg(is_beta)
+        self._prepare(batch_size)
+        self._refuse_injected_masks()
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        off = (getattr(buf, "_prio_online_offset", 0) if offset is None else int(offset)) & 0xFFFFFFFFFFFFFFFF
+        row = self._online_row(buf, state, action, reward, next_state, done)
+        # (the buffer's and the trainer's counters move only once the library call has succeeded)
+        pointer = buf._pointer
+        new_size = min(buf._size + 1, buf._buffer_size)
+        adam_next = {g: t + 1 for g, t in self._adam_t.items()}
+        sc = hb.StepScalars()
+        self._fill_scalars(sc, adam_next, self._current_lrs(), 1.0 / batch_size)
+        out = (C.c_float * 3)()
+        a_in, a_out, act_seed = self._act_next_args(act_next)
+        self._last_td = None
+        hb.check(hb.lib().iqlhip_online_step_prioritized(
+            self._ctx, buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer, row.ctypes.data, batch_size, C.byref(sc), out,
+            None if a_in is None else a_in.ctypes.data, float(self.actor.max_action), act_seed,
+            None if a_out is None else a_out.ctypes.data, self._stream(), buf._weights, seed, off, beta, alpha, eps))
+        buf._weights_version += 2            # (the insert and the update, as the library counts them)
+        buf._prio_online_offset = (off + wtd.online_offset_step(batch_size)) & 0xFFFFFFFFFFFFFFFF
+        res = self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+        self._last_td, self._last_td_it = ("online", batch_size), self.total_it
+        self._last_prio_idx = (self.total_it, batch_size)
+        return res
 
     def online_step_jsrl(self, jsrl, replay_buffer, state, action, reward: float, next_state, done: bool,
                          batch_size: int, act_next, who, gate_max=None):
@@ -1095,8 +1168,10 @@ class ImplicitQLearning:
         nothing.  The table's version moves with every library call: a train_steps_weighted call that follows gathers
         afresh.  Returns what train_steps returns.  ValueError for a static table, for alpha, eps or is_beta negative or
         not finite, for alpha = eps = 0; NotImplementedError at bf16 precision, under data parallelism and with injected
-        dropout masks pending — all before anything moves.  Not covered: mixed batches, online_step*,
-        priorities of newly added rows (follow add_transition with update_sample_weights), annealing inside a call."""
+        dropout masks pending — all before anything moves.  Not covered: mixed batches, annealing inside a call.
+        (The online iteration: online_step_prioritized; rows added between calls enter at the table's largest priority
+        when it tracks it — set_sample_weights(..., track_max=True) — else follow add_transition with
+        update_sample_weights.)"""
         if return_stats and not self._step_stats:
             raise ValueError("iqlhip: train_steps_prioritized(return_stats=True) needs set_step_stats(True) first")
         size, table, alpha, eps, beta = self._prioritized_args(replay_buffer, batch_size, weights, alpha, eps, is_beta)

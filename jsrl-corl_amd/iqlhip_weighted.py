@@ -79,6 +79,42 @@ def check_updatable_args(n: int, capacity, max_weight):
     return capacity, max_weight
 
 
+def check_tracking_args(updatable: bool, track_max: bool, new_row_weight):
+    """track_max / new_row_weight of a table: tracking belongs to an updatable table, new_row_weight (None: 1.0) is a
+    finite float > 0 and means something only with track_max.  Returns new_row_weight (None without track_max);
+    ValueError otherwise."""
+    import math
+    if not track_max:
+        if new_row_weight is not None:
+            raise ValueError("iqlhip: new_row_weight belongs to a table that tracks its maximum (track_max=True)")
+        return None
+    if not updatable:
+        raise ValueError("iqlhip: track_max belongs to an updatable table (updatable=True)")
+    try:
+        w = 1.0 if new_row_weight is None else float(new_row_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"iqlhip: new_row_weight must be a number, not {type(new_row_weight).__name__}")
+    if not math.isfinite(w) or w <= 0.0:
+        raise ValueError(f"iqlhip: new_row_weight must be finite and > 0 (got {new_row_weight})")
+    return w
+
+
+def check_insert_args(row, bound, n: int) -> tuple:
+    """(row, bound) of insert_max on a table over n rows: bound (None: n) in [0, n], row in [0, bound)."""
+    bound = int(n) if bound is None else int(bound)
+    if not 0 <= bound <= int(n):
+        raise ValueError(f"iqlhip: bound {bound} outside [0, {n}]")
+    row = int(row)
+    if not 0 <= row < bound:
+        raise ValueError(f"iqlhip: row {row} outside [0, {bound})")
+    return row, bound
+
+
+def online_offset_step(batch_size: int) -> int:
+    """Philox counters the draw of one prioritised online step consumes: two indices per counter."""
+    return (int(batch_size) + 1) // 2
+
+
 def check_update_args(indices, weights, device=None) -> int:
     """The shape, dtype and device checks of an update: two 1-D device tensors of one length, int64 indices and float32
     weights (no look at the values: bad ones are skipped and flagged on the device).  Returns that length."""
@@ -171,11 +207,16 @@ def check_group_is_beta(K: int, is_beta) -> list:
     return out
 
 
-def build_table(w_dev, n: int, stream, updatable: bool = False, capacity=None, max_weight=None):
-    """The library's table over the device vector w_dev[0..n): (handle, generation)."""
+def build_table(w_dev, n: int, stream, updatable: bool = False, capacity=None, max_weight=None, new_row_weight=None):
+    """The library's table over the device vector w_dev[0..n): (handle, generation).  new_row_weight not None: an
+    updatable table that tracks its maximum."""
     import iqlhip_binding as hb
     table = C.c_void_p()
-    if updatable:
+    if updatable and new_row_weight is not None:
+        capacity, max_weight = check_updatable_args(n, capacity, max_weight)
+        hb.check(hb.lib().iqlhip_weights_build_tracking(w_dev.data_ptr(), n, capacity, max_weight, float(new_row_weight),
+                                                        stream, C.byref(table)))
+    elif updatable:
         capacity, max_weight = check_updatable_args(n, capacity, max_weight)
         hb.check(hb.lib().iqlhip_weights_build_updatable(w_dev.data_ptr(), n, capacity, max_weight, stream, C.byref(table)))
     else:
@@ -194,6 +235,14 @@ def table_state(table, n: int = 0, leaves: bool = False):
     hb.check(hb.lib().iqlhip_weights_state(table, C.byref(total), C.byref(flags), C.byref(version),
                                            q.ctypes.data if leaves else None))
     return int(total.value), int(flags.value), int(version.value), q
+
+
+def table_max(table) -> tuple:
+    """(q_max, w_max) of a tracking table, after waiting for the device."""
+    import iqlhip_binding as hb
+    q, w = C.c_uint64(), C.c_float()
+    hb.check(hb.lib().iqlhip_weights_max(table, C.byref(q), C.byref(w)))
+    return int(q.value), float(w.value)
 
 
 def check_call(buffer) -> int:
@@ -236,13 +285,17 @@ class SampleWeights:
     _device = None
     _updatable = False
     _version = 0
+    _tracks = False
 
-    def __init__(self, weights, device=None, stream=None, updatable: bool = False, capacity=None, max_weight=None):
+    def __init__(self, weights, device=None, stream=None, updatable: bool = False, capacity=None, max_weight=None,
+                 track_max: bool = False, new_row_weight=None):
         """updatable=True: a table that update() changes in place.  capacity: rows it spans (default: len(weights));
         rows beyond the given weights weigh 0.  max_weight: fixes the scale for the table's life — weights are
         quantised to multiples of 2^(floor(log2(max(max_weight, max(weights)))) - 38), and a later weight of twice that
         power of two or more saturates; None: the largest weight given.  ValueError for capacity or max_weight without
-        updatable=True."""
+        updatable=True.  track_max=True (an updatable table only: ValueError otherwise): the table keeps the largest
+        priority an applied update or the build has seen — at least new_row_weight (default 1.0, finite and > 0) — and
+        insert_max(row) enters a row at it."""
         import torch
         import iqlhip_binding as hb
         shape = tuple(getattr(weights, "shape", ()))
@@ -250,6 +303,7 @@ class SampleWeights:
         kind = check_vector(weights, n)
         if not updatable and (capacity is not None or max_weight is not None):
             raise ValueError("iqlhip: capacity and max_weight belong to an updatable table (updatable=True)")
+        new_row_weight = check_tracking_args(updatable, track_max, new_row_weight)
         rows = n
         if updatable:
             rows, max_weight = check_updatable_args(n, capacity, max_weight)
@@ -274,9 +328,9 @@ class SampleWeights:
             w_dev = torch.tensor(host, dtype=torch.float32, device=dev)      # (a copy: the array may be read-only)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
-            table, gen = build_table(w_dev, n, st, updatable, rows, max_weight)
+            table, gen = build_table(w_dev, n, st, updatable, rows, max_weight, new_row_weight)
         self._table, self._n, self._gen, self._device = table, rows, gen, dev
-        self._updatable, self._version = bool(updatable), 0
+        self._updatable, self._version, self._tracks = bool(updatable), 0, bool(track_max)
 
     @property
     def n(self) -> int:
@@ -339,6 +393,34 @@ class SampleWeights:
         with torch.cuda.device(self._device):
             hb.check(hb.lib().iqlhip_weights_update_td(table, idx.data_ptr(), e.data_ptr(), m, bound, alpha, eps,
                                                        torch.cuda.current_stream(self._device).cuda_stream))
+        self._version += 1
+
+    @property
+    def tracks_max(self) -> bool:
+        """Whether the table tracks its largest priority (track_max=True at the build)."""
+        return self._tracks
+
+    def max_priority(self) -> tuple:
+        """(q_max, w_max): the largest quantised priority an applied update or the build has seen (never below
+        new_row_weight's) and the weight it stands for; waits for the device.  ValueError on a table that does not track."""
+        table = self._alive()
+        if not self._tracks:
+            raise ValueError("iqlhip: these sample weights do not track their maximum (SampleWeights(..., track_max=True))")
+        return table_max(table)
+
+    def insert_max(self, row: int, bound=None) -> None:
+        """w[row] = the table's largest priority, on the device, queued on the current stream with no synchronisation:
+        PER's rule for a newly stored transition.  row in [0, bound), bound (default: n) <= n: ValueError otherwise, and
+        on a table that does not track."""
+        import torch
+        import iqlhip_binding as hb
+        table = self._alive()
+        if not self._tracks:
+            raise ValueError("iqlhip: these sample weights do not track their maximum (SampleWeights(..., track_max=True))")
+        row, bound = check_insert_args(row, bound, self._n)
+        with torch.cuda.device(self._device):
+            hb.check(hb.lib().iqlhip_weights_insert_max(table, row, bound,
+                                                        torch.cuda.current_stream(self._device).cuda_stream))
         self._version += 1
 
     def flags(self) -> int:
@@ -507,6 +589,10 @@ def check_group_prioritized(buffers, weights, K: int):
         if not updatable:
             raise ValueError("iqlhip: prioritised replay needs updatable sample weights "
                              f"(set_sample_weights(..., updatable=True) / SampleWeights(..., updatable=True); member {i})")
+        tracks = e.tracks_max if isinstance(e, SampleWeights) else getattr(e, "_weights_tracks", False)
+        if tracks:
+            raise NotImplementedError("iqlhip: sample weights that track their maximum (track_max=True) are not supported "
+                                      f"in trainer groups (member {i})")
         for j in range(i):
             if entries[j] is e:
                 raise ValueError(f"iqlhip: member {i} draws by the table of member {j}: a prioritised call updates one "
