@@ -1027,6 +1027,47 @@ int64_t iqlhip_debug_live_buffers(void);
 int iqlhip_set_timing(iqlhip_ctx* ctx, int enabled);
 int iqlhip_get_timing(iqlhip_ctx* ctx, float out_us[4]); /* fwd, bwd, update, total */
 
+/* ---- the JSRL variance learner (variance_learner.py VarianceLearner._update_v) ----
+ * Two scalar networks S -> 256 -> 256 -> 1 behind an opaque handle of their own, independent of any iqlhip_ctx: net 0
+ * is mf (the value mean), net 1 is vf (the log-variance, the `variance` horizon's gate).  fp32 only.
+ *
+ * The arena holds the two nets one behind the other, each laid out by iqlhip_arena_layout's per-net rule with
+ * k_in = state_dim, d_out = 1 (W1, W0, b0, b1, W2, b2 padded to 4 words, the segment rounded up to 64 words).
+ *
+ * A step reads ONE packed device block of B * S + S + 2 B floats: B states [B][S], the last next-state [S], B rewards,
+ * B next-done flags (0 or 1).  With samp[t] = reward(t) + (0.99 * next) * (1 - next_done[t]) walked from t = B - 1 down
+ * (next = mf of the last next-state at t = B - 1, else samp[t + 1]; every operation rounded on its own), pred = mf(s),
+ * var = clip(exp(vf(s)), 1e-4, 1e8), the loss is mean(0.5 * (log(var) + (pred - samp)^2 / var)).  reward(t) is the
+ * reference's rewards[t - 1] (row 0 takes rewards[B - 1]) unless aligned_rewards is 1: then rewards[t].  The bootstrap
+ * value keeps its gradient, as in the reference.  which_net names the net that is differentiated and stepped with
+ * torch.optim.Adam's defaults; the other net's parameters and moments are not touched.  1 <= B <= max_rows <= 1024. */
+typedef struct iqlhip_var iqlhip_var;
+typedef struct iqlhip_var_scalars {
+  float step_size;         /* lr / (1 - beta1^t): t the stepped net's own step count, float64 on the host */
+  float bc2_sqrt;          /* sqrt(1 - beta2^t) */
+  float beta2, one_minus_beta1, one_minus_beta2, eps;
+  int32_t aligned_rewards; /* 0: the reference's rewards[t - 1]; 1: rewards[t] */
+  int32_t reserved;
+} iqlhip_var_scalars;
+/* out[0], out[1]: the layouts of mf and vf inside the arena; n_params: the arena's words. */
+int iqlhip_var_layout(int32_t state_dim, iqlhip_net_layout out[2], int64_t* n_params);
+int iqlhip_var_create(int32_t state_dim, int32_t max_rows, int device, iqlhip_var** out);
+int iqlhip_var_destroy(iqlhip_var* var);
+/* The caller's arenas (device, n_params floats each): parameters and Adam's two moments. */
+int iqlhip_var_bind(iqlhip_var* var, float* params, float* exp_avg, float* exp_avg_sq);
+/* Forward, recurrence, backward of which_net and its Adam step, queued on `stream` (four launches). */
+int iqlhip_var_step(iqlhip_var* var, const float* batch_dev, int32_t B, int32_t which_net, const iqlhip_var_scalars* sc,
+                    void* stream);
+/* Forward and recurrence only: samp | pred | var, [B] each, into out_dev [3][B]. */
+int iqlhip_var_values(iqlhip_var* var, const float* batch_dev, int32_t B, int32_t aligned_rewards, float* out_dev,
+                      void* stream);
+/* Tests: the flat gradient of which_net (its segment's words, arena order, padding zero) into grad_out_dev; no update. */
+int iqlhip_var_forward_backward(iqlhip_var* var, const float* batch_dev, int32_t B, int32_t which_net,
+                                int32_t aligned_rewards, float* grad_out_dev, void* stream);
+/* Waits for `stream`; then the loss of the last step / forward_backward / values call and, when head is not NULL, the
+ * first n_head (<= B of that call) entries of its samp, pred and var: head[3][n_head]. */
+int iqlhip_var_read_loss(iqlhip_var* var, float* loss, float* head, int32_t n_head, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5577,3 +5577,179 @@ extern "C" int iqlhip_online_prioritized_batch(iqlhip_ctx* c, int32_t n, int64_t
     HIPCHK(hipMemcpyAsync(td_out_dev, prio_td(c), (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return IQLHIP_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The JSRL variance learner's gradient step (include/iqlhip.h "the JSRL variance learner"; kernels:
+// iqlhip_variance_kernels.h, the code object's last).  A handle of its own: two scalar nets in one arena, scratch sized
+// by max_rows, nothing shared with a context.  A step is four launches: forward, row kernel, backward, Adam.
+#include "iqlhip_variance_kernels.h"
+
+struct iqlhip_var {
+  int S = 0, max_rows = 0, device = 0;
+  iqlhip_net_layout L[2];
+  int64_t n_params = 0;
+  Owned own;
+  float *params = nullptr, *m = nullptr, *v = nullptr;      // bound (caller-owned)
+  float *h0 = nullptr, *h1 = nullptr, *dh0 = nullptr;       // [VAR_LD][256]
+  float *out = nullptr;                                     // [2][VAR_LD] head outputs
+  float *dy = nullptr;                                      // [VAR_LD]
+  float *grad = nullptr;                                    // the stepped net's gradient (the longer segment's words)
+  float *land = nullptr;                                    // pinned, host-mapped: [4] loss | [3][VAR_LD] samp, pred, var
+};
+
+static int var_check_dim(int32_t S) {
+  if (S < 1) return fail(IQLHIP_EINVAL, "state_dim must be >= 1");
+  if (S + 1 > IQLHIP_MAX_INPUT) return fail(IQLHIP_EUNSUPPORTED, "state_dim > %d", IQLHIP_MAX_INPUT - 1);
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_layout(int32_t state_dim, iqlhip_net_layout out[2], int64_t* n_params) {
+  if (int rc = var_check_dim(state_dim)) return rc;
+  if (!out || !n_params) return fail(IQLHIP_EINVAL, "NULL argument");
+  // the per-net rule of iqlhip_arena_layout at k_in = S, d_out = 1: a V net's segment, twice
+  iqlhip_dims d{state_dim, 1, IQLHIP_HIDDEN, 2, IQLHIP_POLICY_DETERMINISTIC, 1};
+  iqlhip_layout L;
+  if (int rc = iqlhip_arena_layout(&d, &L)) return rc;
+  const iqlhip_net_layout& v = L.net[IQLHIP_NET_V];
+  const int64_t seg = v.seg_end - v.seg_begin;
+  for (int k = 0; k < 2; ++k) {
+    const int64_t sh = k * seg - v.seg_begin;
+    out[k] = v;
+    out[k].seg_begin += sh; out[k].seg_end += sh;
+    out[k].w0 += sh; out[k].b0 += sh; out[k].w1 += sh; out[k].b1 += sh; out[k].w2 += sh; out[k].b2 += sh;
+    out[k].log_std = -1;
+  }
+  *n_params = 2 * seg;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_destroy(iqlhip_var* s) {
+  if (!s) return IQLHIP_OK;
+  {
+    DevGuard guard(s->device);
+    (void)hipDeviceSynchronize();
+    s->own.release_all();
+  }
+  delete s;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_create(int32_t state_dim, int32_t max_rows, int device, iqlhip_var** out) {
+  if (!out) return fail(IQLHIP_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (int rc = var_check_dim(state_dim)) return rc;
+  if (max_rows < 1 || max_rows > VAR_MAX_ROWS) return fail(IQLHIP_EINVAL, "max_rows must be in [1,%d]", VAR_MAX_ROWS);
+  int n_dev = 0;
+  HIPCHK(hipGetDeviceCount(&n_dev));
+  if (device < 0 || device >= n_dev) return fail(IQLHIP_EINVAL, "device %d out of range (%d devices)", device, n_dev);
+  std::unique_ptr<iqlhip_var> s(new iqlhip_var);
+  s->S = state_dim; s->max_rows = max_rows; s->device = device;
+  if (int rc = iqlhip_var_layout(state_dim, s->L, &s->n_params)) return rc;
+  DevGuard guard(device);
+  auto dalloc = [&](float** p, size_t nfloat) { return s->own.dev(p, nfloat * sizeof(float), 0); };
+  HIPCHK(dalloc(&s->h0, (size_t)VAR_LD * HID));
+  HIPCHK(dalloc(&s->h1, (size_t)VAR_LD * HID));
+  HIPCHK(dalloc(&s->dh0, (size_t)VAR_LD * HID));
+  HIPCHK(dalloc(&s->out, (size_t)2 * VAR_LD));
+  HIPCHK(dalloc(&s->dy, (size_t)VAR_LD));
+  HIPCHK(dalloc(&s->grad, (size_t)(s->L[0].seg_end - s->L[0].seg_begin)));
+  HIPCHK(s->own.pin(&s->land, (size_t)(4 + 3 * VAR_LD) * sizeof(float), /*zero=*/true));
+  *out = s.release();
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_bind(iqlhip_var* s, float* params, float* exp_avg, float* exp_avg_sq) {
+  if (!s || !params || !exp_avg || !exp_avg_sq) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (((uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return fail(IQLHIP_EINVAL, "arenas must be 16-byte aligned");
+  s->params = params; s->m = exp_avg; s->v = exp_avg_sq;
+  return IQLHIP_OK;
+}
+
+static NetPtrs var_net_ptrs(const iqlhip_var* s, int k) {
+  const iqlhip_net_layout& l = s->L[k];
+  const float* p = s->params;
+  return NetPtrs{p + l.w0, p + l.b0, p + l.w1, p + l.b1, p + l.w2, p + l.b2, s->S, 1};
+}
+
+static int var_check_call(const iqlhip_var* s, const float* batch_dev, int32_t B, int32_t which, bool need_net, int32_t aligned) {
+  if (!s || !batch_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (!s->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_var_bind has not been called");
+  if (B < 1 || B > s->max_rows) return fail(IQLHIP_EINVAL, "B = %d outside [1, max_rows = %d]", B, s->max_rows);
+  if (need_net && which != 0 && which != 1) return fail(IQLHIP_EINVAL, "which_net must be 0 (mf) or 1 (vf), got %d", which);
+  if (aligned != 0 && aligned != 1) return fail(IQLHIP_EINVAL, "aligned_rewards must be 0 or 1, got %d", aligned);
+  if ((uintptr_t)batch_dev & 3) return fail(IQLHIP_EINVAL, "the packed block must be 4-byte aligned");
+  return IQLHIP_OK;
+}
+
+// forward + row kernel (which = -1: values only), then the backward of `which` into s->grad
+static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, int aligned, float* vals2, hipStream_t st) {
+  const int S = s->S;
+  VarFwdParams f{};
+  f.net[0] = var_net_ptrs(s, 0); f.net[1] = var_net_ptrs(s, 1);
+  f.x = batch_dev; f.S = S; f.rows0 = B + 1; f.rows1 = B; f.keep = which;
+  f.h0 = s->h0; f.h1 = s->h1; f.out = s->out;
+  hipLaunchKernelGGL(iql_var_fwd_kernel<>, dim3((unsigned)(B + 1 + 31) / 32u, 2), dim3(256), 0, st, f);
+  VarRowParams r{};
+  r.out = s->out; r.rew = batch_dev + (size_t)(B + 1) * S; r.nd = r.rew + B; r.B = B; r.which = which; r.aligned = aligned;
+  r.vals = s->land + 4; r.vals2 = vals2; r.dy = s->dy; r.loss = s->land;
+  hipLaunchKernelGGL(iql_var_row_kernel<>, dim3(1), dim3(256), 0, st, r);
+  if (which < 0) return;
+  const iqlhip_net_layout& l = s->L[which];
+  VarBwdParams b{};
+  b.np = var_net_ptrs(s, which); b.x = batch_dev; b.S = S; b.n = which == 0 ? B + 1 : B;
+  b.h0 = s->h0; b.h1 = s->h1; b.dy = s->dy; b.dh0 = s->dh0; b.grad = s->grad;
+  const int64_t sb = l.seg_begin;
+  b.g_w1 = (unsigned)(l.w1 - sb); b.g_w0 = (unsigned)(l.w0 - sb); b.g_b0 = (unsigned)(l.b0 - sb);
+  b.g_b1 = (unsigned)(l.b1 - sb); b.g_w2 = (unsigned)(l.w2 - sb); b.g_b2 = (unsigned)(l.b2 - sb);
+  hipLaunchKernelGGL(iql_var_bwd_kernel<>, dim3(VAR_BWD_BLOCKS), dim3(256), 0, st, b);
+}
+
+extern "C" int iqlhip_var_step(iqlhip_var* s, const float* batch_dev, int32_t B, int32_t which_net, const iqlhip_var_scalars* sc,
+                               void* stream) {
+  if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (int rc = var_check_call(s, batch_dev, B, which_net, true, sc->aligned_rewards)) return rc;
+  DevGuard guard(s->device);
+  hipStream_t st = (hipStream_t)stream;
+  var_launch(s, batch_dev, B, which_net, sc->aligned_rewards, nullptr, st);
+  const iqlhip_net_layout& l = s->L[which_net];
+  const int n = (int)(l.seg_end - l.seg_begin);
+  hipLaunchKernelGGL(iql_var_adam_kernel<>, dim3((unsigned)(n + 255) / 256u), dim3(256), 0, st, s->params + l.seg_begin,
+                     s->m + l.seg_begin, s->v + l.seg_begin, (const float*)s->grad, n, -sc->step_size, sc->bc2_sqrt,
+                     sc->one_minus_beta1, sc->beta2, sc->one_minus_beta2, sc->eps);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_values(iqlhip_var* s, const float* batch_dev, int32_t B, int32_t aligned_rewards, float* out_dev,
+                                 void* stream) {
+  if (int rc = var_check_call(s, batch_dev, B, -1, false, aligned_rewards)) return rc;
+  if (!out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  DevGuard guard(s->device);
+  var_launch(s, batch_dev, B, -1, aligned_rewards, out_dev, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_forward_backward(iqlhip_var* s, const float* batch_dev, int32_t B, int32_t which_net,
+                                           int32_t aligned_rewards, float* grad_out_dev, void* stream) {
+  if (int rc = var_check_call(s, batch_dev, B, which_net, true, aligned_rewards)) return rc;
+  if (!grad_out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  DevGuard guard(s->device);
+  hipStream_t st = (hipStream_t)stream;
+  var_launch(s, batch_dev, B, which_net, aligned_rewards, nullptr, st);
+  HIPCHK(hipGetLastError());
+  const iqlhip_net_layout& l = s->L[which_net];
+  HIPCHK(hipMemcpyAsync(grad_out_dev, s->grad, (size_t)(l.seg_end - l.seg_begin) * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_read_loss(iqlhip_var* s, float* loss, float* head, int32_t n_head, void* stream) {
+  if (!s || !loss) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n_head < 0 || n_head > s->max_rows) return fail(IQLHIP_EINVAL, "n_head outside [0, max_rows]");
+  DevGuard guard(s->device);
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  *loss = s->land[0];
+  if (head)
+    for (int k = 0; k < 3; ++k) memcpy(head + (size_t)k * n_head, s->land + 4 + (size_t)k * VAR_LD, (size_t)n_head * sizeof(float));
+  return IQLHIP_OK;
+}

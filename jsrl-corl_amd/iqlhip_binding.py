@@ -72,6 +72,12 @@ class StepScalars(C.Structure):
                 ("grad_scale", C.c_float), ("inv_batch", C.c_float)]
 
 
+class VarScalars(C.Structure):
+    """iqlhip_var_scalars: Adam's scalars of the stepped net and the reward alignment of one variance-learner step."""
+    _fields_ = [("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("beta2", C.c_float), ("one_minus_beta1", C.c_float),
+                ("one_minus_beta2", C.c_float), ("eps", C.c_float), ("aligned_rewards", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Batch(C.Structure):
     _fields_ = [("s_dev", C.c_void_p), ("a_dev", C.c_void_p), ("r_dev", C.c_void_p), ("ns_dev", C.c_void_p),
                 ("d_dev", C.c_void_p),
@@ -279,6 +285,15 @@ SYMBOLS = [
                                           C.POINTER(C.c_float), C.c_void_p]),
     ("iqlhip_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("iqlhip_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("iqlhip_var_layout", C.c_int, [C.c_int32, C.POINTER(NetLayout), C.POINTER(C.c_int64)]),
+    ("iqlhip_var_create", C.c_int, [C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_void_p)]),
+    ("iqlhip_var_destroy", C.c_int, [C.c_void_p]),
+    ("iqlhip_var_bind", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("iqlhip_var_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(VarScalars), C.c_void_p]),
+    ("iqlhip_var_values", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("iqlhip_var_forward_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p]),
+    ("iqlhip_var_read_loss", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -329,6 +344,14 @@ def arena_layout(state_dim: int, action_dim: int, gaussian: bool = True, max_bat
     out = Layout()
     check(lib().iqlhip_arena_layout(C.byref(d), C.byref(out)))
     return out
+
+
+def var_layout(state_dim: int):
+    """(layouts of mf and vf, n_params) of a variance learner's two-net arena (iqlhip_var_layout)."""
+    out = (NetLayout * 2)()
+    n = C.c_int64(0)
+    check(lib().iqlhip_var_layout(state_dim, out, C.byref(n)))
+    return out, int(n.value)
 
 
 def row_stride(state_dim: int, action_dim: int) -> int:

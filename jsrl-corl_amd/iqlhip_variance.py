@@ -1,0 +1,366 @@
+"""The JSRL variance learner on the device (include/iqlhip.h "the JSRL variance learner"): the reference's
+variance_learner.py VarianceLearner — the two scalar networks behind the `variance` horizon — with `_update_v` as one
+packed upload, one library step (forward, recurrence, backward, Adam: four launches) and one synchronisation.
+
+The step is the reference's as written, quirks included: sampled values use rewards[t - 1] (row 0 takes rewards[B - 1];
+`aligned_rewards=True` is this project's opt-in for rewards[t]), the bootstrap value keeps its gradient, `actions` and
+`dones` are unused, of `next_observations` only the last row is.  Not ported: StateActionVarianceLearner (its get_values
+cannot run in the reference) and test_model (mismatched signatures, plotting).  There is no CPU fall-back: a learner on a
+CPU device holds its networks and optimizers, and raises when asked to step."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+import iqlhip_binding as hb
+from iqlhip_networks import MLP, linear_layers
+
+GAMMA = 0.99
+VAR_MAX_ROWS = 1024           # rows of one step (csrc/iqlhip_variance_kernels.h)
+NET_MF, NET_VF = 0, 1
+SAVE_DIR = "jsrl-CORL/algorithms/finetune/var_functions"      # the reference's save path
+_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
+
+
+def to_tensor(data) -> torch.Tensor:
+    return torch.tensor(data, dtype=torch.float32)
+
+
+def nll_loss(pred: torch.Tensor, target: torch.Tensor, var: torch.Tensor) -> torch.Tensor:
+    return torch.nn.functional.gaussian_nll_loss(pred, target, var)
+
+
+def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return 0.5 * ((pred - target) ** 2).mean()
+
+
+@torch.no_grad()
+def run_episodes(env, max_steps: int, seeds, actor=None, batch_size=None, random_frac=0):
+    """Roll `env` out (variance_learner.py:16-78): returns (states, actions, rewards, dones, next_states, next_dones),
+    lists with one entry per environment step; states and next_states hold float32 tensors.  seeds: an int (the first
+    episode is seeded with it, later ones continue unseeded, the rollout ends at `batch_size` rows) or a list (every
+    episode ep is seeded, while ep < len(seeds), starting at ep = seeds[0], as the reference writes it).  An actor
+    consumes one np.random.random() per step — none without one; `actor(env, state)` or `actor.act(state, device)`.
+    next_dones is the env's done unless the episode ran into max_steps (a time-out is not a terminal)."""
+    states, next_states, next_dones, actions, rewards, dones = [], [], [], [], [], []
+    listed = isinstance(seeds, list)
+    ep = seeds[0] if listed else seeds
+    while (ep < len(seeds)) if listed else True:
+        if listed or ep == seeds:
+            try:
+                env.seed(ep)
+                next_state = env.reset()
+            except AttributeError:
+                next_state, _ = env.reset(seed=ep)
+                env.action_space.seed(ep)
+        else:
+            next_state = env.reset()
+            if isinstance(next_state, tuple):
+                next_state, _ = next_state
+        ts, next_done = 0, False
+        while not next_done:
+            states.append(to_tensor(next_state))
+            dones.append(next_done)
+            if actor is None or np.random.random() <= random_frac:
+                action = env.action_space.sample()
+            else:
+                try:
+                    action = actor(env, next_state)
+                except TypeError:
+                    try:
+                        action = actor.act(next_state, "cpu")
+                    except RuntimeError:
+                        action = actor.act(next_state, "cuda")
+            next_state, reward, next_done, _ = env.step(action)
+            if "antmaze" in env.unwrapped.spec.name:
+                reward -= 1
+            real_done = bool(next_done and ts < max_steps - 1)
+            actions.append(action)
+            rewards.append(reward)
+            next_states.append(to_tensor(next_state))
+            next_dones.append(real_done)
+            if batch_size is not None and len(states) == batch_size:
+                return states, actions, rewards, dones, next_states, next_dones
+            ts += 1
+        ep += 1
+    return states, actions, rewards, dones, next_states, next_dones
+
+
+class StateDepFunction(nn.Module):
+    """A scalar function of the state (variance_learner.py:363-370): state-dict keys v.net.{0,2,4}.{weight,bias}."""
+
+    def __init__(self, state_dim: int, hidden_dim: int = 256, n_hidden: int = 2):
+        super().__init__()
+        self.v = MLP([state_dim, *([hidden_dim] * n_hidden), 1], squeeze_output=True)
+
+    def forward(self, state: torch.Tensor) -> torch.Tensor:
+        return self.v(state)
+
+
+def _rows(x, S: Optional[int] = None) -> np.ndarray:
+    """A list of tensors / arrays, or a 2-D array -> float32 [n, S]."""
+    if isinstance(x, torch.Tensor):
+        a = x.detach().cpu().numpy()
+    elif isinstance(x, np.ndarray):
+        a = x
+    else:
+        a = np.stack([np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float32).reshape(-1) for r in x])
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or (S is not None and a.shape[1] != S):
+        raise ValueError(f"iqlhip: expected rows of {S} floats, got an array of shape {list(a.shape)}")
+    return a
+
+
+def _column(x, B: int, what: str) -> np.ndarray:
+    a = np.asarray([float(v) for v in x], dtype=np.float32) if not isinstance(x, np.ndarray) else x.astype(np.float32).reshape(-1)
+    if a.shape != (B,):
+        raise ValueError(f"iqlhip: {what} must hold {B} values, got {a.shape[0]}")
+    return a
+
+
+def pack_block(state_dim: int, observations, rewards, next_observations, next_dones) -> Tuple[np.ndarray, int]:
+    """The step's packed block (include/iqlhip.h): B states [B][S], the last next-state [S], B rewards, B next-done
+    flags as 0 / 1 — B * S + S + 2 B float32 — and B."""
+    S = state_dim
+    obs = _rows(observations, S)
+    B = obs.shape[0]
+    if not 1 <= B <= VAR_MAX_ROWS:
+        raise ValueError(f"iqlhip: a variance-learner step takes 1..{VAR_MAX_ROWS} rows, got {B}")
+    if len(next_observations) != B:
+        raise ValueError(f"iqlhip: next_observations must hold {B} rows, got {len(next_observations)}")
+    last = _rows([next_observations[B - 1]], S)
+    out = np.empty(B * S + S + 2 * B, dtype=np.float32)
+    out[:B * S] = obs.reshape(-1)
+    out[B * S:(B + 1) * S] = last.reshape(-1)
+    out[(B + 1) * S:(B + 1) * S + B] = _column(rewards, B, "rewards")
+    out[(B + 1) * S + B:] = _column(next_dones, B, "next_dones")
+    return out, B
+
+
+def adam_scalars(lr: float, betas, eps: float, t: int, aligned_rewards: bool = False) -> hb.VarScalars:
+    """Adam's scalars of step t (>= 1) of one net, in float64 as the trainer computes its own."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    return hb.VarScalars(lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, b2, 1.0 - b1, 1.0 - b2, eps, int(bool(aligned_rewards)), 0)
+
+
+def _mlp_tensors(module: nn.Module) -> Dict[str, nn.Parameter]:
+    lin = linear_layers(module)
+    if len(lin) != 3 or lin[0].weight.shape[0] != hb.IQLHIP_HIDDEN or tuple(lin[1].weight.shape) != (hb.IQLHIP_HIDDEN,) * 2 \
+            or tuple(lin[2].weight.shape) != (1, hb.IQLHIP_HIDDEN):
+        raise NotImplementedError(f"iqlhip: the variance learner's kernels are built for S -> {hb.IQLHIP_HIDDEN} -> "
+                                  f"{hb.IQLHIP_HIDDEN} -> 1 networks")
+    return {"w0": lin[0].weight, "b0": lin[0].bias, "w1": lin[1].weight, "b1": lin[1].bias, "w2": lin[2].weight, "b2": lin[2].bias}
+
+
+class VarianceLearner:
+    """variance_learner.py VarianceLearner with the gradient step on the GPU.  mf / vf and the two optimizers are the
+    reference's attributes; on a GPU device their parameters and Adam moments are views of the library's arenas."""
+
+    def __init__(self, state_dim, action_dim, config, actor, batch_size=256, device=None, aligned_rewards: bool = False):
+        self.state_dim = state_dim
+        self.action_dim = action_dim
+        self.config = config
+        self.batch_size = batch_size
+        self.actor = actor
+        self.aligned_rewards = bool(aligned_rewards)
+        if not 1 <= int(batch_size) <= VAR_MAX_ROWS:
+            raise ValueError(f"iqlhip: batch_size must be in [1, {VAR_MAX_ROWS}], got {batch_size}")
+        self.device = device if device is not None else getattr(config, "device", "cuda")
+
+        self.mf = StateDepFunction(state_dim)
+        self.vf = StateDepFunction(state_dim)
+        self.m_optimizer = torch.optim.Adam(self.mf.parameters(), lr=.0001)
+        self.mv_optimizer = torch.optim.Adam(self.vf.parameters(), lr=.0001)
+
+        self._h = None
+        self._adam_t = [0, 0]
+        if torch.device(self.device).type == "cuda":
+            self._attach()
+
+    # ------------------------------------------------------------------ arenas
+    def _nets(self):
+        return (self.mf, self.m_optimizer), (self.vf, self.mv_optimizer)
+
+    def _attach(self) -> None:
+        dev = torch.device(self.device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self._dev = dev
+        L, n = hb.var_layout(self.state_dim)
+        self._layout, self._n_params = L, n
+        self._params_arena = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._m_arena = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._v_arena = torch.zeros(n, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for k, (net, opt) in enumerate(self._nets()):
+                t = 0
+                for key, p in _mlp_tensors(net).items():
+                    off = int(getattr(L[k], key))
+                    view = lambda arena: arena[off: off + p.numel()].view(p.shape)
+                    pv, mv, vv = view(self._params_arena), view(self._m_arena), view(self._v_arena)
+                    pv.copy_(p.data.to(dev, torch.float32))
+                    p.data = pv
+                    st = opt.state.get(p)
+                    if st and "exp_avg" in st:
+                        mv.copy_(st["exp_avg"].to(dev, torch.float32))
+                        vv.copy_(st["exp_avg_sq"].to(dev, torch.float32))
+                        st["exp_avg"], st["exp_avg_sq"] = mv, vv
+                        t = max(t, int(float(st["step"])))
+                self._adam_t[k] = t
+        h = C.c_void_p()
+        hb.check(hb.lib().iqlhip_var_create(self.state_dim, VAR_MAX_ROWS, dev.index, C.byref(h)))
+        self._h = h
+        hb.check(hb.lib().iqlhip_var_bind(h, self._params_arena.data_ptr(), self._m_arena.data_ptr(), self._v_arena.data_ptr()))
+        words = VAR_MAX_ROWS * self.state_dim + self.state_dim + 2 * VAR_MAX_ROWS
+        self._pin = torch.empty(words, dtype=torch.float32).pin_memory()
+        self._pin_np = self._pin.numpy()
+        self._blk = torch.empty(words, dtype=torch.float32, device=dev)
+
+    def _release(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            hb.lib().iqlhip_var_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _need_gpu(self):
+        if self._h is None:
+            raise RuntimeError("iqlhip: the variance learner steps on the GPU only (device='cuda'); there is no CPU fall-back")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self._dev.index).cuda_stream)
+
+    def _adam_hyper(self, opt):
+        if len(opt.param_groups) != 1:
+            raise NotImplementedError("one param group per optimizer expected (variance_learner.py:246-247)")
+        g = opt.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise NotImplementedError("iqlhip implements torch.optim.Adam defaults only (no weight decay/amsgrad)")
+        return float(g["lr"]), g["betas"], float(g["eps"])
+
+    def _sync_opt_state(self, k: int) -> None:
+        """optimizer.state as torch.optim.Adam leaves it after the net's t steps: the moments are the arena's views."""
+        net, opt = self._nets()[k]
+        for key, p in _mlp_tensors(net).items():
+            off = int(getattr(self._layout[k], key))
+            st = opt.state[p]
+            st["step"] = torch.tensor(float(self._adam_t[k]), dtype=torch.float32)
+            st["exp_avg"] = self._m_arena[off: off + p.numel()].view(p.shape)
+            st["exp_avg_sq"] = self._v_arena[off: off + p.numel()].view(p.shape)
+
+    # ------------------------------------------------------------------ the step
+    def _upload(self, observations, rewards, next_observations, next_dones) -> int:
+        blk, B = pack_block(self.state_dim, observations, rewards, next_observations, next_dones)
+        with torch.cuda.device(self._dev):
+            torch.cuda.current_stream().synchronize()        # (the pinned words may still feed the previous upload)
+            self._pin_np[:blk.size] = blk
+            self._blk[:blk.size].copy_(self._pin[:blk.size], non_blocking=True)
+        return B
+
+    def _read(self, n_head: int):
+        loss = C.c_float(0.0)
+        head = (C.c_float * (3 * max(n_head, 1)))()
+        hb.check(hb.lib().iqlhip_var_read_loss(self._h, C.byref(loss), head, n_head, self._stream()))
+        return float(loss.value), np.ctypeslib.as_array(head).reshape(3, -1)[:, :n_head].copy()
+
+    def _update_v(self, batch, update_vf) -> dict:
+        observations, _actions, rewards, _dones, next_observations, next_dones = batch
+        k = NET_VF if update_vf else NET_MF
+        lr, betas, eps = self._adam_hyper(self._nets()[k][1])
+        self._need_gpu()
+        B = self._upload(observations, rewards, next_observations, next_dones)
+        t = self._adam_t[k] + 1
+        sc = adam_scalars(lr, betas, eps, t, self.aligned_rewards)
+        with torch.cuda.device(self._dev):
+            hb.check(hb.lib().iqlhip_var_step(self._h, self._blk.data_ptr(), B, k, C.byref(sc), self._stream()))
+            loss, head = self._read(min(5, B))
+        self._adam_t[k] = t
+        self._sync_opt_state(k)
+        return {"variance_pred_vec": torch.from_numpy(head[2]), "value_loss": loss,
+                "values_pred_vec": torch.from_numpy(head[1]), "values_samp_vec": torch.from_numpy(head[0])}
+
+    def get_values(self, obs, rewards, next_obs, dones, next_dones):
+        """(values_samp, values_pred, variance_pred), CPU tensors of B entries: forward and recurrence, no gradient."""
+        self._need_gpu()
+        B = self._upload(obs, rewards, next_obs, next_dones)
+        out = torch.empty((3, B), dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            hb.check(hb.lib().iqlhip_var_values(self._h, self._blk.data_ptr(), B, int(self.aligned_rewards), out.data_ptr(),
+                                                self._stream()))
+        out = out.cpu()
+        return out[0], out[1], out[2]
+
+    def flat_gradient(self, batch, update_vf):
+        """Tests: (loss, the flat gradient of mf or vf in arena order) of one batch, nothing updated."""
+        self._need_gpu()
+        observations, _actions, rewards, _dones, next_observations, next_dones = batch
+        k = NET_VF if update_vf else NET_MF
+        B = self._upload(observations, rewards, next_observations, next_dones)
+        n = int(self._layout[k].seg_end - self._layout[k].seg_begin)
+        g = torch.empty(n, dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            hb.check(hb.lib().iqlhip_var_forward_backward(self._h, self._blk.data_ptr(), B, k, int(self.aligned_rewards),
+                                                          g.data_ptr(), self._stream()))
+            loss, _ = self._read(0)
+        return loss, g.cpu()
+
+    def net_gradients(self, flat: torch.Tensor, update_vf) -> Dict[str, torch.Tensor]:
+        """A flat_gradient split into {w0, b0, w1, b1, w2, b2}, shaped like the parameters."""
+        k = NET_VF if update_vf else NET_MF
+        L, base = self._layout[k], int(self._layout[k].seg_begin)
+        return {key: flat[int(getattr(L, key)) - base: int(getattr(L, key)) - base + p.numel()].view(p.shape)
+                for key, p in _mlp_tensors(self._nets()[k][0]).items()}
+
+    def gate(self, device=None):
+        """A GateHolder over a COPY of the current vf, ready for JsrlActors(..., gates=...)."""
+        from iqlhip_jsrl import load_gate
+        sd = {k: v.detach().cpu().clone() for k, v in self.vf.state_dict().items()}
+        return load_gate(sd, action_dim=self.action_dim, device=str(self._dev) if device is None else device)
+
+    # ------------------------------------------------------------------ the reference's loop
+    def run_training(self, env, max_steps, actor, n_updates=10000, evaluate=False, save_dir=SAVE_DIR):
+        """variance_learner.py:297-328: n_updates rollouts and updates, mf in the first half and vf once n > n_updates / 2;
+        every 100th update is printed and its loss kept.  Saves `<env>_<guide|None>_<n_updates>_<frac>_{vf,mf}.pt` (CPU
+        tensors) under save_dir unless it is None; returns self.vf in eval mode, and mf is deleted.  evaluate=True only
+        saves the loss curve, when matplotlib is there (the reference's test_model is not ported)."""
+        vf_losses: List[float] = []
+        log_freq = 100
+        log_dict: dict = {}
+        for n in range(n_updates):
+            batch = run_episodes(env, max_steps, n, actor, batch_size=self.batch_size, random_frac=self.config.variance_learn_frac)
+            log_dict = self._update_v(batch, update_vf=(n > n_updates / 2))
+            if n % log_freq == 0:
+                print(f"Iteration {n}/{n_updates}:")
+                for k, v in log_dict.items():
+                    if "loss" in k:
+                        vf_losses.append(v)
+                    print(f"{k}: {v}")
+        log_dict["var_learner/loss"] = vf_losses
+        self.mf.eval()
+        self.vf.eval()
+        if save_dir is not None:
+            os.makedirs(save_dir, exist_ok=True)
+            name = env.unwrapped.spec.name
+            if evaluate:
+                try:
+                    from matplotlib import pyplot as plt
+                    plt.plot(vf_losses)
+                    plt.savefig(f"{save_dir}/losses_vf_{name}.png")
+                except ImportError:
+                    pass
+            actor_name = "guide" if self.actor is not None else None
+            stem = f"{save_dir}/{name}_{actor_name}_{n_updates}_{str(self.config.variance_learn_frac).replace('.', '-')}"
+            cpu = lambda m: {k: v.detach().cpu() for k, v in m.state_dict().items()}
+            torch.save(cpu(self.vf), stem + "_vf.pt")
+            torch.save(cpu(self.mf), stem + "_mf.pt")
+        del self.mf
+        return self.vf
