@@ -1068,6 +1068,42 @@ int iqlhip_var_forward_backward(iqlhip_var* var, const float* batch_dev, int32_t
  * first n_head (<= B of that call) entries of its samp, pred and var: head[3][n_head]. */
 int iqlhip_var_read_loss(iqlhip_var* var, float* loss, float* head, int32_t n_head, void* stream);
 
+/* ---- the variance learner from a replay buffer (DESIGN.md 6l "From a replay buffer") ----
+ * A dataset is stored in trajectory order and an online ring fills in time order, so B consecutive rows of a packed
+ * replay buffer ([s | a | s' | r | d | pad], stride ld >= iqlhip_row_stride) are a rollout: the window that starts at
+ * row `start` gives the packed block of a step as state t = columns [0, S) of row start + t, the last next-state =
+ * columns [S + A, 2 S + A) of row start + B - 1, rewards[t] = that row's r, next_dones[t] = that row's d.  A window
+ * never wraps: 0 <= start <= size - B.  Row offsets are 64-bit.
+ *
+ * Refused before any launch, with nothing changed (IQLHIP_EINVAL): a NULL argument, state_dim other than the handle's,
+ * B outside [1, max_rows], a buffer of fewer than B rows, start < 0 or start + B beyond the buffer,
+ * ld < iqlhip_row_stride(state_dim, action_dim), n_steps outside [1, IQLHIP_VAR_TRAIN_MAX_STEPS], a starts list with
+ * n_starts < 1.  The handle takes the scratch of these calls (a packed block, the two rings) on first use and releases
+ * it with iqlhip_var_destroy. */
+#define IQLHIP_VAR_TRAIN_MAX_STEPS 1024 /* updates per iqlhip_var_train_steps call = words of the loss and start rings */
+/* One launch: the packed block (B * S + S + 2 B floats) of the window at `start` into block_out_dev. */
+int iqlhip_var_pack_window(iqlhip_var* var, const float* rows_dev, int64_t ld, int64_t n_rows, int32_t state_dim,
+                           int32_t action_dim, int64_t start, int32_t B, float* block_out_dev, void* stream);
+/* iqlhip_var_values on the window at `start` (packed into the handle's scratch): samp | pred | var into out_dev [3][B]. */
+int iqlhip_var_values_window(iqlhip_var* var, const float* rows_dev, int64_t ld, int64_t n_rows, int32_t state_dim,
+                             int32_t action_dim, int64_t start, int32_t B, int32_t aligned_rewards, float* out_dev,
+                             void* stream);
+/* n_steps updates of which_net queued on `stream` as plain launches, five per update (pack, forward, recurrence,
+ * backward, Adam); no synchronisation and no host work between them.  scalars[k] are update k's (all with the same
+ * aligned_rewards).  Update k draws its start row inside the pack kernel from the 64 random bits of INDEX
+ * j = stream_offset + k of the index stream under `seed` at counter offset 0 — what
+ * iqlhip_draw_indices(idx, n, span, seed, 0) writes to idx[j]: stream_offset counts indices, not counters, so that a
+ * call may be split at any update —: start = floor(bits * span / 2^64) with span = size - B + 1, or, with a list of
+ * n_starts int64 device entries, starts_dev[floor(bits * n_starts / 2^64)] (entries are the caller's to keep inside
+ * [0, size - B]; the kernel clamps them there).  Word k of the start ring takes the start used, word k of the loss ring
+ * the update's loss.  iqlhip_var_read_loss's words are not written by this call. */
+int iqlhip_var_train_steps(iqlhip_var* var, const float* rows_dev, int64_t ld, int64_t size, int32_t action_dim, int32_t B,
+                           int32_t n_steps, int32_t which_net, const iqlhip_var_scalars* scalars, uint64_t seed,
+                           uint64_t stream_offset, const int64_t* starts_dev, int64_t n_starts, void* stream);
+/* Waits for `stream`; then the first n_steps words of the loss ring and of the start ring of the last
+ * iqlhip_var_train_steps call. */
+int iqlhip_var_read_train_ring(iqlhip_var* var, float* losses_out, int64_t* starts_out, int32_t n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

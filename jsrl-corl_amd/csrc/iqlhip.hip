@@ -5595,6 +5595,11 @@ struct iqlhip_var {
   float *dy = nullptr;                                      // [VAR_LD]
   float *grad = nullptr;                                    // the stepped net's gradient (the longer segment's words)
   float *land = nullptr;                                    // pinned, host-mapped: [4] loss | [3][VAR_LD] samp, pred, var
+  // windows of a replay buffer (iqlhip_var_train_steps, iqlhip_var_values_window): taken on first use
+  float *wblk = nullptr;                                    // the packed block of the current update
+  float *wvals = nullptr;                                   // [3][VAR_LD] samp, pred, var of a burst's updates (not read back)
+  float *loss_ring = nullptr;                               // pinned, host-mapped: [IQLHIP_VAR_TRAIN_MAX_STEPS] losses
+  long long *start_ring = nullptr;                          // pinned, host-mapped: [IQLHIP_VAR_TRAIN_MAX_STEPS] start rows
 };
 
 static int var_check_dim(int32_t S) {
@@ -5682,7 +5687,9 @@ static int var_check_call(const iqlhip_var* s, const float* batch_dev, int32_t B
 }
 
 // forward + row kernel (which = -1: values only), then the backward of `which` into s->grad
-static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, int aligned, float* vals2, hipStream_t st) {
+// (vals / loss: where the row kernel leaves samp | pred | var and the loss; null: the handle's host-mapped landing words)
+static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, int aligned, float* vals2, hipStream_t st,
+                       float* vals = nullptr, float* loss = nullptr) {
   const int S = s->S;
   VarFwdParams f{};
   f.net[0] = var_net_ptrs(s, 0); f.net[1] = var_net_ptrs(s, 1);
@@ -5691,7 +5698,7 @@ static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, 
   hipLaunchKernelGGL(iql_var_fwd_kernel<>, dim3((unsigned)(B + 1 + 31) / 32u, 2), dim3(256), 0, st, f);
   VarRowParams r{};
   r.out = s->out; r.rew = batch_dev + (size_t)(B + 1) * S; r.nd = r.rew + B; r.B = B; r.which = which; r.aligned = aligned;
-  r.vals = s->land + 4; r.vals2 = vals2; r.dy = s->dy; r.loss = s->land;
+  r.vals = vals ? vals : s->land + 4; r.vals2 = vals2; r.dy = s->dy; r.loss = loss ? loss : s->land;
   hipLaunchKernelGGL(iql_var_row_kernel<>, dim3(1), dim3(256), 0, st, r);
   if (which < 0) return;
   const iqlhip_net_layout& l = s->L[which];
@@ -5704,6 +5711,14 @@ static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, 
   hipLaunchKernelGGL(iql_var_bwd_kernel<>, dim3(VAR_BWD_BLOCKS), dim3(256), 0, st, b);
 }
 
+static void var_launch_adam(iqlhip_var* s, int which, const iqlhip_var_scalars* sc, hipStream_t st) {
+  const iqlhip_net_layout& l = s->L[which];
+  const int n = (int)(l.seg_end - l.seg_begin);
+  hipLaunchKernelGGL(iql_var_adam_kernel<>, dim3((unsigned)(n + 255) / 256u), dim3(256), 0, st, s->params + l.seg_begin,
+                     s->m + l.seg_begin, s->v + l.seg_begin, (const float*)s->grad, n, -sc->step_size, sc->bc2_sqrt,
+                     sc->one_minus_beta1, sc->beta2, sc->one_minus_beta2, sc->eps);
+}
+
 extern "C" int iqlhip_var_step(iqlhip_var* s, const float* batch_dev, int32_t B, int32_t which_net, const iqlhip_var_scalars* sc,
                                void* stream) {
   if (!sc) return fail(IQLHIP_EINVAL, "NULL argument");
@@ -5711,11 +5726,7 @@ extern "C" int iqlhip_var_step(iqlhip_var* s, const float* batch_dev, int32_t B,
   DevGuard guard(s->device);
   hipStream_t st = (hipStream_t)stream;
   var_launch(s, batch_dev, B, which_net, sc->aligned_rewards, nullptr, st);
-  const iqlhip_net_layout& l = s->L[which_net];
-  const int n = (int)(l.seg_end - l.seg_begin);
-  hipLaunchKernelGGL(iql_var_adam_kernel<>, dim3((unsigned)(n + 255) / 256u), dim3(256), 0, st, s->params + l.seg_begin,
-                     s->m + l.seg_begin, s->v + l.seg_begin, (const float*)s->grad, n, -sc->step_size, sc->bc2_sqrt,
-                     sc->one_minus_beta1, sc->beta2, sc->one_minus_beta2, sc->eps);
+  var_launch_adam(s, which_net, sc, st);
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
 }
@@ -5751,5 +5762,115 @@ extern "C" int iqlhip_var_read_loss(iqlhip_var* s, float* loss, float* head, int
   *loss = s->land[0];
   if (head)
     for (int k = 0; k < 3; ++k) memcpy(head + (size_t)k * n_head, s->land + 4 + (size_t)k * VAR_LD, (size_t)n_head * sizeof(float));
+  return IQLHIP_OK;
+}
+
+// ---- windows of a packed replay buffer (include/iqlhip.h "from a replay buffer") ----
+static int var_window_scratch(iqlhip_var* s) {
+  if (s->wblk) return IQLHIP_OK;
+  return all_or_nothing(s->own, [&]() -> int {
+    HIPCHK(s->own.dev(&s->wblk, ((size_t)s->max_rows * s->S + s->S + 2 * (size_t)s->max_rows) * sizeof(float), 0));
+    HIPCHK(s->own.dev(&s->wvals, (size_t)3 * VAR_LD * sizeof(float), 0));
+    HIPCHK(s->own.pin(&s->loss_ring, (size_t)IQLHIP_VAR_TRAIN_MAX_STEPS * sizeof(float), /*zero=*/true));
+    HIPCHK(s->own.pin(&s->start_ring, (size_t)IQLHIP_VAR_TRAIN_MAX_STEPS * sizeof(long long), /*zero=*/true));
+    return IQLHIP_OK;
+  });
+}
+
+// What every window call checks, before a launch and before anything is allocated.
+static int var_check_window(const iqlhip_var* s, const float* rows_dev, int64_t ld, int64_t size, int32_t state_dim,
+                            int32_t action_dim, int32_t B) {
+  if (!s || !rows_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (state_dim != s->S) return fail(IQLHIP_EINVAL, "state_dim = %d, the handle's is %d", state_dim, s->S);
+  if (action_dim < 1) return fail(IQLHIP_EINVAL, "action_dim must be >= 1");
+  if (B < 1 || B > s->max_rows) return fail(IQLHIP_EINVAL, "B = %d outside [1, max_rows = %d]", B, s->max_rows);
+  if (size < B) return fail(IQLHIP_EINVAL, "the buffer holds %lld rows, a window takes B = %d", (long long)size, B);
+  if (ld < iqlhip_row_stride(state_dim, action_dim))
+    return fail(IQLHIP_EINVAL, "ld = %lld below iqlhip_row_stride = %lld", (long long)ld, (long long)iqlhip_row_stride(state_dim, action_dim));
+  if ((uintptr_t)rows_dev & 3) return fail(IQLHIP_EINVAL, "rows must be 4-byte aligned");
+  return IQLHIP_OK;
+}
+
+static VarPackParams var_pack_params(const iqlhip_var* s, const float* rows_dev, int64_t ld, int64_t size, int32_t action_dim,
+                                     int32_t B, float* out) {
+  VarPackParams p{};
+  p.rows = rows_dev; p.ld = ld; p.last_start = size - B; p.S = s->S; p.A = action_dim; p.B = B; p.out = out;
+  return p;
+}
+static unsigned var_pack_blocks(int S, int B) { return (unsigned)((B + 1) * (S + 2) + 255) / 256u; }
+
+extern "C" int iqlhip_var_pack_window(iqlhip_var* s, const float* rows_dev, int64_t ld, int64_t n_rows, int32_t state_dim,
+                                      int32_t action_dim, int64_t start, int32_t B, float* block_out_dev, void* stream) {
+  if (int rc = var_check_window(s, rows_dev, ld, n_rows, state_dim, action_dim, B)) return rc;
+  if (!block_out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (start < 0 || start > n_rows - B) return fail(IQLHIP_EINVAL, "rows %lld .. %lld outside the buffer's %lld", (long long)start,
+                                                   (long long)start + B - 1, (long long)n_rows);
+  if ((uintptr_t)block_out_dev & 3) return fail(IQLHIP_EINVAL, "the packed block must be 4-byte aligned");
+  DevGuard guard(s->device);
+  VarPackParams p = var_pack_params(s, rows_dev, ld, n_rows, action_dim, B, block_out_dev);
+  p.start = start;
+  hipLaunchKernelGGL(iql_var_pack_window_kernel<false>, dim3(var_pack_blocks(s->S, B)), dim3(256), 0, (hipStream_t)stream, p);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_values_window(iqlhip_var* s, const float* rows_dev, int64_t ld, int64_t n_rows, int32_t state_dim,
+                                        int32_t action_dim, int64_t start, int32_t B, int32_t aligned_rewards, float* out_dev,
+                                        void* stream) {
+  if (int rc = var_check_window(s, rows_dev, ld, n_rows, state_dim, action_dim, B)) return rc;
+  if (start < 0 || start > n_rows - B) return fail(IQLHIP_EINVAL, "rows %lld .. %lld outside the buffer's %lld", (long long)start,
+                                                   (long long)start + B - 1, (long long)n_rows);
+  if (int rc = var_check_call(s, rows_dev, B, -1, false, aligned_rewards)) return rc;
+  if (!out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  DevGuard guard(s->device);
+  if (int rc = var_window_scratch(s)) return rc;
+  VarPackParams p = var_pack_params(s, rows_dev, ld, n_rows, action_dim, B, s->wblk);
+  p.start = start;
+  hipLaunchKernelGGL(iql_var_pack_window_kernel<false>, dim3(var_pack_blocks(s->S, B)), dim3(256), 0, (hipStream_t)stream, p);
+  var_launch(s, s->wblk, B, -1, aligned_rewards, out_dev, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_train_steps(iqlhip_var* s, const float* rows_dev, int64_t ld, int64_t size, int32_t action_dim, int32_t B,
+                                      int32_t n_steps, int32_t which_net, const iqlhip_var_scalars* scalars, uint64_t seed,
+                                      uint64_t stream_offset, const int64_t* starts_dev, int64_t n_starts, void* stream) {
+  if (!s || !scalars) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (int rc = var_check_window(s, rows_dev, ld, size, s->S, action_dim, B)) return rc;
+  if (n_steps < 1 || n_steps > IQLHIP_VAR_TRAIN_MAX_STEPS)
+    return fail(IQLHIP_EINVAL, "n_steps = %d outside [1, %d]", n_steps, IQLHIP_VAR_TRAIN_MAX_STEPS);
+  if (starts_dev && n_starts < 1) return fail(IQLHIP_EINVAL, "a starts list needs n_starts >= 1, got %lld", (long long)n_starts);
+  if ((uintptr_t)starts_dev & 7) return fail(IQLHIP_EINVAL, "the starts list must be 8-byte aligned");
+  for (int k = 0; k < n_steps; ++k)
+    if (scalars[k].aligned_rewards != scalars[0].aligned_rewards) return fail(IQLHIP_EINVAL, "aligned_rewards differs inside a call");
+  if (int rc = var_check_call(s, rows_dev, B, which_net, true, scalars[0].aligned_rewards)) return rc;
+  DevGuard guard(s->device);
+  if (int rc = var_window_scratch(s)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  VarPackParams p = var_pack_params(s, rows_dev, ld, size, action_dim, B, s->wblk);
+  p.seed = seed;
+  p.span = starts_dev ? (unsigned long long)n_starts : (unsigned long long)(size - B + 1);
+  p.starts = (const long long*)starts_dev;
+  const unsigned blocks = var_pack_blocks(s->S, B);
+  for (int k = 0; k < n_steps; ++k) {
+    p.j = stream_offset + (uint64_t)k;
+    p.start_out = s->start_ring + k;
+    hipLaunchKernelGGL(iql_var_pack_window_kernel<true>, dim3(blocks), dim3(256), 0, st, p);
+    var_launch(s, s->wblk, B, which_net, scalars[k].aligned_rewards, nullptr, st, s->wvals, s->loss_ring + k);
+    var_launch_adam(s, which_net, &scalars[k], st);
+  }
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_read_train_ring(iqlhip_var* s, float* losses_out, int64_t* starts_out, int32_t n_steps, void* stream) {
+  if (!s || !losses_out || !starts_out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n_steps < 1 || n_steps > IQLHIP_VAR_TRAIN_MAX_STEPS)
+    return fail(IQLHIP_EINVAL, "n_steps = %d outside [1, %d]", n_steps, IQLHIP_VAR_TRAIN_MAX_STEPS);
+  if (!s->loss_ring) return fail(IQLHIP_EINVAL, "iqlhip_var_train_steps has not been called");
+  DevGuard guard(s->device);
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  memcpy(losses_out, s->loss_ring, (size_t)n_steps * sizeof(float));
+  memcpy(starts_out, s->start_ring, (size_t)n_steps * sizeof(int64_t));
   return IQLHIP_OK;
 }

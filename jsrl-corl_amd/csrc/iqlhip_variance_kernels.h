@@ -13,6 +13,8 @@
 //                         layer-0 units over all rows and from it dW0 / db0, block 32 dW2, db1, db2.  Every sum runs
 //                         over the rows in a fixed order inside one wave or one thread: no atomics
 //   iql_var_adam_kernel   torch's Adam on the net's segment of the arena (iql_update_kernel's operation order)
+//   iql_var_pack_window_kernel   the packed block from B consecutive rows of a packed replay buffer, the start row an
+//                         argument or drawn in the kernel (iqlhip_var_train_steps; DESIGN.md 6l "From a replay buffer")
 //
 // The kernels are templates of one unused parameter and read neither gridDim nor blockDim, as the scoring group kernels
 // (iqlhip_score_kernels.h: why): they are emitted behind every other kernel of the code object.
@@ -317,4 +319,46 @@ template <int = 0> __global__ __launch_bounds__(256) void iql_var_adam_kernel(fl
   m[i] = mk;
   v[i] = vk;
   pw[i] = fmaf(step_neg, mk / denom, pw[i]);
+}
+
+// ---------------------------------------------------------------------------
+struct VarPackParams {
+  const float* rows;             // packed replay rows [s | a | s' | r | d | pad] of stride ld
+  long long ld;
+  long long start;               // the window's first row (the eager form)
+  long long last_start;          // size - B: the largest start whose window stays inside the buffer
+  unsigned long long seed, j;    // DRAWN: index j of the index stream under `seed` at counter offset 0
+  unsigned long long span;       // DRAWN: size - B + 1 values, or the length of `starts`
+  const long long* starts;       // DRAWN: a list the draw indexes, or null
+  long long* start_out;          // DRAWN: this update's word of the start ring
+  int S, A, B;
+  float* out;                    // the packed block: [B][S] states | [S] last next-state | [B] rewards | [B] next-dones
+};
+
+// Thread e = (t, c) of (B + 1) x (S + 2): t < B copies column c of row start + t — c < S a state word, c = S the reward,
+// c = S + 1 the done flag (the buffer stores real_done: run_episodes' next_dones) —, t = B copies word c < S of the
+// last row's next-state.  Consecutive lanes read consecutive words of a row.  Row offsets are 64-bit: start * ld floats
+// passes 2^31 and 2^32 bytes on a 10 M-row buffer.  DRAWN: every thread draws the start itself (draw_index, as
+// gather_rows_drawn: ~150 ALU instructions instead of a dependent load); an entry of `starts` is clamped into
+// [0, last_start], so that no list can send a read outside the buffer.
+template <bool DRAWN> __global__ __launch_bounds__(256) void iql_var_pack_window_kernel(VarPackParams p) {
+  const int S = p.S, B = p.B, W = S + 2;
+  const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;      // (B + 1) * W <= 1025 * 129
+  if (e >= (B + 1) * W) return;
+  long long start = p.start;
+  if (DRAWN) {
+    start = draw_index(p.seed, 0ull, p.j, p.span);
+    if (p.starts) start = min(max(p.starts[start], 0ll), p.last_start);
+    if (e == 0) *p.start_out = start;
+  }
+  const int t = e / W, c = e - t * W;
+  const int r = 2 * S + p.A;
+  if (t < B) {
+    const float* row = p.rows + (start + (long long)t) * p.ld;
+    if (c < S) p.out[t * S + c] = row[c];
+    else if (c == S) p.out[(B + 1) * S + t] = row[r];
+    else p.out[(B + 1) * S + B + t] = row[r + 1];
+  } else if (c < S) {
+    p.out[B * S + c] = p.rows[(start + (long long)(B - 1)) * p.ld + (S + p.A + c)];
+  }
 }

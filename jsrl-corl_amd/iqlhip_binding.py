@@ -32,6 +32,7 @@ IQLHIP_GROUP_ACT_WAIT = 1     # iqlhip_group_actor_forward: return once the acti
 IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train with actor dropout
 IQLHIP_GROUP_MAX_STEPS = 1024  # steps per iqlhip_group_train_steps call
 IQLHIP_GROUP_TS_CONTINUE = 1   # iqlhip_group_train_steps_weighted_is / _prioritized: go on with the previous call's staged rows
+IQLHIP_VAR_TRAIN_MAX_STEPS = 1024  # updates per iqlhip_var_train_steps call (the rings' length)
 IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
 XCH_NONE, XCH_RCCL, XCH_P2P = 0, 1, 2
@@ -294,6 +295,14 @@ SYMBOLS = [
     ("iqlhip_var_forward_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_void_p]),
     ("iqlhip_var_read_loss", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
+    ("iqlhip_var_pack_window", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                         C.c_int32, C.c_void_p, C.c_void_p]),
+    ("iqlhip_var_values_window", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("iqlhip_var_train_steps", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.POINTER(VarScalars), C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64,
+                                         C.c_void_p]),
+    ("iqlhip_var_read_train_ring", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -6,7 +6,12 @@ The step is the reference's as written, quirks included: sampled values use rewa
 `aligned_rewards=True` is this project's opt-in for rewards[t]), the bootstrap value keeps its gradient, `actions` and
 `dones` are unused, of `next_observations` only the last row is.  Not ported: StateActionVarianceLearner (its get_values
 cannot run in the reference) and test_model (mismatched signatures, plotting).  There is no CPU fall-back: a learner on a
-CPU device holds its networks and optimizers, and raises when asked to step."""
+CPU device holds its networks and optimizers, and raises when asked to step.
+
+Beyond the reference: B consecutive rows of a GPU ReplayBuffer are a rollout (a dataset is stored in trajectory order,
+an online ring fills in time order), so pack_window / update_from_buffer / get_values_window build the packed block with
+one launch instead of the host, and train_on_buffer / run_training_on_buffer queue whole bursts of updates whose
+windows are drawn on the device (DESIGN.md 6l "From a replay buffer")."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,6 +27,7 @@ from iqlhip_networks import MLP, linear_layers
 
 GAMMA = 0.99
 VAR_MAX_ROWS = 1024           # rows of one step (csrc/iqlhip_variance_kernels.h)
+TRAIN_MAX_STEPS = hb.IQLHIP_VAR_TRAIN_MAX_STEPS      # updates per library call of train_on_buffer (the rings' length)
 NET_MF, NET_VF = 0, 1
 SAVE_DIR = "jsrl-CORL/algorithms/finetune/var_functions"      # the reference's save path
 _KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
@@ -278,6 +284,10 @@ class VarianceLearner:
         lr, betas, eps = self._adam_hyper(self._nets()[k][1])
         self._need_gpu()
         B = self._upload(observations, rewards, next_observations, next_dones)
+        return self._step_block(B, k, lr, betas, eps)
+
+    def _step_block(self, B: int, k: int, lr, betas, eps) -> dict:
+        """The library step of net k on the packed block in self._blk, its read-back and _update_v's dict."""
         t = self._adam_t[k] + 1
         sc = adam_scalars(lr, betas, eps, t, self.aligned_rewards)
         with torch.cuda.device(self._dev):
@@ -298,6 +308,135 @@ class VarianceLearner:
                                                 self._stream()))
         out = out.cpu()
         return out[0], out[1], out[2]
+
+    # ------------------------------------------------------------------ from a replay buffer
+    def _window_source(self, buffer):
+        """(rows address, ld, size, action_dim) of a GPU replay buffer whose rows this learner may read as windows."""
+        if self._h is None:
+            raise NotImplementedError("iqlhip: the variance learner reads replay-buffer windows on the GPU only "
+                                      "(device='cuda'); there is no CPU fall-back")
+        rows = buffer._rows
+        if rows.device != self._dev:
+            raise ValueError(f"iqlhip: the replay buffer lives on {rows.device}, the variance learner on {self._dev}")
+        if int(buffer._state_dim) != int(self.state_dim):
+            raise ValueError(f"iqlhip: the replay buffer's state_dim is {buffer._state_dim}, the learner's {self.state_dim}")
+        return rows.data_ptr(), int(buffer._ld), int(buffer._size), int(buffer._action_dim)
+
+    def pack_window(self, buffer, start: int) -> torch.Tensor:
+        """The packed block (pack_block's layout) of the batch_size consecutive rows of `buffer` from row `start`, as a
+        device tensor: one launch, nothing downloaded.  0 <= start <= size - batch_size, size the rows the buffer holds;
+        a window does not wrap."""
+        ptr, ld, size, A = self._window_source(buffer)
+        B, S = int(self.batch_size), int(self.state_dim)
+        out = torch.empty(B * S + S + 2 * B, dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            hb.check(hb.lib().iqlhip_var_pack_window(self._h, ptr, ld, size, S, A, int(start), B, out.data_ptr(), self._stream()))
+        return out
+
+    def update_from_buffer(self, buffer, start: int, update_vf) -> dict:
+        """_update_v on the window of `buffer` that starts at row `start`: one pack launch, the step, one
+        synchronisation.  Bit for bit _update_v on the same rows downloaded."""
+        k = NET_VF if update_vf else NET_MF
+        lr, betas, eps = self._adam_hyper(self._nets()[k][1])
+        ptr, ld, size, A = self._window_source(buffer)
+        B = int(self.batch_size)
+        with torch.cuda.device(self._dev):
+            hb.check(hb.lib().iqlhip_var_pack_window(self._h, ptr, ld, size, int(self.state_dim), A, int(start), B,
+                                                     self._blk.data_ptr(), self._stream()))
+        return self._step_block(B, k, lr, betas, eps)
+
+    def get_values_window(self, buffer, start: int):
+        """get_values on the window of `buffer` that starts at row `start`: (values_samp, values_pred, variance_pred)."""
+        ptr, ld, size, A = self._window_source(buffer)
+        B = int(self.batch_size)
+        out = torch.empty((3, B), dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            hb.check(hb.lib().iqlhip_var_values_window(self._h, ptr, ld, size, int(self.state_dim), A, int(start), B,
+                                                       int(self.aligned_rewards), out.data_ptr(), self._stream()))
+        out = out.cpu()
+        return out[0], out[1], out[2]
+
+    def _window_starts(self, starts, last_start: int):
+        """starts= of train_on_buffer as an int64 device tensor, every entry checked once to lie in [0, last_start]."""
+        if isinstance(starts, np.ndarray):
+            starts = torch.from_numpy(np.ascontiguousarray(starts))
+        if not isinstance(starts, torch.Tensor) or starts.dtype != torch.int64:
+            raise ValueError("iqlhip: starts must be an int64 tensor or array")
+        t = starts.reshape(-1).to(self._dev).contiguous()
+        if t.numel() < 1:
+            raise ValueError("iqlhip: starts is empty")
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi > last_start:
+            raise ValueError(f"iqlhip: starts must lie in [0, size - batch_size = {last_start}], got {lo} .. {hi}")
+        return t
+
+    def train_on_buffer(self, buffer, n_updates: int, seed: int, offset: int = 0, update_vf=False, starts=None) -> dict:
+        """n_updates updates of mf (or vf) on windows of `buffer`, drawn and packed on the device: five launches per
+        update, no host work between updates, one synchronisation per TRAIN_MAX_STEPS updates.  Update k takes the
+        window whose start is index offset + k of iqlhip_draw_indices' stream under `seed` (counter offset 0) over
+        size - batch_size + 1 values — or, with starts= (an int64 tensor or array, checked once), that index of the
+        stream over len(starts) picks the entry.  Update k depends on offset + k alone, so neither the split into
+        library calls nor a split into several train_on_buffer calls changes a result.  Returns {"losses": float32 [n],
+        "starts": int64 [n]}, the windows used.
+
+        `size` is the number of rows the buffer holds.  In a ring that has wrapped, the window that straddles the write
+        pointer is not consecutive in time: pass starts= to exclude it — the first rows of
+        buffer.episode_returns(...).episode_table() make windows begin at episode starts, as run_episodes' rollouts do."""
+        k = NET_VF if update_vf else NET_MF
+        lr, betas, eps = self._adam_hyper(self._nets()[k][1])
+        ptr, ld, size, A = self._window_source(buffer)
+        B, n = int(self.batch_size), int(n_updates)
+        if n < 1:
+            raise ValueError(f"iqlhip: n_updates must be >= 1, got {n_updates}")
+        if size < B:
+            raise ValueError(f"iqlhip: the replay buffer holds {size} rows, a window takes batch_size = {B}")
+        st = None if starts is None else self._window_starts(starts, size - B)
+        st_ptr, n_st = (None, 0) if st is None else (st.data_ptr(), st.numel())
+        losses, used = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int64)
+        m64 = (1 << 64) - 1
+        with torch.cuda.device(self._dev):
+            done = 0
+            while done < n:
+                m = min(TRAIN_MAX_STEPS, n - done)
+                t0 = self._adam_t[k]
+                sc = (hb.VarScalars * m)(*[adam_scalars(lr, betas, eps, t0 + i + 1, self.aligned_rewards) for i in range(m)])
+                hb.check(hb.lib().iqlhip_var_train_steps(self._h, ptr, ld, size, A, B, m, k, sc, int(seed) & m64,
+                                                         (int(offset) + done) & m64, st_ptr, n_st, self._stream()))
+                self._adam_t[k] = t0 + m
+                hb.check(hb.lib().iqlhip_var_read_train_ring(self._h, losses[done:].ctypes.data_as(C.POINTER(C.c_float)),
+                                                             used[done:].ctypes.data_as(C.POINTER(C.c_int64)), m, self._stream()))
+                done += m
+        self._sync_opt_state(k)
+        return {"losses": losses, "starts": used}
+
+    def run_training_on_buffer(self, buffer, n_updates=10000, seed=0, save_dir=SAVE_DIR, env_name="buffer", starts=None):
+        """run_training with windows of a replay buffer in place of rollouts: mf is stepped for the updates
+        n <= n_updates / 2 and vf for the rest (the reference's `n > n_updates / 2`), as two train_on_buffer bursts on one
+        start stream (update n uses index n).  Every 100th update's loss is printed; all losses and starts are kept in
+        self.buffer_log.  Saves run_training's files (`<env_name>_<guide|None>_<n_updates>_<frac>_{vf,mf}.pt`) unless
+        save_dir is None; returns self.vf in eval mode, and mf is deleted."""
+        n_updates = int(n_updates)
+        n_mf = min(n_updates, n_updates // 2 + 1)          # the n in [0, n_updates) with n <= n_updates / 2
+        logs = []
+        if n_mf:
+            logs.append(self.train_on_buffer(buffer, n_mf, seed, 0, False, starts))
+        if n_updates - n_mf:
+            logs.append(self.train_on_buffer(buffer, n_updates - n_mf, seed, n_mf, True, starts))
+        self.buffer_log = {key: np.concatenate([l[key] for l in logs]) if logs else np.empty(0) for key in ("losses", "starts")}
+        for n in range(0, n_updates, 100):
+            print(f"Iteration {n}/{n_updates}:\nvalue_loss: {float(self.buffer_log['losses'][n])}")
+        self.mf.eval()
+        self.vf.eval()
+        if save_dir is not None:
+            os.makedirs(save_dir, exist_ok=True)
+            actor_name = "guide" if self.actor is not None else None
+            frac = getattr(self.config, "variance_learn_frac", 0.0)
+            stem = f"{save_dir}/{env_name}_{actor_name}_{n_updates}_{str(frac).replace('.', '-')}"
+            cpu = lambda m: {k: v.detach().cpu() for k, v in m.state_dict().items()}
+            torch.save(cpu(self.vf), stem + "_vf.pt")
+            torch.save(cpu(self.mf), stem + "_mf.pt")
+        del self.mf
+        return self.vf
 
     def flat_gradient(self, batch, update_vf):
         """Tests: (loss, the flat gradient of mf or vf in arena order) of one batch, nothing updated."""

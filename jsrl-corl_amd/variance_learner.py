@@ -1,7 +1,10 @@
 """Drop-in for the reference's variance_learner.py (jsrl_utils.py:15 imports StateDepFunction and VarianceLearner from
 it): the implementation is iqlhip_variance.py, whose gradient step runs on the GPU.  StateActionVarianceLearner and
-test_model are not ported (iqlhip_variance.py: why)."""
-from iqlhip_variance import (GAMMA, StateDepFunction, VarianceLearner, mse_loss, nll_loss, run_episodes,  # noqa: F401
-                             to_tensor)
+test_model are not ported (iqlhip_variance.py: why).  Beyond the reference's surface, VarianceLearner trains from a
+GPU replay buffer (pack_window, update_from_buffer, get_values_window, train_on_buffer, run_training_on_buffer;
+TRAIN_MAX_STEPS updates per library call)."""
+from iqlhip_variance import (GAMMA, TRAIN_MAX_STEPS, StateDepFunction, VarianceLearner, mse_loss, nll_loss,  # noqa: F401
+                             pack_block, run_episodes, to_tensor)
 
-__all__ = ["GAMMA", "StateDepFunction", "VarianceLearner", "mse_loss", "nll_loss", "run_episodes", "to_tensor"]
+__all__ = ["GAMMA", "TRAIN_MAX_STEPS", "StateDepFunction", "VarianceLearner", "mse_loss", "nll_loss", "pack_block",
+           "run_episodes", "to_tensor"]
