@@ -1104,6 +1104,57 @@ int iqlhip_var_train_steps(iqlhip_var* var, const float* rows_dev, int64_t ld, i
  * iqlhip_var_train_steps call. */
 int iqlhip_var_read_train_ring(iqlhip_var* var, float* losses_out, int64_t* starts_out, int32_t n_steps, void* stream);
 
+/* ---- groups of variance learners (DESIGN.md 6l "Groups of learners") ----
+ * K <= IQLHIP_MAX_GROUP bound iqlhip_var handles of one state_dim on one device, updated by one set of launches: every
+ * launch of an update covers all members, a member's arithmetic is the solo call's (no sum crosses a member), and its
+ * result is the solo call's bit for bit.  The group owns its launch records, the scalar table and K loss / start rings;
+ * a member keeps its arenas, scratch and landing words, and may be stepped by the solo calls before and after a group
+ * call (the group's records are written anew by every call).  Destroy the group before its members.
+ *
+ * Arguments with [K] are host arrays with one entry per member, in member order.  B and which_net are per call, the
+ * same for every member.  Refused before any launch, with nothing changed (IQLHIP_EINVAL): NULL, K outside
+ * [1, IQLHIP_MAX_GROUP], a member named twice, members of different state_dim or on different devices (create); and
+ * whatever the solo call of the same name refuses, for any member — the message then starts with "member <i>: ". */
+typedef struct iqlhip_var_group iqlhip_var_group;
+int iqlhip_var_group_create(iqlhip_var* const* members, int k, iqlhip_var_group** out);
+int iqlhip_var_group_destroy(iqlhip_var_group* group);
+/* iqlhip_var_step for every member: blocks_dev[K] packed device blocks of B rows, scalars[K].  One host-to-device copy
+ * of the records and scalars, then four launches.  A member's loss and samp | pred | var land in its own host-mapped
+ * words: iqlhip_var_group_read_loss (or the member's iqlhip_var_read_loss) reads them. */
+int iqlhip_var_group_step(iqlhip_var_group* group, const float* const* blocks_dev, int32_t B, int32_t which_net,
+                          const iqlhip_var_scalars* scalars, void* stream);
+/* iqlhip_var_values for every member: samp | pred | var into outs_dev[i] [3][B]. */
+int iqlhip_var_group_values(iqlhip_var_group* group, const float* const* blocks_dev, int32_t B, const int32_t* aligned_rewards,
+                            float* const* outs_dev, void* stream);
+/* Waits for `stream` once; then every member's loss into losses[K] and, when heads is not NULL, the first n_head
+ * entries of its samp, pred and var into heads[K][3][n_head]. */
+int iqlhip_var_group_read_loss(iqlhip_var_group* group, float* losses, float* heads, int32_t n_head, void* stream);
+/* The window forms (iqlhip_var_pack_window, the step and iqlhip_var_values_window on it): member i reads the window at
+ * start[i] of the buffer rows_dev[i] (ld[i], size[i] rows, action_dim[i]); rows_dev may name one buffer K times or K
+ * buffers.  One launch packs every member's window (into blocks_out_dev[i], or the member's scratch). */
+int iqlhip_var_group_pack_windows(iqlhip_var_group* group, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                  const int32_t* action_dim, const int64_t* start, int32_t B, float* const* blocks_out_dev,
+                                  void* stream);
+int iqlhip_var_group_step_windows(iqlhip_var_group* group, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                  const int32_t* action_dim, const int64_t* start, int32_t B, int32_t which_net,
+                                  const iqlhip_var_scalars* scalars, void* stream);
+int iqlhip_var_group_values_windows(iqlhip_var_group* group, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                    const int32_t* action_dim, const int64_t* start, int32_t B, const int32_t* aligned_rewards,
+                                    float* const* outs_dev, void* stream);
+/* iqlhip_var_train_steps for every member: n_steps x five group launches queued on `stream`, no synchronisation and no
+ * host work between them.  scalars[n_steps][K] (update-major) travel with the records in one host-to-device copy before
+ * the first launch; the kernels index the table by the update number.  Member i draws update s's start from index
+ * stream_offsets[i] + s of the stream under seeds[i] — over size[i] - B + 1 values, or, where starts_dev[i] is not NULL,
+ * over its n_starts[i] entries (entries of starts_dev may be NULL: that member draws from the whole buffer). */
+int iqlhip_var_group_train_steps(iqlhip_var_group* group, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                 const int32_t* action_dim, int32_t B, int32_t n_steps, int32_t which_net,
+                                 const iqlhip_var_scalars* scalars, const uint64_t* seeds, const uint64_t* stream_offsets,
+                                 const int64_t* const* starts_dev, const int64_t* n_starts, void* stream);
+/* Waits for `stream`; then the first n_steps words of every member's loss ring and start ring of the last
+ * iqlhip_var_group_train_steps call: losses_out[K][n_steps], starts_out[K][n_steps]. */
+int iqlhip_var_group_read_train_ring(iqlhip_var_group* group, float* losses_out, int64_t* starts_out, int32_t n_steps,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5686,28 +5686,42 @@ static int var_check_call(const iqlhip_var* s, const float* batch_dev, int32_t B
   return IQLHIP_OK;
 }
 
-// forward + row kernel (which = -1: values only), then the backward of `which` into s->grad
-// (vals / loss: where the row kernel leaves samp | pred | var and the loss; null: the handle's host-mapped landing words)
-static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, int aligned, float* vals2, hipStream_t st,
-                       float* vals = nullptr, float* loss = nullptr) {
-  const int S = s->S;
+// The three launches' arguments (the solo launches pass them by value, a learner group writes them into its records).
+// vals / loss: where the row kernel leaves samp | pred | var and the loss; null: the handle's host-mapped landing words
+static VarFwdParams var_fwd_params(const iqlhip_var* s, const float* batch_dev, int B, int which) {
   VarFwdParams f{};
   f.net[0] = var_net_ptrs(s, 0); f.net[1] = var_net_ptrs(s, 1);
-  f.x = batch_dev; f.S = S; f.rows0 = B + 1; f.rows1 = B; f.keep = which;
+  f.x = batch_dev; f.S = s->S; f.rows0 = B + 1; f.rows1 = B; f.keep = which;
   f.h0 = s->h0; f.h1 = s->h1; f.out = s->out;
-  hipLaunchKernelGGL(iql_var_fwd_kernel<>, dim3((unsigned)(B + 1 + 31) / 32u, 2), dim3(256), 0, st, f);
+  return f;
+}
+static VarRowParams var_row_params(const iqlhip_var* s, const float* batch_dev, int B, int which, int aligned, float* vals2,
+                                   float* vals, float* loss) {
   VarRowParams r{};
-  r.out = s->out; r.rew = batch_dev + (size_t)(B + 1) * S; r.nd = r.rew + B; r.B = B; r.which = which; r.aligned = aligned;
+  r.out = s->out; r.rew = batch_dev + (size_t)(B + 1) * s->S; r.nd = r.rew + B; r.B = B; r.which = which; r.aligned = aligned;
   r.vals = vals ? vals : s->land + 4; r.vals2 = vals2; r.dy = s->dy; r.loss = loss ? loss : s->land;
-  hipLaunchKernelGGL(iql_var_row_kernel<>, dim3(1), dim3(256), 0, st, r);
-  if (which < 0) return;
+  return r;
+}
+static VarBwdParams var_bwd_params(const iqlhip_var* s, const float* batch_dev, int B, int which) {
   const iqlhip_net_layout& l = s->L[which];
   VarBwdParams b{};
-  b.np = var_net_ptrs(s, which); b.x = batch_dev; b.S = S; b.n = which == 0 ? B + 1 : B;
+  b.np = var_net_ptrs(s, which); b.x = batch_dev; b.S = s->S; b.n = which == 0 ? B + 1 : B;
   b.h0 = s->h0; b.h1 = s->h1; b.dy = s->dy; b.dh0 = s->dh0; b.grad = s->grad;
   const int64_t sb = l.seg_begin;
   b.g_w1 = (unsigned)(l.w1 - sb); b.g_w0 = (unsigned)(l.w0 - sb); b.g_b0 = (unsigned)(l.b0 - sb);
   b.g_b1 = (unsigned)(l.b1 - sb); b.g_w2 = (unsigned)(l.w2 - sb); b.g_b2 = (unsigned)(l.b2 - sb);
+  return b;
+}
+
+// forward + row kernel (which = -1: values only), then the backward of `which` into s->grad
+static void var_launch(iqlhip_var* s, const float* batch_dev, int B, int which, int aligned, float* vals2, hipStream_t st,
+                       float* vals = nullptr, float* loss = nullptr) {
+  const VarFwdParams f = var_fwd_params(s, batch_dev, B, which);
+  hipLaunchKernelGGL(iql_var_fwd_kernel<>, dim3((unsigned)(B + 1 + 31) / 32u, 2), dim3(256), 0, st, f);
+  const VarRowParams r = var_row_params(s, batch_dev, B, which, aligned, vals2, vals, loss);
+  hipLaunchKernelGGL(iql_var_row_kernel<>, dim3(1), dim3(256), 0, st, r);
+  if (which < 0) return;
+  const VarBwdParams b = var_bwd_params(s, batch_dev, B, which);
   hipLaunchKernelGGL(iql_var_bwd_kernel<>, dim3(VAR_BWD_BLOCKS), dim3(256), 0, st, b);
 }
 
@@ -5872,5 +5886,311 @@ extern "C" int iqlhip_var_read_train_ring(iqlhip_var* s, float* losses_out, int6
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   memcpy(losses_out, s->loss_ring, (size_t)n_steps * sizeof(float));
   memcpy(starts_out, s->start_ring, (size_t)n_steps * sizeof(int64_t));
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Groups of variance learners (include/iqlhip.h "groups of variance learners"; DESIGN.md 6l "Groups of learners";
+// kernels: iqlhip_variance_group_kernels.h, behind the solo kernels in the code object).  K bound iqlhip_var handles of
+// one state_dim on one device, every launch of an update covering all of them.  The group owns the record table, the
+// scalar table behind it (one staging, ONE host-to-device copy per call) and the K loss / start rings; a member keeps
+// its arenas, its scratch and its landing words, and stays a solo handle.  Records are written anew by every call from
+// what the members hold then, so nothing a solo call does in between can make them stale.
+#include "iqlhip_variance_group_kernels.h"
+
+struct iqlhip_var_group {
+  int k = 0, device = 0, S = 0;
+  iqlhip_var* m[IQLHIP_MAX_GROUP] = {};
+  Owned own;
+  Staging stg;
+  Section<VarGroupRec> recs; Section<iqlhip_var_scalars> tab;      // tab [IQLHIP_VAR_TRAIN_MAX_STEPS][k], the staging's last
+  hipEvent_t up_done = nullptr;       // the last upload has read stg.pin
+  bool up_pending = false;
+  float* loss_ring = nullptr;         // pinned, host-mapped [k][IQLHIP_VAR_TRAIN_MAX_STEPS]
+  long long* start_ring = nullptr;
+};
+
+// rc of a member's check with the member named in front of the message
+static int var_member_fail(int rc, int i) {
+  const std::string msg = g_err;
+  return fail(rc, "member %d: %s", i, msg.c_str());
+}
+
+extern "C" int iqlhip_var_group_destroy(iqlhip_var_group* g) {
+  if (!g) return IQLHIP_OK;
+  {
+    DevGuard guard(g->device);
+    (void)hipDeviceSynchronize();
+    g->own.release_all();
+  }
+  delete g;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_group_create(iqlhip_var* const* members, int k, iqlhip_var_group** out) {
+  if (!out) return fail(IQLHIP_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!members) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (k < 1 || k > IQLHIP_MAX_GROUP) return fail(IQLHIP_EINVAL, "k = %d outside [1, %d]", k, IQLHIP_MAX_GROUP);
+  for (int i = 0; i < k; ++i) {
+    if (!members[i]) return fail(IQLHIP_EINVAL, "member %d: NULL handle", i);
+    for (int j = 0; j < i; ++j)
+      if (members[j] == members[i]) return fail(IQLHIP_EINVAL, "member %d: the handle is member %d too", i, j);
+    if (members[i]->S != members[0]->S)
+      return fail(IQLHIP_EINVAL, "member %d: state_dim = %d, member 0's is %d", i, members[i]->S, members[0]->S);
+    if (members[i]->device != members[0]->device)
+      return fail(IQLHIP_EINVAL, "member %d: device %d, member 0's is %d", i, members[i]->device, members[0]->device);
+  }
+  std::unique_ptr<iqlhip_var_group> g(new iqlhip_var_group);
+  g->k = k; g->device = members[0]->device; g->S = members[0]->S;
+  for (int i = 0; i < k; ++i) g->m[i] = members[i];
+  DevGuard guard(g->device);
+  g->recs = g->stg.add<VarGroupRec>(k);
+  g->tab = g->stg.add<iqlhip_var_scalars>((size_t)k * IQLHIP_VAR_TRAIN_MAX_STEPS);
+  if (int rc = g->stg.alloc(g->own)) return rc;
+  HIPCHK(g->own.pin(&g->loss_ring, (size_t)k * IQLHIP_VAR_TRAIN_MAX_STEPS * sizeof(float), /*zero=*/true));
+  HIPCHK(g->own.pin(&g->start_ring, (size_t)k * IQLHIP_VAR_TRAIN_MAX_STEPS * sizeof(long long), /*zero=*/true));
+  HIPCHK(g->own.event(&g->up_done, hipEventDisableTiming));
+  *out = g.release();
+  return IQLHIP_OK;
+}
+
+// What a call asks of every member's window, with the solo calls' checks and messages (start: null for a burst).
+struct VarGroupWin { const float* const* rows; const int64_t* ld; const int64_t* size; const int32_t* action_dim; const int64_t* start; };
+static int var_group_check_windows(const iqlhip_var_group* g, const VarGroupWin& w, int32_t B) {
+  if (!g || !w.rows || !w.ld || !w.size || !w.action_dim) return fail(IQLHIP_EINVAL, "NULL argument");
+  for (int i = 0; i < g->k; ++i) {
+    if (int rc = var_check_window(g->m[i], w.rows[i], w.ld[i], w.size[i], g->S, w.action_dim[i], B)) return var_member_fail(rc, i);
+    if (!g->m[i]->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_var_bind has not been called", i);
+    if (w.start && (w.start[i] < 0 || w.start[i] > w.size[i] - B))
+      return fail(IQLHIP_EINVAL, "member %d: rows %lld .. %lld outside the buffer's %lld", i, (long long)w.start[i],
+                  (long long)w.start[i] + B - 1, (long long)w.size[i]);
+  }
+  return IQLHIP_OK;
+}
+static int var_group_check_blocks(const iqlhip_var_group* g, const float* const* blocks_dev, int32_t B, int32_t which, bool need_net,
+                                  const int32_t* aligned, int64_t aligned_stride) {
+  if (!g || !blocks_dev || !aligned) return fail(IQLHIP_EINVAL, "NULL argument");
+  for (int i = 0; i < g->k; ++i)
+    if (int rc = var_check_call(g->m[i], blocks_dev[i], B, which, need_net, aligned[i * aligned_stride])) return var_member_fail(rc, i);
+  return IQLHIP_OK;
+}
+static int var_group_window_scratch(iqlhip_var_group* g) {
+  for (int i = 0; i < g->k; ++i)
+    if (int rc = var_window_scratch(g->m[i])) return var_member_fail(rc, i);
+  return IQLHIP_OK;
+}
+
+// Member i's record of a call: the solo launches' arguments on its block.
+static void var_group_record(iqlhip_var_group* g, int i, const float* blk, int B, int which, int aligned, float* vals2, float* vals,
+                             float* loss) {
+  iqlhip_var* s = g->m[i];
+  VarGroupRec& r = g->stg.host(g->recs)[i];
+  memset(&r, 0, sizeof r);
+  r.f = var_fwd_params(s, blk, B, which);
+  r.r = var_row_params(s, blk, B, which, aligned, vals2, vals, loss);
+  if (which < 0) return;
+  r.b = var_bwd_params(s, blk, B, which);
+  const iqlhip_net_layout& l = s->L[which];
+  r.pw = s->params + l.seg_begin; r.m = s->m + l.seg_begin; r.v = s->v + l.seg_begin;
+  r.n_adam = (int)(l.seg_end - l.seg_begin);
+}
+// ... and of its window: into the member's packed-block scratch, or `out`
+static void var_group_record_pack(iqlhip_var_group* g, int i, const VarGroupWin& w, int B, float* out) {
+  VarPackParams& p = g->stg.host(g->recs)[i].pk;
+  p = var_pack_params(g->m[i], w.rows[i], w.ld[i], w.size[i], w.action_dim[i], B, out);
+  if (w.start) p.start = w.start[i];
+}
+static int var_group_staging_free(iqlhip_var_group* g) {
+  if (g->up_pending) HIPCHK(hipEventSynchronize(g->up_done));
+  g->up_pending = false;
+  return IQLHIP_OK;
+}
+// the records and the first n_steps rows of the scalar table, in one copy
+static int var_group_upload(iqlhip_var_group* g, int n_steps, hipStream_t st) {
+  const size_t bytes = n_steps ? g->tab.off + (size_t)n_steps * g->k * sizeof(iqlhip_var_scalars) : (size_t)g->k * sizeof(VarGroupRec);
+  HIPCHK(hipMemcpyAsync(g->stg.dev, g->stg.pin, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(g->up_done, st));
+  g->up_pending = true;
+  return IQLHIP_OK;
+}
+
+enum VarGroupPack { VG_NO_PACK, VG_PACK_AT, VG_PACK_DRAWN };
+// One update's launches for all members: [pack,] forward, recurrence[, backward, Adam with row `step` of the table].
+static void var_group_launch(const iqlhip_var_group* g, int B, int which, int step, VarGroupPack pack, hipStream_t st) {
+  const int K = g->k, G = (K + 7) / 8;
+  const VarGroupRec* recs = g->stg.device(g->recs);
+  if (pack == VG_PACK_AT)
+    hipLaunchKernelGGL(iql_var_pack_window_group_kernel<false>, dim3(var_group_grid(K, var_pack_blocks(g->S, B))), dim3(256), 0, st,
+                       recs, K, G, step);
+  else if (pack == VG_PACK_DRAWN)
+    hipLaunchKernelGGL(iql_var_pack_window_group_kernel<true>, dim3(var_group_grid(K, var_pack_blocks(g->S, B))), dim3(256), 0, st,
+                       recs, K, G, step);
+  hipLaunchKernelGGL(iql_var_fwd_group_kernel<>, dim3(var_group_grid(K, 2u * ((unsigned)(B + 1 + 31) / 32u))), dim3(256), 0, st, recs, K, G);
+  hipLaunchKernelGGL(iql_var_row_group_kernel<>, dim3(var_group_grid(K, 1)), dim3(256), 0, st, recs, K, G, step);
+  if (which < 0) return;
+  hipLaunchKernelGGL(iql_var_bwd_group_kernel<>, dim3(var_group_grid(K, VAR_BWD_BLOCKS)), dim3(256), 0, st, recs, K, G);
+  const iqlhip_net_layout& l = g->m[0]->L[which];      // (one state_dim: every member's segment has these words)
+  const unsigned nb = (unsigned)((l.seg_end - l.seg_begin + 255) / 256);
+  hipLaunchKernelGGL(iql_var_adam_group_kernel<>, dim3(var_group_grid(K, nb)), dim3(256), 0, st, recs, g->stg.device(g->tab), K, G, step);
+}
+
+// The eager forms: blocks_dev null = every member's window (packed by the first launch into its scratch, or into
+// blocks_out), else K packed blocks.  which = -1: values only.
+static int var_group_eager(iqlhip_var_group* g, const float* const* blocks_dev, const VarGroupWin* w, int32_t B, int32_t which,
+                           const iqlhip_var_scalars* scalars, const int32_t* aligned, float* const* outs_dev, void* stream) {
+  DevGuard guard(g->device);
+  if (w)
+    if (int rc = var_group_window_scratch(g)) return rc;
+  if (int rc = var_group_staging_free(g)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < g->k; ++i) {
+    const float* blk = w ? g->m[i]->wblk : blocks_dev[i];
+    var_group_record(g, i, blk, B, which, scalars ? scalars[i].aligned_rewards : aligned[i], outs_dev ? outs_dev[i] : nullptr, nullptr,
+                     nullptr);
+    if (w) var_group_record_pack(g, i, *w, B, g->m[i]->wblk);
+    if (scalars) g->stg.host(g->tab)[i] = scalars[i];
+  }
+  if (int rc = var_group_upload(g, scalars ? 1 : 0, st)) return rc;
+  var_group_launch(g, B, which, 0, w ? VG_PACK_AT : VG_NO_PACK, st);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_group_step(iqlhip_var_group* g, const float* const* blocks_dev, int32_t B, int32_t which_net,
+                                     const iqlhip_var_scalars* scalars, void* stream) {
+  if (!g || !scalars) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (int rc = var_group_check_blocks(g, blocks_dev, B, which_net, true, &scalars[0].aligned_rewards,
+                                      sizeof(iqlhip_var_scalars) / sizeof(int32_t)))
+    return rc;
+  return var_group_eager(g, blocks_dev, nullptr, B, which_net, scalars, nullptr, nullptr, stream);
+}
+
+extern "C" int iqlhip_var_group_values(iqlhip_var_group* g, const float* const* blocks_dev, int32_t B, const int32_t* aligned_rewards,
+                                       float* const* outs_dev, void* stream) {
+  if (!g || !outs_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (int rc = var_group_check_blocks(g, blocks_dev, B, -1, false, aligned_rewards, 1)) return rc;
+  for (int i = 0; i < g->k; ++i)
+    if (!outs_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL argument", i);
+  return var_group_eager(g, blocks_dev, nullptr, B, -1, nullptr, aligned_rewards, outs_dev, stream);
+}
+
+extern "C" int iqlhip_var_group_pack_windows(iqlhip_var_group* g, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                             const int32_t* action_dim, const int64_t* start, int32_t B, float* const* blocks_out_dev,
+                                             void* stream) {
+  if (!start || !blocks_out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  const VarGroupWin w{rows_dev, ld, size, action_dim, start};
+  if (int rc = var_group_check_windows(g, w, B)) return rc;
+  for (int i = 0; i < g->k; ++i) {
+    if (!blocks_out_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL argument", i);
+    if ((uintptr_t)blocks_out_dev[i] & 3) return fail(IQLHIP_EINVAL, "member %d: the packed block must be 4-byte aligned", i);
+  }
+  DevGuard guard(g->device);
+  if (int rc = var_group_staging_free(g)) return rc;
+  for (int i = 0; i < g->k; ++i) {
+    memset(&g->stg.host(g->recs)[i], 0, sizeof(VarGroupRec));
+    var_group_record_pack(g, i, w, B, blocks_out_dev[i]);
+  }
+  if (int rc = var_group_upload(g, 0, (hipStream_t)stream)) return rc;
+  hipLaunchKernelGGL(iql_var_pack_window_group_kernel<false>, dim3(var_group_grid(g->k, var_pack_blocks(g->S, B))), dim3(256), 0,
+                     (hipStream_t)stream, g->stg.device(g->recs), g->k, (g->k + 7) / 8, 0);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_group_step_windows(iqlhip_var_group* g, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                             const int32_t* action_dim, const int64_t* start, int32_t B, int32_t which_net,
+                                             const iqlhip_var_scalars* scalars, void* stream) {
+  if (!start || !scalars) return fail(IQLHIP_EINVAL, "NULL argument");
+  const VarGroupWin w{rows_dev, ld, size, action_dim, start};
+  if (int rc = var_group_check_windows(g, w, B)) return rc;
+  if (int rc = var_group_check_blocks(g, rows_dev, B, which_net, true, &scalars[0].aligned_rewards,
+                                      sizeof(iqlhip_var_scalars) / sizeof(int32_t)))
+    return rc;
+  return var_group_eager(g, nullptr, &w, B, which_net, scalars, nullptr, nullptr, stream);
+}
+
+extern "C" int iqlhip_var_group_values_windows(iqlhip_var_group* g, const float* const* rows_dev, const int64_t* ld,
+                                               const int64_t* size, const int32_t* action_dim, const int64_t* start, int32_t B,
+                                               const int32_t* aligned_rewards, float* const* outs_dev, void* stream) {
+  if (!start || !outs_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  const VarGroupWin w{rows_dev, ld, size, action_dim, start};
+  if (int rc = var_group_check_windows(g, w, B)) return rc;
+  if (int rc = var_group_check_blocks(g, rows_dev, B, -1, false, aligned_rewards, 1)) return rc;
+  for (int i = 0; i < g->k; ++i)
+    if (!outs_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL argument", i);
+  return var_group_eager(g, nullptr, &w, B, -1, nullptr, aligned_rewards, outs_dev, stream);
+}
+
+extern "C" int iqlhip_var_group_read_loss(iqlhip_var_group* g, float* losses, float* heads, int32_t n_head, void* stream) {
+  if (!g || !losses) return fail(IQLHIP_EINVAL, "NULL argument");
+  for (int i = 0; i < g->k; ++i)
+    if (n_head < 0 || n_head > g->m[i]->max_rows) return fail(IQLHIP_EINVAL, "member %d: n_head outside [0, max_rows]", i);
+  DevGuard guard(g->device);
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int i = 0; i < g->k; ++i) {
+    losses[i] = g->m[i]->land[0];
+    if (heads)
+      for (int k = 0; k < 3; ++k)
+        memcpy(heads + ((size_t)i * 3 + k) * n_head, g->m[i]->land + 4 + (size_t)k * VAR_LD, (size_t)n_head * sizeof(float));
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_group_train_steps(iqlhip_var_group* g, const float* const* rows_dev, const int64_t* ld, const int64_t* size,
+                                            const int32_t* action_dim, int32_t B, int32_t n_steps, int32_t which_net,
+                                            const iqlhip_var_scalars* scalars, const uint64_t* seeds, const uint64_t* stream_offsets,
+                                            const int64_t* const* starts_dev, const int64_t* n_starts, void* stream) {
+  if (!scalars || !seeds || !stream_offsets || !starts_dev || !n_starts) return fail(IQLHIP_EINVAL, "NULL argument");
+  const VarGroupWin w{rows_dev, ld, size, action_dim, nullptr};
+  if (int rc = var_group_check_windows(g, w, B)) return rc;
+  if (n_steps < 1 || n_steps > IQLHIP_VAR_TRAIN_MAX_STEPS)
+    return fail(IQLHIP_EINVAL, "n_steps = %d outside [1, %d]", n_steps, IQLHIP_VAR_TRAIN_MAX_STEPS);
+  const int K = g->k;
+  for (int i = 0; i < K; ++i) {
+    if (starts_dev[i] && n_starts[i] < 1)
+      return fail(IQLHIP_EINVAL, "member %d: a starts list needs n_starts >= 1, got %lld", i, (long long)n_starts[i]);
+    if ((uintptr_t)starts_dev[i] & 7) return fail(IQLHIP_EINVAL, "member %d: the starts list must be 8-byte aligned", i);
+    for (int s = 0; s < n_steps; ++s)
+      if (scalars[(size_t)s * K + i].aligned_rewards != scalars[i].aligned_rewards)
+        return fail(IQLHIP_EINVAL, "member %d: aligned_rewards differs inside a call", i);
+  }
+  if (int rc = var_group_check_blocks(g, rows_dev, B, which_net, true, &scalars[0].aligned_rewards,
+                                      sizeof(iqlhip_var_scalars) / sizeof(int32_t)))
+    return rc;
+  DevGuard guard(g->device);
+  if (int rc = var_group_window_scratch(g)) return rc;
+  if (int rc = var_group_staging_free(g)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < K; ++i) {
+    iqlhip_var* s = g->m[i];
+    var_group_record(g, i, s->wblk, B, which_net, scalars[i].aligned_rewards, nullptr, s->wvals,
+                     g->loss_ring + (size_t)i * IQLHIP_VAR_TRAIN_MAX_STEPS);
+    var_group_record_pack(g, i, w, B, s->wblk);
+    VarPackParams& p = g->stg.host(g->recs)[i].pk;
+    p.seed = seeds[i];
+    p.j = stream_offsets[i];
+    p.span = starts_dev[i] ? (unsigned long long)n_starts[i] : (unsigned long long)(size[i] - B + 1);
+    p.starts = (const long long*)starts_dev[i];
+    p.start_out = g->start_ring + (size_t)i * IQLHIP_VAR_TRAIN_MAX_STEPS;
+  }
+  memcpy(g->stg.host(g->tab), scalars, (size_t)n_steps * K * sizeof(iqlhip_var_scalars));
+  if (int rc = var_group_upload(g, n_steps, st)) return rc;
+  for (int s = 0; s < n_steps; ++s) var_group_launch(g, B, which_net, s, VG_PACK_DRAWN, st);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_var_group_read_train_ring(iqlhip_var_group* g, float* losses_out, int64_t* starts_out, int32_t n_steps,
+                                                void* stream) {
+  if (!g || !losses_out || !starts_out) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n_steps < 1 || n_steps > IQLHIP_VAR_TRAIN_MAX_STEPS)
+    return fail(IQLHIP_EINVAL, "n_steps = %d outside [1, %d]", n_steps, IQLHIP_VAR_TRAIN_MAX_STEPS);
+  DevGuard guard(g->device);
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int i = 0; i < g->k; ++i) {
+    memcpy(losses_out + (size_t)i * n_steps, g->loss_ring + (size_t)i * IQLHIP_VAR_TRAIN_MAX_STEPS, (size_t)n_steps * sizeof(float));
+    memcpy(starts_out + (size_t)i * n_steps, g->start_ring + (size_t)i * IQLHIP_VAR_TRAIN_MAX_STEPS, (size_t)n_steps * sizeof(int64_t));
+  }
   return IQLHIP_OK;
 }

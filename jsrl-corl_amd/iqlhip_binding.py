@@ -303,6 +303,27 @@ SYMBOLS = [
                                          C.c_int32, C.POINTER(VarScalars), C.c_uint64, C.c_uint64, C.c_void_p, C.c_int64,
                                          C.c_void_p]),
     ("iqlhip_var_read_train_ring", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]),
+    # groups of variance learners: [K] arguments are host arrays (of addresses: POINTER(c_void_p))
+    ("iqlhip_var_group_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    ("iqlhip_var_group_destroy", C.c_int, [C.c_void_p]),
+    ("iqlhip_var_group_step", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.POINTER(VarScalars), C.c_void_p]),
+    ("iqlhip_var_group_values", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_void_p), C.c_void_p]),
+    ("iqlhip_var_group_read_loss", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
+    ("iqlhip_var_group_pack_windows", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_void_p),
+                                                C.c_void_p]),
+    ("iqlhip_var_group_step_windows", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                                C.POINTER(VarScalars), C.c_void_p]),
+    ("iqlhip_var_group_values_windows", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_void_p), C.c_void_p]),
+    ("iqlhip_var_group_train_steps", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(VarScalars),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                               C.POINTER(C.c_int64), C.c_void_p]),
+    ("iqlhip_var_group_read_train_ring", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_int32, C.c_void_p]),
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -11,7 +11,9 @@ CPU device holds its networks and optimizers, and raises when asked to step.
 Beyond the reference: B consecutive rows of a GPU ReplayBuffer are a rollout (a dataset is stored in trajectory order,
 an online ring fills in time order), so pack_window / update_from_buffer / get_values_window build the packed block with
 one launch instead of the host, and train_on_buffer / run_training_on_buffer queue whole bursts of updates whose
-windows are drawn on the device (DESIGN.md 6l "From a replay buffer")."""
+windows are drawn on the device (DESIGN.md 6l "From a replay buffer"); VarianceLearnerGroup does every one of these calls
+for up to 16 learners with one set of launches, each member's result its solo call's bit for bit (DESIGN.md 6l "Groups of
+learners")."""
 from __future__ import annotations
 
 import ctypes as C
@@ -423,6 +425,11 @@ class VarianceLearner:
         if n_updates - n_mf:
             logs.append(self.train_on_buffer(buffer, n_updates - n_mf, seed, n_mf, True, starts))
         self.buffer_log = {key: np.concatenate([l[key] for l in logs]) if logs else np.empty(0) for key in ("losses", "starts")}
+        return self._finish_buffer_training(n_updates, save_dir, env_name)
+
+    def _finish_buffer_training(self, n_updates: int, save_dir, env_name: str):
+        """run_training_on_buffer behind its bursts (self.buffer_log holds their losses and starts): the printed losses,
+        eval mode, the saved files, mf deleted; returns self.vf.  (VarianceLearnerGroup ends every member's run with it.)"""
         for n in range(0, n_updates, 100):
             print(f"Iteration {n}/{n_updates}:\nvalue_loss: {float(self.buffer_log['losses'][n])}")
         self.mf.eval()
@@ -503,3 +510,275 @@ class VarianceLearner:
             torch.save(cpu(self.mf), stem + "_mf.pt")
         del self.mf
         return self.vf
+
+
+# ---------------------------------------------------------------------- groups of learners
+MAX_GROUP = hb.IQLHIP_MAX_GROUP
+
+
+def per_member(x, K: int, what: str) -> list:
+    """An argument given once for all members, or as a list / tuple of K entries: the K entries."""
+    if isinstance(x, (list, tuple)):
+        if len(x) != K:
+            raise ValueError(f"iqlhip: {what} must hold one entry per member ({K}), got {len(x)}")
+        return list(x)
+    return [x] * K
+
+
+def per_member_starts(starts, K: int) -> list:
+    """starts= of a group burst as K entries.  None: every member draws from its whole buffer.  A tensor, an array or a
+    list of integers: that one list for every member.  A list / tuple with a None, a tensor, an array or a list in it:
+    one entry per member, None for a member that draws from its whole buffer."""
+    if starts is None:
+        return [None] * K
+    if isinstance(starts, (list, tuple)) and any(s is None or isinstance(s, (torch.Tensor, np.ndarray, list, tuple)) for s in starts):
+        if len(starts) != K:
+            raise ValueError(f"iqlhip: starts must hold one entry per member ({K}), got {len(starts)}")
+        return [None if s is None else (np.asarray(s, dtype=np.int64) if isinstance(s, (list, tuple)) else s) for s in starts]
+    if isinstance(starts, (list, tuple)):
+        starts = np.asarray(starts, dtype=np.int64)
+    return [starts] * K
+
+
+def burst_chunks(n_updates: int) -> List[int]:
+    """The library calls of a burst of n_updates: at most TRAIN_MAX_STEPS updates each, as train_on_buffer splits it."""
+    return [min(TRAIN_MAX_STEPS, n_updates - done) for done in range(0, n_updates, TRAIN_MAX_STEPS)]
+
+
+def group_scalar_table(hypers, t0s, m: int, aligned):
+    """Adam's scalars of m updates of K members, update-major [m][K] (iqlhip_var_group_train_steps): entry [i][k] is
+    adam_scalars of member k's step t0s[k] + i + 1 under hypers[k] = (lr, betas, eps)."""
+    K = len(hypers)
+    return (hb.VarScalars * (m * K))(*[adam_scalars(*hypers[k], t0s[k] + i + 1, aligned[k]) for i in range(m) for k in range(K)])
+
+
+class VarianceLearnerGroup:
+    """K VarianceLearners of one state_dim and batch_size on one GPU, updated by one set of launches per update
+    (iqlhip_var_group).  Every call is the solo call of the same name for every member, bit for bit: `update` is K
+    `_update_v`s, `train_on_buffer` K bursts.  A member stays a VarianceLearner: it may be stepped alone before and
+    after a group call; step counts and optimizer state are kept per member."""
+
+    def __init__(self, learners):
+        self.learners = list(learners)
+        K = len(self.learners)
+        if K < 1 or K > MAX_GROUP:
+            raise ValueError(f"iqlhip: a variance-learner group takes 1..{MAX_GROUP} members, got {K}")
+        for i, l in enumerate(self.learners):
+            if getattr(l, "_h", None) is None:
+                raise NotImplementedError(f"iqlhip: member {i}: the variance learner steps on the GPU only (device='cuda'); "
+                                          "there is no CPU fall-back")
+            for j in range(i):
+                if self.learners[j] is l:
+                    raise ValueError(f"iqlhip: member {i}: the learner is member {j} too")
+            first = self.learners[0]
+            if int(l.state_dim) != int(first.state_dim):
+                raise ValueError(f"iqlhip: member {i}: state_dim = {l.state_dim}, member 0's is {first.state_dim}")
+            if l._dev != first._dev:
+                raise ValueError(f"iqlhip: member {i}: device {l._dev}, member 0's is {first._dev}")
+        self._dev = self.learners[0]._dev
+        self._g = None
+        self._members = None          # the library handles the group was built over
+
+    # ------------------------------------------------------------------ the handle
+    def _release(self) -> None:
+        if getattr(self, "_g", None) is not None:
+            hb.lib().iqlhip_var_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _group(self):
+        """The library group over the members' current handles (rebuilt when a member has re-attached)."""
+        for i, l in enumerate(self.learners):
+            if l._h is None:
+                raise RuntimeError(f"iqlhip: member {i} has released its library handle")
+        now = [int(l._h.value) for l in self.learners]
+        if self._g is None or now != self._members:
+            self._release()
+            g = C.c_void_p()
+            hb.check(hb.lib().iqlhip_var_group_create((C.c_void_p * len(now))(*now), len(now), C.byref(g)))
+            self._g, self._members = g, now
+        return self._g
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self._dev.index).cuda_stream)
+
+    @property
+    def K(self) -> int:
+        return len(self.learners)
+
+    def _hypers(self, k: int):
+        return [l._adam_hyper(l._nets()[k][1]) for l in self.learners]
+
+    def _aligned(self):
+        return [l.aligned_rewards for l in self.learners]
+
+    def _batch_size(self) -> int:
+        B = int(self.learners[0].batch_size)
+        for i, l in enumerate(self.learners):
+            if int(l.batch_size) != B:
+                raise ValueError(f"iqlhip: member {i}: batch_size = {l.batch_size}, member 0's is {B}")
+        return B
+
+    @staticmethod
+    def _ptrs(values):
+        return (C.c_void_p * len(values))(*values)
+
+    def _windows(self, buffers):
+        """(rows[K], ld[K], size[K], action_dim[K]) as the library's host arrays, and the sizes."""
+        K = self.K
+        src = [l._window_source(b) for l, b in zip(self.learners, per_member(buffers, K, "buffers"))]
+        return (self._ptrs([s[0] for s in src]), (C.c_int64 * K)(*[s[1] for s in src]), (C.c_int64 * K)(*[s[2] for s in src]),
+                (C.c_int32 * K)(*[s[3] for s in src])), [s[2] for s in src]
+
+    # ------------------------------------------------------------------ eager
+    def _read(self, n_head: int):
+        K = self.K
+        losses = (C.c_float * K)()
+        heads = (C.c_float * (K * 3 * max(n_head, 1)))()
+        hb.check(hb.lib().iqlhip_var_group_read_loss(self._g, losses, heads, n_head, self._stream()))
+        return list(losses), np.ctypeslib.as_array(heads)[:K * 3 * n_head].reshape(K, 3, n_head).copy()
+
+    def _stepped(self, B: int, k: int, launch) -> List[dict]:
+        """`launch(scalars)` (a library step of net k for every member), the read-back, and the members' _update_v dicts."""
+        sc = group_scalar_table(self._hypers(k), [l._adam_t[k] for l in self.learners], 1, self._aligned())
+        with torch.cuda.device(self._dev):
+            hb.check(launch(sc))
+            losses, heads = self._read(min(5, B))
+        out = []
+        for i, l in enumerate(self.learners):
+            l._adam_t[k] += 1
+            l._sync_opt_state(k)
+            out.append({"variance_pred_vec": torch.from_numpy(heads[i][2]), "value_loss": float(losses[i]),
+                        "values_pred_vec": torch.from_numpy(heads[i][1]), "values_samp_vec": torch.from_numpy(heads[i][0])})
+        return out
+
+    def _upload(self, packed) -> int:
+        """packed[K] = (observations, rewards, next_observations, next_dones): every member's block, of one length."""
+        lengths = [len(p[0]) for p in packed]
+        for i, b in enumerate(lengths):
+            if b != lengths[0]:
+                raise ValueError(f"iqlhip: member {i}: the batch holds {b} rows, member 0's {lengths[0]}")
+        return [l._upload(*p) for l, p in zip(self.learners, packed)][0]
+
+    def _values(self, B: int, call):
+        K = self.K
+        out = torch.empty((K, 3, B), dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            hb.check(call((C.c_int32 * K)(*[int(a) for a in self._aligned()]), self._ptrs([out[i].data_ptr() for i in range(K)])))
+        out = out.cpu()
+        return [(out[i][0], out[i][1], out[i][2]) for i in range(K)]
+
+    def update(self, batches, update_vf) -> List[dict]:
+        """_update_v for every member: batches[K] are run_episodes-shaped batches of one length; K _update_v dicts."""
+        k = NET_VF if update_vf else NET_MF
+        batches = per_member(list(batches), self.K, "batches")
+        self._hypers(k)
+        g = self._group()
+        B = self._upload([(b[0], b[2], b[4], b[5]) for b in batches])
+        blocks = self._ptrs([l._blk.data_ptr() for l in self.learners])
+        return self._stepped(B, k, lambda sc: hb.lib().iqlhip_var_group_step(g, blocks, B, k, sc, self._stream()))
+
+    def get_values(self, batches):
+        """get_values for every member: batches[K] = (obs, rewards, next_obs, dones, next_dones); K triples of CPU tensors."""
+        batches = per_member(list(batches), self.K, "batches")
+        g = self._group()
+        B = self._upload([(b[0], b[1], b[2], b[4]) for b in batches])
+        blocks = self._ptrs([l._blk.data_ptr() for l in self.learners])
+        return self._values(B, lambda al, outs: hb.lib().iqlhip_var_group_values(g, blocks, B, al, outs, self._stream()))
+
+    # ------------------------------------------------------------------ windows of replay buffers
+    def _starts(self, starts):
+        K = self.K
+        return (C.c_int64 * K)(*[int(s) for s in per_member(starts, K, "starts")])
+
+    def update_from_buffer(self, buffers, starts, update_vf) -> List[dict]:
+        """update_from_buffer for every member: buffers is one buffer or K, starts an int or K."""
+        k = NET_VF if update_vf else NET_MF
+        self._hypers(k)
+        B = self._batch_size()
+        win, _ = self._windows(buffers)
+        st = self._starts(starts)
+        g = self._group()
+        return self._stepped(B, k, lambda sc: hb.lib().iqlhip_var_group_step_windows(g, *win, st, B, k, sc, self._stream()))
+
+    def get_values_window(self, buffers, starts):
+        """get_values_window for every member: K triples (values_samp, values_pred, variance_pred)."""
+        B = self._batch_size()
+        win, _ = self._windows(buffers)
+        st = self._starts(starts)
+        g = self._group()
+        return self._values(B, lambda al, outs: hb.lib().iqlhip_var_group_values_windows(g, *win, st, B, al, outs, self._stream()))
+
+    def train_on_buffer(self, buffers, n_updates: int, seeds, offsets=0, update_vf=False, starts=None) -> dict:
+        """train_on_buffer for every member, as one burst: five launches per update for all K.  buffers: one buffer or K;
+        seeds, offsets: an int or K; starts: per_member_starts' forms.  Member i's update j uses index offsets[i] + j of
+        the stream under seeds[i], as its solo burst does.  Returns {"losses": float32 [K, n_updates], "starts": int64
+        [K, n_updates]}."""
+        k = NET_VF if update_vf else NET_MF
+        K, n = self.K, int(n_updates)
+        hypers = self._hypers(k)
+        B = self._batch_size()
+        win, sizes = self._windows(buffers)
+        seeds, offsets = per_member(seeds, K, "seeds"), per_member(offsets, K, "offsets")
+        lists = per_member_starts(starts, K)
+        if n < 1:
+            raise ValueError(f"iqlhip: n_updates must be >= 1, got {n_updates}")
+        for i, size in enumerate(sizes):
+            if size < B:
+                raise ValueError(f"iqlhip: member {i}: the replay buffer holds {size} rows, a window takes batch_size = {B}")
+        for i, (l, s) in enumerate(zip(self.learners, lists)):
+            if s is not None:
+                try:
+                    lists[i] = l._window_starts(s, sizes[i] - B)
+                except ValueError as e:
+                    raise ValueError(f"iqlhip: member {i}: {e}") from None
+        st_ptrs = self._ptrs([None if s is None else s.data_ptr() for s in lists])
+        n_st = (C.c_int64 * K)(*[0 if s is None else s.numel() for s in lists])
+        m64 = (1 << 64) - 1
+        seeds_c = (C.c_uint64 * K)(*[int(s) & m64 for s in seeds])
+        g = self._group()
+        losses, used = np.empty((K, n), dtype=np.float32), np.empty((K, n), dtype=np.int64)
+        with torch.cuda.device(self._dev):
+            done = 0
+            for m in burst_chunks(n):
+                sc = group_scalar_table(hypers, [l._adam_t[k] for l in self.learners], m, self._aligned())
+                offs = (C.c_uint64 * K)(*[(int(o) + done) & m64 for o in offsets])
+                hb.check(hb.lib().iqlhip_var_group_train_steps(g, *win, B, m, k, sc, seeds_c, offs, st_ptrs, n_st, self._stream()))
+                for l in self.learners:
+                    l._adam_t[k] += m
+                lo, so = np.empty((K, m), dtype=np.float32), np.empty((K, m), dtype=np.int64)
+                hb.check(hb.lib().iqlhip_var_group_read_train_ring(g, lo.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                   so.ctypes.data_as(C.POINTER(C.c_int64)), m, self._stream()))
+                losses[:, done:done + m], used[:, done:done + m] = lo, so
+                done += m
+        for l in self.learners:
+            l._sync_opt_state(k)
+        return {"losses": losses, "starts": used}
+
+    def run_training_on_buffer(self, buffers, n_updates=10000, seeds=0, env_names="buffer", save_dir=SAVE_DIR, starts=None):
+        """run_training_on_buffer for every member as two bursts: mf for the updates n <= n_updates / 2, vf for the rest.
+        env_names: one name or K (members that share a name, an actor setting and a variance_learn_frac write the same
+        files, as their solo runs would).  Every member's buffer_log, printed losses, saved files and deleted mf are the
+        solo call's; returns the K vf networks in eval mode."""
+        K, n_updates = self.K, int(n_updates)
+        names = per_member(env_names, K, "env_names")
+        n_mf = min(n_updates, n_updates // 2 + 1)
+        logs = []
+        if n_mf:
+            logs.append(self.train_on_buffer(buffers, n_mf, seeds, 0, False, starts))
+        if n_updates - n_mf:
+            logs.append(self.train_on_buffer(buffers, n_updates - n_mf, seeds, n_mf, True, starts))
+        out = []
+        for i, l in enumerate(self.learners):
+            l.buffer_log = {key: np.concatenate([x[key][i] for x in logs]) if logs else np.empty(0) for key in ("losses", "starts")}
+            out.append(l._finish_buffer_training(n_updates, save_dir, names[i]))
+        return out
+
+    def gates(self, device=None) -> list:
+        """The members' gate()s, in member order: JsrlActors(learners, guides, gates=group.gates())."""
+        return [l.gate(device) for l in self.learners]
