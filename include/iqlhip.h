@@ -1022,6 +1022,9 @@ int iqlhip_debug_drain_spin(iqlhip_ctx* ctx, void* stream, double* spin_us);
 /* Tests: the device buffers, pinned buffers and events this process's contexts and groups hold right now (what
  * iqlhip_destroy / iqlhip_group_destroy release; cached graphs and the P2P exchange block are not counted). */
 int64_t iqlhip_debug_live_buffers(void);
+/* Tests: how many training forwards this context has LAUNCHED OR CAPTURED as iql_fwd_kernel_early (the one-slice fp32
+ * forward with preloaded arguments; every other forward is iql_fwd_kernel or a chunk kind's kernel).  -1: null context. */
+int64_t iqlhip_debug_fwd_early_launches(const iqlhip_ctx* ctx);
 /* Average device time (microseconds) of the kernels of the last iqlhip_step /
  * train_steps call measured with hipEvents on `stream`; 0 when timing is off. */
 int iqlhip_set_timing(iqlhip_ctx* ctx, int enabled);

@@ -269,6 +269,9 @@ struct iqlhip_ctx {
   int bwd_donate_pct = -1;            // diagnostic (IQLHIP_BWD_DONATE_PCT): share of the policy's dW1 tiles run on the other XCDs
   int bwd_spb_force = -1;             // the same for the backward's (b) blocks (IQLHIP_BWD_SPB_L2)
   int fwd_spb_force = -1;             // diagnostic (IQLHIP_FWD_SPB_L2): fixed slices-per-block exponent of the forward
+  bool fwd_early = true;              // diagnostic (IQLHIP_FWD_EARLY=0): plain one-slice fp32 steps keep iql_fwd_kernel
+  bool fwd_early_layout = false;      // the dims and the arena layout are what iql_fwd_kernel_early restates (fwd_early_layout_ok)
+  mutable std::atomic<int64_t> fwd_early_launches{0};      // tests: forwards launched or captured as iql_fwd_kernel_early
   // large-batch bf16 path (iqlhip_lb_kernels.h): bf16 precision and more than LB_MIN_ROWS rows per step
   float* pi_t = nullptr;              // [max_batch][32] T | [max_batch][32] G | [max_batch] L: the policy's loss terms without w
   __bf16* dh1g = nullptr;             // [4][max_batch][256] dH1 rows, [4][max_batch][256] dH0 rows, [max_batch][32] policy dY (allocated
@@ -399,6 +402,7 @@ static int xld_host(int k0) { int k0p = (k0 + 3) & ~3; return ((k0p + 29) / 32) 
 extern "C" int iqlhip_destroy(iqlhip_ctx* c);
 extern "C" int iqlhip_xch_shutdown(iqlhip_ctx* c);
 
+static bool fwd_early_layout_ok(const iqlhip_ctx* c);      // (defined in front of launch_fwd_grid)
 static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hyper* hyper, int device) {
   c->dims = *dims;
   c->hyper = *hyper;
@@ -472,6 +476,7 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   if (const char* ov = getenv("IQLHIP_BWD_DONATE_PCT")) c->bwd_donate_pct = std::max(0, std::min(100, atoi(ov)));   // diagnostic (tools/)
   if (const char* ov = getenv("IQLHIP_BWD_SPB_L2")) c->bwd_spb_force = std::max(0, std::min(2, atoi(ov)));   // diagnostic (tools/)
   if (const char* ov = getenv("IQLHIP_FWD_SPB_L2")) c->fwd_spb_force = std::max(0, std::min(2, atoi(ov)));   // diagnostic (tools/)
+  if (const char* ov = getenv("IQLHIP_FWD_EARLY")) c->fwd_early = atoi(ov) != 0;                             // diagnostic (tools/)
   if (const char* ov = getenv("IQLHIP_LB")) c->lb_enabled = atoi(ov) != 0;                                     // diagnostic (tools/)
   if (const char* ov = getenv("IQLHIP_LB_NBB")) c->lb_nbb_force = std::max(2, atoi(ov));
   if (const char* ov = getenv("IQLHIP_LB_CSPLIT")) c->lb_csplit = atoi(ov) != 0;
@@ -494,11 +499,13 @@ static int create_impl(iqlhip_ctx* c, const iqlhip_dims* dims, const iqlhip_hype
   // large-batch backward, row blocks: [dH1 tile | H1 tile | dH0 tile | dY | dy] (iql_bwd_rows_kernel)
   c->lds_bwd_lb = (size_t)(3 * 32 * H0B_LD + 32 * LB_DYLD) * 2 + 32 * 4 + (size_t)(2 * 4 * 32 + 16) * 4;      // (+ the block sums' partials)
   int rc = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_kernel(m & 1, m & 2, m & 4); });
+  if (!rc) rc = set_max_lds(0, c->lds_fwd_solo, [](unsigned) { return &iql_fwd_kernel_early; });
   if (!rc) rc = set_max_lds(2, c->lds_fwd_solo, [](unsigned m) { return fwd_one_kernel(m & 1, m & 2); });
   if (!rc) rc = set_max_lds(3, c->lds_bwd, [](unsigned m) { return bwd_kernel(m & 1, m & 2, m & 4); });
   if (!rc) rc = set_max_lds(1, c->lds_bwd_lb, [](unsigned m) { return bwd_rows_kernel(m & 1); });
   if (!rc) rc = set_max_lds(2, c->lds_bwd, [](unsigned m) { return bwd_rw_kernel(m & 1, m & 2); });
   c->fwd_lds_set[(int)ChunkKind::Plain] = !rc;      // (the other kinds: ensure_fwd_lds, at their first call)
+  c->fwd_early_layout = fwd_early_layout_ok(c);
   return rc;
 }
 
@@ -885,9 +892,63 @@ static size_t fwd_lds(const iqlhip_ctx* c, int n_blocks) { return (n_blocks <= c
 // The training forward of a chunk kind: every one takes a StepParams.  Defined at the end of the file, behind the last
 // kind's selector — the selectors stand where their kernels are to lie in the code object (with_bools).
 static const void* fwd_kernel_of(ChunkKind kind, bool bf, bool dma, bool multi);
+// iql_fwd_kernel_early takes the plain one-slice fp32 training forward whenever its premises hold: every instance
+// stages W0 in LDS through registers (state_dim + action_dim <= FWD_EARLY_MAX_K and staged), a packed row tile is at most
+// three float4 per thread, and the arenas are laid out as the kernel restates them from the dims.
+// Once per context (iqlhip_create): the dims fit the packed words, and iqlhip_arena_layout's result is what arena_off
+// (csrc/iqlhip_kernels.h) computes — W1 leads a net's segment, then W0, b0, b1, W2, b2; segments V, Q1, Q2, pi, each
+// rounded up to 64 floats.  (The layout is stated three times: iqlhip_arena_layout, arena_off for the kernels with
+// preloaded arguments, and here, where the first two are held against each other.)
+extern "C" int64_t iqlhip_debug_fwd_early_launches(const iqlhip_ctx* ctx) {
+  return ctx ? ctx->fwd_early_launches.load(std::memory_order_relaxed) : -1;
+}
+static bool fwd_early_layout_ok(const iqlhip_ctx* c) {
+  const iqlhip_layout& L = c->L;
+  const int S = c->dims.state_dim, A = c->dims.action_dim, kq = S + A;
+  if (kq > FWD_EARLY_MAX_K || kq > c->w0_lds_k || c->w0_lds_k > W0_LDS_MAX_K) return false;
+  if (RT_ROWS * c->row_ld / 4 > 3 * 256 || S > 255 || A > 63 || c->row_ld > 1023) return false;      // (the packed words' fields)
+  long long begin = 0;
+  for (int n = 0; n < 4; ++n) {
+    const iqlhip_net_layout& nl = L.net[n];
+    const long long k0 = nl.k_in, d = nl.d_out;
+    if (k0 != ((n == IQLHIP_NET_Q1 || n == IQLHIP_NET_Q2) ? kq : S) || d != (n == IQLHIP_NET_PI ? A : 1)) return false;
+    if (nl.seg_begin != begin || nl.w1 != begin || nl.w0 != begin + 65536 || nl.b0 != nl.w0 + 256 * k0 || nl.b1 != nl.b0 + 256 ||
+        nl.w2 != nl.b1 + 256 || nl.b2 != nl.w2 + 256 * d)
+      return false;
+    const long long seg_n = (65536 + 256 * k0 + 512 + 256 * d + ((d + 3) & ~3LL) + 63) & ~63LL;      // (V, Q1, Q2: no log_std)
+    if (n != IQLHIP_NET_PI && nl.seg_end != begin + seg_n) return false;
+    begin = nl.seg_end;
+  }
+  return true;
+}
+// Per launch: the kind of step, and the instance table of `p` being the context's own arenas (the kernel forms every
+// weight address from the two arena pointers).
+static bool fwd_early_ok(const iqlhip_ctx* c, const StepParams& p, ChunkKind kind, bool bf, bool dma, bool multi) {
+  if (!c->fwd_early || !c->fwd_early_layout || kind != ChunkKind::Plain || bf || dma || multi || p.only_inst >= 0) return false;
+  if (p.S != c->dims.state_dim || p.A != c->dims.action_dim || p.ld != (int)c->row_ld || p.rows >= (1 << 22)) return false;
+  const float* tb = c->target - c->L.target_src;
+  const int netof[7] = {IQLHIP_NET_V, IQLHIP_NET_V, IQLHIP_NET_Q1, IQLHIP_NET_Q2, IQLHIP_NET_Q1, IQLHIP_NET_Q2, IQLHIP_NET_PI};
+  for (int i = 0; i < 7; ++i)
+    if (p.inst[i].w1 != ((i == 2 || i == 3) ? tb : c->params) + c->L.net[netof[i]].w1) return false;
+  return true;
+}
 static void launch_fwd_grid(const iqlhip_ctx* c, const StepParams& p, int nb, hipStream_t st, ChunkKind kind = ChunkKind::Plain) {
   const bool dma = c->w0_lds_k > W0_LDS_MAX_K;       // some instance stages wide layer-0 weights by LDS-DMA
   const bool bf = c->precision == 1, multi = (p.spb_l2 & 3) > 0;
+  if (fwd_early_ok(c, p, kind, bf, dma, multi)) {
+    // leading arguments, preloaded into SGPRs with each wave (build: -mllvm -amdgpu-kernarg-preload-count=14)
+    const float* q_params = c->params;
+    const float* q_target = c->target - c->L.target_src;
+    const float* q_xb = p.xb;
+    const unsigned* q_drop = p.drop_bits;
+    unsigned q_dims = (unsigned)p.S | ((unsigned)p.A << 8) | ((unsigned)p.policy << 14);
+    unsigned q_ldB = (unsigned)p.ld | ((unsigned)p.rows << 10);
+    unsigned q_mb = (unsigned)p.sc.max_batch;
+    void* args[] = {&q_params, &q_target, &q_xb, &q_drop, &q_dims, &q_ldB, &q_mb, const_cast<StepParams*>(&p)};
+    (void)hipLaunchKernel((const void*)&iql_fwd_kernel_early, dim3(nb), dim3(256), args, fwd_lds(c, nb), st);
+    c->fwd_early_launches.fetch_add(1, std::memory_order_relaxed);
+    return;
+  }
   // (policy inference — iqlhip_actor_forward — has its own instantiations)
   const void* kernel = (p.only_inst >= 0) ? (const void*)fwd_one_kernel(bf, dma) : fwd_kernel_of(kind, bf, dma, multi);
   void* args[] = {const_cast<StepParams*>(&p)};

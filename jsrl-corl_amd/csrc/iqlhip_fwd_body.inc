@@ -5,6 +5,13 @@
 // agent's `p` (StepParams) and ROW_EXIT: a block whose row tile
 // lies outside the agent's batch exits under every block map (iql_fwd_group_kernel only: its grid.x is the largest
 // member's; a single agent's one- and two-slice grids are sized exactly and compile without the test).
+// EARLY (iql_fwd_kernel_early only; everywhere else false, and the leading arguments q_* null constants: FWD_NOT_EARLY()):
+// the one-slice fp32 forward whose every instance stages W0 in LDS through registers (k0 <= 32, packed rows of at most
+// 3 float4 per thread).  Every address of the issue section is formed from the PRELOADED leading arguments q_*, so the
+// small operands leave before the by-value `p` has arrived, and the first FWD_EARLY_W1 of the wave's 16 W1 fragment loads
+// follow them at once, in front of the LDS stores and the barrier (the wait there is a counted one that leaves them in
+// flight); layer 0's MFMA loop hosts the other 12.  Same loads, same k-maps, same arithmetic as the other
+// instantiations, which `if constexpr` keeps instruction for instruction as they were.
   RT_ENTRY();
   const int bid = blockIdx.x;
   // XCD-affine block map (consecutive workgroups go round the 8 XCDs: XCD x = blockIdx & 7).  Across a kernel boundary an
@@ -52,25 +59,37 @@
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
 
-  const NetPtrs np = p.inst[inst];
-  const int xoff = p.xoff[inst];
-  const int slot = p.slot[inst];
+  // EARLY: the instance's tensors from the preloaded arena pointers and dims (instances V(s'), V(s), Qt1, Qt2, Q1, Q2, pi;
+  // the target instances read the target arena, whose pointer is biased so that the parameter arena's offsets hold in
+  // it; W1 leads a net's segment).  xoff, slot and the activation / head pointers are not needed to issue a load: they
+  // come from `p` behind the issue section (below, behind the W1 loads).
+  const int e_net = (inst < 2) ? IQLHIP_NET_V : ((inst == 6) ? IQLHIP_NET_PI : IQLHIP_NET_Q1 + (inst & 1));
+  const ArenaOff e_ao = arena_off(EARLY ? e_net : 0, (int)(q_dims & 255u), (int)((q_dims >> 8) & 63u),
+                                  (int)((q_dims >> 14) & 1u) == IQLHIP_POLICY_GAUSSIAN);
+  const float* const e_base = (inst == 2 || inst == 3) ? q_target : q_params;
+  const NetPtrs np = EARLY ? NetPtrs{e_base + e_ao.w0, e_base + e_ao.b0, e_base + (e_ao.w0 - 65536u), e_base + e_ao.b1,
+                                     e_base + e_ao.w2, e_base + e_ao.b2, e_ao.k0, e_ao.d}
+                           : p.inst[inst];
+  int xoff = EARLY ? 0 : p.xoff[inst];
+  int slot = EARLY ? -1 : p.slot[inst];
   const int k0 = np.k0;
   const int k0p = (k0 + 3) & ~3;
   const int D = np.d;
-  const int ld = p.ld;
-  const int B = p.rows;
-  const int w0k = p.w0_lds_k;
-  const float* xb = p.xb;
-  float* h0g = p.sc.h0;
-  float* h1g = p.sc.h1;
-  float* headsg = p.sc.heads;
-  const int MB = p.sc.max_batch;
-  const int Aact = p.A;
-  PIN_P(np.w0); PIN_P(np.b0); PIN_P(np.w1); PIN_P(np.b1); PIN_P(np.w2); PIN_P(np.b2);
-  PIN_S(k0); PIN_S(D); PIN_S(xoff); PIN_S(slot); PIN_S(ld); PIN_S(B); PIN_S(MB); PIN_S(Aact);
-  PIN_P(xb); PIN_P(h0g); PIN_P(h1g); PIN_P(headsg); PIN_S(w0k);
-  const bool w0_lds = W0DMA ? (k0 <= w0k) : (k0 <= min(w0k, W0_LDS_MAX_K));
+  const int ld = EARLY ? (int)(q_ldB & 1023u) : p.ld;
+  const int B = EARLY ? (int)(q_ldB >> 10) : p.rows;
+  const int w0k = EARLY ? FWD_EARLY_MAX_K : p.w0_lds_k;   // (EARLY: the host launches it only when every k0 is at most this, and staged)
+  const float* xb = EARLY ? q_xb : p.xb;
+  float* h0g = EARLY ? nullptr : p.sc.h0;
+  float* h1g = EARLY ? nullptr : p.sc.h1;
+  float* headsg = EARLY ? nullptr : p.sc.heads;
+  const int MB = EARLY ? (int)q_mb : p.sc.max_batch;
+  const int Aact = EARLY ? (int)((q_dims >> 8) & 63u) : p.A;
+  if constexpr (!EARLY) {
+    PIN_P(np.w0); PIN_P(np.b0); PIN_P(np.w1); PIN_P(np.b1); PIN_P(np.w2); PIN_P(np.b2);
+    PIN_S(k0); PIN_S(D); PIN_S(xoff); PIN_S(slot); PIN_S(ld); PIN_S(B); PIN_S(MB); PIN_S(Aact);
+    PIN_P(xb); PIN_P(h0g); PIN_P(h1g); PIN_P(headsg); PIN_S(w0k);
+  }
+  const bool w0_lds = EARLY ? true : (W0DMA ? (k0 <= w0k) : (k0 <= min(w0k, W0_LDS_MAX_K)));
   const bool w0_dma = W0DMA && w0_lds && (k0 > W0_LDS_MAX_K);      // wide inputs: copied by LDS-DMA, no staging registers
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -96,7 +115,13 @@
   const int n_x = RT_ROWS * ld / 4;
   const int x_last = B * ld / 4 - 1;
   f32x4 xr[XR_MAX_F4];
-  xr_load(xr, xb, row0 * ld / 4, n_x, x_last);
+  if constexpr (EARLY) {      // (n_x <= 3 * 256 on this path: no run-time trip count between the loads)
+#pragma unroll
+    for (int q = 0; q < XR_MAX_F4; ++q) xr[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    xr_issue<0, 3>(xr, xb, row0 * ld / 4, n_x, x_last);
+  } else {
+    xr_load(xr, xb, row0 * ld / 4, n_x, x_last);
+  }
   // (b) head weights of this slice + b2, biases
   f32x4 w2pre[2];
 #pragma unroll
@@ -110,9 +135,18 @@
   for (int ct = 0; ct < 4; ++ct) bias0[ct] = *(const f32x4*)(np.b0 + (unsigned)(wave * 64 + ct * 16 + 4 * g));
   f32x4 bias1 = *(const f32x4*)(np.b1 + (unsigned)(ns * 64 + wave * 16 + 4 * g));
   // (b2) dropout keep-bits of this row tile (policy instance only): thread -> (row tid >> 3, word tid & 7)
-  const bool drop = (inst == 6) && (p.drop_bits != nullptr);
+  const bool drop = (inst == 6) && ((EARLY ? q_drop : p.drop_bits) != nullptr);
   unsigned mk0 = 0xFFFFFFFFu, mk1 = 0xFFFFFFFFu;
-  if (drop) {
+  if constexpr (EARLY) {
+    // unconditional (a load inside a branch makes the join wait vmcnt(0), and W1 is to stay in flight across it):
+    // blocks without dropout read the first words of the batch instead and discard them
+    const int mrow = min(row0 + (tid >> 3), B - 1);
+    const unsigned* const dsrc = drop ? q_drop : (const unsigned*)q_xb;
+    const unsigned l0w = *(dsrc + (unsigned)(drop ? mrow * 8 + (tid & 7) : 0));
+    const unsigned l1w = *(dsrc + (unsigned)(drop ? (MB + mrow) * 8 + (tid & 7) : 0));
+    mk0 = l0w;      // (raw until the LDS store below)
+    mk1 = l1w;
+  } else if (drop) {
     const int mrow = min(row0 + (tid >> 3), B - 1);
     mk0 = p.drop_bits[mrow * 8 + (tid & 7)];
     mk1 = p.drop_bits[(MB + mrow) * 8 + (tid & 7)];
@@ -130,7 +164,7 @@
   } else if (w0_lds) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) w0v[j] = *(const f32x4*)(np.w0 + 4u * (unsigned)min(tid + 256 * j, n_w0v - 1));
-    if (k0 > 32) {
+    if (!EARLY && k0 > 32) {
 #pragma unroll
       for (int j = 8; j < 16; ++j) w0v[j] = *(const f32x4*)(np.w0 + 4u * (unsigned)min(tid + 256 * j, n_w0v - 1));
     }
@@ -143,6 +177,30 @@
   f32x4 bw[BF16 ? 1 : 16];
   bf16x8 bwb[BF16 ? 8 : 1];
   __bf16* H0b = (__bf16*)H0s;          // [32][H0B_LD] (bf16 path: the H0 tile lives here instead of H0s)
+#define BW_LOAD(ks_) bw[ks_] = *(const f32x4*)(np.w1 + (unsigned)(n1 * HID + 16 * (ks_) + 4 * g))
+#define BWB_AT(unit_, j_) (*(const bf16x8*)((const __bf16*)np.w1 + (unsigned)((unit_) * HID + 32 * (j_) + 8 * g)))
+  if constexpr (EARLY) {
+    // the first W1 fragment loads of the wave NOW, behind the small operands (vmcnt retires in issue order, and those
+    // are waited for first: the wait in front of the LDS stores below is a counted one that leaves these in flight).
+    // How many: a fragment load (16 lanes -> 16 rows) occupies the CU's one vector-memory pipe for ~64 cycles, so all 64
+    // of a block take ~4 k cycles to issue, and a wave cannot reach its LDS stores before its last one has left.  With
+    // all 16 per wave here the prologue grew from 3.1 k to 5.3 k cycles and the step LOST 0.5 us although layer 0
+    // shrank by 0.85 k (profiles/fwd_early_w1_stamps_all16.txt); the small operands' round trip hides about 4 per wave
+    // (2..5 measured alike, 0 and 8 worse: profiles/fwd_early_w1_ab.txt).  The fences keep hipcc from moving them
+    // behind the LDS stores or mixing them into the small loads.  Then the rest of `p`, in one batch of scalar loads,
+    // whose fetch has had the whole issue section to arrive.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < FWD_EARLY_W1; ++ks) BW_LOAD(ks);
+    __builtin_amdgcn_sched_barrier(0);
+    xoff = p.xoff[inst];
+    slot = p.slot[inst];
+    h0g = p.sc.h0;
+    h1g = p.sc.h1;
+    headsg = p.sc.heads;
+    PIN_S(xoff); PIN_S(slot); PIN_P(h0g); PIN_P(h1g); PIN_P(headsg); PIN_S(p.drop_scale);
+    __builtin_amdgcn_sched_barrier(0);
+  }
 
   xr_store(xr, Xr, n_x);
   const int Dp = (D + 15) & ~15;
@@ -152,6 +210,13 @@
     if (e < Dp * 16) *(f32x4*)(W2s + (e >> 4) * W2_LD + 4 * (e & 15)) = (e < D * 16) ? w2pre[q] : (f32x4){0.f, 0.f, 0.f, 0.f};
   }
   if (tid < D) W2s[Dp * W2_LD + tid] = b2v;
+  if constexpr (EARLY) {
+    // (the loaded words are used as loaded, here where they are waited for anyway: hipcc otherwise moves a load whose
+    //  value a block discards into a branch)
+    asm volatile("" : "+v"(mk0), "+v"(mk1));
+    mk0 = drop ? mk0 : 0xFFFFFFFFu;
+    mk1 = drop ? mk1 : 0xFFFFFFFFu;
+  }
   Mk[tid] = mk0;
   Mk[256 + tid] = mk1;
   if (w0_lds && !w0_dma) {
@@ -160,7 +225,7 @@
       const int f = tid + 256 * j;
       if (f < n_w0v) *(f32x4*)(W0s + 4 * f) = w0v[j];
     }
-    if (k0 > 32) {
+    if (!EARLY && k0 > 32) {
 #pragma unroll
       for (int j = 8; j < 16; ++j) {
         const int f = tid + 256 * j;
@@ -174,9 +239,8 @@
   // fp32 paths with LDS-staged weights go one step further and request them BETWEEN the groups of layer-0 MFMAs (an MFMA
   // holds the SIMD's issue for 8 of its 32 cycles: four loads per 8 MFMAs trickle out at 42 B/clk over the four waves),
   // so that not even the issue time stands in front of layer 0.
+  // (EARLY: they are on their way since the issue section, see there)
   const bool bw_in_l0 = !BF16 && w0_lds;
-#define BW_LOAD(ks_) bw[ks_] = *(const f32x4*)(np.w1 + (unsigned)(n1 * HID + 16 * (ks_) + 4 * g))
-#define BWB_AT(unit_, j_) (*(const bf16x8*)((const __bf16*)np.w1 + (unsigned)((unit_) * HID + 32 * (j_) + 8 * g)))
   if constexpr (BF16) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) bwb[j] = BWB_AT(n1, j);
@@ -199,7 +263,7 @@
     const float* x0 = Xr + l15 * ld + xoff;
     const float* x1 = Xr + (16 + l15) * ld + xoff;
     float bcur[4], bnxt[4], acur[2], anxt[2];
-    if (w0_lds && nks <= 8) {
+    if (w0_lds && (EARLY || nks <= 8)) {      // (EARLY: k0 <= 32, always this branch)
       // all operands of the (<= 8) k-steps are read up front, then the MFMAs run back to back
       const float* wl[4];
 #pragma unroll
@@ -236,9 +300,11 @@
               acc[1][ct] = MFMA16(bq[ks][ct], aq[ks][1], acc[1][ct]);
             }
           }
-          if (ks < 4) {       // W1 fragments 4 ks .. 4 ks + 3 behind this group of MFMAs
+          if (ks < 4) {       // W1 fragments 4 ks .. 4 ks + 3 behind this group of MFMAs (EARLY: those not yet requested)
 #pragma unroll
-            for (int k2 = 4 * ks; k2 < 4 * ks + 4; ++k2) BW_LOAD(k2);
+            for (int k2 = 4 * ks; k2 < 4 * ks + 4; ++k2) {
+              if (!EARLY || k2 >= FWD_EARLY_W1) BW_LOAD(k2);
+            }
           }
         }
       }
@@ -356,6 +422,14 @@
   STAMP(p, 7);
   __syncthreads();
   STAMP(p, 2);
+#ifdef IQL_STAMPS
+  // one-slice blocks (stamp 13 is the multi-slice blocks' otherwise): the cycle at which this wave's last W1 fragment
+  // has landed — nothing else is in flight here, the H0 stores below not yet issued
+  if constexpr (!MULTI) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    STAMP(p, 13);
+  }
+#endif
 
   // ======== per column slice: layer 1 over the block's H0 tile, head partials.  One pass when the grid holds a block
   // per slice; 2 or 4 passes for large batches — the next slice's W1 fragments, head weights and bias are requested

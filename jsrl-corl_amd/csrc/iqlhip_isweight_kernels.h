@@ -129,5 +129,6 @@ template <bool W0DMA, bool MULTI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_weighted_is_kernel(StepParams p) {
   constexpr bool BF16 = false, ONE = false, ROW_EXIT = false;
   constexpr int MIXED_IDLE = 3;
+  FWD_NOT_EARLY();
 #include "iqlhip_fwd_body.inc"
 }

@@ -202,6 +202,18 @@ struct StepParams {
 // "uses" the values makes the compiler issue all the loads in one batch behind a single wait.
 #define PIN_S(x) asm volatile("" ::"s"(x))
 #define PIN_P(x) asm volatile("" ::"s"((unsigned long long)(uintptr_t)(x)))
+// For every includer of iqlhip_fwd_body.inc but iql_fwd_kernel_early: the body's EARLY flag off and its leading
+// arguments null constants (no code of theirs survives `if constexpr`).
+#define FWD_EARLY_MAX_K 32   // iql_fwd_kernel_early: every layer-0 input at most this wide (8 float4 of W0 per thread, 8 k-steps)
+// W1 fragment loads (of a wave's 16) that iql_fwd_kernel_early requests in front of the LDS stores; the others go out
+// behind layer 0's MFMA groups in fours, as in iql_fwd_kernel (measured 0 .. 16: profiles/fwd_early_w1_ab.txt)
+#define FWD_EARLY_W1 4
+static_assert(FWD_EARLY_W1 >= 0 && FWD_EARLY_W1 <= 16, "a wave has 16 W1 fragments");
+#define FWD_NOT_EARLY()                                                                                   \
+  constexpr bool EARLY = false;                                                                           \
+  constexpr const float *q_params = nullptr, *q_target = nullptr, *q_xb = nullptr;                        \
+  constexpr const unsigned* q_drop = nullptr;                                                             \
+  constexpr unsigned q_dims = 0, q_ldB = 0, q_mb = 0
 
 // ---------------------------------------------------------------------------
 // A 32-row tile of packed rows is staged whole (flat float4 copy).  The packed stride 2S+A+2 (padded to 4)
@@ -445,6 +457,28 @@ __device__ __forceinline__ void idle_block_work(const IdleWork* wk, int blk, int
                    (nblk - 1 - blk) * 256 + (int)threadIdx.x, nblk * 256);
 }
 
+// A net's tensors inside the parameter arena, from the dims alone (restates iqlhip_arena_layout; used by the kernels whose
+// leading, preloaded arguments carry the arena pointer and the packed dims: iql_fwd_kernel_early, iql_bwd_kernel).
+struct ArenaOff { unsigned w0, b0, b1, w2, b2, log_std; int k0, d; };
+__device__ __forceinline__ ArenaOff arena_off(int net, int S, int A, bool gauss) {
+  auto seg = [&](int k, int d, bool ls) -> unsigned {
+    const unsigned n = 65536u + 256u * (unsigned)k + 512u + 256u * (unsigned)d + (((unsigned)d + 3u) & ~3u) + (ls ? (((unsigned)A + 3u) & ~3u) : 0u);
+    return (n + 63u) & ~63u;
+  };
+  const unsigned sV = seg(S, 1, false), sQ = seg(S + A, 1, false);
+  const unsigned begin = (net == IQLHIP_NET_V) ? 0u : ((net == IQLHIP_NET_Q1) ? sV : ((net == IQLHIP_NET_Q2) ? sV + sQ : sV + 2u * sQ));
+  ArenaOff o;
+  o.k0 = (net == IQLHIP_NET_Q1 || net == IQLHIP_NET_Q2) ? S + A : S;
+  o.d = (net == IQLHIP_NET_PI) ? A : 1;
+  o.w0 = begin + 65536u;
+  o.b0 = o.w0 + 256u * (unsigned)o.k0;
+  o.b1 = o.b0 + 256u;
+  o.w2 = o.b1 + 256u;
+  o.b2 = o.w2 + 256u * (unsigned)o.d;
+  o.log_std = o.b2 + (((unsigned)o.d + 3u) & ~3u);
+  return o;
+}
+
 // Forward: block = (instance, row tile of 32 rows, column slice ns of 64 hidden-1 units).
 // grid = 8 * n_rt * NSPLIT; blockIdx & 7 = instance (7 = idle) so that the
 // blocks of one instance share an XCD and hence one L2 copy of its weights.
@@ -481,6 +515,27 @@ template <bool BF16, bool W0DMA, bool MULTI, bool ONE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_kernel(StepParams p) {
   constexpr bool ROW_EXIT = false;      // (a grid of exactly this agent's row tiles)
   constexpr bool MIXED_IDLE = false;
+  FWD_NOT_EARLY();
+#include "iqlhip_fwd_body.inc"
+}
+// The one-slice fp32 training forward of a plain step when every instance stages W0 in LDS through registers
+// (state_dim + action_dim <= 32; host: fwd_early_ok): iql_fwd_kernel<false, false, false>'s work with LEADING, PRELOADED
+// arguments (the library is built with -mllvm -amdgpu-kernarg-preload-count=14; these are 11 dwords) that suffice to
+// form every address of the block's issue section — the parameter arena, the target arena biased by the target
+// segment's offset so that parameter-arena offsets hold in it, the staged batch, the dropout keep-bits (null: off) and
+//   q_dims = S | A << 8 | policy << 14      q_ldB = ld | rows << 10      q_mb = max_batch
+// (arena_off gives a net's tensors from the dims; W1 leads its segment).  A block therefore requests its small
+// operands and the first quarter of its W1 slice in the first few hundred cycles, instead of waiting 450-700 cycles for
+// the by-value `p`; the rest of W1 still goes out between layer 0's MFMAs (iqlhip_fwd_body.inc: why not all of it).
+// What `p` still supplies (the instance's row offset and slot, the activation and head pointers, the idle blocks'
+// record) is fetched behind the issue section.  `p` follows at byte 48: the argument block stays below
+// iql_bwd_kernel's (56 + sizeof(StepParams)).
+// A kernel of its own, not a flag of iql_fwd_kernel: every other instantiation keeps its symbol and its code.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_kernel_early(
+    const float* q_params, const float* q_target, const float* q_xb, const unsigned* q_drop, unsigned q_dims, unsigned q_ldB,
+    unsigned q_mb, StepParams p) {
+  constexpr bool BF16 = false, W0DMA = false, MULTI = false, ONE = false, ROW_EXIT = false, MIXED_IDLE = false;
+  constexpr bool EARLY = true;
 #include "iqlhip_fwd_body.inc"
 }
 
@@ -667,25 +722,6 @@ __device__ __forceinline__ void pi_items8(const f32x4 (&hv)[8], const float (&ac
 // restates iqlhip_arena_layout) and the dims; everything else still comes from `p`, whose fetch now overlaps them.
 //   q_dims = S | A << 8 | policy << 14      q_ldB = ld | rows << 10      q_mbc = max_batch | n_chunk << 16
 //   q_rts  = n_rt | spb_l2 word << 10
-struct ArenaOff { unsigned w0, b0, b1, w2, b2, log_std; int k0, d; };
-__device__ __forceinline__ ArenaOff arena_off(int net, int S, int A, bool gauss) {
-  auto seg = [&](int k, int d, bool ls) -> unsigned {
-    const unsigned n = 65536u + 256u * (unsigned)k + 512u + 256u * (unsigned)d + (((unsigned)d + 3u) & ~3u) + (ls ? (((unsigned)A + 3u) & ~3u) : 0u);
-    return (n + 63u) & ~63u;
-  };
-  const unsigned sV = seg(S, 1, false), sQ = seg(S + A, 1, false);
-  const unsigned begin = (net == IQLHIP_NET_V) ? 0u : ((net == IQLHIP_NET_Q1) ? sV : ((net == IQLHIP_NET_Q2) ? sV + sQ : sV + 2u * sQ));
-  ArenaOff o;
-  o.k0 = (net == IQLHIP_NET_Q1 || net == IQLHIP_NET_Q2) ? S + A : S;
-  o.d = (net == IQLHIP_NET_PI) ? A : 1;
-  o.w0 = begin + 65536u;
-  o.b0 = o.w0 + 256u * (unsigned)o.k0;
-  o.b1 = o.b0 + 256u;
-  o.w2 = o.b1 + 256u;
-  o.b2 = o.w2 + 256u * (unsigned)o.d;
-  o.log_std = o.b2 + (((unsigned)o.d + 3u) & ~3u);
-  return o;
-}
 template <bool BF16, bool FULL, bool MULTI>
 __global__ __launch_bounds__(256) void iql_bwd_kernel(const float* q_heads, const float* q_xb, const float* q_h1, const float* q_h0,
                                                       const float* q_params, unsigned q_dims, unsigned q_ldB, unsigned q_mbc,
@@ -1210,6 +1246,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   constexpr bool ROW_EXIT = true;       // (grid.x: the member with the most row tiles — the others' extra blocks exit)
   constexpr bool MIXED_IDLE = false;
   const StepParams& p = recs[blockIdx.y].p;
+  FWD_NOT_EARLY();
 #include "iqlhip_fwd_body.inc"
 }
 
@@ -2053,6 +2090,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   constexpr bool MULTI = false, ONE = true, ROW_EXIT = false;      // (blocks past a member's rows store nothing)
   constexpr bool MIXED_IDLE = false;
   const StepParams& p = ps[blockIdx.y];
+  FWD_NOT_EARLY();
 #include "iqlhip_fwd_body.inc"
 }
 
@@ -2129,5 +2167,6 @@ __global__ __launch_bounds__(256) void iql_actor_finish_rows_group_kernel(const 
 template <bool BF16, bool W0DMA, bool MULTI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_mixed_kernel(StepParams p) {
   constexpr bool ONE = false, ROW_EXIT = false, MIXED_IDLE = true;
+  FWD_NOT_EARLY();
 #include "iqlhip_fwd_body.inc"
 }

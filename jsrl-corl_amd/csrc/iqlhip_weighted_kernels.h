@@ -443,6 +443,7 @@ template <bool BF16, bool W0DMA, bool MULTI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void iql_fwd_weighted_kernel(StepParams p) {
   constexpr bool ONE = false, ROW_EXIT = false;
   constexpr int MIXED_IDLE = 2;
+  FWD_NOT_EARLY();
 #include "iqlhip_fwd_body.inc"
 }
 

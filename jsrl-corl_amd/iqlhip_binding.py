@@ -212,6 +212,7 @@ SYMBOLS = [
                                            C.c_void_p]),
     ("iqlhip_debug_drain_spin", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     ("iqlhip_debug_live_buffers", C.c_int64, []),
+    ("iqlhip_debug_fwd_early_launches", C.c_int64, [C.c_void_p]),
     ("iqlhip_group_create", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     ("iqlhip_group_create_flags", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.POINTER(C.c_void_p)]),
     ("iqlhip_group_destroy", C.c_int, [C.c_void_p]),

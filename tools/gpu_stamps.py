@@ -100,8 +100,12 @@ fwd_blocks = np.arange(8 * 2 * ((n_rt + 1) // 2) if fsl2 == 2 else 8 * n_rt * (4
 FWD_NAMES = ("V(s)", "Q1", "Q2", "PI", "V(s')", "Qt1", "Qt2", "idle")
 fwd_inst = np.where(((fwd_blocks >> 3) & 1) == 0, fwd_blocks & 3, 4 + (fwd_blocks & 3))
 report("fwd slice 0 (after the layer-0 barrier)", fwd_blocks, [(2, "(layer-0 barrier)"), (8, "H0 save (+ next slice's W2/b1 requests)"), (9, "layer-1 operand reads + MFMAs"), (10, "epilogue + H1 tile write"), (11, "barrier"),
-                                                              (12, "H1 save + head partials"), (13, "barrier before the next slice")])
+                                                              (12, "H1 save + head partials")] + ([(13, "barrier before the next slice")] if fsl2 > 0 else []))
 report("fwd", fwd_blocks, [(1, "prefetch+gather"), (5, "L0: LDS operand reads"), (6, "L0: MFMAs"), (7, "L0: epilogue + H0 writes"), (2, "L0: barrier"), (3, "H0 save + layer1"), (4, "H1 save + head")])
+# one-slice blocks: stamp 13 is taken behind the layer-0 barrier and a wait for every outstanding load, i.e. when the wave's
+# last W1 fragment has landed (0 cycles behind the barrier: W1 was there before layer 0 ended)
+if fsl2 == 0:
+    report("fwd W1 landing (one-slice blocks)", fwd_blocks, [(1, "prologue up to the first barrier"), (2, "layer 0 up to its barrier"), (13, "wait for the last W1 fragment")])
 n_chunk = (B + 255) // 256
 # launch_bwd's layout: beyond two rounds of the chip the (b) blocks walk 4 column slices and take the FIRST block indices
 bsl2 = int(os.environ.get("IQLHIP_BWD_SPB_L2", 2 if 4 * (32 * n_chunk + 4 * n_rt) > 512 else 0))
