@@ -989,6 +989,37 @@ int iqlhip_jsrl_act(iqlhip_jsrl* jsrl, const float* const* states, int64_t ld_s,
                     const int8_t* const* who, const float* gate_max, const uint64_t* seeds,
                     const float* max_action_learner, const float* max_action_guide, float* const* actions, int64_t ld_a,
                     int32_t* const* use_learner, float* const* gate_out, int32_t flags, void* stream);
+/* Selection by the critic (DESIGN.md 6k "who == 3"): iqlhip_jsrl_act plus one more byte.  A row of member k with
+ * who[k][r] = 3 takes whichever of the two proposed actions the member's twin critic values more:
+ *   a_g = the guide's eval-mode mean for the row (bit for bit a who == 0 row), a_l = the learner's action (bit for bit
+ *   a who == 1 row of the same call, device noise of (seeds[k], call) at element r * A + d included), both after the
+ *   scale by max_action and the clamp;
+ *   qg = min(Q1, Q2)(s, a_g), ql = min(Q1, Q2)(s, a_l)  in fp32, head partials summed in the step's fixed order;
+ *   q_inv_temp[k] infinite, or seeds[k] == 0:  use_learner = (ql >= qg)   (a tie goes to the learner);
+ *   else  p = 1 / (1 + expf(-(ql - qg) * q_inv_temp[k])),  use_learner = (u < p),  u = ((c[2] >> 8) + 0.5) * 2^-24 of
+ *   the Philox block the act() noise stream already draws for element r * A (key, counter and tag 0xAC7 unchanged;
+ *   words 0 and 1 are its Box-Muller pair) — no new stream, no new counter.
+ * The output row is the chosen candidate, bit for bit.  The critic is the twin Q of the context set by
+ * iqlhip_jsrl_set_critics — critics == NULL or critics[k] == NULL: the member's learner; otherwise a bound context on
+ * the learner's device with its state_dim and action_dim (IQLHIP_EINVAL / IQLHIP_ENOTBOUND), e.g. a frozen offline
+ * critic.  It runs at its own precision.  The contexts must outlive the handle.
+ * Launches: a call without a `3` launches exactly what iqlhip_jsrl_act launches.  With one, five for any K: pack (the
+ * states also into both halves of the critic's rows), the policy and gate forwards, candidates (the finish launch,
+ * which finishes rows with 0..2 as before and writes [s | a_g] to row r and [s | a_l] to row n + r of the critic's
+ * packed act rows), ONE Q forward per precision kind (two records per member, instances Q1 and Q2, over 2 n rows),
+ * select.  The handle owns those rows and partials (allocated by the first call that has a `3`).
+ * q_out[k] (NULL table or entry: not written) receives [rows[k]][4] floats (Q1g, Q2g, Q1l, Q2l) per row, NaN on rows
+ * whose byte is not 3.  Counters as in iqlhip_jsrl_act; the critic's never move.
+ * Checked before any launch or counter change, on top of iqlhip_jsrl_act's checks (who in 0..3 here): IQLHIP_EINVAL for
+ * q_inv_temp[k] negative or NaN, a `3` with q_inv_temp == NULL, a q_out entry on a member without a `3`, 2 * rows[k]
+ * above the smallest act capacity of learner, guide, gate and critic for a member with a `3`; IQLHIP_ENOTBOUND for an
+ * unbound critic.  iqlhip_jsrl_act and iqlhip_jsrl_online_step still refuse a `3`. */
+int iqlhip_jsrl_set_critics(iqlhip_jsrl* jsrl, iqlhip_ctx* const* critics);
+int iqlhip_jsrl_act_q(iqlhip_jsrl* jsrl, const float* const* states, int64_t ld_s, const int32_t* rows,
+                      const int8_t* const* who, const float* gate_max, const uint64_t* seeds,
+                      const float* max_action_learner, const float* max_action_guide, float* const* actions, int64_t ld_a,
+                      int32_t* const* use_learner, float* const* gate_out, const float* q_inv_temp, float* const* q_out,
+                      int32_t flags, void* stream);
 /* One online iteration of a K = 1 handle's learner plus the next action's selection, under ONE synchronisation: the
  * ring write, gather and step of iqlhip_online_step without an act (same arguments, same checks), then the one-row
  * selection above with the just-updated learner — state, action, flag and h travel through host-mapped words.  Losses

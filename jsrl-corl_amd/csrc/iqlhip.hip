@@ -4802,6 +4802,7 @@ extern "C" int iqlhip_rows_episode_returns(const float* rows_dev, int64_t ld, in
 // included HERE, behind every other kernel of the file).  Pack (iql_pack_states_group_kernel), forward
 // (iql_act_fwd_group_kernel over the call's records) and finish, with the records uploaded as the group act uploads its.
 #include "iqlhip_jsrl_kernels.h"
+#include "iqlhip_jsrl_q_kernels.h"
 
 struct iqlhip_jsrl {
   int k = 0;
@@ -4809,6 +4810,7 @@ struct iqlhip_jsrl {
   iqlhip_ctx* l[IQLHIP_MAX_GROUP] = {};      // learners
   iqlhip_ctx* g[IQLHIP_MAX_GROUP] = {};      // guides
   iqlhip_ctx* v[IQLHIP_MAX_GROUP] = {};      // gates (entries may be NULL)
+  iqlhip_ctx* c[IQLHIP_MAX_GROUP] = {};      // critics of who == 3 (iqlhip_jsrl_set_critics; NULL: the member's learner)
   int cap[IQLHIP_MAX_GROUP] = {};            // the smallest act capacity of the triple
   Owned own;
   // per member: the packed states (the learner's row stride; xb_v: the gate's own copy where its stride differs, else
@@ -4818,10 +4820,15 @@ struct iqlhip_jsrl {
   float* heads_l[IQLHIP_MAX_GROUP] = {};
   float* heads_g[IQLHIP_MAX_GROUP] = {};
   float* heads_v[IQLHIP_MAX_GROUP] = {};
+  // who == 3 (allocated by the first call that has one): the critic's packed act rows [cap][row_ld] — row r the guide's
+  // candidate, row n + r the learner's — and its scalar head partials [cap][HEAD_LD]
+  float* xq[IQLHIP_MAX_GROUP] = {};
+  float* heads_q[IQLHIP_MAX_GROUP] = {};
   // the call's records (built in `host`, uploaded through act.pin when their used part differs from the last upload's):
-  // packs [2 k], forwards [3 k], finishes [k], then the members' who bytes, back to back from `who`
+  // packs [4 k], forwards [5 k], finishes [k], critic records [k], then the members' who bytes, back to back from `who`
   Staging act;
-  Section<GroupPackRec> packs; Section<StepParams> ps; Section<JsrlFinRec> fins; Section<signed char> who;
+  Section<GroupPackRec> packs; Section<StepParams> ps; Section<JsrlFinRec> fins; Section<JsrlQRec> qrecs;
+  Section<signed char> who;
   std::vector<char> host, last;
   size_t last_used = 0;
   hipEvent_t up = nullptr;
@@ -4887,9 +4894,10 @@ extern "C" int iqlhip_jsrl_create(iqlhip_ctx* const* learners, iqlhip_ctx* const
       for (const iqlhip_ctx* c : {(const iqlhip_ctx*)l, (const iqlhip_ctx*)g, (const iqlhip_ctx*)v})
         if (c) lds = std::max(lds, c->lds_fwd_solo);
     }
-    j->packs = j->act.add<GroupPackRec>(2 * (size_t)k);
-    j->ps = j->act.add<StepParams>(3 * (size_t)k);
+    j->packs = j->act.add<GroupPackRec>(4 * (size_t)k);
+    j->ps = j->act.add<StepParams>(5 * (size_t)k);
     j->fins = j->act.add<JsrlFinRec>(k);
+    j->qrecs = j->act.add<JsrlQRec>(k);
     j->who = j->act.add<signed char>(who_bytes);
     if (int rc_s = j->act.alloc(j->own)) return rc_s;
     j->host.assign(j->act.bytes, 0);
@@ -4911,13 +4919,16 @@ extern "C" int iqlhip_jsrl_create(iqlhip_ctx* const* learners, iqlhip_ctx* const
 }
 
 // What the host reads out of `who` before anything is launched: which forwards member i needs.
-struct JsrlPlan { bool need_l[IQLHIP_MAX_GROUP], need_g[IQLHIP_MAX_GROUP], need_v[IQLHIP_MAX_GROUP]; };
+// need_q: the member has a `3` (iqlhip_jsrl_act_q only): both policy forwards, then the critic's stage.
+struct JsrlPlan { bool need_l[IQLHIP_MAX_GROUP], need_g[IQLHIP_MAX_GROUP], need_v[IQLHIP_MAX_GROUP], need_q[IQLHIP_MAX_GROUP]; };
+// What iqlhip_jsrl_act_q adds to a call's arguments.
+struct JsrlQArgs { const float* inv_temp; float* const* q_out; };
 
-// Every check of iqlhip_jsrl_act; moves and launches nothing.
+// Every check of iqlhip_jsrl_act; moves and launches nothing.  who_max: the largest byte the entry point accepts.
 static int jsrl_check(const iqlhip_jsrl* j, const float* const* states, int64_t ld_s, const int32_t* rows,
                       const int8_t* const* who, const float* gate_max, const uint64_t* seeds, const float* max_l,
                       const float* max_g, float* const* actions, int64_t ld_a, float* const* gate_out, int32_t flags,
-                      JsrlPlan* plan) {
+                      JsrlPlan* plan, int who_max = 2) {
   if (!j) return fail(IQLHIP_EINVAL, "NULL handle");
   if (!states || !rows || !who || !seeds || !max_l || !max_g || !actions) return fail(IQLHIP_EINVAL, "NULL argument");
   int rc = jsrl_check_triples(j->l, j->g, j->v, j->k);
@@ -4932,17 +4943,18 @@ static int jsrl_check(const iqlhip_jsrl* j, const float* const* states, int64_t 
     if (l->act_drop_p > 0.f || g->act_drop_p > 0.f)
       return fail(IQLHIP_EUNSUPPORTED, "member %d: inference dropout (iqlhip_set_act_dropout) is not supported here", i);
     if (rows[i] < 0 || rows[i] > j->cap[i]) return fail(IQLHIP_EINVAL, "member %d: rows %d outside [0, %d]", i, rows[i], j->cap[i]);
-    plan->need_l[i] = plan->need_g[i] = plan->need_v[i] = false;
+    plan->need_l[i] = plan->need_g[i] = plan->need_v[i] = plan->need_q[i] = false;
     if (rows[i] == 0) continue;
     if (!states[i] || !who[i] || !actions[i]) return fail(IQLHIP_EINVAL, "member %d: NULL states, who or actions", i);
     if (ld_s < l->dims.state_dim || ld_a < l->dims.action_dim) return fail(IQLHIP_EINVAL, "row stride smaller than the row");
     bool two = false;
     for (int r = 0; r < rows[i]; ++r) {
       const int w = who[i][r];
-      if (w < 0 || w > 2) return fail(IQLHIP_EINVAL, "member %d: who[%d] = %d outside 0..2", i, r, w);
+      if (w < 0 || w > who_max) return fail(IQLHIP_EINVAL, "member %d: who[%d] = %d outside 0..%d", i, r, w, who_max);
       if (w != 0) plan->need_l[i] = true;
       if (w != 1) plan->need_g[i] = true;
       if (w == 2) two = true;
+      if (w == 3) plan->need_q[i] = true;
     }
     const bool wants_h = gate_out && gate_out[i];
     if ((two || wants_h) && !v) return fail(IQLHIP_EINVAL, "member %d: who == 2 or a gate_out entry on a member without a gate", i);
@@ -4958,21 +4970,22 @@ static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const
                         const int8_t* const* who, const float* gate_max, const uint64_t* seeds, const float* max_l,
                         const float* max_g, float* const* actions, int64_t ld_a, int32_t* const* use_learner,
                         float* const* gate_out, int32_t flags, hipStream_t st, unsigned long long* done_flag,
-                        unsigned long long done_val) {
+                        unsigned long long done_val, const JsrlQArgs* qa = nullptr) {
   const int K = j->k;
   Staging& act = j->act;
   GroupPackRec* packs = Staging::at(j->host.data(), j->packs);
   StepParams* ps = Staging::at(j->host.data(), j->ps);
   JsrlFinRec* fins = Staging::at(j->host.data(), j->fins);
+  JsrlQRec* qrecs = Staging::at(j->host.data(), j->qrecs);
   signed char* who_host = Staging::at(j->host.data(), j->who);
   const signed char* who_dev = act.device(j->who);
   // forward records sorted by kernel variant (bit 0: bf16, bit 1: wide layer-0 staging by LDS-DMA): one launch each
   struct Fwd { StepParams p; int variant; size_t lds; int rows; };
-  Fwd fwd[3 * IQLHIP_MAX_GROUP];
-  int n_fwd = 0, n_pack = 0, n_req = 0, max_rows = 0, max_pack = 0, max_fin = 0;
+  Fwd fwd[3 * IQLHIP_MAX_GROUP], fwd_q[2 * IQLHIP_MAX_GROUP];      // fwd_q: the critics' Q1 and Q2 records (a later launch)
+  int n_fwd = 0, n_fwd_q = 0, n_pack = 0, n_req = 0, max_rows = 0, max_pack = 0, max_fin = 0;
   size_t who_off = 0;
   auto add_fwd = [&](const iqlhip_ctx* c, int n, const float* xb, float* heads, int inst) {
-    Fwd& f = fwd[n_fwd++];
+    Fwd& f = (inst == 4 || inst == 5) ? fwd_q[n_fwd_q++] : fwd[n_fwd++];
     f.p = act_step_params(c, n);
     f.p.xb = xb;
     f.p.only_inst = inst;
@@ -5000,6 +5013,23 @@ static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const
     if (plan.need_l[i]) add_fwd(l, n, j->xb[i], j->heads_l[i], 6);
     if (plan.need_g[i]) add_fwd(g, n, j->xb[i], j->heads_g[i], 6);
     if (plan.need_v[i]) add_fwd(v, n, j->xb_v[i], j->heads_v[i], 1);
+    JsrlQRec& qr = qrecs[n_req];
+    qr = JsrlQRec{};
+    if (plan.need_q[i]) {
+      // both halves of the critic's rows get the states from the same pack launch (columns past S zeroed), then the
+      // candidates launch fills the action columns of the `3` rows; Q1 and Q2 are two records over the 2 n rows
+      const iqlhip_ctx* cq = j->c[i] ? j->c[i] : l;
+      for (int half = 0; half < 2; ++half) {
+        GroupPackRec& pq = packs[n_pack++];
+        pq = pk; pq.xb = j->xq[i] + (size_t)half * n * l->row_ld;
+      }
+      add_fwd(cq, 2 * n, j->xq[i], j->heads_q[i], 4);
+      add_fwd(cq, 2 * n, j->xq[i], j->heads_q[i], 5);
+      qr.xq = j->xq[i]; qr.heads_q = j->heads_q[i];
+      qr.q_out = qa->q_out ? qa->q_out[i] : nullptr;
+      qr.inv_temp = qa->inv_temp[i];
+      qr.ld_q = (int)l->row_ld; qr.S = S;
+    }
     memcpy(who_host + who_off, who[i], (size_t)n);
     JsrlFinRec& f = fins[n_req++];
     f.heads_l = plan.need_l[i] ? j->heads_l[i] : nullptr;
@@ -5021,7 +5051,9 @@ static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const
   }
   if (n_req == 0) return IQLHIP_OK;
   std::stable_sort(fwd, fwd + n_fwd, [](const Fwd& a, const Fwd& b) { return a.variant < b.variant; });
+  std::stable_sort(fwd_q, fwd_q + n_fwd_q, [](const Fwd& a, const Fwd& b) { return a.variant < b.variant; });
   for (int q = 0; q < n_fwd; ++q) ps[q] = fwd[q].p;
+  for (int q = 0; q < n_fwd_q; ++q) ps[n_fwd + q] = fwd_q[q].p;
   const size_t used = j->who.off + who_off;
   if (used != j->last_used || memcmp(j->host.data(), j->last.data(), used) != 0) {
     if (j->pending) HIPCHK(hipEventSynchronize(j->up));    // the previous upload has read act.pin
@@ -5040,23 +5072,35 @@ static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const
     if (plan.need_l[i]) refresh_shadows(j->l[i], st);
     if (plan.need_g[i] && j->g[i] != j->l[i]) refresh_shadows(j->g[i], st);
     if (plan.need_v[i]) refresh_shadows(j->v[i], st);
+    if (plan.need_q[i] && j->c[i] && j->c[i] != j->l[i]) refresh_shadows(j->c[i], st);
   }
-  for (int q0 = 0; q0 < n_fwd;) {
-    int q1 = q0, fr = 0;
-    size_t lds = 0;
-    for (; q1 < n_fwd && fwd[q1].variant == fwd[q0].variant; ++q1) { fr = std::max(fr, fwd[q1].rows); lds = std::max(lds, fwd[q1].lds); }
-    const int nbx = (fr + RT_ROWS - 1) / RT_ROWS * NSPLIT;
-    hipLaunchKernelGGL(act_fwd_group_kernel(fwd[q0].variant & 1, fwd[q0].variant & 2), dim3(nbx, q1 - q0), dim3(256), lds, st,
-                       act.device(j->ps) + q0);
-    q0 = q1;
-  }
+  // one launch per kernel variant over records [first, first + count) of the uploaded table
+  auto launch_fwds = [&](const Fwd* fw, int count, int first) {
+    for (int q0 = 0; q0 < count;) {
+      int q1 = q0, fr = 0;
+      size_t lds = 0;
+      for (; q1 < count && fw[q1].variant == fw[q0].variant; ++q1) { fr = std::max(fr, fw[q1].rows); lds = std::max(lds, fw[q1].lds); }
+      const int nbx = (fr + RT_ROWS - 1) / RT_ROWS * NSPLIT;
+      hipLaunchKernelGGL(act_fwd_group_kernel(fw[q0].variant & 1, fw[q0].variant & 2), dim3(nbx, q1 - q0), dim3(256), lds, st,
+                         act.device(j->ps) + first + q0);
+      q0 = q1;
+    }
+  };
+  launch_fwds(fwd, n_fwd, 0);
   if (done_flag) {
-    if (n_req != 1 || max_fin > 256) return fail(IQLHIP_EINVAL, "a completion flag needs a one-block finish launch");
+    if (n_req != 1 || max_fin > 256 || n_fwd_q) return fail(IQLHIP_EINVAL, "a completion flag needs a one-block finish launch");
     hipLaunchKernelGGL(iql_jsrl_finish_done_kernel, dim3(1), dim3(256), 0, st, act.device(j->fins), done_flag, done_val);
     HIPCHK(hipGetLastError());
     return IQLHIP_OK;
   }
-  hipLaunchKernelGGL(iql_jsrl_finish_kernel, dim3((max_fin + 255) / 256, n_req), dim3(256), 0, st, act.device(j->fins));
+  if (n_fwd_q == 0) {
+    hipLaunchKernelGGL(iql_jsrl_finish_kernel, dim3((max_fin + 255) / 256, n_req), dim3(256), 0, st, act.device(j->fins));
+  } else {      // candidates, the critics' Q forward over them, select (include/iqlhip.h iqlhip_jsrl_act_q)
+    const dim3 grid((max_fin + 255) / 256, n_req);
+    hipLaunchKernelGGL(iql_jsrl_q_cand_kernel, grid, dim3(256), 0, st, act.device(j->fins), act.device(j->qrecs));
+    launch_fwds(fwd_q, n_fwd_q, n_fwd);
+    hipLaunchKernelGGL(iql_jsrl_q_select_kernel, grid, dim3(256), 0, st, act.device(j->fins), act.device(j->qrecs));
+  }
   if (!(flags & IQLHIP_GROUP_ACT_WAIT)) {
     HIPCHK(hipGetLastError());
     return IQLHIP_OK;
@@ -5079,6 +5123,69 @@ extern "C" int iqlhip_jsrl_act(iqlhip_jsrl* j, const float* const* states, int64
   DevGuard guard(j->device);
   return jsrl_enqueue(j, plan, states, ld_s, rows, who, gate_max, seeds, max_action_learner, max_action_guide, actions,
                       ld_a, use_learner, gate_out, flags, (hipStream_t)stream, nullptr, 0);
+}
+
+extern "C" int iqlhip_jsrl_set_critics(iqlhip_jsrl* j, iqlhip_ctx* const* critics) {
+  if (!j) return fail(IQLHIP_EINVAL, "NULL handle");
+  size_t lds = 0;
+  for (int i = 0; i < j->k && critics; ++i) {
+    const iqlhip_ctx* c = critics[i];
+    const iqlhip_ctx* l = j->l[i];
+    if (!c) continue;
+    if (c->device != l->device) return fail(IQLHIP_EINVAL, "member %d: critic on another device", i);
+    if (c->dims.state_dim != l->dims.state_dim || c->dims.action_dim != l->dims.action_dim)
+      return fail(IQLHIP_EINVAL, "member %d: state_dim or action_dim differs between learner and critic", i);
+    if (!c->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called on its critic", i);
+    lds = std::max(lds, c->lds_fwd_solo);
+  }
+  DevGuard guard(j->device);
+  if (lds) {
+    const int rc = set_max_lds(2, lds, [](unsigned m) { return act_fwd_group_kernel(m & 1, m & 2); });
+    if (rc) return rc;
+  }
+  for (int i = 0; i < j->k; ++i) j->c[i] = (critics && critics[i] != j->l[i]) ? critics[i] : nullptr;
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_jsrl_act_q(iqlhip_jsrl* j, const float* const* states, int64_t ld_s, const int32_t* rows,
+                                 const int8_t* const* who, const float* gate_max, const uint64_t* seeds,
+                                 const float* max_action_learner, const float* max_action_guide, float* const* actions,
+                                 int64_t ld_a, int32_t* const* use_learner, float* const* gate_out, const float* q_inv_temp,
+                                 float* const* q_out, int32_t flags, void* stream) {
+  JsrlPlan plan;
+  int rc = jsrl_check(j, states, ld_s, rows, who, gate_max, seeds, max_action_learner, max_action_guide, actions, ld_a,
+                      gate_out, flags, &plan, /*who_max=*/3);
+  if (rc) return rc;
+  bool any = false;
+  for (int i = 0; i < j->k; ++i) {
+    const iqlhip_ctx* c = j->c[i];
+    if (c && !c->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_bind has not been called on its critic", i);
+    if (q_inv_temp && !(q_inv_temp[i] >= 0.f)) return fail(IQLHIP_EINVAL, "member %d: q_inv_temp must be >= 0 (infinite: argmax)", i);
+    if (rows[i] == 0) continue;
+    if (q_out && q_out[i] && !plan.need_q[i]) return fail(IQLHIP_EINVAL, "member %d: a q_out entry on a member without who == 3", i);
+    if (!plan.need_q[i]) continue;
+    if (!q_inv_temp) return fail(IQLHIP_EINVAL, "who == 3 without q_inv_temp");
+    const int cap = std::min(j->cap[i], c ? c->act_cap : j->cap[i]);
+    if (2 * (int64_t)rows[i] > cap)
+      return fail(IQLHIP_EINVAL, "member %d: who == 3 needs 2 * rows (%d) within the act capacity %d", i, rows[i], cap);
+    any = true;
+  }
+  DevGuard guard(j->device);
+  if (any) {      // the critic stage's scratch, made whole or not at all, by the first call that needs it
+    const size_t mark = j->own.mark();
+    for (int i = 0; i < j->k; ++i) {
+      if (!plan.need_q[i] || j->xq[i]) continue;
+      hipError_t e = j->own.dev(&j->xq[i], (size_t)j->cap[i] * j->l[i]->row_ld * sizeof(float), 0);
+      if (e == hipSuccess) e = j->own.dev(&j->heads_q[i], (size_t)j->cap[i] * HEAD_LD * sizeof(float), 0);
+      if (e != hipSuccess) {
+        j->own.rollback(mark);
+        HIPCHK(e);
+      }
+    }
+  }
+  const JsrlQArgs qa{q_inv_temp, q_out};
+  return jsrl_enqueue(j, plan, states, ld_s, rows, who, gate_max, seeds, max_action_learner, max_action_guide, actions,
+                      ld_a, use_learner, gate_out, flags, (hipStream_t)stream, nullptr, 0, &qa);
 }
 
 extern "C" int iqlhip_jsrl_online_step(iqlhip_jsrl* j, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,

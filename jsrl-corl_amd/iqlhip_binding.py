@@ -281,6 +281,11 @@ SYMBOLS = [
                                   C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                   C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
                                   C.c_void_p]),
+    ("iqlhip_jsrl_set_critics", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("iqlhip_jsrl_act_q", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                    C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     ("iqlhip_jsrl_online_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p, C.c_int8,
                                           C.c_float, C.c_uint64, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int32),

@@ -184,16 +184,24 @@ _JSRL_ACCUMULATORS = {"time_step": np.mean, "agent_type": lambda v: 1, "goal_dis
 
 
 @torch.no_grad()
-def eval_actors_jsrl(envs, jsrl, configs, horizon_fn: str, n_episodes: int, seeds, goal_dist=None):
+def eval_actors_jsrl(envs, jsrl, configs, horizon_fn: str, n_episodes: int, seeds, goal_dist=None, who=None,
+                     q_inv_temp=None):
     """jsrl_w_iql.eval_actor (guide and learner mixed per step) for every member of `jsrl` in lockstep, on ONE
     jsrl.act per round: returns per member (episode returns, mean success, horizon, mean agent type).  configs[k] is
     the member's JsrlTrainConfig; its ep_agent_type is maintained as the reference does (0 at an episode's first step,
     then the mean of the episode's choices so far); the episode horizons are accumulated with the reference's
     accumulator of `horizon_fn` — or, for a member without a guide and config.max_init_horizon, with max.  The
-    `variance` horizon is the gate's value, compared on the device with config.curriculum_stage."""
+    `variance` horizon is the gate's value, compared on the device with config.curriculum_stage.
+    who: None, or per member None (the horizon rule decides) or a byte that replaces the rule's at every step — 3, the
+    member's critic picks (JsrlActors(..., critics=...)), is written this way: the horizon rules never produce it.
+    q_inv_temp goes to jsrl.act as it is."""
     from iqlhip_jsrl import who_from_config
     envs, configs, seeds = list(envs), list(configs), list(seeds)
     K = len(envs)
+    fixed = [None] * K if who is None else list(who)
+    if len(fixed) != K:
+        raise ValueError(f"eval_actors_jsrl: who needs one entry per member ({K})")
+    more = {} if q_inv_temp is None else {"q_inv_temp": q_inv_temp}
     if len(configs) != K or len(seeds) != K or len(jsrl.learners) != K:
         raise ValueError(f"eval_actors_jsrl: {K} envs, {len(configs)} configs, {len(seeds)} seeds and "
                          f"{len(jsrl.learners)} JSRL members (one each)")
@@ -213,17 +221,17 @@ def eval_actors_jsrl(envs, jsrl, configs, horizon_fn: str, n_episodes: int, seed
     while live:
         for k in live:
             configs[k].ep_agent_type = 0 if ts[k] == 0 else np.mean(ep_types[k])
-        who, hz = who_from_config([configs[k] for k in live], horizon_fn, [ts[k] for k in live],
+        who_k, hz = who_from_config([configs[k] for k in live], horizon_fn, [ts[k] for k in live],
                                   [state[k] for k in live], [envs[k] for k in live], goal_dist=goal_dist)
         who_all, gate_max = [None] * K, [0.0] * K
         for j, k in enumerate(live):
-            who_all[k] = who[j]
+            who_all[k] = who_k[j] if fixed[k] is None else np.array([fixed[k]], dtype=np.int8)
             stage = configs[k].curriculum_stage
             gate_max[k] = 0.0 if np.isnan(stage) else float(stage)
-        got = jsrl.act([state[k] if k in live else None for k in range(K)], who_all, gate_max)
+        got = jsrl.act([state[k] if k in live else None for k in range(K)], who_all, gate_max, **more)
         still = []
         for j, k in enumerate(live):
-            acts, use, h = got[k]
+            acts, use, h = got[k][:3]
             action, use_learner = acts[0], bool(use[0])
             if getattr(configs[k], "discrete", False) and use_learner and jsrl.guides[k] is not None:
                 action = np.argmax(action)
