@@ -3,6 +3,7 @@
 #include "iqlhip_kernels.h"
 #include "iqlhip_lb_kernels.h"
 #include "iqlhip_owned.h"
+#include "iqlhip_staging.h"
 
 #include <dlfcn.h>
 
@@ -48,7 +49,9 @@ static inline int64_t up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 struct HipApi {
   using err_t = hipError_t;
   using event_t = hipEvent_t;
+  using stream_t = hipStream_t;
   static constexpr err_t ok = hipSuccess;
+  static constexpr unsigned event_no_timing = hipEventDisableTiming;
   static err_t dev_alloc(void** p, size_t n) { return hipMalloc(p, n); }
   static err_t dev_fill(void* p, int byte, size_t n) { return hipMemset(p, byte, n); }
   static err_t dev_free(void* p) { return hipFree(p); }
@@ -56,8 +59,13 @@ struct HipApi {
   static err_t pin_free(void* p) { return hipHostFree(p); }
   static err_t event_create(event_t* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
   static err_t event_destroy(event_t e) { return hipEventDestroy(e); }
+  static err_t copy_to_dev(void* dst, const void* src, size_t n, stream_t st) { return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st); }
+  static err_t event_record(event_t e, stream_t st) { return hipEventRecord(e, st); }
+  static err_t event_wait(event_t e) { return hipEventSynchronize(e); }
 };
 using Owned = OwnedT<HipApi>;
+using Staging = StagingT<HipApi>;                // launch records: pinned block, device block, upload event (iqlhip_staging.h)
+using CachedStaging = CachedStagingT<HipApi>;    // ... uploaded only when they differ from the last upload
 extern "C" int64_t iqlhip_debug_live_buffers(void) { return Owned::live().load(std::memory_order_relaxed); }
 // All of `allocate`'s allocations or none: on an error what it made is freed and its pointers are null again (the
 // error message stays), so the caller's "already allocated" test, whichever pointer it looks at, is false again.
@@ -2950,29 +2958,7 @@ extern "C" int iqlhip_debug_read(iqlhip_ctx* c, const char* name, float* host_ou
 // A group created with IQLHIP_GROUP_DROPOUT also uploads one GroupDropRec per member in that copy: the members' actor
 // dropout keep-bits are drawn by the group's own launches, each from the member's own stream (seed, rate, position).
 
-// A block of launch records that exists twice: `pin`, pinned host memory the host writes, and `dev`, the device memory
-// one hipMemcpyAsync brings it to.  Sections are appended in order (add), each at the next 256-byte boundary; a
-// Section<T> is the typed handle of one, host() / device() its view in either copy, at() in any buffer of the same layout.
-template <class T> struct Section { size_t off = 0; };
-struct Staging {
-  char* dev = nullptr;
-  char* pin = nullptr;
-  size_t bytes = 0;
-  template <class T> Section<T> add(size_t count) {
-    Section<T> s;
-    s.off = (size_t)up((int64_t)bytes, 256);
-    bytes = s.off + count * sizeof(T);
-    return s;
-  }
-  template <class T> static T* at(char* base, Section<T> s) { return (T*)(base + s.off); }
-  template <class T> T* host(Section<T> s) const { return at(pin, s); }
-  template <class T> const T* device(Section<T> s) const { return at(dev, s); }
-  int alloc(Owned& own) {      // (the pinned copy starts zeroed: records are uploaded — and compared — whole, padding included)
-    HIPCHK(own.dev(&dev, bytes));
-    HIPCHK(own.pin(&pin, bytes, /*zero=*/true));
-    return IQLHIP_OK;
-  }
-};
+// (Staging, Section<T>: iqlhip_staging.h.)
 // The per-member records of the opt-in features that look at a step's gradient, as they lie in a staging: the
 // statistics records, the clip records, and the records the block-partial launch runs under when some member clips.
 struct AuxSections {
@@ -2981,6 +2967,21 @@ struct AuxSections {
     srecs = s.add<GroupStatsRec>(k);
     crecs = s.add<GroupClipRec>(k);
     gqrecs = s.add<GroupStatsRec>(k);
+  }
+};
+// A staging the group's training calls run from, and what every one of them has in it: the agents' records (one set,
+// or one per half of the members' double-buffered rows), the dropout records, the statistics / clip records per set,
+// and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS] — the staging's last section: upload_steps copies up to their
+// used rows.  The owner lays it out (its other sections lie between these).
+struct GroupStage {
+  Staging stg;
+  Section<GroupRec> recs[2]; Section<GroupDropRec> drops; AuxSections aux[2]; Section<iqlhip_step_scalars> tabs;
+  // Agent i's scalar table: the host copy the caller's rows go to, and its device address.
+  iqlhip_step_scalars* tab(int i) const { return stg.host(tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
+  const iqlhip_step_scalars* sched(int i) const { return stg.device(tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
+  // records + the first n rows of every one of the k agents' tables (the tables are strided by IQLHIP_GROUP_MAX_STEPS)
+  hipError_t upload_steps(int k, int n, hipStream_t st) {
+    return stg.upload(tabs.off + ((size_t)(k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars), st);
   }
 };
 
@@ -2992,11 +2993,9 @@ struct iqlhip_group {
   int flags = 0;                      // IQLHIP_GROUP_*
   iqlhip_ctx* m[IQLHIP_MAX_GROUP] = {};
   Owned own;                          // every buffer and event of the group (the members own theirs)
-  // iqlhip_group_step / iqlhip_group_train_steps: the agents' records, the IQLHIP_GROUP_DROPOUT records (no rows
-  // without the flag), the statistics / clip records and the scalar tables, [k][IQLHIP_GROUP_MAX_STEPS] — the tables
-  // last: group_upload copies up to their used rows
-  Staging train;
-  Section<GroupRec> recs; Section<GroupDropRec> drops; AuxSections aux; Section<iqlhip_step_scalars> tabs;
+  // iqlhip_group_step / iqlhip_group_train_steps: one record set, dropout records only with IQLHIP_GROUP_DROPOUT (no rows
+  // without the flag).  (An asynchronous call: the staging waits for its upload before the next call rewrites it.)
+  GroupStage train;
   Section<GroupWtRec> wts;            // iqlhip_group_train_steps_weighted: one table record per member (before the tables)
   // clip_ones: three floats of 1.0f, the coefficients a member without clipping reads (allocated by the first call
   // with a clipping member)
@@ -3009,9 +3008,8 @@ struct iqlhip_group {
   float* ring_dev = nullptr;          // [k][IQLHIP_GROUP_MAX_STEPS][4] losses of the last call
   float* ring_pin = nullptr;
   int last_n = 0;                     // steps of the last call (rows of the ring that are valid)
-  hipEvent_t up_done = nullptr;       // the last upload has read train.pin
-  bool up_pending = false;
-  // iqlhip_group_online_step: its own records (a synchronous call — the staging is free again when it returns): the
+  // iqlhip_group_online_step: its own records (a synchronous call — the staging is free again when it returns, so it
+  // has no upload event): the
   // agents' records, the act forwards' and the ring writes + gathers', the act finishes', the dropout records (as above)
   // and one row of scalars per agent
   Staging on;
@@ -3020,19 +3018,15 @@ struct iqlhip_group {
   AuxSections on_aux;
   unsigned long long* done_pin = nullptr;   // host-mapped completion word of the call (the host spins on it)
   unsigned long long done_seq = 0;
-  // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in act_host (the
-  // same layout); uploaded through act.pin only when they differ from the last upload (act_last) — an evaluation loop's
-  // calls repeat theirs.  (An asynchronous call: the next upload waits for act_up, this one's, before it rewrites act.pin.)
-  Staging act;
+  // iqlhip_group_actor_forward: its own records — the state packs', the forwards', the finishes' — built in the staging's
+  // build buffer and uploaded only when they differ from the last upload: an evaluation loop's calls repeat theirs.
+  CachedStaging act;
   Section<GroupPackRec> act_packs; Section<StepParams> act_ps; Section<GroupActRowsRec> act_fins;
   Section<ActDropRec> act_drops;      // (IQLHIP_GROUP_DROPOUT groups: the inference keep-bit draws, indexed like act_packs)
-  std::vector<char> act_host, act_last;
-  hipEvent_t act_up = nullptr;
-  bool act_pending = false;
   // iqlhip_group_score_rows: the scratch of a chunk of every member — member i's regions start at i * score_chunk rows
   // (score_chunk = the largest chunk a member scores: 65 536 / k rows, so the k members together take what one solo
-  // context's scratch takes) — and the call's records, which go the way the act records go (score_host / score_last /
-  // score_up).  All of it is allocated by the group's first scoring call; a group that never scores holds none.
+  // context's scratch takes) — and the call's records, which go the way the act records go.  All of it is
+  // allocated by the group's first scoring call; a group that never scores holds none.
   int score_chunk = 0;
   float* score_heads = nullptr;       // device [k][score_chunk][HEAD_LD]
   float* score_pi = nullptr;          // device [k][score_chunk][A][NSPLIT]
@@ -3041,23 +3035,17 @@ struct iqlhip_group {
   double* score_acc = nullptr;        // device [k][16]: the call's running sums
   float* score_pin = nullptr;         // pinned, host-mapped [k][16]: the summaries' landing words
   unsigned long long* score_status = nullptr;   // pinned, host-mapped [k][2]: the index check's verdicts
-  Staging score;
+  CachedStaging score;
   Section<ScoreParams> score_ps; Section<ScoreRowsParams> score_qs; Section<ScoreGroupAux> score_aux;
-  std::vector<char> score_host, score_last;
-  hipEvent_t score_up = nullptr;
-  bool score_pending = false;
   // iqlhip_group_step_rw, iqlhip_group_train_steps_weighted_is / _prioritized (DESIGN.md 6j "trainer groups"): a staging
   // of their own, allocated by the group's first such call — the plain calls upload what they always did.  The agents'
   // records twice — set h has the pointers of staging half h: a burst's step s runs under set s & 1, an eager step under
   // set 0 — the dropout records (k, whatever the flags), the statistics / clip records per set, the row-weight and the
-  // draw / update records, and the scalar tables last (group_rw_upload copies up to their used rows).
+  // draw / update records (rw_rws, rw_prs), and the scalar tables last.
   // rw_ones: max over the members' max_batch floats of 1.0f, the weights of a member given none.
-  Staging rw;
-  Section<GroupRec> rw_recs[2]; Section<GroupDropRec> rw_drops; AuxSections rw_aux[2];
-  Section<GroupRwRec> rw_rws; Section<GroupPrioRec> rw_prs; Section<iqlhip_step_scalars> rw_tabs;
+  GroupStage rw;
+  Section<GroupRwRec> rw_rws; Section<GroupPrioRec> rw_prs;
   float* rw_ones = nullptr;
-  hipEvent_t rw_up = nullptr;
-  bool rw_pending = false;
 };
 
 static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
@@ -3116,11 +3104,12 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
   DevGuard guard(g->device);
   auto setup = [&]() -> int {
     const size_t n_drop = (flags & IQLHIP_GROUP_DROPOUT) ? k : 0;      // (without the flag: the layouts of a plain group)
-    g->recs = g->train.add<GroupRec>(k);
-    g->drops = g->train.add<GroupDropRec>(n_drop);
-    g->aux.add(g->train, k);
-    g->wts = g->train.add<GroupWtRec>(k);
-    g->tabs = g->train.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
+    GroupStage& tr = g->train;
+    tr.recs[0] = tr.stg.add<GroupRec>(k);
+    tr.drops = tr.stg.add<GroupDropRec>(n_drop);
+    tr.aux[0].add(tr.stg, k);
+    g->wts = tr.stg.add<GroupWtRec>(k);
+    tr.tabs = tr.stg.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
     g->on_recs = g->on.add<GroupRec>(k);
     g->on_aps = g->on.add<StepParams>(k);
     g->on_gathers = g->on.add<GroupOnlineRec>(k);
@@ -3133,16 +3122,13 @@ extern "C" int iqlhip_group_create_flags(iqlhip_ctx* const* members, int k, int3
     g->act_ps = g->act.add<StepParams>(k);
     g->act_fins = g->act.add<GroupActRowsRec>(k);
     g->act_drops = g->act.add<ActDropRec>(n_drop);
-    for (Staging* s : {&g->train, &g->on, &g->act})
-      if (int rc_s = s->alloc(g->own)) return rc_s;
-    g->act_host.assign(g->act.bytes, 0);
-    g->act_last.assign(g->act.bytes, 1);     // (differs from any first call's records: the first call uploads)
+    HIPCHK(tr.stg.alloc(g->own));
+    HIPCHK(g->on.alloc(g->own, /*with_event=*/false));
+    HIPCHK(g->act.alloc(g->own));
     const size_t ring = (size_t)k * IQLHIP_GROUP_MAX_STEPS * 4 * sizeof(float);
     HIPCHK(g->own.dev(&g->ring_dev, ring, 0));
     HIPCHK(g->own.pin(&g->ring_pin, ring));
     HIPCHK(g->own.pin(&g->done_pin, 8 * sizeof(unsigned long long), /*zero=*/true));
-    HIPCHK(g->own.event(&g->up_done, hipEventDisableTiming));
-    HIPCHK(g->own.event(&g->act_up, hipEventDisableTiming));
     const iqlhip_ctx* c = members[0];
     int rc_a = set_max_lds(3, c->lds_fwd_solo, [](unsigned m) { return fwd_group_kernel(m & 1, m & 2, m & 4); });
     if (!rc_a) rc_a = set_max_lds(2, c->lds_bwd, [](unsigned m) { return bwd_group_kernel(m & 1, m & 2); });
@@ -3293,27 +3279,6 @@ static void group_launch_dropmask(iqlhip_group* g, const GroupDropRec* drops, in
     if (group_draws(g->m[i])) g->m[i]->drop_step += 1;
 }
 
-// Wait until the previous upload has read the pinned staging (normally long done: the host builds the next call's
-// records while the GPU runs this one's steps).
-static int group_staging_free(iqlhip_group* g) {
-  if (g->up_pending) HIPCHK(hipEventSynchronize(g->up_done));
-  g->up_pending = false;
-  return IQLHIP_OK;
-}
-
-static int group_upload(iqlhip_group* g, int n, hipStream_t st) {
-  // records + the used rows of every agent's table (the tables are strided by IQLHIP_GROUP_MAX_STEPS)
-  const size_t bytes = g->tabs.off + ((size_t)(g->k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars);
-  HIPCHK(hipMemcpyAsync(g->train.dev, g->train.pin, bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(g->up_done, st));
-  g->up_pending = true;
-  return IQLHIP_OK;
-}
-
-// Agent i's scalar table of a train-staging call: the host copy the caller's rows go to, and its device address.
-static iqlhip_step_scalars* group_tab(const iqlhip_group* g, int i) { return g->train.host(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
-static const iqlhip_step_scalars* group_sched(const iqlhip_group* g, int i) { return g->train.device(g->tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
-
 // The device copies of a call's per-member statistics / clip records; nullptr: no member has the feature on.
 struct GroupAux { const GroupStatsRec* srecs = nullptr; const GroupClipRec* crecs = nullptr; const GroupStatsRec* gqrecs = nullptr; };
 // Build them in staging `s` at sections `x` from the members' step records (host side) and point `aux` at their device
@@ -3415,23 +3380,19 @@ static int group_losses_out(iqlhip_group* g, float* out, int n, hipStream_t st) 
   return IQLHIP_OK;
 }
 
-// The row-weighted calls' staging (iqlhip_group::rw; defined with their entry points at the end of the file): everything
-// they need beyond the members' own buffers, made by the group's first such call; the wait for the previous upload's read
-// of the pinned copy; the upload; member i's scalar table in it; and the step's row-weight records from the caller's arrays.
+// The row-weighted calls (defined with their entry points at the end of the file, where GroupRwRec / GroupPrioRec are
+// complete): their staging (iqlhip_group::rw) and everything else they need beyond the members' own buffers, made by the
+// group's first such call; the eager call's checks; and the step's row-weight records from the caller's arrays.
 struct GroupRwArgs { const float* const* w; float* const* td; };
 static int group_rw_ready(iqlhip_group* g);
-static int group_rw_staging_free(iqlhip_group* g);
-static int group_rw_upload(iqlhip_group* g, int n, hipStream_t st);
-static iqlhip_step_scalars* group_rw_tab(const iqlhip_group* g, int i);
-static const iqlhip_step_scalars* group_rw_sched(const iqlhip_group* g, int i);
 static int group_rw_check_eager(const iqlhip_group* g, const int32_t* rows, const GroupRwArgs& a);
 static const GroupRwRec* group_rw_records(iqlhip_group* g, const GroupRwArgs& a);
 
 // iqlhip_group_step (mixed = false: every batch has batches[0]'s rows) and iqlhip_group_step_mixed.
 // iqlhip_group_step_rw (rwa != nullptr; mixed): the same step from the row-weighted calls' staging, its backward the
-// row-weighted one.
-static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out, void* stream,
-                      bool mixed, const GroupRwArgs* rwa = nullptr) {
+// row-weighted one.  `stage`: the staging the step runs from (record set 0).
+static int group_step(iqlhip_group* g, GroupStage iqlhip_group::* stage, const iqlhip_batch* batches, const iqlhip_step_scalars* sc,
+                      float* out, void* stream, bool mixed, const GroupRwArgs* rwa = nullptr) {
   if (!g || !batches || !sc) return fail(IQLHIP_EINVAL, "NULL argument");
   GroupRows rows = group_rows_all(batches[0].rows);
   if (mixed)
@@ -3449,11 +3410,9 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
   if (rwa && (rc = group_rw_ready(g))) return rc;
   for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   hipStream_t st = (hipStream_t)stream;
-  rc = rwa ? group_rw_staging_free(g) : group_staging_free(g);
-  if (rc) return rc;
-  const Staging& stg = rwa ? g->rw : g->train;
-  const Section<GroupRec> s_recs = rwa ? g->rw_recs[0] : g->recs;
-  const Section<GroupDropRec> s_drops = rwa ? g->rw_drops : g->drops;
+  GroupStage& sg = g->*stage;
+  Staging& stg = sg.stg;
+  HIPCHK(stg.wait_free());
   const GroupGeom q = group_geom(g, rows.v);
   for (int i = 0; i < g->k; ++i) {
     iqlhip_ctx* c = g->m[i];
@@ -3462,28 +3421,27 @@ static int group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip
     rc = stage_batch(c, &batches[i], st, &xb);
     if (rc) return rc;
     refresh_shadows(c, st);
-    group_record(g, stg.host(s_recs)[i], i, q, rows.v[i], 1, xb, &sc[i], rwa ? group_rw_sched(g, i) : group_sched(g, i));
-    (rwa ? group_rw_tab(g, i) : group_tab(g, i))[0] = sc[i];
+    group_record(g, stg.host(sg.recs[0])[i], i, q, rows.v[i], 1, xb, &sc[i], sg.sched(i));
+    sg.tab(i)[0] = sc[i];
   }
-  const int n_draw = group_drop_records_packed(g, stg.host(s_drops), rows.v);
+  const int n_draw = group_drop_records_packed(g, stg.host(sg.drops), rows.v);
   GroupAux aux;
-  if ((rc = group_aux(g, stg, rwa ? g->rw_aux[0] : g->aux, stg.host(s_recs), &aux))) return rc;
+  if ((rc = group_aux(g, stg, sg.aux[0], stg.host(sg.recs[0]), &aux))) return rc;
   const GroupRwRec* rws = rwa ? group_rw_records(g, *rwa) : nullptr;
-  rc = rwa ? group_rw_upload(g, 1, st) : group_upload(g, 1, st);
-  if (rc) return rc;
-  group_launch_dropmask(g, stg.device(s_drops), n_draw, q.max_rows, st);
-  group_launch_step(g, stg.device(s_recs), q, 0, st, aux, rws);
+  HIPCHK(sg.upload_steps(g->k, 1, st));
+  group_launch_dropmask(g, stg.device(sg.drops), n_draw, q.max_rows, st);
+  group_launch_step(g, stg.device(sg.recs[0]), q, 0, st, aux, rws);
   HIPCHK(hipGetLastError());
   g->last_n = 1;
   return group_losses_out(g, out, 1, st);
 }
 extern "C" int iqlhip_group_step(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc, float* out,
                                  void* stream) {
-  return group_step(g, batches, sc, out, stream, /*mixed=*/false);
+  return group_step(g, &iqlhip_group::train, batches, sc, out, stream, /*mixed=*/false);
 }
 extern "C" int iqlhip_group_step_mixed(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc,
                                        float* out, void* stream) {
-  return group_step(g, batches, sc, out, stream, /*mixed=*/true);
+  return group_step(g, &iqlhip_group::train, batches, sc, out, stream, /*mixed=*/true);
 }
 
 // The second source of a two-source group call, per member (the group form of a Mixed ChunkSrc): iqlhip_group_train_steps_replay2
@@ -3535,25 +3493,26 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
   for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
-  rc = group_staging_free(g);
-  if (rc) return rc;
+  GroupStage& sg = g->train;
+  Staging& stg = sg.stg;
+  HIPCHK(stg.wait_free());
   const GroupGeom q = group_geom(g, B);
   for (int i = 0; i < g->k; ++i) {
     iqlhip_ctx* c = g->m[i];
     c->cont.valid = false;             // the staging buffer is overwritten: a later solo call must gather its own rows
     refresh_shadows(c, st);
     const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
-    GroupRec& r = g->train.host(g->recs)[i];
-    group_record(g, r, i, q, B[i], n, c->xb, &tab[0], group_sched(g, i));
+    GroupRec& r = stg.host(sg.recs[0])[i];
+    group_record(g, r, i, q, B[i], n, c->xb, &tab[0], sg.sched(i));
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
     if (mx) { r.rows_on = mx->rows[i]; r.size_on = mx->size[i]; r.n_off = mx->n_off[i]; }
-    memcpy(group_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
-    if (wtabs) g->train.host(g->wts)[i].wt = wtabs[i] ? weights_tab(wtabs[i]) : WTab{nullptr, 0u, 0};
+    memcpy(sg.tab(i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
+    if (wtabs) stg.host(g->wts)[i].wt = wtabs[i] ? weights_tab(wtabs[i]) : WTab{nullptr, 0u, 0};
   }
   // actor dropout: one record per member (indexed like the GroupRecs; active = the member draws), step s at drop_step + s
   bool draws = false;
   if (g->flags & IQLHIP_GROUP_DROPOUT) {
-    GroupDropRec* d = g->train.host(g->drops);
+    GroupDropRec* d = stg.host(sg.drops);
     for (int i = 0; i < g->k; ++i) {
       d[i] = group_drop_record(g->m[i], B[i]);
       d[i].active = group_draws(g->m[i]) ? 1 : 0;
@@ -3561,29 +3520,28 @@ static int group_train_steps(iqlhip_group* g, const float* const* rows, int64_t 
     }
   }
   GroupAux aux;
-  if ((rc = group_aux(g, g->train, g->aux, g->train.host(g->recs), &aux))) return rc;
-  rc = group_upload(g, n, st);
-  if (rc) return rc;
+  if ((rc = group_aux(g, stg, sg.aux[0], stg.host(sg.recs[0]), &aux))) return rc;
+  HIPCHK(sg.upload_steps(g->k, n, st));
   const iqlhip_ctx* c0 = g->m[0];
   // (grids sized by the largest member: every record bounds its own member's rows and words)
   const int gather_nb = (int)std::min<int64_t>(((int64_t)q.max_rows * (c0->row_ld / 4) + 255) / 256, 1024);
   // (a grid with a thread per gathered float4 and per keep-bit word: the words come from its far end)
   const int drop_nb = gather_nb + (2 * q.max_rows * 8 + 255) / 256;
-  const GroupRec* recs = g->train.device(g->recs);
+  const GroupRec* recs = stg.device(sg.recs[0]);
   // weighted: a wave resolves an index and copies that row — a wave per IQL_GROUP_WT_ROWS_PER_WAVE rows of the largest
   // member, four waves a block; with keep-bits, their words fit behind the gather at the far end as above
   const int wt_nb = (q.max_rows + 4 * IQL_GROUP_WT_ROWS_PER_WAVE - 1) / (4 * IQL_GROUP_WT_ROWS_PER_WAVE);
   const int wt_drop_nb = wt_nb + (2 * q.max_rows * 8 + 255) / 256;
-  const GroupWtRec* wts = g->train.device(g->wts);
+  const GroupWtRec* wts = stg.device(g->wts);
   for (int s = 0; s < n; ++s) {
     if (wtabs && draws)
       hipLaunchKernelGGL(iql_gather_weighted_drop_group_kernel, dim3(wt_drop_nb, g->k), dim3(256), 0, st, recs, wts,
-                         g->train.device(g->drops), s);
+                         stg.device(sg.drops), s);
     else if (wtabs)
       hipLaunchKernelGGL(iql_gather_weighted_group_kernel, dim3(wt_nb, g->k), dim3(256), 0, st, recs, wts, s);
     else if (draws)
       hipLaunchKernelGGL(mx ? iql_gather2_drop_group_kernel : iql_gather_drop_group_kernel, dim3(drop_nb, g->k), dim3(256), 0,
-                         st, recs, g->train.device(g->drops), s);
+                         st, recs, stg.device(sg.drops), s);
     else
       hipLaunchKernelGGL(mx ? iql_gather2_group_kernel : iql_gather_group_kernel, dim3(gather_nb, g->k), dim3(256), 0, st,
                          recs, s);
@@ -3747,7 +3705,7 @@ static int group_online_step(iqlhip_group* g, float* const* rows_dev, int64_t ld
   GroupAux aux;
   if ((rc = group_aux(g, on, g->on_aux, recs, &aux))) return rc;
   // (a synchronous call: the previous one's upload has been read long ago)
-  HIPCHK(hipMemcpyAsync(on.dev, on.pin, on.bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(g->on.upload(on.bytes, st));
   const int gather_nb = (int)((q.max_rows * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
   if (act_draws)
     hipLaunchKernelGGL(mx ? iql_online_gather2_drop_group_kernel : iql_online_gather_drop_group_kernel, dim3(gather_nb, K),
@@ -3839,14 +3797,14 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
   if (n_req == 0) return IQLHIP_OK;
   DevGuard guard(g->device);
   hipStream_t st = (hipStream_t)stream;
-  Staging& act = g->act;
-  // (records are written field by field into act_host, whose padding bytes stay zero, or copied whole from a record
-  //  make_step has zeroed: the comparison below sees equal bytes for equal records)
-  GroupPackRec* packs = Staging::at(g->act_host.data(), g->act_packs);
-  StepParams* ps = Staging::at(g->act_host.data(), g->act_ps);
-  GroupActRowsRec* fins = Staging::at(g->act_host.data(), g->act_fins);
+  CachedStaging& act = g->act;
+  // (records are written field by field into the build buffer, whose padding bytes stay zero, or copied whole from a
+  //  record make_step has zeroed: upload_if_changed sees equal bytes for equal records)
+  GroupPackRec* packs = act.build(g->act_packs);
+  StepParams* ps = act.build(g->act_ps);
+  GroupActRowsRec* fins = act.build(g->act_fins);
   const bool with_drops = (g->flags & IQLHIP_GROUP_DROPOUT) != 0;
-  ActDropRec* drops = with_drops ? Staging::at(g->act_host.data(), g->act_drops) : nullptr;
+  ActDropRec* drops = with_drops ? act.build(g->act_drops) : nullptr;
   bool act_draws = false;
   int j = 0;
   for (int i = 0; i < K; ++i) {
@@ -3867,15 +3825,7 @@ extern "C" int iqlhip_group_actor_forward(iqlhip_group* g, const float* const* s
     f.call = seeds[i] != 0 ? c->act_calls++ : 0ull;      // (iqlhip_actor_sample: one call number per call)
     ++j;
   }
-  if (memcmp(g->act_host.data(), g->act_last.data(), act.bytes) != 0) {
-    if (g->act_pending) HIPCHK(hipEventSynchronize(g->act_up));    // the previous upload has read act.pin
-    g->act_pending = false;
-    memcpy(act.pin, g->act_host.data(), act.bytes);
-    HIPCHK(hipMemcpyAsync(act.dev, act.pin, act.bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(g->act_up, st));
-    g->act_pending = true;
-    g->act_last = g->act_host;
-  }
+  HIPCHK(act.upload_if_changed(act.bytes, st));
   const int pack_nb = (int)std::min<int64_t>(((int64_t)max_rows * c0->row_ld + 255) / 256, 1024);
   if (act_draws)           // (a grid with blocks for the longest member's keep-bit words at its far end)
     hipLaunchKernelGGL(iql_pack_states_drop_group_kernel, dim3(pack_nb + (2 * max_rows * 8 + 255) / 256, n_req), dim3(256), 0,
@@ -4186,7 +4136,7 @@ static int ensure_group_score(iqlhip_group* g) {
     const size_t K = (size_t)g->k, cap = (size_t)group_score_cap(g->k);
     const size_t b_heads = K * cap * HEAD_LD * sizeof(float), b_pi = K * cap * c0->dims.action_dim * NSPLIT * sizeof(float),
                  b_part = K * (cap / RT_ROWS) * SCORE_N_PART * sizeof(float), b_out = K * cap * IQLHIP_N_SCORE * sizeof(float);
-    Staging stg;
+    CachedStaging& stg = g->score;      // (laid out and allocated in place: the owner keeps the addresses of its members)
     const int rc = all_or_nothing(g->own, [&]() -> int {
       Owned& own = g->own;
       HIPCHK(own.dev(&g->score_heads, b_heads, 0));
@@ -4199,16 +4149,14 @@ static int ensure_group_score(iqlhip_group* g) {
       g->score_ps = stg.add<ScoreParams>(K);
       g->score_qs = stg.add<ScoreRowsParams>(K);
       g->score_aux = stg.add<ScoreGroupAux>(K);
-      if (int rc_s = stg.alloc(own)) return rc_s;
-      HIPCHK(own.event(&g->score_up, hipEventDisableTiming));
+      HIPCHK(stg.alloc(own));
       return IQLHIP_OK;
     });
-    if (rc) return rc;
-    g->score = stg;
+    if (rc) {
+      stg.bytes = 0;      // (a retry lays out again)
+      return rc;
+    }
     g->score_chunk = (int)cap;
-    g->score_host.assign(stg.bytes, 0);
-    g->score_last.assign(stg.bytes, 1);      // (differs from any first call's records: the first call uploads)
-    g->score_pending = false;
   }
   // every call: the limit belongs to the kernel, not to the group, and another live group of other dims may have set its own
   HIPCHK(hipFuncSetAttribute((const void*)&iql_score_fwd_group_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)score_lds(c0)));
@@ -4248,10 +4196,10 @@ extern "C" int iqlhip_group_score_rows(iqlhip_group* g, const float* const* rows
   const int S = c0->dims.state_dim, A = c0->dims.action_dim;
   const size_t cap = (size_t)g->score_chunk;
 
-  // the members' records (written whole into score_host, whose padding bytes stay zero: equal records compare equal)
-  ScoreParams* ps = Staging::at(g->score_host.data(), g->score_ps);
-  ScoreRowsParams* qs = Staging::at(g->score_host.data(), g->score_qs);
-  ScoreGroupAux* aux = Staging::at(g->score_host.data(), g->score_aux);
+  // the members' records (written whole into the build buffer, whose padding bytes stay zero: equal records compare equal)
+  ScoreParams* ps = g->score.build(g->score_ps);
+  ScoreRowsParams* qs = g->score.build(g->score_qs);
+  ScoreGroupAux* aux = g->score.build(g->score_aux);
   ScoreSpreadSrc src;
   long long src_step[IQLHIP_MAX_GROUP];
   memset(&src, 0, sizeof src);
@@ -4292,15 +4240,7 @@ extern "C" int iqlhip_group_score_rows(iqlhip_group* g, const float* const* rows
     src.src[i] = q.out;
     src_step[i] = a.out_step;
   }
-  if (memcmp(g->score_host.data(), g->score_last.data(), g->score.bytes) != 0) {
-    if (g->score_pending) HIPCHK(hipEventSynchronize(g->score_up));    // the previous upload has read score.pin
-    g->score_pending = false;
-    memcpy(g->score.pin, g->score_host.data(), g->score.bytes);
-    HIPCHK(hipMemcpyAsync(g->score.dev, g->score.pin, g->score.bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(g->score_up, st));
-    g->score_pending = true;
-    g->score_last = g->score_host;
-  }
+  HIPCHK(g->score.upload_if_changed(g->score.bytes, st));
   const ScoreParams* d_ps = g->score.device(g->score_ps);
   const ScoreRowsParams* d_qs = g->score.device(g->score_qs);
   const ScoreGroupAux* d_aux = g->score.device(g->score_aux);
@@ -4824,15 +4764,11 @@ struct iqlhip_jsrl {
   // candidate, row n + r the learner's — and its scalar head partials [cap][HEAD_LD]
   float* xq[IQLHIP_MAX_GROUP] = {};
   float* heads_q[IQLHIP_MAX_GROUP] = {};
-  // the call's records (built in `host`, uploaded through act.pin when their used part differs from the last upload's):
+  // the call's records (built in the staging's build buffer, uploaded when their used part differs from the last upload's):
   // packs [4 k], forwards [5 k], finishes [k], critic records [k], then the members' who bytes, back to back from `who`
-  Staging act;
+  CachedStaging act;
   Section<GroupPackRec> packs; Section<StepParams> ps; Section<JsrlFinRec> fins; Section<JsrlQRec> qrecs;
   Section<signed char> who;
-  std::vector<char> host, last;
-  size_t last_used = 0;
-  hipEvent_t up = nullptr;
-  bool pending = false;
   unsigned long long* done_pin = nullptr;    // completion word of IQLHIP_GROUP_ACT_WAIT calls
   unsigned long long done_seq = 0;
   float* on_pin = nullptr;                   // iqlhip_jsrl_online_step: host-mapped [0] the flag (an int), [1] h
@@ -4899,12 +4835,9 @@ extern "C" int iqlhip_jsrl_create(iqlhip_ctx* const* learners, iqlhip_ctx* const
     j->fins = j->act.add<JsrlFinRec>(k);
     j->qrecs = j->act.add<JsrlQRec>(k);
     j->who = j->act.add<signed char>(who_bytes);
-    if (int rc_s = j->act.alloc(j->own)) return rc_s;
-    j->host.assign(j->act.bytes, 0);
-    j->last.assign(j->act.bytes, 0);
+    HIPCHK(j->act.alloc(j->own));
     HIPCHK(j->own.pin(&j->done_pin, 8 * sizeof(unsigned long long), /*zero=*/true));
     HIPCHK(j->own.pin(&j->on_pin, 8 * sizeof(float), /*zero=*/true));
-    HIPCHK(j->own.event(&j->up, hipEventDisableTiming));
     return set_max_lds(2, lds, [](unsigned m) { return act_fwd_group_kernel(m & 1, m & 2); });
   };
   rc = setup();
@@ -4972,12 +4905,12 @@ static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const
                         float* const* gate_out, int32_t flags, hipStream_t st, unsigned long long* done_flag,
                         unsigned long long done_val, const JsrlQArgs* qa = nullptr) {
   const int K = j->k;
-  Staging& act = j->act;
-  GroupPackRec* packs = Staging::at(j->host.data(), j->packs);
-  StepParams* ps = Staging::at(j->host.data(), j->ps);
-  JsrlFinRec* fins = Staging::at(j->host.data(), j->fins);
-  JsrlQRec* qrecs = Staging::at(j->host.data(), j->qrecs);
-  signed char* who_host = Staging::at(j->host.data(), j->who);
+  CachedStaging& act = j->act;
+  GroupPackRec* packs = act.build(j->packs);
+  StepParams* ps = act.build(j->ps);
+  JsrlFinRec* fins = act.build(j->fins);
+  JsrlQRec* qrecs = act.build(j->qrecs);
+  signed char* who_host = act.build(j->who);
   const signed char* who_dev = act.device(j->who);
   // forward records sorted by kernel variant (bit 0: bf16, bit 1: wide layer-0 staging by LDS-DMA): one launch each
   struct Fwd { StepParams p; int variant; size_t lds; int rows; };
@@ -5054,17 +4987,7 @@ static int jsrl_enqueue(iqlhip_jsrl* j, const JsrlPlan& plan, const float* const
   std::stable_sort(fwd_q, fwd_q + n_fwd_q, [](const Fwd& a, const Fwd& b) { return a.variant < b.variant; });
   for (int q = 0; q < n_fwd; ++q) ps[q] = fwd[q].p;
   for (int q = 0; q < n_fwd_q; ++q) ps[n_fwd + q] = fwd_q[q].p;
-  const size_t used = j->who.off + who_off;
-  if (used != j->last_used || memcmp(j->host.data(), j->last.data(), used) != 0) {
-    if (j->pending) HIPCHK(hipEventSynchronize(j->up));    // the previous upload has read act.pin
-    j->pending = false;
-    memcpy(act.pin, j->host.data(), used);
-    HIPCHK(hipMemcpyAsync(act.dev, act.pin, used, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(j->up, st));
-    j->pending = true;
-    memcpy(j->last.data(), j->host.data(), used);
-    j->last_used = used;
-  }
+  HIPCHK(act.upload_if_changed(j->who.off + who_off, st));
   const int pack_nb = std::min((max_pack + 255) / 256, 1024);
   hipLaunchKernelGGL(iql_pack_states_group_kernel, dim3(pack_nb, n_pack), dim3(256), 0, st, act.device(j->packs));
   for (int i = 0; i < K; ++i) {
@@ -5387,43 +5310,28 @@ static void launch_bwd_group_rw(const iqlhip_ctx* c, const GroupRec* recs, const
 }
 
 static int group_rw_ready(iqlhip_group* g) {
-  if (g->rw.dev) return IQLHIP_OK;
+  GroupStage& rw = g->rw;
+  Staging& s = rw.stg;
+  if (s.dev) return IQLHIP_OK;
   const int k = g->k;
-  Staging s;
-  for (int h = 0; h < 2; ++h) g->rw_recs[h] = s.add<GroupRec>(k);
-  g->rw_drops = s.add<GroupDropRec>(k);
-  for (int h = 0; h < 2; ++h) g->rw_aux[h].add(s, k);
+  for (int h = 0; h < 2; ++h) rw.recs[h] = s.add<GroupRec>(k);
+  rw.drops = s.add<GroupDropRec>(k);
+  for (int h = 0; h < 2; ++h) rw.aux[h].add(s, k);
   g->rw_rws = s.add<GroupRwRec>(k);
   g->rw_prs = s.add<GroupPrioRec>(k);
-  g->rw_tabs = s.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
-  g->rw.bytes = s.bytes;
+  rw.tabs = s.add<iqlhip_step_scalars>((size_t)k * IQLHIP_GROUP_MAX_STEPS);
   int max_batch = 0;
   for (int i = 0; i < k; ++i) max_batch = std::max(max_batch, (int)g->m[i]->dims.max_batch);
   const int rc = all_or_nothing(g->own, [&]() -> int {
-    if (int rc_s = g->rw.alloc(g->own)) return rc_s;
-    HIPCHK(g->own.event(&g->rw_up, hipEventDisableTiming));
+    HIPCHK(s.alloc(g->own));
     HIPCHK(g->own.dev(&g->rw_ones, (size_t)max_batch * sizeof(float)));
     const std::vector<float> ones((size_t)max_batch, 1.f);
     HIPCHK(hipMemcpy(g->rw_ones, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
     return set_max_lds(1, g->m[0]->lds_bwd, [](unsigned m) { return bwd_group_rw_kernel(m & 1); });
   });
-  if (rc) g->rw.dev = g->rw.pin = nullptr;
+  if (rc) s.bytes = 0;      // (the rollback has nulled the blocks and the event; a retry lays out again)
   return rc;
 }
-static int group_rw_staging_free(iqlhip_group* g) {
-  if (g->rw_pending) HIPCHK(hipEventSynchronize(g->rw_up));
-  g->rw_pending = false;
-  return IQLHIP_OK;
-}
-static int group_rw_upload(iqlhip_group* g, int n, hipStream_t st) {
-  const size_t bytes = g->rw_tabs.off + ((size_t)(g->k - 1) * IQLHIP_GROUP_MAX_STEPS + (size_t)n) * sizeof(iqlhip_step_scalars);
-  HIPCHK(hipMemcpyAsync(g->rw.dev, g->rw.pin, bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(g->rw_up, st));
-  g->rw_pending = true;
-  return IQLHIP_OK;
-}
-static iqlhip_step_scalars* group_rw_tab(const iqlhip_group* g, int i) { return g->rw.host(g->rw_tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
-static const iqlhip_step_scalars* group_rw_sched(const iqlhip_group* g, int i) { return g->rw.device(g->rw_tabs) + (size_t)i * IQLHIP_GROUP_MAX_STEPS; }
 
 // `rc` of a solo check as member i's refusal: the message names the member.
 static int member_fail(int i, int rc) {
@@ -5448,16 +5356,16 @@ static int group_rw_check_eager(const iqlhip_group* g, const int32_t* rows, cons
   return IQLHIP_OK;
 }
 static const GroupRwRec* group_rw_records(iqlhip_group* g, const GroupRwArgs& a) {
-  GroupRwRec* r = g->rw.host(g->rw_rws);
+  GroupRwRec* r = g->rw.stg.host(g->rw_rws);
   for (int i = 0; i < g->k; ++i) r[i] = GroupRwRec{a.w[i] ? a.w[i] : g->rw_ones, a.td[i]};
-  return g->rw.device(g->rw_rws);
+  return g->rw.stg.device(g->rw_rws);
 }
 
 extern "C" int iqlhip_group_step_rw(iqlhip_group* g, const iqlhip_batch* batches, const iqlhip_step_scalars* sc,
                                     const float* const* row_w_dev, float* const* td_out_dev, float* out, void* stream) {
   if (!row_w_dev || !td_out_dev) return fail(IQLHIP_EINVAL, "NULL argument");
   const GroupRwArgs a{row_w_dev, td_out_dev};
-  return group_step(g, batches, sc, out, stream, /*mixed=*/true, &a);
+  return group_step(g, &iqlhip_group::rw, batches, sc, out, stream, /*mixed=*/true, &a);
 }
 
 // iqlhip_group_train_steps_weighted_is (alpha == nullptr) and iqlhip_group_train_steps_prioritized.  Per call: the rows of
@@ -5511,10 +5419,12 @@ static int group_train_steps_rw(iqlhip_group* g, const float* const* rows, int64
   }
   for (int i = 0; i < g->k; ++i) note_stream(g->m[i], stream);
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = group_rw_staging_free(g))) return rc;
+  GroupStage& sg = g->rw;
+  Staging& stg = sg.stg;
+  HIPCHK(stg.wait_free());
   const GroupGeom q = group_geom(g, B);
   const int cont_class = prio ? 2 : 1;      // (KindInfo::cont_class of the solo kinds: what lies staged besides the rows)
-  GroupRec* recs_host[2] = {g->rw.host(g->rw_recs[0]), g->rw.host(g->rw_recs[1])};
+  GroupRec* recs_host[2] = {stg.host(sg.recs[0]), stg.host(sg.recs[1])};
   bool all_cont = true;
   for (int i = 0; i < g->k; ++i) {
     iqlhip_ctx* c = g->m[i];
@@ -5531,14 +5441,14 @@ static int group_train_steps_rw(iqlhip_group* g, const float* const* rows, int64
     refresh_shadows(c, st);
     const iqlhip_step_scalars* tab = (const iqlhip_step_scalars*)tables[i];
     GroupRec& r = recs_host[0][i];
-    group_record(g, r, i, q, B[i], n, c->xb, &tab[0], group_rw_sched(g, i));
+    group_record(g, r, i, q, B[i], n, c->xb, &tab[0], sg.sched(i));
     r.rows = rows[i]; r.ld = ld; r.size = size[i]; r.seed = seeds[i]; r.offset = offsets[i];
     GroupRec& r1 = recs_host[1][i];      // the other half's set: the rows and the keep-bits the odd steps read
     r1 = r;
     r1.p.xb = c->xb2; r1.q_xb = c->xb2; r1.xb = c->xb2;
     if (r1.p.drop_bits) r1.p.drop_bits = c->drop_bits + (size_t)2 * MB * 8;
-    memcpy(group_rw_tab(g, i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
-    GroupPrioRec& w = g->rw.host(g->rw_prs)[i];
+    memcpy(sg.tab(i), tab, (size_t)n * sizeof(iqlhip_step_scalars));
+    GroupPrioRec& w = stg.host(g->rw_prs)[i];
     memset(&w, 0, sizeof w);
     w.wt = t ? weights_tab(t) : WTab{nullptr, 0u, 0, 0};
     w.xb[0] = c->xb; w.xb[1] = c->xb2;
@@ -5556,24 +5466,24 @@ static int group_train_steps_rw(iqlhip_group* g, const float* const* rows, int64
       w.m = (unsigned)B[i];
       w.alpha = alpha[i]; w.eps = eps[i];
     }
-    g->rw.host(g->rw_rws)[i] = GroupRwRec{w.c, prio ? prio_td(c) : nullptr};
+    stg.host(g->rw_rws)[i] = GroupRwRec{w.c, prio ? prio_td(c) : nullptr};
   }
   // actor dropout: every member's record inside its GroupPrioRec (active = the member draws), step s at drop_step + s into
   // half s & 1 (GroupPrioRec::drop_bits)
   bool draws = false;
   for (int i = 0; i < g->k; ++i) {
-    GroupDropRec& d = g->rw.host(g->rw_prs)[i].drop;
+    GroupDropRec& d = stg.host(g->rw_prs)[i].drop;
     d = group_drop_record(g->m[i], B[i]);
     d.active = ((g->flags & IQLHIP_GROUP_DROPOUT) && group_draws(g->m[i])) ? 1 : 0;
     draws = draws || d.active;
   }
   GroupAux aux[2];
   for (int h = 0; h < 2; ++h)
-    if ((rc = group_aux(g, g->rw, g->rw_aux[h], recs_host[h], &aux[h]))) return rc;
-  if ((rc = group_rw_upload(g, n, st))) return rc;
-  const GroupRec* recs[2] = {g->rw.device(g->rw_recs[0]), g->rw.device(g->rw_recs[1])};
-  const GroupPrioRec* prs = g->rw.device(g->rw_prs);
-  const GroupRwRec* rws = g->rw.device(g->rw_rws);
+    if ((rc = group_aux(g, stg, sg.aux[h], recs_host[h], &aux[h]))) return rc;
+  HIPCHK(sg.upload_steps(g->k, n, st));
+  const GroupRec* recs[2] = {stg.device(sg.recs[0]), stg.device(sg.recs[1])};
+  const GroupPrioRec* prs = stg.device(g->rw_prs);
+  const GroupRwRec* rws = stg.device(g->rw_rws);
   // (grids sized by the largest member, as iqlhip_group_train_steps_weighted's: a wave per IQL_GROUP_WT_ROWS_PER_WAVE rows,
   //  the keep-bit words behind the gather at the far end; every record bounds its own member's rows and words)
   const int wt_nb = (q.max_rows + 4 * IQL_GROUP_WT_ROWS_PER_WAVE - 1) / (4 * IQL_GROUP_WT_ROWS_PER_WAVE);
@@ -6072,17 +5982,9 @@ struct iqlhip_var_group {
   Owned own;
   Staging stg;
   Section<VarGroupRec> recs; Section<iqlhip_var_scalars> tab;      // tab [IQLHIP_VAR_TRAIN_MAX_STEPS][k], the staging's last
-  hipEvent_t up_done = nullptr;       // the last upload has read stg.pin
-  bool up_pending = false;
   float* loss_ring = nullptr;         // pinned, host-mapped [k][IQLHIP_VAR_TRAIN_MAX_STEPS]
   long long* start_ring = nullptr;
 };
-
-// rc of a member's check with the member named in front of the message
-static int var_member_fail(int rc, int i) {
-  const std::string msg = g_err;
-  return fail(rc, "member %d: %s", i, msg.c_str());
-}
 
 extern "C" int iqlhip_var_group_destroy(iqlhip_var_group* g) {
   if (!g) return IQLHIP_OK;
@@ -6115,10 +6017,9 @@ extern "C" int iqlhip_var_group_create(iqlhip_var* const* members, int k, iqlhip
   DevGuard guard(g->device);
   g->recs = g->stg.add<VarGroupRec>(k);
   g->tab = g->stg.add<iqlhip_var_scalars>((size_t)k * IQLHIP_VAR_TRAIN_MAX_STEPS);
-  if (int rc = g->stg.alloc(g->own)) return rc;
+  HIPCHK(g->stg.alloc(g->own));
   HIPCHK(g->own.pin(&g->loss_ring, (size_t)k * IQLHIP_VAR_TRAIN_MAX_STEPS * sizeof(float), /*zero=*/true));
   HIPCHK(g->own.pin(&g->start_ring, (size_t)k * IQLHIP_VAR_TRAIN_MAX_STEPS * sizeof(long long), /*zero=*/true));
-  HIPCHK(g->own.event(&g->up_done, hipEventDisableTiming));
   *out = g.release();
   return IQLHIP_OK;
 }
@@ -6128,7 +6029,7 @@ struct VarGroupWin { const float* const* rows; const int64_t* ld; const int64_t*
 static int var_group_check_windows(const iqlhip_var_group* g, const VarGroupWin& w, int32_t B) {
   if (!g || !w.rows || !w.ld || !w.size || !w.action_dim) return fail(IQLHIP_EINVAL, "NULL argument");
   for (int i = 0; i < g->k; ++i) {
-    if (int rc = var_check_window(g->m[i], w.rows[i], w.ld[i], w.size[i], g->S, w.action_dim[i], B)) return var_member_fail(rc, i);
+    if (int rc = var_check_window(g->m[i], w.rows[i], w.ld[i], w.size[i], g->S, w.action_dim[i], B)) return member_fail(i, rc);
     if (!g->m[i]->params) return fail(IQLHIP_ENOTBOUND, "member %d: iqlhip_var_bind has not been called", i);
     if (w.start && (w.start[i] < 0 || w.start[i] > w.size[i] - B))
       return fail(IQLHIP_EINVAL, "member %d: rows %lld .. %lld outside the buffer's %lld", i, (long long)w.start[i],
@@ -6140,12 +6041,12 @@ static int var_group_check_blocks(const iqlhip_var_group* g, const float* const*
                                   const int32_t* aligned, int64_t aligned_stride) {
   if (!g || !blocks_dev || !aligned) return fail(IQLHIP_EINVAL, "NULL argument");
   for (int i = 0; i < g->k; ++i)
-    if (int rc = var_check_call(g->m[i], blocks_dev[i], B, which, need_net, aligned[i * aligned_stride])) return var_member_fail(rc, i);
+    if (int rc = var_check_call(g->m[i], blocks_dev[i], B, which, need_net, aligned[i * aligned_stride])) return member_fail(i, rc);
   return IQLHIP_OK;
 }
 static int var_group_window_scratch(iqlhip_var_group* g) {
   for (int i = 0; i < g->k; ++i)
-    if (int rc = var_window_scratch(g->m[i])) return var_member_fail(rc, i);
+    if (int rc = var_window_scratch(g->m[i])) return member_fail(i, rc);
   return IQLHIP_OK;
 }
 
@@ -6169,18 +6070,10 @@ static void var_group_record_pack(iqlhip_var_group* g, int i, const VarGroupWin&
   p = var_pack_params(g->m[i], w.rows[i], w.ld[i], w.size[i], w.action_dim[i], B, out);
   if (w.start) p.start = w.start[i];
 }
-static int var_group_staging_free(iqlhip_var_group* g) {
-  if (g->up_pending) HIPCHK(hipEventSynchronize(g->up_done));
-  g->up_pending = false;
-  return IQLHIP_OK;
-}
-// the records and the first n_steps rows of the scalar table, in one copy
-static int var_group_upload(iqlhip_var_group* g, int n_steps, hipStream_t st) {
+// the records and the first n_steps rows of the scalar table, in one copy (n_steps == 0: the records only)
+static hipError_t var_group_upload(iqlhip_var_group* g, int n_steps, hipStream_t st) {
   const size_t bytes = n_steps ? g->tab.off + (size_t)n_steps * g->k * sizeof(iqlhip_var_scalars) : (size_t)g->k * sizeof(VarGroupRec);
-  HIPCHK(hipMemcpyAsync(g->stg.dev, g->stg.pin, bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(g->up_done, st));
-  g->up_pending = true;
-  return IQLHIP_OK;
+  return g->stg.upload(bytes, st);
 }
 
 enum VarGroupPack { VG_NO_PACK, VG_PACK_AT, VG_PACK_DRAWN };
@@ -6210,7 +6103,7 @@ static int var_group_eager(iqlhip_var_group* g, const float* const* blocks_dev, 
   DevGuard guard(g->device);
   if (w)
     if (int rc = var_group_window_scratch(g)) return rc;
-  if (int rc = var_group_staging_free(g)) return rc;
+  HIPCHK(g->stg.wait_free());
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < g->k; ++i) {
     const float* blk = w ? g->m[i]->wblk : blocks_dev[i];
@@ -6219,7 +6112,7 @@ static int var_group_eager(iqlhip_var_group* g, const float* const* blocks_dev, 
     if (w) var_group_record_pack(g, i, *w, B, g->m[i]->wblk);
     if (scalars) g->stg.host(g->tab)[i] = scalars[i];
   }
-  if (int rc = var_group_upload(g, scalars ? 1 : 0, st)) return rc;
+  HIPCHK(var_group_upload(g, scalars ? 1 : 0, st));
   var_group_launch(g, B, which, 0, w ? VG_PACK_AT : VG_NO_PACK, st);
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;
@@ -6254,12 +6147,12 @@ extern "C" int iqlhip_var_group_pack_windows(iqlhip_var_group* g, const float* c
     if ((uintptr_t)blocks_out_dev[i] & 3) return fail(IQLHIP_EINVAL, "member %d: the packed block must be 4-byte aligned", i);
   }
   DevGuard guard(g->device);
-  if (int rc = var_group_staging_free(g)) return rc;
+  HIPCHK(g->stg.wait_free());
   for (int i = 0; i < g->k; ++i) {
     memset(&g->stg.host(g->recs)[i], 0, sizeof(VarGroupRec));
     var_group_record_pack(g, i, w, B, blocks_out_dev[i]);
   }
-  if (int rc = var_group_upload(g, 0, (hipStream_t)stream)) return rc;
+  HIPCHK(var_group_upload(g, 0, (hipStream_t)stream));
   hipLaunchKernelGGL(iql_var_pack_window_group_kernel<false>, dim3(var_group_grid(g->k, var_pack_blocks(g->S, B))), dim3(256), 0,
                      (hipStream_t)stream, g->stg.device(g->recs), g->k, (g->k + 7) / 8, 0);
   HIPCHK(hipGetLastError());
@@ -6328,7 +6221,7 @@ extern "C" int iqlhip_var_group_train_steps(iqlhip_var_group* g, const float* co
     return rc;
   DevGuard guard(g->device);
   if (int rc = var_group_window_scratch(g)) return rc;
-  if (int rc = var_group_staging_free(g)) return rc;
+  HIPCHK(g->stg.wait_free());
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < K; ++i) {
     iqlhip_var* s = g->m[i];
@@ -6343,7 +6236,7 @@ extern "C" int iqlhip_var_group_train_steps(iqlhip_var_group* g, const float* co
     p.start_out = g->start_ring + (size_t)i * IQLHIP_VAR_TRAIN_MAX_STEPS;
   }
   memcpy(g->stg.host(g->tab), scalars, (size_t)n_steps * K * sizeof(iqlhip_var_scalars));
-  if (int rc = var_group_upload(g, n_steps, st)) return rc;
+  HIPCHK(var_group_upload(g, n_steps, st));
   for (int s = 0; s < n_steps; ++s) var_group_launch(g, B, which_net, s, VG_PACK_DRAWN, st);
   HIPCHK(hipGetLastError());
   return IQLHIP_OK;

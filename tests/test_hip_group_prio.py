@@ -361,6 +361,36 @@ def test_two_python_calls_in_a_row_and_nothing_stale_afterwards():
         _assert_same(members[i], twins[i], f"solo afterwards, member {i}")
 
 
+def test_plain_and_row_weighted_calls_interleaved_on_one_group():
+    """step, step_rw, step, then a 2-step train_steps_weighted_is on ONE group: the plain and the row-weighted calls run
+    from two stagings through the same host code, each with its own upload event — every call equals the members' solo
+    calls in the same order, bit for bit."""
+    iql = _hip()[0]
+    K, B, seeds, betas = 2, 10, [71, 72], [0.4, 1.0]
+    buf = _buffer()
+    tabs = _tables(K, updatable=False, count=1)[0]
+    members, twins = _pairs(K)
+    group = iql.ImplicitQLearningGroup(members)
+    calls = [(_batches((B,) * K, seed=80), None), (_batches((B,) * K, seed=84), _row_weights((B,) * K)),
+             (_batches((B,) * K, seed=88), None)]
+    for n, (batches, cs) in enumerate(calls):
+        kw = [{} if cs is None else {"loss_weights": cs[i], "return_td": True} for i in range(K)]
+        logs = group.train(batches) if cs is None else group.train(batches, loss_weights=cs, return_td=True)
+        for i in range(K):
+            want = twins[i].train(batches[i], **kw[i])
+            assert _logs_equal(logs[i], want), (n, i, logs[i], want)
+            _assert_same(members[i], twins[i], f"call {n}, member {i}")
+            if cs is not None:
+                assert torch.equal(group.last_td_errors()[i], twins[i].last_td_errors()), (n, i)
+    got = group.train_steps_weighted(buf, 2, B, seeds, weights=tabs, is_beta=betas, chunk=2)
+    assert got.shape == (K, 2, 3)
+    for i in range(K):
+        want = twins[i].train_steps_weighted(buf, 2, B, seed=seeds[i], weights=tabs[i], is_beta=betas[i], chunk=2)
+        _assert_losses(got[i], want, f"burst, member {i}")
+        _assert_same(members[i], twins[i], f"burst, member {i}")
+    assert not np.array_equal(got[0], got[1])
+
+
 # ---------------------------------------------------------------------------------------------------------------- 8
 def _snapshot(members, tables):
     H = _hip()[2]
