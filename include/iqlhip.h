@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define IQLHIP_VERSION 400          /* 0.4.0 */
+#define IQLHIP_VERSION 410          /* 0.4.1 */
 #define IQLHIP_HIDDEN 256           /* hidden width the kernels are tiled for (reference default, iql.py:352) */
 #define IQLHIP_MAX_INPUT 128        /* max state_dim + action_dim */
 #define IQLHIP_MAX_ACTION 32        /* max action_dim */
@@ -438,6 +438,21 @@ int iqlhip_online_step_prioritized(iqlhip_ctx* ctx, float* rows_dev, int64_t ld,
                                    void* stream, iqlhip_weights* table, uint64_t seed, uint64_t stream_offset, float is_beta,
                                    float alpha, float eps);
 int iqlhip_online_prioritized_batch(iqlhip_ctx* ctx, int32_t n, int64_t* idx_out_dev, float* td_out_dev, void* stream);
+/* iqlhip_online_step for a raw ring and the n-step ring derived from it ("n-step rows" below), in one
+ * call and under one synchronisation.  One launch of at most four blocks in front of iqlhip_online_step's own: it stores
+ * row_host at raw_dev[pointer], stores episode_end != 0 at ends_dev[pointer] and refreshes the min(horizon, size_after)
+ * derived rows that end at `pointer` — iqlhip_rows_nstep_ring with newest = pointer, reading the new row from the host
+ * words.  Then iqlhip_online_step's launches run on the DERIVED ring rows_dev: its gather stores row_host at
+ * rows_dev[pointer], which is what the refresh stored there (the newest derived row has k = 1), and the step trains on
+ * rows_dev[idx_host[..]].  size_after: the ring's size with the new row.  steps_dev (uint8 [capacity]) may be NULL.
+ * Bit for bit: the ring write, iqlhip_rows_nstep_ring, iqlhip_rows_sample_packed on rows_dev and iqlhip_step_sync.
+ * Refuses what iqlhip_online_step and iqlhip_rows_nstep_ring refuse, and a data-parallel exchange
+ * (IQLHIP_EUNSUPPORTED), before anything is launched. */
+int iqlhip_online_step_nstep(iqlhip_ctx* ctx, float* raw_dev, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                             const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
+                             float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
+                             float* act_out_host, void* stream, uint8_t* ends_dev, int32_t episode_end, int64_t size_after,
+                             int32_t horizon, double discount, uint8_t* steps_dev);
 
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is
@@ -677,6 +692,47 @@ int iqlhip_rows_episode_returns(const float* rows_dev, int64_t ld, int32_t state
                                 int32_t flags, const double* sparse_value, double* ep_return_dev,
                                 double* return_to_go_dev, int64_t* ep_first_dev, int64_t* ep_last_dev,
                                 int64_t* episodes_out, void* stream);
+
+/* ---- n-step rows --------------------------------------------------------------------------------
+ * A DERIVED row store: one-step packed rows rewritten so that the unchanged step kernels, which all form
+ *   y = r + ((1.f - d) * discount) * next_v,
+ * compute a k-step target from them: r holds the discounted reward sum of k rows, s' the state k rows ahead and
+ * d = 1 - discount^(k - 1) * (1 - d_last), so that (1 - d) * discount = discount^k * (1 - d_last).  Every call that takes
+ * packed rows takes a derived store as it is.  The d column of a derived store therefore holds fractions by design.
+ * Arithmetic (integers and float64, fp contract off; tests/nstep_ref.py restates it and agrees to the bit), for row i of
+ * a range, horizon N in [1, IQLHIP_NSTEP_MAX_HORIZON]:
+ *   limit L(i)  build form: min(i + N - 1, end(i)); end(i) = ep_last[i] when a table is given and the entry is >= 0 (an
+ *               entry outside [i, n - 1] is clamped into it), else n - 1, the last row of the range.
+ *               ring form: rows in ring order (oldest first, positions modulo the capacity); the chain also stops at a
+ *               row whose end byte is not 0, and at the newest row: it never passes the newest row.
+ *   chain       m = the first row j in [i, L(i)] with d[j] != 0, or L(i) if there is none; k = m - i + 1.
+ *   r           G = (double)r[m]; for j = m - 1 down to i: G = (double)r[j] + discount * G, the product rounded, then
+ *               the sum; the row stores (float)G.
+ *   d           d[m] itself if d[m] != 0; else c = 1.0, (k - 1) times c = c * discount, and the row stores
+ *               (float)(1.0 - c): +0.0 for k = 1.  (A stored done of -0.0 is outside the contract.)
+ *   columns     s, a and the pad columns below iqlhip_row_stride of row i, s' of row m; steps[i] = k (uint8).
+ * So N = 1 copies the rows bit for bit.  NaN rewards are outside the contract.  Row-parallel, one launch, 64-bit row
+ * offsets; the source rows are only read.  Nothing is allocated; nothing stays attached to a context. */
+#define IQLHIP_NSTEP_MAX_HORIZON 64
+/* Build form: rows [row0, row0 + n) of src_dev -> the same rows of dst_dev.  ep_last_dev (int64 [n], may be NULL) and
+ * steps_dev (uint8 [n], may be NULL) are indexed from 0 in the range; ep_last is iqlhip_rows_episode_returns' column,
+ * relative to row0.  IQLHIP_EINVAL before any device work: a NULL store, n < 1, row0 < 0, a stride below
+ * iqlhip_row_stride or no multiple of 4, a store not 16-byte aligned, src_dev == dst_dev or overlapping ranges (the
+ * rows are not built in place), a horizon outside [1, 64], a discount that is not finite or outside (0, 1]. */
+int iqlhip_rows_nstep(const float* src_dev, int64_t src_ld, float* dst_dev, int64_t dst_ld, int32_t state_dim,
+                      int32_t action_dim, int64_t row0, int64_t n, int32_t horizon, double discount,
+                      const int64_t* ep_last_dev, uint8_t* steps_dev, void* stream);
+/* Ring form: src_dev and dst_dev are rings of `capacity` rows of stride ld that hold `size` rows, the newest at position
+ * `newest` (the oldest at (newest - size + 1) mod capacity); ends_dev[capacity] holds one byte per position, not 0
+ * where the stored row ends an episode (a terminal state or a time limit).  Recomputes the min(horizon, size) derived
+ * rows that end at `newest` — the only rows whose chains a new transition can extend — in one launch of at most four
+ * blocks; steps_dev (uint8 [capacity], may be NULL) is indexed by position.  Invariant: a derived ring refreshed after
+ * every insert equals the build form applied to the ring unrolled into time order, ep_last taken from the end bytes.
+ * IQLHIP_EINVAL before any device work: what the build form refuses, size outside [1, capacity], newest outside the
+ * ring (or beyond size in a ring that has not wrapped), a NULL ends_dev. */
+int iqlhip_rows_nstep_ring(const float* src_dev, float* dst_dev, int64_t ld, int32_t state_dim, int32_t action_dim,
+                           int64_t capacity, int64_t size, int64_t newest, const uint8_t* ends_dev, int32_t horizon,
+                           double discount, uint8_t* steps_dev, void* stream);
 /* Device-side index draw used by iqlhip_train_steps, exposed for tests. */
 int iqlhip_draw_indices(int64_t* idx_dev, int64_t n, int64_t size, uint64_t seed, uint64_t offset, void* stream);
 

@@ -1786,11 +1786,20 @@ struct OnlinePrio { iqlhip_weights* table; uint64_t seed, offset; float is_beta,
 static void online_prio_gather(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t pointer, int32_t n, const OnlinePrio& pr,
                                hipStream_t st, RowWeights* rw);
 static void online_prio_update(iqlhip_ctx* c, int32_t n, const OnlinePrio& pr, hipStream_t st);
+// ns != nullptr — iqlhip_online_step_nstep (its own checks made): rows_dev is the DERIVED ring; one launch in front of the
+// gather stores the host row into the raw ring, sets its end byte and refreshes the derived rows the new transition
+// extends (online_nstep_refresh, defined with the n-step rows at the end of the file).  The gather's own ring write then
+// stores at derived[pointer] the bytes that launch stored there (the newest derived row is the host row: k = 1).
+struct OnlineNstep { float* raw_dev; unsigned char* ends_dev; unsigned char* steps_dev; int64_t size_after; int32_t horizon;
+                     int32_t episode_end; double discount; };
+static void online_nstep_refresh(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                 const OnlineNstep& ns, hipStream_t st);
 static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
                              const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
                              const float* out, bool act_follows, void* stream, const float* rows_off_dev,
                              int64_t size_off, const int64_t* idx_off_host, int32_t n_off,
-                             unsigned long long* done_val_out, const OnlinePrio* pr = nullptr) {
+                             unsigned long long* done_val_out, const OnlinePrio* pr = nullptr,
+                             const OnlineNstep* ns = nullptr) {
   if (!c || !rows_dev || !row_host || (!idx_host && !pr) || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (!c->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_bind has not been called");
   if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
@@ -1812,6 +1821,7 @@ static int online_step_front(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t
   if (!pr) memcpy(c->on_idx_pin + n_off, idx_host, (size_t)n * sizeof(long long));
   const int total = B * (int)(ld / 4);
   RowWeights rw = {nullptr, nullptr};
+  if (ns) online_nstep_refresh(c, rows_dev, ld, capacity, pointer, *ns, st);
   if (pr)
     online_prio_gather(c, rows_dev, ld, pointer, n, *pr, st, &rw);
   else if (n_off)
@@ -1838,12 +1848,13 @@ static int online_step(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capac
                        const float* row_host, const int64_t* idx_host, int32_t n, const iqlhip_step_scalars* sc,
                        float out[3], const float* act_state_host, float max_action, uint64_t act_seed,
                        float* act_out_host, void* stream, const float* rows_off_dev, int64_t size_off,
-                       const int64_t* idx_off_host, int32_t n_off, const OnlinePrio* pr = nullptr) {
+                       const int64_t* idx_off_host, int32_t n_off, const OnlinePrio* pr = nullptr,
+                       const OnlineNstep* ns = nullptr) {
   if (!c || !rows_dev || !row_host || (!idx_host && !pr) || !sc || !out) return fail(IQLHIP_EINVAL, "NULL argument");
   if (act_state_host && !act_out_host) return fail(IQLHIP_EINVAL, "act_state_host without act_out_host");
   unsigned long long done_val = 0;
   int rc = online_step_front(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host != nullptr,
-                             stream, rows_off_dev, size_off, idx_off_host, n_off, &done_val, pr);
+                             stream, rows_off_dev, size_off, idx_off_host, n_off, &done_val, pr, ns);
   if (rc) return rc;
   DevGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -6254,4 +6265,116 @@ extern "C" int iqlhip_var_group_read_train_ring(iqlhip_var_group* g, float* loss
     memcpy(starts_out + (size_t)i * n_steps, g->start_ring + (size_t)i * IQLHIP_VAR_TRAIN_MAX_STEPS, (size_t)n_steps * sizeof(int64_t));
   }
   return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// N-step rows (include/iqlhip.h "n-step rows"; kernels: iqlhip_nstep_kernels.h, the code object's
+// last).  Nothing is allocated and nothing stays attached to a context: a build is one launch, a ring refresh one
+// launch of at most four blocks.
+#include "iqlhip_nstep_kernels.h"
+static_assert(NS_MAX_HORIZON == IQLHIP_NSTEP_MAX_HORIZON, "kernel and header disagree on the largest horizon");
+
+static int nstep_args_ok(int32_t horizon, double discount) {
+  if (horizon < 1 || horizon > IQLHIP_NSTEP_MAX_HORIZON)
+    return fail(IQLHIP_EINVAL, "horizon = %d outside [1, %d]", horizon, IQLHIP_NSTEP_MAX_HORIZON);
+  if (!std::isfinite(discount) || !(discount > 0.0) || discount > 1.0)
+    return fail(IQLHIP_EINVAL, "discount must be finite and in (0, 1]");
+  return IQLHIP_OK;
+}
+static int nstep_store_ok(const float* src, int64_t src_ld, const float* dst, int64_t dst_ld, int32_t S, int32_t A, int64_t row0,
+                          int64_t n, const char* who) {
+  if (!dst) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (dst_ld < iqlhip_row_stride(S, A)) return fail(IQLHIP_EINVAL, "bad %s geometry", who);
+  if ((src_ld & 3) || (dst_ld & 3)) return fail(IQLHIP_EINVAL, "row strides must be multiples of 4 floats");
+  if ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
+  if (src == dst) return fail(IQLHIP_EINVAL, "source and derived rows are the same buffer: n-step rows are not built in place");
+  const uintptr_t s0 = (uintptr_t)(src + row0 * src_ld), s1 = (uintptr_t)(src + (row0 + n) * src_ld);
+  const uintptr_t d0 = (uintptr_t)(dst + row0 * dst_ld), d1 = (uintptr_t)(dst + (row0 + n) * dst_ld);
+  if (s0 < d1 && d0 < s1) return fail(IQLHIP_EINVAL, "source and derived rows overlap: n-step rows are not built in place");
+  return IQLHIP_OK;
+}
+static NstepArgs nstep_kernel_args(const float* src, int64_t src_ld, float* dst, int64_t dst_ld, int32_t S, int32_t A,
+                                   int32_t horizon, double discount, uint8_t* steps) {
+  return NstepArgs{src, dst, (long long)src_ld, (long long)dst_ld, (int)S, (int)A, (int)(iqlhip_row_stride(S, A) / 4), (int)horizon,
+                   (int)((horizon + NS_LANES - 1) / NS_LANES), discount, steps};
+}
+
+extern "C" int iqlhip_rows_nstep(const float* src_dev, int64_t src_ld, float* dst_dev, int64_t dst_ld, int32_t S, int32_t A,
+                                 int64_t row0, int64_t n, int32_t horizon, double discount, const int64_t* ep_last_dev,
+                                 uint8_t* steps_dev, void* stream) {
+  int rc = reward_args_ok(src_dev, src_ld, S, A, row0, n, "rows_nstep");
+  if (!rc) rc = nstep_store_ok(src_dev, src_ld, dst_dev, dst_ld, S, A, row0, n, "rows_nstep");
+  if (!rc) rc = nstep_args_ok(horizon, discount);
+  if (rc) return rc;
+  if (((uintptr_t)ep_last_dev) & 7) return fail(IQLHIP_EINVAL, "ep_last must be 8-byte aligned");
+  const long long rounds = ((long long)n + NS_ROWS_PER_BLOCK - 1) / NS_ROWS_PER_BLOCK;
+  const dim3 grid((unsigned)std::min<long long>(rounds, NS_MAX_BLOCKS));
+  const NstepArgs a = nstep_kernel_args(src_dev, src_ld, dst_dev, dst_ld, S, A, horizon, discount, steps_dev);
+  if (ep_last_dev)
+    hipLaunchKernelGGL(iql_nstep_build_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, (long long)row0, (long long)n,
+                       (const long long*)ep_last_dev);
+  else
+    hipLaunchKernelGGL(iql_nstep_build_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, (long long)row0, (long long)n,
+                       (const long long*)nullptr);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+static int nstep_ring_ok(const float* src, const float* dst, int64_t ld, int32_t S, int32_t A, int64_t capacity, int64_t size,
+                         int64_t newest, const uint8_t* ends, int32_t horizon, double discount) {
+  if (!src || !ends) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (S < 1 || A < 1 || ld < iqlhip_row_stride(S, A)) return fail(IQLHIP_EINVAL, "bad rows_nstep_ring geometry");
+  if (capacity < 1 || size < 1 || size > capacity) return fail(IQLHIP_EINVAL, "ring size %lld outside [1, capacity=%lld]", (long long)size, (long long)capacity);
+  if (newest < 0 || newest >= capacity) return fail(IQLHIP_EINVAL, "newest row outside the ring");
+  if (size < capacity && newest >= size) return fail(IQLHIP_EINVAL, "newest row %lld beyond the %lld rows of a ring that has not wrapped", (long long)newest, (long long)size);
+  int rc = nstep_store_ok(src, ld, dst, ld, S, A, 0, capacity, "rows_nstep_ring");
+  if (!rc) rc = nstep_args_ok(horizon, discount);
+  return rc;
+}
+static void launch_nstep_ring(const NstepArgs& a, int64_t capacity, int64_t size, int64_t newest, uint8_t* ends,
+                              const float* newest_row, int newest_end, float* raw_out, hipStream_t st) {
+  const int todo = (int)std::min<int64_t>(a.horizon, size);
+  const dim3 grid((unsigned)(todo + NS_ROWS_PER_BLOCK - 1) / NS_ROWS_PER_BLOCK);
+  if (newest_row)
+    hipLaunchKernelGGL(iql_nstep_ring_kernel<true>, grid, dim3(256), 0, st, a, (long long)capacity, (long long)size,
+                       (long long)newest, todo, ends, newest_row, newest_end, raw_out);
+  else
+    hipLaunchKernelGGL(iql_nstep_ring_kernel<false>, grid, dim3(256), 0, st, a, (long long)capacity, (long long)size,
+                       (long long)newest, todo, ends, newest_row, newest_end, raw_out);
+}
+
+extern "C" int iqlhip_rows_nstep_ring(const float* src_dev, float* dst_dev, int64_t ld, int32_t S, int32_t A, int64_t capacity,
+                                      int64_t size, int64_t newest, const uint8_t* ends_dev, int32_t horizon, double discount,
+                                      uint8_t* steps_dev, void* stream) {
+  const int rc = nstep_ring_ok(src_dev, dst_dev, ld, S, A, capacity, size, newest, ends_dev, horizon, discount);
+  if (rc) return rc;
+  launch_nstep_ring(nstep_kernel_args(src_dev, ld, dst_dev, ld, S, A, horizon, discount, steps_dev), capacity, size, newest,
+                    const_cast<uint8_t*>(ends_dev), nullptr, 0, nullptr, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+// The launch of iqlhip_online_step_nstep in front of the step (online_step_front): ring write, end byte and refresh.
+static void online_nstep_refresh(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                 const OnlineNstep& ns, hipStream_t st) {
+  launch_nstep_ring(nstep_kernel_args(ns.raw_dev, ld, rows_dev, ld, c->dims.state_dim, c->dims.action_dim, ns.horizon, ns.discount,
+                                      ns.steps_dev),
+                    capacity, ns.size_after, pointer, ns.ends_dev, (const float*)c->on_row_pin, ns.episode_end, ns.raw_dev, st);
+}
+
+extern "C" int iqlhip_online_step_nstep(iqlhip_ctx* c, float* raw_dev, float* rows_dev, int64_t ld, int64_t capacity,
+                                        int64_t pointer, const float* row_host, const int64_t* idx_host, int32_t n,
+                                        const iqlhip_step_scalars* sc, float out[3], const float* act_state_host,
+                                        float max_action, uint64_t act_seed, float* act_out_host, void* stream,
+                                        uint8_t* ends_dev, int32_t episode_end, int64_t size_after, int32_t horizon,
+                                        double discount, uint8_t* steps_dev) {
+  if (!c || !raw_dev || !rows_dev || !ends_dev) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "the n-step online step is not supported with a data-parallel exchange");
+  const int rc = nstep_ring_ok(raw_dev, rows_dev, ld, c->dims.state_dim, c->dims.action_dim, capacity, size_after, pointer,
+                               ends_dev, horizon, discount);
+  if (rc) return rc;
+  const OnlineNstep ns{raw_dev, ends_dev, steps_dev, size_after, horizon, episode_end, discount};
+  return online_step(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, max_action, act_seed,
+                     act_out_host, stream, nullptr, 0, nullptr, 0, nullptr, &ns);
 }

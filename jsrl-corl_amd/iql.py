@@ -16,4 +16,5 @@ from iqlhip_networks import (LOG_STD_MAX, LOG_STD_MIN, MLP, DeterministicPolicy,
 from iqlhip_replay import OfflineReplayBuffer, ReplayBuffer, TensorBatch  # noqa: F401
 from iqlhip_trainer import EXP_ADV_MAX, ImplicitQLearning  # noqa: F401
 from iqlhip_group import ImplicitQLearningGroup  # noqa: F401  (K trainers of one shape stepped together)
+from iqlhip_nstep import NStepReplay  # noqa: F401  (n-step rows derived from a GPU ReplayBuffer)
 from iqlhip_jsrl import WHO_CRITIC, GateHolder, JsrlActors, load_gate, who_from_config  # noqa: F401  (JSRL guide / learner selection)

@@ -38,6 +38,7 @@ IQLHIP_IPC_HANDLE_BYTES = 64
 XCH_NONE, XCH_RCCL, XCH_P2P = 0, 1, 2
 TS_CONTINUE = 1
 IQLHIP_EP_KEEP_TAIL = 1       # iqlhip_rows_episode_returns: the last row of the range ends an episode
+IQLHIP_NSTEP_MAX_HORIZON = 64  # iqlhip_rows_nstep: the largest horizon
 NET_V, NET_Q1, NET_Q2, NET_PI = 0, 1, 2, 3
 POLICY_GAUSSIAN, POLICY_DETERMINISTIC = 0, 1
 
@@ -169,6 +170,14 @@ SYMBOLS = [
     ("iqlhip_rows_episode_returns", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                               C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    ("iqlhip_rows_nstep", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                    C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("iqlhip_rows_nstep_ring", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    ("iqlhip_online_step_nstep", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p,
+                                           C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                           C.c_int32, C.c_double, C.c_void_p]),
     ("iqlhip_draw_indices", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("iqlhip_weights_build", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("iqlhip_weights_free", C.c_int, [C.c_void_p]),

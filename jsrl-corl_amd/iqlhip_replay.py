@@ -225,6 +225,12 @@ class ReplayBuffer:
         return ing.episode_returns_device(self._rows, self._state_dim, self._action_dim, self._size, max_episode_steps,
                                           discount, state_break_tol, keep_tail, sparse_value)
 
+    def nstep(self, n: int, discount: float, episodes=None):
+        """An iqlhip_nstep.NStepReplay of this buffer: its rows as n-step transitions in a derived GPU ReplayBuffer that
+        every training, sampling and scoring call takes as it is."""
+        import iqlhip_nstep
+        return iqlhip_nstep.NStepReplay(self, n, discount, episodes)
+
     def _index_bound(self) -> int:
         return self._size
 

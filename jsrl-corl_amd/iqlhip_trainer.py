@@ -808,6 +808,18 @@ class ImplicitQLearning:
                                              seed, None if a_out is None else a_out.ctypes.data, self._stream()))
         return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
 
+    def online_step_nstep(self, nstep, state, action, reward: float, next_state, done: bool, batch_size: int,
+                          episode_end: Optional[bool] = None, act_next: Optional[np.ndarray] = None):
+        """online_step for a raw ring and the n-step buffer derived from it (an iqlhip_nstep.NStepReplay; DESIGN.md
+        6c-3), in ONE library call and under one synchronisation.  Bit for bit the sequence
+            nstep.add_transition(state, action, reward, next_state, done, episode_end)
+            log = trainer.train(nstep.buffer.sample(batch_size))
+            a = trainer.actor.act(act_next, device)  # with act_next
+        The indices are sample()'s draw over the size after the insert.  Returns online_step's result.
+        NotImplementedError under data parallelism and for a derived buffer with a tracking sample-weight table."""
+        from iqlhip_nstep import online_step_nstep
+        return online_step_nstep(self, nstep, state, action, reward, next_state, done, batch_size, episode_end, act_next)
+
     def online_step_prioritized(self, replay_buffer, state, action, reward: float, next_state, done: bool,
                                 batch_size: int, seed: int, offset: Optional[int] = None, alpha: float = 0.6,
                                 eps: float = 1e-6, is_beta: float = 0.4, act_next: Optional[np.ndarray] = None):
