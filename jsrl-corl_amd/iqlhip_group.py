@@ -92,6 +92,7 @@ import numpy as np
 import torch
 
 import iqlhip_binding as hb
+from iqlhip_replay import check_online_ring, draw_indices, pack_transition
 from iqlhip_trainer import K_MAX, ImplicitQLearning
 
 BF16_MAX_ROWS = 512      # bf16 batches beyond this run the large-batch kernels, which have no group form
@@ -580,11 +581,7 @@ class ImplicitQLearningGroup:
         S, A = t0._S, t0._A
         rows = np.zeros((K, ld), dtype=np.float32)
         for k in range(K):
-            rows[k, :S] = np.asarray(states[k], dtype=np.float32).reshape(-1)
-            rows[k, S: S + A] = np.asarray(actions[k], dtype=np.float32).reshape(-1)
-            rows[k, S + A: 2 * S + A] = np.asarray(next_states[k], dtype=np.float32).reshape(-1)
-            rows[k, 2 * S + A] = np.float32(rewards[k])
-            rows[k, 2 * S + A + 1] = np.float32(dones[k])
+            pack_transition(rows[k], S, A, states[k], actions[k], rewards[k], next_states[k], dones[k])
         want = [k for k in range(K) if act_next is not None and act_next[k] is not None]
         a_in = a_out = mask = max_a = seeds = None
         if want:
@@ -598,17 +595,47 @@ class ImplicitQLearningGroup:
                              dtype=np.uint64)
         return rows, want, (a_in, mask, max_a, seeds, a_out)
 
-    def _online_commit(self, bufs, pointers, new_sizes, adam_next, out, act_next, want, a_out):
-        """Behind an online call that succeeded: every ring past its insert, every member past its step.  Returns the
+    def _online_lists(self, what: str, act_next, rngs, **per) -> None:
+        """Every per-member argument of an online call is a list of K entries (act_next and rngs when given)."""
+        K = len(self.trainers)
+        if act_next is not None:
+            per["act_next"] = act_next
+        if rngs is not None:
+            per["rngs"] = rngs
+        for name, v in per.items():
+            if not isinstance(v, (list, tuple)) or len(v) != K:
+                raise ValueError(f"iqlhip: {what} of a group of {K} needs {name} as a list of {K} entries")
+
+    def _run_online(self, rings, transitions, Bs, act_next, rngs, draw, call):
+        """Every member inserts one transition into its ring, draws its batch, takes one step and (where act_next asks)
+        acts, in the one library call `call` makes — what both online methods do once their checks have passed.
+        transitions: (states, actions, rewards, next_states, dones), K entries each.  draw(k, new_size, rng): member
+        k's host index arrays over its size after the insert, in batch order, from rng (rngs[k]; None: the global
+        np.random) — called in member order.  call(g, ring_args, rows, idx, scs, out, act_args, stream) returns the
+        library's status: ring_args = (rings, ld, capacities, pointers) and act_args = (states in, member mask,
+        max_action, seeds, actions out) are in the library's argument order, rows and idx are host addresses.  Only
+        when the status is OK does anything move: every ring past its insert, every member past its step.  Returns the
         logs, or (logs, actions) when the call took act_next."""
-        for k, buf in enumerate(bufs):
+        K, ld = len(self.trainers), rings[0]._ld
+        rows, want, act = self._online_rows(ld, *transitions, act_next)
+        slots = [b._insert_slot() for b in rings]
+        idx = []                         # (the members' index lists one after another)
+        for k in range(K):
+            idx.extend(draw(k, slots[k][1], None if rngs is None else rngs[k]))
+        idx = np.ascontiguousarray(np.concatenate(idx), dtype=np.int64)
+        scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
+        out = (C.c_float * (3 * K))()
+        ring_args = ((C.c_void_p * K)(*[b._rows.data_ptr() for b in rings]), ld,
+                     (C.c_int64 * K)(*[b._buffer_size for b in rings]), (C.c_int64 * K)(*[p for p, _ in slots]))
+        hb.check(call(self._group(), ring_args, rows.ctypes.data, idx.ctypes.data, scs, out, tuple(map(_addr, act)),
+                      self.trainers[0]._stream()))
+        for buf, slot in zip(rings, slots):
             buf._writes += 1
-            buf._pointer = (pointers[k] + 1) % buf._buffer_size
-            buf._size = new_sizes[k]
+            buf._advance(*slot)
         logs = self._commit_step(adam_next, out)
         if act_next is None:
             return logs
-        return logs, [a_out[k].copy() if k in want else None for k in range(len(bufs))]
+        return logs, [act[4][k].copy() if k in want else None for k in range(K)]
 
     @staticmethod
     def _solo_online_result(res, act_next):
@@ -632,15 +659,8 @@ class ImplicitQLearningGroup:
         where actions[k] is None for members that asked for none.  Buffers, step counts and schedules move only once
         the call has succeeded."""
         K = len(self.trainers)
-        per = {"buffers": buffers, "states": states, "actions": actions, "rewards": rewards,
-               "next_states": next_states, "dones": dones}
-        if act_next is not None:
-            per["act_next"] = act_next
-        if rngs is not None:
-            per["rngs"] = rngs
-        for name, v in per.items():
-            if not isinstance(v, (list, tuple)) or len(v) != K:
-                raise ValueError(f"iqlhip: online_step of a group of {K} needs {name} as a list of {K} entries")
+        self._online_lists("online_step", act_next, rngs, buffers=buffers, states=states, actions=actions, rewards=rewards,
+                           next_states=next_states, dones=dones)
         bufs = list(buffers)
         Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
         self._check_members()
@@ -652,43 +672,21 @@ class ImplicitQLearningGroup:
             return self._solo_online_result(
                 self.trainers[0].online_step(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], Bs[0],
                                              act_next=None if act_next is None else act_next[0]), act_next)
-        from iqlhip_replay import ReplayBuffer
         for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
             t._prepare(Bs[i])
-            if not getattr(buf, "_gpu", False) or buf._rows.device != t._dev:
-                raise ValueError(f"iqlhip: online_step needs a ReplayBuffer on the trainer's GPU (member {i})")
-            if type(buf)._index_bound is not ReplayBuffer._index_bound or \
-                    type(buf).add_transition is not ReplayBuffer.add_transition:
-                raise NotImplementedError("online_step needs the finetune ReplayBuffer (the offline flavour has no "
-                                          f"add_transition; member {i})")
+            check_online_ring(buf, t._dev, "online_step", member=i)
             if any(buf is b or buf._rows.data_ptr() == b._rows.data_ptr() for b in bufs[:i]):
                 raise ValueError(f"iqlhip: member {i} shares a replay buffer with an earlier member (one buffer each)")
-        ld = bufs[0]._ld
-        if any(b._ld != ld for b in bufs):
+        if any(b._ld != bufs[0]._ld for b in bufs):
             raise ValueError("iqlhip: the members' buffers have different row strides")
-        rows, want, act = self._online_rows(ld, states, actions, rewards, next_states, dones, act_next)
-        # (the buffers' and the trainers' counters move only once the library call has succeeded)
-        pointers = [b._pointer for b in bufs]
-        new_sizes = [min(b._size + 1, b._buffer_size) for b in bufs]
-        idx = []                         # (the members' index lists one after another)
-        for k in range(K):               # sample()'s draw over the size AFTER the insert
-            rng = np.random if rngs is None else rngs[k]
-            idx.append(np.asarray(rng.randint(0, new_sizes[k], size=Bs[k]), dtype=np.int64))
-        idx = np.ascontiguousarray(np.concatenate(idx))
-        scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
-        out = (C.c_float * (3 * K))()
-        ring_ptrs = (C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs])
-        caps = (C.c_int64 * K)(*[b._buffer_size for b in bufs])
-        ptrs = (C.c_int64 * K)(*pointers)
-        g, stream = self._group(), self.trainers[0]._stream()
-        if self._mixed_batch:
-            rc = hb.lib().iqlhip_group_online_step_mixed(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
-                                                         (C.c_int32 * K)(*Bs), scs, out, *map(_addr, act), stream)
-        else:
-            rc = hb.lib().iqlhip_group_online_step(g, ring_ptrs, ld, caps, ptrs, rows.ctypes.data, idx.ctypes.data,
-                                                   Bs[0], scs, out, *map(_addr, act), stream)
-        hb.check(rc)
-        return self._online_commit(bufs, pointers, new_sizes, adam_next, out, act_next, want, act[4])
+
+        def call(g, ring_args, rows, idx, scs, out, act_args, stream):
+            if self._mixed_batch:
+                return hb.lib().iqlhip_group_online_step_mixed(g, *ring_args, rows, idx, (C.c_int32 * K)(*Bs), scs, out,
+                                                               *act_args, stream)
+            return hb.lib().iqlhip_group_online_step(g, *ring_args, rows, idx, Bs[0], scs, out, *act_args, stream)
+        return self._run_online(bufs, (states, actions, rewards, next_states, dones), Bs, act_next, rngs,
+                                lambda k, new_size, rng: (draw_indices(new_size, Bs[k], rng),), call)
 
     # ------------------------------------------------------------------ batches mixed from an offline and an online buffer
     def _replay_mix_args(self, offline_buffers, online_buffers, batch_size, mixing_ratio, burst: bool):
@@ -744,14 +742,8 @@ class ImplicitQLearningGroup:
         the return value as online_step.  Everything is checked before anything is drawn, launched or moved."""
         import iqlhip_mixed as mixed
         K = len(self.trainers)
-        per = {"states": states, "actions": actions, "rewards": rewards, "next_states": next_states, "dones": dones}
-        if act_next is not None:
-            per["act_next"] = act_next
-        if rngs is not None:
-            per["rngs"] = rngs
-        for name, v in per.items():
-            if not isinstance(v, (list, tuple)) or len(v) != K:
-                raise ValueError(f"iqlhip: online_step_replay_mix of a group of {K} needs {name} as a list of {K} entries")
+        self._online_lists("online_step_replay_mix", act_next, rngs, states=states, actions=actions, rewards=rewards,
+                           next_states=next_states, dones=dones)
         offs, ons, Bs, n_offs = self._replay_mix_args(offline_buffers, online_buffers, batch_size, mixing_ratio, burst=False)
         if act_next is not None:         # (before any ring, counter or parameter moves)
             self._check_eval_forward([k for k in range(K) if act_next[k] is not None],
@@ -764,29 +756,15 @@ class ImplicitQLearningGroup:
                 act_next)
         for t, B in zip(self.trainers, Bs):
             t._prepare(B)
-        ld = ons[0]._ld
-        rows, want, act = self._online_rows(ld, states, actions, rewards, next_states, dones, act_next)
-        # (the buffers' and the trainers' counters move only once the library call has succeeded)
-        pointers = [b._pointer for b in ons]
-        new_sizes = [min(b._size + 1, b._buffer_size) for b in ons]
-        idx = []                         # (per member: its offline indices, then its online ones — the batch order)
-        for k in range(K):
-            if rngs is None:
-                pair = mixed.draw_host_indices(offs[k]._size, n_offs[k], new_sizes[k], Bs[k] - n_offs[k])
-            else:
-                pair = mixed.draw_host_indices(offs[k]._size, n_offs[k], new_sizes[k], Bs[k] - n_offs[k], rng=rngs[k])
-            idx.extend(pair)
-        idx = np.ascontiguousarray(np.concatenate(idx), dtype=np.int64)
-        scs, adam_next = self._next_scalars([1.0 / B for B in Bs])
-        out = (C.c_float * (3 * K))()
-        rc = hb.lib().iqlhip_group_online_step_replay2(
-            self._group(), (C.c_void_p * K)(*[b._rows.data_ptr() for b in ons]), ld,
-            (C.c_int64 * K)(*[b._buffer_size for b in ons]), (C.c_int64 * K)(*pointers), rows.ctypes.data, idx.ctypes.data,
-            (C.c_int32 * K)(*Bs), scs, out, *map(_addr, act), self.trainers[0]._stream(),
-            (C.c_void_p * K)(*[b._rows.data_ptr() for b in offs]), (C.c_int64 * K)(*[b._size for b in offs]),
-            (C.c_int32 * K)(*n_offs))
-        hb.check(rc)
-        return self._online_commit(ons, pointers, new_sizes, adam_next, out, act_next, want, act[4])
+
+        def call(g, ring_args, rows, idx, scs, out, act_args, stream):
+            return hb.lib().iqlhip_group_online_step_replay2(
+                g, *ring_args, rows, idx, (C.c_int32 * K)(*Bs), scs, out, *act_args, stream,
+                (C.c_void_p * K)(*[b._rows.data_ptr() for b in offs]), (C.c_int64 * K)(*[b._size for b in offs]),
+                (C.c_int32 * K)(*n_offs))
+        return self._run_online(ons, (states, actions, rewards, next_states, dones), Bs, act_next, rngs,
+                                lambda k, new_size, rng: mixed.draw_host_indices(offs[k]._size, n_offs[k], new_size,
+                                                                                 Bs[k] - n_offs[k], rng=rng), call)
 
     def train_steps_replay_mix(self, offline_buffers, online_buffers, n_steps: int, batch_size, seeds: Sequence[int],
                                mixing_ratio=0.5, return_losses: bool = True, chunk: int = K_MAX,

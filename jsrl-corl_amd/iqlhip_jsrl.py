@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 import iqlhip_binding as hb
+from iqlhip_replay import check_online_ring, draw_indices
 
 WHO_GUIDE, WHO_LEARNER, WHO_GATE, WHO_CRITIC = 0, 1, 2, 3
 HORIZON_FNS = ("time_step", "agent_type", "goal_dist", "variance")
@@ -411,30 +412,18 @@ def online_step_jsrl(trainer, jsrl: JsrlActors, replay_buffer, state, action, re
         log = self.online_step(replay_buffer, state, action, reward, next_state, done, batch_size)
         a, u, h = jsrl.act([act_next], [w], None if gate_max is None else [gm])[0]
         return log, a[0], int(u[0]), (None if h is None else float(h[0]))
-    buf = replay_buffer
-    if not getattr(buf, "_gpu", False) or buf._rows.device != self._dev:
-        raise ValueError("online_step needs a ReplayBuffer on the trainer's GPU")
-    from iqlhip_replay import ReplayBuffer
-    if type(buf)._index_bound is not ReplayBuffer._index_bound or type(buf).add_transition is not ReplayBuffer.add_transition:
-        raise NotImplementedError("online_step needs the finetune ReplayBuffer (the offline flavour has no add_transition)")
-    row = self._online_row(buf, state, action, reward, next_state, done)
-    pointer = buf._pointer
-    new_size = min(buf._size + 1, buf._buffer_size)
-    idx = np.random.randint(0, new_size, size=batch_size)
-    if idx.dtype != np.int64:
-        idx = idx.astype(np.int64)
-    adam_next = {g: t + 1 for g, t in self._adam_t.items()}
-    sc = hb.StepScalars()
-    self._fill_scalars(sc, adam_next, self._current_lrs(), dp.inv_batch(batch_size, self._dp_world))
-    out = (C.c_float * 3)()
+    check_online_ring(replay_buffer, self._dev, "online_step")
     _, gs, _ = jsrl._members()
-    gs[0]._prepare_act()
-    a_in, a_out, seed = self._act_next_args(act_next)
+    gs[0]._prepare_act()                 # (at most sends the guide's inference rate and key: no random stream is consumed)
     flag, h = C.c_int32(0), C.c_float(0.0)
     has_gate = jsrl.gates[0] is not None
-    hb.check(hb.lib().iqlhip_jsrl_online_step(
-        jsrl._handle(), buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer, row.ctypes.data, idx.ctypes.data,
-        batch_size, C.byref(sc), out, a_in.ctypes.data, int(w[0]), gm, seed, float(self.actor.max_action),
-        float(gs[0].actor.max_action), a_out.ctypes.data, C.byref(flag), C.byref(h) if has_gate else None, self._stream()))
-    log, a = self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+
+    def call(ring_args, row, idx, sc, out, act_args, stream):
+        a_in, max_action, seed, a_out = act_args
+        return hb.lib().iqlhip_jsrl_online_step(jsrl._handle(), *ring_args, row, idx, batch_size, sc, out, a_in, int(w[0]), gm,
+                                                seed, max_action, float(gs[0].actor.max_action), a_out, C.byref(flag),
+                                                C.byref(h) if has_gate else None, stream)
+    log, a = self._run_online(replay_buffer, (state, action, reward, next_state, done), act_next,
+                              lambda new_size: draw_indices(new_size, batch_size), dp.inv_batch(batch_size, self._dp_world),
+                              call)
     return log, a, int(flag.value), (float(h.value) if has_gate else None)

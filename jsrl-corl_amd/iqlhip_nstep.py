@@ -15,16 +15,14 @@ it as it is.  Its `sample().dones` therefore holds FRACTIONS by design (0 only f
 The `discount` given here must be the trainer's.  There is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
-import numpy as np
 import torch
 
 import iqlhip_binding as hb
 import iqlhip_dp as dp
-from iqlhip_replay import ReplayBuffer
+from iqlhip_replay import check_online_ring, draw_indices
 
 MAX_HORIZON = hb.IQLHIP_NSTEP_MAX_HORIZON
 
@@ -130,32 +128,22 @@ def online_step_nstep(trainer, nstep: NStepReplay, state, action, reward, next_s
                                   "(use nstep.add_transition / nstep.buffer.sample / train)")
     self._prepare(batch_size)
     raw, buf = nstep.raw, nstep.buffer
-    if buf._rows.device != self._dev:
-        raise ValueError("online_step_nstep needs an NStepReplay on the trainer's GPU")
-    if type(raw)._index_bound is not ReplayBuffer._index_bound or type(raw).add_transition is not ReplayBuffer.add_transition:
-        raise NotImplementedError("online_step_nstep needs the finetune ReplayBuffer (the offline flavour has no add_transition)")
+    check_online_ring(raw, self._dev, "online_step_nstep", holder="an NStepReplay")
     if buf._weights_tracks:
         raise NotImplementedError("iqlhip: online_step_nstep does not enter the new row into a tracking sample-weight table "
                                   "(use nstep.add_transition, then the prioritised calls)")
     end = bool(done) if episode_end is None else bool(episode_end)
-    row = self._online_row(raw, state, action, reward, next_state, done)
-    # (the buffers' and the trainer's counters move only once the library call has succeeded)
-    pointer = raw._pointer
-    new_size = min(raw._size + 1, raw._buffer_size)
-    idx = np.random.randint(0, new_size, size=batch_size)        # sample()'s draw over the size AFTER the insert
-    if idx.dtype != np.int64:
-        idx = idx.astype(np.int64)
-    adam_next = {g: t + 1 for g, t in self._adam_t.items()}
-    sc = hb.StepScalars()
-    self._fill_scalars(sc, adam_next, self._current_lrs(), dp.inv_batch(batch_size, self._dp_world))
-    out = (C.c_float * 3)()
-    a_in, a_out, seed = self._act_next_args(act_next)
-    hb.check(hb.lib().iqlhip_online_step_nstep(
-        self._ctx, raw._rows.data_ptr(), buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer, row.ctypes.data,
-        idx.ctypes.data, batch_size, C.byref(sc), out, None if a_in is None else a_in.ctypes.data,
-        float(self.actor.max_action), seed, None if a_out is None else a_out.ctypes.data, self._stream(),
-        nstep.ends.data_ptr(), int(end), new_size, nstep.n, nstep.discount, nstep.steps.data_ptr()))
-    raw._writes += 1
-    raw._pointer = (pointer + 1) % raw._buffer_size
-    raw._size = new_size
-    return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+    new_size = raw._insert_slot()[1]     # (the library takes it next to the pointer; the driver's draw runs over the same)
+
+    def call(ring_args, row, idx, sc, out, act_args, stream):      # (the driver's ring is the raw one)
+        raw_rows, ld, capacity, pointer = ring_args
+        return hb.lib().iqlhip_online_step_nstep(self._ctx, raw_rows, buf._rows.data_ptr(), ld, capacity, pointer, row, idx,
+                                                 batch_size, sc, out, *act_args, stream, nstep.ends.data_ptr(), int(end),
+                                                 new_size, nstep.n, nstep.discount, nstep.steps.data_ptr())
+
+    def commit_extra():                  # (the raw ring has moved: the derived one follows it)
+        buf._writes += 1
+        nstep._sync_counters()
+    return self._run_online(raw, (state, action, reward, next_state, done), act_next,
+                            lambda bound: draw_indices(bound, batch_size), dp.inv_batch(batch_size, self._dp_world),
+                            call, commit_extra)

@@ -541,11 +541,7 @@ class ReplayBuffer:
         else:
             host = None
             row = np.zeros((self._ld,), dtype=np.float32)
-        row[:S] = np.asarray(state, dtype=np.float32).reshape(-1)
-        row[S: S + A] = np.asarray(action, dtype=np.float32).reshape(-1)
-        row[S + A: 2 * S + A] = np.asarray(next_state, dtype=np.float32).reshape(-1)
-        row[2 * S + A] = np.float32(reward)
-        row[2 * S + A + 1] = np.float32(done)
+        pack_transition(row, S, A, state, action, reward, next_state, done)
         if host is not None:
             dev = self._rows.device
             if torch.cuda.current_device() == dev.index:
@@ -559,8 +555,17 @@ class ReplayBuffer:
             self._rows[self._pointer].copy_(torch.from_numpy(row))
         if self._weights_tracks:             # behind the ring write, on the same stream: the new row at the running maximum
             self.insert_max_sample_weight(self._pointer)
-        self._pointer = (self._pointer + 1) % self._buffer_size
-        self._size = min(self._size + 1, self._buffer_size)
+        self._advance(*self._insert_slot())
+
+    # ---- what add_transition and the fused online calls (online_step*, which write the row in the library) share ----
+    def _insert_slot(self):
+        """(the ring position the next row goes to, the size after that insert)."""
+        return self._pointer, min(self._size + 1, self._buffer_size)
+
+    def _advance(self, pointer: int, new_size: int) -> None:
+        """Behind a row written at `pointer`: the ring's pointer and size move past it."""
+        self._pointer = (pointer + 1) % self._buffer_size
+        self._size = new_size
 
 
 class OfflineReplayBuffer(ReplayBuffer):
@@ -572,3 +577,32 @@ class OfflineReplayBuffer(ReplayBuffer):
 
     def add_transition(self, *args, **kwargs):
         raise NotImplementedError
+
+
+def pack_transition(row: np.ndarray, S: int, A: int, state, action, reward, next_state, done) -> None:
+    """One transition into a packed float32 host row [ld]: s | a | s' | r | d (the pad columns stay as they are)."""
+    row[:S] = np.asarray(state, dtype=np.float32).reshape(-1)
+    row[S: S + A] = np.asarray(action, dtype=np.float32).reshape(-1)
+    row[S + A: 2 * S + A] = np.asarray(next_state, dtype=np.float32).reshape(-1)
+    row[2 * S + A] = np.float32(reward)
+    row[2 * S + A + 1] = np.float32(done)
+
+
+def check_online_ring(buf, device, what: str, holder: str = "a ReplayBuffer", member=None) -> None:
+    """What every fused online call asks of the ring it inserts into: a finetune ReplayBuffer on `device`, the trainer's
+    GPU.  what: the calling method, as the message names it; holder: what the caller was given (an NStepReplay wraps
+    its ring); member: the group member the ring belongs to, named in the message.  ValueError for a ring elsewhere,
+    NotImplementedError for the offline flavour — before anything is drawn or moves."""
+    if not getattr(buf, "_gpu", False) or buf._rows.device != device:
+        raise ValueError(f"{what} needs {holder} on the trainer's GPU" if member is None else
+                         f"iqlhip: {what} needs {holder} on the trainer's GPU (member {member})")
+    if type(buf)._index_bound is not ReplayBuffer._index_bound or type(buf).add_transition is not ReplayBuffer.add_transition:
+        raise NotImplementedError(f"{what} needs the finetune ReplayBuffer (the offline flavour has no add_transition" +
+                                  (")" if member is None else f"; member {member})"))
+
+
+def draw_indices(bound: int, n: int, rng=None) -> np.ndarray:
+    """sample()'s host draw as the fused online calls pass it to the library: n int64 indices below `bound`, from `rng`
+    (a np.random.RandomState) or the global np.random."""
+    idx = (np.random if rng is None else rng).randint(0, bound, size=n)
+    return idx if idx.dtype == np.int64 else idx.astype(np.int64)

@@ -29,6 +29,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 
 import iqlhip_binding as hb
 import iqlhip_dp as dp
+from iqlhip_replay import check_online_ring, draw_indices, pack_transition
 from iqlhip_networks import (DeterministicPolicy, GaussianPolicy, LOG_STD_MAX, LOG_STD_MIN, dropout_p, register_actor_owner,
                              linear_layers)
 
@@ -106,6 +107,7 @@ class ImplicitQLearning:
         self._ts_token = None         # (buffer, its write count) of the last train_steps call
         self._eager_next = None       # scalars of the next eager step, computed ahead (train() on a fresh sample() block)
         self._loss_out = (C.c_float * 3)()
+        self._on_scalars = hb.StepScalars()     # the online calls' step scalars, filled anew by every call
 
         self._ctx = None
         self._max_batch = 0
@@ -180,6 +182,7 @@ class ImplicitQLearning:
                                    "trainer's first step (or call reserve_batch) with the largest batch first")
             old = (self._params_arena, self._target_arena, self._m_arena, self._v_arena)
         self._S, self._A, self._gaussian, self._layout = S, A, gaussian, L
+        self._on_row = np.zeros(hb.row_stride(S, A), dtype=np.float32)      # the online calls' packed host row
         if old is None:
             self._params_arena = torch.zeros(L.n_params, dtype=torch.float32, device=dev)
             self._target_arena = torch.zeros(L.n_target, dtype=torch.float32, device=dev)
@@ -730,18 +733,13 @@ class ImplicitQLearning:
             log.update(self._stats_entries())
         return log
 
-    # ---- what online_step and online_step_mixed share: the packed host row, the act_next arguments, the commit
+    # ---- the online iteration: one driver behind every online_step* method ---------------------------------------
     def _online_row(self, buf, state, action, reward, next_state, done) -> np.ndarray:
         """The new transition as one packed host row [ld] (pad columns zero)."""
-        S, A = self._S, self._A
-        row = getattr(self, "_on_row", None)
-        if row is None or row.shape[0] != buf._ld:
+        row = self._on_row
+        if row.shape[0] != buf._ld:      # (a ring of another stride: the library reads ld floats of the row)
             row = self._on_row = np.zeros(buf._ld, dtype=np.float32)
-        row[:S] = np.asarray(state, dtype=np.float32).reshape(-1)
-        row[S: S + A] = np.asarray(action, dtype=np.float32).reshape(-1)
-        row[S + A: 2 * S + A] = np.asarray(next_state, dtype=np.float32).reshape(-1)
-        row[2 * S + A] = np.float32(reward)
-        row[2 * S + A + 1] = np.float32(done)
+        pack_transition(row, self._S, self._A, state, action, reward, next_state, done)
         return row
 
     def _act_next_args(self, act_next):
@@ -756,14 +754,37 @@ class ImplicitQLearning:
         a_out = np.empty(self._A, dtype=np.float32)
         return a_in, a_out, (self._act_seed() if (self.actor.training and self._gaussian) else 0)
 
-    def _online_commit(self, buf, pointer: int, new_size: int, adam_next, out, a_out):
-        """After the library call has succeeded: the ring's and the trainer's counters move, the result is built."""
-        buf._writes += 1
-        buf._pointer = (pointer + 1) % buf._buffer_size
-        buf._size = new_size
+    def _run_online(self, ring, transition, act_next, draw, inv_batch: float, call, commit_extra=None):
+        """Insert one transition into `ring`, draw a batch, take one step and (with act_next) act, in the one library
+        call `call` makes — what every online_step* method does once its own checks have passed.
+        transition: (state, action, reward, next_state, done).  draw(new_size): the batch's host indices over the size
+        after the insert, an int64 array; None for a call that draws on the device.  inv_batch: what the step's
+        scalars carry — dp.inv_batch(batch_size, world) from the callers that run under data parallelism, 1.0 /
+        batch_size from those that refuse it (world = 1: the two coincide).  call(ring_args, row, idx, sc, out, act_args,
+        stream) returns the library's status: ring_args = (rows, ld, capacity, pointer) and act_args = (state in,
+        max_action, seed, action out) are in the library's argument order, row and idx are host addresses (idx None
+        without draw), sc is the scalars by reference, out the three losses.  The global numpy stream is consumed
+        by draw alone, behind the row and in front of the act seed.  Only when the status is OK does anything move:
+        the ring's counters, total_it, the Adam step counts and the schedule — then commit_extra(), for what one
+        variant moves besides.  Returns train()'s dict, or (dict, action) with act_next."""
+        row = self._online_row(ring, *transition)
+        pointer, new_size = ring._insert_slot()
+        idx = None if draw is None else draw(new_size)
+        adam_next = {g: t + 1 for g, t in self._adam_t.items()}
+        sc, out = self._on_scalars, self._loss_out          # (both are read and written inside the call alone)
+        self._fill_scalars(sc, adam_next, self._current_lrs(), inv_batch)
+        a_in, a_out, seed = self._act_next_args(act_next)
+        act_args = (None if a_in is None else a_in.ctypes.data, float(self.actor.max_action), seed,
+                    None if a_out is None else a_out.ctypes.data)
+        hb.check(call((ring._rows.data_ptr(), ring._ld, ring._buffer_size, pointer), row.ctypes.data,
+                      None if idx is None else idx.ctypes.data, C.byref(sc), out, act_args, self._stream()))
+        ring._writes += 1
+        ring._advance(pointer, new_size)
         self.total_it += 1
         self._adam_t = adam_next
         self._advance_schedule(1)
+        if commit_extra is not None:
+            commit_extra()
         log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
         if self._step_stats:
             log.update(self._stats_entries())
@@ -780,33 +801,17 @@ class ImplicitQLearning:
         `self.actor.act(act_next, device)` evaluated with the UPDATED policy — what the loop's next iteration would
         compute first (iql.py:728) — under the same single synchronisation: returns (log, action)."""
         self._prepare(batch_size)
-        buf = replay_buffer
-        if not getattr(buf, "_gpu", False) or buf._rows.device != self._dev:
-            raise ValueError("online_step needs a ReplayBuffer on the trainer's GPU")
+        check_online_ring(replay_buffer, self._dev, "online_step")
         if self._dp_world > 1 and self._dp_exchange == "torch":
             raise NotImplementedError("online_step runs the whole step in one library call: it needs an in-library "
                                       "exchange, enable_data_parallel(exchange='rccl'|'p2p') — with exchange='torch' "
                                       "use add_transition / sample / train")
-        row = self._online_row(buf, state, action, reward, next_state, done)
-        # (the buffer's and the trainer's counters move only once the library call has succeeded)
-        pointer = buf._pointer
-        new_size = min(buf._size + 1, buf._buffer_size)
-        from iqlhip_replay import ReplayBuffer
-        if type(buf)._index_bound is not ReplayBuffer._index_bound or type(buf).add_transition is not ReplayBuffer.add_transition:
-            raise NotImplementedError("online_step needs the finetune ReplayBuffer (the offline flavour has no add_transition)")
-        idx = np.random.randint(0, new_size, size=batch_size)        # sample()'s draw over the size AFTER the insert
-        if idx.dtype != np.int64:
-            idx = idx.astype(np.int64)
-        adam_next = {g: t + 1 for g, t in self._adam_t.items()}
-        sc = hb.StepScalars()
-        self._fill_scalars(sc, adam_next, self._current_lrs(), dp.inv_batch(batch_size, self._dp_world))
-        out = (C.c_float * 3)()
-        a_in, a_out, seed = self._act_next_args(act_next)
-        hb.check(hb.lib().iqlhip_online_step(self._ctx, buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer,
-                                             row.ctypes.data, idx.ctypes.data, batch_size, C.byref(sc), out,
-                                             None if a_in is None else a_in.ctypes.data, float(self.actor.max_action),
-                                             seed, None if a_out is None else a_out.ctypes.data, self._stream()))
-        return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+
+        def call(ring_args, row, idx, sc, out, act_args, stream):
+            return hb.lib().iqlhip_online_step(self._ctx, *ring_args, row, idx, batch_size, sc, out, *act_args, stream)
+        return self._run_online(replay_buffer, (state, action, reward, next_state, done), act_next,
+                                lambda new_size: draw_indices(new_size, batch_size),
+                                dp.inv_batch(batch_size, self._dp_world), call)
 
     def online_step_nstep(self, nstep, state, action, reward: float, next_state, done: bool, batch_size: int,
                           episode_end: Optional[bool] = None, act_next: Optional[np.ndarray] = None):
@@ -837,14 +842,9 @@ class ImplicitQLearning:
         alpha, eps or is_beta negative, not finite (or alpha = eps = 0); NotImplementedError at bf16 precision, under
         data parallelism and with injected dropout masks pending — all before anything moves."""
         import iqlhip_weighted as wtd
-        from iqlhip_replay import ReplayBuffer
         self._require_gpu()
         buf = replay_buffer
-        if not getattr(buf, "_gpu", False) or buf._rows.device != self._dev:
-            raise ValueError("online_step_prioritized needs a ReplayBuffer on the trainer's GPU")
-        if type(buf)._index_bound is not ReplayBuffer._index_bound or type(buf).add_transition is not ReplayBuffer.add_transition:
-            raise NotImplementedError("online_step_prioritized needs the finetune ReplayBuffer (the offline flavour has "
-                                      "no add_transition)")
+        check_online_ring(buf, self._dev, "online_step_prioritized")
         wtd.check_call(buf)
         if not buf._weights_updatable or not buf._weights_tracks:
             raise ValueError("iqlhip: online_step_prioritized needs sample weights that track their maximum "
@@ -857,26 +857,21 @@ class ImplicitQLearning:
         self._refuse_injected_masks()
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         off = (getattr(buf, "_prio_online_offset", 0) if offset is None else int(offset)) & 0xFFFFFFFFFFFFFFFF
-        row = self._online_row(buf, state, action, reward, next_state, done)
-        # (the buffer's and the trainer's counters move only once the library call has succeeded)
-        pointer = buf._pointer
-        new_size = min(buf._size + 1, buf._buffer_size)
-        adam_next = {g: t + 1 for g, t in self._adam_t.items()}
-        sc = hb.StepScalars()
-        self._fill_scalars(sc, adam_next, self._current_lrs(), 1.0 / batch_size)
-        out = (C.c_float * 3)()
-        a_in, a_out, act_seed = self._act_next_args(act_next)
-        self._last_td = None
-        hb.check(hb.lib().iqlhip_online_step_prioritized(
-            self._ctx, buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer, row.ctypes.data, batch_size, C.byref(sc), out,
-            None if a_in is None else a_in.ctypes.data, float(self.actor.max_action), act_seed,
-            None if a_out is None else a_out.ctypes.data, self._stream(), buf._weights, seed, off, beta, alpha, eps))
-        buf._weights_version += 2            # (the insert and the update, as the library counts them)
-        buf._prio_online_offset = (off + wtd.online_offset_step(batch_size)) & 0xFFFFFFFFFFFFFFFF
-        res = self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
-        self._last_td, self._last_td_it = ("online", batch_size), self.total_it
-        self._last_prio_idx = (self.total_it, batch_size)
-        return res
+
+        def call(ring_args, row, idx, sc, out, act_args, stream):
+            # (the one side effect of a `call`: the library may overwrite the device's TD errors before it fails, so the
+            # previous ones are given up here, behind every check and immediately in front of the library call)
+            self._last_td = None
+            return hb.lib().iqlhip_online_step_prioritized(self._ctx, *ring_args, row, batch_size, sc, out, *act_args, stream,
+                                                           buf._weights, seed, off, beta, alpha, eps)
+
+        def commit_extra():
+            buf._weights_version += 2            # (the insert and the update, as the library counts them)
+            buf._prio_online_offset = (off + wtd.online_offset_step(batch_size)) & 0xFFFFFFFFFFFFFFFF
+            self._last_td, self._last_td_it = ("online", batch_size), self.total_it
+            self._last_prio_idx = (self.total_it, batch_size)
+        return self._run_online(buf, (state, action, reward, next_state, done), act_next, None, 1.0 / batch_size, call,
+                                commit_extra)
 
     def online_step_jsrl(self, jsrl, replay_buffer, state, action, reward: float, next_state, done: bool,
                          batch_size: int, act_next, who, gate_max=None):
@@ -991,23 +986,19 @@ class ImplicitQLearning:
         import iqlhip_mixed as mixed
         n_off, n_on = self._mixed_args(offline_buffer, online_buffer, batch_size, mixing_ratio)
         self._prepare(batch_size)
-        buf = online_buffer
-        row = self._online_row(buf, state, action, reward, next_state, done)
-        # (the buffer's and the trainer's counters move only once the library call has succeeded)
-        pointer = buf._pointer
-        new_size = min(buf._size + 1, buf._buffer_size)
-        idx_off, idx_on = mixed.draw_host_indices(offline_buffer._size, n_off, new_size, n_on)
-        adam_next = {g: t + 1 for g, t in self._adam_t.items()}
-        sc = hb.StepScalars()
-        self._fill_scalars(sc, adam_next, self._current_lrs(), 1.0 / batch_size)
-        out = (C.c_float * 3)()
-        a_in, a_out, seed = self._act_next_args(act_next)
-        hb.check(hb.lib().iqlhip_online_step_mixed(
-            self._ctx, buf._rows.data_ptr(), buf._ld, buf._buffer_size, pointer, row.ctypes.data, idx_on.ctypes.data,
-            n_on, C.byref(sc), out, None if a_in is None else a_in.ctypes.data, float(self.actor.max_action), seed,
-            None if a_out is None else a_out.ctypes.data, self._stream(), offline_buffer._rows.data_ptr(),
-            offline_buffer._size, idx_off.ctypes.data, n_off))
-        return self._online_commit(buf, pointer, new_size, adam_next, out, a_out)
+        idx_off = None
+
+        def draw(new_size):
+            nonlocal idx_off
+            idx_off, idx_on = mixed.draw_host_indices(offline_buffer._size, n_off, new_size, n_on)
+            return idx_on
+
+        def call(ring_args, row, idx, sc, out, act_args, stream):
+            return hb.lib().iqlhip_online_step_mixed(self._ctx, *ring_args, row, idx, n_on, sc, out, *act_args, stream,
+                                                     offline_buffer._rows.data_ptr(), offline_buffer._size,
+                                                     idx_off.ctypes.data, n_off)
+        return self._run_online(online_buffer, (state, action, reward, next_state, done), act_next, draw, 1.0 / batch_size,
+                                call)
 
     def prepare_train_steps_mixed(self, offline_buffer, online_buffer, batch_size: int, mixing_ratio: float = 0.5) -> None:
         """prepare_train_steps for the chunk graphs train_steps_mixed replays on this pair of buffers and this split."""
