@@ -454,6 +454,52 @@ int iqlhip_online_step_nstep(iqlhip_ctx* ctx, float* raw_dev, float* rows_dev, i
                              float* act_out_host, void* stream, uint8_t* ends_dev, int32_t episode_end, int64_t size_after,
                              int32_t horizon, double discount, uint8_t* steps_dev);
 
+/* ---- vector-environment online step --------------------------------------------------------------------------
+ * One agent, E environments and an update-to-data ratio of U: E transitions into the ring, U gradient steps and the
+ * next actions of E2 states in one call and under one synchronisation.
+ * IQLHIP_VEC_MAX_ENVS bounds E and E2: one pinned staging block of 64 rows of at most iqlhip_row_stride(S, A) floats,
+ * under 70 KB at IQLHIP_MAX_INPUT.  IQLHIP_VEC_MAX_UPDATES bounds U.
+ *
+ * iqlhip_rows_write_ring: the n_rows packed rows rows_pin[j][ld] — pinned, host-mapped memory (or device memory) that the
+ * caller leaves untouched until the launch has run — are stored at ring rows (pointer + j) mod capacity of rows_dev, in
+ * one launch on `stream`; no context.  1 <= n_rows <= min(capacity, IQLHIP_VEC_MAX_ENVS), ld a multiple of 4 and >= 8,
+ * both blocks 16-byte aligned, 0 <= pointer < capacity (IQLHIP_EINVAL otherwise, before the launch).
+ *
+ * iqlhip_online_step_vec, queued on `stream`:
+ *   1. one launch stores the n_rows new rows rows_host[j][ld] at ring rows (pointer + j) mod capacity and gathers the
+ *      n_updates * batch_rows rows rows_dev[idx_host[..]] — the indices of n_updates consecutive sample() draws over the
+ *      size after all inserts — into a staging block [n_updates][batch_rows][ld] the context owns (sized on first use,
+ *      grown when a call needs more).  A drawn index i with (i - pointer) mod capacity < n_rows reads new row j from
+ *      the host words: the ring write of another block may not have landed.  No other ring row is written;
+ *   2. n_updates eager steps back to back, the launches of iqlhip_step each: step u trains on slice u of the staging
+ *      block with the scalars sc[u]; its losses land in out[3 * u ..]; with statistics enabled its 16 numbers go to slot
+ *      u of the ring iqlhip_read_stats_ring reads; actor dropout draws its keep-bits per step as iqlhip_step does;
+ *      iqlhip_read_grad_clip reports the last step;
+ *   3. act_states_host != NULL: the actions of act_rows states [act_rows][state_dim] by the updated policy —
+ *      iqlhip_actor_sample's launches over act_rows rows when act_seed != 0 and the policy is Gaussian (the noise call
+ *      counter advances by one), else iqlhip_actor_forward's; the inference keep-bit stream advances by one call as
+ *      theirs does — into act_out_host [act_rows][action_dim].
+ * The call's last launch stores the completion word the host spins on (an act over more than 256 action words adds a
+ * one-thread launch for it); n_updates = 0 without an act ends on a stream synchronisation.  Launches: 1 + 3 n_updates
+ * + the act's, plus per step the keep-bit launch with actor dropout, the two or three statistics / clip launches when
+ * those are on, and the shadow refresh at bf16 precision — what iqlhip_step itself launches.
+ * rows_host, idx_host, sc, act_states_host are ordinary host memory (copied into pinned staging inside the call);
+ * idx_host, sc and out may be NULL when n_updates = 0.  Bit for bit what n_rows single ring writes, n_updates times
+ * iqlhip_rows_sample_packed + iqlhip_step_sync, and the actor call give.
+ * Refused before anything is launched or any counter moves — IQLHIP_EINVAL: a NULL argument, ld other than the context's
+ * row stride, misaligned rows, pointer outside the ring, n_rows outside [1, min(capacity, IQLHIP_VEC_MAX_ENVS)],
+ * n_updates outside [0, IQLHIP_VEC_MAX_UPDATES], act_rows outside [1, IQLHIP_VEC_MAX_ENVS], batch_rows outside
+ * [1, min(512, max_batch)]; IQLHIP_EINDEX: an index outside [0, capacity); IQLHIP_EUNSUPPORTED: a data-parallel exchange
+ * attached, injected keep-bits pending, bf16 batches of more than 512 rows, and what statistics and clipping refuse. */
+#define IQLHIP_VEC_MAX_ENVS 64
+#define IQLHIP_VEC_MAX_UPDATES 32
+int iqlhip_rows_write_ring(float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer, const float* rows_pin,
+                           int32_t n_rows, void* stream);
+int iqlhip_online_step_vec(iqlhip_ctx* ctx, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                           const float* rows_host, int32_t n_rows, const int64_t* idx_host, int32_t batch_rows,
+                           int32_t n_updates, const iqlhip_step_scalars* sc, float* out, const float* act_states_host,
+                           int32_t act_rows, float max_action, uint64_t act_seed, float* act_out_host, void* stream);
+
 /* Data-parallel split of the same step: forward+backward, then the
  * flat gradient (n_params floats + 4 tail words: 3 loss sums and a spare) is
  * written to grads_dev for the caller's all-reduce, then the update consumes it. */

@@ -355,6 +355,19 @@ struct iqlhip_ctx {
   int ev_used = 0;
   float t_acc[4] = {0, 0, 0, 0};
   int t_n = 0;
+  // the vector-environment online call (iqlhip_online_step_vec; allocated by the first call): pinned, host-mapped staging
+  // of the new rows [IQLHIP_VEC_MAX_ENVS][row_ld], of the drawn indices [IQLHIP_VEC_MAX_UPDATES][VEC_MAX_BATCH], of the
+  // steps' losses [IQLHIP_VEC_MAX_UPDATES][4] and of the act: states in [IQLHIP_VEC_MAX_ENVS][IQLHIP_MAX_INPUT], actions
+  // out [IQLHIP_VEC_MAX_ENVS][IQLHIP_MAX_ACTION]
+  float* vec_rows_pin = nullptr;
+  long long* vec_idx_pin = nullptr;
+  float* vec_loss_pin = nullptr;
+  float* vec_act_pin = nullptr;
+  // ... and the gathered batches of its steps, device [updates][batch_rows][row_ld]: an owner of its own, because the
+  // block is freed and allocated anew when a call needs more (vec_xb_cap floats)
+  Owned vec_own;
+  float* vec_xb = nullptr;
+  size_t vec_xb_cap = 0;
 };
 
 extern "C" int iqlhip_version(void) { return IQLHIP_VERSION; }
@@ -561,6 +574,7 @@ extern "C" int iqlhip_destroy(iqlhip_ctx* c) {
   (void)iqlhip_xch_shutdown(c);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
+  c->vec_own.release_all();
   c->own.release_all();
   delete c;
   return IQLHIP_OK;
@@ -6377,4 +6391,129 @@ extern "C" int iqlhip_online_step_nstep(iqlhip_ctx* c, float* raw_dev, float* ro
   const OnlineNstep ns{raw_dev, ends_dev, steps_dev, size_after, horizon, episode_end, discount};
   return online_step(c, rows_dev, ld, capacity, pointer, row_host, idx_host, n, sc, out, act_state_host, max_action, act_seed,
                      act_out_host, stream, nullptr, 0, nullptr, 0, nullptr, &ns);
+}
+
+// ---------------------------------------------------------------------------
+// The vector-environment online step (include/iqlhip.h "vector-environment online step"; kernel:
+// iqlhip_online_vec_kernels.h, the code object's last): E ring writes, the batches of U steps gathered in the same
+// launch, the U eager steps back to back and the act forward on E2 states, under one synchronisation.
+#include "iqlhip_online_vec_kernels.h"
+constexpr int VEC_MAX_BATCH = 512;      // rows per step: the small-batch kernels, fp32 or bf16
+static_assert(VEC_MAX_BATCH == LB_MIN_ROWS, "the vector online step stays below the large-batch path");
+static_assert(IQLHIP_VEC_MAX_UPDATES <= 1024, "the steps' statistics go to the first slots of the statistics ring");
+
+// What the multi-row ring write asks of its arguments, with or without a context.
+static int vec_ring_ok(const float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer, int32_t n_rows) {
+  if (ld < 8 || (ld & 3)) return fail(IQLHIP_EINVAL, "row stride must be a multiple of 4 floats and at least 8");
+  if (((uintptr_t)rows_dev) & 15) return fail(IQLHIP_EINVAL, "packed rows must be 16-byte aligned");
+  if (capacity < 1 || pointer < 0 || pointer >= capacity) return fail(IQLHIP_EINVAL, "ring pointer outside the buffer");
+  if (n_rows < 1 || n_rows > IQLHIP_VEC_MAX_ENVS || n_rows > capacity)
+    return fail(IQLHIP_EINVAL, "%d new rows outside [1, min(capacity=%lld, %d)]", n_rows, (long long)capacity, IQLHIP_VEC_MAX_ENVS);
+  return IQLHIP_OK;
+}
+static void launch_vec_gather(float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer, const float* rows_pin,
+                              int32_t n_rows, const long long* idx_pin, float* xb, int n, hipStream_t st) {
+  const int total = std::max((int)n_rows, n) * (int)(ld / 4);
+  hipLaunchKernelGGL(iql_online_vec_gather_kernel, dim3((total + 255) / 256), dim3(256), 0, st, rows_dev, (long long)ld,
+                     (long long)capacity, (long long)pointer, rows_pin, (int)n_rows, idx_pin, xb, n);
+}
+
+extern "C" int iqlhip_rows_write_ring(float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer, const float* rows_pin,
+                                      int32_t n_rows, void* stream) {
+  if (!rows_dev || !rows_pin) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (int rc = vec_ring_ok(rows_dev, ld, capacity, pointer, n_rows)) return rc;
+  if (((uintptr_t)rows_pin) & 15) return fail(IQLHIP_EINVAL, "the new rows must be 16-byte aligned");
+  launch_vec_gather(rows_dev, ld, capacity, pointer, rows_pin, n_rows, nullptr, nullptr, 0, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+// The call's buffers: the pinned blocks once, the device staging whenever a call needs more than there is.
+static int vec_buffers(iqlhip_ctx* c, size_t stage_floats) {
+  if (!c->vec_rows_pin) {
+    const int rc = all_or_nothing(c->own, [&]() -> int {
+      HIPCHK(c->own.pin(&c->vec_rows_pin, (size_t)IQLHIP_VEC_MAX_ENVS * c->row_ld * sizeof(float)));
+      HIPCHK(c->own.pin(&c->vec_idx_pin, (size_t)IQLHIP_VEC_MAX_UPDATES * VEC_MAX_BATCH * sizeof(long long)));
+      HIPCHK(c->own.pin(&c->vec_loss_pin, (size_t)IQLHIP_VEC_MAX_UPDATES * 4 * sizeof(float)));
+      HIPCHK(c->own.pin(&c->vec_act_pin, (size_t)IQLHIP_VEC_MAX_ENVS * (IQLHIP_MAX_INPUT + IQLHIP_MAX_ACTION) * sizeof(float)));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
+  }
+  if (c->vec_xb_cap < stage_floats) {
+    HIPCHK(hipDeviceSynchronize());          // (an earlier call's steps may still read the old block)
+    c->vec_own.release_all();
+    c->vec_xb_cap = 0;
+    HIPCHK(c->vec_own.dev(&c->vec_xb, stage_floats * sizeof(float)));
+    c->vec_xb_cap = stage_floats;
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_online_step_vec(iqlhip_ctx* c, float* rows_dev, int64_t ld, int64_t capacity, int64_t pointer,
+                                      const float* rows_host, int32_t n_rows, const int64_t* idx_host, int32_t batch_rows,
+                                      int32_t n_updates, const iqlhip_step_scalars* sc, float* out,
+                                      const float* act_states_host, int32_t act_rows, float max_action, uint64_t act_seed,
+                                      float* act_out_host, void* stream) {
+  if (!c || !rows_dev || !rows_host) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (n_updates > 0 && (!idx_host || !sc || !out)) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (act_states_host && !act_out_host) return fail(IQLHIP_EINVAL, "act_states_host without act_out_host");
+  if (!c->params) return fail(IQLHIP_ENOTBOUND, "iqlhip_bind has not been called");
+  if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
+  if (int rc = vec_ring_ok(rows_dev, ld, capacity, pointer, n_rows)) return rc;
+  const int U = n_updates, B = batch_rows;
+  if (U < 0 || U > IQLHIP_VEC_MAX_UPDATES) return fail(IQLHIP_EINVAL, "n_updates = %d outside [0, %d]", U, IQLHIP_VEC_MAX_UPDATES);
+  if (act_states_host && (act_rows < 1 || act_rows > IQLHIP_VEC_MAX_ENVS))
+    return fail(IQLHIP_EINVAL, "act_rows = %d outside [1, %d]", act_rows, IQLHIP_VEC_MAX_ENVS);
+  if (c->xch_mode != IQLHIP_XCH_NONE)
+    return fail(IQLHIP_EUNSUPPORTED, "the vector online step is not supported with a data-parallel exchange");
+  if (c->drop_inject)
+    return fail(IQLHIP_EUNSUPPORTED, "keep-bits injected by iqlhip_debug_write_masks are pending: the vector online step draws "
+                "every step's own (call iqlhip_set_dropout first, or step with iqlhip_step)");
+  if (B >= 1 && use_lb(c, B))
+    return fail(IQLHIP_EUNSUPPORTED, "the vector online step is not supported on the large-batch bf16 path (more than %d rows)", LB_MIN_ROWS);
+  if (B < 1 || B > VEC_MAX_BATCH || B > c->dims.max_batch)
+    return fail(IQLHIP_EINVAL, "batch rows %d outside [1, min(%d, max_batch=%d)]", B, VEC_MAX_BATCH, c->dims.max_batch);
+  if (U > 0) {
+    if (int rc = check_host_indices(idx_host, (int64_t)U * B, capacity)) return rc;
+    if (int rc = step_entry(c, B, stream, /*multi_step=*/false)) return rc;
+  }
+  DevGuard guard(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const int S = c->dims.state_dim, A = c->dims.action_dim;
+  if (int rc = vec_buffers(c, (size_t)std::max(U, 1) * B * (size_t)ld)) return rc;
+  memcpy(c->vec_rows_pin, rows_host, (size_t)n_rows * ld * sizeof(float));
+  if (U > 0) memcpy(c->vec_idx_pin, idx_host, (size_t)U * B * sizeof(long long));
+  launch_vec_gather(rows_dev, ld, capacity, pointer, c->vec_rows_pin, n_rows, c->vec_idx_pin, c->vec_xb, U * B, st);
+  const unsigned long long done_val = ++c->done_seq;
+  for (int u = 0; u < U; ++u) {
+    EagerStep e;
+    eager_begin(c, B, sc + u, st, c->vec_xb + (size_t)u * B * ld, e);
+    if (e.with_stats) e.sa = make_stats(c, e.p, c->stats_ring, u, c->k_max, nullptr);      // (and stats_last, as every step)
+    e.u.losses_mirror = c->vec_loss_pin + 4 * u;
+    if (u == U - 1 && !act_states_host) { e.u.done_flag = c->done_pin; e.u.done_val = done_val; }
+    if (int rc = enqueue_step(c, e.p, e.u, IQLHIP_XCH_NONE, 0, 0, /*from_hdr=*/false, st, nullptr, e.stats())) return rc;
+  }
+  float* a_out = c->vec_act_pin + (size_t)IQLHIP_VEC_MAX_ENVS * IQLHIP_MAX_INPUT;
+  if (act_states_host) {
+    // the next iteration's actions by the policy the U steps left: states and actions travel through host-mapped pinned words
+    memcpy(c->vec_act_pin, act_states_host, (size_t)act_rows * S * sizeof(float));
+    const bool noisy = act_seed != 0 && c->dims.policy == IQLHIP_POLICY_GAUSSIAN;
+    const bool one_block = act_rows * A <= 256;      // (the finish launch stores the completion word only when it is one block)
+    const int rc = actor_forward_impl(c, c->vec_act_pin, S, act_rows, nullptr, 0, noisy ? act_seed : 0, noisy ? c->act_calls++ : 0,
+                                      max_action, a_out, A, stream, one_block ? c->done_pin : nullptr, done_val);
+    if (rc) return rc;
+    if (!one_block) hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, c->done_pin, done_val);
+  }
+  // (a synchronous call: the pinned staging is free again on return)
+  if (U > 0 || act_states_host) {
+    if (int rc = wait_word(c->done_pin, done_val, st)) return rc;
+  } else {
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int u = 0; u < U; ++u)
+    for (int k = 0; k < 3; ++k) out[3 * u + k] = c->vec_loss_pin[4 * u + k];
+  if (act_states_host) memcpy(act_out_host, a_out, (size_t)act_rows * A * sizeof(float));
+  HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
 }

@@ -33,6 +33,8 @@ IQLHIP_GROUP_DROPOUT = 1      # iqlhip_group_create_flags: members may train wit
 IQLHIP_GROUP_MAX_STEPS = 1024  # steps per iqlhip_group_train_steps call
 IQLHIP_GROUP_TS_CONTINUE = 1   # iqlhip_group_train_steps_weighted_is / _prioritized: go on with the previous call's staged rows
 IQLHIP_VAR_TRAIN_MAX_STEPS = 1024  # updates per iqlhip_var_train_steps call (the rings' length)
+IQLHIP_VEC_MAX_ENVS = 64       # transitions, and act states, per iqlhip_online_step_vec call (include/iqlhip.h)
+IQLHIP_VEC_MAX_UPDATES = 32    # gradient steps per iqlhip_online_step_vec call
 IQLHIP_UNIQUE_ID_BYTES = 128
 IQLHIP_IPC_HANDLE_BYTES = 64
 XCH_NONE, XCH_RCCL, XCH_P2P = 0, 1, 2
@@ -178,6 +180,10 @@ SYMBOLS = [
                                            C.c_void_p, C.c_int32, C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p,
                                            C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                            C.c_int32, C.c_double, C.c_void_p]),
+    ("iqlhip_rows_write_ring", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("iqlhip_online_step_vec", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_float, C.c_uint64, C.c_void_p, C.c_void_p]),
     ("iqlhip_draw_indices", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     ("iqlhip_weights_build", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("iqlhip_weights_free", C.c_int, [C.c_void_p]),

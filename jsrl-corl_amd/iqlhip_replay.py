@@ -557,14 +557,49 @@ class ReplayBuffer:
             self.insert_max_sample_weight(self._pointer)
         self._advance(*self._insert_slot())
 
-    # ---- what add_transition and the fused online calls (online_step*, which write the row in the library) share ----
-    def _insert_slot(self):
-        """(the ring position the next row goes to, the size after that insert)."""
-        return self._pointer, min(self._size + 1, self._buffer_size)
+    def add_transitions(self, states, actions, rewards, next_states, dones) -> None:
+        """E transitions at once — what a vector environment hands over per iteration: states / next_states [E, S],
+        actions [E, A], rewards / dones [E], numpy arrays or sequences.  Everything is afterwards exactly what E calls of
+        add_transition in row order leave (the rows bit for bit, pointer, size, the write count advanced by E, and with a
+        tracking sample-weight table every new row at the running maximum), but a GPU buffer gets them in ONE packed
+        upload and ONE launch that wraps at the capacity (iqlhip_rows_write_ring).  1 <= E <= min(capacity,
+        IQLHIP_VEC_MAX_ENVS): ValueError otherwise, and for shapes that disagree.  Not part of the reference's surface."""
+        S, A = self._state_dim, self._action_dim
+        E = check_transitions(S, A, self._buffer_size, states, actions, rewards, next_states, dones)
+        pointer, new_size = self._insert_slot(E)
+        if self._gpu:
+            # pinned staging blocks the kernel reads in place (ring of 4, each guarded by an event, as add_transition's rows)
+            ring = getattr(self, "_rows_ring", None)
+            if ring is None:
+                ring = [(torch.zeros((hb.IQLHIP_VEC_MAX_ENVS, self._ld), dtype=torch.float32).pin_memory(), torch.cuda.Event())
+                        for _ in range(4)]
+                self._rows_ring, self._rows_slot = ring, 0
+            host, done_ev = ring[self._rows_slot]
+            self._rows_slot = (self._rows_slot + 1) % len(ring)
+            done_ev.synchronize()
+            pack_transitions(host.numpy()[:E], S, A, states, actions, rewards, next_states, dones)
+            with torch.cuda.device(self._rows.device):
+                hb.check(hb.lib().iqlhip_rows_write_ring(self._rows.data_ptr(), self._ld, self._buffer_size, pointer,
+                                                         host.data_ptr(), E, self._stream()))
+                done_ev.record()
+        else:
+            block = np.zeros((E, self._ld), dtype=np.float32)
+            pack_transitions(block, S, A, states, actions, rewards, next_states, dones)
+            self._rows[(pointer + torch.arange(E)) % self._buffer_size] = torch.from_numpy(block)
+        self._writes += E
+        if self._weights_tracks:             # behind the ring write, on the same stream: add_transition's insert, row by row
+            for j in range(E):
+                self.insert_max_sample_weight((pointer + j) % self._buffer_size)
+        self._advance(pointer, new_size, E)
 
-    def _advance(self, pointer: int, new_size: int) -> None:
-        """Behind a row written at `pointer`: the ring's pointer and size move past it."""
-        self._pointer = (pointer + 1) % self._buffer_size
+    # ---- what add_transition(s) and the fused online calls (online_step*, which write the rows in the library) share ----
+    def _insert_slot(self, n: int = 1):
+        """(the ring position the next row goes to, the size after the next n inserts)."""
+        return self._pointer, min(self._size + n, self._buffer_size)
+
+    def _advance(self, pointer: int, new_size: int, n: int = 1) -> None:
+        """Behind n rows written from `pointer` on: the ring's pointer and size move past them."""
+        self._pointer = (pointer + n) % self._buffer_size
         self._size = new_size
 
 
@@ -578,6 +613,9 @@ class OfflineReplayBuffer(ReplayBuffer):
     def add_transition(self, *args, **kwargs):
         raise NotImplementedError
 
+    def add_transitions(self, *args, **kwargs):
+        raise NotImplementedError
+
 
 def pack_transition(row: np.ndarray, S: int, A: int, state, action, reward, next_state, done) -> None:
     """One transition into a packed float32 host row [ld]: s | a | s' | r | d (the pad columns stay as they are)."""
@@ -586,6 +624,31 @@ def pack_transition(row: np.ndarray, S: int, A: int, state, action, reward, next
     row[S + A: 2 * S + A] = np.asarray(next_state, dtype=np.float32).reshape(-1)
     row[2 * S + A] = np.float32(reward)
     row[2 * S + A + 1] = np.float32(done)
+
+
+def check_transitions(S: int, A: int, capacity: int, states, actions, rewards, next_states, dones) -> int:
+    """E of the E transitions add_transitions and online_step_vec take: states / next_states [E, S], actions [E, A],
+    rewards / dones [E] (or [E, 1]).  ValueError for shapes that disagree and for E outside [1, min(capacity,
+    IQLHIP_VEC_MAX_ENVS)]."""
+    s, a, ns = (np.asarray(x) for x in (states, actions, next_states))
+    r, d = np.asarray(rewards), np.asarray(dones)
+    E = s.shape[0] if s.ndim == 2 else -1
+    if s.ndim != 2 or s.shape != (E, S) or ns.shape != (E, S) or a.shape != (E, A) or r.size != E or d.size != E \
+            or r.ndim not in (1, 2) or d.ndim not in (1, 2):
+        raise ValueError(f"iqlhip: E transitions are states / next_states [E, {S}], actions [E, {A}], rewards / dones [E]; got "
+                         f"{list(s.shape)}, {list(ns.shape)}, {list(a.shape)}, {list(r.shape)}, {list(d.shape)}")
+    if not 1 <= E <= min(capacity, hb.IQLHIP_VEC_MAX_ENVS):
+        raise ValueError(f"iqlhip: {E} transitions per call outside [1, min(capacity={capacity}, {hb.IQLHIP_VEC_MAX_ENVS})]")
+    return E
+
+
+def pack_transitions(block: np.ndarray, S: int, A: int, states, actions, rewards, next_states, dones) -> None:
+    """pack_transition for every row of block [E, ld] (the same float32 conversions; the pad columns stay as they are)."""
+    block[:, :S] = np.asarray(states, dtype=np.float32)
+    block[:, S: S + A] = np.asarray(actions, dtype=np.float32)
+    block[:, S + A: 2 * S + A] = np.asarray(next_states, dtype=np.float32)
+    block[:, 2 * S + A] = np.asarray(rewards, dtype=np.float32).reshape(-1)
+    block[:, 2 * S + A + 1] = np.asarray(dones, dtype=np.float32).reshape(-1)
 
 
 def check_online_ring(buf, device, what: str, holder: str = "a ReplayBuffer", member=None) -> None:

@@ -29,7 +29,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 
 import iqlhip_binding as hb
 import iqlhip_dp as dp
-from iqlhip_replay import check_online_ring, draw_indices, pack_transition
+from iqlhip_replay import check_online_ring, check_transitions, draw_indices, pack_transition, pack_transitions
 from iqlhip_networks import (DeterministicPolicy, GaussianPolicy, LOG_STD_MAX, LOG_STD_MIN, dropout_p, register_actor_owner,
                              linear_layers)
 
@@ -37,6 +37,7 @@ TensorBatch = List[torch.Tensor]
 EXP_ADV_MAX = 100.0
 K_MAX = 1024  # steps per captured hipGraph chunk (library limit)
 STATS_BF16_MAX_ROWS = 512  # bf16 batches beyond this take the large-batch kernels, which keep no step statistics
+VEC_MAX_BATCH = 512        # rows per step of online_step_vec: the small-batch kernels, fp32 or bf16
 
 
 def _is_gpu(device) -> bool:
@@ -742,8 +743,9 @@ class ImplicitQLearning:
         pack_transition(row, self._S, self._A, state, action, reward, next_state, done)
         return row
 
-    def _act_next_args(self, act_next):
-        """(state in, action out, noise seed) of the call's act forward; (None, None, 0) without act_next."""
+    def _act_next_args(self, act_next, rows: Optional[int] = None):
+        """(state in, action out, noise seed) of the call's act forward; (None, None, 0) without act_next.  rows: the
+        states of a vector call, [rows, S] in and [rows, A] out."""
         if act_next is None:
             return None, None, 0
         if self.acts_with_dropout() and not self._act_dropout:
@@ -751,8 +753,20 @@ class ImplicitQLearning:
                                       "unless set_act_dropout(True) was called")
         self._prepare_act()
         a_in = np.ascontiguousarray(np.asarray(act_next, dtype=np.float32).reshape(-1))
-        a_out = np.empty(self._A, dtype=np.float32)
+        a_out = np.empty(self._A if rows is None else (rows, self._A), dtype=np.float32)
         return a_in, a_out, (self._act_seed() if (self.actor.training and self._gaussian) else 0)
+
+    def _commit_online(self, ring, pointer: int, new_size: int, rows: int, steps: int, adam_after, commit_extra=None) -> None:
+        """What a successful online call moves — the one place for both drivers: the ring's counters past the `rows`
+        written from `pointer` on, total_it, the Adam step counts and the schedule by `steps`, then commit_extra()."""
+        ring._writes += rows
+        ring._advance(pointer, new_size, rows)
+        self.total_it += steps
+        self._adam_t = adam_after
+        if steps:
+            self._advance_schedule(steps)
+        if commit_extra is not None:
+            commit_extra()
 
     def _run_online(self, ring, transition, act_next, draw, inv_batch: float, call, commit_extra=None):
         """Insert one transition into `ring`, draw a batch, take one step and (with act_next) act, in the one library
@@ -778,17 +792,109 @@ class ImplicitQLearning:
                     None if a_out is None else a_out.ctypes.data)
         hb.check(call((ring._rows.data_ptr(), ring._ld, ring._buffer_size, pointer), row.ctypes.data,
                       None if idx is None else idx.ctypes.data, C.byref(sc), out, act_args, self._stream()))
-        ring._writes += 1
-        ring._advance(pointer, new_size)
-        self.total_it += 1
-        self._adam_t = adam_next
-        self._advance_schedule(1)
-        if commit_extra is not None:
-            commit_extra()
+        self._commit_online(ring, pointer, new_size, 1, 1, adam_next, commit_extra)
         log = {"value_loss": float(out[0]), "q_loss": float(out[1]), "actor_loss": float(out[2])}
         if self._step_stats:
             log.update(self._stats_entries())
         return log if a_out is None else (log, a_out)
+
+    def _run_online_vec(self, ring, transitions, batch_size: int, updates: int, act_next, act_rows: int, call):
+        """_run_online's sibling for E transitions and U = `updates` steps in the one library call `call` makes, once the
+        caller's checks have passed.  transitions: (states, actions, rewards, next_states, dones) of E rows.
+        call(ring_args, rows, n_rows, idx, scs, out, act_args, stream) returns the library's status: ring_args = (rows,
+        ld, capacity, pointer), rows the E packed host rows, idx the U * batch_size host indices (None with U = 0), scs the
+        U sets of step scalars, out [U][3]; act_args = (states in, rows, max_action, seed, actions out).  The global
+        numpy stream is consumed by the U index draws alone — U consecutive sample() draws over the size after all E
+        inserts — behind the packed rows and in front of the act seed.  The scalars are what U single steps would use:
+        the Adam counts t + 1 .. t + U and the actor rates the schedule gives them, looked up ahead.  Only when the
+        status is OK does anything move (_commit_online).  Returns the U dicts, or (dicts, actions) with act_next."""
+        S, A = self._S, self._A
+        E = len(transitions[0])
+        rows = np.zeros((E, ring._ld), dtype=np.float32)
+        pack_transitions(rows, S, A, *transitions)
+        pointer, new_size = ring._insert_slot(E)
+        U, B = updates, batch_size
+        idx = np.concatenate([draw_indices(new_size, B) for _ in range(U)]) if U else None
+        lrs = self._current_lrs()
+        pk = self._peek_schedule(U) if U else None
+        if U > 1 and pk is None:
+            raise NotImplementedError("iqlhip: online_step_vec with updates > 1 needs an actor schedule whose rates can "
+                                      "be looked up ahead (CosineAnnealingLR with eta_min = 0, stepped by this trainer)")
+        lr_pi = [lrs["pi"]] if pk is None else pk[0]      # (one step: the rate in force, whatever the schedule's state)
+        scs = (hb.StepScalars * max(U, 1))()
+        for u in range(U):
+            self._fill_scalars(scs[u], {g: t + u + 1 for g, t in self._adam_t.items()}, dict(lrs, pi=float(lr_pi[u])), 1.0 / B)
+        out = (C.c_float * (3 * max(U, 1)))()
+        a_in, a_out, seed = self._act_next_args(act_next, act_rows)
+        act_args = (None if a_in is None else a_in.ctypes.data, act_rows, float(self.actor.max_action), seed,
+                    None if a_out is None else a_out.ctypes.data)
+        stream = self._stream()
+        hb.check(call((ring._rows.data_ptr(), ring._ld, ring._buffer_size, pointer), rows.ctypes.data, E,
+                      None if idx is None else idx.ctypes.data, scs, out, act_args, stream))
+        self._commit_online(ring, pointer, new_size, E, U, {g: t + U for g, t in self._adam_t.items()})
+        logs = [{"value_loss": float(out[3 * u]), "q_loss": float(out[3 * u + 1]), "actor_loss": float(out[3 * u + 2])}
+                for u in range(U)]
+        if self._step_stats and U:
+            stats = np.empty((U, hb.IQLHIP_N_STATS), dtype=np.float32)
+            self._read_rings(U, stream, None, stats)
+            for u, log in enumerate(logs):
+                log.update({"stats/" + name: float(stats[u, i]) for i, name in enumerate(hb.STAT_NAMES)})
+        return logs if a_out is None else (logs, a_out)
+
+    def online_step_vec(self, replay_buffer, states, actions, rewards, next_states, dones, batch_size: int,
+                        updates: int = 1, act_next=None):
+        """One iteration of an online loop over E environments with an update-to-data ratio of `updates`, in ONE library
+        call and under one synchronisation (iqlhip_online_step_vec).  Bit for bit the sequence
+            for e in range(E): replay_buffer.add_transition(states[e], actions[e], rewards[e], next_states[e], dones[e])
+            logs = [trainer.train(replay_buffer.sample(batch_size)) for _ in range(updates)]
+            acts = trainer.actor_forward(act_next, sample=trainer.actor.training)     # with act_next [E2, S]
+        states / next_states [E, S], actions [E, A], rewards / dones [E]; 1 <= E <= min(capacity, 64), 0 <= updates <= 32,
+        batch_size <= 512, 1 <= E2 <= 64 (E2 need not equal E: the caller resets the envs that ended).  updates = 0 is
+        the loop's warm-up — rows in, actions out, no gradient step: returns [] and moves no step counter.  The indices are
+        `updates` consecutive sample() draws from the global numpy stream over the size after all E inserts.  Returns the
+        list of `updates` dicts like train()'s (each with its own step's statistics under set_step_stats), or (list,
+        actions [E2, A] float32) with act_next; the act() noise counter and the act-dropout counter advance once.
+        last_grad_clip() reports the last step.  ValueError for sizes out of range and shapes that disagree;
+        NotImplementedError under data parallelism, with injected dropout masks pending, at bf16 precision above 512
+        rows, for a ring with a tracking sample-weight table and for act_next of a training-mode dropout actor without
+        set_act_dropout(True) — all before anything is launched, drawn or moved."""
+        self._require_gpu()
+        buf = replay_buffer
+        check_online_ring(buf, self._dev, "online_step_vec")
+        U, B = int(updates), int(batch_size)
+        if self._dp_world > 1 or self._dp_exchange is not None:
+            raise NotImplementedError("iqlhip: online_step_vec is not supported under data parallelism")
+        if buf._weights_tracks:
+            raise NotImplementedError("iqlhip: online_step_vec has no insert for a tracking sample-weight table; use "
+                                      "add_transitions and online_step_prioritized's sequence")
+        if getattr(self, "_precision", "f32") == "bf16" and B > STATS_BF16_MAX_ROWS:
+            raise NotImplementedError(f"iqlhip: online_step_vec runs the small-batch kernels: bf16 batches of more than "
+                                      f"{STATS_BF16_MAX_ROWS} rows are not supported (got {B})")
+        if not 0 <= U <= hb.IQLHIP_VEC_MAX_UPDATES:
+            raise ValueError(f"iqlhip: updates = {U} outside [0, {hb.IQLHIP_VEC_MAX_UPDATES}]")
+        if not 1 <= B <= VEC_MAX_BATCH:
+            raise ValueError(f"iqlhip: batch_size = {B} outside [1, {VEC_MAX_BATCH}]")
+        check_transitions(self._S, self._A, buf._buffer_size, states, actions, rewards, next_states, dones)
+        act_rows = 0
+        if act_next is not None:
+            act_next = np.asarray(act_next, dtype=np.float32)
+            if act_next.ndim != 2 or act_next.shape[1] != self._S or not 1 <= act_next.shape[0] <= hb.IQLHIP_VEC_MAX_ENVS:
+                raise ValueError(f"iqlhip: act_next must be [E2, {self._S}] with 1 <= E2 <= {hb.IQLHIP_VEC_MAX_ENVS}, got "
+                                 f"{list(act_next.shape)}")
+            act_rows = act_next.shape[0]
+            if self.acts_with_dropout() and not self._act_dropout:      # (_act_next_args' refusal, in front of the index draw)
+                raise NotImplementedError("act_next: the library's inference forward is eval-mode (no actor dropout) "
+                                          "unless set_act_dropout(True) was called")
+        self._prepare(B)
+        if getattr(self, "_masks_injected", False):
+            raise NotImplementedError("iqlhip: online_step_vec draws every step's keep-bits and cannot use the masks written "
+                                      "by inject_dropout_masks; step with train(), or clear them (set_dropout_seed)")
+
+        def call(ring_args, rows, n_rows, idx, scs, out, act_args, stream):
+            a_in, a_rows, max_action, seed, a_out = act_args
+            return hb.lib().iqlhip_online_step_vec(self._ctx, *ring_args, rows, n_rows, idx, B, U, C.addressof(scs), C.addressof(out),
+                                                   a_in, a_rows, max_action, seed, a_out, stream)
+        return self._run_online_vec(buf, (states, actions, rewards, next_states, dones), B, U, act_next, act_rows, call)
 
     def online_step(self, replay_buffer, state, action, reward: float, next_state, done: bool,
                     batch_size: int, act_next: Optional[np.ndarray] = None):
