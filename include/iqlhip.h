@@ -895,6 +895,43 @@ int iqlhip_group_online_step_mixed(iqlhip_group* group, float* const* rows_dev, 
                                    const int32_t* n, const iqlhip_step_scalars* sc, float* out,
                                    const float* act_state_host, const int32_t* act_mask, const float* max_action,
                                    const uint64_t* act_seed, float* act_out_host, void* stream);
+/* ---- group vector-environment online step ----------------------------------------------------------------------
+ * iqlhip_online_step_vec ("vector-environment online step" above) for each member k, in one set of launches, one upload
+ * and one synchronisation: member k's n_rows[k] new rows go to ring rows (pointer[k] + j) mod capacity[k]
+ * of rows_dev[k], n_updates steps run on batches of batch_rows[k] rows, and its policy, as the steps left it, acts on
+ * act_rows[k] states.  n_updates is common to the call: the members' steps run in lockstep.
+ *   rows_host        the members' new rows one member after another, n_rows[k] rows of ld floats each
+ *   idx_host         the members' n_updates * batch_rows[k] indices one member after another, step by step (each step's
+ *                    batch_rows[k] indices a sample() draw over the member's size after all its inserts)
+ *   sc[k][u]         step u's scalars of member k (sc[k * n_updates + u]);  out[k][u][3]: its losses
+ *   act_states_host  NULL: no member acts; else the members' act states one member after another, act_rows[k] rows of
+ *                    state_dim floats each (act_rows[k] = 0: none for member k), with max_action[k] and the device noise
+ *                    of act_seed[k] (0: the mean action) as in iqlhip_online_step_vec, into act_out_host, packed alike
+ *                    with action_dim floats a row
+ * Launches, whatever the group's size: one (iql_online_vec_gather_group_kernel, grid.y = member: the ring writes, the
+ * gathers into a staging block [k][n_updates][batch_rows[k]][ld] the group owns — sized on first use, grown when a call
+ * needs more — and the act states' packing; a drawn index i with (i - pointer[k]) mod capacity[k] < n_rows[k] is read
+ * from the host words, never from the ring), then n_updates times the launches of iqlhip_group_step_mixed — step u on
+ * slice u of every member's staging, its statistics in slot u of what iqlhip_group_read_step_stats reads, the clip record
+ * the last step's — then iqlhip_group_actor_forward's policy forward and rows finish over the requesting members and a
+ * one-block launch that stores the completion word the host spins on; n_updates = 0 with no act ends on a stream
+ * synchronisation.  Every requesting member's noise and inference keep-bit counters advance once, every drawing
+ * member's keep-bit position by n_updates.  Host arrays are ordinary memory (copied into pinned staging inside the
+ * call); idx_host, sc and out may be NULL when n_updates = 0.  Member k ends bit for bit where its iqlhip_online_step_vec
+ * call leaves it.  Synchronous.
+ * Refused before anything is launched or any counter moves, naming the member — IQLHIP_EINVAL: a NULL argument, a NULL or
+ * misaligned ring, ld other than the row stride, a pointer outside its ring, rings that overlap, n_rows[k] outside
+ * [1, min(capacity[k], IQLHIP_VEC_MAX_ENVS)], n_updates outside [0, IQLHIP_VEC_MAX_UPDATES], act_rows[k] outside
+ * [0, IQLHIP_VEC_MAX_ENVS], batch_rows[k] outside [1, min(512, max_batch)]; IQLHIP_EINDEX: an index outside
+ * [0, capacity[k]); IQLHIP_EUNSUPPORTED: the group rules (an exchange, bf16 batches of more than 512 rows, dropout
+ * without IQLHIP_GROUP_DROPOUT), injected keep-bits pending, and — n_updates > 0 only, as in the solo call — what
+ * statistics and clipping refuse. */
+int iqlhip_group_online_step_vec(iqlhip_group* group, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                 const int64_t* pointer, const float* rows_host, const int32_t* n_rows,
+                                 const int64_t* idx_host, const int32_t* batch_rows, int32_t n_updates,
+                                 const iqlhip_step_scalars* sc, float* out, const float* act_states_host,
+                                 const int32_t* act_rows, const float* max_action, const uint64_t* act_seed,
+                                 float* act_out_host, void* stream);
 /* Group calls on batches mixed from two replay buffers ("mixed offline / online batches" above, for every member in one
  * set of launches; "replay2" because _mixed already names the per-member batch sizes above).  One pair serves equal
  * and unequal batch sizes: every count is per member.

@@ -3011,7 +3011,8 @@ struct GroupStage {
 };
 
 struct ScoreParams; struct ScoreRowsParams; struct ScoreGroupAux;      // (iqlhip_score_kernels.h, included further down)
-struct GroupRwRec; struct GroupPrioRec;                                // (iqlhip_group_prio_kernels.h, the file's last include)
+struct GroupRwRec; struct GroupPrioRec;                                // (iqlhip_group_prio_kernels.h, included further down)
+struct GroupVecRec;                                                    // (iqlhip_group_online_vec_kernels.h, the file's last include)
 struct iqlhip_group {
   int k = 0;
   int device = 0;
@@ -3071,6 +3072,29 @@ struct iqlhip_group {
   GroupStage rw;
   Section<GroupRwRec> rw_rws; Section<GroupPrioRec> rw_prs;
   float* rw_ones = nullptr;
+  // iqlhip_group_online_step_vec (DESIGN.md 6b "group vector-environment online step"), all of it made by the group's
+  // first such call.  A staging of its own (a synchronous call: no upload event): the gather records, the inference
+  // keep-bit records (both indexed by member), the act forwards' and finishes' records (packed: requesting members), then
+  // one block per step — the agents' records, the packed dropout records, the statistics / clip records and one row of
+  // scalars per agent — so that a call uploads the prefix its n_updates steps use (vec_end[u]: the bytes up to and
+  // including step u's block; vec_head: those in front of step 0's).
+  Staging vec;
+  Section<GroupVecRec> vec_gathers; Section<ActDropRec> vec_adrops; Section<StepParams> vec_aps; Section<GroupActRowsRec> vec_fins;
+  struct VecStep { Section<GroupRec> recs; Section<GroupDropRec> drops; AuxSections aux; Section<iqlhip_step_scalars> tabs; };
+  VecStep vec_steps[IQLHIP_VEC_MAX_UPDATES];
+  size_t vec_head = 0, vec_end[IQLHIP_VEC_MAX_UPDATES] = {};
+  // pinned, host-mapped staging per member: the new rows [k][IQLHIP_VEC_MAX_ENVS][ld], the drawn indices
+  // [k][IQLHIP_VEC_MAX_UPDATES * 512], the steps' losses [k][IQLHIP_VEC_MAX_UPDATES][4] and the act: states in
+  // [k][IQLHIP_VEC_MAX_ENVS][IQLHIP_MAX_INPUT], then actions out [k][IQLHIP_VEC_MAX_ENVS][IQLHIP_MAX_ACTION]
+  float* vec_rows_pin = nullptr;
+  long long* vec_idx_pin = nullptr;
+  float* vec_loss_pin = nullptr;
+  float* vec_act_pin = nullptr;
+  // ... and the gathered batches of every member's steps, device [k][updates][batch_rows[k]][ld]: an owner of its own,
+  // because the block is freed and allocated anew when a call needs more (vec_xb_cap floats)
+  Owned vec_own;
+  float* vec_xb = nullptr;
+  size_t vec_xb_cap = 0;
 };
 
 static int group_check_members(iqlhip_ctx* const* members, int k, int flags) {
@@ -3111,6 +3135,7 @@ extern "C" int iqlhip_group_destroy(iqlhip_group* g) {
   if (!g) return fail(IQLHIP_EINVAL, "NULL group");
   DevGuard guard(g->device);
   (void)hipDeviceSynchronize();       // a group call may still be running on some stream
+  g->vec_own.release_all();
   g->own.release_all();
   delete g;
   return IQLHIP_OK;
@@ -6515,5 +6540,234 @@ extern "C" int iqlhip_online_step_vec(iqlhip_ctx* c, float* rows_dev, int64_t ld
     for (int k = 0; k < 3; ++k) out[3 * u + k] = c->vec_loss_pin[4 * u + k];
   if (act_states_host) memcpy(act_out_host, a_out, (size_t)act_rows * A * sizeof(float));
   HIPCHK(hipGetLastError());
+  return IQLHIP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The vector-environment online step of a trainer group (include/iqlhip.h "group vector-environment online step";
+// DESIGN.md 6b; kernels: iqlhip_group_online_vec_kernels.h, the code object's last): iqlhip_online_step_vec for every
+// member in one set of launches — one launch for all members' ring writes, gathers and act-state packing, n_updates
+// times the group step launches on the slices of a group-owned staging block, the group inference launches over the
+// requesting members' act_rows rows, and one completion word.
+#include "iqlhip_group_online_vec_kernels.h"
+
+// The call's buffers.  Once: the staging's layout and blocks and the pinned blocks; whenever a call needs more than
+// there is: the device staging of the gathered batches.
+static int group_vec_buffers(iqlhip_group* g, size_t stage_floats) {
+  const size_t K = (size_t)g->k;
+  if (g->vec.bytes == 0) {
+    const size_t n_drop = (g->flags & IQLHIP_GROUP_DROPOUT) ? K : 0;
+    Staging& s = g->vec;
+    g->vec_gathers = s.add<GroupVecRec>(K);
+    g->vec_adrops = s.add<ActDropRec>(n_drop);
+    g->vec_aps = s.add<StepParams>(K);
+    g->vec_fins = s.add<GroupActRowsRec>(K);
+    g->vec_head = s.bytes;
+    for (int u = 0; u < IQLHIP_VEC_MAX_UPDATES; ++u) {
+      iqlhip_group::VecStep& v = g->vec_steps[u];
+      v.recs = s.add<GroupRec>(K);
+      v.drops = s.add<GroupDropRec>(n_drop);
+      v.aux.add(s, K);
+      v.tabs = s.add<iqlhip_step_scalars>(K);
+      g->vec_end[u] = s.bytes;
+    }
+  }
+  if (!g->vec_rows_pin) {
+    const size_t ld = (size_t)g->m[0]->row_ld;
+    const int rc = all_or_nothing(g->own, [&]() -> int {
+      HIPCHK(g->vec.alloc(g->own, /*with_event=*/false));
+      HIPCHK(g->own.pin(&g->vec_idx_pin, K * IQLHIP_VEC_MAX_UPDATES * VEC_MAX_BATCH * sizeof(long long)));
+      HIPCHK(g->own.pin(&g->vec_loss_pin, K * IQLHIP_VEC_MAX_UPDATES * 4 * sizeof(float)));
+      HIPCHK(g->own.pin(&g->vec_act_pin, K * IQLHIP_VEC_MAX_ENVS * (IQLHIP_MAX_INPUT + IQLHIP_MAX_ACTION) * sizeof(float)));
+      HIPCHK(g->own.pin(&g->vec_rows_pin, K * IQLHIP_VEC_MAX_ENVS * ld * sizeof(float)));
+      return IQLHIP_OK;
+    });
+    if (rc) return rc;
+  }
+  if (g->vec_xb_cap < stage_floats) {
+    HIPCHK(hipDeviceSynchronize());          // (an earlier call's steps may still read the old block)
+    g->vec_own.release_all();
+    g->vec_xb_cap = 0;
+    HIPCHK(g->vec_own.dev(&g->vec_xb, stage_floats * sizeof(float)));
+    g->vec_xb_cap = stage_floats;
+  }
+  return IQLHIP_OK;
+}
+
+extern "C" int iqlhip_group_online_step_vec(iqlhip_group* g, float* const* rows_dev, int64_t ld, const int64_t* capacity,
+                                            const int64_t* pointer, const float* rows_host, const int32_t* n_rows,
+                                            const int64_t* idx_host, const int32_t* batch_rows, int32_t n_updates,
+                                            const iqlhip_step_scalars* sc, float* out, const float* act_states_host,
+                                            const int32_t* act_rows, const float* max_action, const uint64_t* act_seed,
+                                            float* act_out_host, void* stream) {
+  if (!g || !rows_dev || !capacity || !pointer || !rows_host || !n_rows || !batch_rows) return fail(IQLHIP_EINVAL, "NULL argument");
+  const int U = n_updates;
+  if (U < 0 || U > IQLHIP_VEC_MAX_UPDATES) return fail(IQLHIP_EINVAL, "n_updates = %d outside [0, %d]", U, IQLHIP_VEC_MAX_UPDATES);
+  if (U > 0 && (!idx_host || !sc || !out)) return fail(IQLHIP_EINVAL, "NULL argument");
+  if (act_states_host && (!act_rows || !max_action || !act_seed || !act_out_host))
+    return fail(IQLHIP_EINVAL, "act_states_host without act_rows, max_action, act_seed or act_out_host");
+  // (the warm-up takes no step: as the solo call with n_updates = 0, it asks what the steps' optional features need of
+  //  no member — the members, their arenas and the batch size are checked all the same)
+  int rc = U > 0 ? group_check_call(g, batch_rows) : group_check_members(g->m, g->k, g->flags);
+  if (rc) return rc;
+  const int K = g->k;
+  for (int i = 0; i < K && U == 0; ++i) {
+    if ((rc = group_check_bound(g, i))) return rc;
+    if (batch_rows[i] < 1 || batch_rows[i] > g->m[i]->dims.max_batch)
+      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, max_batch=%d]", i, batch_rows[i], g->m[i]->dims.max_batch);
+  }
+  size_t idx0[IQLHIP_MAX_GROUP], row0[IQLHIP_MAX_GROUP], act0[IQLHIP_MAX_GROUP];      // where member i's indices, new rows and act rows start
+  auto n_act = [&](int i) { return act_states_host ? (int)act_rows[i] : 0; };
+  for (int i = 0; i < K; ++i) {
+    const iqlhip_ctx* c = g->m[i];
+    if (batch_rows[i] > VEC_MAX_BATCH)
+      return fail(IQLHIP_EINVAL, "member %d: batch rows %d outside [1, %d]", i, batch_rows[i], VEC_MAX_BATCH);
+    if (ld != c->row_ld) return fail(IQLHIP_EINVAL, "row stride must be iqlhip_row_stride(S,A)=%lld", (long long)c->row_ld);
+    if (!rows_dev[i]) return fail(IQLHIP_EINVAL, "member %d: NULL ring", i);
+    if (((uintptr_t)rows_dev[i]) & 15) return fail(IQLHIP_EINVAL, "member %d: packed rows must be 16-byte aligned", i);
+    if (capacity[i] < 1 || pointer[i] < 0 || pointer[i] >= capacity[i])
+      return fail(IQLHIP_EINVAL, "member %d: ring pointer outside the buffer", i);
+    if (n_rows[i] < 1 || n_rows[i] > IQLHIP_VEC_MAX_ENVS || n_rows[i] > capacity[i])
+      return fail(IQLHIP_EINVAL, "member %d: %d new rows outside [1, min(capacity=%lld, %d)]", i, n_rows[i],
+                  (long long)capacity[i], IQLHIP_VEC_MAX_ENVS);
+    if (n_act(i) < 0 || n_act(i) > IQLHIP_VEC_MAX_ENVS)
+      return fail(IQLHIP_EINVAL, "member %d: act_rows = %d outside [0, %d]", i, n_act(i), IQLHIP_VEC_MAX_ENVS);
+    if (c->drop_inject)
+      return fail(IQLHIP_EUNSUPPORTED, "member %d: keep-bits injected by iqlhip_debug_write_masks are pending: the vector online "
+                  "step draws every step's own (call iqlhip_set_dropout first)", i);
+    for (int j = 0; j < i; ++j) {      // (two members writing one ring would race on its rows)
+      const uintptr_t a0 = (uintptr_t)rows_dev[i], a1 = a0 + (uintptr_t)(capacity[i] * ld) * sizeof(float);
+      const uintptr_t b0 = (uintptr_t)rows_dev[j], b1 = b0 + (uintptr_t)(capacity[j] * ld) * sizeof(float);
+      if (a0 < b1 && b0 < a1) return fail(IQLHIP_EINVAL, "members %d and %d share ring rows (one buffer per member)", j, i);
+    }
+    idx0[i] = i ? idx0[i - 1] + (size_t)U * batch_rows[i - 1] : 0;
+    row0[i] = i ? row0[i - 1] + (size_t)n_rows[i - 1] : 0;
+    act0[i] = i ? act0[i - 1] + (size_t)n_act(i - 1) : 0;
+  }
+  for (int i = 0; i < K && U > 0; ++i)
+    if ((rc = check_host_indices(idx_host + idx0[i], (int64_t)U * batch_rows[i], capacity[i]))) return rc;
+  for (int i = 0; i < K; ++i) note_stream(g->m[i], stream);
+  DevGuard guard(g->device);
+  hipStream_t st = (hipStream_t)stream;
+  const iqlhip_ctx* c0 = g->m[0];
+  const int S = c0->dims.state_dim, A = c0->dims.action_dim;
+  const bool gauss = c0->dims.policy == IQLHIP_POLICY_GAUSSIAN;
+  size_t xb0[IQLHIP_MAX_GROUP], stage_floats = 0;      // where member i's slices start in the staging block
+  for (int i = 0; i < K; ++i) {
+    xb0[i] = stage_floats;
+    stage_floats += (size_t)std::max(U, 1) * batch_rows[i] * (size_t)ld;
+  }
+  if ((rc = group_vec_buffers(g, stage_floats))) return rc;
+  const GroupGeom q = group_geom(g, batch_rows);
+  const Staging& vs = g->vec;
+  GroupVecRec* gathers = vs.host(g->vec_gathers);
+  StepParams* aps = vs.host(g->vec_aps);
+  GroupActRowsRec* fins = vs.host(g->vec_fins);
+  const bool with_drops = (g->flags & IQLHIP_GROUP_DROPOUT) != 0;
+  ActDropRec* adrops = with_drops ? vs.host(g->vec_adrops) : nullptr;
+  const size_t act_pin_k = (size_t)IQLHIP_VEC_MAX_ENVS * (IQLHIP_MAX_INPUT + IQLHIP_MAX_ACTION);
+  auto act_out_pin = [&](int i) { return g->vec_act_pin + (size_t)i * act_pin_k + (size_t)IQLHIP_VEC_MAX_ENVS * IQLHIP_MAX_INPUT; };
+  bool act_draws = false;
+  int n_req = 0, max_act = 0, max_work = 0;
+  for (int i = 0; i < K; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    const int B = batch_rows[i], E = n_rows[i], E2 = n_act(i);
+    float* rows_pin = g->vec_rows_pin + (size_t)i * IQLHIP_VEC_MAX_ENVS * ld;
+    long long* idx_pin = g->vec_idx_pin + (size_t)i * IQLHIP_VEC_MAX_UPDATES * VEC_MAX_BATCH;
+    float* act_pin = g->vec_act_pin + (size_t)i * act_pin_k;
+    memcpy(rows_pin, rows_host + row0[i] * ld, (size_t)E * ld * sizeof(float));
+    if (U > 0) memcpy(idx_pin, idx_host + idx0[i], (size_t)U * B * sizeof(long long));
+    GroupVecRec& o = gathers[i];
+    memset(&o, 0, sizeof o);
+    o.rows = rows_dev[i]; o.rows_pin = rows_pin; o.idx_pin = idx_pin; o.xb = g->vec_xb + xb0[i];
+    o.act_pin = E2 ? act_pin : nullptr; o.xb_act = c->xb_act;
+    o.ld = ld; o.capacity = capacity[i]; o.pointer = pointer[i];
+    o.n_new = E; o.n = U * B; o.act_rows = E2; o.S = S;
+    max_work = std::max(max_work, std::max(std::max(E, U * B), E2));
+    if (with_drops) adrops[i] = act_drop_record(c, E2);
+    if (!E2) continue;
+    memcpy(act_pin, act_states_host + act0[i] * S, (size_t)E2 * S * sizeof(float));
+    aps[n_req] = act_step_params(c, E2);
+    if (with_drops && adrops[i].active) act_draws = true;
+    GroupActRowsRec& f = fins[n_req];
+    const bool noise = act_seed[i] != 0 && gauss;      // (the call counter moves only when noise is drawn, as solo)
+    f.heads = c->heads_act; f.log_std = aps[n_req].log_std; f.out = act_out_pin(i); f.ld_out = (long long)A; f.n = E2; f.A = A;
+    f.max_action = max_action[i]; f.ls_min = c->hyper.log_std_min; f.ls_max = c->hyper.log_std_max;
+    f.seed = noise ? act_seed[i] : 0ull;
+    f.call = noise ? c->act_calls : 0ull;              // (the counters move behind the upload, below)
+    max_act = std::max(max_act, E2);
+    ++n_req;
+  }
+  // the steps' records: step u is a one-step group call on slice u of every member's staging, its scalars in the
+  // block's own row, its losses and statistics in slot u of the members' rings and mirrors
+  GroupAux aux[IQLHIP_VEC_MAX_UPDATES];
+  int n_draw = 0;
+  for (int u = 0; u < U; ++u) {
+    const iqlhip_group::VecStep& v = g->vec_steps[u];
+    GroupRec* recs = vs.host(v.recs);
+    iqlhip_step_scalars* tab = vs.host(v.tabs);
+    for (int i = 0; i < K; ++i) {
+      const int B = batch_rows[i];
+      tab[i] = sc[(size_t)i * U + u];
+      group_record(g, recs[i], i, q, B, 1, g->vec_xb + xb0[i] + (size_t)u * B * ld, &tab[i], vs.device(v.tabs) + i);
+      recs[i].u.ring_slot = u;
+      recs[i].u.losses_mirror = g->vec_loss_pin + ((size_t)i * IQLHIP_VEC_MAX_UPDATES + u) * 4;
+    }
+    if ((rc = group_aux(g, vs, v.aux, recs, &aux[u]))) return rc;
+    if (aux[u].srecs)
+      for (int i = 0; i < K; ++i) vs.host(v.aux.srecs)[i].a.ring_slot = u;
+    if (with_drops) {      // (the drawing members' records at the front, step u's draw at the member's position + u)
+      GroupDropRec* d = vs.host(v.drops);
+      n_draw = group_drop_records_packed(g, d, batch_rows);
+      for (int j = 0; j < n_draw; ++j) d[j].step0 += (unsigned long long)u;
+    }
+  }
+  // (a synchronous call: the previous one's upload has been read long ago)
+  HIPCHK(g->vec.upload(U > 0 ? g->vec_end[U - 1] : g->vec_head, st));
+  // nothing below returns before the launches are queued: only now do the members' counters move — the noise and the
+  // inference keep-bit position of every requesting member by one call, and the staged rows of a solo continuation go
+  for (int i = 0; i < K; ++i) {
+    iqlhip_ctx* c = g->m[i];
+    if (U > 0) c->cont.valid = false;      // (as after any group step: a later solo call gathers its own rows)
+    if (!n_act(i)) continue;
+    if (with_drops && adrops[i].active) c->act_drop_calls += 1;
+    if (act_seed[i] != 0 && gauss) c->act_calls += 1;
+  }
+  const int gather_nb = (int)(((long long)max_work * (ld / 4) + 255) / 256);      // (the largest member's: a record bounds its own)
+  if (act_draws)
+    hipLaunchKernelGGL(iql_online_vec_gather_drop_group_kernel, dim3(gather_nb + (2 * max_act * 8 + 255) / 256, K), dim3(256), 0, st,
+                       vs.device(g->vec_gathers), vs.device(g->vec_adrops));
+  else
+    hipLaunchKernelGGL(iql_online_vec_gather_group_kernel, dim3(gather_nb, K), dim3(256), 0, st, vs.device(g->vec_gathers));
+  for (int i = 0; i < K; ++i)
+    if (U > 0 || n_act(i)) refresh_shadows(g->m[i], st);
+  for (int u = 0; u < U; ++u) {
+    const iqlhip_group::VecStep& v = g->vec_steps[u];
+    group_launch_dropmask(g, vs.device(v.drops), n_draw, q.max_rows, st);      // (every drawing member's position moves by one)
+    group_launch_step(g, vs.device(v.recs), q, 0, st, aux[u]);
+  }
+  const unsigned long long done_val = ++g->done_seq;
+  if (n_req > 0) {
+    // (bf16: the last update has rewritten the shadows from the new masters — the conversion refresh_shadows makes)
+    const int nbx = (max_act + RT_ROWS - 1) / RT_ROWS * NSPLIT;
+    group_launch_act_fwd(c0, vs.device(g->vec_aps), nbx, n_req, fwd_lds(c0, nbx * n_req), st);
+    hipLaunchKernelGGL(iql_actor_finish_rows_group_kernel, dim3((max_act * A + 255) / 256, n_req), dim3(256), 0, st,
+                       vs.device(g->vec_fins));
+  }
+  // (the rows finish stores no completion word: the one-block launch behind it does)
+  if (U > 0 || n_req > 0) hipLaunchKernelGGL(iql_group_done_kernel, dim3(1), dim3(64), 0, st, g->done_pin, done_val);
+  HIPCHK(hipGetLastError());
+  g->last_n = U;
+  if (U > 0 || n_req > 0) {
+    if ((rc = wait_word(g->done_pin, done_val, st))) return rc;
+  } else {
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  for (int i = 0; i < K; ++i) {
+    for (int u = 0; u < U; ++u)
+      for (int j = 0; j < 3; ++j)
+        out[((size_t)i * U + u) * 3 + j] = g->vec_loss_pin[((size_t)i * IQLHIP_VEC_MAX_UPDATES + u) * 4 + j];
+    if (n_act(i)) memcpy(act_out_host + act0[i] * A, act_out_pin(i), (size_t)n_act(i) * A * sizeof(float));
+  }
   return IQLHIP_OK;
 }

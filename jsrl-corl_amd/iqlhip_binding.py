@@ -244,6 +244,10 @@ SYMBOLS = [
                                                  C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                                  C.POINTER(StepScalars), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("iqlhip_group_online_step_vec", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
+                                               C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("iqlhip_group_read_losses", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
     ("iqlhip_group_online_step", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int32,

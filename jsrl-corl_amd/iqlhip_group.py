@@ -15,6 +15,12 @@ iteration (ImplicitQLearning.online_step for each member, in member order; one r
 
     logs, actions = group.online_step(buffers, states, actions, rewards, next_states, dones, 256, act_next=next_states)
 
+Vector environments and an update-to-data ratio (ImplicitQLearning.online_step_vec for each member, in member order):
+member k stores E_k transitions, takes U steps and acts on E2_k states, again in one call; updates=0 is the warm-up:
+
+    logs, actions = group.online_step_vec(buffers, states, actions, rewards, next_states, dones, 256, updates=4,
+                                          act_next=next_states)
+
 Policy inference of all members is one call too (actor.act / ImplicitQLearning.actor_forward for each, in member
 order): `group.act(states)` for one state per member (lockstep evaluation: iqlhip_hostutil.eval_actors),
 `group.actor_forward(states)` for batches.
@@ -80,7 +86,7 @@ over seeds or over alpha / eps / is_beta stays in the group, every member's tabl
 
 Not supported (NotImplementedError): data parallelism, bf16 batches of more than 512 rows.  Groups
 capture no graphs, and their members train on the same iterations (a loop's warm-up before `batch_size` transitions
-runs add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
+is online_step_vec(updates=0), or add_transition per member).  A group of one runs the solo entry points themselves (the same results; the solo
 driver is faster for one agent).
 """
 from __future__ import annotations
@@ -92,8 +98,8 @@ import numpy as np
 import torch
 
 import iqlhip_binding as hb
-from iqlhip_replay import check_online_ring, draw_indices, pack_transition
-from iqlhip_trainer import K_MAX, ImplicitQLearning
+from iqlhip_replay import check_online_ring, check_transitions, draw_indices, pack_transition, pack_transitions
+from iqlhip_trainer import K_MAX, VEC_MAX_BATCH, ImplicitQLearning
 
 BF16_MAX_ROWS = 512      # bf16 batches beyond this run the large-batch kernels, which have no group form
 
@@ -687,6 +693,152 @@ class ImplicitQLearningGroup:
             return hb.lib().iqlhip_group_online_step(g, *ring_args, rows, idx, Bs[0], scs, out, *act_args, stream)
         return self._run_online(bufs, (states, actions, rewards, next_states, dones), Bs, act_next, rngs,
                                 lambda k, new_size, rng: (draw_indices(new_size, Bs[k], rng),), call)
+
+    # ------------------------------------------------------------------ the online loop over vector environments
+    def _run_online_vec(self, rings, blocks, Bs, U: int, acts, rngs, peeks):
+        """_run_online's sibling for E_k transitions per member and U steps in the one library call
+        (iqlhip_group_online_step_vec), once every check has passed.  blocks[k]: member k's (states, actions, rewards,
+        next_states, dones) of E_k rows; acts[k]: its [E2_k, S] float32 act states or None; peeks[k]: its
+        _peek_schedule(U) (None for U <= 1 without a schedule to look ahead in).  The members' rows, indices and act
+        states go to the library one member after another.  The indices are drawn per member in member order: U
+        consecutive sample() draws over the member's size after all its E_k inserts, from rngs[k] (None: the global
+        np.random).  The scalars are what U single steps of the member would use (ImplicitQLearning._run_online_vec).
+        Only when the status is OK does anything move: every ring by E_k, every member by U steps.  Returns one list of
+        U dicts per member, or (lists, actions) when the call took act_next."""
+        K, ld = len(self.trainers), rings[0]._ld
+        t0 = self.trainers[0]
+        S, A = t0._S, t0._A
+        Es = [len(b[0]) for b in blocks]
+        rows = np.zeros((sum(Es), ld), dtype=np.float32)
+        lo = 0
+        for k, b in enumerate(blocks):
+            pack_transitions(rows[lo: lo + Es[k]], S, A, *b)
+            lo += Es[k]
+        slots = [b._insert_slot(E) for b, E in zip(rings, Es)]
+        idx = None
+        if U:
+            idx = np.ascontiguousarray(np.concatenate(
+                [draw_indices(slots[k][1], Bs[k], None if rngs is None else rngs[k]) for k in range(K) for _ in range(U)]),
+                dtype=np.int64)
+        scs = (hb.StepScalars * max(K * U, 1))()
+        for k, t in enumerate(self.trainers):
+            lrs = t._current_lrs()
+            lr_pi = [lrs["pi"]] if peeks[k] is None else peeks[k][0]      # (one step: the rate in force, whatever the schedule's state)
+            for u in range(U):
+                t._fill_scalars(scs[k * U + u], {g: n + u + 1 for g, n in t._adam_t.items()}, dict(lrs, pi=float(lr_pi[u])),
+                                1.0 / Bs[k])
+        out = (C.c_float * max(3 * K * U, 1))()
+        want = [k for k in range(K) if acts is not None and acts[k] is not None]
+        a_in = a_rows = max_a = seeds = a_out = None
+        if want:
+            a_rows = np.array([acts[k].shape[0] if k in want else 0 for k in range(K)], dtype=np.int32)
+            a_in = np.ascontiguousarray(np.concatenate([acts[k].reshape(-1) for k in want]), dtype=np.float32)
+            a_out = np.zeros((int(a_rows.sum()), A), dtype=np.float32)
+            max_a = np.array([float(t.actor.max_action) for t in self.trainers], dtype=np.float32)
+            seeds = np.array([t._act_seed() if (k in want and t.actor.training and t._gaussian) else 0
+                              for k, t in enumerate(self.trainers)], dtype=np.uint64)
+        hb.check(hb.lib().iqlhip_group_online_step_vec(
+            self._group(), (C.c_void_p * K)(*[b._rows.data_ptr() for b in rings]), ld,
+            (C.c_int64 * K)(*[b._buffer_size for b in rings]), (C.c_int64 * K)(*[p for p, _ in slots]), rows.ctypes.data,
+            (C.c_int32 * K)(*Es), _addr(idx), (C.c_int32 * K)(*Bs), U, C.addressof(scs), C.addressof(out), _addr(a_in),
+            _addr(a_rows), _addr(max_a), _addr(seeds), _addr(a_out), t0._stream()))
+        for t, ring, (pointer, new_size), E in zip(self.trainers, rings, slots, Es):
+            t._commit_online(ring, pointer, new_size, E, U, {g: n + U for g, n in t._adam_t.items()})
+            if U:
+                t._ts_token = None
+                t._eager_next = None
+        stats = self._group_stats(U) if U else None
+        logs = []
+        for k, t in enumerate(self.trainers):
+            logs.append([{"value_loss": float(out[3 * (k * U + u)]), "q_loss": float(out[3 * (k * U + u) + 1]),
+                          "actor_loss": float(out[3 * (k * U + u) + 2])} for u in range(U)])
+            if t._step_stats and U:
+                for u, log in enumerate(logs[-1]):
+                    log.update({"stats/" + name: float(stats[u, k, i]) for i, name in enumerate(hb.STAT_NAMES)})
+        if acts is None:
+            return logs
+        actions, lo = [None] * K, 0
+        for k in want:
+            actions[k] = a_out[lo: lo + int(a_rows[k])].copy()
+            lo += int(a_rows[k])
+        return logs, actions
+
+    def online_step_vec(self, buffers, states, actions, rewards, next_states, dones, batch_size, updates: int = 1,
+                        act_next: Optional[Sequence] = None, rngs: Optional[Sequence[np.random.RandomState]] = None):
+        """One iteration of an online loop over vector environments, with an update-to-data ratio of `updates`, for every
+        member in ONE library call, one upload and one synchronisation (ImplicitQLearning.online_step_vec for each, in
+        member order; DESIGN.md 6b "Group vector-environment online step"): member k stores its E_k transitions
+        (states[k] [E_k, S], actions[k] [E_k, A], rewards[k] / dones[k] [E_k], next_states[k] [E_k, S]) in buffers[k],
+        makes `updates` consecutive sample() draws of batch_size rows over its size after all E_k inserts — from rngs[k]
+        (a np.random.RandomState), or from the global np.random in member order when rngs is None — takes `updates` steps
+        on them, and acts on act_next[k] ([E2_k, S], or None) with its UPDATED policy.  1 <= E_k <= min(capacity_k, 64)
+        and E2_k in [1, 64] may differ between members; 0 <= updates <= 32 is common to the call (the members' steps run
+        in lockstep); batch_size: an int, or one int per member (unequal sizes: mixed_batch groups only), each <= 512.
+        updates = 0 is the loop's warm-up: rows in, actions out, an empty list per member, no step counter moves.
+        Afterwards member k — ring and counters, parameters, Adam state, schedule, total_it, noise and keep-bit counters,
+        per-step logs and statistics, clip record, actions — is bit for bit where its solo online_step_vec leaves it.
+        Returns one list of `updates` train()-style dicts per member; with act_next, (lists, actions) where actions[k]
+        is [E2_k, A] float32, or None for a member that asked for none.  The refusals are online_step's and the solo
+        online_step_vec's, each naming the member, all before anything is launched, drawn or moved."""
+        K = len(self.trainers)
+        what = "online_step_vec"
+        self._online_lists(what, act_next, rngs, buffers=buffers, states=states, actions=actions, rewards=rewards,
+                           next_states=next_states, dones=dones)
+        bufs = list(buffers)
+        Bs = self._batch_sizes(K, batch_size, self._mixed_batch)
+        U = int(updates)
+        self._check_members()
+        for B in Bs:
+            self._check_batch_size(B)
+        if not 0 <= U <= hb.IQLHIP_VEC_MAX_UPDATES:
+            raise ValueError(f"iqlhip: updates = {U} outside [0, {hb.IQLHIP_VEC_MAX_UPDATES}]")
+        if any(B > VEC_MAX_BATCH for B in Bs):
+            raise ValueError(f"iqlhip: batch sizes {Bs} outside [1, {VEC_MAX_BATCH}]")
+        acts = None if act_next is None else [None] * K
+        for i, (t, buf) in enumerate(zip(self.trainers, bufs)):
+            check_online_ring(buf, t._dev, what, member=i)
+            if buf._weights_tracks:
+                raise NotImplementedError(f"iqlhip: {what} has no insert for a tracking sample-weight table (member {i}); use "
+                                          "add_transitions and the prioritised calls")
+            try:
+                check_transitions(t._S, t._A, buf._buffer_size, states[i], actions[i], rewards[i], next_states[i], dones[i])
+            except ValueError as e:
+                raise ValueError(f"{e} (member {i})") from None
+            if act_next is not None and act_next[i] is not None:
+                a = np.asarray(act_next[i], dtype=np.float32)
+                if a.ndim != 2 or a.shape[1] != t._S or not 1 <= a.shape[0] <= hb.IQLHIP_VEC_MAX_ENVS:
+                    raise ValueError(f"iqlhip: act_next must be [E2, {t._S}] with 1 <= E2 <= {hb.IQLHIP_VEC_MAX_ENVS}, got "
+                                     f"{list(a.shape)} (member {i})")
+                acts[i] = np.ascontiguousarray(a)
+        if act_next is not None:         # (before any ring, counter or parameter moves)
+            self._check_eval_forward([k for k in range(K) if acts[k] is not None], f"{what}(act_next=...)")
+        if K == 1 and rngs is None:      # a group of one IS the solo call
+            return self._solo_online_result(
+                self.trainers[0].online_step_vec(bufs[0], states[0], actions[0], rewards[0], next_states[0], dones[0], Bs[0],
+                                                 updates=U, act_next=None if act_next is None else act_next[0]), act_next)
+        peeks = []
+        for i, (t, buf) in enumerate(zip(self.trainers, bufs)):      # (every member's refusals, then every member's settings)
+            # (injected masks are pending unless the member's _prepare is about to send another dropout rate, which clears them)
+            p_eff = t._actor_dropout_p() if t.actor.training else 0.0
+            if getattr(t, "_masks_injected", False) and p_eff == getattr(t, "_dropout_sent", p_eff):
+                raise NotImplementedError(f"iqlhip: {what} draws every step's keep-bits and cannot use the masks written by "
+                                          f"inject_dropout_masks (member {i}); step with train(), or clear them "
+                                          "(set_dropout_seed)")
+            if any(buf is b or buf._rows.data_ptr() == b._rows.data_ptr() for b in bufs[:i]):
+                raise ValueError(f"iqlhip: member {i} shares a replay buffer with an earlier member (one buffer each)")
+            pk = t._peek_schedule(U) if U else None
+            if U > 1 and pk is None:
+                raise NotImplementedError(f"iqlhip: {what} with updates > 1 needs an actor schedule whose rates can be looked "
+                                          f"up ahead (CosineAnnealingLR with eta_min = 0, stepped by its trainer; member {i})")
+            peeks.append(pk)
+            t._check_step_stats(Bs[i])       # (what _prepare refuses, in front of any member's _prepare)
+            t._check_grad_clip(Bs[i])
+        if any(b._ld != bufs[0]._ld for b in bufs):
+            raise ValueError("iqlhip: the members' buffers have different row strides")
+        for t, B in zip(self.trainers, Bs):
+            t._prepare(B)
+        blocks = [(states[k], actions[k], rewards[k], next_states[k], dones[k]) for k in range(K)]
+        return self._run_online_vec(bufs, blocks, Bs, U, acts, rngs, peeks)
 
     # ------------------------------------------------------------------ batches mixed from an offline and an online buffer
     def _replay_mix_args(self, offline_buffers, online_buffers, batch_size, mixing_ratio, burst: bool):
